@@ -15,7 +15,13 @@ buffers, the way a stream of batches is served: iteration counts differ 10x
 between QPs, so the tail of one batch (a few slow QPs) overlaps the bulk of the
 next.  Rank 0 prints ONE JSON line.
 
-Besides the contract's keys the line carries, measured in the same run at N = 1:
+A plain run measures the headline alone (set-up, warm-up, the timed steps, the
+line).  --dump-outputs DIR then writes what the last timed step computed as
+DIR/<name>.npy (float64; solutions of a fixed, seeded sample of 2048 QPs, the
+SolverOut fields of every QP), so that two builds can be compared output for
+output on the same inputs.
+
+With --full the line also carries, measured in the same run at N = 1:
   serial          the same steps one at a time (--pipeline 1): latency of a batch
   ltv_dense_rows  the same shape with per-stage-distinct matrices and dense
                   constraint rows (no matrix copy shared between stages, no
@@ -31,6 +37,7 @@ Besides the contract's keys the line carries, measured in the same run at N = 1:
   wide            the row-pair record instances (stage widths 17..32), one launch at a time: 2048 random
                   time-varying QPs of (30, 20, 6, 16) on <24,8,16>, the reference's reactor N = 80 on <18,5,10>
   cpu_baseline    the oracle on the host cores (bounded sample)
+and at N > 1 the receding sweep sharded over the ranks.
 """
 import argparse
 import json
@@ -220,6 +227,25 @@ def memory_plan(world, lanes, batch, sizes, data_bytes_per_qp, scratch_bytes_per
                 total=batch * data_bytes_per_qp + lanes * per_lane + recv, record_bytes=rec)
 
 
+DUMP_SAMPLE_QPS = 2048          # solutions of 2048 QPs: 2048 x 2108 doubles = 34.5 MB, under the 64 MB of a dump
+DUMP_ALL_OUT_QPS = 1 << 18      # SolverOut fields of every QP up to 2^18 QPs (5 doubles each: 10.5 MB)
+
+
+def step_outputs(torch, x, out, nz, nl, nv):
+    """What a caller of the timed path receives from one step, as float64 arrays for --dump-outputs: z, l, v, y
+    (x = the rows [z l v y] on the device) of a fixed, seeded sample of the batch, and the SolverOut fields
+    (`out`, numpy structured) of every QP - of the same sample for batches over DUMP_ALL_OUT_QPS.  solve_time is
+    left out: it is a clock reading, not a result."""
+    n = x.shape[0]
+    ids = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_SAMPLE_QPS), replace=False))
+    rows = x.index_select(0, torch.from_numpy(ids).to(x.device)).cpu().numpy()
+    res = {"z": rows[:, :nz], "l": rows[:, nz:nz + nl], "v": rows[:, nz + nl:nz + nl + nv], "y": rows[:, nz + nl + nv:]}
+    sel = slice(None) if n <= DUMP_ALL_OUT_QPS else ids
+    for f in ("eflag", "newton_iters", "prox_iters", "residual", "initial_residual"):
+        res[f] = out[f][sel]
+    return {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in res.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -231,10 +257,15 @@ def main():
     ap.add_argument("--first-id", type=int, default=None,
                     help="developer option: first global instance id of this rank's shard "
                          "(default: rank * batch, the shard bench runs under torch.distributed.run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary blocks and the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="QPs for the CPU baseline (0 disables; default sized for ~15 s)")
+                    help="QPs for the CPU baseline (0 disables; default: sized for ~15 s with --full, else 0)")
     ap.add_argument("--extras", type=int, default=-1,
-                    help="secondary blocks (serial, ltv_dense_rows, dense, receding): 1/0; default on at N = 1")
+                    help="secondary blocks (serial, ltv_dense_rows, dense, receding, latency, wide; at N > 1 the "
+                         "sharded receding sweep): 1/0; default on with --full")
     args = ap.parse_args()
 
     import torch
@@ -280,8 +311,9 @@ def main():
             self.out, self.grec = b["out"], b["grec"]
             self.events = []
 
-    def run_mpc(p, data, P, steps, warmup, gather):
-        """`steps` timed solves of the batch `p`, P in flight.  Returns a dict."""
+    def run_mpc(p, data, P, steps, warmup, gather, keep_last=False):
+        """`steps` timed solves of the batch `p`, P in flight.  Returns a dict; with `keep_last`, on rank 0
+        `last` holds what the last timed step returned (every rank's block when gathered)."""
         lanes = [Lane(p, gather, P) for _ in range(P)]
 
         def step(k, timed):
@@ -335,6 +367,13 @@ def main():
                    not_converged=int((eflag != 0).sum()), mean_newton=float(newton.mean()),
                    query=lanes[0].solver.query(), kernel=lanes[0].solver.kernel_name(), wall=(w0, w1),
                    untimed=max(warmup, min(P, steps)))
+        if keep_last and rank == 0 and steps > 0:
+            ln = lanes[(steps - 1) % P]
+            if gather:
+                recs = torch.cat(ln.grec)
+                res["last"] = step_outputs(torch, recs[:, :ln.x.shape[1]], sharding.unpack_out(recs), p.nz, p.nl, p.nv)
+            else:
+                res["last"] = step_outputs(torch, ln.x, hip_api.out_to_numpy(ln.out), p.nz, p.nl, p.nv)
         for ln in lanes:
             ln.solver.close()
         del lanes
@@ -344,11 +383,16 @@ def main():
     P = max(1, args.pipeline)
     p = fx.synthetic_mpc_batch(B, first_id=first_id)  # shard by global instance id
     data = upload(p)
-    head = run_mpc(p, data, P, args.steps, args.warmup, dist is not None)
+    head = run_mpc(p, data, P, args.steps, args.warmup, dist is not None, keep_last=args.dump_outputs is not None)
+    if "last" in head:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in head.pop("last").items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
-    extras = args.extras if args.extras >= 0 else (1 if world == 1 else 0)
+    # the secondary blocks: on rank 0 at N = 1 (--extras 1: at any N), and at N > 1 the sharded receding sweep
+    extras = args.extras if args.extras >= 0 else int(args.full)
     blocks = {}
-    if extras and rank == 0:
+    if extras and rank == 0 and (world == 1 or args.extras == 1):
         ser = run_mpc(p, data, 1, min(args.steps, 6), 1, False)
         blocks["serial"] = {"value": B * min(args.steps, 6) / ser["elapsed"], "unit": "QPs/sec",
                             "ms_per_step": 1e3 * ser["elapsed"] / min(args.steps, 6), "kernel_ms": ser["kernel_ms"],
@@ -372,7 +416,7 @@ def main():
         blocks["receding"] = bench_receding(torch, dev, fx, hip_api)
         blocks["latency"] = bench_latency(torch, dev, fx, hip_api)
         blocks["wide"] = bench_wide(torch, dev, fx, hip_api)
-    if dist is not None and args.extras != 0 and (world > 1 or os.environ.get("FBSTAB_BENCH_SHARDED_SWEEP") == "1"):
+    if dist is not None and extras and (world > 1 or os.environ.get("FBSTAB_BENCH_SHARDED_SWEEP") == "1"):
         # N > 1: configs[4] sharded by trajectory (every rank takes part: one gather at
         # the end).  (The environment variable rehearses this branch with one rank.)
         data = None
@@ -459,7 +503,7 @@ def main():
         rec.update(blocks)
         n_cpu = args.cpu_sample
         if n_cpu < 0:
-            n_cpu = 256 * max(1, (os.cpu_count() or 1))
+            n_cpu = 256 * max(1, (os.cpu_count() or 1)) if args.full else 0
         if n_cpu > 0 and world == 1:
             rec["cpu_baseline"] = cpu_baseline(n_cpu)
             if "latency" in rec:

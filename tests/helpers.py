@@ -204,3 +204,28 @@ def display_texts_agree(a, b, rtol=5e-4, atol=1e-7):
         if err > atol + rtol * abs(fy) and not (abs(fy) < 1e4 * atol and err <= 0.5 * max(abs(fx_), abs(fy))):
             return False, "%r vs %r" % (x, y)
     return True, ""
+
+
+LOOP_FIELDS = ("eflag", "newton_iters", "prox_iters", "residual", "initial_residual")
+
+
+def reference_loop_cases(kats):
+    """The problems the restated loop is pinned on against the reference's own FBstabAlgorithm<> loop:
+    (kind, problem, options).  tests/golden/reference_loop.npz holds what the reference loop returned for
+    them (tests/golden/make_loop_golden.py)."""
+    from oracle.oracle_py import default_options, reliable_options
+    cases = []
+    for k in kats["dense_end_to_end"]:
+        cases.append(("dense", dense_from_kat(k), default_options(abs_tol=1e-8)))
+    for k in kats["mpc_end_to_end"][:4]:
+        cases.append(("mpc", mpc_from_kat(k), default_options(abs_tol=1e-8)))
+    cases.append(("mpc", fx.synthetic_mpc_batch(6), default_options()))
+    cases.append(("mpc", fx.synthetic_mpc_batch(3, first_id=11), reliable_options(display_level=0)))
+    cases.append(("dense", fx.synthetic_dense_batch(6, 20, 5, 40), default_options()))
+    cases.append(("dense", fx.synthetic_dense_batch(3, 50, 10, 100), default_options(max_newton_iters=7)))
+    return cases
+
+
+def solve_case(orc, kind, p, opts):
+    """(z, l, v, y, out) of `orc` on one of reference_loop_cases."""
+    return orc.solve_dense(p, opts=opts) if kind == "dense" else orc.solve_mpc(p, opts=opts)

@@ -1,11 +1,14 @@
 """Pins the CPU oracle against every known-answer vector the reference's own
 tests hold for the hot path, and against the reference's
-own FBstabAlgorithm<> loop (oracle/_ref).  CPU only."""
+own FBstabAlgorithm<> loop (its outputs, stored from oracle/_ref).  CPU only."""
+import os
+
 import numpy as np
 import pytest
 
 from oracle.oracle_py import default_options, reliable_options
 from tests import helpers as H
+from tests.conftest import GOLDEN
 
 
 # -- end-to-end: fbstab/test/fbstab_dense_unit_tests.cc ----------------------
@@ -225,28 +228,19 @@ def test_feasibility_certificates(oracle, kats):
 
 
 # -- the restated loop is the reference's loop ---------------------------------
-def test_restated_loop_equals_reference_template(oracle, ref_oracle, kats):
-    """oracle/_ref drives the same components with the reference's own
-    fbstab_algorithm.h; outputs must be identical (bitwise)."""
-    from tools import fixtures as fx
-    cases = []
-    for k in kats["dense_end_to_end"]:
-        cases.append(("dense", H.dense_from_kat(k), default_options(abs_tol=1e-8)))
-    for k in kats["mpc_end_to_end"][:4]:
-        cases.append(("mpc", H.mpc_from_kat(k), default_options(abs_tol=1e-8)))
-    cases.append(("mpc", fx.synthetic_mpc_batch(6), default_options()))
-    cases.append(("mpc", fx.synthetic_mpc_batch(3, first_id=11), reliable_options(display_level=0)))
-    cases.append(("dense", fx.synthetic_dense_batch(6, 20, 5, 40), default_options()))
-    cases.append(("dense", fx.synthetic_dense_batch(3, 50, 10, 100), default_options(max_newton_iters=7)))
-    for kind, p, o in cases:
-        fn = (lambda orc: orc.solve_dense(p, opts=o)) if kind == "dense" else (
-            lambda orc: orc.solve_mpc(p, opts=o))
-        a = fn(oracle)
-        b = fn(ref_oracle)
-        for i in range(4):
-            assert np.array_equal(a[i], b[i])
-        for fld in ("eflag", "newton_iters", "prox_iters", "residual", "initial_residual"):
-            assert np.array_equal(a[4][fld], b[4][fld]), fld
+def test_restated_loop_equals_reference_template(oracle, kats):
+    """oracle/_ref drove the same components with the reference's own
+    fbstab_algorithm.h and stored its outputs in tests/golden/reference_loop.npz
+    (make_loop_golden.py); the restated loop's must be identical (bitwise)."""
+    g = np.load(os.path.join(GOLDEN, "reference_loop.npz"))
+    cases = H.reference_loop_cases(kats)
+    assert len(g.files) == len(cases) * (4 + len(H.LOOP_FIELDS))
+    for i, (kind, p, o) in enumerate(cases):
+        a = H.solve_case(oracle, kind, p, o)
+        for j, n in enumerate("zlvy"):
+            assert np.array_equal(a[j], g["%d_%s" % (i, n)]), (i, n)
+        for fld in H.LOOP_FIELDS:
+            assert np.array_equal(a[4][fld], g["%d_%s" % (i, fld)]), (i, fld)
 
 
 def test_options_validate_and_profiles(oracle):

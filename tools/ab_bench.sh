@@ -5,7 +5,7 @@ O=gpurun_out/$1; shift; mkdir -p $O
 for rep in 1 2; do
   for L in "$@"; do
     N=$(basename $L .so)
-    FBSTAB_HIP_LIB=$PWD/$L timeout 600 python bench.py --cpu-sample 0 > $O/bench_${N}_$rep.json 2>> $O/bench.err
+    FBSTAB_HIP_LIB=$PWD/$L timeout 600 python bench.py --full --cpu-sample 0 > $O/bench_${N}_$rep.json 2>> $O/bench.err
     python3 - <<PY
 import json
 d=json.loads(open("$O/bench_${N}_$rep.json").read().strip().splitlines()[-1])

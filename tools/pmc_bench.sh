@@ -13,7 +13,7 @@ for set in \
  "TCP_TOTAL_CACHE_ACCESSES TCP_TCC_READ_REQ TCP_TCC_WRITE_REQ TCC_HIT TCC_MISS TCC_REQ" \
  "TCC_EA0_RDREQ TCC_EA0_WRREQ TCC_EA0_RDREQ_32B TCC_EA0_WRREQ_64B" ; do
   i=$((i+1))
-  timeout 300 rocprofv3 --pmc $set --kernel-trace -d $OUT/p$i -o p -- python3 $R/bench.py --cpu-sample 0 --steps 16 > $OUT/p$i.log 2>&1
+  timeout 300 rocprofv3 --pmc $set --kernel-trace -d $OUT/p$i -o p -- python3 $R/bench.py --full --cpu-sample 0 --steps 16 > $OUT/p$i.log 2>&1
   echo "pass $i rc=$? $set"
 done
 cd $R
