@@ -665,6 +665,9 @@ int fbstab_hip_mpc_create_in_flight(int N, int nx, int nu, int nc, int max_batch
     const int need = s->rec ? max_batch : (max_batch + s->qps_per_wg - 1) / s->qps_per_wg;
     if (s->workgroups > need) s->workgroups = need;
   }
+  // test knob: FBSTAB_HIP_MAX_WORKGROUPS=n caps the grid, so that small batches pack every row and re-fetch
+  const char* cap = getenv("FBSTAB_HIP_MAX_WORKGROUPS");
+  if (cap && atoi(cap) > 0 && s->workgroups > atoi(cap)) s->workgroups = atoi(cap);
   const long long ws_doubles = s->rec ? s->rec->ws_doubles(N) : (long long)s->lay.ws_doubles;
   s->scratch_bytes = ws_doubles * sizeof(double) * s->workgroups * s->qps_per_wg;
   e = hipMalloc(&s->scratch, (size_t)s->scratch_bytes);
@@ -1141,6 +1144,9 @@ int fbstab_hip_dense_create(int nz, int nl, int nv, int max_batch, int device,
   if (env && atoi(env) > 0) per_cu = atoi(env);
   s->workgroups = prop.multiProcessorCount * per_cu;
   if (s->workgroups > max_batch) s->workgroups = max_batch;
+  // test knob: FBSTAB_HIP_MAX_WORKGROUPS=n caps the grid, so that one workgroup solves several QPs in turn
+  const char* cap = getenv("FBSTAB_HIP_MAX_WORKGROUPS");
+  if (cap && atoi(cap) > 0 && s->workgroups > atoi(cap)) s->workgroups = atoi(cap);
   s->scratch_bytes = 0;
   if (s->wave)  // A' and the multipliers of every resident workgroup (fb_dense_wave.h)
     s->scratch_bytes = (long long)sizeof(double) * s->wlay.ws_doubles * s->workgroups;

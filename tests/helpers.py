@@ -35,6 +35,82 @@ def mpc_component_fixture(c):
     return p
 
 
+# -- the parity bar of the GPU tests (test_gpu_parity.py, test_gpu_queue.py) ------------------
+def _opts(hip, o):
+    """oracle Options -> hip_api Options (same POD)."""
+    h = hip.Options()
+    for name, _ in h._fields_:
+        setattr(h, name, getattr(o, name))
+    return h
+
+
+def _unique_duals(dense, vc, act_tol=1e-7):
+    """Dense QPs of the batch whose multipliers are pinned by the KKT conditions: the
+    gradients of the equalities and of the active inequalities (oracle's v > 0) are
+    linearly independent.  Elsewhere (l, v) is any point of a face - FBstab returns the
+    one its proximal path runs into, which depends on the rounding of every Newton solve
+    in the directions where K's eigenvalues are of the size of sigma (cond(K) ~ 1e16):
+    the one-wavefront kernel in its opt-in NATURAL / AUTO elimination orders
+    (fbstab_hip_dense_set_factorisation) and the oracle, which pivots like Eigen, then
+    agree in z, y and G'l + A'v but not in l and v.  (The default order is Eigen's and is
+    compared entry by entry.)"""
+    nz, nl, nv = dense.nz, dense.nl, dense.nv
+    B = vc.shape[0]
+    uniq = np.zeros(B, dtype=bool)
+    for i in range(B):
+        A = dense.arrays["A"][i].reshape(nz, nv).T
+        rows = [A[vc[i] > act_tol]]
+        if nl:
+            rows.append(dense.arrays["G"][i].reshape(nz, nl).T)
+        M = np.vstack(rows)
+        uniq[i] = M.shape[0] == 0 or np.linalg.matrix_rank(M, tol=1e-8) == M.shape[0]
+    return uniq
+
+
+def _assert_parity(gpu, cpu, abs_tol, exact_frac=1.0, max_dn=0, dense=None):
+    """The parity bar.  STRICT by default: exit flag, proximal and Newton count of
+    EVERY instance equal to the oracle's.  Only the opt-in dense elimination orders (NATURAL / AUTO: a
+    different pivot order than Eigen's, by the caller's choice) pass a looser `exact_frac` / `max_dn`."""
+    zg, lg, vg, yg, og = gpu
+    zc, lc, vc, yc, oc = cpu
+    assert np.array_equal(og["eflag"], oc["eflag"])
+    assert np.array_equal(og["prox_iters"], oc["prox_iters"])
+    dn = np.abs(og["newton_iters"].astype(int) - oc["newton_iters"].astype(int))
+    assert dn.max() <= max_dn, (dn.max(), np.nonzero(dn)[0][:10])
+    assert (dn == 0).mean() >= exact_frac, ((dn != 0).sum(), np.nonzero(dn)[0][:10])
+    if max_dn == 0:
+        assert int(og["newton_iters"].sum()) == int(oc["newton_iters"].sum())
+    pinned = np.ones(zc.shape[0], dtype=bool)
+    if dense is not None:
+        # multipliers: entry by entry where they are unique, through G'l + A'v everywhere
+        pinned = _unique_duals(dense, vc)
+        nz, nl, nv = dense.nz, dense.nl, dense.nv
+        A = dense.arrays["A"].reshape(-1, nz, nv)   # A[b, k, i] = A_b[i][k]
+        img = lambda l, v: (np.einsum("bki,bi->bk", A, v) +
+                            (np.einsum("bkq,bq->bk", dense.arrays["G"].reshape(-1, nz, nl), l) if nl else 0.0))
+        ig, ic = img(lg, vg), img(lc, vc)
+        scale = 1.0 + np.abs(ic).max(axis=1, keepdims=True)
+        assert (np.abs(ig - ic) <= 10 * abs_tol * scale).all(), np.abs(ig - ic).max()
+    for g, c, sel in ((zg, zc, None), (lg, lc, pinned), (vg, vc, pinned), (yg, yc, None)):
+        if c.size:
+            scale = 1.0 + np.abs(c).max(axis=1, keepdims=True)
+            close = np.abs(g - c) <= 10 * abs_tol * scale
+            if sel is not None:
+                close = close[sel]
+            assert close.all(), np.abs(g - c).max()
+    ok = oc["eflag"] == 0
+    np.testing.assert_allclose(og["initial_residual"], oc["initial_residual"], rtol=1e-10)
+    # residuals agree where they are well above the rounding floor of a
+    # cancellation-dominated quantity (terms are O(1..100), eps*100 ~ 1e-14,
+    # amplified by the Newton step's conditioning, cond(K) up to 1e11: a few 1e-8)
+    big = ok & (oc["residual"] > 1e-7)
+    # (a different elimination order - `dense` - rounds the last step differently:
+    # a tenth of the tolerance the solve stops at)
+    if big.any():
+        np.testing.assert_allclose(og["residual"][big], oc["residual"][big], rtol=2e-2,
+                                   atol=3e-8 if dense is None else max(3e-8, 0.1 * abs_tol))
+
+
 # Variant builds of the product sources the tests load beside the product library (`with
 # hip_api.library(VARIANT_LIBS[name])`); built by `make -C fbstab_amd/csrc <name>` into tests/_build/:
 #   "pattern"  every automatic variable initialised to a bit pattern (-ftrivial-auto-var-init=pattern)

@@ -333,24 +333,30 @@ def test_the_one_count_the_references_rounding_decides(hip, oracle, oracle_fma):
     assert np.abs(z - c[0]).max() <= 3e-7 * (1.0 + np.abs(c[0]).max())
 
 
-def _solve_on(hipmod, which, p, o, shape):
+def _solve_on(hipmod, which, p, o, shape, monkeypatch=None, cap=None):
     """One batch through the C-ABI of the product library (which = None) or of a variant
-    build (hip_api.library), host pointers."""
+    build (hip_api.library), host pointers; ``cap``: FBSTAB_HIP_MAX_WORKGROUPS at the handle's
+    creation.  Returns (kernel, z, l, v, y, out, workgroups)."""
     import contextlib
     N, nx, nu, nc = shape
     B = p.batch
+    if cap is not None:
+        monkeypatch.setenv("FBSTAB_HIP_MAX_WORKGROUPS", str(cap))
     with (hipmod.library(H.VARIANT_LIBS[which]) if which else contextlib.nullcontext()):
         s = hipmod.FBstabMpcBatch(N, nx, nu, nc, max_batch=B)
+    if cap is not None:
+        monkeypatch.delenv("FBSTAB_HIP_MAX_WORKGROUPS")
     kern = s.kernel_name()
+    wg = s.query()["workgroups"]
     s.UpdateOptions(_opts(hipmod, o))
     z = np.zeros((B, p.nz)); l = np.zeros((B, p.nl)); v = np.zeros((B, p.nv)); y = np.zeros((B, p.nv))
     out = s.Solve({k: np.ascontiguousarray(a) for k, a in p.arrays.items()}, z, l, v, y)
     s.close()
-    return kern, z, l, v, y, out
+    return kern, z, l, v, y, out, wg
 
 
 @pytest.mark.parametrize("inst", range(5))
-def test_pattern_initialised_build_agrees_bitwise_on_every_record_instance(hip, oracle, inst):
+def test_pattern_initialised_build_agrees_bitwise_on_every_record_instance(hip, oracle, monkeypatch, inst):
     """VERDICT r3 item 5.  The record kernels' cooperative passes read EVERY lane's policy
     object (v_readlane of rec, pack, lpo, N ...), also of rows that hold no QP; a member
     that no code path has set is `undef` in the IR, which the optimiser may resolve
@@ -363,9 +369,11 @@ def test_pattern_initialised_build_agrees_bitwise_on_every_record_instance(hip, 
     broadcast-FMAs (FB_FMAC_GUARD_NOP=1), which the product build drops where
     tools/check_dpp_hazards.py proves them unnecessary: an operand read too early would show
     here as a difference too.  For each of the five record instances: its four fuzz shapes of
-    test_random_shapes_on_every_mpc_instance plus batches of 1, 2, 3, 5 and 7 QPs (rows
-    and whole wavefront halves without a QP) on an exact and a padded shape - outputs of
-    the two builds bitwise equal, and at parity with the oracle."""
+    test_random_shapes_on_every_mpc_instance plus batches of 1, 2, 3, 5 and 7 QPs on an exact
+    and a padded shape - outputs of the two builds bitwise equal, and at parity with the oracle.
+    A handle made for such a batch runs it spread (one QP per wavefront, the other rows idle), so
+    the tiny batches run a second time on ONE workgroup (FBSTAB_HIP_MAX_WORKGROUPS=1): rows and
+    whole wavefront halves without a QP beside busy ones, and rows that fetch again."""
     import os
     if not os.path.exists(H.VARIANT_LIBS["pattern"]):
         pytest.fail("tests/_build/libfbstab_hip_pattern.so is missing: `make -C fbstab_amd/csrc pattern` "
@@ -380,16 +388,20 @@ def test_pattern_initialised_build_agrees_bitwise_on_every_record_instance(hip, 
         if idx % 3 == 2:
             o = default_options(max_linesearch_iters=int(rng.integers(1, 12)),
                                 nonmonotone_linesearch=int(rng.random() < 0.5))
-        cases.append((shape, kern, fx.random_ltv_mpc(rng, B, *shape), o))
-    for j in (0, 1):  # exact and padded shape of the instance, tiny batches
+        cases.append((shape, kern, fx.random_ltv_mpc(rng, B, *shape), o, None))
+    for j in (0, 1):  # exact and padded shape of the instance, tiny batches, spread and on one workgroup
         shape, kern = _MPC_SHAPES[4 * inst + j]
         for B in (1, 2, 3, 5, 7):
             rng = np.random.default_rng(9000 + 100 * inst + 10 * j + B)
-            cases.append((shape, kern, fx.random_ltv_mpc(rng, B, *shape), default_options()))
-    for shape, kern, p, o in cases:
-        a = _solve_on(hip, None, p, o, shape)
-        b = _solve_on(hip, "pattern", p, o, shape)
+            p = fx.random_ltv_mpc(rng, B, *shape)
+            cases.append((shape, kern, p, default_options(), None))
+            cases.append((shape, kern, p, default_options(), 1))
+    for shape, kern, p, o, cap in cases:
+        a = _solve_on(hip, None, p, o, shape, monkeypatch, cap)
+        b = _solve_on(hip, "pattern", p, o, shape, monkeypatch, cap)
         assert a[0] == kern and b[0] == kern, (a[0], b[0], kern)
+        if cap is not None:
+            assert a[6] == b[6] == cap, (a[6], b[6])
         for x, y_ in zip(a[1:5], b[1:5]):
             assert np.array_equal(x, y_), (shape, p.batch)
         for f in ("eflag", "residual", "newton_iters", "prox_iters", "initial_residual"):

@@ -13,6 +13,7 @@ import pytest
 from tools import fixtures as fx
 from oracle.oracle_py import default_options, reliable_options
 from tests import helpers as H
+from tests.helpers import _opts, _unique_duals, _assert_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -23,14 +24,6 @@ def hip():
     hip_api.load_library()
     assert hip_api.load_library().fbstab_hip_device_count() >= 1
     return hip_api
-
-
-def _opts(hip, o):
-    """oracle Options -> hip_api Options (same POD)."""
-    h = hip.Options()
-    for name, _ in h._fields_:
-        setattr(h, name, getattr(o, name))
-    return h
 
 
 def _solve_mpc_host(hip, p, opts, guess=None):
@@ -59,73 +52,6 @@ def _solve_dense_host(hip, p, opts, guess=None, order=None):
     out = s.Solve(data, z, l, v, y)
     s.close()
     return z, l, v, y, out
-
-
-def _unique_duals(dense, vc, act_tol=1e-7):
-    """Dense QPs of the batch whose multipliers are pinned by the KKT conditions: the
-    gradients of the equalities and of the active inequalities (oracle's v > 0) are
-    linearly independent.  Elsewhere (l, v) is any point of a face - FBstab returns the
-    one its proximal path runs into, which depends on the rounding of every Newton solve
-    in the directions where K's eigenvalues are of the size of sigma (cond(K) ~ 1e16):
-    the one-wavefront kernel in its opt-in NATURAL / AUTO elimination orders
-    (fbstab_hip_dense_set_factorisation) and the oracle, which pivots like Eigen, then
-    agree in z, y and G'l + A'v but not in l and v.  (The default order is Eigen's and is
-    compared entry by entry.)"""
-    nz, nl, nv = dense.nz, dense.nl, dense.nv
-    B = vc.shape[0]
-    uniq = np.zeros(B, dtype=bool)
-    for i in range(B):
-        A = dense.arrays["A"][i].reshape(nz, nv).T
-        rows = [A[vc[i] > act_tol]]
-        if nl:
-            rows.append(dense.arrays["G"][i].reshape(nz, nl).T)
-        M = np.vstack(rows)
-        uniq[i] = M.shape[0] == 0 or np.linalg.matrix_rank(M, tol=1e-8) == M.shape[0]
-    return uniq
-
-
-def _assert_parity(gpu, cpu, abs_tol, exact_frac=1.0, max_dn=0, dense=None):
-    """The parity bar.  STRICT by default: exit flag, proximal and Newton count of
-    EVERY instance equal to the oracle's.  Only the opt-in dense elimination orders (NATURAL / AUTO: a
-    different pivot order than Eigen's, by the caller's choice) pass a looser `exact_frac` / `max_dn`."""
-    zg, lg, vg, yg, og = gpu
-    zc, lc, vc, yc, oc = cpu
-    assert np.array_equal(og["eflag"], oc["eflag"])
-    assert np.array_equal(og["prox_iters"], oc["prox_iters"])
-    dn = np.abs(og["newton_iters"].astype(int) - oc["newton_iters"].astype(int))
-    assert dn.max() <= max_dn, (dn.max(), np.nonzero(dn)[0][:10])
-    assert (dn == 0).mean() >= exact_frac, ((dn != 0).sum(), np.nonzero(dn)[0][:10])
-    if max_dn == 0:
-        assert int(og["newton_iters"].sum()) == int(oc["newton_iters"].sum())
-    pinned = np.ones(zc.shape[0], dtype=bool)
-    if dense is not None:
-        # multipliers: entry by entry where they are unique, through G'l + A'v everywhere
-        pinned = _unique_duals(dense, vc)
-        nz, nl, nv = dense.nz, dense.nl, dense.nv
-        A = dense.arrays["A"].reshape(-1, nz, nv)   # A[b, k, i] = A_b[i][k]
-        img = lambda l, v: (np.einsum("bki,bi->bk", A, v) +
-                            (np.einsum("bkq,bq->bk", dense.arrays["G"].reshape(-1, nz, nl), l) if nl else 0.0))
-        ig, ic = img(lg, vg), img(lc, vc)
-        scale = 1.0 + np.abs(ic).max(axis=1, keepdims=True)
-        assert (np.abs(ig - ic) <= 10 * abs_tol * scale).all(), np.abs(ig - ic).max()
-    for g, c, sel in ((zg, zc, None), (lg, lc, pinned), (vg, vc, pinned), (yg, yc, None)):
-        if c.size:
-            scale = 1.0 + np.abs(c).max(axis=1, keepdims=True)
-            close = np.abs(g - c) <= 10 * abs_tol * scale
-            if sel is not None:
-                close = close[sel]
-            assert close.all(), np.abs(g - c).max()
-    ok = oc["eflag"] == 0
-    np.testing.assert_allclose(og["initial_residual"], oc["initial_residual"], rtol=1e-10)
-    # residuals agree where they are well above the rounding floor of a
-    # cancellation-dominated quantity (terms are O(1..100), eps*100 ~ 1e-14,
-    # amplified by the Newton step's conditioning, cond(K) up to 1e11: a few 1e-8)
-    big = ok & (oc["residual"] > 1e-7)
-    # (a different elimination order - `dense` - rounds the last step differently:
-    # a tenth of the tolerance the solve stops at)
-    if big.any():
-        np.testing.assert_allclose(og["residual"][big], oc["residual"][big], rtol=2e-2,
-                                   atol=3e-8 if dense is None else max(3e-8, 0.1 * abs_tol))
 
 
 # -- reference end-to-end tests through the C-ABI ------------------------------
@@ -361,18 +287,30 @@ def test_up_to_32_constraint_rows_per_stage_run_on_a_record_kernel(hip, oracle):
 
 
 @pytest.mark.parametrize("batch", [1, 2, 3, 5, 7])
-def test_rows_that_never_get_a_qp_join_the_cooperative_passes(hip, oracle, batch):
+def test_rows_that_never_get_a_qp_join_the_cooperative_passes(hip, oracle, monkeypatch, batch):
     """Batches that leave rows of a wavefront without a QP from the start (one 16-lane row
     per QP, four rows per wavefront): those rows still take part in the cooperative
     line-search, open_prox and close_subproblem passes of their wavefront.  Their policy
     objects used to be unbound there (indeterminate members: the failures of the <12,4,32>
     instance that came and went with unrelated changes); both
-    16-lane instances, BASELINE plant with 20 and with 32 constraint rows per stage."""
+    16-lane instances, BASELINE plant with 20 and with 32 constraint rows per stage.
+    A handle made for such a batch runs it spread, one QP per wavefront (rows 1-3 idle
+    everywhere); the same batches on ONE workgroup (FBSTAB_HIP_MAX_WORKGROUPS=1) put idle rows
+    beside busy ones (batches 1-3) and make rows fetch a second QP (5 and 7)."""
     o = default_options()
     for p in (fx.synthetic_mpc_batch(batch, first_id=40 + batch), fx.boxed_mpc_batch(batch)):
-        gpu = _solve_mpc_host(hip, p, o)
         cpu = oracle.solve_mpc(p, opts=o, nthreads=oracle.num_threads())
-        _assert_parity(gpu, cpu, o.abs_tol)
+        for cap in (None, 1):
+            if cap is None:
+                monkeypatch.delenv("FBSTAB_HIP_MAX_WORKGROUPS", raising=False)
+            else:
+                monkeypatch.setenv("FBSTAB_HIP_MAX_WORKGROUPS", str(cap))
+            s = hip.FBstabMpcBatch(*p.sizes(), max_batch=batch)
+            assert s.query()["workgroups"] == (cap or batch) and "r16" in s.kernel_name()
+            s.close()
+            gpu = _solve_mpc_host(hip, p, o)
+            monkeypatch.delenv("FBSTAB_HIP_MAX_WORKGROUPS", raising=False)
+            _assert_parity(gpu, cpu, o.abs_tol)
         assert (cpu[4]["eflag"] == 0).all() and (cpu[4]["newton_iters"] > 3).all()
 
 
