@@ -31,6 +31,7 @@
 
 #include <type_traits>
 
+#include "fb_adjoint.h"
 #include "fb_common.h"
 
 namespace fbk {
@@ -632,6 +633,9 @@ struct MpcProblem {
   // and produces dz, dl, dv, adz = A dz, wz = H dz + G'dl + A'dv, wl = -G dz.
   // Returns false iff a Cholesky pivot was not positive
   // (riccati_linear_solver.cc:131-136).
+  // ADJ (mpc_adjoint below): rvm holds the seed gv on entry, and the constraint block's -pfb(ys, v) becomes
+  // -C.gv; the solver's instance (ADJ = false) is the step as it always was.
+  template <bool ADJ = false>
   FB_DEV bool newton_step(const C& c, double sigma, double alpha) const {
     const int N = lay.N, nx = lay.nx, nu = lay.nu, nc = lay.nc, ns = lay.ns;
     mptr tQ = lds + lay.t_q; mptr tR = lds + lay.t_r; mptr tS = lds + lay.t_s;
@@ -671,7 +675,9 @@ struct MpcProblem {
         pfb_gradient(ys, vk, alpha, &g0, &g1);
         const double mu = g1 + sigma * g0;
         const double G_ = g0 / mu;
-        const double rm = -pfb(ys, vk, alpha) / mu;  // (-rv)/mus
+        double rm;
+        if constexpr (ADJ) rm = -(g0 * rvm[g]) / mu;  // (-C.gv)/mus
+        else rm = -pfb(ys, vk, alpha) / mu;  // (-rv)/mus
         Gam[k] = G_;
         Rvm[k] = rm;
         gam[g] = G_;
@@ -864,5 +870,35 @@ struct MpcProblem {
     }
   }
 };
+
+// ---- reverse-mode derivative of the solution map (fbstab_hip_mpc_adjoint_batch) -------------------------
+// At a returned point x = (z, l, v) with xbar = x, the Newton matrix of the step above,
+//   V = [H + sigma I, G', A'; -G, sigma I, 0; -C.A, 0, mus.]   (C = d phi / d y, mus = d phi / d v + sigma C),
+// is the Jacobian of the inner residual (full_residual.cc:49-74; riccati_linear_solver.cc:77-344 factors it).
+// For seeds (gz, gl, gv) = dL/d(z, l, v) the adjoint system V' w = (gz, gl, gv) reduces to the same
+// factorisation: the step with the right-hand side (gz, -gl, -C.gv) gives (dz, dl, dv), and then
+// w = (dz, -dl, (gv - A dz)/mus).  The step's inner residual holds -R, so rz = -gz, rl = gl; the seed gv
+// goes to rvm, which newton_step<true> reads in place of pfb.  sigma(z - zb) etc. vanish exactly.
+// Returns false iff a factorisation failed.
+template <class C, bool WG>
+FB_DEV bool mpc_adjoint(const MpcProblem<C, WG>& p, const C& c, double sigma, double alpha, const double* gz,
+                        const double* gl, const double* gv) {
+  p.load_guess(c);  // (z, l, v) <- the point, y = b - A z
+  for (int i = c.tid; i < p.nz; i += C::nt) { p.zb[i] = p.z[i]; p.rz[i] = -gz[i]; }
+  for (int i = c.tid; i < p.nl; i += C::nt) { p.lb[i] = p.l[i]; p.rl[i] = gl ? gl[i] : 0.0; }
+  for (int i = c.tid; i < p.nv; i += C::nt) { p.vb[i] = p.v[i]; p.yb[i] = p.y[i]; p.rvm[i] = gv ? gv[i] : 0.0; }
+  c.sync();
+  return p.template newton_step<true>(c, sigma, alpha);
+}
+
+// theta_bar = -J_theta' w for the MPC data theta: the contraction of fb_adjoint.h from the point and the step
+// in this workgroup's scratch.
+template <class C, bool WG>
+FB_DEV void mpc_adjoint_gradients(const MpcProblem<C, WG>& p, const C& c, const MpcGrad& G, bool ok, double* az,
+                                  double* al, double* av) {
+  const MpcLayout& lay = p.lay;
+  mpc_adjoint_contract(c, lay.N, lay.nx, lay.nu, lay.nc, p.z, p.l, p.v, p.dz, p.dl, p.dv, G, ok, az, al, av);
+  c.sync();
+}
 
 }  // namespace fbk

@@ -2328,11 +2328,15 @@ struct MpcR16 {
   }
   // (gamma, rv / mu) of constraint k at (v, y) for the subproblem centred at vbar
   // (riccati_linear_solver.cc:91-99)
+  // ADJ (adjoint_step): x = xbar, so v - vbar is zero and the vbar slot carries the seed gv instead; the
+  // second term is then (-C.gv) / mu in place of (-rv) / mu.
+  template <bool ADJ = false>
   static FB_DEV dbl2 barrier_terms(double vk, double yk, double vb, double sigma, double alpha, bool real) {
-    const double ys = yk + sigma * (vk - vb);
+    const double ys = ADJ ? yk : yk + sigma * (vk - vb);
     double ph, g0, g1;
     pfb_all(ys, vk, alpha, &ph, &g0, &g1);
     const double imu = rcp_fast(g1 + sigma * g0);
+    if constexpr (ADJ) ph = g0 * vb;
     dbl2 o = {real ? g0 * imu : 0.0, real ? -ph * imu : 0.0};
     return o;
   }
@@ -2415,10 +2419,54 @@ struct MpcR16 {
     return true;
   }
 
+  // ---- the adjoint (fbstab_hip_mpc_adjoint_batch; fb_adjoint.h) ---------------------------------------
+  // At x = xbar = the point load_guess() put in the record (no displacement): the seeds go where the step's
+  // inner residual goes (rz = -gz, rl = gl) and gv to the vbar slots, which barrier_terms<true> reads as the
+  // seed - the constraint block's right-hand side becomes -C.gv.  One step, factor and both sweeps as the
+  // solver runs them, then (dz, dl, dv) flat to `flat` (nz + nl + nv doubles) for the contraction.  gl, gv may
+  // be null (zero).  Returns false on a non-positive pivot.
+  FB_DEV bool adjoint_step(const C& c, double sigma, double alpha, const double* gz, const double* gl,
+                           const double* gv, double* flat) {
+    const int r = c.tid, N_ = N;
+    const int nx_ = prob_nx(), nu_ = prob_nu(), nc_ = prob_nc();
+    const long nz = (long)(N_ + 1) * (nx_ + nu_), nl = (long)(N_ + 1) * nx_;
+    for (int i = 0; i <= N_; i++) {
+      double* R = rec + (long)i * kRec;
+      const long zi = z_index(i, r);
+      st(R, sRZ, zi >= 0 ? -gz[zi] : 0.0);
+      st(R, sRL, (r < nx_ && gl) ? gl[(long)i * nx_ + r] : 0.0);
+      sfor<0, KS>([&](auto S_) {
+        constexpr int sl = decltype(S_)::value;
+        const int k = r + LPQ * sl;
+        st(R, sVB + sl, (k < nc_ && gv) ? gv[(long)i * nc_ + k] : 0.0);
+      });
+    }
+    c.sync();
+    const StepOut o = rowdl ? newton_core<true, false, true>(c, rec, pack, lpo, lds, pack_view(c), N, bounds, 0.0, lds_off,
+                                                             sigma, alpha)
+                            : newton_core<false, false, true>(c, rec, pack, lpo, lds, pack_view(c), N, bounds, 0.0,
+                                                              lds_off, sigma, alpha);
+    lds_off = o.loff;
+    if (!o.ok) return false;
+    for (int i = 0; i <= N_; i++) {
+      const double* R = rec + (long)i * kRec;
+      const long zi = z_index(i, r);
+      if (zi >= 0) flat[zi] = ld(R, sDZ);
+      if (r < nx_) flat[nz + (long)i * nx_ + r] = ld(R, sDL);
+      sfor<0, KS>([&](auto S_) {
+        constexpr int sl = decltype(S_)::value;
+        const int k = r + LPQ * sl;
+        if (k < nc_) flat[nz + nl + (long)i * nc_ + k] = ld(R, sDV + 2 * sl);
+      });
+    }
+    return true;
+  }
+
   // ROW: the costate step from the Newton system's row, form (b) above.
   // REFINE: the right-hand side is the Newton system's residual at the step in the record, and the
   // backward sweep ADDS its solution to that step (refine_step()).
-  template <bool ROW, bool REFINE>
+  // ADJ: the adjoint's step (adjoint_step): barrier_terms<true> in both sweeps, nothing else changes.
+  template <bool ROW, bool REFINE, bool ADJ = false>
   static FB_DEV StepOut newton_core(const C& c, double* const R0, const double* const P0, const lds_iptr po,
                                     lds_ptr lds_row, pk_ptr Lp, const int N_, const bool bnd, const double tp,
                                     int loff, double sigma, double alpha) {
@@ -2479,7 +2527,7 @@ struct MpcR16 {
         const int k = r + LPQ * s;
         const double vk = fma(tp, cur.da[s][0], cur.vy[s][0]);
         const double yk = fma(-tp, cur.da[s][1], cur.vy[s][1]);
-        const dbl2 bt = barrier_terms(vk, yk, cur.vb[s], sigma, alpha, LPQ * (s + 1) <= NC || k < NC);
+        const dbl2 bt = barrier_terms<ADJ>(vk, yk, cur.vb[s], sigma, alpha, LPQ * (s + 1) <= NC || k < NC);
         Gam[s] = bt[0];
         Rvm[s] = bt[1];
         if constexpr (!REFINE) {  // (the refinement sweep finds all of this in the record: tp = 0)
@@ -2792,8 +2840,8 @@ struct MpcR16 {
       if constexpr (!kStoreGamma) {
         sfor<0, KS>([&](auto S_) {
           constexpr int sl = decltype(S_)::value;
-          cu.gr[sl] = barrier_terms(cu.vy[sl][0], cu.vy[sl][1], cu.vb[sl], sigma, alpha,
-                                    LPQ * (sl + 1) <= NC || r + LPQ * sl < NC);
+          cu.gr[sl] = barrier_terms<ADJ>(cu.vy[sl][0], cu.vy[sl][1], cu.vb[sl], sigma, alpha,
+                                         LPQ * (sl + 1) <= NC || r + LPQ * sl < NC);
         });
       }
       double Cc_[NC], Hr[NS], AB[NS];

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fbstab_hip.h"
+#include "fb_adjoint.h"
 #include "fb_algorithm.h"
 #include "fb_mpc_r16.h"
 
@@ -23,6 +24,22 @@ struct RecordInstance {
   long long (*ws_doubles)(int N);
   const void *solve, *solve_keep, *probe;  // kernels of the padded instance
   const void *solve_exact, *solve_keep_exact, *probe_exact;  // problem == instance shape
+  // fbstab_hip_mpc_adjoint_batch on the record (one-row instances; null: the flat-vector adjoint serves the shape)
+  const void *adjoint, *adjoint_exact;
+};
+
+// Arguments of the record adjoint kernel (fbstab_hip_mpc_adjoint_batch): the seeds (gz, gl, gv; gl and gv may be
+// null), the gradient slots (FBSTAB_MPC_* order; null: not wanted), the adjoint (dz, dl, dv; null slots skipped),
+// the per-QP status, sigma and the options' alpha.
+struct AdjointArgs {
+  const double* seed[3];
+  long long sstride[3];
+  double* grad[FBSTAB_MPC_NSEQ];
+  long long gstride[FBSTAB_MPC_NSEQ];
+  double* adj[3];
+  long long astride[3];
+  int* status;
+  double sigma, alpha;
 };
 
 namespace {
@@ -306,6 +323,65 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_kernel(
 #endif
 }
 
+// The adjoint of fbstab_hip_mpc_adjoint_batch on the one-row record instances: rows pull QPs from the counter as
+// the solve's do; per QP the record is packed with the point as x = xbar (load_guess), one Newton step runs with
+// the adjoint's right-hand side (MpcR16::adjoint_step: the solver's factor and sweeps, barrier_terms<true>), and
+// the row's lanes contract (dz, dl, dv) - left flat in the slot's matrix-copy region, which nothing reads after
+// the step - with the point into the gradients (fb_adjoint.h).  The slot's matrix copies are overwritten: a
+// FBSTAB_HIP_KEEP_MATRICES solve after it rebuilds them (fbstab_hip.hip resets kept_batch).
+template <int NX, int NU, int NC, bool EXACT>
+__global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_adjoint_kernel(
+    MpcBatchPtrs data, VarBatchPtrs x, AdjointArgs a, double* scratch, int* counter, int batch, int N) {
+  typedef MpcR16<NX, NU, NC, EXACT, false, 1> P;
+  typename P::C ctx;
+  ctx.tid = threadIdx.x & (P::LPQ - 1);
+  P p;
+  R16Queue<P, false> qu;
+  qu.data = &data;
+  qu.x = &x;
+  qu.ctl = counter;
+  qu.scratch = scratch;
+  qu.batch = batch;
+  qu.N = N;
+  qu.reuse = false;
+  p.bind_idle(qu.lds(), qu.pack_lds(), qu.lpo(), N);
+  const int nx = EXACT ? NX : data.nx, nu = EXACT ? NU : data.nu, nc = EXACT ? NC : data.nc;
+  const long nz = (long)(N + 1) * (nx + nu), nl = (long)(N + 1) * nx;
+  for (;;) {
+    const long q = qu.fetch(p);
+    if (q < 0) break;
+    auto at = [q](auto* b, long long s) { return b ? b + q * s : nullptr; };
+    p.load_guess(ctx);
+    p.choose_costate_form(a.sigma);
+    double* const flat = qu.slot_ptr(qu.home()) + P::hdr_doubles(N);
+    const bool ok = p.adjoint_step(ctx, a.sigma, a.alpha, at(a.seed[0], a.sstride[0]), at(a.seed[1], a.sstride[1]),
+                                   at(a.seed[2], a.sstride[2]), flat);
+    // the lanes' stores of the step are read by the row's other lanes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    MpcGrad G;
+    G.Q = at(a.grad[FBSTAB_MPC_Q], a.gstride[FBSTAB_MPC_Q]);
+    G.R = at(a.grad[FBSTAB_MPC_R], a.gstride[FBSTAB_MPC_R]);
+    G.S = at(a.grad[FBSTAB_MPC_S], a.gstride[FBSTAB_MPC_S]);
+    G.q = at(a.grad[FBSTAB_MPC_q], a.gstride[FBSTAB_MPC_q]);
+    G.r = at(a.grad[FBSTAB_MPC_r], a.gstride[FBSTAB_MPC_r]);
+    G.A = at(a.grad[FBSTAB_MPC_A], a.gstride[FBSTAB_MPC_A]);
+    G.B = at(a.grad[FBSTAB_MPC_B], a.gstride[FBSTAB_MPC_B]);
+    G.c = at(a.grad[FBSTAB_MPC_c], a.gstride[FBSTAB_MPC_c]);
+    G.E = at(a.grad[FBSTAB_MPC_E], a.gstride[FBSTAB_MPC_E]);
+    G.L = at(a.grad[FBSTAB_MPC_L], a.gstride[FBSTAB_MPC_L]);
+    G.d = at(a.grad[FBSTAB_MPC_d], a.gstride[FBSTAB_MPC_d]);
+    G.x0 = at(a.grad[FBSTAB_MPC_x0], a.gstride[FBSTAB_MPC_x0]);
+    mpc_adjoint_contract(ctx, N, nx, nu, nc, x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
+                         x.base[2] + q * x.stride[2], flat, flat + nz, flat + nz + nl, G, ok, at(a.adj[0], a.astride[0]),
+                         at(a.adj[1], a.astride[1]), at(a.adj[2], a.astride[2]));
+    if (ctx.tid == 0) a.status[q] = ok ? 0 : 1;
+    // (the next QP of this row packs its record over the flat step the contraction has read)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+}
+
 template <int NX, int NU, int NC, int R>
 long long r16_ws_doubles(int N) { return fbk::MpcR16<NX, NU, NC, true, false, R>::ws_doubles(N); }
 template <int NX, int NU, int NC, int R>
@@ -329,6 +405,11 @@ RecordInstance r16_instance(const char* name) {
   r.solve_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, false, true, false, R>);
   r.solve_keep_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, false, true, true, R>);
   r.probe_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, true, true, false, R>);
+  r.adjoint = r.adjoint_exact = nullptr;  // (row-pair instances: the flat-vector adjoint)
+  if constexpr (R == 1) {
+    r.adjoint = reinterpret_cast<const void*>(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, false>);
+    r.adjoint_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, true>);
+  }
   return r;
 }
 

@@ -123,6 +123,58 @@ __global__ __launch_bounds__(NT, FB_MPC_MIN_WAVES) void fbstab_mpc_kernel(MpcLay
 }
 
 
+// The adjoint of fbstab_hip_mpc_adjoint_batch on the flat-vector policy (fb_mpc.h: mpc_adjoint,
+// mpc_adjoint_gradients), one QP per workgroup pulled from the queue like the solve: the shapes of the flat-vector
+// kernel and of the row-pair record instances (their handles give it a scratch of its own; the one-row instances
+// run fbstab_mpc_r16_adjoint_kernel, fb_record_kernel.h).  `x`: the point
+// (z, l, v); `seed`: (gz, gl, gv), null l / v slots meaning zero; `adj`: null slots, or (dz, dl, dv).
+struct MpcGradArgs {
+  double* base[FBSTAB_MPC_NSEQ];
+  long long stride[FBSTAB_MPC_NSEQ];
+};
+template <int NT, bool WG>
+__global__ __launch_bounds__(NT, FB_MPC_MIN_WAVES) void fbstab_mpc_adjoint_kernel(
+    MpcLayout lay, MpcBatchArgs data, VarBatchArgs x, VarBatchArgs seed, MpcGradArgs grad, VarBatchArgs adj,
+    int* status, double sigma, double alpha, double* scratch, int* counter, int batch) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  lds_ptr lds = (lds_ptr)smem;
+  typedef Ctx<NT> C;
+  C ctx;
+  ctx.tid = threadIdx.x;
+  ctx.red = WG ? lds : lds + lay.w_red;
+  double* ws = scratch + (long)blockIdx.x * lay.ws_doubles;
+  for (;;) {
+    const int q = next_qp<NT>(counter, WG ? lds + kMaxReduce * ((NT + 63) / 64) : lds + lay.w_out);
+    if (q >= batch) break;
+    MpcProblem<C, WG> p;
+    typename MpcProblem<C, WG>::mptr mb;
+    if constexpr (WG) mb = ws + lay.v_carve;
+    else mb = lds;
+    p.bind(lay, mpc_data_of(data, q), x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
+           x.base[2] + q * x.stride[2], nullptr, mb, ws);
+    auto at = [q](double* b, long long s) { return b ? b + q * s : nullptr; };
+    const bool ok = mpc_adjoint(p, ctx, sigma, alpha, seed.base[0] + q * seed.stride[0],
+                                at(seed.base[1], seed.stride[1]), at(seed.base[2], seed.stride[2]));
+    MpcGrad G;
+    G.Q = at(grad.base[FBSTAB_MPC_Q], grad.stride[FBSTAB_MPC_Q]);
+    G.R = at(grad.base[FBSTAB_MPC_R], grad.stride[FBSTAB_MPC_R]);
+    G.S = at(grad.base[FBSTAB_MPC_S], grad.stride[FBSTAB_MPC_S]);
+    G.q = at(grad.base[FBSTAB_MPC_q], grad.stride[FBSTAB_MPC_q]);
+    G.r = at(grad.base[FBSTAB_MPC_r], grad.stride[FBSTAB_MPC_r]);
+    G.A = at(grad.base[FBSTAB_MPC_A], grad.stride[FBSTAB_MPC_A]);
+    G.B = at(grad.base[FBSTAB_MPC_B], grad.stride[FBSTAB_MPC_B]);
+    G.c = at(grad.base[FBSTAB_MPC_c], grad.stride[FBSTAB_MPC_c]);
+    G.E = at(grad.base[FBSTAB_MPC_E], grad.stride[FBSTAB_MPC_E]);
+    G.L = at(grad.base[FBSTAB_MPC_L], grad.stride[FBSTAB_MPC_L]);
+    G.d = at(grad.base[FBSTAB_MPC_d], grad.stride[FBSTAB_MPC_d]);
+    G.x0 = at(grad.base[FBSTAB_MPC_x0], grad.stride[FBSTAB_MPC_x0]);
+    mpc_adjoint_gradients(p, ctx, G, ok, at(adj.base[0], adj.stride[0]), at(adj.base[1], adj.stride[1]),
+                          at(adj.base[2], adj.stride[2]));
+    if (ctx.tid == 0) status[q] = ok ? 0 : 1;
+    ctx.sync();
+  }
+}
+
 // Closed-loop step of the receding-horizon sweep (fbstab_hip_mpc_receding_sweep):
 // one thread per trajectory.  u0 = first input of the solution just computed,
 // x0 <- A x0 + B u0 (the SimulationInputs of the reference's generator,
@@ -501,6 +553,10 @@ struct fbstab_mpc_solver : SolverBase {
   bool exact = false;     // the problem has exactly the instance's shape
   int kept_batch = -1;    // batch size of the last FBSTAB_HIP_KEEP_MATRICES call whose copies are still in the slots
   int qps_per_wg = 1;
+  // fbstab_hip_mpc_adjoint_batch: the flat-vector kernel's scratch on a row-pair record handle (whose own scratch
+  // is laid out for the record kernel), allocated by the first call; the LDS attribute set once
+  double* adj_scratch = nullptr;
+  bool adj_ready = false;
 };
 
 namespace {
@@ -689,6 +745,7 @@ int fbstab_hip_mpc_create_in_flight(int N, int nx, int nu, int nc, int max_batch
 int fbstab_hip_mpc_destroy(fbstab_mpc_handle_t h) {
   if (!h) return FBSTAB_HIP_OK;
   h->release();
+  if (h->adj_scratch) (void)hipFree(h->adj_scratch);
   delete h;
   return FBSTAB_HIP_OK;
 }
@@ -1014,6 +1071,173 @@ int fbstab_hip_mpc_debug_newton(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t*
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(io, d_io, sizeof(double) * n_io, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  return FBSTAB_HIP_OK;
+}
+
+// Reverse-mode derivative of the solution map at returned points (include/fbstab_hip.h).  One launch of
+// fbstab_mpc_adjoint_kernel: the Newton matrix of RiccatiLinearSolver::Initialize at x = xbar = the point
+// (riccati_linear_solver.cc:77-210), one Solve (:212-344) with the adjoint's right-hand side, one contraction.
+int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                 const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                                 const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
+                                 int flags, void* stream) {
+  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  if (!seed || !grad) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
+    if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
+  for (int i = 0; i < 3; i++)
+    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
+  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null seed pointer (z)");
+  // strides: every QP its own slot (a gradient or adjoint shared by the batch would be written by all of them)
+  for (int i = 0; i < 3; i++) {
+    if (batch > 1 && x->stride[i] < h->var_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
+    if (batch > 1 && seed->base[i] && seed->stride[i] < h->var_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "seed stride smaller than the vector length");
+    if (batch > 1 && adj && adj->base[i] && adj->stride[i] < h->var_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
+  }
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
+    if (batch > 1 && grad->base[i] && grad->stride[i] < h->arr_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
+  if (batch == 0) return FBSTAB_HIP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
+  const bool status_host = !dev_ptrs || (flags & FBSTAB_HIP_OUT_ON_HOST);
+  const fbk::MpcLayout& L = h->lay;
+  const long long vlen[3] = {L.nz, L.nl, L.nv};
+  MpcBatchArgs a;
+  VarBatchArgs v, sd, ad;
+  MpcGradArgs g;
+  for (int i = 0; i < 4; i++) { v.base[i] = sd.base[i] = ad.base[i] = nullptr; v.stride[i] = sd.stride[i] = ad.stride[i] = 0; }
+  DevBuf d_seed[3], d_adj[3], d_grad[FBSTAB_MPC_NSEQ], d_status;
+  if (dev_ptrs) {
+    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { a.base[i] = data->base[i]; a.stride[i] = data->stride[i]; }
+    for (int i = 0; i < 3; i++) {
+      v.base[i] = x->base[i]; v.stride[i] = x->stride[i];
+      sd.base[i] = seed->base[i]; sd.stride[i] = seed->stride[i];
+      if (adj) { ad.base[i] = adj->base[i]; ad.stride[i] = adj->stride[i]; }
+    }
+    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { g.base[i] = grad->base[i]; g.stride[i] = grad->stride[i]; }
+  } else {
+    rc = h->ensure_staging();
+    if (rc != FBSTAB_HIP_OK) return rc;
+    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
+      if (data->stride[i] != 0 && data->stride[i] < h->arr_len[i] && batch > 1)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
+      rc = h->upload(data->base[i], data->stride[i], h->arr_len[i], batch, h->d_arr[i], &a.stride[i], s);
+      if (rc != FBSTAB_HIP_OK) return rc;
+      a.base[i] = h->d_arr[i];
+    }
+    for (int i = 0; i < 3; i++) {
+      long long st;
+      rc = h->upload(x->base[i], x->stride[i] ? x->stride[i] : vlen[i], vlen[i], batch, h->d_var[i], &st, s);
+      if (rc != FBSTAB_HIP_OK) return rc;
+      v.base[i] = h->d_var[i]; v.stride[i] = vlen[i];
+      if (seed->base[i]) {
+        HIP_TRY(hipMalloc(&d_seed[i].p, sizeof(double) * (size_t)(vlen[i] > 0 ? vlen[i] : 1) * batch));
+        sd.base[i] = static_cast<double*>(d_seed[i].p);
+        rc = h->upload(seed->base[i], seed->stride[i] ? seed->stride[i] : vlen[i], vlen[i], batch, sd.base[i], &st, s);
+        if (rc != FBSTAB_HIP_OK) return rc;
+        sd.stride[i] = vlen[i];
+      }
+      if (adj && adj->base[i]) {
+        HIP_TRY(hipMalloc(&d_adj[i].p, sizeof(double) * (size_t)(vlen[i] > 0 ? vlen[i] : 1) * batch));
+        ad.base[i] = static_cast<double*>(d_adj[i].p); ad.stride[i] = vlen[i];
+      }
+    }
+    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
+      g.base[i] = nullptr; g.stride[i] = 0;
+      if (grad->base[i] && h->arr_len[i] > 0) {
+        HIP_TRY(hipMalloc(&d_grad[i].p, sizeof(double) * (size_t)h->arr_len[i] * batch));
+        g.base[i] = static_cast<double*>(d_grad[i].p); g.stride[i] = h->arr_len[i];
+      }
+    }
+  }
+  int* d_st = status;
+  if (status_host) {
+    HIP_TRY(hipMalloc(&d_status.p, sizeof(int) * (size_t)batch));
+    d_st = static_cast<int*>(d_status.p);
+  }
+  double sig = sigma > 0.0 ? sigma : 1e-8;  // the reference's default sigma0 (fbstab_algorithm-impl.h:34)
+  double alpha = h->opts.alpha;
+  HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
+  if (h->rec && h->rec->adjoint) {
+    // one-row record instances: the adjoint on the record, in the handle's own slots (their matrix copies are
+    // overwritten: the next FBSTAB_HIP_KEEP_MATRICES solve rebuilds them)
+    const RecordInstance& r = *h->rec;
+    const void* kern = h->exact ? r.adjoint_exact : r.adjoint;
+    if (!h->adj_ready) {
+      HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
+      h->adj_ready = true;
+    }
+    h->kept_batch = -1;
+    MpcBatchPtrs d;
+    VarBatchPtrs xp;
+    AdjointArgs aa;
+    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
+      d.base[i] = a.base[i]; d.stride[i] = a.stride[i];
+      aa.grad[i] = g.base[i]; aa.gstride[i] = g.stride[i];
+    }
+    d.nx = L.nx; d.nu = L.nu; d.nc = L.nc;
+    for (int i = 0; i < 4; i++) { xp.base[i] = v.base[i]; xp.stride[i] = v.stride[i]; }
+    for (int i = 0; i < 3; i++) {
+      aa.seed[i] = sd.base[i]; aa.sstride[i] = sd.stride[i];
+      aa.adj[i] = ad.base[i]; aa.astride[i] = ad.stride[i];
+    }
+    aa.status = d_st;
+    aa.sigma = sig;
+    aa.alpha = alpha;
+    // (as the solve: a batch that does not outnumber the workgroups runs one QP per wavefront)
+    int grid = (batch + h->qps_per_wg - 1) / h->qps_per_wg;
+    if (batch <= h->workgroups) grid = batch;
+    if (grid > h->workgroups) grid = h->workgroups;
+    int N = L.N;
+    void* args[] = {&d, &xp, &aa, &h->scratch, &h->counter, &batch, &N};
+    HIP_TRY(hipEventRecord(h->ev0, s));
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)h->lds_bytes, s));
+  } else {
+    // the flat-vector kernel: the handle's own workspace on flat-vector handles; on row-pair record handles one of
+    // its own, L.ws_doubles x workgroups doubles (fbstab_hip_mpc_query does not count it), allocated once
+    const int grid = batch < h->workgroups ? batch : h->workgroups;
+    double* scratch = h->scratch;
+    if (h->rec) {
+      if (!h->adj_scratch)
+        HIP_TRY(hipMalloc(&h->adj_scratch, sizeof(double) * (size_t)L.ws_doubles * (size_t)h->workgroups));
+      scratch = h->adj_scratch;
+    }
+    const void* kern = L.wglobal ? reinterpret_cast<const void*>(fbstab_mpc_adjoint_kernel<kMpcThreads, true>)
+                                 : reinterpret_cast<const void*>(fbstab_mpc_adjoint_kernel<kMpcThreads, false>);
+    const int lds = L.launch_lds_doubles * (int)sizeof(double);
+    if (!h->adj_ready) {
+      HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      h->adj_ready = true;
+    }
+    void* args[] = {const_cast<fbk::MpcLayout*>(&L), &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &scratch, &h->counter,
+                    &batch};
+    HIP_TRY(hipEventRecord(h->ev0, s));
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(kMpcThreads), args, (size_t)lds, s));
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(h->ev1, s));
+  h->timed = true;
+  if (!dev_ptrs) {
+    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
+      if (g.base[i]) {
+        rc = h->download(grad->base[i], grad->stride[i] ? grad->stride[i] : h->arr_len[i], h->arr_len[i], batch,
+                         g.base[i], s);
+        if (rc != FBSTAB_HIP_OK) return rc;
+      }
+    for (int i = 0; i < 3; i++)
+      if (ad.base[i]) {
+        rc = h->download(adj->base[i], adj->stride[i] ? adj->stride[i] : vlen[i], vlen[i], batch, ad.base[i], s);
+        if (rc != FBSTAB_HIP_OK) return rc;
+      }
+  }
+  if (status_host) HIP_TRY(hipMemcpyAsync(status, d_st, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
+  if (status_host || !(flags & FBSTAB_HIP_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
   return FBSTAB_HIP_OK;
 }
 

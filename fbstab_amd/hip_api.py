@@ -81,6 +81,10 @@ class _VarBatch(C.Structure):
     _fields_ = [("base", C.c_void_p * 4), ("stride", C.c_longlong * 4)]
 
 
+class _MpcGradBatch(C.Structure):
+    _fields_ = [("base", C.c_void_p * 12), ("stride", C.c_longlong * 12)]
+
+
 class _Plant(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("stride_A", C.c_longlong), ("stride_B", C.c_longlong)]
 
@@ -147,6 +151,10 @@ def load_library() -> C.CDLL:
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.fbstab_hip_mpc_kernel_name.restype = C.c_char_p
     lib.fbstab_hip_mpc_kernel_name.argtypes = [C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_adjoint_batch"):  # (absent from a build of an earlier round loaded for an A/B)
+        lib.fbstab_hip_mpc_adjoint_batch.argtypes = [
+            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_int, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -176,7 +184,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_solve_traced", "fbstab_hip_mpc_receding_sweep",
     "fbstab_hip_mpc_last_kernel_ms", "fbstab_hip_mpc_query", "fbstab_hip_mpc_kernel_name",
     "fbstab_hip_mpc_refined_steps", "fbstab_hip_mpc_create_in_flight",
-    "fbstab_hip_mpc_debug_newton", "fbstab_hip_debug_stamps",
+    "fbstab_hip_mpc_debug_newton", "fbstab_hip_mpc_adjoint_batch", "fbstab_hip_debug_stamps",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",
     "fbstab_hip_dense_solve_traced",
@@ -484,6 +492,76 @@ class FBstabMpcBatch(_SolverBase):
             o += s
         out["ok"] = bool(io[o] > 0.5)
         return out
+
+    def Adjoint(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0,
+                want: Optional[Sequence[str]] = None, adj: bool = False, stream: int = 0,
+                async_: bool = False) -> Dict[str, object]:
+        """Reverse-mode derivative of the solution map (fbstab_hip_mpc_adjoint_batch): for a loss L with
+        seeds ``gz, gl, gv`` = dL/d(z, l, v) at the returned point ``(z, l, v)`` (``(batch, n)`` arrays, all numpy
+        or all torch CUDA tensors, like ``Solve``), returns a dict with dL/d(sequence) for every name of ``want``
+        (default: all 12 of MPC_SEQ, each ``(batch, len)``), ``"status"`` (``(batch,)`` int32: 0, or 1 where
+        the factorisation failed and the gradients are zero) and, with ``adj=True``, ``"dz", "dl", "dv"``.
+        ``gl``/``gv`` None: zero seeds.  ``sigma <= 0``: 1e-8."""
+        want = tuple(MPC_SEQ if want is None else want)
+        unknown = set(want) - set(MPC_SEQ)
+        assert not unknown, unknown
+        b = _MpcBatch()
+        dev_flags = []
+        B = None
+        for i, (k, n) in enumerate(zip(MPC_SEQ, self.seq_len)):
+            p, st, d = _ptr_stride(data[k], n)
+            b.base[i], b.stride[i] = p, st
+            dev_flags.append(d)
+            B = data[k].shape[0] if B is None else B
+        lens = (self.nz, self.nl, self.nv)
+
+        def var(arrs, allow_none):
+            vb = _VarBatch()
+            for i, (a, n) in enumerate(zip(arrs, lens)):
+                if a is None:
+                    assert allow_none and i > 0, "z, l, v and gz are required"
+                    vb.base[i], vb.stride[i] = None, 0
+                    continue
+                p, st, d = _ptr_stride(a, n)
+                assert a.shape[0] == B
+                vb.base[i], vb.stride[i] = p, st
+                dev_flags.append(d)
+            return vb
+
+        xb = var((z, l, v), False)
+        sb = var((gz, gl, gv), True)
+        on_dev = all(dev_flags)
+        assert on_dev or not any(dev_flags), "mix of host and device arrays"
+        if on_dev:
+            import torch
+            zeros = lambda n, dt=torch.float64: torch.zeros((B, n), dtype=dt, device=z.device)
+            if not stream:
+                stream = torch.cuda.current_stream(z.device).cuda_stream
+            flags = DEVICE_POINTERS | (ASYNC if async_ else 0)
+            status = torch.zeros(B, dtype=torch.int32, device=z.device)
+        else:
+            zeros = lambda n, dt=np.float64: np.zeros((B, n), dtype=dt)
+            flags = HOST_POINTERS
+            status = np.zeros(B, dtype=np.int32)
+        res = {}
+        g = _MpcGradBatch()
+        for i, (k, n) in enumerate(zip(MPC_SEQ, self.seq_len)):
+            if k in want:
+                res[k] = zeros(n)
+                g.base[i], g.stride[i] = _ptr_stride(res[k], n)[:2]
+            else:
+                g.base[i], g.stride[i] = None, 0
+        ab = None
+        if adj:
+            for k, n in zip(("dz", "dl", "dv"), lens):
+                res[k] = zeros(n)
+            ab = var((res["dz"], res["dl"], res["dv"]), False)
+        _check(self._lib, self._lib.fbstab_hip_mpc_adjoint_batch(
+            self._h, B, C.byref(b), C.byref(xb), C.byref(sb), C.c_double(sigma), C.byref(g),
+            C.byref(ab) if ab is not None else None, C.c_void_p(status.data_ptr() if on_dev else status.ctypes.data),
+            flags, C.c_void_p(stream) if stream else None))
+        res["status"] = status
+        return res
 
 
 class FBstabDenseBatch(_SolverBase):

@@ -256,6 +256,52 @@ int fbstab_hip_mpc_refined_steps(fbstab_mpc_handle_t handle, long long* steps);
 int fbstab_hip_mpc_debug_newton(fbstab_mpc_handle_t handle, const fbstab_mpc_batch_t* data,
                                 const fbstab_var_batch_t* x, double* io);
 
+/* ---- derivatives of the solution map (no counterpart in the reference) ------
+ * Gradients dL/d(data) of a loss L of the solutions (z, l, v) of a batch, given the seeds
+ * (gz, gl, gv) = dL/d(z, l, v) at the returned points x.  One launch, one QP per workgroup:
+ * at x = xbar = the point the reference's Newton matrix
+ *   V = [H + sigma I, G', A'; -G, sigma I, 0; -C A, 0, mus]
+ * (RiccatiLinearSolver::Initialize, fbstab/components/riccati_linear_solver.cc:77-210; the
+ * inner residual's Jacobian, full_residual.cc:49-74, C = d phi / d y and mus = d phi / d v
+ * + sigma C of the penalised FB function with options.alpha) is factored once, and one
+ * Solve (:212-344) with the right-hand side (gz, -gl, -C gv) gives (dz, dl, dv).  For the QP
+ * min 1/2 z'Hz + f'z s.t. Gz = h, Az <= b (mpc_data.cc: G = [-I; A B -I; ...], h = -(x0, c),
+ * A = blockdiag([E L]), b = -d) that is f_bar = -dz, h_bar = dl, b_bar = dv,
+ * H_bar = -(dz z' + z dz')/2, G_bar = -(dl z' + l dz'), A_bar = -(dv z' + v dz'), returned per
+ * sequence in the layout of fbstab_mpc_batch_t (Q and R: the gradient of the symmetric part).
+ * This is the derivative of the solution map with V regularised by sigma (a bias of
+ * O(sigma); at a strictly complementary point it tends to the active-set derivative as
+ * sigma -> 0).  sigma <= 0 selects 1e-8, the reference's default sigma0
+ * (fbstab_algorithm-impl.h:34), whatever the handle's options say.
+ *   x:      the points, (z, l, v) (the y slot is not read).
+ *   seed:   (gz, gl, gv); the l and v slots may be NULL (zero).
+ *   grad:   one slot per sequence, strides as in fbstab_mpc_batch_t; a NULL slot is not
+ *           computed.  Every slot that is not NULL is written.
+ *   adj:    NULL, or (dz, dl, dv) (its NULL slots are skipped).
+ *   status: per QP, 0, or 1 where a factorisation failed (its gradients and adj are zero).
+ *           It lives where solve_batch's `out` lives (host for host-pointer calls and with
+ *           FBSTAB_HIP_OUT_ON_HOST, device otherwise).
+ * Flags, streams and validation are those of fbstab_hip_mpc_solve_batch; every QP needs
+ * its own slots in x, seed, grad and adj (stride >= length when batch > 1).  Kernels: the
+ * one-row record instances (<12,4,20>, <12,4,32>: the headline and bounds shapes) run the
+ * adjoint on their own records (fbstab_mpc_r16_adjoint_kernel, in the handle's scratch; the
+ * slots' matrix copies are rebuilt by the next FBSTAB_HIP_KEEP_MATRICES solve); the row-pair
+ * instances (<18,5,10>, <24,8,*>) and the flat-vector kernel's shapes run the flat-vector
+ * adjoint (fbstab_mpc_adjoint_kernel).  On a row-pair handle the first call allocates that
+ * kernel's scratch: MpcLayout::ws_doubles (fb_mpc.h; the iterate vectors and the per-stage
+ * factor record: 58 k doubles = 463 KB at (N, nx, nu, nc) = (30, 18, 5, 10), 101 k at
+ * (30, 24, 8, 16)) per workgroup, times the handle's workgroups, held until destroy and not
+ * counted in fbstab_hip_mpc_query's scratch_bytes.
+ * fbstab_hip_mpc_last_kernel_ms then reports this launch. */
+typedef struct fbstab_mpc_grad_batch_t {
+  double* base[FBSTAB_MPC_NSEQ];
+  long long stride[FBSTAB_MPC_NSEQ];
+} fbstab_mpc_grad_batch_t;
+int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t handle, int batch, const fbstab_mpc_batch_t* data,
+                                 const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                                 const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj,
+                                 int* status, int flags, void* stream);
+
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);
 

@@ -1,0 +1,132 @@
+"""CPU-only checks of the MPC adjoint (fbstab_hip_mpc_adjoint_batch): the export and the argument validation of
+the C-ABI without a GPU, and the flat-vector adjoint of fb_mpc.h compiled single-threaded for the host
+(tests/hostsim/adjoint.cc, against the shim hostsim.cc uses) against the oracle's linear solver."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tools import fixtures as fx
+from tests import helpers as H
+from tests import adjoint_helpers as AH
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOSTSIM = os.path.join(ROOT, "tests", "hostsim")
+_SO = os.path.join(HOSTSIM, "libhostsim_adjoint.so")
+
+
+def _build():
+    src = os.path.join(HOSTSIM, "adjoint.cc")
+    shim = os.path.join(HOSTSIM, "shim")
+    deps = [src, os.path.join(shim, "hip", "hip_runtime.h")] + [
+        os.path.join(ROOT, "fbstab_amd", "csrc", f) for f in ("fb_common.h", "fb_mpc.h")]
+    if os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps):
+        return
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + shim,
+                           "-Wno-attributes", "-Wno-unknown-pragmas", "-o", _SO, src])
+
+
+class HostAdjoint:
+    def __init__(self):
+        _build()
+        self.lib = C.CDLL(_SO)
+        self.lib.hostsim_mpc_adjoint.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7 + [C.c_double, C.c_double,
+                                                                                     C.c_void_p, C.c_void_p]
+
+    def adjoint(self, p, q, x, seeds, sigma=AH.SIGMA, alpha=0.95, want=AH.MPC_SEQ):
+        """Adjoint of QP ``q`` at x = (z, l, v) for seeds (gz, gl, gv) (gl / gv may be None): (status, (dz, dl,
+        dv), gradients)."""
+        keep = [np.ascontiguousarray(p.arrays[k][q]) for k in AH.MPC_SEQ]
+        data = (C.c_void_p * 12)(*[a.ctypes.data for a in keep])
+        lens = p.seq_lengths()
+        grads = {k: np.full(lens[k], np.nan) for k in want}
+        gptr = (C.c_void_p * 12)(*[grads[k].ctypes.data if k in grads else None for k in AH.MPC_SEQ])
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        z, l, v = (f64(t) for t in x)
+        gz, gl, gv = (f64(t) for t in seeds)
+        adj = np.full(p.nz + p.nl + p.nv, np.nan)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        st = self.lib.hostsim_mpc_adjoint(p.N, p.nx, p.nu, p.nc, data, ptr(z), ptr(l), ptr(v), ptr(gz), ptr(gl),
+                                          ptr(gv), sigma, alpha, adj.ctypes.data, gptr)
+        return st, (adj[:p.nz], adj[p.nz:p.nz + p.nl], adj[p.nz + p.nl:]), grads
+
+
+@pytest.fixture(scope="module")
+def host():
+    return HostAdjoint()
+
+
+def _problems(kats):
+    out = [H.mpc_from_kat(k) for k in kats["mpc_end_to_end"]]
+    out.append(fx.synthetic_mpc_batch(6))
+    return out
+
+
+def test_adjoint_residual_and_gradient_table_on_the_host(host, oracle, kats):
+    """The device logic's (dz, dl, dv) leaves no more of V (dz, dl, dv) = (gz, -gl, -C.gv) than 3 x what the
+    oracle's RiccatiLinearSolver leaves (longdouble residuals, at the oracle's solutions and at the origin), and
+    its gradients are the table applied to its own adjoint."""
+    rng = np.random.default_rng(31)
+    checked = 0
+    for p in _problems(kats):
+        sol = oracle.solve_mpc(p)
+        for q in range(p.batch):
+            points = [(sol[0][q], sol[1][q], sol[2][q]), (np.zeros(p.nz), np.zeros(p.nl), np.zeros(p.nv))]
+            for x in points:
+                seeds = tuple(t[0] for t in AH.random_seeds(rng, p, 1))
+                st, step, grads = host.adjoint(p, q, x, seeds)
+                assert st == 0
+                ref = AH.oracle_adjoint(oracle, p, q, x, seeds)
+                r_dev = AH.adjoint_residual(p, q, x, step, seeds)
+                r_orc = AH.adjoint_residual(p, q, x, ref, seeds)
+                assert r_dev <= 3 * r_orc, (q, r_dev, r_orc)
+                scale = max(np.abs(np.concatenate(step)).max(), 1.0)
+                assert np.abs(np.concatenate(step) - np.concatenate(ref)).max() <= 1e-5 * scale  # (forward error: cond(V) ~ 1e11 at sigma = 1e-8)
+                tab = AH.gradient_table(AH.one_qp(p, q), x, step)
+                for k in AH.MPC_SEQ:
+                    np.testing.assert_allclose(grads[k], tab[k], rtol=1e-14, atol=1e-14 * scale, err_msg=k)
+                checked += 1
+    assert checked >= 2 * 7
+
+
+def test_null_seeds_are_zero_and_unwanted_slots_are_not_written(host, oracle):
+    p = fx.synthetic_mpc_batch(1)
+    sol = oracle.solve_mpc(p)
+    x = (sol[0][0], sol[1][0], sol[2][0])
+    gz = np.random.default_rng(2).standard_normal(p.nz)
+    st, a, g = host.adjoint(p, 0, x, (gz, None, None), want=("q", "E"))
+    st0, b, g0 = host.adjoint(p, 0, x, (gz, np.zeros(p.nl), np.zeros(p.nv)), want=("q", "E"))
+    assert st == st0 == 0 and set(g) == {"q", "E"}
+    for s, t in zip(a, b):
+        assert np.array_equal(s, t)
+    assert np.array_equal(g["q"], g0["q"]) and np.array_equal(g["E"], g0["E"])
+
+
+def test_factorisation_failure_gives_status_1_and_zero_gradients(host):
+    """An indefinite stage Hessian (Q = -I) fails the Cholesky factorisation: status 1, every gradient and the
+    adjoint zero."""
+    p = fx.synthetic_mpc_batch(1)
+    nx = p.nx
+    p.arrays["Q"] = np.ascontiguousarray(np.tile(-np.eye(nx).reshape(-1), (1, p.N + 1)))
+    x = (np.zeros(p.nz), np.zeros(p.nl), np.zeros(p.nv))
+    st, step, grads = host.adjoint(p, 0, x, (np.ones(p.nz), np.ones(p.nl), np.ones(p.nv)))
+    assert st == 1
+    for t in step:
+        assert np.array_equal(t, np.zeros_like(t))
+    for k in AH.MPC_SEQ:
+        assert np.array_equal(grads[k], np.zeros_like(grads[k])), k
+
+
+def test_adjoint_entry_point_is_exported_and_validates_without_gpu():
+    from fbstab_amd import hip_api
+    lib = hip_api.load_library()
+    assert "fbstab_hip_mpc_adjoint_batch" in hip_api.EXPORTED_SYMBOLS
+    b, x, s, g = hip_api._MpcBatch(), hip_api._VarBatch(), hip_api._VarBatch(), hip_api._MpcGradBatch()
+    st = np.zeros(1, dtype=np.int32)
+    rc = lib.fbstab_hip_mpc_adjoint_batch(None, 1, C.byref(b), C.byref(x), C.byref(s), 0.0, C.byref(g), None,
+                                          st.ctypes.data, 0, None)
+    assert rc == 1  # FBSTAB_HIP_ERR_ARGUMENT
+    assert b"null solver handle" in lib.fbstab_hip_last_error()
+    assert C.sizeof(hip_api._MpcGradBatch) == C.sizeof(hip_api._MpcBatch) == 12 * 16
