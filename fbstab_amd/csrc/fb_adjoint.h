@@ -93,4 +93,51 @@ FB_DEV void mpc_adjoint_contract(const C& c, int N, int nx, int nu, int nc, cons
     for (long e = c.tid; e < nv; e += C::nt) av[e] = ok ? dv[e] : 0.0;
 }
 
+// ---- dense (fbstab_hip_dense_adjoint_batch) -------------------------------------------------------------
+// The same contraction for the dense data min 1/2 z'Hz + f'z s.t. Gz = h, Az <= b (h and b enter directly):
+//   f: -dz      h: dl      b: dv
+//   H: -(dz z' + z dz')/2 (the gradient of the symmetric part)      G: -(dl z' + l dz')      A: -(dv z' + v dz')
+// column-major like the inputs (H_bar[r + c nz], G_bar[r + c nl], A_bar[r + c nv]).
+// Pointers to one QP's gradients of the six arrays (the order of fbstab_dense_batch_t; nullptr: not wanted).
+struct DenseGrad {
+  double *H, *f, *G, *h, *A, *b;
+};
+
+// out[r + k m] = s (a[r] z[k] + w[r] dz[k]), r < m, k < nz: thread c.tid takes entries c.tid, c.tid + C::nt, ...
+// of the column-major image, so that a wavefront's stores are one contiguous run; (r, k) follow the entry
+// without a division.
+template <class C, class VP>
+FB_DEV void dense_adjoint_outer(const C& c, double* out, int m, int nz, double s, VP a, VP w, VP z, VP dz, bool ok) {
+  if (m <= 0) return;
+  int r = c.tid % m, k = c.tid / m;
+  for (int e = c.tid; e < m * nz; e += C::nt) {
+    out[e] = ok ? s * (a[r] * z[k] + w[r] * dz[k]) : 0.0;
+    r += C::nt;
+    while (r >= m) { r -= m; k++; }
+  }
+}
+
+// Every slot of G that is not null is written; ok = false writes zeros there, and to (az, al, av) where they are
+// not null (which otherwise receive dz, dl, dv).  VP: where the policy keeps its vectors (LDS, or global scratch
+// for DenseLayout::v_global).  The caller synchronises before and after.
+template <class C, class VP>
+FB_DEV void dense_adjoint_contract(const C& c, int nz, int nl, int nv, VP z, VP l, VP v, VP dz, VP dl, VP dv,
+                                   const DenseGrad& G, bool ok, double* az, double* al, double* av) {
+  if (G.H) dense_adjoint_outer(c, G.H, nz, nz, -0.5, dz, z, z, dz, ok);
+  if (G.G) dense_adjoint_outer(c, G.G, nl, nz, -1.0, dl, l, z, dz, ok);
+  if (G.A) dense_adjoint_outer(c, G.A, nv, nz, -1.0, dv, v, z, dz, ok);
+  if (G.f)
+    for (int e = c.tid; e < nz; e += C::nt) G.f[e] = ok ? -dz[e] : 0.0;
+  if (G.h)
+    for (int e = c.tid; e < nl; e += C::nt) G.h[e] = ok ? dl[e] : 0.0;
+  if (G.b)
+    for (int e = c.tid; e < nv; e += C::nt) G.b[e] = ok ? dv[e] : 0.0;
+  if (az)
+    for (int e = c.tid; e < nz; e += C::nt) az[e] = ok ? dz[e] : 0.0;
+  if (al)
+    for (int e = c.tid; e < nl; e += C::nt) al[e] = ok ? dl[e] : 0.0;
+  if (av)
+    for (int e = c.tid; e < nv; e += C::nt) av[e] = ok ? dv[e] : 0.0;
+}
+
 }  // namespace fbk

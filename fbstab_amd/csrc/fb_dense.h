@@ -697,6 +697,23 @@ struct DenseProblem {
     c.sync();
   }
 
+  // dv_i of the adjoint step, in the reference's own order of operations: (rv + gamma (A dz)) / mus
+  // (dense_cholesky_solver.cc:116-121), rv = -C.gv from yb.  The solver's form rv/mus + Gamma (A dz) divides
+  // first; at a solution the active rows have mus ~ sigma, its two terms are ~ |gv| / sigma and cancel to O(1),
+  // which leaves eps |gv| / sigma of rounding error in dv and, through A'dv, in the first block row's residual -
+  // more than the reference leaves there.
+  FB_DEV double dv_as_the_reference(int i, double a, double sigma, double alpha) const {
+    const double ys = y[i] + sigma * (v[i] - vb[i]);
+    double g0, g1;
+    pfb_gradient(ys, v[i], alpha, &g0, &g1);
+    const double mu = g1 + sigma * g0;
+    return (yb[i] + g0 * a) / mu;
+  }
+
+  // ADJ (dense_adjoint below): rvm holds the seed gv on entry, the constraint block's -pfb(ys, v) becomes
+  // -C.gv (kept in yb, which the step does not otherwise read), and dv is formed by dv_as_the_reference; the
+  // solver's instance (ADJ = false) is the step as it always was.
+  template <bool ADJ = false>
   FB_DEV bool newton_step(const C& c, double sigma, double alpha) const {
     FB_WAVE_LAP_DECL;
     const int n = lay.nk;
@@ -707,7 +724,12 @@ struct DenseProblem {
       pfb_gradient(ys, v[i], alpha, &g0, &g1);
       const double mu = g1 + sigma * g0;
       gam[i] = g0 / mu;
-      rvm[i] = -pfb(ys, v[i], alpha) / mu;
+      if constexpr (ADJ) {
+        yb[i] = -(g0 * rvm[i]);  // rv = -C.gv, kept for dv below
+        rvm[i] = yb[i] / mu;
+      } else {
+        rvm[i] = -pfb(ys, v[i], alpha) / mu;  // (-rv)/mus
+      }
     }
     c.sync();
     FB_WAVE_LAP(10);
@@ -848,7 +870,8 @@ struct DenseProblem {
     for (int i = c.tid; i < nv; i += C::nt) {
       const double a = A_row_dot(i, dz);
       adz[i] = a;
-      dv[i] = rvm[i] + gam[i] * a;
+      if constexpr (ADJ) dv[i] = dv_as_the_reference(i, a, sigma, alpha);
+      else dv[i] = rvm[i] + gam[i] * a;
     }
     c.sync();
     // W = (H dz + G'dl + A'dv, -G dz)
@@ -882,5 +905,34 @@ struct DenseProblem {
     }
   }
 };
+
+// ---- reverse-mode derivative of the solution map (fbstab_hip_dense_adjoint_batch) ------------------------
+// At a returned point x = (z, l, v) with xbar = x, the Newton matrix of the step above,
+//   V = [H + sigma I, G', A'; -G, sigma I, 0; -C.A, 0, mus.]   (C = d phi / d y, mus = d phi / d v + sigma C),
+// is what DenseCholeskySolver::Initialize factors (dense_cholesky_solver.cc:32-79).  For seeds (gz, gl, gv) =
+// dL/d(z, l, v) one Solve (:81-127) with the right-hand side (gz, -gl, -C.gv) gives (dz, dl, dv): the step's
+// inner residual holds -R, so rz = -gz, rl = gl; the seed gv goes to rvm, which newton_step<true> reads in
+// place of pfb (and forms dv from in the reference's order of operations).  sigma (z - zb) etc. vanish exactly.
+// P: DenseProblem or DenseWave (fb_dense_wave.h).
+// Returns false iff the factorisation failed.
+template <class P, class C>
+FB_DEV bool dense_adjoint(const P& p, const C& c, double sigma, double alpha, const double* gz, const double* gl,
+                          const double* gv) {
+  p.load_guess(c);  // (z, l, v) <- the point, y = b - A z
+  for (int i = c.tid; i < p.nz; i += C::nt) { p.zb[i] = p.z[i]; p.rz[i] = -gz[i]; }
+  for (int i = c.tid; i < p.nl; i += C::nt) { p.lb[i] = p.l[i]; p.rl[i] = gl ? gl[i] : 0.0; }
+  for (int i = c.tid; i < p.nv; i += C::nt) { p.vb[i] = p.v[i]; p.rvm[i] = gv ? gv[i] : 0.0; }  // (yb: the step's rv)
+  c.sync();
+  return p.template newton_step<true>(c, sigma, alpha);
+}
+
+// theta_bar = -J_theta' w for the dense data: the contraction of fb_adjoint.h from the point and the step where
+// the policy keeps them.
+template <class P, class C>
+FB_DEV void dense_adjoint_gradients(const P& p, const C& c, const DenseGrad& G, bool ok, double* az, double* al,
+                                    double* av) {
+  dense_adjoint_contract(c, p.nz, p.nl, p.nv, p.z, p.l, p.v, p.dz, p.dl, p.dv, G, ok, az, al, av);
+  c.sync();
+}
 
 }  // namespace fbk

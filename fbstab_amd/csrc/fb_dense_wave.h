@@ -879,6 +879,29 @@ struct DenseWave {
     return x;
   }
 
+  // dv_i from (A dz)_i = a.  The solver: rv/mus + Gamma a.  The adjoint: (rv + gamma a) / mus with rv = -C.gv
+  // from yb, the reference's own order of operations (dense_cholesky_solver.cc:116-121) - at a solution the
+  // solver's two terms are ~ |gv| / sigma on the active rows and cancel to O(1), which would leave
+  // eps |gv| / sigma of rounding error in dv (see DenseProblem::dv_as_the_reference, fb_dense.h).
+  template <bool ADJ>
+  FB_DEV double dv_of(int i, double a, double sigma, double alpha) const {
+    if constexpr (ADJ) {
+      const double ys = y[i] + sigma * (v[i] - vb[i]);
+      double g0, g1;
+      pfb_gradient(ys, v[i], alpha, &g0, &g1);
+      const double mu = g1 + sigma * g0;
+      return (yb[i] + g0 * a) / mu;
+    } else {
+      return rvm[i] + gam[i] * a;
+    }
+  }
+
+  // ADJ (dense_adjoint, fb_dense.h): rvm holds the seed gv on entry and the constraint block's -pfb(ys, v)
+  // becomes -C.gv (kept in yb for dv_of); the step then always factors by the pivoted rule (factor + substitute),
+  // whatever `order` says, and leaves the nfallback counters alone - at a solution the active rows carry
+  // Gamma ~ 1 / sigma, the case AUTO hands to the pivoted path anyway, and a gradient must not depend on a speed
+  // option.  The solver's instance (ADJ = false) is the step as it always was.
+  template <bool ADJ = false>
   FB_DEV bool newton_step(const C& c, double sigma, double alpha) const {
     FB_WAVE_LAP_DECL;
     int t = c.tid;
@@ -899,12 +922,19 @@ struct DenseWave {
         const double mu = g1 + sigma * g0;
         const double g = g0 / mu;
         gam[i] = g;
-        rvm[i] = -pfb(ys, v[i], alpha) / mu;
+        if constexpr (ADJ) {
+          yb[i] = -(g0 * rvm[i]);  // rv = -C.gv, kept for dv below
+          rvm[i] = yb[i] / mu;
+        } else {
+          rvm[i] = -pfb(ys, v[i], alpha) / mu;  // (-rv)/mus
+        }
         act = g * sigma > act_thr;
       }
       nact += __popcll(__ballot(act));
     }
-    if (lay.order == 0 && lay.act_bits > 0 && nact + nl >= nz) went_pivoted = true;
+    if constexpr (!ADJ) {
+      if (lay.order == 0 && lay.act_bits > 0 && nact + nl >= nz) went_pivoted = true;
+    }
     c.sync();
     FB_WAVE_LAP(10);
     double Kr[64], dg, atr;
@@ -917,7 +947,7 @@ struct DenseWave {
     FB_WAVE_LAP(11);
 #if FB_DW_STATIC_ORDER
     bool solved = false;
-    {
+    if constexpr (!ADJ) {
       // (a NaN on the diagonal - an overflowed iterate - goes straight to the pivoted
       // path, which answers it the way Eigen does)
       const double x0 = x;
@@ -1002,13 +1032,13 @@ struct DenseWave {
         if (k0 + 20 < nz) load_chunk(k0 + 20, ca);
         if (k0 + 10 < nz) use_chunk(k0 + 10, cb);
       }
-      if (r0) { adz[t] = s0; dv[t] = rvm[t] + gam[t] * s0; }
-      if (r1) { adz[t + 64] = s1; dv[t + 64] = rvm[t + 64] + gam[t + 64] * s1; }
+      if (r0) { adz[t] = s0; dv[t] = dv_of<ADJ>(t, s0, sigma, alpha); }
+      if (r1) { adz[t + 64] = s1; dv[t + 64] = dv_of<ADJ>(t + 64, s1, sigma, alpha); }
     } else {
       for (int i = t; i < nv; i += 64) {
         const double a = A_row_dot(i, dz);
         adz[i] = a;
-        dv[i] = rvm[i] + gam[i] * a;
+        dv[i] = dv_of<ADJ>(i, a, sigma, alpha);
       }
 #if !FB_DW_W_FROM_THE_SYSTEM
       if (t < nz) hdz = row_dot(D.H, nz, nz, t, dz);

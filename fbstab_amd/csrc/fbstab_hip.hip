@@ -360,6 +360,96 @@ __global__ __launch_bounds__(64, FB_DW_MIN_WAVES) void fbstab_dense_wave_kernel(
   }
 }
 
+// The adjoint of fbstab_hip_dense_adjoint_batch (fb_dense.h: dense_adjoint, dense_adjoint_gradients; the
+// contraction of fb_adjoint.h), one QP per workgroup pulled from the queue like the solve.  `x`: the point
+// (z, l, v); `seed`: (gz, gl, gv), null l / v slots meaning zero; `adj`: null slots, or (dz, dl, dv).
+struct DenseGradArgs {
+  double* base[FBSTAB_DENSE_NARR];
+  long long stride[FBSTAB_DENSE_NARR];
+};
+__device__ __forceinline__ DenseData dense_data_of(const DenseBatchArgs& data, long q) {
+  DenseData D;
+  D.H = data.base[FBSTAB_DENSE_H] + q * data.stride[FBSTAB_DENSE_H];
+  D.f = data.base[FBSTAB_DENSE_f] + q * data.stride[FBSTAB_DENSE_f];
+  D.G = data.base[FBSTAB_DENSE_G] + q * data.stride[FBSTAB_DENSE_G];
+  D.h = data.base[FBSTAB_DENSE_h] + q * data.stride[FBSTAB_DENSE_h];
+  D.A = data.base[FBSTAB_DENSE_A] + q * data.stride[FBSTAB_DENSE_A];
+  D.b = data.base[FBSTAB_DENSE_b] + q * data.stride[FBSTAB_DENSE_b];
+  return D;
+}
+__device__ __forceinline__ DenseGrad dense_grad_of(const DenseGradArgs& grad, long q) {
+  auto at = [q](double* b, long long s) { return b ? b + q * s : nullptr; };
+  DenseGrad G;
+  G.H = at(grad.base[FBSTAB_DENSE_H], grad.stride[FBSTAB_DENSE_H]);
+  G.f = at(grad.base[FBSTAB_DENSE_f], grad.stride[FBSTAB_DENSE_f]);
+  G.G = at(grad.base[FBSTAB_DENSE_G], grad.stride[FBSTAB_DENSE_G]);
+  G.h = at(grad.base[FBSTAB_DENSE_h], grad.stride[FBSTAB_DENSE_h]);
+  G.A = at(grad.base[FBSTAB_DENSE_A], grad.stride[FBSTAB_DENSE_A]);
+  G.b = at(grad.base[FBSTAB_DENSE_b], grad.stride[FBSTAB_DENSE_b]);
+  return G;
+}
+
+// The four-wavefront policy (fb_dense.h), the instances of fbstab_dense_kernel: K in LDS, K in global scratch
+// (KGLOBAL), the iterate vectors there too (VGLOBAL), and NT = 64.  Its factorisation always pivots.
+template <int NT, bool KGLOBAL = false, bool VGLOBAL = false>
+__global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_adjoint_kernel(
+    DenseLayout lay, DenseBatchArgs data, VarBatchArgs x, VarBatchArgs seed, DenseGradArgs grad, VarBatchArgs adj,
+    int* status, double sigma, double alpha, int* counter, int batch, KScratchArg<KGLOBAL> kscratch) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  lds_ptr lds = (lds_ptr)smem;
+  typedef Ctx<NT> C;
+  C ctx;
+  ctx.tid = threadIdx.x;
+  ctx.red = lds + lay.o_red;
+  for (;;) {
+    const int q = next_qp<NT>(counter, lds + lay.o_slot);
+    if (q >= batch) break;
+    DenseProblem<C, KGLOBAL, VGLOBAL> p;
+    double* ks = nullptr;
+    if constexpr (KGLOBAL) ks = kscratch.get() + (long)blockIdx.x * (lay.k_doubles + lay.v_doubles);
+    p.bind(lay, dense_data_of(data, q), x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
+           x.base[2] + q * x.stride[2], nullptr, lds, ks);
+    auto at = [q](double* b, long long s) { return b ? b + q * s : nullptr; };
+    const bool ok = dense_adjoint(p, ctx, sigma, alpha, seed.base[0] + q * seed.stride[0],
+                                  at(seed.base[1], seed.stride[1]), at(seed.base[2], seed.stride[2]));
+    ctx.sync();
+    dense_adjoint_gradients(p, ctx, dense_grad_of(grad, q), ok, at(adj.base[0], adj.stride[0]),
+                            at(adj.base[1], adj.stride[1]), at(adj.base[2], adj.stride[2]));
+    if (ctx.tid == 0) status[q] = ok ? 0 : 1;
+    ctx.sync();
+  }
+}
+
+// The one-wavefront policy (fb_dense_wave.h; nz + nl <= 64): K in registers, A'Gamma A on the matrix cores, the
+// handle's own scratch region per workgroup.  newton_step<true> factors by the pivoted rule whatever the handle's
+// order, and the fallback counters of the last solve are neither passed nor reset.
+__global__ __launch_bounds__(64, FB_DW_MIN_WAVES) void fbstab_dense_wave_adjoint_kernel(
+    DenseWaveLayout lay, DenseBatchArgs data, VarBatchArgs x, VarBatchArgs seed, DenseGradArgs grad, VarBatchArgs adj,
+    int* status, double sigma, double alpha, int* counter, int batch, double* scratch) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  lds_ptr lds = (lds_ptr)smem;
+  typedef DenseWave::C C;
+  C ctx;
+  ctx.tid = threadIdx.x;
+  ctx.red = lds;  // (unused: one wavefront reduces in registers)
+  double* ws = scratch + (long)blockIdx.x * lay.ws_doubles;
+  for (;;) {
+    const int q = next_qp<64>(counter, lds);
+    if (q >= batch) break;
+    DenseWave p;
+    p.bind(lay, dense_data_of(data, q), x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
+           x.base[2] + q * x.stride[2], nullptr, lds, ws, nullptr);
+    auto at = [q](double* b, long long s) { return b ? b + q * s : nullptr; };
+    const bool ok = dense_adjoint(p, ctx, sigma, alpha, seed.base[0] + q * seed.stride[0],
+                                  at(seed.base[1], seed.stride[1]), at(seed.base[2], seed.stride[2]));
+    ctx.sync();
+    dense_adjoint_gradients(p, ctx, dense_grad_of(grad, q), ok, at(adj.base[0], adj.stride[0]),
+                            at(adj.base[1], adj.stride[1]), at(adj.base[2], adj.stride[2]));
+    if (ctx.tid == 0) status[q] = ok ? 0 : 1;
+    ctx.sync();
+  }
+}
+
 // ---------------------------------------------------------------------------
 thread_local std::string g_error;
 
@@ -627,6 +717,7 @@ struct fbstab_dense_solver : SolverBase {
   // kernel batches of nz + nl <= 64 run on; `lay` then only serves the traced solve
   bool wave = false;
   fbk::DenseWaveLayout wlay;
+  bool adj_ready = false;  // fbstab_hip_dense_adjoint_batch: the LDS attribute of its kernel, set once
 };
 
 extern "C" {
@@ -1625,6 +1716,160 @@ int fbstab_hip_dense_debug_newton(fbstab_dense_handle_t h, const fbstab_dense_ba
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(io, d_io, sizeof(double) * n_io, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  return FBSTAB_HIP_OK;
+}
+
+// Reverse-mode derivative of the dense solution map at returned points (include/fbstab_hip.h).  One launch of the
+// adjoint kernel that matches the handle's solve kernel: the Newton matrix of DenseCholeskySolver::Initialize at
+// x = xbar = the point (dense_cholesky_solver.cc:32-79), one Solve (:81-127) with the adjoint's right-hand side,
+// one contraction.
+int fbstab_hip_dense_adjoint_batch(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
+                                   const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                                   const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
+                                   int flags, void* stream) {
+  // what needs no handle comes first: the argument blocks, the one seed that is required, and strides that no
+  // handle accepts (nz and nv are positive: z, v, H, f, A, b are never empty)
+  if (!data || !x || !seed || !grad || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
+  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null seed pointer (z)");
+  if (batch > 1) {
+    for (int i = 0; i < 3; i += 2) {
+      if (x->stride[i] < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
+      if (seed->base[i] && seed->stride[i] < 1)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "seed stride smaller than the vector length");
+      if (adj && adj->base[i] && adj->stride[i] < 1)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
+    }
+    for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b})
+      if (grad->base[i] && grad->stride[i] < 1)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
+  }
+  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  for (int i = 0; i < FBSTAB_DENSE_NARR; i++)
+    if (!data->base[i] && h->arr_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
+  for (int i = 0; i < 3; i++)
+    if (!x->base[i] && h->var_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
+  // strides: every QP its own slot (a gradient or adjoint shared by the batch would be written by all of them)
+  for (int i = 0; i < 3; i++) {
+    if (batch > 1 && x->stride[i] < h->var_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
+    if (batch > 1 && seed->base[i] && seed->stride[i] < h->var_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "seed stride smaller than the vector length");
+    if (batch > 1 && adj && adj->base[i] && adj->stride[i] < h->var_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
+  }
+  for (int i = 0; i < FBSTAB_DENSE_NARR; i++)
+    if (batch > 1 && grad->base[i] && grad->stride[i] < h->arr_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
+  if (batch == 0) return FBSTAB_HIP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
+  const bool status_host = !dev_ptrs || (flags & FBSTAB_HIP_OUT_ON_HOST);
+  const long long* vlen = h->var_len;
+  DenseBatchArgs a;
+  VarBatchArgs v, sd, ad;
+  DenseGradArgs g;
+  for (int i = 0; i < 4; i++) { v.base[i] = sd.base[i] = ad.base[i] = nullptr; v.stride[i] = sd.stride[i] = ad.stride[i] = 0; }
+  DevBuf d_seed[3], d_adj[3], d_grad[FBSTAB_DENSE_NARR], d_status;
+  if (dev_ptrs) {
+    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) { a.base[i] = data->base[i]; a.stride[i] = data->stride[i]; }
+    for (int i = 0; i < 3; i++) {
+      v.base[i] = x->base[i]; v.stride[i] = x->stride[i];
+      if (vlen[i] > 0) { sd.base[i] = seed->base[i]; sd.stride[i] = seed->stride[i]; }
+      if (adj && vlen[i] > 0) { ad.base[i] = adj->base[i]; ad.stride[i] = adj->stride[i]; }
+    }
+    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
+      g.base[i] = h->arr_len[i] > 0 ? grad->base[i] : nullptr;  // (nl == 0: the G and h slots are ignored)
+      g.stride[i] = grad->stride[i];
+    }
+  } else {
+    rc = h->ensure_staging();
+    if (rc != FBSTAB_HIP_OK) return rc;
+    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
+      if (data->stride[i] != 0 && data->stride[i] < h->arr_len[i] && batch > 1)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
+      rc = h->upload(data->base[i], data->stride[i], h->arr_len[i], batch, h->d_arr[i], &a.stride[i], s);
+      if (rc != FBSTAB_HIP_OK) return rc;
+      a.base[i] = h->d_arr[i];
+    }
+    for (int i = 0; i < 3; i++) {
+      long long st;
+      rc = h->upload(x->base[i], x->stride[i] ? x->stride[i] : vlen[i], vlen[i], batch, h->d_var[i], &st, s);
+      if (rc != FBSTAB_HIP_OK) return rc;
+      v.base[i] = h->d_var[i]; v.stride[i] = vlen[i];
+      if (seed->base[i] && vlen[i] > 0) {
+        HIP_TRY(hipMalloc(&d_seed[i].p, sizeof(double) * (size_t)vlen[i] * batch));
+        sd.base[i] = static_cast<double*>(d_seed[i].p);
+        rc = h->upload(seed->base[i], seed->stride[i] ? seed->stride[i] : vlen[i], vlen[i], batch, sd.base[i], &st, s);
+        if (rc != FBSTAB_HIP_OK) return rc;
+        sd.stride[i] = vlen[i];
+      }
+      if (adj && adj->base[i] && vlen[i] > 0) {
+        HIP_TRY(hipMalloc(&d_adj[i].p, sizeof(double) * (size_t)vlen[i] * batch));
+        ad.base[i] = static_cast<double*>(d_adj[i].p); ad.stride[i] = vlen[i];
+      }
+    }
+    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
+      g.base[i] = nullptr; g.stride[i] = 0;
+      if (grad->base[i] && h->arr_len[i] > 0) {
+        HIP_TRY(hipMalloc(&d_grad[i].p, sizeof(double) * (size_t)h->arr_len[i] * batch));
+        g.base[i] = static_cast<double*>(d_grad[i].p); g.stride[i] = h->arr_len[i];
+      }
+    }
+  }
+  int* d_st = status;
+  if (status_host) {
+    HIP_TRY(hipMalloc(&d_status.p, sizeof(int) * (size_t)batch));
+    d_st = static_cast<int*>(d_status.p);
+  }
+  double sig = sigma > 0.0 ? sigma : 1e-8;  // the reference's default sigma0 (fbstab_algorithm-impl.h:34)
+  double alpha = h->opts.alpha;
+  // the queue word alone: the words from kDenseFallbackSlot on still describe the last solve
+  // (fbstab_hip_dense_get_factorisation)
+  HIP_TRY(hipMemsetAsync(h->counter, 0, sizeof(int) * kDenseFallbackSlot, s));
+  const int grid = h->workgroups < batch ? h->workgroups : batch;
+  const void* kern;
+  if (h->wave) kern = reinterpret_cast<const void*>(fbstab_dense_wave_adjoint_kernel);
+  else if (h->threads == 64) kern = reinterpret_cast<const void*>(fbstab_dense_adjoint_kernel<64>);
+  else if (h->lay.v_global) kern = reinterpret_cast<const void*>(fbstab_dense_adjoint_kernel<kDenseThreads, true, true>);
+  else if (h->lay.k_global) kern = reinterpret_cast<const void*>(fbstab_dense_adjoint_kernel<kDenseThreads, true>);
+  else kern = reinterpret_cast<const void*>(fbstab_dense_adjoint_kernel<kDenseThreads>);
+  if (!h->adj_ready) {
+    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
+    h->adj_ready = true;
+  }
+  HIP_TRY(hipEventRecord(h->ev0, s));
+  if (h->wave) {
+    void* args[] = {&h->wlay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch, &h->scratch};
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)h->lds_bytes, s));
+  } else if (h->lay.k_global) {
+    KScratchArg<true> ks{h->scratch};
+    void* args[] = {&h->lay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch, &ks};
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(h->threads), args, (size_t)h->lds_bytes, s));
+  } else {
+    KScratchArg<false> ks;
+    void* args[] = {&h->lay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch, &ks};
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(h->threads), args, (size_t)h->lds_bytes, s));
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(h->ev1, s));
+  h->timed = true;
+  if (!dev_ptrs) {
+    for (int i = 0; i < FBSTAB_DENSE_NARR; i++)
+      if (g.base[i]) {
+        rc = h->download(grad->base[i], grad->stride[i] ? grad->stride[i] : h->arr_len[i], h->arr_len[i], batch,
+                         g.base[i], s);
+        if (rc != FBSTAB_HIP_OK) return rc;
+      }
+    for (int i = 0; i < 3; i++)
+      if (ad.base[i]) {
+        rc = h->download(adj->base[i], adj->stride[i] ? adj->stride[i] : vlen[i], vlen[i], batch, ad.base[i], s);
+        if (rc != FBSTAB_HIP_OK) return rc;
+      }
+  }
+  if (status_host) HIP_TRY(hipMemcpyAsync(status, d_st, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
+  if (status_host || !(flags & FBSTAB_HIP_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
   return FBSTAB_HIP_OK;
 }
 

@@ -85,6 +85,10 @@ class _MpcGradBatch(C.Structure):
     _fields_ = [("base", C.c_void_p * 12), ("stride", C.c_longlong * 12)]
 
 
+class _DenseGradBatch(C.Structure):
+    _fields_ = [("base", C.c_void_p * 6), ("stride", C.c_longlong * 6)]
+
+
 class _Plant(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("stride_A", C.c_longlong), ("stride_B", C.c_longlong)]
 
@@ -155,6 +159,10 @@ def load_library() -> C.CDLL:
         lib.fbstab_hip_mpc_adjoint_batch.argtypes = [
             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(lib, "fbstab_hip_dense_adjoint_batch"):  # (absent from a build of an earlier round loaded for an A/B)
+        lib.fbstab_hip_dense_adjoint_batch.argtypes = [
+            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_int, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -187,7 +195,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_debug_newton", "fbstab_hip_mpc_adjoint_batch", "fbstab_hip_debug_stamps",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",
-    "fbstab_hip_dense_solve_traced",
+    "fbstab_hip_dense_solve_traced", "fbstab_hip_dense_adjoint_batch",
     "fbstab_hip_dense_debug_newton", "fbstab_hip_dense_last_kernel_ms", "fbstab_hip_dense_query",
     "fbstab_hip_dense_set_factorisation", "fbstab_hip_dense_get_factorisation",
     "fbstab_hip_shard_group_create", "fbstab_hip_shard_group_destroy", "fbstab_hip_shard_group_stats",
@@ -642,6 +650,80 @@ class FBstabDenseBatch(_SolverBase):
         display returned as records (fbstab_hip_dense_solve_traced)."""
         return _solve_traced(self, _DenseBatch(), DENSE_ARR, self.arr_len, data,
                              (self.nz, self.nl, self.nv, self.nv), z, l, v, y, capacity)
+
+    def Adjoint(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0,
+                want: Optional[Sequence[str]] = None, adj: bool = False, stream: int = 0,
+                async_: bool = False) -> Dict[str, object]:
+        """Reverse-mode derivative of the dense solution map (fbstab_hip_dense_adjoint_batch): for a loss L with
+        seeds ``gz, gl, gv`` = dL/d(z, l, v) at the returned point ``(z, l, v)`` (``(batch, n)`` arrays, all numpy
+        or all torch CUDA tensors, like ``Solve``), returns a dict with dL/d(array) for every name of ``want``
+        (default: all six of DENSE_ARR, each ``(batch, len)``, the matrices column-major like the inputs),
+        ``"status"`` (``(batch,)`` int32: 0, or 1 where the factorisation failed and the gradients are zero) and,
+        with ``adj=True``, ``"dz", "dl", "dv"``.  ``gl``/``gv`` None: zero seeds.  ``sigma <= 0``: 1e-8.  With
+        ``nl == 0`` the G, h and l arrays are ``(batch, 0)`` (or None on input)."""
+        want = tuple(DENSE_ARR if want is None else want)
+        unknown = set(want) - set(DENSE_ARR)
+        assert not unknown, unknown
+        b = _DenseBatch()
+        dev_flags = []
+        B = z.shape[0]
+        for i, (k, n) in enumerate(zip(DENSE_ARR, self.arr_len)):
+            if n == 0:
+                b.base[i], b.stride[i] = None, 0
+                continue
+            p, st, d = _ptr_stride(data[k], n)
+            assert data[k].shape[0] == B
+            b.base[i], b.stride[i] = p, st
+            dev_flags.append(d)
+        lens = (self.nz, self.nl, self.nv)
+
+        def var(arrs, allow_none):
+            vb = _VarBatch()
+            for i, (a, n) in enumerate(zip(arrs, lens)):
+                if a is None or n == 0:
+                    assert n == 0 or (allow_none and i > 0), "z, l, v and gz are required"
+                    vb.base[i], vb.stride[i] = None, 0
+                    continue
+                p, st, d = _ptr_stride(a, n)
+                assert a.shape[0] == B
+                vb.base[i], vb.stride[i] = p, st
+                dev_flags.append(d)
+            return vb
+
+        xb = var((z, l, v), False)
+        sb = var((gz, gl, gv), True)
+        on_dev = all(dev_flags)
+        assert on_dev or not any(dev_flags), "mix of host and device arrays"
+        if on_dev:
+            import torch
+            zeros = lambda n, dt=torch.float64: torch.zeros((B, n), dtype=dt, device=z.device)
+            if not stream:
+                stream = torch.cuda.current_stream(z.device).cuda_stream
+            flags = DEVICE_POINTERS | (ASYNC if async_ else 0)
+            status = torch.zeros(B, dtype=torch.int32, device=z.device)
+        else:
+            zeros = lambda n, dt=np.float64: np.zeros((B, n), dtype=dt)
+            flags = HOST_POINTERS
+            status = np.zeros(B, dtype=np.int32)
+        res = {}
+        g = _DenseGradBatch()
+        for i, (k, n) in enumerate(zip(DENSE_ARR, self.arr_len)):
+            g.base[i], g.stride[i] = None, 0
+            if k in want:
+                res[k] = zeros(n)
+                if n > 0:
+                    g.base[i], g.stride[i] = _ptr_stride(res[k], n)[:2]
+        ab = None
+        if adj:
+            for k, n in zip(("dz", "dl", "dv"), lens):
+                res[k] = zeros(n)
+            ab = var((res["dz"], res["dl"], res["dv"]), False)
+        _check(self._lib, self._lib.fbstab_hip_dense_adjoint_batch(
+            self._h, B, C.byref(b), C.byref(xb), C.byref(sb), C.c_double(sigma), C.byref(g),
+            C.byref(ab) if ab is not None else None, C.c_void_p(status.data_ptr() if on_dev else status.ctypes.data),
+            flags, C.c_void_p(stream) if stream else None))
+        res["status"] = status
+        return res
 
 
 class ShardGroup:

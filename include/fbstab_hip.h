@@ -409,6 +409,50 @@ int fbstab_hip_dense_solve_batch_sharded(fbstab_shard_group_t group, const fbsta
  * [dz, dl, dv, A*dz, W_z, W_l, r_z, r_l, ok] out. */
 int fbstab_hip_dense_debug_newton(fbstab_dense_handle_t handle, const fbstab_dense_batch_t* data,
                                   const fbstab_var_batch_t* x, double* io);
+/* Derivatives of the dense solution map: fbstab_hip_mpc_adjoint_batch for FBstabDense's QP
+ *   min 1/2 z'Hz + f'z  s.t. Gz = h, Az <= b
+ * (the OptNet-style QP layer).  At x = xbar = the returned point the Newton matrix of
+ * DenseCholeskySolver::Initialize (fbstab/components/dense_cholesky_solver.cc:32-79),
+ *   V = [H + sigma I, G', A'; -G, sigma I, 0; -C A, 0, mus],
+ * C = d phi / d y and mus = d phi / d v + sigma C of the penalised FB function with options.alpha,
+ * is factored once, and one Solve (:81-127) with the right-hand side (gz, -gl, -C gv) gives
+ * (dz, dl, dv).  The gradients of the six arrays of fbstab_dense_batch_t are
+ *   f_bar = -dz        h_bar = dl        b_bar = dv
+ *   H_bar = -(dz z' + z dz')/2   (the gradient of the symmetric part, as for Q and R)
+ *   G_bar = -(dl z' + l dz')     A_bar = -(dv z' + v dz')
+ * column-major like the inputs: H_bar[r + c nz], G_bar[r + c nl], A_bar[r + c nv].  (h and b enter
+ * the dense data directly, not negated as in the MPC mapping.)  sigma <= 0 selects 1e-8 whatever
+ * the handle's options say.
+ *   x:      the points, (z, l, v) (the y slot is not read).
+ *   seed:   (gz, gl, gv); the l and v slots may be NULL (zero).
+ *   grad:   one slot per array, strides as in fbstab_dense_batch_t; a NULL slot is not computed.
+ *           Every slot that is not NULL is written.
+ *   adj:    NULL, or (dz, dl, dv) (its NULL slots are skipped).
+ *   status: per QP, 0, or 1 where the factorisation failed (its gradients and adj are zero).  It
+ *           lives where solve_batch's `out` lives (host for host-pointer calls and with
+ *           FBSTAB_HIP_OUT_ON_HOST, device otherwise).
+ * Flags, streams, host staging and validation are those of fbstab_hip_dense_solve_batch; every QP
+ * needs its own slots in x, seed, grad and adj (with batch > 1 a stride below the vector or array
+ * length is FBSTAB_HIP_ERR_ARGUMENT).  Handles with nl == 0 ignore the G and h slots (and the l
+ * slots of x, seed and adj).  batch == 0 returns OK.  All validation runs before any device call;
+ * what needs no handle is checked first - the argument blocks, the z seed, and strides below 1 on
+ * the slots that are never empty (z, v; H, f, A, b) - then the handle and the lengths it knows.
+ * Kernels: one per solve kernel.  Handles with nz + nl <= 64 run fbstab_dense_wave_adjoint_kernel
+ * (one wavefront per QP, K in registers, the handle's own scratch); it ALWAYS factors by the pivoted
+ * rule, whatever fbstab_hip_dense_set_factorisation says - at a solution the active rows carry
+ * Gamma ~ 1 / sigma, the case AUTO hands to the pivoted path anyway, and a gradient should not
+ * depend on a speed option - and leaves fbstab_hip_dense_get_factorisation's pivoted_steps
+ * describing the last SOLVE.  The other handles run fbstab_dense_adjoint_kernel<NT, KGLOBAL,
+ * VGLOBAL>, the instance that matches their solve kernel.
+ * fbstab_hip_dense_last_kernel_ms then reports this launch. */
+typedef struct fbstab_dense_grad_batch_t {
+  double* base[FBSTAB_DENSE_NARR];
+  long long stride[FBSTAB_DENSE_NARR];
+} fbstab_dense_grad_batch_t;
+int fbstab_hip_dense_adjoint_batch(fbstab_dense_handle_t handle, int batch, const fbstab_dense_batch_t* data,
+                                   const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                                   const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj,
+                                   int* status, int flags, void* stream);
 double fbstab_hip_dense_last_kernel_ms(fbstab_dense_handle_t handle);
 int fbstab_hip_dense_query(fbstab_dense_handle_t handle, long long* scratch_bytes,
                            int* lds_bytes, int* workgroups, int* threads);
