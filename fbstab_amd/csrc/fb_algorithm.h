@@ -27,12 +27,9 @@
 
 #include "fb_common.h"
 
-// Step lengths evaluated per line-search pass (build knob).
-#ifndef FB_LS_KT
-#define FB_LS_KT 4
-#endif
-
 namespace fbk {
+
+constexpr int kLineSearchTrials = 4;  // step lengths evaluated per line-search pass
 
 // TRACE: the kernel instance behind fbstab_hip_*_solve_traced.  It records the
 // numbers of every display line of the reference (PrintIterLine,
@@ -67,12 +64,6 @@ template <class P, class = void>
 struct can_refine_of : std::false_type {};
 template <class P>
 struct can_refine_of<P, typename std::enable_if<P::kCanRefine>::type> : std::true_type {};
-
-// policies that pack a QP as a cooperative pass (P::kCoopLoad, P::load_guess_coop)
-template <class P, class = void>
-struct coop_load_of : std::false_type {};
-template <class P>
-struct coop_load_of<P, typename std::enable_if<P::kCoopLoad>::type> : std::true_type {};
 
 template <class P, class C, bool TRACE = false>
 struct Solver : TraceState<TRACE> {
@@ -412,7 +403,7 @@ struct Solver : TraceState<TRACE> {
       double t = 1.0;
       double Et = sqrt(ti2), Eot = sqrt(to2);
       bool known = true;  // (Et, Eot) belong to the current t
-      constexpr int KT = FB_LS_KT;
+      constexpr int KT = kLineSearchTrials;
       double Em[KT], Eom[KT];
       int have = 0, used = 0;  // batch of trial norms for t, t*beta, ...
       for (int j = 0; j < o.max_linesearch_iters; j++) {
@@ -502,7 +493,7 @@ struct Solver : TraceState<TRACE> {
     // waits here until no row of the wavefront stands before a Newton step, and the
     // waiting rows then fetch together: their passes over a fresh QP run side by side
     // again instead of one row at a time.
-    // kWantOpen / kWantClose (policies with P::kCoopProx): the row asks for its open_prox /
+    // kWantOpen / kWantClose (kCoop): the row asks for its open_prox /
     // close_subproblem pass and yields; the wavefront runs the pass for it with ALL its rows
     // (below) and the row goes on at kAfterOpen / kAfterClose.
     enum { kFetch = 0, kProxTop = 1, kInnerTop = 2, kEpilogue = 3, kNewton = 4, kDone = 5, kPause = 6,
@@ -518,12 +509,12 @@ struct Solver : TraceState<TRACE> {
     double merit[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     int newton = 0, prox = 0, k = 0, inner_i = 0;
     [[maybe_unused]] bool fetch_now = true;  // (align_rows) the wavefront has just released its waiting rows
-    // line-search trial passes run by all rows of the wavefront for one of them at a time
-    constexpr bool kCoop = P::kCoopTrials && !Queue::kCanAlignRows;
-    constexpr bool kCoopP = kCoop && P::kCoopProx;
-    constexpr bool kCoopL = kCoopP && coop_load_of<P>::value;  // load_guess as a cooperative pass too
-    [[maybe_unused]] bool fresh = false;   // (kCoopP) the open_prox asked for is the first of its QP
-    [[maybe_unused]] int feas_c = kFeasible;  // (kCoopP) verdict of the close pass served last
+    // line-search trial passes and the proximal-level passes run by all rows of the wavefront for one of them
+    // at a time
+    constexpr bool kCoop = !Queue::kCanAlignRows;
+    constexpr bool kCoopL = kCoop && P::kCoopLoad;  // load_guess (P::load_guess_coop) as a cooperative pass too
+    [[maybe_unused]] bool fresh = false;   // (kCoop) the open_prox asked for is the first of its QP
+    [[maybe_unused]] int feas_c = kFeasible;  // (kCoop) verdict of the close pass served last
     for (;;) {
       while (phase != kNewton && phase != kDone && phase != kPause && phase != kWantOpen && phase != kWantClose &&
              phase != kWantLoad) {
@@ -549,7 +540,7 @@ struct Solver : TraceState<TRACE> {
           p.load_guess(c);
           p.choose_costate_form(sigma);
           dx_norm = sqrt((double)p.num_primal_dual());
-          if constexpr (kCoopP) {
+          if constexpr (kCoop) {
             fresh = true;
             phase = kWantOpen;
             continue;
@@ -574,7 +565,7 @@ struct Solver : TraceState<TRACE> {
           fresh = true;
           phase = kWantOpen;
         } else if (phase == kAfterOpen) {
-          // (kCoopP) the wavefront has run this row's open_prox pass: Ek, Ei0 are in
+          // (kCoop) the wavefront has run this row's open_prox pass: Ek, Ei0 are in
           if (fresh) {
             fresh = false;
             E0 = Ek;
@@ -637,7 +628,7 @@ struct Solver : TraceState<TRACE> {
           // kEpilogue: subproblem epilogue (impl:301-303) and the rest of the
           // proximal iteration (impl:186-216)
           int feas = kFeasible;
-          if constexpr (kCoopP) {
+          if constexpr (kCoop) {
             if (phase == kEpilogue) {
               phase = kWantClose;
               continue;
@@ -676,7 +667,7 @@ struct Solver : TraceState<TRACE> {
           }
           prox++;
           k++;
-          if constexpr (kCoopP) {
+          if constexpr (kCoop) {
             phase = kWantOpen;
             continue;
           }
@@ -684,7 +675,7 @@ struct Solver : TraceState<TRACE> {
           phase = kProxTop;
         }
       }
-      if constexpr (kCoopP) {
+      if constexpr (kCoop) {
         // ---- the proximal-level passes the rows have asked for, each run by ALL rows of the
         // wavefront for one of them (P::close_subproblem_coop / open_prox_coop); the rows that
         // stand before a Newton step wait for them - with their lanes at work
@@ -787,7 +778,7 @@ struct Solver : TraceState<TRACE> {
             }
           }
         }
-        constexpr int KT = FB_LS_KT;
+        constexpr int KT = kLineSearchTrials;
         for (;;) {
           unsigned long long need = __ballot(searching);
           if (need == 0ull) break;
@@ -920,7 +911,7 @@ struct Solver : TraceState<TRACE> {
       double t = 1.0;
       double Et = sqrt(ti2), Eot = sqrt(to2);
       bool known = true;
-      constexpr int KT = FB_LS_KT;
+      constexpr int KT = kLineSearchTrials;
       double Em[KT], Eom[KT];
       int have = 0, used = 0;
       for (int j = 0; j < o.max_linesearch_iters; j++) {

@@ -126,14 +126,12 @@ struct Ctx {
   // operations stay in program order), so it waits on lgkmcnt alone and leaves
   // global loads/stores in flight; __syncthreads() would drain vmcnt too.
   FB_DEV void sync() const {
-#if !defined(FB_NO_WAVE_SYNC)
     if (NT <= 64) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
       return;
     }
-#endif
     __syncthreads();
   }
 

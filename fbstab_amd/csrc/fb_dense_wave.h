@@ -589,17 +589,8 @@ struct DenseWave {
     const double r0 = lane_of(v, 0), r1 = lane_of(v, 16), r2 = lane_of(v, 32), r3 = lane_of(v, 48);
     return fmax(fmax(r0, r1), fmax(r2, r3));
   }
-#ifndef FB_DW_W_FROM_THE_SYSTEM
-#define FB_DW_W_FROM_THE_SYSTEM 1
-#endif
-#ifndef FB_DW_LDS_COLS
-#define FB_DW_LDS_COLS 48
-#endif
-  static constexpr int kLdsCols = FB_DW_LDS_COLS;  // even
-#ifndef FB_DW_LDS_BATCH
-#define FB_DW_LDS_BATCH 24
-#endif
-  static constexpr int kLdsBatch = FB_DW_LDS_BATCH;  // columns per batch of LDS reads (even)
+  static constexpr int kLdsCols = 48;  // even
+  static constexpr int kLdsBatch = 24;  // columns per batch of LDS reads (even)
   FB_DEV bool factor(const C& c, double (&Kr)[64], double dg, int* ord_o, double* dpiv_o, int* permv_o) const {
     int n = lay.nk, t = c.tid;
     asm volatile("" : "+s"(n), "+v"(t));
@@ -713,20 +704,9 @@ struct DenseWave {
   // Returns false - and leaves K and x destroyed - if a pivot is zero, denormal, infinite
   // or NaN: the caller assembles K again and takes the pivoted path, whose verdict on such
   // a matrix is Eigen's.
-#ifndef FB_DW_STATIC_ORDER
-#define FB_DW_STATIC_ORDER 1
-#endif
-#ifndef FB_DW_RL_COLS
-#define FB_DW_RL_COLS 8
-#endif
-  static constexpr int kRlCols = FB_DW_RL_COLS;
-#ifndef FB_DW_ST_BATCH
-#define FB_DW_ST_BATCH 8
-#endif
-#ifndef FB_DW_RCP_STEPS
-#define FB_DW_RCP_STEPS 3
-#endif
-  static constexpr int kStBatch = FB_DW_ST_BATCH;  // 16-byte LDS reads in flight
+  static constexpr int kRlCols = 8;
+  static constexpr int kStBatch = 8;  // 16-byte LDS reads in flight
+  static constexpr int kRcpSteps = 3;
   // 1 / d: hardware seed and three Newton steps, without the scaling and fix-up of the
   // IEEE sequence (the exponent of d is checked by the caller).  Two steps are what the
   // IEEE sequence takes before its final correction of the quotient and gave the same
@@ -735,7 +715,7 @@ struct DenseWave {
   static FB_DEV double rcp_nr(double d) {
     double r = __builtin_amdgcn_rcp(d);
 #pragma unroll
-    for (int i = 0; i < FB_DW_RCP_STEPS; i++) r = fma(fma(-d, r, 1.0), r, r);
+    for (int i = 0; i < kRcpSteps; i++) r = fma(fma(-d, r, 1.0), r, r);
     return r;
   }
   FB_DEV bool factor_solve_static(const C& c, double (&Kr)[64], double& x) const {
@@ -945,7 +925,6 @@ struct DenseWave {
     if (t < nz) { rhs0 = -(rz[t] + sigma * (z[t] - zb[t])); x = rhs0 - atr; }
     else if (t < n) { rhs0 = rl[t - nz] + sigma * (l[t - nz] - lb[t - nz]); x = rhs0; }
     FB_WAVE_LAP(11);
-#if FB_DW_STATIC_ORDER
     bool solved = false;
     if constexpr (!ADJ) {
       // (a NaN on the diagonal - an overflowed iterate - goes straight to the pivoted
@@ -964,9 +943,7 @@ struct DenseWave {
       }
     }
     FB_WAVE_LAP(12);
-    if (!solved)
-#endif
-    {
+    if (!solved) {
       int ord, permv;
       double dpiv;
       if (!factor(c, Kr, dg, &ord, &dpiv, &permv)) return false;
@@ -976,7 +953,6 @@ struct DenseWave {
     FB_WAVE_LAP(13);
     if (t < nz) dz[t] = x;
     else if (t < n) dl[t - nz] = x;
-#if FB_DW_W_FROM_THE_SYSTEM
     // W = (H dz + G'dl + A'dv, -G dz), the increment of the natural residual's (z, l)
     // rows along the step (the line search evaluates its trial points from it), is what
     // the rows of the Newton system just solved leave of their right-hand sides:
@@ -986,30 +962,27 @@ struct DenseWave {
     // products it replaces.
     if (t < nz) wz[t] = rhs0 - sigma * x;
     else if (t < n) wl[t - nz] = -(rhs0 + sigma * x);
-#endif
     c.sync();
     // dv = rv/mus + Gamma .* (A dz) (:114-121); adz = A dz (dy = b - A dz, :124): rows t
-    // and t + 64 of A against dz (and, for the explicit W, row t of H or of G in the same
-    // loop), the loads of ten entries in flight together.  Rows past the end read row 0
-    // and are dropped.
-    [[maybe_unused]] double hdz = 0.0;  // (H dz)_t, t < nz; (G dz)_(t - nz), nz <= t < n
+    // and t + 64 of A against dz, the loads of ten entries in flight together.  Rows past
+    // the end read row 0 and are dropped.
     if (nv <= 128) {
       const bool r0 = t < nv, r1 = t + 64 < nv;
       const double* a0 = D.A + (r0 ? t : 0);
       const double* a1 = D.A + (r1 ? t + 64 : 0);
+      // (hr, hs: unused - row t of H or of G, what an explicit W read: LABNOTES, retired switches.  Without them
+      // the compiler allocates two registers of the adjoint kernel the other way round; they stay so that retiring
+      // the switch left the compiled library bit-identical, and go with the next change of this kernel's code.)
       [[maybe_unused]] const double* hr = t < nz ? D.H + t : (nl > 0 ? D.G + (t < n ? t - nz : 0) : D.H);
       [[maybe_unused]] const long hs = t < nz ? nz : (nl > 0 ? nl : nz);
       double s0 = 0.0, s1 = 0.0;
-      struct Chunk { double x0[10], x1[10], xh[10]; };
+      struct Chunk { double x0[10], x1[10]; };
       auto load_chunk = [&](int k0, Chunk& ch) {
 #pragma unroll
         for (int u = 0; u < 10; u++) {
           const int k = k0 + u < nz ? k0 + u : nz - 1;
           ch.x0[u] = a0[(long)k * nv];
           ch.x1[u] = a1[(long)k * nv];
-#if !FB_DW_W_FROM_THE_SYSTEM
-          ch.xh[u] = hr[(long)k * hs];
-#endif
         }
       };
       auto use_chunk = [&](int k0, const Chunk& ch) {
@@ -1018,12 +991,9 @@ struct DenseWave {
           const double d = k0 + u < nz ? dz[k0 + u < nz ? k0 + u : nz - 1] : 0.0;
           s0 = fma(ch.x0[u], d, s0);
           s1 = fma(ch.x1[u], d, s1);
-#if !FB_DW_W_FROM_THE_SYSTEM
-          hdz = fma(ch.xh[u], d, hdz);
-#endif
         }
       };
-      // (the next ten entries' thirty loads go out before these ten are used)
+      // (the next ten entries' twenty loads go out before these ten are used)
       Chunk ca, cb;
       load_chunk(0, ca);
       for (int k0 = 0; k0 < nz; k0 += 20) {
@@ -1040,22 +1010,8 @@ struct DenseWave {
         adz[i] = a;
         dv[i] = dv_of<ADJ>(i, a, sigma, alpha);
       }
-#if !FB_DW_W_FROM_THE_SYSTEM
-      if (t < nz) hdz = row_dot(D.H, nz, nz, t, dz);
-      else if (t < n) hdz = row_dot(D.G, nl, nz, t - nz, dz);
-#endif
     }
     c.sync();
-#if !FB_DW_W_FROM_THE_SYSTEM
-    if (t < nz) {
-      double gdl = 0.0;  // (G'dl)_t from the transposed copy
-      for (int q = 0; q < nl; q++) gdl = fma(Gt[64 * q + t], dl[q], gdl);
-      wz[t] = hdz + gdl + A_col_dot(t, dv);
-    } else if (t < n) {
-      wl[t - nz] = -hdz;
-    }
-    c.sync();
-#endif
     FB_WAVE_LAP(14);
     return true;
   }

@@ -67,9 +67,6 @@ struct MpcR16 {
   // pair, two QPs per wavefront - fb_row16.h), QPs per wavefront
   static constexpr int LPQ = 16 * RQ, kQpPerWave = 64 / LPQ;
   typedef double dbl2 __attribute__((ext_vector_type(2)));
-#ifndef FB_R16_ASM_IMAGES
-#define FB_R16_ASM_IMAGES 1
-#endif
   static constexpr bool kFusedTrial = true;
   static constexpr bool kOwnVectorOps = true;
   static constexpr int NS = NX + NU;
@@ -93,10 +90,7 @@ struct MpcR16 {
   // traffic per stage less, 90 instructions more.  (Rounds 1-2 measured that at -6 %; with the fused
   // broadcast-FMAs the kernel sits nearer its memory wall and it is +1.1 % pipelined, +1 % one launch at a
   // time - gpurun_out/r05_j; same bits either way: the same function of the same stored values.)
-#ifndef FB_R16_RECOMPUTE_GAMMA
-#define FB_R16_RECOMPUTE_GAMMA 1  // 0: never; 1: on the one-row instances; 2: everywhere
-#endif
-  static constexpr bool kStoreGamma = !(FB_R16_RECOMPUTE_GAMMA == 2 || (FB_R16_RECOMPUTE_GAMMA == 1 && RQ == 1));
+  static constexpr bool kStoreGamma = RQ != 1;
   static constexpr int sGAM = sDV + 2 * KS;  // (kStoreGamma) pairs (GAM_s, RVM_s)
   static constexpr int sF = sGAM + (kStoreGamma ? 2 * KS : 0), sH = sF + 1;
   static constexpr int sB = sH + 1;          // KS slots
@@ -138,7 +132,7 @@ struct MpcR16 {
 
   // LDS of a workgroup (one wavefront):
   //   the matrix-copy area   the copy each QP's current stage uses, minus the [A B] columns (the
-  //                          pair-interleaved image of HBM, the QPs' images interleaved pair by pair:
+  //                          pair-interleaved image of HBM, one image per QP with padded pairs:
   //                          kPackPair): loaded when poff[i] changes, i.e. three to five times per sweep
   //                          pair for a time-invariant plant, and read by every pass with 16-byte loads;
   //   one region per QP      C as [col][k] (A z products) or the triangle images (sweeps); odd strides;
@@ -155,58 +149,39 @@ struct MpcR16 {
   // 24 spare doubles behind the images for the solver loop's parked scalars
   static constexpr int kLdsBase = ((kLdsDoubles + 31) & ~31) + 16;
   static constexpr int kLdsPerRow = kLdsBase - kLdsDoubles >= 24 ? kLdsBase : kLdsBase + 32;
-  static constexpr bool kPackInLds = true;
-  static constexpr int kPackLds = kPackInLds ? LPQ * kPackLdsSlots : 0;  // doubles of one QP's image
-  // The images of a wavefront's QPs share ONE area in front of the QPs' own regions, interleaved pair by
-  // pair: pair p of QP q at p * kPackPair + q * 2 LPQ, lane r at + 2 r.  A slot pair of all the wavefront's
-  // lanes is then 1 KiB of consecutive LDS in lane order - what an LDS-DMA load writes
-  // (global_load_lds_dwordx4: wave-uniform base + lane x 16 bytes; stage_pack_dma below).
-  // Round 6 (FB_R16_ABC_FROM_LDS, the default): the images are laid out per QP instead - pair p of QP q at
-  // q * kPackQp + p * kPackPair, lane r at + 2 r - with a pair stride of 2 LPQ + 2 doubles: PADDED, so that lane r
+  // The images of a wavefront's QPs share ONE area in front of the QPs' own regions, laid out per QP - pair p of QP q
+  // at q * kPackQp + p * kPackPair, lane r at + 2 r - with a pair stride of 2 LPQ + 2 doubles: PADDED, so that lane r
   // can read COLUMN r of a row-held matrix out of the image (slot pABr + r, entry j: the lanes' addresses are
   // (r >> 1) kPackPair + (r & 1) + 2 j apart - with the stride a multiple of the 64 banks all sixteen would
   // hit two bank pairs, with 2 LPQ + 2 they fall on 16 different ones).  That is what lets the backward sweep
   // take the columns of [A B] from the rows it has staged anyway instead of reading the 12 column slots of
   // the matrix copy from memory: for a plant whose matrices change with the stage - 31 copies per sweep, a
   // workload at the HBM's limit with eight launches in flight - 12 of the 116 slots a stage pair moves.
-  // (The interleaved layout stays behind FB_R16_PACK_DMA: the LDS-DMA load writes a wavefront's lanes in order.)
-#ifndef FB_R16_ABC_FROM_LDS
-#define FB_R16_ABC_FROM_LDS 1
-#endif
-#ifndef FB_R16_PACK_DMA
-#define FB_R16_PACK_DMA 0
-#endif
-  static constexpr bool kAbcFromLds = FB_R16_ABC_FROM_LDS != 0 && FB_R16_PACK_DMA == 0 && kPackInLds;
-  static constexpr int kPackPair = kAbcFromLds ? 2 * LPQ + 2 : 2 * LPQ * kQpPerWave;  // doubles between consecutive slot pairs of a QP's image
+  // (The layout this replaced, the QPs' images interleaved pair by pair for an LDS-DMA load: LABNOTES, retired switches.)
+  static constexpr int kPackPair = 2 * LPQ + 2;  // doubles between consecutive slot pairs of a QP's image
   // The rows of [A B] are NX: lanes r >= NX hold zeros in those slot pairs (and the sweeps rely on reading them:
   // W, Pi+ and T come out zero there without a select).  Where it buys a workgroup per CU the pairs of [A B] are
-  // therefore TRIMMED (FB_R16_TRIM_AB, round 6): 2 NX + 2 doubles apart, lanes r < NX at + 2 r and the two
+  // therefore TRIMMED: 2 NX + 2 doubles apart, lanes r < NX at + 2 r and the two
   // doubles of padding - kept zero: every lane r >= NX stores its zeros there and reads them back from there -
   // at + 2 NX.  <24,8,16>: 57,600 -> 53,504 bytes (N = 30), three workgroups per CU (160 KB) instead of two; the column
   // reads of the backward sweep stay conflict-free (pair stride 50 doubles: 100 dwords = 36 mod 64, sixteen
   // lane pairs on sixteen different bank quads).  Row-pair instances only, and only where a workgroup is gained:
   // <24,8,32> stays at two, <18,5,10> has its four - no other instance's code changes.
-#ifndef FB_R16_TRIM_AB
-#define FB_R16_TRIM_AB 1
-#endif
   static constexpr int kAbPairTrim = 2 * NX + 2;
   static constexpr int pack_qp(int ab_pair) { return (pABr / 2) * kPackPair + (NSP / 2) * ab_pair; }
   static constexpr int wgs_per_cu(int pack_qp_doubles) {  // by LDS (160 KB a CU), at most the four SIMDs' one wavefront each
     const int per = 163840 / ((kQpPerWave * (pack_qp_doubles + kLdsPerRow)) * 8 + 512);  // (+ the offset tables: 8 (N + 1) bytes a QP)
     return per > 4 ? 4 : per;
   }
-  static constexpr bool kTrimAb = FB_R16_TRIM_AB != 0 && kAbcFromLds && RQ == 2 && NX < LPQ &&
+  static constexpr bool kTrimAb = RQ == 2 && NX < LPQ &&
                                   wgs_per_cu(pack_qp(kAbPairTrim)) > wgs_per_cu(pack_qp(kPackPair));
   static constexpr int kAbPair = kTrimAb ? kAbPairTrim : kPackPair;  // doubles between consecutive slot pairs of [A B]'s rows
   // ... and where leaving the rows of K = [Q S'; S R] OUT of the image buys another workgroup they are read from the
-  // matrix copy in memory instead (FB_R16_K_FROM_MEMORY, round 6: the `if constexpr (kKinLds)` at the five places K is read).  A sweep stages a stage's copy once and
+  // matrix copy in memory instead (the `if constexpr (kKinLds)` at the five places K is read).  A sweep stages a stage's copy once and
   // reads K from it once, so a plant whose matrices change with the stage moves the same bytes either way, and a
   // time-invariant one finds its few copies in L2.  <24,8,16>: 53,504 -> 36,608 bytes, FOUR workgroups per CU - every
   // SIMD; <24,8,32>: 68,608 -> 51,712, three instead of two.
-#ifndef FB_R16_K_FROM_MEMORY
-#define FB_R16_K_FROM_MEMORY 1
-#endif
-  static constexpr bool kKinLds = !(FB_R16_K_FROM_MEMORY != 0 && kAbcFromLds && RQ == 2 &&
+  static constexpr bool kKinLds = !(RQ == 2 &&
                                     wgs_per_cu(pack_qp(kAbPair) - (pC / 2) * kPackPair) > wgs_per_cu(pack_qp(kAbPair)));
   static constexpr int kLdsFirstPair = kKinLds ? 0 : pC / 2;  // the image starts with this slot pair of the matrix copy
   // where slot pair `pr` of a QP's image starts, in doubles
@@ -222,10 +197,8 @@ struct MpcR16 {
       return 0;
     }
   }
-  static constexpr int kPackQp = kAbcFromLds ? pack_qp(kAbPair) - kLdsFirstPair * kPackPair : 2 * LPQ;  // doubles between the images of two QPs
-  static constexpr int kPackArea = kAbcFromLds ? kQpPerWave * kPackQp : kQpPerWave * kPackLds;  // doubles of the wavefront's area
-  // this lane's view of the matrix copy in use
-  typedef typename std::conditional<kPackInLds, lds_ptr, const double*>::type pk_ptr;
+  static constexpr int kPackQp = pack_qp(kAbPair) - kLdsFirstPair * kPackPair;  // doubles between the images of two QPs
+  static constexpr int kPackArea = kQpPerWave * kPackQp;  // doubles of the wavefront's area
 
 
   // ---- the triangle images in LDS, hand-scheduled (instance <12,4,20>, one row per QP) ----
@@ -242,7 +215,7 @@ struct MpcR16 {
   // flight together and waited for once.  EXEC is restored before the block ends, and
   // five wait states follow (the compiler's hazard recognizer does not look inside the
   // block: a DPP instruction of its own must not sit in the shadow of the last v_cmpx).
-  static constexpr bool kAsmImages = FB_R16_ASM_IMAGES && RQ == 1 && NS == 16 && NX == 12;
+  static constexpr bool kAsmImages = RQ == 1 && NS == 16 && NX == 12;
   // The row-pair instances (stages up to 32 wide) SUBSTITUTE with Lc where the one-row instances multiply
   // with its explicit inverse (fb_row16.h, subst_rows): the factor record then holds Lc itself - rows of
   // the packed triangle, the diagonal as its reciprocal - and t = inv(Lc) g, s = t - inv(Lc) u and
@@ -251,10 +224,7 @@ struct MpcR16 {
   // under the tolerance (and is what the headline's time is made of); on stages wider than that, with
   // nx > N nu, it left up to 4.6e-6 where the oracle leaves 1e-7 - the one deviation round 4's fuzz found
   // (tests/test_gpu_components.py::test_one_step_qp_...).
-#ifndef FB_R16_SUBST
-#define FB_R16_SUBST 2  // substitute on the instances with at least this many rows per QP (1: all, 3: none)
-#endif
-  static constexpr bool kSubst = RQ >= FB_R16_SUBST;
+  static constexpr bool kSubst = RQ >= 2;
   static_assert(!(kSubst && kAsmImages), "the hand-written image blocks move the inverse's columns");
   static FB_DEV unsigned lds_addr(lds_ptr p) { return (unsigned)(unsigned long)p; }
 #define FB_IMG_WP(cc, off) "v_cmpx_le_i32_e32 vcc, " #cc ", %[ro]\n\tds_write_b64 %[rb], %[p" #cc "] offset:" #off "\n\t"
@@ -500,11 +470,8 @@ struct MpcR16 {
   // lanes masked out of the accesses instead - `if (tail_lane())` - the counters showed the same bytes and
   // the headline lost 7 %: five conditional regions per stage pair cut the sweeps' basic blocks and the
   // waits at their joins, gpurun_out/r05_t1.)
-#ifndef FB_R16_TAIL_CUT
-#define FB_R16_TAIL_CUT 1
-#endif
   static constexpr int kTail = NC - LPQ * (KS - 1);
-  static constexpr bool kTailCut = FB_R16_TAIL_CUT != 0 && 2 * kTail <= LPQ;
+  static constexpr bool kTailCut = 2 * kTail <= LPQ;
   static constexpr int kSpareRecords = kTailCut ? 1 : 0;
   static FB_DEV bool tail_lane() { return (int)(threadIdx.x & (LPQ - 1)) < kTail; }
   // where this lane finds the last constraint slot of the stage whose record is R (Rd: the spare record)
@@ -546,16 +513,8 @@ struct MpcR16 {
   }
 
   // Makes the matrix copy at offset `off` the one resident in LDS (row-uniform).
-  template <bool L = kPackInLds>
-  FB_DEV auto pack_view(const C& c) const {
-    if constexpr (L) return lpk + 2 * c.tid;
-    else return static_cast<const double*>(pack);
-  }
-  FB_DEV void stage_pack(const C& c, pk_ptr& view, int off) { stage_pack_s(c, pack, view, lds_off, off); }
-  static FB_DEV void stage_pack_s(const C&, const double* pack0, const double*& view, int& cur, int off) {
-    view = pack0 + off;
-    cur = off;
-  }
+  FB_DEV lds_ptr pack_view(const C& c) const { return lpk + 2 * c.tid; }
+  FB_DEV void stage_pack(const C& c, lds_ptr& view, int off) { stage_pack_s(c, pack, view, lds_off, off); }
   static FB_DEV void stage_pack_s(const C& c, const double* pack0, lds_ptr& view, int& cur, int off) {
     if (off == cur) return;
     cur = off;
@@ -577,44 +536,10 @@ struct MpcR16 {
     });
     c.sync();
   }
-  // The same by LDS-DMA (round 5; build knob FB_R16_PACK_DMA, OFF): global_load_lds_dwordx4 moves 16 bytes
-  // per lane from the lane's own address to LDS at a wave-uniform base + lane x 16 - one slot pair of the
-  // wavefront's area per instruction, no register in between, nothing waits.  The sweeps of the Newton step
-  // issue it for the NEXT stage's copy as soon as the current stage has read the image for the last time
-  // and wait for it at the top of the next stage, so that a plant whose matrices change from stage to
-  // stage (31 stagings per sweep instead of three to five) does not pay a trip to memory and back per
-  // stage.  Built, correct (same checksums, 161 parity tests) - and measured: the time-varying workload
-  // +1.8 % one launch at a time, +-0 with eight in flight (427-432 k either way), the headline +-0
-  // (gpurun_out/r05_v).  That workload is bound by the BYTES of its 31 matrix copies per QP (LABNOTES
-  // Part II), which a different way of fetching them does not change.  Left in as a knob, not the default.
-  // Lp: this lane's view; the lanes of a QP whose copy does not change sit the call out (EXEC).
-#ifndef FB_R16_PACK_DMA
-#define FB_R16_PACK_DMA 0
-#endif
-  static constexpr bool kPackDma = FB_R16_PACK_DMA != 0 && kPackInLds;
-  static FB_DEV void stage_pack_dma(const double* src, lds_ptr Lp) {
-    // (the area's base: the view minus the lane's place in the wavefront - the same in every lane)
-    FB_LDS char* const area = reinterpret_cast<FB_LDS char*>(Lp - 2 * (threadIdx.x & 63));
-    sfor<0, kPackLdsSlots / 2>([&](auto I) {
-      constexpr int pr = decltype(I)::value;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + pr * 2 * LPQ),
-                                       (FB_LDS void*)(area + pr * kPackPair * 8), 16, 0, 0);
-    });
-  }
-  // ... and the wait for it: every lane of the wavefront calls this at the top of a stage; `issued` says
-  // whether this lane's QP had a copy on its way
-  static FB_DEV void stage_pack_dma_wait(bool issued) {
-    if (__ballot(issued) != 0ull) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
+  // (Staging the next stage's copy by LDS-DMA - global_load_lds_dwordx4 - changed nothing the workloads are
+  // bound by: LABNOTES, retired switches.)
 
   // slots [S0, S0 + CNT) of the LDS-resident copy into out[0..CNT)
-  template <int S0, int CNT, int NOUT>
-  static FB_DEV void ldl(const double* G, double (&out)[NOUT]) {
-    ldv<S0, CNT>(G, out);
-  }
   template <int S0, int CNT, int NOUT>
   static FB_DEV void ldl(lds_ptr L, double (&out)[NOUT]) {
     static_assert((S0 & 1) == 0 && S0 + CNT <= kPackLdsSlots, "inside the LDS image, on a pair");
@@ -710,11 +635,12 @@ struct MpcR16 {
     sfor<0, NSP>([&](auto Cc_) { lastKr[decltype(Cc_)::value] = lastABr[decltype(Cc_)::value] = 0.0; });
     sfor<0, NC>([&](auto Kk) { lastCc[decltype(Kk)::value] = 0.0; });
     sfor<0, NX>([&](auto J) { lastABc[decltype(J)::value] = 0.0; });
-    // The stage's vectors from the caller's arrays (f, h, the guess, b, v): requested a
-    // stage AHEAD.  Behind the matrix loads, the comparison and the stores of their own
-    // stage - the compiler may not move a load of the caller's memory above a store to
-    // the records - they were three more trips to memory per stage, one after the other
-    // (f h; z l; b v), in a pass that has nothing to cover a trip with.
+    // The stage's vectors from the caller's arrays (f, h, the guess, b, v): loaded at the top
+    // of their own stage, with the matrix loads.  Behind the matrix loads, the comparison and
+    // the stores of their own stage - the compiler may not move a load of the caller's memory
+    // above a store to the records - they were three more trips to memory per stage, one after
+    // the other (f h; z l; b v), in a pass that has nothing to cover a trip with.  (A stage
+    // ahead was slower still: LABNOTES, retired switches.)
     struct Small {
       double f, h, zz, ll, b[KS], vv[KS];
     };
@@ -731,24 +657,12 @@ struct MpcR16 {
         sm.vv[sl] = real ? uv[(long)i * nc_ + k] : 0.0;
       });
     };
-#ifndef FB_R16_LOAD_AHEAD
-#define FB_R16_LOAD_AHEAD 0
-#endif
-    [[maybe_unused]] Small nxt_small;
-    if constexpr (FB_R16_LOAD_AHEAD != 0) load_small(0, nxt_small);
     for (int i = 0; i <= N_; i++) {
       double* R = R0 + (long)i * kRec;
       double* PK = P0 + (long)i * kPack;
       const bool has_ab = i < N_;
       Small sm;
-      if constexpr (FB_R16_LOAD_AHEAD != 0) {
-        sm = nxt_small;
-        if (i < N_) load_small(i + 1, nxt_small);
-      } else {
-        load_small(i, sm);  // (at the top of their own stage, with the matrix loads: 531 k QP/s
-                            //  against 519 k with the loads where they were and 480 k with
-                            //  them a stage ahead, gpurun_out/r03_ai)
-      }
+      load_small(i, sm);
       double Cc[NC];
       bool fresh = true;
       if constexpr (KEEP) fresh = !reuse;
@@ -876,18 +790,12 @@ struct MpcR16 {
 
   // Which form of the costate step this QP's backward sweeps take (see `rowdl`); called
   // once per QP, after load_guess().
-#ifndef FB_R16_ROW_COSTATE
-#define FB_R16_ROW_COSTATE 1  // 0: every QP takes the reference's form (a) - to tell the two apart in a comparison
-#endif
-#ifndef FB_R16_ROW_SPARSE
-#define FB_R16_ROW_SPARSE 1  // 0: only bound constraints take the row form
-#endif
   FB_DEV void choose_costate_form(double sigma) {
     // |C'Gamma C| <= (nonzeros per row) x (column sums of C'C) / sigma: bounds with entries up to 2, or sparse
     // rows (a few entries of order one per row - the bench line's time-varying workload) within the same
     // factor 8 of 1/sigma in all
-    const bool small = bounds ? cmax2 <= 4.f : (FB_R16_ROW_SPARSE != 0 && (float)nzmax * cmax2 <= 8.f);
-    rowdl = FB_R16_ROW_COSTATE != 0 && small && (double)hmax * sigma <= 1.0;
+    const bool small = bounds ? cmax2 <= 4.f : (float)nzmax * cmax2 <= 8.f;
+    rowdl = small && (double)hmax * sigma <= 1.0;
   }
 
   // Natural residual blocks at x: rz = Hz + f + G'l + A'v, rl = h - Gz
@@ -898,7 +806,7 @@ struct MpcR16 {
     double* const R0 = rec;
     const double* const P0 = pack;
     const lds_iptr po = lpo;
-    pk_ptr Lp = pack_view(c);  // this lane's view of the matrix copy in use
+    lds_ptr Lp = pack_view(c);  // this lane's view of the matrix copy in use
     for (int i = 0; i <= N_; i++) {
       double* R = R0 + (long)i * kRec;
       const int pofs = po[i];
@@ -1055,10 +963,6 @@ struct MpcR16 {
   // kind of failure to rows that join these passes with a policy object no fetch has
   // bound yet - bind_idle() - see profiles/r03_q_coop_inline_miscompile_notes.txt;
   // tests/test_gpu_parity.py runs every instance, exact and padded).
-#ifndef FB_R16_COOP_TRIALS
-#define FB_R16_COOP_TRIALS 1
-#endif
-  static constexpr bool kCoopTrials = FB_R16_COOP_TRIALS != 0;
   static FB_DEV double lane_value(double x, int lane) {  // x of lane `lane` (wave-uniform index)
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), lane),
                             __builtin_amdgcn_readlane(__double2loint(x), lane));
@@ -1084,16 +988,8 @@ struct MpcR16 {
   }
   // R0: the owner's record base with this lane's offset within ITS row (2 * r)
   template <int K>
-#ifndef FB_R16_COOP_INLINE
-#define FB_R16_COOP_INLINE 0
-#endif
-#if FB_R16_COOP_INLINE
-  static __device__ __forceinline__ TrialNorms<K> trial_pass_coop(const double* R0, int N_, double t0,
-                                                                            double beta, double sigma, double alpha) {
-#else
   static __device__ __attribute__((noinline)) TrialNorms<K> trial_pass_coop(const double* R0, int N_, double t0,
                                                                             double beta, double sigma, double alpha) {
-#endif
     constexpr int QW = kQpPerWave;
     const int lane = threadIdx.x & 63;
     const int q = lane / LPQ;
@@ -1103,31 +999,21 @@ struct MpcR16 {
     sfor<0, 2 * K>([&](auto Kk) { s[decltype(Kk)::value] = 0.0; });
     auto stage_ptr = [&](int i) { return R0 + (long)(i < N_ ? i : N_) * kRec; };
     const double* const Rd = spare_of(R0, N_);
-    // (The slots of a trip are requested a trip ahead - this pass stores nothing.  At the top
-    // of their own trip, FB_R16_TRIAL_AHEAD=0: 485 k against 533 k QP/s, gpurun_out/r03_ap;
-    // two trips ahead: -6 %, round 2.  In the passes that also STORE records - open, close,
-    // the packing pass - every form of requesting ahead has lost, see open_pass_coop.)
-#ifndef FB_R16_TRIAL_AHEAD
-#define FB_R16_TRIAL_AHEAD 1
-#endif
-    // TS stages per trip and row (stages i, i + QW, ...): the pass is bound by the latency of a trip's
-    // loads, not by their bytes - with the z and l slots gone a trip of one stage moves five slot pairs,
-    // so two stages per trip keep as many loads in flight as the pass had before and halve the trips.
-#ifndef FB_R16_TRIAL_STAGES
-#define FB_R16_TRIAL_STAGES 1  // (2: one launch at a time 2 % faster, eight in flight 0.7 % slower; 4: +3 % / -7 %; gpurun_out/r05_m)
-#endif
-    constexpr int TS = FB_R16_TRIAL_STAGES;
+    // (The slots of a trip are requested a trip ahead - this pass stores nothing; at the top of their own
+    // trip, two trips ahead and two or four stages per trip all lost: LABNOTES, retired switches.  In the
+    // passes that also STORE records - open, close, the packing pass - every form of requesting ahead has
+    // lost, see open_pass_coop.)
+    // One stage per trip and row (stages i, i + QW, ...): the pass is bound by the latency of a trip's
+    // loads, not by their bytes - with the z and l slots gone a trip moves five slot pairs.  (Written for TS stages
+    // per trip; as straight code for one stage the headline's object comes out different, so the arrays stay.)
+    constexpr int TS = 1;
     TrialInV in[TS];
-    if constexpr (FB_R16_TRIAL_AHEAD != 0)
-      sfor<0, TS>([&](auto J) { load_trial_v(stage_ptr(q + QW * decltype(J)::value), Rd, in[decltype(J)::value]); });
+    sfor<0, TS>([&](auto J) { load_trial_v(stage_ptr(q + QW * decltype(J)::value), Rd, in[decltype(J)::value]); });
     for (int i = q; i - q <= N_; i += TS * QW) {  // (the same trip count in every row)
       FB_PHASE(trip_top);
-      if constexpr (FB_R16_TRIAL_AHEAD == 0)
-        sfor<0, TS>([&](auto J) { load_trial_v(stage_ptr(i + QW * decltype(J)::value), Rd, in[decltype(J)::value]); });
       TrialInV cu[TS];
       sfor<0, TS>([&](auto J) { cu[decltype(J)::value] = in[decltype(J)::value]; });
-      if constexpr (FB_R16_TRIAL_AHEAD != 0)
-        sfor<0, TS>([&](auto J) { load_trial_v(stage_ptr(i + QW * (TS + decltype(J)::value)), Rd, in[decltype(J)::value]); });
+      sfor<0, TS>([&](auto J) { load_trial_v(stage_ptr(i + QW * (TS + decltype(J)::value)), Rd, in[decltype(J)::value]); });
       sfor<0, TS>([&](auto J) {
         constexpr int j = decltype(J)::value;
         // A row that has run out of stages (the last trip) re-reads the last stage - lines the row that owns
@@ -1165,106 +1051,8 @@ struct MpcR16 {
     });
     return out;
   }
-  // ---- the same pass with the LAST constraint slot of four stages evaluated as ONE slot (round 6) --------
-  // NC = 20 on 16 lanes: the second slot of a stage holds entries 16..19 on 4 lanes and nothing on the other
-  // 12, and the pass above evaluates it - four step lengths, both functions - once per stage all the same: 37 %
-  // of the pass's arithmetic on 25 % full slots.  Here a row evaluates the full slots of its stage trip by
-  // trip as before, and once per FOUR trips the last slots of the four stages it took in them together: lane
-  // l loads entry l % kTail of the stage of trip l / kTail straight from that stage's record.  Same terms;
-  // a row's partial sums collect them in a different order (as this pass already does against the
-  // sequential one).  12 evaluations of 32 fewer per four trips.
-  // MEASURED (gpurun_out/r06_o, same box, 3 interleaved runs): SQ_INSTS_VALU of the 8192-QP launch 3.953 G ->
-  // 3.779 G (-4.4 %), every count and the Newton total unchanged, 162 parity tests green - and the headline
-  // 630.5 k -> 624.9 k QP/s (-0.9 %), one launch at a time +-0: the pass is a chain of eight trips each
-  // waiting for loads requested one trip earlier, and a trip with half the arithmetic covers half the
-  // latency.  The third time this round that a shorter trial pass was not a faster one (the other two are
-  // in trial_pass_coop).  OFF: the knob is the record of the experiment, not the product.
-#ifndef FB_R16_TAIL_PACK
-#define FB_R16_TAIL_PACK 0
-#endif
-  static constexpr int kTailGroup = 4;
-  static constexpr bool kTailPack = FB_R16_TAIL_PACK != 0 && KS >= 2 && kTail * kTailGroup <= LPQ && kTailCut &&
-                                    FB_R16_TRIAL_STAGES == 1;
-  template <int K>
-  static __device__ __attribute__((noinline)) TrialNorms<K> trial_pass_coop_packed(const double* R0, int N_, double t0,
-                                                                                   double beta, double sigma, double alpha) {
-    constexpr int QW = kQpPerWave, G = kTailGroup, KF = KS - 1;
-    const int lane = threadIdx.x & 63;
-    const int q = lane / LPQ, r = lane & (LPQ - 1);
-    double tt[K], s[2 * K];
-    tt[0] = t0;
-    sfor<1, K>([&](auto Kk) { tt[decltype(Kk)::value] = tt[decltype(Kk)::value - 1] * beta; });
-    sfor<0, 2 * K>([&](auto Kk) { s[decltype(Kk)::value] = 0.0; });
-    auto stage_ptr = [&](int i) { return R0 + (long)(i < N_ ? i : N_) * kRec; };
-    struct Full {
-      dbl2 vy[KF], da[KF];
-      double vb[KF];
-    };
-    struct Tail {
-      dbl2 vy, da;
-      double vb;
-    };
-    auto load_full = [&](const double* R, Full& in) {
-      sfor<0, KF>([&](auto S_) {
-        constexpr int sl = decltype(S_)::value;
-        in.vy[sl] = ld2(R, sV + 2 * sl);
-        in.da[sl] = ld2(R, sDV + 2 * sl);
-        in.vb[sl] = ld(R, sVB + sl);
-      });
-    };
-    // this lane's place in a packed last slot: entry te of the stage this row takes in trip tsub of the group
-    const int tsub = r / kTail, te = r - tsub * kTail;
-    auto load_tail = [&](int g, Tail& in) {
-      const double* Rt = stage_ptr(q + QW * (G * g + tsub)) - 2 * r + 2 * te;  // (R0 carries this lane's 2 r)
-      in.vy = ld2(Rt, sV + 2 * KF);
-      in.da = ld2(Rt, sDV + 2 * KF);
-      in.vb = ld(Rt, sVB + KF);
-    };
-    auto terms = [&](const dbl2& vy, const dbl2& da, double vb, bool live) {
-      sfor<0, K>([&](auto Kk) {
-        constexpr int k = decltype(Kk)::value;
-        const double vi = fma(tt[k], da[0], vy[0]);
-        const double yi = fma(-tt[k], da[1], vy[1]);
-        const double ys = yi + sigma * (vi - vb);
-        const double ph = pfb(ys, vi, alpha);
-        const double pn = pnr(yi, vi, alpha);
-        s[k] = live ? fma(ph, ph, s[k]) : s[k];
-        s[K + k] = live ? fma(pn, pn, s[K + k]) : s[K + k];
-      });
-    };
-    const int last_trip = N_ / QW;  // (the same trip count in every row: trips t with QW t <= N)
-    Full in;
-    load_full(stage_ptr(q), in);
-    for (int g = 0; G * g <= last_trip; g++) {
-      FB_PHASE(trip_top);
-      Tail tl;
-      load_tail(g, tl);  // (used at the end of the group: three trips of cover)
-      sfor<0, G>([&](auto J) {
-        const int t = G * g + decltype(J)::value;
-        if (t <= last_trip) {  // (wave-uniform)
-          const Full cu = in;
-          load_full(stage_ptr(q + QW * (t + 1)), in);
-          const bool live = q + QW * t <= N_;
-          sfor<0, KF>([&](auto S_) {
-            constexpr int sl = decltype(S_)::value;
-            terms(cu.vy[sl], cu.da[sl], cu.vb[sl], live);
-          });
-        }
-      });
-      terms(tl.vy, tl.da, tl.vb, tsub < G && q + QW * (G * g + tsub) <= N_);
-      FB_PHASE(trip_end);
-    }
-    TrialNorms<K> out;
-    sfor<0, 2 * K>([&](auto Kk) {
-      constexpr int k = decltype(Kk)::value;
-      const double rs = qp_reduce<RQ, OpSum16>(s[k]);
-      double tot = lane_value(rs, 0);
-      sfor<1, QW>([&](auto Q_) { tot += lane_value(rs, LPQ * decltype(Q_)::value); });
-      if constexpr (k < K) out.vi[k] = tot;
-      else out.vo[k - K] = tot;
-    });
-    return out;
-  }
+  // (Round 6 also evaluated the LAST constraint slot of four stages as one slot: 4.4 % fewer vector instructions and
+  // 0.9 % slower, the third shorter trial pass that was not a faster one - LABNOTES, retired switches.)
   // The z and l blocks' share of the squared trial norms at x + t dx, from four sums of the Newton step.
   // Both residuals are affine there: with a = the inner (natural) residual's z, l blocks at x and b its
   // increment along dx (b = W + sigma dx for the inner one, b = W for the natural one),
@@ -1293,11 +1081,7 @@ struct MpcR16 {
     const unsigned long long rbo = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(rb >> 32), own0) << 32) |
                                    (unsigned)__builtin_amdgcn_readlane((int)rb, own0);
     const double* const R0 = reinterpret_cast<const double*>(rbo) + 2 * (threadIdx.x & (LPQ - 1));
-    TrialNorms<K> n;
-    if constexpr (kTailPack)
-      n = trial_pass_coop_packed<K>(R0, __builtin_amdgcn_readlane(N, own0), lane_value(t0, own0), beta, sigma, alpha);
-    else
-      n = trial_pass_coop<K>(R0, __builtin_amdgcn_readlane(N, own0), lane_value(t0, own0), beta, sigma, alpha);
+    const TrialNorms<K> n = trial_pass_coop<K>(R0, __builtin_amdgcn_readlane(N, own0), lane_value(t0, own0), beta, sigma, alpha);
     sfor<0, K>([&](auto Kk) {
       Vi[decltype(Kk)::value] = n.vi[decltype(Kk)::value];
       Vo[decltype(Kk)::value] = n.vo[decltype(Kk)::value];
@@ -1364,7 +1148,7 @@ struct MpcR16 {
     double* const R0 = rec;
     const double* const P0 = pack;
     const lds_iptr po = lpo;
-    pk_ptr Lp = pack_view(c);  // this lane's view of the matrix copy in use
+    lds_ptr Lp = pack_view(c);  // this lane's view of the matrix copy in use
     lds_ptr Cl = lds;
     double m_adz = -1e300, m_gdz = 0.0, m_hdz = 0.0, m_dz = 0.0, m_atv = 0.0, m_u = 0.0;
     double s_fdz = 0.0, s_p2 = 0.0, s_dx = 0.0;
@@ -1490,7 +1274,7 @@ struct MpcR16 {
     double* const R0 = rec;
     const double* const P0 = pack;
     const lds_iptr po = lpo;
-    pk_ptr Lp = pack_view(c);  // this lane's view of the matrix copy in use
+    lds_ptr Lp = pack_view(c);  // this lane's view of the matrix copy in use
     double s_nat = 0.0, s_vo = 0.0, s_vi = 0.0;
     struct OIn {
       dbl2 fh, vy[KS];
@@ -1597,10 +1381,6 @@ struct MpcR16 {
   // restaging those after every pass is what made the first attempt at this a loss (round 2).
   // Same terms as the owner's passes; the sums over the stages are formed per row and then
   // over the rows.  Real calls, like the trial pass.
-#ifndef FB_R16_COOP_PROX
-#define FB_R16_COOP_PROX 1
-#endif
-  static constexpr bool kCoopProx = FB_R16_COOP_PROX != 0 && kCoopTrials;
   struct OwnerView {
     double* R0;        // the owner's records, this lane's offset within ITS row included
     const double* P0;  // the owner's matrix copies, likewise
@@ -1956,16 +1736,13 @@ struct MpcR16 {
     return kBothInfeasible;
   }
 
-  // ---- load_guess() for the owner's QP, run by all rows (FB_R16_COOP_LOAD) ---------------
+  // ---- load_guess() for the owner's QP, run by all rows (kCoopLoad) -----------------------
   // Row q packs stages q, q + QW, ...: the stage's matrices and vectors from the caller's
   // arrays, its records, y = b - A z.  Whether a stage shares the matrix copy of the stage
   // before it is decided by reading that stage's matrices as well (the sequential pass
   // carries them from stage to stage); the offsets of the copies in use - "this stage's own"
   // or "whatever the stage before uses" - follow from one scan over the stages afterwards.
-#ifndef FB_R16_COOP_LOAD
-#define FB_R16_COOP_LOAD 1
-#endif
-  static constexpr bool kCoopLoad = FB_R16_COOP_LOAD != 0 && kCoopProx && !KEEP;
+  static constexpr bool kCoopLoad = !KEEP;
   struct LoadSums {
     double c2m, hm;
     int nzm;
@@ -2377,7 +2154,7 @@ struct MpcR16 {
   // residual r - V dx orders above eps |V| |dx|.  The REFERENCE form of those instances did the same until round
   // 6, and there it showed: a warm-started one-step solve of a (3, 12, 1, 17) QP left 1.4e-6 where the oracle
   // leaves 2e-8 and took a second proximal iteration (the option closed it: one step refined, the oracle's
-  // counts); that form now substitutes (newton_core: FB_R16_SUBST_REF_FORM) and takes the oracle's counts as it
+  // counts); that form now substitutes (newton_core: kSubst) and takes the oracle's counts as it
   // is.  The ROW-PAIR instances and the flat-vector kernel substitute since round 5 (kSubst, fb_row16.h
   // subst_rows): for all of those the option only ever makes a solve more accurate than the reference's.
   // refine_step() solves
@@ -2391,14 +2168,14 @@ struct MpcR16 {
   // Real calls (no inlining): a second copy of the sweeps inside the solver loop would cost the common
   // path its register allocation.  They take scalars only, like the cooperative passes.
   static __device__ __attribute__((noinline)) StepOut refine_row_form(double* R0, const double* P0, lds_iptr po,
-                                                                      lds_ptr lds_row, pk_ptr Lp, int N_, bool bnd, int loff,
+                                                                      lds_ptr lds_row, lds_ptr Lp, int N_, bool bnd, int loff,
                                                                       double sigma, double alpha) {
     C c;
     c.tid = threadIdx.x & (LPQ - 1);
     return newton_core<true, true>(c, R0, P0, po, lds_row, Lp, N_, bnd, 0.0, loff, sigma, alpha);
   }
   static __device__ __attribute__((noinline)) StepOut refine_ref_form(double* R0, const double* P0, lds_iptr po,
-                                                                      lds_ptr lds_row, pk_ptr Lp, int N_, bool bnd, int loff,
+                                                                      lds_ptr lds_row, lds_ptr Lp, int N_, bool bnd, int loff,
                                                                       double sigma, double alpha) {
     C c;
     c.tid = threadIdx.x & (LPQ - 1);
@@ -2468,7 +2245,7 @@ struct MpcR16 {
   // ADJ: the adjoint's step (adjoint_step): barrier_terms<true> in both sweeps, nothing else changes.
   template <bool ROW, bool REFINE, bool ADJ = false>
   static FB_DEV StepOut newton_core(const C& c, double* const R0, const double* const P0, const lds_iptr po,
-                                    lds_ptr lds_row, pk_ptr Lp, const int N_, const bool bnd, const double tp,
+                                    lds_ptr lds_row, lds_ptr Lp, const int N_, const bool bnd, const double tp,
                                     int loff, double sigma, double alpha) {
     // Locals only below: the lambdas capture no object.
     // (round 6) The REFERENCE form of the costate step substitutes with the factor on the one-row instances as
@@ -2477,10 +2254,7 @@ struct MpcR16 {
     // QP, nx > N nu: 1.4e-6 left of the Newton system where the oracle leaves 2e-8, one proximal iteration more
     // than the oracle - LABNOTES R6.5).  The ROW form - bounds, sparse rows: the headline - keeps the explicit
     // inverse and its independent streams.  A per-template choice: the two forms are two copies of this function.
-#ifndef FB_R16_SUBST_REF_FORM
-#define FB_R16_SUBST_REF_FORM 1
-#endif
-    constexpr bool kSubst = MpcR16::kSubst || (FB_R16_SUBST_REF_FORM != 0 && !ROW);
+    constexpr bool kSubst = MpcR16::kSubst || !ROW;
     constexpr bool kAsmFwdX = MpcR16::kAsmImages && !kSubst;  // the forward stage's hand-written blocks move COLUMNS of the inverse
     const int r = c.tid;
     lds_ptr Tr = lds_row;
@@ -2502,7 +2276,6 @@ struct MpcR16 {
     double wln = 0.0;  // WLN of the previous stage = wl of this one
     // offsets of the matrix copies of stages i and i+1 (fetched a stage ahead)
     int pcur = po[0], pnxt = po[N_ > 0 ? 1 : 0];
-    [[maybe_unused]] bool dma_out = false;  // (kPackDma) this QP's next matrix copy is on its way into the image
     double* const Rd = spare_of(R0, N_);  // (kTailCut: the padding lanes' place for the last constraint slot)
     load_fwd(R0, Rd, cur);  // (loff: the copy resident in LDS)
     // ===================== forward sweep ===================================
@@ -2510,7 +2283,6 @@ struct MpcR16 {
       FB_PHASE(fwd_top);
       double* R = R0 + (long)i * kRec;
       const int pnn = po[i + 2 <= N_ ? i + 2 : N_];
-      if constexpr (kPackDma) stage_pack_dma_wait(dma_out);
       stage_pack_s(c, P0, Lp, loff, pcur);
       // Lane id made opaque per iteration: (ro == j) selects are then recomputed
       // where used instead of being hoisted out of the loop as 16+ live masks.
@@ -2636,9 +2408,9 @@ struct MpcR16 {
       double XC[NS];
       // (one-row instances, round 6: factorisation, inverse and W solve as ONE pass over the pivots -
       // fb_row16.h, chol_inv_cols_solve; bitwise the two-pass results)
-      constexpr bool kFusedChol = FB_CHOL_FUSED != 0 && !kSubst && kFmacDpp<RQ> && FB_FMAC_DPP_SOLVE != 0;
+      constexpr bool kFusedChol = !kSubst && kFmacDpp<RQ>;
       // (row-pair instances: factorisation and W solve as one pass likewise, the factor left as chol_rows leaves it)
-      constexpr bool kFusedCholSubst = FB_CHOL_FUSED != 0 && kSubst && kFmacDpp<RQ> && !kPackDma;
+      constexpr bool kFusedCholSubst = kSubst && kFmacDpp<RQ>;
       if constexpr (kFusedChol) {
         ldl<pABr, NS>(Lp, W);  // [A B] row r, the right-hand side of the W solve
         ok = chol_inv_cols_solve<NS, RQ>(K, XC, W, ro, sigma) && ok;
@@ -2652,15 +2424,6 @@ struct MpcR16 {
       FB_STAMP_LAP(3);
       FB_SB();
       if constexpr (!kFusedChol && !kFusedCholSubst) ldl<pABr, NS>(Lp, W);  // [A B] row r, the right-hand side of the W solve
-      if constexpr (kPackDma) {
-        // the image has been read for the last time in this stage: the next stage's copy on its way
-        dma_out = i < N_ && pnxt != loff;
-        if (dma_out) {
-          c.sync();
-          stage_pack_dma(P0 + pnxt, Lp);
-          loff = pnxt;
-        }
-      }
       if constexpr (kSubst) {
         if constexpr (!kFusedCholSubst) tri_solve_right<NS, RQ>(K, W, ro);
       } else if constexpr (!kFusedChol) {
@@ -2738,7 +2501,7 @@ struct MpcR16 {
         FB_SB();
         FB_STAMP_LAP(7);
         double T[NX];
-        if constexpr (FB_CHOL_FUSED != 0 && kFmacDpp<RQ>) {
+        if constexpr (kFmacDpp<RQ>) {
           ok = chol_inv_cols<NX, RQ>(Pn, T, ro, sigma) && ok;
           if (!ok) { ret.loff = loff; return ret; }
           FB_SB();
@@ -2805,33 +2568,28 @@ struct MpcR16 {
       if constexpr (!ROW) ldv<fP, nPs + 1>(R, Pp);
     };
     BwdIn bin;
-    dma_out = false;
     pcur = po[N_];
     {
       const double* R = R0 + (long)N_ * kRec;
       load_fac(R);
-      if constexpr (!kAbcFromLds) ldv<pABc, NX>(P0 + pcur, Ac);
       load_bwd<REFINE>(R, Rd, bin);
     }
-    // (kAbcFromLds) where this lane finds column r of [A B] in the staged image: slot pABr + r, entry j at + 2 j
+    // where this lane finds column r of [A B] in the staged image: slot pABr + r, entry j at + 2 j
     // (lanes without a row or column - NS < LPQ: the <18,5,10> instance - have no such slot: they read lane 0's
     // and get the zero the column slots of the matrix copy hold for them)
     const int rcol = (NS < LPQ && r >= NS) ? 0 : r;
-    [[maybe_unused]] const lds_ptr abcol = (kTrimAb || !kKinLds) ? Lp - 2 * r + pair_at(pABr / 2) + (rcol >> 1) * kAbPair + (rcol & 1)
+    const lds_ptr abcol = (kTrimAb || !kKinLds) ? Lp - 2 * r + pair_at(pABr / 2) + (rcol >> 1) * kAbPair + (rcol & 1)
                                                                  : Lp - 2 * r + ((pABr + rcol) >> 1) * kPackPair + ((pABr + rcol) & 1);
     for (int i = N_; i >= 0; i--) {
       FB_PHASE(bwd_top);
       double* R = R0 + (long)i * kRec;
       const double* Rp = i > 0 ? R - kRec : R;  // the stage fetched next (stage 0 once more at the end)
-      if constexpr (kPackDma) stage_pack_dma_wait(dma_out);
       stage_pack_s(c, P0, Lp, loff, pcur);
-      if constexpr (kAbcFromLds) {
-        // the columns of this stage's [A B] out of the rows just staged (entries j < NX of lanes j: rows of A, B)
-        sfor<0, NX>([&](auto J) {
-          const double e = abcol[2 * decltype(J)::value];
-          Ac[decltype(J)::value] = (NS < LPQ && r >= NS) ? 0.0 : e;
-        });
-      }
+      // the columns of this stage's [A B] out of the rows just staged (entries j < NX of lanes j: rows of A, B)
+      sfor<0, NX>([&](auto J) {
+        const double e = abcol[2 * decltype(J)::value];
+        Ac[decltype(J)::value] = (NS < LPQ && r >= NS) ? 0.0 : e;
+      });
       pcur = po[i > 0 ? i - 1 : 0];
       int ro = r;
       asm volatile("" : "+v"(ro));
@@ -2860,19 +2618,7 @@ struct MpcR16 {
       load_fac(Rp);
       FB_SB();
       // u = [A B]' dl(i+1) (zero at the terminal stage: lp = 0)
-#ifndef FB_R16_BWD_FUSED_BC
-#define FB_R16_BWD_FUSED_BC 1  // 0: the round-5 form (a copy of the vector in every lane, plain dot products) for A/B runs
-#endif
-      constexpr bool kBwdFusedBc = FB_R16_BWD_FUSED_BC != 0;
-      double u;
-      if constexpr (kBwdFusedBc) {
-        u = bc_dot<0, NX, RQ>(Ac, lp);  // (round 6: was bc_all + dot4 - the same sums, 12 moves fewer)
-      } else {
-        double lpb[NX];
-        bc_all<NX, RQ>(lp, lpb);
-        u = dot4<NX>(Ac, lpb);
-      }
-      if constexpr (!kAbcFromLds) ldv<pABc, NX>(P0 + pcur, Ac);
+      const double u = bc_dot<0, NX, RQ>(Ac, lp);  // (the same sums as bc_all + dot4, 12 moves fewer)
       c.sync();
       // column r and row r of inv(Lc), row r of inv(Pi)
       double XC[NS], XR[NS];
@@ -2922,30 +2668,20 @@ struct MpcR16 {
         if (!rx) dli = 0.0;
       }
       FB_SB();
-      // ([dx; du](i) reaches the four products below through the fused broadcast-FMA: round 6, was a copy of
-      // it in every lane - bc_all, 16 moves - and plain dot products; bitwise the same sums)
+      // ([dx; du](i) reaches the four products below through the fused broadcast-FMA: bitwise the sums of a copy
+      // of it in every lane - bc_all, 16 moves - and plain dot products)
+      // (dzb: unused - that copy.  Without it the compiler exchanges two independent moves in refine_row_form of
+      // the row-pair instances; it stays so that retiring the switch left the compiled library bit-identical,
+      // and goes with the next change of this kernel's code.)
       [[maybe_unused]] double dzb[NS];
-      if constexpr (!kBwdFusedBc) bc_all<NS, RQ>(dzu, dzb);
       if constexpr (kKinLds) ldl<pK, NS>(Lp, Hr);
       else ldv<pK, NS>(P0 + loff, Hr);
       ldl<pABr, NS>(Lp, AB);
-      if constexpr (kPackDma) {
-        // (pcur is the stage below's already) its copy on its way while this stage finishes
-        dma_out = i > 0 && pcur != loff;
-        if (dma_out) {
-          c.sync();
-          stage_pack_dma(P0 + pcur, Lp);
-          loff = pcur;
-        }
-      }
       FB_STAMP_LAP(9);
       // ---- A dz and dv (:329-341) through the LDS copy of C
       C_to_lds(c, Cl, Cc_, r);
       double dvs[KS];
-      auto c_rows = [&](auto&& f) {
-        if constexpr (kBwdFusedBc) rows_of_C_times_lane(Cl, dzu, r, f);
-        else rows_of_C_times(Cl, dzb, r, f);
-      };
+      auto c_rows = [&](auto&& f) { rows_of_C_times_lane(Cl, dzu, r, f); };
       c_rows([&](auto S_, bool valid, double a) {
         constexpr int sl = decltype(S_)::value;
         double d = 0.0;
@@ -2977,9 +2713,7 @@ struct MpcR16 {
       // ---- wz = H dz + G'dl + A'dv; (G'dl)_x = [A B]'dl(i+1) - dl(i)
       double w;
       {
-        double hdz;
-        if constexpr (kBwdFusedBc) hdz = bc_dot<0, NS, RQ>(Hr, dzu);
-        else hdz = dot4<NS>(Hr, dzb);
+        const double hdz = bc_dot<0, NS, RQ>(Hr, dzu);
         double p[4] = {hdz + (ROW ? u : u - dli), 0.0, 0.0, 0.0};
         bc_cols_dot<NC, RQ>(Cc_, dvs, p);
         w = (p[0] + p[1]) + (p[2] + p[3]);
@@ -3002,9 +2736,7 @@ struct MpcR16 {
       double wlv = 0.0;  // wl(i + 1)
       if (i < N_) {
         // l block i+1: wl = -(A dx + B du - dx(i+1)); trial norms (full_residual.cc:60-66)
-        double abz;
-        if constexpr (kBwdFusedBc) abz = bc_dot<0, NS, RQ>(AB, dzu);
-        else abz = dot4<NS>(AB, dzb);
+        const double abz = bc_dot<0, NS, RQ>(AB, dzu);
         wlv = rx ? -(abz - dzn) : 0.0;
         if constexpr (REFINE) wlv += cu.dwl[1];  // (dzn is the correction's: wl(i + 1) of the step + its increment)
         const double lr = lrn[1] + wlv;

@@ -284,12 +284,6 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_kernel(
   const long long clk0 = __builtin_readcyclecounter(), rt0 = wall_clock64();
 #endif
   const int lane = threadIdx.x;
-#if defined(FB_SCRATCH_PAD)
-  // (diagnostic knob: FB_SCRATCH_PAD more bytes of private memory per lane, nothing else changed - the
-  // runtime's handling of a dispatch depends on its scratch size, LABNOTES R6.3)
-  volatile char scratch_pad_[FB_SCRATCH_PAD];
-  scratch_pad_[threadIdx.x % FB_SCRATCH_PAD] = 1;
-#endif
   typename P::C ctx;
   ctx.tid = lane & (P::LPQ - 1);
   P p;
@@ -305,9 +299,7 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_kernel(
     qu.sweep = reinterpret_cast<const SweepArgs*>(dbg);
     qu.out = out;
   }
-#if !defined(FB_R16_NO_BIND_IDLE)  // (the switch exists to show what the rows' unbound policy objects did: DESIGN.md section 7)
-  p.bind_idle(qu.lds(), qu.pack_lds(), qu.lpo(), N);
-#endif
+  p.bind_idle(qu.lds(), qu.pack_lds(), qu.lpo(), N);  // (what the rows' unbound policy objects did: DESIGN.md section 7)
   if constexpr (DBG) {
     if (qu.fetch(p) >= 0) newton_probe(p, ctx, opts, dbg);
   } else {

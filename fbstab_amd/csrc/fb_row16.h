@@ -153,10 +153,7 @@ typedef CtxRow<1> Ctx16;
 // products below spell the order out and fence it.
 #define FB_SB() __builtin_amdgcn_sched_barrier(0)
 
-#ifndef FB_BC_AHEAD
-#define FB_BC_AHEAD 4
-#endif
-constexpr int kBcAhead = FB_BC_AHEAD;  // broadcasts in flight ahead of their consumers
+constexpr int kBcAhead = 4;  // broadcasts in flight ahead of their consumers
 
 // Runs consume(I, mov(I)) for I in [0, CNT) with the mov of I + kBcAhead issued
 // before the consumer of I.
@@ -203,9 +200,6 @@ FB_DEV void bc_pipeline(Mov&& mov, Use&& use) {
 #ifndef FB_FMAC_DPP
 #define FB_FMAC_DPP 1
 #endif
-#ifndef FB_FMAC_DPP_R2
-#define FB_FMAC_DPP_R2 1  // row pairs too: the spread halves are ordinary registers, each its own group
-#endif
 // (NEG: acc -= ...: the source modifier of the multiplier, no instruction of its own)
 // FB_FMAC_GUARD_NOP = 1: the first instruction of every group carries the s_nop 1 itself - safe by
 // construction, 155 s_nop per forward stage, 6 % of the arithmetic core's time
@@ -235,8 +229,9 @@ FB_DEV void fmac_bc(double& acc, double src, double mult) {
     asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(mult), "n"(J));
   FB_SB();
 }
+// (row pairs too: the spread halves are ordinary registers, each its own group)
 template <int R>
-constexpr bool kFmacDpp = FB_FMAC_DPP != 0 && (R == 1 || FB_FMAC_DPP_R2 != 0);
+constexpr bool kFmacDpp = FB_FMAC_DPP != 0;
 // The same for a spread source: lane J of the QP is lane J of the value itself (R = 1), or lane
 // J & 15 of the even row's copy (J < 16) / of the odd row's (J >= 16), which spread() left in
 // both rows of the pair.  J0: the lane the group starts at - the first reader of each copy is
@@ -251,12 +246,7 @@ FB_DEV void fmac_bcs(double& acc, const Spread<R>& s, double mult) {
     else fmac_bc<J - 16, first, NEG, true>(acc, s.hi, mult);
   }
 }
-#ifndef FB_FMAC_DPP_DOT
-#define FB_FMAC_DPP_DOT 1   // the broadcast dot products (bc_dot) too
-#endif
-#ifndef FB_FMAC_DPP_SOLVE
-#define FB_FMAC_DPP_SOLVE 1 // tri_inv_cols_solve, where one broadcast feeds two FMAs (measured: +1.3 % on top)
-#endif
+// (the broadcast dot products - bc_dot - and tri_inv_cols_solve, where one broadcast feeds two FMAs, use it too)
 
 // 1/sqrt(d) to full double precision: v_rsq_f64 seed (~2^-24 relative) and one
 // third-order step r(1 + e/2 + 3e^2/8), e = 1 - d r^2 (error ~e^3): four
@@ -407,7 +397,7 @@ FB_DEV void tri_inv_cols_solve(const double (&a)[N], double (&x)[N], double (&w)
     }
     const double nx = -x[k], nw = -w[k];
     if constexpr (k + 1 < N) dg = bcr<R, k + 1>(a[k + 1]);
-    if constexpr (kFmacDpp<R> && FB_FMAC_DPP_SOLVE != 0) {
+    if constexpr (kFmacDpp<R>) {
       const Spread<R> aks = spread<R>(a[k]);
       FB_SB();
       sfor<0, N - k - 1>([&](auto I) {
@@ -452,9 +442,6 @@ FB_DEV void tri_inv_cols_solve(const double (&a)[N], double (&x)[N], double (&w)
 // (the diagonal slot is NOT the reciprocal here: nothing reads it), x = column r of inv(L), w = row r of
 // B inv(L)'.  The next pivot's dependent chain is spread over three times as many independent
 // instructions as in chol_rows.
-#ifndef FB_CHOL_FUSED
-#define FB_CHOL_FUSED 1
-#endif
 // WITH_X / WITH_W: which of the two riders of the factorisation run (the inverse's column, the right-solve).
 // PARK: lane j's a[j] receives 1 / L[j][j] as chol_rows leaves it - for callers that go on to SUBSTITUTE with
 // the rows of the factor (the row-pair instances: subst_rows reads the reciprocal out of the row).
@@ -615,7 +602,7 @@ FB_DEV double subst_cols_t(const double (&a)[N], double b, int r) {
 template <int B, int E, int R = 1, int N>
 FB_DEV double bc_dot(const double (&m)[N], double v, double init = 0.0) {
   double p[4] = {init, 0.0, 0.0, 0.0};
-  if constexpr (kFmacDpp<R> && FB_FMAC_DPP_DOT != 0) {
+  if constexpr (kFmacDpp<R>) {
     const Spread<R> vs = spread<R>(v);
     sfor<0, E - B>([&](auto I) {
       constexpr int i = decltype(I)::value;
@@ -638,7 +625,7 @@ FB_DEV double bc_dot(const double (&m)[N], double v, double init = 0.0) {
 template <int NC, int R, bool NEG = false, int NSRC>
 FB_DEV void bc_cols_dot(const double (&C)[NC], const double (&src)[NSRC], double (&p)[4]) {
   constexpr int LPQ = 16 * R;
-  if constexpr (kFmacDpp<R> && FB_FMAC_DPP_DOT != 0) {
+  if constexpr (kFmacDpp<R>) {
     sfor<0, (NC + LPQ - 1) / LPQ>([&](auto S_) {
       constexpr int sl = decltype(S_)::value;
       const Spread<R> ss = spread<R>(src[sl]);

@@ -83,14 +83,12 @@ __device__ __forceinline__ MpcData mpc_data_of(const MpcBatchArgs& data, long q)
   return D;
 }
 
-#ifndef FB_MPC_MIN_WAVES
-#define FB_MPC_MIN_WAVES 1
-#endif
+constexpr int kMpcMinWaves = 1;  // wavefronts per SIMD the flat-vector MPC kernels are compiled for
 // DBG: the Newton-step probe; TRACE: `dbg` is the trace buffer of
 // fbstab_hip_mpc_solve_traced (see Solver in fb_algorithm.h); WG: the stage tile and the
 // work matrices in global scratch (MpcLayout::wglobal: shapes beyond the LDS).
 template <int NT, bool DBG, bool TRACE = false, bool WG = false>
-__global__ __launch_bounds__(NT, FB_MPC_MIN_WAVES) void fbstab_mpc_kernel(MpcLayout lay, MpcBatchArgs data,
+__global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_kernel(MpcLayout lay, MpcBatchArgs data,
                                                         VarBatchArgs x,
                                                         fbstab_solver_out_t* out,
                                                         fbstab_options_t opts, double* scratch,
@@ -133,7 +131,7 @@ struct MpcGradArgs {
   long long stride[FBSTAB_MPC_NSEQ];
 };
 template <int NT, bool WG>
-__global__ __launch_bounds__(NT, FB_MPC_MIN_WAVES) void fbstab_mpc_adjoint_kernel(
+__global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_adjoint_kernel(
     MpcLayout lay, MpcBatchArgs data, VarBatchArgs x, VarBatchArgs seed, MpcGradArgs grad, VarBatchArgs adj,
     int* status, double sigma, double alpha, double* scratch, int* counter, int batch) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -320,11 +318,9 @@ __global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_probe_kern
 // One wavefront per dense QP for every phase (fb_dense_wave.h; nz + nl <= 64): the KKT
 // matrix in registers, two wavefronts per SIMD.  scratch: one region of
 // lay.ws_doubles per workgroup (A' and the multipliers).  DBG: the Newton-step probe.
-#ifndef FB_DW_MIN_WAVES
-#define FB_DW_MIN_WAVES 2
-#endif
+constexpr int kDwMinWaves = 2;
 template <bool DBG>
-__global__ __launch_bounds__(64, FB_DW_MIN_WAVES) void fbstab_dense_wave_kernel(DenseWaveLayout lay, DenseBatchArgs data,
+__global__ __launch_bounds__(64, kDwMinWaves) void fbstab_dense_wave_kernel(DenseWaveLayout lay, DenseBatchArgs data,
                                                                    VarBatchArgs x, fbstab_solver_out_t* out,
                                                                    fbstab_options_t opts, int* counter, int batch,
                                                                    double* scratch, double* dbg) {
@@ -423,7 +419,7 @@ __global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_adjoint_ke
 // The one-wavefront policy (fb_dense_wave.h; nz + nl <= 64): K in registers, A'Gamma A on the matrix cores, the
 // handle's own scratch region per workgroup.  newton_step<true> factors by the pivoted rule whatever the handle's
 // order, and the fallback counters of the last solve are neither passed nor reset.
-__global__ __launch_bounds__(64, FB_DW_MIN_WAVES) void fbstab_dense_wave_adjoint_kernel(
+__global__ __launch_bounds__(64, kDwMinWaves) void fbstab_dense_wave_adjoint_kernel(
     DenseWaveLayout lay, DenseBatchArgs data, VarBatchArgs x, VarBatchArgs seed, DenseGradArgs grad, VarBatchArgs adj,
     int* status, double sigma, double alpha, int* counter, int batch, double* scratch) {
   extern __shared__ __attribute__((aligned(16))) double smem[];

@@ -270,7 +270,7 @@ def test_warm_started_second_solve_on_every_mpc_instance(hip, oracle, oracle_fma
     one that FAILED this test when it was written: the one-row instances multiplied with an explicitly inverted
     factor in the reference form of the costate step too, a warm-started one-step solve left 1.4e-6 of its
     Newton system behind (the oracle's substitution: 2e-8) and took a second proximal iteration.  That form
-    substitutes since (fb_mpc_r16.h: FB_R16_SUBST_REF_FORM; LABNOTES R6.5) and the shape passes as it is, with
+    substitutes since (fb_mpc_r16.h: newton_core; LABNOTES R6.5) and the shape passes as it is, with
     no step refined."""
     (N, nx, nu, nc), kern = _MPC_SHAPES[idx]
     rng = np.random.default_rng(9000 + idx)
