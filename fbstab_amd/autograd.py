@@ -28,39 +28,47 @@ from .hip_api import DENSE_ARR, MPC_SEQ
 __all__ = ["MpcSolveFunction", "solve_mpc", "DenseSolveFunction", "solve_dense"]
 
 
+def _forward(names, ctx, solver, sigma, arrs):
+    data = {k: a.detach().contiguous() for k, a in zip(names, arrs)}
+    first = data[names[0]]  # (Q and H are never empty)
+    B, dev = first.shape[0], first.device
+    z = torch.zeros((B, solver.nz), dtype=torch.float64, device=dev)
+    l = torch.zeros((B, solver.nl), dtype=torch.float64, device=dev)
+    v = torch.zeros((B, solver.nv), dtype=torch.float64, device=dev)
+    y = torch.zeros((B, solver.nv), dtype=torch.float64, device=dev)
+    out = solver.Solve(data, z, l, v, y)
+    ctx.solver, ctx.sigma = solver, sigma
+    ctx.save_for_backward(*[data[k] for k in names], z, l, v, out)
+    ctx.mark_non_differentiable(out)
+    return z, l, v, out
+
+
+def _backward(names, ctx, gz, gl, gv, gout):
+    need = ctx.needs_input_grad[2:]
+    want = [k for k, n in zip(names, need) if n]
+    if not want:
+        return (None, None) + (None,) * len(names)
+    saved = ctx.saved_tensors
+    data = dict(zip(names, saved[:len(names)]))
+    z, l, v, out = saved[len(names):]
+    g = ctx.solver.Adjoint(data, z, l, v, gz.contiguous(), gl.contiguous(), gv.contiguous(), sigma=ctx.sigma,
+                           want=want)
+    eflag = out[:, 0:4].contiguous().view(torch.int32)[:, 0]  # SolverOut::eflag, on the device
+    keep = ((eflag == 0) & (g["status"] == 0))[:, None]
+    grads = [torch.where(keep, g[k], torch.zeros_like(g[k])) if k in g else None for k in names]
+    return (None, None) + tuple(grads)
+
+
 class MpcSolveFunction(torch.autograd.Function):
     """apply(solver, sigma, *sequences in MPC_SEQ order) -> (z, l, v, out)."""
 
     @staticmethod
     def forward(ctx, solver, sigma, *seqs):
-        data = {k: s.detach().contiguous() for k, s in zip(MPC_SEQ, seqs)}
-        B = data["x0"].shape[0]
-        dev = data["x0"].device
-        z = torch.zeros((B, solver.nz), dtype=torch.float64, device=dev)
-        l = torch.zeros((B, solver.nl), dtype=torch.float64, device=dev)
-        v = torch.zeros((B, solver.nv), dtype=torch.float64, device=dev)
-        y = torch.zeros((B, solver.nv), dtype=torch.float64, device=dev)
-        out = solver.Solve(data, z, l, v, y)
-        ctx.solver, ctx.sigma = solver, sigma
-        ctx.save_for_backward(*[data[k] for k in MPC_SEQ], z, l, v, out)
-        ctx.mark_non_differentiable(out)
-        return z, l, v, out
+        return _forward(MPC_SEQ, ctx, solver, sigma, seqs)
 
     @staticmethod
     def backward(ctx, gz, gl, gv, gout):
-        need = ctx.needs_input_grad[2:]
-        want = [k for k, n in zip(MPC_SEQ, need) if n]
-        if not want:
-            return (None, None) + (None,) * len(MPC_SEQ)
-        saved = ctx.saved_tensors
-        data = dict(zip(MPC_SEQ, saved[:len(MPC_SEQ)]))
-        z, l, v, out = saved[len(MPC_SEQ):]
-        g = ctx.solver.Adjoint(data, z, l, v, gz.contiguous(), gl.contiguous(), gv.contiguous(), sigma=ctx.sigma,
-                               want=want)
-        eflag = out[:, 0:4].contiguous().view(torch.int32)[:, 0]  # SolverOut::eflag, on the device
-        keep = ((eflag == 0) & (g["status"] == 0))[:, None]
-        grads = [torch.where(keep, g[k], torch.zeros_like(g[k])) if k in g else None for k in MPC_SEQ]
-        return (None, None) + tuple(grads)
+        return _backward(MPC_SEQ, ctx, gz, gl, gv, gout)
 
 
 def solve_mpc(solver, data, sigma: float = 0.0):
@@ -74,34 +82,11 @@ class DenseSolveFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, solver, sigma, *arrs):
-        data = {k: a.detach().contiguous() for k, a in zip(DENSE_ARR, arrs)}
-        B = data["f"].shape[0]
-        dev = data["f"].device
-        z = torch.zeros((B, solver.nz), dtype=torch.float64, device=dev)
-        l = torch.zeros((B, solver.nl), dtype=torch.float64, device=dev)
-        v = torch.zeros((B, solver.nv), dtype=torch.float64, device=dev)
-        y = torch.zeros((B, solver.nv), dtype=torch.float64, device=dev)
-        out = solver.Solve(data, z, l, v, y)
-        ctx.solver, ctx.sigma = solver, sigma
-        ctx.save_for_backward(*[data[k] for k in DENSE_ARR], z, l, v, out)
-        ctx.mark_non_differentiable(out)
-        return z, l, v, out
+        return _forward(DENSE_ARR, ctx, solver, sigma, arrs)
 
     @staticmethod
     def backward(ctx, gz, gl, gv, gout):
-        need = ctx.needs_input_grad[2:]
-        want = [k for k, n in zip(DENSE_ARR, need) if n]
-        if not want:
-            return (None, None) + (None,) * len(DENSE_ARR)
-        saved = ctx.saved_tensors
-        data = dict(zip(DENSE_ARR, saved[:len(DENSE_ARR)]))
-        z, l, v, out = saved[len(DENSE_ARR):]
-        g = ctx.solver.Adjoint(data, z, l, v, gz.contiguous(), gl.contiguous(), gv.contiguous(), sigma=ctx.sigma,
-                               want=want)
-        eflag = out[:, 0:4].contiguous().view(torch.int32)[:, 0]  # SolverOut::eflag, on the device
-        keep = ((eflag == 0) & (g["status"] == 0))[:, None]
-        grads = [torch.where(keep, g[k], torch.zeros_like(g[k])) if k in g else None for k in DENSE_ARR]
-        return (None, None) + tuple(grads)
+        return _backward(DENSE_ARR, ctx, gz, gl, gv, gout)
 
 
 def solve_dense(solver, data, sigma: float = 0.0):

@@ -576,6 +576,118 @@ struct SolverBase {
     return FBSTAB_HIP_OK;
   }
 
+  // ---- staging shared by the solves, the adjoints and the Newton probes of both kinds ----
+  // `out`, `norms` and the adjoints' `status` are host arrays for host-pointer calls and with FBSTAB_HIP_OUT_ON_HOST.
+  static bool out_on_host(int flags) {
+    return !(flags & FBSTAB_HIP_DEVICE_POINTERS) || (flags & FBSTAB_HIP_OUT_ON_HOST);
+  }
+
+  // Problem arrays in: the caller's arr_len.size() base / stride pairs -> the kernel-side ones.  Device pointers
+  // pass through; host arrays are checked and packed into d_arr.
+  int stage_arrays(const double* const* base, const long long* stride, int batch, bool dev_ptrs, hipStream_t s,
+                   const double** kbase, long long* kstride) {
+    const int n = (int)arr_len.size();
+    if (dev_ptrs) {
+      for (int i = 0; i < n; i++) { kbase[i] = base[i]; kstride[i] = stride[i]; }
+      return FBSTAB_HIP_OK;
+    }
+    int rc = ensure_staging();
+    if (rc != FBSTAB_HIP_OK) return rc;
+    for (int i = 0; i < n; i++) {
+      if (stride[i] != 0 && stride[i] < arr_len[i] && batch > 1)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
+      rc = upload(base[i], stride[i], arr_len[i], batch, d_arr[i], &kstride[i], s);
+      if (rc != FBSTAB_HIP_OK) return rc;
+      kbase[i] = d_arr[i];
+    }
+    return FBSTAB_HIP_OK;
+  }
+
+  // The stride rule of the caller's (z, l, v, y): with batch > 1 every QP has its own vectors.
+  int check_var_stride(const long long* stride, int i, int batch) const {
+    if (batch > 1 && stride[i] < var_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
+    return FBSTAB_HIP_OK;
+  }
+
+  // Variables in: the first n vectors of the caller's (z, l, v, y) -> v (the others null).  Device pointers pass
+  // through; host vectors go to d_var, z, l, v uploaded (y is output only).  `check`: the solves' stride rule, on
+  // host vectors only (the adjoints have checked theirs on both paths by now).
+  int stage_vars(double* const* base, const long long* stride, int n, bool check, int batch, bool dev_ptrs,
+                 hipStream_t s, VarBatchArgs* v) {
+    for (int i = 0; i < 4; i++) { v->base[i] = nullptr; v->stride[i] = 0; }
+    if (dev_ptrs) {
+      for (int i = 0; i < n; i++) { v->base[i] = base[i]; v->stride[i] = stride[i]; }
+      return FBSTAB_HIP_OK;
+    }
+    int rc = ensure_staging();
+    if (rc != FBSTAB_HIP_OK) return rc;
+    for (int i = 0; i < n; i++) {
+      if (check) {
+        rc = check_var_stride(stride, i, batch);
+        if (rc != FBSTAB_HIP_OK) return rc;
+      }
+      if (i < 3) {
+        long long st;
+        rc = upload(base[i], stride[i] ? stride[i] : var_len[i], var_len[i], batch, d_var[i], &st, s);
+        if (rc != FBSTAB_HIP_OK) return rc;
+      }
+      v->base[i] = d_var[i];
+      v->stride[i] = var_len[i];
+    }
+    return FBSTAB_HIP_OK;
+  }
+
+  // Where the solve kernel writes its records: `out` itself, or the device side of a host `out`.
+  int stage_out(fbstab_solver_out_t* out, int flags, fbstab_solver_out_t** dev_out) {
+    *dev_out = out;
+    if (!(flags & FBSTAB_HIP_DEVICE_POINTERS)) {
+      int rc = ensure_staging();
+      if (rc != FBSTAB_HIP_OK) return rc;
+      *dev_out = d_out;
+    } else if (flags & FBSTAB_HIP_OUT_ON_HOST) {
+      int rc = ensure_out();
+      if (rc != FBSTAB_HIP_OK) return rc;
+      *dev_out = d_out_only;
+    }
+    return FBSTAB_HIP_OK;
+  }
+
+  // Solve tail, before the final-norms kernel: where that kernel writes (`norms` lives where `out` lives).
+  int stage_norms(double* norms, int flags, double** dev_norms) {
+    *dev_norms = norms;
+    if (out_on_host(flags)) {
+      int rc = ensure_norms();
+      if (rc != FBSTAB_HIP_OK) return rc;
+      *dev_norms = d_norms;
+    }
+    return FBSTAB_HIP_OK;
+  }
+
+  // Solve tail, after it: norms, solution and records back to a host caller, who also gets the wall time of the
+  // call from t0 on; the wait that the flags ask for.
+  int finish_solve(const fbstab_var_batch_t* x, fbstab_solver_out_t* out, const fbstab_solver_out_t* dev_out,
+                   double* norms, int batch, int flags, std::chrono::high_resolution_clock::time_point t0,
+                   hipStream_t s) {
+    if (norms && out_on_host(flags))
+      HIP_TRY(hipMemcpyAsync(norms, d_norms, sizeof(double) * 4 * (size_t)batch, hipMemcpyDeviceToHost, s));
+    if (!(flags & FBSTAB_HIP_DEVICE_POINTERS)) {
+      for (int i = 0; i < 4; i++) {
+        int rc = download(x->base[i], x->stride[i] ? x->stride[i] : var_len[i], var_len[i], batch, d_var[i], s);
+        if (rc != FBSTAB_HIP_OK) return rc;
+      }
+    }
+    if (out_on_host(flags)) {
+      HIP_TRY(hipMemcpyAsync(out, dev_out, sizeof(fbstab_solver_out_t) * batch, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+      for (int i = 0; i < batch; i++) out[i].solve_time = dt;
+    } else if (!(flags & FBSTAB_HIP_ASYNC)) {
+      HIP_TRY(hipStreamSynchronize(s));
+    }
+    return FBSTAB_HIP_OK;
+  }
+
   double last_kernel_ms() {
     if (!timed) return -1.0;
     (void)hipSetDevice(device);
@@ -620,6 +732,127 @@ struct TraceBuf {
       HIP_TRY(hipMemcpy(trace, dev() + 8, sizeof(fbstab_trace_record_t) * (size_t)n, hipMemcpyDeviceToHost));
     return FBSTAB_HIP_OK;
   }
+};
+
+// Host side of fbstab_hip_*_adjoint_batch around the launch: `open` validates what takes the handle's lengths and
+// stages the caller's arrays, `close` brings the results back.  In between the members are the kernel-side
+// arguments.  (The `> 0` guards on arr_len / var_len act on dense handles with nl == 0 only: every length of an MPC
+// handle is positive, fbstab_hip_mpc_create_in_flight refuses N, nx, nu, nc < 1.)
+struct AdjointStage {
+  static constexpr int kMaxArrays = FBSTAB_MPC_NSEQ;
+  static_assert(FBSTAB_DENSE_NARR <= kMaxArrays, "one slot per problem array of either kind");
+  const double* a_base[kMaxArrays];  // problem arrays
+  long long a_stride[kMaxArrays];
+  double* g_base[kMaxArrays];  // their gradients (null: not asked for)
+  long long g_stride[kMaxArrays];
+  VarBatchArgs v, sd, ad;  // point, seeds, adjoints
+  int* d_st = nullptr;     // status
+  hipStream_t s = nullptr;
+
+  // data, grad: base[] / stride[] of the caller's fbstab_*_batch_t and fbstab_*_grad_batch_t (h->arr_len.size()
+  // slots).  With batch == 0 nothing is staged and the caller returns.
+  int open(SolverBase* h, int batch, const double* const* data_base, const long long* data_stride,
+           const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double* const* grad_base,
+           const long long* grad_stride, const fbstab_var_batch_t* adj, int* status, int flags, void* stream) {
+    const int n = (int)h->arr_len.size();
+    const long long* vlen = h->var_len;
+    for (int i = 0; i < n; i++)
+      if (!data_base[i] && h->arr_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
+    for (int i = 0; i < 3; i++)
+      if (!x->base[i] && vlen[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
+    // (the dense entry point has refused this one already)
+    if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null seed pointer (z)");
+    // strides: every QP its own slot (a gradient or adjoint shared by the batch would be written by all of them)
+    for (int i = 0; i < 3; i++) {
+      int rc = h->check_var_stride(x->stride, i, batch);
+      if (rc != FBSTAB_HIP_OK) return rc;
+      if (batch > 1 && seed->base[i] && seed->stride[i] < vlen[i])
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "seed stride smaller than the vector length");
+      if (batch > 1 && adj && adj->base[i] && adj->stride[i] < vlen[i])
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
+    }
+    for (int i = 0; i < n; i++)
+      if (batch > 1 && grad_base[i] && grad_stride[i] < h->arr_len[i])
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
+    if (batch == 0) return FBSTAB_HIP_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    s = stream ? (hipStream_t)stream : h->stream;
+    h_ = h; batch_ = batch; grad_base_ = grad_base; grad_stride_ = grad_stride; adj_ = adj; status_ = status;
+    flags_ = flags;
+    const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
+    int rc = h->stage_arrays(data_base, data_stride, batch, dev_ptrs, s, a_base, a_stride);
+    if (rc != FBSTAB_HIP_OK) return rc;
+    rc = h->stage_vars(x->base, x->stride, 3, false, batch, dev_ptrs, s, &v);
+    if (rc != FBSTAB_HIP_OK) return rc;
+    for (int i = 0; i < 4; i++) { sd.base[i] = ad.base[i] = nullptr; sd.stride[i] = ad.stride[i] = 0; }
+    for (int i = 0; i < 3; i++) {
+      if (vlen[i] == 0) continue;
+      if (dev_ptrs) {
+        sd.base[i] = seed->base[i]; sd.stride[i] = seed->stride[i];
+        if (adj) { ad.base[i] = adj->base[i]; ad.stride[i] = adj->stride[i]; }
+        continue;
+      }
+      if (seed->base[i]) {
+        HIP_TRY(hipMalloc(&d_seed[i].p, sizeof(double) * (size_t)vlen[i] * batch));
+        sd.base[i] = static_cast<double*>(d_seed[i].p);
+        rc = h->upload(seed->base[i], seed->stride[i] ? seed->stride[i] : vlen[i], vlen[i], batch, sd.base[i],
+                       &sd.stride[i], s);
+        if (rc != FBSTAB_HIP_OK) return rc;
+      }
+      if (adj && adj->base[i]) {
+        HIP_TRY(hipMalloc(&d_adj[i].p, sizeof(double) * (size_t)vlen[i] * batch));
+        ad.base[i] = static_cast<double*>(d_adj[i].p); ad.stride[i] = vlen[i];
+      }
+    }
+    for (int i = 0; i < n; i++) {
+      const bool asked = grad_base[i] && h->arr_len[i] > 0;  // (nl == 0: the G and h slots are ignored)
+      if (dev_ptrs) {
+        g_base[i] = asked ? grad_base[i] : nullptr; g_stride[i] = grad_stride[i];
+      } else if (asked) {
+        HIP_TRY(hipMalloc(&d_grad[i].p, sizeof(double) * (size_t)h->arr_len[i] * batch));
+        g_base[i] = static_cast<double*>(d_grad[i].p); g_stride[i] = h->arr_len[i];
+      } else {
+        g_base[i] = nullptr; g_stride[i] = 0;
+      }
+    }
+    d_st = status;
+    if (SolverBase::out_on_host(flags)) {
+      HIP_TRY(hipMalloc(&d_status.p, sizeof(int) * (size_t)batch));
+      d_st = static_cast<int*>(d_status.p);
+    }
+    return FBSTAB_HIP_OK;
+  }
+
+  int close() {
+    if (!(flags_ & FBSTAB_HIP_DEVICE_POINTERS)) {
+      for (size_t i = 0; i < h_->arr_len.size(); i++)
+        if (g_base[i]) {
+          int rc = h_->download(grad_base_[i], grad_stride_[i] ? grad_stride_[i] : h_->arr_len[i], h_->arr_len[i],
+                                batch_, g_base[i], s);
+          if (rc != FBSTAB_HIP_OK) return rc;
+        }
+      for (int i = 0; i < 3; i++)
+        if (ad.base[i]) {
+          int rc = h_->download(adj_->base[i], adj_->stride[i] ? adj_->stride[i] : h_->var_len[i], h_->var_len[i],
+                                batch_, ad.base[i], s);
+          if (rc != FBSTAB_HIP_OK) return rc;
+        }
+    }
+    const bool status_host = SolverBase::out_on_host(flags_);
+    if (status_host) HIP_TRY(hipMemcpyAsync(status_, d_st, sizeof(int) * (size_t)batch_, hipMemcpyDeviceToHost, s));
+    if (status_host || !(flags_ & FBSTAB_HIP_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
+    return FBSTAB_HIP_OK;
+  }
+
+ private:
+  DevBuf d_seed[3], d_adj[3], d_grad[kMaxArrays], d_status;
+  // what `close` copies back to, and how
+  SolverBase* h_ = nullptr;
+  int batch_ = 0, flags_ = 0;
+  double* const* grad_base_ = nullptr;
+  const long long* grad_stride_ = nullptr;
+  const fbstab_var_batch_t* adj_ = nullptr;
+  int* status_ = nullptr;
 };
 
 int check_common(const void* handle, int batch, const void* data, const fbstab_var_batch_t* x,
@@ -869,40 +1102,13 @@ static int mpc_solve_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_bat
   const auto t0 = std::chrono::high_resolution_clock::now();
   MpcBatchArgs a;
   VarBatchArgs v;
-  fbstab_solver_out_t* d_out = out;
-  const bool out_host = dev_ptrs && (flags & FBSTAB_HIP_OUT_ON_HOST);
-  if (dev_ptrs) {
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { a.base[i] = data->base[i]; a.stride[i] = data->stride[i]; }
-    for (int i = 0; i < 4; i++) { v.base[i] = x->base[i]; v.stride[i] = x->stride[i]; }
-    if (out_host) {
-      rc = h->ensure_out();
-      if (rc != FBSTAB_HIP_OK) return rc;
-      d_out = h->d_out_only;
-    }
-  } else {
-    rc = h->ensure_staging();
-    if (rc != FBSTAB_HIP_OK) return rc;
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-      if (data->stride[i] != 0 && data->stride[i] < h->arr_len[i] && batch > 1)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
-      rc = h->upload(data->base[i], data->stride[i], h->arr_len[i], batch, h->d_arr[i], &a.stride[i], s);
-      if (rc != FBSTAB_HIP_OK) return rc;
-      a.base[i] = h->d_arr[i];
-    }
-    for (int i = 0; i < 4; i++) {
-      if (x->stride[i] < h->var_len[i] && batch > 1)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
-      if (i < 3) {
-        long long st;
-        rc = h->upload(x->base[i], x->stride[i] ? x->stride[i] : h->var_len[i], h->var_len[i], batch,
-                       h->d_var[i], &st, s);
-        if (rc != FBSTAB_HIP_OK) return rc;
-      }
-      v.base[i] = h->d_var[i];
-      v.stride[i] = h->var_len[i];
-    }
-    d_out = h->d_out;
-  }
+  fbstab_solver_out_t* d_out;
+  rc = h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = h->stage_vars(x->base, x->stride, 4, true, batch, dev_ptrs, s, &v);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = h->stage_out(out, flags, &d_out);
+  if (rc != FBSTAB_HIP_OK) return rc;
   HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
   int grid = (batch + h->qps_per_wg - 1) / h->qps_per_wg;
   // Record kernels, a batch of no more QPs than the handle has workgroups: one QP per WAVEFRONT (row 0 of
@@ -943,42 +1149,18 @@ static int mpc_solve_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_bat
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(h->ev1, s));
   h->timed = true;
-  const bool norms_host = norms && (!dev_ptrs || out_host);
   if (norms) {
-    double* dn = norms;
-    if (norms_host) {
-      rc = h->ensure_norms();
-      if (rc != FBSTAB_HIP_OK) return rc;
-      dn = h->d_norms;
-    }
+    double* dn;
+    rc = h->stage_norms(norms, flags, &dn);
+    if (rc != FBSTAB_HIP_OK) return rc;
     MpcNormArgs na;
     for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { na.base[i] = a.base[i]; na.stride[i] = a.stride[i]; }
     for (int i = 0; i < 4; i++) { na.x[i] = v.base[i]; na.xstride[i] = v.stride[i]; }
     na.N = h->lay.N; na.nx = h->lay.nx; na.nu = h->lay.nu; na.nc = h->lay.nc;
     hipLaunchKernelGGL(fbstab_mpc_final_norms_kernel, dim3(batch), dim3(64), 0, s, na, h->opts, dn, batch);
     HIP_TRY(hipGetLastError());
-    if (norms_host)
-      HIP_TRY(hipMemcpyAsync(norms, dn, sizeof(double) * 4 * (size_t)batch, hipMemcpyDeviceToHost, s));
   }
-  if (!dev_ptrs) {
-    for (int i = 0; i < 4; i++) {
-      rc = h->download(x->base[i], x->stride[i] ? x->stride[i] : h->var_len[i], h->var_len[i], batch,
-                       h->d_var[i], s);
-      if (rc != FBSTAB_HIP_OK) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, h->d_out, sizeof(fbstab_solver_out_t) * batch, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-    for (int i = 0; i < batch; i++) out[i].solve_time = dt;
-  } else if (out_host) {
-    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(fbstab_solver_out_t) * batch, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-    for (int i = 0; i < batch; i++) out[i].solve_time = dt;
-  } else if (!(flags & FBSTAB_HIP_ASYNC)) {
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  return FBSTAB_HIP_OK;
+  return h->finish_solve(x, out, d_out, norms, batch, flags, t0, s);
 }
 
 int fbstab_hip_mpc_solve_batch_final(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
@@ -1023,9 +1205,10 @@ int fbstab_hip_mpc_receding_sweep(fbstab_mpc_handle_t h, int batch, const fbstab
   // x0 is advanced in place, one state per trajectory: a shared x0 would be written by all of them
   if (batch > 1 && data->stride[FBSTAB_MPC_x0] < h->lay.nx)
     return fail(FBSTAB_HIP_ERR_ARGUMENT, "receding sweep: every trajectory needs its own x0 (stride >= nx)");
-  for (int i = 0; i < 4; i++)
-    if (batch > 1 && x->stride[i] < h->var_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
+  for (int i = 0; i < 4; i++) {
+    rc = h->check_var_stride(x->stride, i, batch);
+    if (rc != FBSTAB_HIP_OK) return rc;
+  }
   if (batch == 0 || steps == 0) return FBSTAB_HIP_OK;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -1117,25 +1300,14 @@ int fbstab_hip_mpc_debug_newton(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t*
                                 const fbstab_var_batch_t* x, double* io) {
   if (!h || !data || !x || !io) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
-  int rc = h->ensure_staging();
-  if (rc != FBSTAB_HIP_OK) return rc;
   hipStream_t s = h->stream;
   MpcBatchArgs a;
   VarBatchArgs v;
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-    rc = h->upload(data->base[i], h->arr_len[i], h->arr_len[i], 1, h->d_arr[i], &a.stride[i], s);
-    if (rc != FBSTAB_HIP_OK) return rc;
-    a.base[i] = h->d_arr[i];
-  }
-  for (int i = 0; i < 4; i++) {
-    long long st;
-    if (i < 3) {
-      rc = h->upload(x->base[i], h->var_len[i], h->var_len[i], 1, h->d_var[i], &st, s);
-      if (rc != FBSTAB_HIP_OK) return rc;
-    }
-    v.base[i] = h->d_var[i];
-    v.stride[i] = h->var_len[i];
-  }
+  // (one packed QP whatever strides the caller wrote: the lengths stand in for them)
+  int rc = h->stage_arrays(data->base, h->arr_len.data(), 1, false, s, a.base, a.stride);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = h->stage_vars(x->base, h->var_len, 4, false, 1, false, s, &v);
+  if (rc != FBSTAB_HIP_OK) return rc;
   const fbk::MpcLayout& L = h->lay;
   const size_t n_io = (size_t)(3 * L.nz + 3 * L.nl + 2 * L.nv + 1);
   DevBuf d_io_buf;
@@ -1171,83 +1343,19 @@ int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t h, int batch, const fbstab_
   int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
   if (rc != FBSTAB_HIP_OK) return rc;
   if (!seed || !grad) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
-    if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
-  for (int i = 0; i < 3; i++)
-    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
-  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null seed pointer (z)");
-  // strides: every QP its own slot (a gradient or adjoint shared by the batch would be written by all of them)
-  for (int i = 0; i < 3; i++) {
-    if (batch > 1 && x->stride[i] < h->var_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
-    if (batch > 1 && seed->base[i] && seed->stride[i] < h->var_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "seed stride smaller than the vector length");
-    if (batch > 1 && adj && adj->base[i] && adj->stride[i] < h->var_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
-  }
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
-    if (batch > 1 && grad->base[i] && grad->stride[i] < h->arr_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
-  if (batch == 0) return FBSTAB_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
-  const bool status_host = !dev_ptrs || (flags & FBSTAB_HIP_OUT_ON_HOST);
+  AdjointStage st;
+  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream);
+  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
+  hipStream_t s = st.s;
   const fbk::MpcLayout& L = h->lay;
-  const long long vlen[3] = {L.nz, L.nl, L.nv};
   MpcBatchArgs a;
-  VarBatchArgs v, sd, ad;
   MpcGradArgs g;
-  for (int i = 0; i < 4; i++) { v.base[i] = sd.base[i] = ad.base[i] = nullptr; v.stride[i] = sd.stride[i] = ad.stride[i] = 0; }
-  DevBuf d_seed[3], d_adj[3], d_grad[FBSTAB_MPC_NSEQ], d_status;
-  if (dev_ptrs) {
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { a.base[i] = data->base[i]; a.stride[i] = data->stride[i]; }
-    for (int i = 0; i < 3; i++) {
-      v.base[i] = x->base[i]; v.stride[i] = x->stride[i];
-      sd.base[i] = seed->base[i]; sd.stride[i] = seed->stride[i];
-      if (adj) { ad.base[i] = adj->base[i]; ad.stride[i] = adj->stride[i]; }
-    }
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { g.base[i] = grad->base[i]; g.stride[i] = grad->stride[i]; }
-  } else {
-    rc = h->ensure_staging();
-    if (rc != FBSTAB_HIP_OK) return rc;
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-      if (data->stride[i] != 0 && data->stride[i] < h->arr_len[i] && batch > 1)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
-      rc = h->upload(data->base[i], data->stride[i], h->arr_len[i], batch, h->d_arr[i], &a.stride[i], s);
-      if (rc != FBSTAB_HIP_OK) return rc;
-      a.base[i] = h->d_arr[i];
-    }
-    for (int i = 0; i < 3; i++) {
-      long long st;
-      rc = h->upload(x->base[i], x->stride[i] ? x->stride[i] : vlen[i], vlen[i], batch, h->d_var[i], &st, s);
-      if (rc != FBSTAB_HIP_OK) return rc;
-      v.base[i] = h->d_var[i]; v.stride[i] = vlen[i];
-      if (seed->base[i]) {
-        HIP_TRY(hipMalloc(&d_seed[i].p, sizeof(double) * (size_t)(vlen[i] > 0 ? vlen[i] : 1) * batch));
-        sd.base[i] = static_cast<double*>(d_seed[i].p);
-        rc = h->upload(seed->base[i], seed->stride[i] ? seed->stride[i] : vlen[i], vlen[i], batch, sd.base[i], &st, s);
-        if (rc != FBSTAB_HIP_OK) return rc;
-        sd.stride[i] = vlen[i];
-      }
-      if (adj && adj->base[i]) {
-        HIP_TRY(hipMalloc(&d_adj[i].p, sizeof(double) * (size_t)(vlen[i] > 0 ? vlen[i] : 1) * batch));
-        ad.base[i] = static_cast<double*>(d_adj[i].p); ad.stride[i] = vlen[i];
-      }
-    }
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-      g.base[i] = nullptr; g.stride[i] = 0;
-      if (grad->base[i] && h->arr_len[i] > 0) {
-        HIP_TRY(hipMalloc(&d_grad[i].p, sizeof(double) * (size_t)h->arr_len[i] * batch));
-        g.base[i] = static_cast<double*>(d_grad[i].p); g.stride[i] = h->arr_len[i];
-      }
-    }
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
+    a.base[i] = st.a_base[i]; a.stride[i] = st.a_stride[i];
+    g.base[i] = st.g_base[i]; g.stride[i] = st.g_stride[i];
   }
-  int* d_st = status;
-  if (status_host) {
-    HIP_TRY(hipMalloc(&d_status.p, sizeof(int) * (size_t)batch));
-    d_st = static_cast<int*>(d_status.p);
-  }
+  VarBatchArgs &v = st.v, &sd = st.sd, &ad = st.ad;
+  int* d_st = st.d_st;
   double sig = sigma > 0.0 ? sigma : 1e-8;  // the reference's default sigma0 (fbstab_algorithm-impl.h:34)
   double alpha = h->opts.alpha;
   HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
@@ -1310,22 +1418,7 @@ int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t h, int batch, const fbstab_
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(h->ev1, s));
   h->timed = true;
-  if (!dev_ptrs) {
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
-      if (g.base[i]) {
-        rc = h->download(grad->base[i], grad->stride[i] ? grad->stride[i] : h->arr_len[i], h->arr_len[i], batch,
-                         g.base[i], s);
-        if (rc != FBSTAB_HIP_OK) return rc;
-      }
-    for (int i = 0; i < 3; i++)
-      if (ad.base[i]) {
-        rc = h->download(adj->base[i], adj->stride[i] ? adj->stride[i] : vlen[i], vlen[i], batch, ad.base[i], s);
-        if (rc != FBSTAB_HIP_OK) return rc;
-      }
-  }
-  if (status_host) HIP_TRY(hipMemcpyAsync(status, d_st, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
-  if (status_host || !(flags & FBSTAB_HIP_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
-  return FBSTAB_HIP_OK;
+  return st.close();
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;
@@ -1515,40 +1608,13 @@ static int dense_solve_impl(fbstab_dense_handle_t h, int batch, const fbstab_den
   const auto t0 = std::chrono::high_resolution_clock::now();
   DenseBatchArgs a;
   VarBatchArgs v;
-  fbstab_solver_out_t* d_out = out;
-  const bool out_host = dev_ptrs && (flags & FBSTAB_HIP_OUT_ON_HOST);
-  if (dev_ptrs) {
-    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) { a.base[i] = data->base[i]; a.stride[i] = data->stride[i]; }
-    for (int i = 0; i < 4; i++) { v.base[i] = x->base[i]; v.stride[i] = x->stride[i]; }
-    if (out_host) {
-      rc = h->ensure_out();
-      if (rc != FBSTAB_HIP_OK) return rc;
-      d_out = h->d_out_only;
-    }
-  } else {
-    rc = h->ensure_staging();
-    if (rc != FBSTAB_HIP_OK) return rc;
-    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
-      if (data->stride[i] != 0 && data->stride[i] < h->arr_len[i] && batch > 1)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
-      rc = h->upload(data->base[i], data->stride[i], h->arr_len[i], batch, h->d_arr[i], &a.stride[i], s);
-      if (rc != FBSTAB_HIP_OK) return rc;
-      a.base[i] = h->d_arr[i];
-    }
-    for (int i = 0; i < 4; i++) {
-      if (x->stride[i] < h->var_len[i] && batch > 1)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
-      if (i < 3) {
-        long long st;
-        rc = h->upload(x->base[i], x->stride[i] ? x->stride[i] : h->var_len[i], h->var_len[i], batch,
-                       h->d_var[i], &st, s);
-        if (rc != FBSTAB_HIP_OK) return rc;
-      }
-      v.base[i] = h->d_var[i];
-      v.stride[i] = h->var_len[i];
-    }
-    d_out = h->d_out;
-  }
+  fbstab_solver_out_t* d_out;
+  rc = h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = h->stage_vars(x->base, x->stride, 4, true, batch, dev_ptrs, s, &v);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = h->stage_out(out, flags, &d_out);
+  if (rc != FBSTAB_HIP_OK) return rc;
   HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));  // (the queue word and the kDenseFallbackSlot counters)
   int grid = h->workgroups < batch ? h->workgroups : batch;
   HIP_TRY(hipEventRecord(h->ev0, s));
@@ -1598,42 +1664,18 @@ static int dense_solve_impl(fbstab_dense_handle_t h, int batch, const fbstab_den
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(h->ev1, s));
   h->timed = true;
-  const bool norms_host = norms && (!dev_ptrs || out_host);
   if (norms) {
-    double* dn = norms;
-    if (norms_host) {
-      rc = h->ensure_norms();
-      if (rc != FBSTAB_HIP_OK) return rc;
-      dn = h->d_norms;
-    }
+    double* dn;
+    rc = h->stage_norms(norms, flags, &dn);
+    if (rc != FBSTAB_HIP_OK) return rc;
     DenseNormArgs na;
     for (int i = 0; i < FBSTAB_DENSE_NARR; i++) { na.base[i] = a.base[i]; na.stride[i] = a.stride[i]; }
     for (int i = 0; i < 4; i++) { na.x[i] = v.base[i]; na.xstride[i] = v.stride[i]; }
     na.nz = h->lay.nz; na.nl = h->lay.nl; na.nv = h->lay.nv;
     hipLaunchKernelGGL(fbstab_dense_final_norms_kernel, dim3(batch), dim3(64), 0, s, na, h->opts, dn, batch);
     HIP_TRY(hipGetLastError());
-    if (norms_host)
-      HIP_TRY(hipMemcpyAsync(norms, dn, sizeof(double) * 4 * (size_t)batch, hipMemcpyDeviceToHost, s));
   }
-  if (!dev_ptrs) {
-    for (int i = 0; i < 4; i++) {
-      rc = h->download(x->base[i], x->stride[i] ? x->stride[i] : h->var_len[i], h->var_len[i], batch,
-                       h->d_var[i], s);
-      if (rc != FBSTAB_HIP_OK) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, h->d_out, sizeof(fbstab_solver_out_t) * batch, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-    for (int i = 0; i < batch; i++) out[i].solve_time = dt;
-  } else if (out_host) {
-    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(fbstab_solver_out_t) * batch, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const double dt = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-    for (int i = 0; i < batch; i++) out[i].solve_time = dt;
-  } else if (!(flags & FBSTAB_HIP_ASYNC)) {
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  return FBSTAB_HIP_OK;
+  return h->finish_solve(x, out, d_out, norms, batch, flags, t0, s);
 }
 
 int fbstab_hip_dense_solve_batch_final(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
@@ -1670,25 +1712,14 @@ int fbstab_hip_dense_debug_newton(fbstab_dense_handle_t h, const fbstab_dense_ba
   if (!h || !data || !x || !io) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
   if (!h->wave && h->lay.k_global) return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "dense probe: K must fit the LDS");
   HIP_TRY(hipSetDevice(h->device));
-  int rc = h->ensure_staging();
-  if (rc != FBSTAB_HIP_OK) return rc;
   hipStream_t s = h->stream;
   DenseBatchArgs a;
   VarBatchArgs v;
-  for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
-    rc = h->upload(data->base[i], h->arr_len[i], h->arr_len[i], 1, h->d_arr[i], &a.stride[i], s);
-    if (rc != FBSTAB_HIP_OK) return rc;
-    a.base[i] = h->d_arr[i];
-  }
-  for (int i = 0; i < 4; i++) {
-    long long st;
-    if (i < 3) {
-      rc = h->upload(x->base[i], h->var_len[i], h->var_len[i], 1, h->d_var[i], &st, s);
-      if (rc != FBSTAB_HIP_OK) return rc;
-    }
-    v.base[i] = h->d_var[i];
-    v.stride[i] = h->var_len[i];
-  }
+  // (one packed QP whatever strides the caller wrote: the lengths stand in for them)
+  int rc = h->stage_arrays(data->base, h->arr_len.data(), 1, false, s, a.base, a.stride);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = h->stage_vars(x->base, h->var_len, 4, false, 1, false, s, &v);
+  if (rc != FBSTAB_HIP_OK) return rc;
   const fbk::DenseLayout& L = h->lay;
   const size_t n_io = (size_t)(3 * L.nz + 3 * L.nl + 2 * L.nv + 1);
   DevBuf d_io_buf;
@@ -1741,84 +1772,18 @@ int fbstab_hip_dense_adjoint_batch(fbstab_dense_handle_t h, int batch, const fbs
   }
   int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
   if (rc != FBSTAB_HIP_OK) return rc;
-  for (int i = 0; i < FBSTAB_DENSE_NARR; i++)
-    if (!data->base[i] && h->arr_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
-  for (int i = 0; i < 3; i++)
-    if (!x->base[i] && h->var_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
-  // strides: every QP its own slot (a gradient or adjoint shared by the batch would be written by all of them)
-  for (int i = 0; i < 3; i++) {
-    if (batch > 1 && x->stride[i] < h->var_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
-    if (batch > 1 && seed->base[i] && seed->stride[i] < h->var_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "seed stride smaller than the vector length");
-    if (batch > 1 && adj && adj->base[i] && adj->stride[i] < h->var_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
-  }
-  for (int i = 0; i < FBSTAB_DENSE_NARR; i++)
-    if (batch > 1 && grad->base[i] && grad->stride[i] < h->arr_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
-  if (batch == 0) return FBSTAB_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
-  const bool status_host = !dev_ptrs || (flags & FBSTAB_HIP_OUT_ON_HOST);
-  const long long* vlen = h->var_len;
+  AdjointStage st;
+  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream);
+  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
+  hipStream_t s = st.s;
   DenseBatchArgs a;
-  VarBatchArgs v, sd, ad;
   DenseGradArgs g;
-  for (int i = 0; i < 4; i++) { v.base[i] = sd.base[i] = ad.base[i] = nullptr; v.stride[i] = sd.stride[i] = ad.stride[i] = 0; }
-  DevBuf d_seed[3], d_adj[3], d_grad[FBSTAB_DENSE_NARR], d_status;
-  if (dev_ptrs) {
-    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) { a.base[i] = data->base[i]; a.stride[i] = data->stride[i]; }
-    for (int i = 0; i < 3; i++) {
-      v.base[i] = x->base[i]; v.stride[i] = x->stride[i];
-      if (vlen[i] > 0) { sd.base[i] = seed->base[i]; sd.stride[i] = seed->stride[i]; }
-      if (adj && vlen[i] > 0) { ad.base[i] = adj->base[i]; ad.stride[i] = adj->stride[i]; }
-    }
-    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
-      g.base[i] = h->arr_len[i] > 0 ? grad->base[i] : nullptr;  // (nl == 0: the G and h slots are ignored)
-      g.stride[i] = grad->stride[i];
-    }
-  } else {
-    rc = h->ensure_staging();
-    if (rc != FBSTAB_HIP_OK) return rc;
-    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
-      if (data->stride[i] != 0 && data->stride[i] < h->arr_len[i] && batch > 1)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
-      rc = h->upload(data->base[i], data->stride[i], h->arr_len[i], batch, h->d_arr[i], &a.stride[i], s);
-      if (rc != FBSTAB_HIP_OK) return rc;
-      a.base[i] = h->d_arr[i];
-    }
-    for (int i = 0; i < 3; i++) {
-      long long st;
-      rc = h->upload(x->base[i], x->stride[i] ? x->stride[i] : vlen[i], vlen[i], batch, h->d_var[i], &st, s);
-      if (rc != FBSTAB_HIP_OK) return rc;
-      v.base[i] = h->d_var[i]; v.stride[i] = vlen[i];
-      if (seed->base[i] && vlen[i] > 0) {
-        HIP_TRY(hipMalloc(&d_seed[i].p, sizeof(double) * (size_t)vlen[i] * batch));
-        sd.base[i] = static_cast<double*>(d_seed[i].p);
-        rc = h->upload(seed->base[i], seed->stride[i] ? seed->stride[i] : vlen[i], vlen[i], batch, sd.base[i], &st, s);
-        if (rc != FBSTAB_HIP_OK) return rc;
-        sd.stride[i] = vlen[i];
-      }
-      if (adj && adj->base[i] && vlen[i] > 0) {
-        HIP_TRY(hipMalloc(&d_adj[i].p, sizeof(double) * (size_t)vlen[i] * batch));
-        ad.base[i] = static_cast<double*>(d_adj[i].p); ad.stride[i] = vlen[i];
-      }
-    }
-    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
-      g.base[i] = nullptr; g.stride[i] = 0;
-      if (grad->base[i] && h->arr_len[i] > 0) {
-        HIP_TRY(hipMalloc(&d_grad[i].p, sizeof(double) * (size_t)h->arr_len[i] * batch));
-        g.base[i] = static_cast<double*>(d_grad[i].p); g.stride[i] = h->arr_len[i];
-      }
-    }
+  for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
+    a.base[i] = st.a_base[i]; a.stride[i] = st.a_stride[i];
+    g.base[i] = st.g_base[i]; g.stride[i] = st.g_stride[i];
   }
-  int* d_st = status;
-  if (status_host) {
-    HIP_TRY(hipMalloc(&d_status.p, sizeof(int) * (size_t)batch));
-    d_st = static_cast<int*>(d_status.p);
-  }
+  VarBatchArgs &v = st.v, &sd = st.sd, &ad = st.ad;
+  int* d_st = st.d_st;
   double sig = sigma > 0.0 ? sigma : 1e-8;  // the reference's default sigma0 (fbstab_algorithm-impl.h:34)
   double alpha = h->opts.alpha;
   // the queue word alone: the words from kDenseFallbackSlot on still describe the last solve
@@ -1851,22 +1816,7 @@ int fbstab_hip_dense_adjoint_batch(fbstab_dense_handle_t h, int batch, const fbs
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(h->ev1, s));
   h->timed = true;
-  if (!dev_ptrs) {
-    for (int i = 0; i < FBSTAB_DENSE_NARR; i++)
-      if (g.base[i]) {
-        rc = h->download(grad->base[i], grad->stride[i] ? grad->stride[i] : h->arr_len[i], h->arr_len[i], batch,
-                         g.base[i], s);
-        if (rc != FBSTAB_HIP_OK) return rc;
-      }
-    for (int i = 0; i < 3; i++)
-      if (ad.base[i]) {
-        rc = h->download(adj->base[i], adj->stride[i] ? adj->stride[i] : vlen[i], vlen[i], batch, ad.base[i], s);
-        if (rc != FBSTAB_HIP_OK) return rc;
-      }
-  }
-  if (status_host) HIP_TRY(hipMemcpyAsync(status, d_st, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
-  if (status_host || !(flags & FBSTAB_HIP_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
-  return FBSTAB_HIP_OK;
+  return st.close();
 }
 
 double fbstab_hip_dense_last_kernel_ms(fbstab_dense_handle_t h) { return h ? h->last_kernel_ms() : -1.0; }

@@ -331,6 +331,71 @@ class _SolverBase:
         _check(self._lib, rc)
         return out
 
+    def _adjoint(self, fn, batch_struct, grad_struct, names: Sequence[str], lens: Sequence[int], data,
+                 z, l, v, gz, gl, gv, sigma, want, adj, stream, async_):
+        """fbstab_hip_*_adjoint_batch (``fn``) behind ``Adjoint``; an array of length 0 is a NULL slot."""
+        want = tuple(names if want is None else want)
+        unknown = set(want) - set(names)
+        assert not unknown, unknown
+        dev_flags = []
+        B = z.shape[0]
+        for i, (k, n) in enumerate(zip(names, lens)):
+            if n == 0:
+                batch_struct.base[i], batch_struct.stride[i] = None, 0
+                continue
+            p, st, d = _ptr_stride(data[k], n)
+            assert data[k].shape[0] == B
+            batch_struct.base[i], batch_struct.stride[i] = p, st
+            dev_flags.append(d)
+        var_lens = (self.nz, self.nl, self.nv)
+
+        def var(arrs, allow_none):
+            vb = _VarBatch()
+            for i, (a, n) in enumerate(zip(arrs, var_lens)):
+                if a is None or n == 0:
+                    assert n == 0 or (allow_none and i > 0), "z, l, v and gz are required"
+                    vb.base[i], vb.stride[i] = None, 0
+                    continue
+                p, st, d = _ptr_stride(a, n)
+                assert a.shape[0] == B
+                vb.base[i], vb.stride[i] = p, st
+                dev_flags.append(d)
+            return vb
+
+        xb = var((z, l, v), False)
+        sb = var((gz, gl, gv), True)
+        on_dev = all(dev_flags)
+        assert on_dev or not any(dev_flags), "mix of host and device arrays"
+        if on_dev:
+            import torch
+            zeros = lambda n, dt=torch.float64: torch.zeros((B, n), dtype=dt, device=z.device)
+            if not stream:
+                stream = torch.cuda.current_stream(z.device).cuda_stream
+            flags = DEVICE_POINTERS | (ASYNC if async_ else 0)
+            status = torch.zeros(B, dtype=torch.int32, device=z.device)
+        else:
+            zeros = lambda n, dt=np.float64: np.zeros((B, n), dtype=dt)
+            flags = HOST_POINTERS
+            status = np.zeros(B, dtype=np.int32)
+        res = {}
+        for i, (k, n) in enumerate(zip(names, lens)):
+            grad_struct.base[i], grad_struct.stride[i] = None, 0
+            if k in want:
+                res[k] = zeros(n)
+                if n > 0:
+                    grad_struct.base[i], grad_struct.stride[i] = _ptr_stride(res[k], n)[:2]
+        ab = None
+        if adj:
+            for k, n in zip(("dz", "dl", "dv"), var_lens):
+                res[k] = zeros(n)
+            ab = var((res["dz"], res["dl"], res["dv"]), False)
+        _check(self._lib, fn(
+            self._h, B, C.byref(batch_struct), C.byref(xb), C.byref(sb), C.c_double(sigma), C.byref(grad_struct),
+            C.byref(ab) if ab is not None else None, C.c_void_p(status.data_ptr() if on_dev else status.ctypes.data),
+            flags, C.c_void_p(stream) if stream else None))
+        res["status"] = status
+        return res
+
 
 def _solve_traced(self, batch_struct, names, lens, arrays, var_lens, z, l, v, y, capacity):
     """fbstab_hip_*_solve_traced for ONE QP in (1, n) numpy arrays.  Returns
@@ -510,66 +575,8 @@ class FBstabMpcBatch(_SolverBase):
         (default: all 12 of MPC_SEQ, each ``(batch, len)``), ``"status"`` (``(batch,)`` int32: 0, or 1 where
         the factorisation failed and the gradients are zero) and, with ``adj=True``, ``"dz", "dl", "dv"``.
         ``gl``/``gv`` None: zero seeds.  ``sigma <= 0``: 1e-8."""
-        want = tuple(MPC_SEQ if want is None else want)
-        unknown = set(want) - set(MPC_SEQ)
-        assert not unknown, unknown
-        b = _MpcBatch()
-        dev_flags = []
-        B = None
-        for i, (k, n) in enumerate(zip(MPC_SEQ, self.seq_len)):
-            p, st, d = _ptr_stride(data[k], n)
-            b.base[i], b.stride[i] = p, st
-            dev_flags.append(d)
-            B = data[k].shape[0] if B is None else B
-        lens = (self.nz, self.nl, self.nv)
-
-        def var(arrs, allow_none):
-            vb = _VarBatch()
-            for i, (a, n) in enumerate(zip(arrs, lens)):
-                if a is None:
-                    assert allow_none and i > 0, "z, l, v and gz are required"
-                    vb.base[i], vb.stride[i] = None, 0
-                    continue
-                p, st, d = _ptr_stride(a, n)
-                assert a.shape[0] == B
-                vb.base[i], vb.stride[i] = p, st
-                dev_flags.append(d)
-            return vb
-
-        xb = var((z, l, v), False)
-        sb = var((gz, gl, gv), True)
-        on_dev = all(dev_flags)
-        assert on_dev or not any(dev_flags), "mix of host and device arrays"
-        if on_dev:
-            import torch
-            zeros = lambda n, dt=torch.float64: torch.zeros((B, n), dtype=dt, device=z.device)
-            if not stream:
-                stream = torch.cuda.current_stream(z.device).cuda_stream
-            flags = DEVICE_POINTERS | (ASYNC if async_ else 0)
-            status = torch.zeros(B, dtype=torch.int32, device=z.device)
-        else:
-            zeros = lambda n, dt=np.float64: np.zeros((B, n), dtype=dt)
-            flags = HOST_POINTERS
-            status = np.zeros(B, dtype=np.int32)
-        res = {}
-        g = _MpcGradBatch()
-        for i, (k, n) in enumerate(zip(MPC_SEQ, self.seq_len)):
-            if k in want:
-                res[k] = zeros(n)
-                g.base[i], g.stride[i] = _ptr_stride(res[k], n)[:2]
-            else:
-                g.base[i], g.stride[i] = None, 0
-        ab = None
-        if adj:
-            for k, n in zip(("dz", "dl", "dv"), lens):
-                res[k] = zeros(n)
-            ab = var((res["dz"], res["dl"], res["dv"]), False)
-        _check(self._lib, self._lib.fbstab_hip_mpc_adjoint_batch(
-            self._h, B, C.byref(b), C.byref(xb), C.byref(sb), C.c_double(sigma), C.byref(g),
-            C.byref(ab) if ab is not None else None, C.c_void_p(status.data_ptr() if on_dev else status.ctypes.data),
-            flags, C.c_void_p(stream) if stream else None))
-        res["status"] = status
-        return res
+        return self._adjoint(self._lib.fbstab_hip_mpc_adjoint_batch, _MpcBatch(), _MpcGradBatch(), MPC_SEQ,
+                             self.seq_len, data, z, l, v, gz, gl, gv, sigma, want, adj, stream, async_)
 
 
 class FBstabDenseBatch(_SolverBase):
@@ -661,69 +668,8 @@ class FBstabDenseBatch(_SolverBase):
         ``"status"`` (``(batch,)`` int32: 0, or 1 where the factorisation failed and the gradients are zero) and,
         with ``adj=True``, ``"dz", "dl", "dv"``.  ``gl``/``gv`` None: zero seeds.  ``sigma <= 0``: 1e-8.  With
         ``nl == 0`` the G, h and l arrays are ``(batch, 0)`` (or None on input)."""
-        want = tuple(DENSE_ARR if want is None else want)
-        unknown = set(want) - set(DENSE_ARR)
-        assert not unknown, unknown
-        b = _DenseBatch()
-        dev_flags = []
-        B = z.shape[0]
-        for i, (k, n) in enumerate(zip(DENSE_ARR, self.arr_len)):
-            if n == 0:
-                b.base[i], b.stride[i] = None, 0
-                continue
-            p, st, d = _ptr_stride(data[k], n)
-            assert data[k].shape[0] == B
-            b.base[i], b.stride[i] = p, st
-            dev_flags.append(d)
-        lens = (self.nz, self.nl, self.nv)
-
-        def var(arrs, allow_none):
-            vb = _VarBatch()
-            for i, (a, n) in enumerate(zip(arrs, lens)):
-                if a is None or n == 0:
-                    assert n == 0 or (allow_none and i > 0), "z, l, v and gz are required"
-                    vb.base[i], vb.stride[i] = None, 0
-                    continue
-                p, st, d = _ptr_stride(a, n)
-                assert a.shape[0] == B
-                vb.base[i], vb.stride[i] = p, st
-                dev_flags.append(d)
-            return vb
-
-        xb = var((z, l, v), False)
-        sb = var((gz, gl, gv), True)
-        on_dev = all(dev_flags)
-        assert on_dev or not any(dev_flags), "mix of host and device arrays"
-        if on_dev:
-            import torch
-            zeros = lambda n, dt=torch.float64: torch.zeros((B, n), dtype=dt, device=z.device)
-            if not stream:
-                stream = torch.cuda.current_stream(z.device).cuda_stream
-            flags = DEVICE_POINTERS | (ASYNC if async_ else 0)
-            status = torch.zeros(B, dtype=torch.int32, device=z.device)
-        else:
-            zeros = lambda n, dt=np.float64: np.zeros((B, n), dtype=dt)
-            flags = HOST_POINTERS
-            status = np.zeros(B, dtype=np.int32)
-        res = {}
-        g = _DenseGradBatch()
-        for i, (k, n) in enumerate(zip(DENSE_ARR, self.arr_len)):
-            g.base[i], g.stride[i] = None, 0
-            if k in want:
-                res[k] = zeros(n)
-                if n > 0:
-                    g.base[i], g.stride[i] = _ptr_stride(res[k], n)[:2]
-        ab = None
-        if adj:
-            for k, n in zip(("dz", "dl", "dv"), lens):
-                res[k] = zeros(n)
-            ab = var((res["dz"], res["dl"], res["dv"]), False)
-        _check(self._lib, self._lib.fbstab_hip_dense_adjoint_batch(
-            self._h, B, C.byref(b), C.byref(xb), C.byref(sb), C.c_double(sigma), C.byref(g),
-            C.byref(ab) if ab is not None else None, C.c_void_p(status.data_ptr() if on_dev else status.ctypes.data),
-            flags, C.c_void_p(stream) if stream else None))
-        res["status"] = status
-        return res
+        return self._adjoint(self._lib.fbstab_hip_dense_adjoint_batch, _DenseBatch(), _DenseGradBatch(), DENSE_ARR,
+                             self.arr_len, data, z, l, v, gz, gl, gv, sigma, want, adj, stream, async_)
 
 
 class ShardGroup:

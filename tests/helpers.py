@@ -305,3 +305,68 @@ def reference_loop_cases(kats):
 def solve_case(orc, kind, p, opts):
     """(z, l, v, y, out) of `orc` on one of reference_loop_cases."""
     return orc.solve_dense(p, opts=opts) if kind == "dense" else orc.solve_mpc(p, opts=opts)
+
+
+# Every bad-argument call of fbstab_hip_<kind>_adjoint_batch / _solve_batch that a machine without a GPU can make:
+# no handle exists there, so the handle is NULL in all of them - alone ("valid": everything else in order) and
+# together with each other fault.  `null`: argument blocks passed as NULL; `zero`: blocks whose strides are 0.
+HANDLE_FREE_CASES = {
+    "valid": dict(),
+    "valid_batch2": dict(batch=2),
+    "null_data": dict(null=("data",)),
+    "null_x": dict(null=("x",)),
+    "null_seed": dict(null=("seed",)),
+    "null_grad": dict(null=("grad",)),
+    "null_out": dict(null=("out",)),
+    "null_all": dict(null=("data", "x", "seed", "grad", "out")),
+    "null_seed_z": dict(seed_z=False),
+    "null_seed_z_batch2": dict(batch=2, seed_z=False),
+    "zero_data_stride": dict(batch=2, zero=("data",)),
+    "zero_x_stride": dict(batch=2, zero=("x",)),
+    "zero_seed_stride": dict(batch=2, zero=("seed",)),
+    "zero_grad_stride": dict(batch=2, zero=("grad",)),
+    "zero_adj_stride": dict(batch=2, zero=("adj",)),
+    "zero_strides": dict(batch=2, zero=("data", "x", "seed", "grad", "adj")),
+    "zero_strides_batch1": dict(batch=1, zero=("data", "x", "seed", "grad", "adj")),
+}
+_ADJOINT_ONLY = ("seed", "grad", "adj")
+
+
+def handle_free_cases(entry):
+    """Names of the HANDLE_FREE_CASES that apply to ``entry`` ("adjoint_batch" or "solve_batch": no seeds,
+    gradients or adjoints there)."""
+    if entry == "adjoint_batch":
+        return list(HANDLE_FREE_CASES)
+    return [k for k in HANDLE_FREE_CASES if not any(t in k for t in _ADJOINT_ONLY)]
+
+
+def handle_free_call(lib, kind, entry, batch=1, null=(), zero=(), seed_z=True):
+    """``(rc, message)`` of fbstab_hip_<kind>_<entry> with a NULL handle and otherwise valid host arguments (every
+    slot of every block a buffer with stride 8, an ``adj`` block included) except as the case says."""
+    import ctypes as C
+    from fbstab_amd import hip_api
+    buf = np.zeros(64)
+    out = np.zeros(2 * 40, dtype=np.uint8)   # two SolverOut records, or two status words
+    data_t, grad_t = ((hip_api._MpcBatch, hip_api._MpcGradBatch) if kind == "mpc"
+                      else (hip_api._DenseBatch, hip_api._DenseGradBatch))
+
+    def block(cls, name, slots):
+        b = cls()
+        for i in range(slots):
+            b.base[i], b.stride[i] = buf.ctypes.data, (0 if name in zero else 8)
+        return b
+
+    n = len(data_t().base)
+    blocks = dict(data=block(data_t, "data", n), x=block(hip_api._VarBatch, "x", 4),
+                  seed=block(hip_api._VarBatch, "seed", 3), grad=block(grad_t, "grad", n),
+                  adj=block(hip_api._VarBatch, "adj", 3))
+    if not seed_z:
+        blocks["seed"].base[0] = None
+    ref = lambda name: None if name in null else C.byref(blocks[name])
+    outp = None if "out" in null else out.ctypes.data
+    fn = getattr(lib, f"fbstab_hip_{kind}_{entry}")
+    if entry == "adjoint_batch":
+        rc = fn(None, batch, ref("data"), ref("x"), ref("seed"), 0.0, ref("grad"), ref("adj"), outp, 0, None)
+    else:
+        rc = fn(None, batch, ref("data"), ref("x"), outp, 0, None)
+    return rc, lib.fbstab_hip_last_error().decode()

@@ -130,3 +130,16 @@ def test_adjoint_entry_point_is_exported_and_validates_without_gpu():
     assert rc == 1  # FBSTAB_HIP_ERR_ARGUMENT
     assert b"null solver handle" in lib.fbstab_hip_last_error()
     assert C.sizeof(hip_api._MpcGradBatch) == C.sizeof(hip_api._MpcBatch) == 12 * 16
+
+
+_ENTRIES = ("adjoint_batch", "solve_batch")
+
+
+@pytest.mark.parametrize("entry,case", [(e, c) for e in _ENTRIES for c in H.handle_free_cases(e)])
+def test_mpc_bad_argument_calls_without_a_handle(entry, case):
+    """tests/helpers.py: HANDLE_FREE_CASES on fbstab_hip_mpc_adjoint_batch and fbstab_hip_mpc_solve_batch.  Both
+    look at the handle before anything else, so whatever else is wrong with the call the answer is the same one
+    (recorded from the library as it was before the entry points shared their staging code)."""
+    from fbstab_amd import hip_api
+    lib = hip_api.load_library()
+    assert H.handle_free_call(lib, "mpc", entry, **H.HANDLE_FREE_CASES[case]) == (1, "null solver handle")

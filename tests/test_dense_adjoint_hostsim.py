@@ -153,3 +153,51 @@ def test_adjoint_entry_point_is_exported_and_validates_without_gpu():
     rc, msg = call(None, 2)
     assert rc == 1 and b"null solver handle" in msg
     assert lib.fbstab_hip_dense_adjoint_batch(None, 1, None, None, None, 0.0, None, None, None, 0, None) == 1
+
+
+# (rc, message) of every case of tests/helpers.py: HANDLE_FREE_CASES, recorded from the library as it was before
+# the entry points shared their staging code.  fbstab_hip_dense_adjoint_batch checks what needs no handle first;
+# fbstab_hip_dense_solve_batch looks at the handle before anything else.
+_NO_HANDLE = (1, "null solver handle")
+_HANDLE_FREE_EXPECTED = {
+    "adjoint_batch": {
+        "valid": _NO_HANDLE,
+        "valid_batch2": _NO_HANDLE,
+        "null_data": (1, "null argument"),
+        "null_x": (1, "null argument"),
+        "null_seed": (1, "null argument"),
+        "null_grad": (1, "null argument"),
+        "null_out": (1, "null argument"),
+        "null_all": (1, "null argument"),
+        "null_seed_z": (1, "null seed pointer (z)"),
+        "null_seed_z_batch2": (1, "null seed pointer (z)"),
+        "zero_data_stride": _NO_HANDLE,
+        "zero_x_stride": (1, "variable stride smaller than the vector length"),
+        "zero_seed_stride": (1, "seed stride smaller than the vector length"),
+        "zero_grad_stride": (1, "gradient stride smaller than the array length"),
+        "zero_adj_stride": (1, "adjoint stride smaller than the vector length"),
+        "zero_strides": (1, "variable stride smaller than the vector length"),
+        "zero_strides_batch1": _NO_HANDLE,
+    },
+    "solve_batch": {
+        "valid": _NO_HANDLE,
+        "valid_batch2": _NO_HANDLE,
+        "null_data": _NO_HANDLE,
+        "null_x": _NO_HANDLE,
+        "null_out": _NO_HANDLE,
+        "null_all": _NO_HANDLE,
+        "zero_data_stride": _NO_HANDLE,
+        "zero_x_stride": _NO_HANDLE,
+        "zero_strides": _NO_HANDLE,
+        "zero_strides_batch1": _NO_HANDLE,
+    },
+}
+
+
+@pytest.mark.parametrize("entry,case", [(e, c) for e, t in _HANDLE_FREE_EXPECTED.items() for c in t])
+def test_dense_bad_argument_calls_without_a_handle(entry, case):
+    from fbstab_amd import hip_api
+    assert set(_HANDLE_FREE_EXPECTED[entry]) == set(H.handle_free_cases(entry))
+    lib = hip_api.load_library()
+    rc, msg = H.handle_free_call(lib, "dense", entry, **H.HANDLE_FREE_CASES[case])
+    assert (rc, msg) == _HANDLE_FREE_EXPECTED[entry][case]
