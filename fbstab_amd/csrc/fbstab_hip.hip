@@ -19,6 +19,7 @@
 #include "fb_dense.h"
 #include "fb_dense_wave.h"
 #include "fb_final_norms.h"
+#include "fb_in_flight.h"
 #include "fb_mpc.h"
 #include "fb_mpc_r16.h"
 #include "fb_record_kernel.h"
@@ -1030,8 +1031,10 @@ int fbstab_hip_mpc_create_in_flight(int N, int nx, int nu, int nc, int max_batch
   if (per_cu < 1) per_cu = 1;
   if (per_cu > 8) per_cu = 8;
   // a handle that shares the device with others takes its share of the resident workgroups (and of the
-  // scratch memory that goes with them), at least one per CU: the launches of the other handles fill the rest
-  per_cu = (per_cu + handles_in_flight - 1) / handles_in_flight;
+  // scratch memory that goes with them), at least one per CU: the launches that can really run beside it - no
+  // more than the process has hardware queues - want twice the resident slots between them, so that waiting
+  // workgroups fill the SIMDs a launch frees in its tail (fb_in_flight.h)
+  per_cu = fbk::in_flight_wgs_per_cu(per_cu, handles_in_flight, fbk::hw_queues_hint());
   const char* env = getenv("FBSTAB_HIP_WGS_PER_CU");
   if (env && atoi(env) > 0) per_cu = atoi(env);
   s->workgroups = cus * per_cu;

@@ -443,7 +443,13 @@ class FBstabMpcBatch(_SolverBase):
     def __init__(self, N: int, nx: int, nu: int, nc: int, max_batch: int = 1,
                  device: int = 0, handles_in_flight: int = 1):
         """handles_in_flight: how many such solvers the caller keeps busy on the device at the same time
-        (fbstab_hip_mpc_create_in_flight: each then takes its share of the resident workgroups)."""
+        (fbstab_hip_mpc_create_in_flight: each then takes its share of the resident workgroups).  The share
+        counts the launches that can really overlap, min(handles_in_flight, hardware queues of the process):
+        ceil(2 x resident / that) workgroups per CU, at most half the grid for handles_in_flight >= 2 - on the
+        BASELINE shape one per CU for eight in flight on eight queues, two per CU (0.87 GB of scratch per
+        handle) on HIP's default of four queues or for four in flight.  The queue count is GPU_MAX_HW_QUEUES as
+        the environment holds it when the handle is created (read only; unset = 4); FBSTAB_HIP_WGS_PER_CU
+        forces a share.  ``query()`` reports the workgroups and scratch bytes the handle got."""
         super().__init__()
         if hasattr(self._lib, "fbstab_hip_mpc_create_in_flight"):
             _check(self._lib, self._lib.fbstab_hip_mpc_create_in_flight(

@@ -134,9 +134,22 @@ int fbstab_hip_mpc_create(int N, int nx, int nu, int nc, int max_batch, int devi
  * that have run out of QPs while their wavefront's last one finishes - shrinks (rows busy 0.95 instead of 0.82
  * per Newton step at eight in flight; +2.7 % throughput, and a quarter of the scratch memory: 0.44 instead
  * of 1.75 GB per handle).  handles_in_flight = 1 is fbstab_hip_mpc_create.
- * What the share costs a handle that is then used ALONE: it keeps its fraction of the grid - one eighth of
- * the workgroups at handles_in_flight = 8 (never fewer than one per CU), so a lone launch fills an eighth of
- * the chip - and fbstab_hip_mpc_receding_sweep, whose one-launch form needs batch <= workgroups x QPs per
+ * The rule (fbstab_amd/csrc/fb_in_flight.h): with `resident` workgroups per CU from the occupancy query,
+ *     concurrent = min(handles_in_flight, hw_queues)      launches that can really run side by side
+ *     per CU     = ceil(2 * resident / concurrent)        clamped to [1, resident], and for
+ *                                                         handles_in_flight >= 2 to max(1, resident / 2)
+ * so that the launches in flight want TWICE the resident slots between them: the workgroups that wait take
+ * the SIMDs a launch frees when it runs into its tail.  Streams that share a hardware queue run their launches
+ * one after the other, so `hw_queues` counts what can overlap: it is what the HIP runtime of this process was
+ * told, GPU_MAX_HW_QUEUES read (only read; 1..32, unset or unparsable = 4, HIP's default) at handle creation -
+ * a hint about how many of the caller's streams run side by side.  On the BASELINE shape (resident = 4): eight
+ * in flight on eight queues one workgroup per CU, 0.44 GB of scratch per handle; eight in flight on four
+ * queues, or four in flight, two per CU and 0.87 GB; two in flight two per CU; a handle that shares the device
+ * never keeps more than half the grid.  A caller whose streams share queues for other reasons can force a
+ * share with FBSTAB_HIP_WGS_PER_CU in the environment at handle creation.
+ * What the share costs a handle that is then used ALONE: it keeps its fraction of the grid - a quarter of
+ * the workgroups at handles_in_flight = 8 on eight queues (never fewer than one per CU), so a lone launch fills
+ * a quarter of the chip - and fbstab_hip_mpc_receding_sweep, whose one-launch form needs batch <= workgroups x QPs per
  * workgroup, falls back to one launch per step at a batch that much smaller (same results, bitwise; slower).
  * fbstab_hip_mpc_query reports the handle's `workgroups` and `scratch_bytes` as created, so a caller can see
  * the share it got.  Values outside 1..64 are refused (FBSTAB_HIP_ERR_ARGUMENT).
