@@ -2202,8 +2202,13 @@ struct MpcR16 {
   // seed - the constraint block's right-hand side becomes -C.gv.  One step, factor and both sweeps as the
   // solver runs them, then (dz, dl, dv) flat to `flat` (nz + nl + nv doubles) for the contraction.  gl, gv may
   // be null (zero).  Returns false on a non-positive pivot.
+  // Row pairs (LPQ = 32) take the same path: lane r of the pair owns element r of every slot, the partner row's
+  // lanes 16..31 included; the forward sweep leaves (gamma, rvm) of barrier_terms<true> in the record
+  // (kStoreGamma) and the backward sweep reads them there.
   FB_DEV bool adjoint_step(const C& c, double sigma, double alpha, const double* gz, const double* gl,
                            const double* gv, double* flat) {
+    // `flat` is the slot's matrix-copy region, (N + 1) kPack doubles, free once the sweeps have run
+    static_assert(kPack >= NS + NX + NC, "the matrix-copy region holds the flat step (nz + nl + nv doubles)");
     const int r = c.tid, N_ = N;
     const int nx_ = prob_nx(), nu_ = prob_nu(), nc_ = prob_nc();
     const long nz = (long)(N_ + 1) * (nx_ + nu_), nl = (long)(N_ + 1) * nx_;
@@ -2242,7 +2247,9 @@ struct MpcR16 {
   // ROW: the costate step from the Newton system's row, form (b) above.
   // REFINE: the right-hand side is the Newton system's residual at the step in the record, and the
   // backward sweep ADDS its solution to that step (refine_step()).
-  // ADJ: the adjoint's step (adjoint_step): barrier_terms<true> in both sweeps, nothing else changes.
+  // ADJ: the adjoint's step (adjoint_step): barrier_terms<true> wherever the barrier terms are formed - in both
+  // sweeps on the one-row instances, in the forward sweep alone where the pair travels in the record
+  // (kStoreGamma) -, nothing else changes.
   template <bool ROW, bool REFINE, bool ADJ = false>
   static FB_DEV StepOut newton_core(const C& c, double* const R0, const double* const P0, const lds_iptr po,
                                     lds_ptr lds_row, lds_ptr Lp, const int N_, const bool bnd, const double tp,

@@ -1,7 +1,7 @@
 // The record kernels' entry point and queue (fb_mpc_r16.h holds the numerics), shared by
 // the translation units of the library: every instance <NX, NU, NC, R> is compiled in a
 // file of its own (rec_*.hip, a minute or two each, in parallel under `make -j`) and
-// hands fbstab_hip.hip a RecordInstance with the addresses of its six kernels.
+// hands fbstab_hip.hip a RecordInstance with the addresses of its kernels (six of the solve, two of the adjoint).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,8 +24,9 @@ struct RecordInstance {
   long long (*ws_doubles)(int N);
   const void *solve, *solve_keep, *probe;  // kernels of the padded instance
   const void *solve_exact, *solve_keep_exact, *probe_exact;  // problem == instance shape
-  // fbstab_hip_mpc_adjoint_batch on the record (one-row instances; null: the flat-vector adjoint serves the shape)
+  // fbstab_hip_mpc_adjoint_batch on the record (fbstab_mpc_r16_adjoint_kernel) and the name it is reported under
   const void *adjoint, *adjoint_exact;
+  const char* adjoint_name;
 };
 
 // Arguments of the record adjoint kernel (fbstab_hip_mpc_adjoint_batch): the seeds (gz, gl, gv; gl and gv may be
@@ -315,16 +316,17 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_kernel(
 #endif
 }
 
-// The adjoint of fbstab_hip_mpc_adjoint_batch on the one-row record instances: rows pull QPs from the counter as
-// the solve's do; per QP the record is packed with the point as x = xbar (load_guess), one Newton step runs with
-// the adjoint's right-hand side (MpcR16::adjoint_step: the solver's factor and sweeps, barrier_terms<true>), and
-// the row's lanes contract (dz, dl, dv) - left flat in the slot's matrix-copy region, which nothing reads after
-// the step - with the point into the gradients (fb_adjoint.h).  The slot's matrix copies are overwritten: a
-// FBSTAB_HIP_KEEP_MATRICES solve after it rebuilds them (fbstab_hip.hip resets kept_batch).
-template <int NX, int NU, int NC, bool EXACT>
+// The adjoint of fbstab_hip_mpc_adjoint_batch on the record instances (R: 16-lane rows per QP, as the solve
+// kernel's): rows - row pairs - pull QPs from the counter as the solve's do; per QP the record is packed with the
+// point as x = xbar (load_guess), one Newton step runs with the adjoint's right-hand side (MpcR16::adjoint_step: the
+// solver's factor and sweeps, barrier_terms<true>), and the QP's lanes contract (dz, dl, dv) - left flat in the
+// slot's matrix-copy region, which nothing reads after the step - with the point into the gradients
+// (fb_adjoint.h).  The slot's matrix copies are overwritten: a FBSTAB_HIP_KEEP_MATRICES solve after it rebuilds
+// them (fbstab_hip.hip resets kept_batch).
+template <int NX, int NU, int NC, bool EXACT, int R>
 __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_adjoint_kernel(
     MpcBatchPtrs data, VarBatchPtrs x, AdjointArgs a, double* scratch, int* counter, int batch, int N) {
-  typedef MpcR16<NX, NU, NC, EXACT, false, 1> P;
+  typedef MpcR16<NX, NU, NC, EXACT, false, R> P;
   typename P::C ctx;
   ctx.tid = threadIdx.x & (P::LPQ - 1);
   P p;
@@ -384,9 +386,10 @@ int r16_lds_bytes(int N) {
 // R: 16-lane rows of the wavefront per QP (1: four QPs per wavefront, stage width
 // <= 16; 2: two QPs per wavefront, stage width <= 32)
 template <int NX, int NU, int NC, int R = 1>
-RecordInstance r16_instance(const char* name) {
+RecordInstance r16_instance(const char* name, const char* adjoint_name) {
   RecordInstance r;
   r.name = name;
+  r.adjoint_name = adjoint_name;
   r.nx = NX; r.nu = NU; r.nc = NC;
   r.qps_per_wg = 4 / R;
   r.lds_bytes = r16_lds_bytes<NX, NU, NC, R>;
@@ -397,11 +400,8 @@ RecordInstance r16_instance(const char* name) {
   r.solve_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, false, true, false, R>);
   r.solve_keep_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, false, true, true, R>);
   r.probe_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, true, true, false, R>);
-  r.adjoint = r.adjoint_exact = nullptr;  // (row-pair instances: the flat-vector adjoint)
-  if constexpr (R == 1) {
-    r.adjoint = reinterpret_cast<const void*>(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, false>);
-    r.adjoint_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, true>);
-  }
+  r.adjoint = reinterpret_cast<const void*>(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, false, R>);
+  r.adjoint_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, true, R>);
   return r;
 }
 
@@ -410,7 +410,7 @@ RecordInstance r16_instance(const char* name) {
 // Defines the factory of one instance (one per rec_*.hip); fbstab_hip.hip lists them.
 #define FB_RECORD_INSTANCE(NX, NU, NC, R, NAME)                                              \
   __attribute__((visibility("hidden"))) RecordInstance fbstab_record_instance_##NX##_##NU##_##NC##_##R() { \
-    return r16_instance<NX, NU, NC, R>(NAME);                                                \
+    return r16_instance<NX, NU, NC, R>(NAME, "fbstab_mpc_r16_adjoint_kernel<" #NX "," #NU "," #NC ">"); \
   }
 #define FB_RECORD_INSTANCE_DECL(NX, NU, NC, R) \
   __attribute__((visibility("hidden"))) RecordInstance fbstab_record_instance_##NX##_##NU##_##NC##_##R();

@@ -124,8 +124,8 @@ __global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_kernel(MpcLayout 
 
 // The adjoint of fbstab_hip_mpc_adjoint_batch on the flat-vector policy (fb_mpc.h: mpc_adjoint,
 // mpc_adjoint_gradients), one QP per workgroup pulled from the queue like the solve: the shapes of the flat-vector
-// kernel and of the row-pair record instances (their handles give it a scratch of its own; the one-row instances
-// run fbstab_mpc_r16_adjoint_kernel, fb_record_kernel.h).  `x`: the point
+// kernel, and the record handles that FBSTAB_HIP_FLAT_ADJOINT or the row-pair instances' default keeps on it (they
+// give it a scratch of its own; the others run fbstab_mpc_r16_adjoint_kernel, fb_record_kernel.h).  `x`: the point
 // (z, l, v); `seed`: (gz, gl, gv), null l / v slots meaning zero; `adj`: null slots, or (dz, dl, dv).
 struct MpcGradArgs {
   double* base[FBSTAB_MPC_NSEQ];
@@ -873,8 +873,10 @@ struct fbstab_mpc_solver : SolverBase {
   bool exact = false;     // the problem has exactly the instance's shape
   int kept_batch = -1;    // batch size of the last FBSTAB_HIP_KEEP_MATRICES call whose copies are still in the slots
   int qps_per_wg = 1;
-  // fbstab_hip_mpc_adjoint_batch: the flat-vector kernel's scratch on a row-pair record handle (whose own scratch
-  // is laid out for the record kernel), allocated by the first call; the LDS attribute set once
+  // fbstab_hip_mpc_adjoint_batch: a record handle on the flat-vector adjoint (FBSTAB_HIP_FLAT_ADJOINT at creation;
+  // the row-pair instances' default) - then with a scratch of the flat kernel's own (the handle's is laid out for
+  // the record kernel), allocated by the first call; the LDS attribute set once
+  bool flat_adjoint = false;
   double* adj_scratch = nullptr;
   bool adj_ready = false;
 };
@@ -983,9 +985,15 @@ int fbstab_hip_mpc_create_in_flight(int N, int nx, int nu, int nc, int max_batch
   // FBSTAB_HIP_GENERIC=1 forces the flat-vector kernel (comparisons, tests)
   const char* force_generic = getenv("FBSTAB_HIP_GENERIC");
   if (!(force_generic && atoi(force_generic) > 0)) s->rec = record_instance_for(nx, nu, nc);
+  s->flat_adjoint = false;
   if (s->rec) {
     s->exact = nx == s->rec->nx && nu == s->rec->nu && nc == s->rec->nc;
     s->qps_per_wg = s->rec->qps_per_wg;
+    // FBSTAB_HIP_FLAT_ADJOINT, read here: 1 - the flat-vector adjoint on this record handle; 0 - its record adjoint;
+    // unset - the record adjoint on the one-row instances and the flat-vector adjoint on the row-pair instances,
+    // whose record adjoint has not been timed against it on the wide workloads yet
+    const char* flat_adj = getenv("FBSTAB_HIP_FLAT_ADJOINT");
+    s->flat_adjoint = (flat_adj && *flat_adj) ? atoi(flat_adj) > 0 : s->rec->qps_per_wg != 4;
     s->lds_bytes = s->rec->lds_bytes(N);
   }
   {
@@ -1362,8 +1370,8 @@ int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t h, int batch, const fbstab_
   double sig = sigma > 0.0 ? sigma : 1e-8;  // the reference's default sigma0 (fbstab_algorithm-impl.h:34)
   double alpha = h->opts.alpha;
   HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
-  if (h->rec && h->rec->adjoint) {
-    // one-row record instances: the adjoint on the record, in the handle's own slots (their matrix copies are
+  if (h->rec && h->rec->adjoint && !h->flat_adjoint) {
+    // record instances: the adjoint on the record, in the handle's own slots (their matrix copies are
     // overwritten: the next FBSTAB_HIP_KEEP_MATRICES solve rebuilds them)
     const RecordInstance& r = *h->rec;
     const void* kern = h->exact ? r.adjoint_exact : r.adjoint;
@@ -1397,8 +1405,8 @@ int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t h, int batch, const fbstab_
     HIP_TRY(hipEventRecord(h->ev0, s));
     HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)h->lds_bytes, s));
   } else {
-    // the flat-vector kernel: the handle's own workspace on flat-vector handles; on row-pair record handles one of
-    // its own, L.ws_doubles x workgroups doubles (fbstab_hip_mpc_query does not count it), allocated once
+    // the flat-vector kernel: the handle's own workspace on flat-vector handles; on record handles (`flat_adjoint`)
+    // one of its own, L.ws_doubles x workgroups doubles (fbstab_hip_mpc_query does not count it), allocated once
     const int grid = batch < h->workgroups ? batch : h->workgroups;
     double* scratch = h->scratch;
     if (h->rec) {
@@ -1457,6 +1465,13 @@ int fbstab_hip_mpc_query(fbstab_mpc_handle_t h, long long* scratch_bytes, int* l
 const char* fbstab_hip_mpc_kernel_name(fbstab_mpc_handle_t h) {
   if (!h) return "";
   return h->rec ? h->rec->name : "fbstab_mpc_kernel<64>";
+}
+
+// Name of the kernel the next fbstab_hip_mpc_adjoint_batch of this handle launches (diagnostics, tests, tools).
+const char* fbstab_hip_mpc_adjoint_kernel_name(fbstab_mpc_handle_t h) {
+  if (!h) return "";
+  if (!h->rec || !h->rec->adjoint || h->flat_adjoint) return "fbstab_mpc_adjoint_kernel<64>";
+  return h->rec->adjoint_name;
 }
 
 int fbstab_hip_mpc_refined_steps(fbstab_mpc_handle_t h, long long* steps) {

@@ -159,6 +159,9 @@ def load_library() -> C.CDLL:
         lib.fbstab_hip_mpc_adjoint_batch.argtypes = [
             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_adjoint_kernel_name"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_adjoint_kernel_name.restype = C.c_char_p
+        lib.fbstab_hip_mpc_adjoint_kernel_name.argtypes = [C.c_void_p]
     if hasattr(lib, "fbstab_hip_dense_adjoint_batch"):  # (absent from a build of an earlier round loaded for an A/B)
         lib.fbstab_hip_dense_adjoint_batch.argtypes = [
             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
@@ -192,7 +195,8 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_solve_traced", "fbstab_hip_mpc_receding_sweep",
     "fbstab_hip_mpc_last_kernel_ms", "fbstab_hip_mpc_query", "fbstab_hip_mpc_kernel_name",
     "fbstab_hip_mpc_refined_steps", "fbstab_hip_mpc_create_in_flight",
-    "fbstab_hip_mpc_debug_newton", "fbstab_hip_mpc_adjoint_batch", "fbstab_hip_debug_stamps",
+    "fbstab_hip_mpc_debug_newton", "fbstab_hip_mpc_adjoint_batch", "fbstab_hip_mpc_adjoint_kernel_name",
+    "fbstab_hip_debug_stamps",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",
     "fbstab_hip_dense_solve_traced", "fbstab_hip_dense_adjoint_batch",
@@ -464,6 +468,16 @@ class FBstabMpcBatch(_SolverBase):
 
     def kernel_name(self) -> str:
         return self._lib.fbstab_hip_mpc_kernel_name(self._h).decode()
+
+    def adjoint_kernel_name(self) -> str:
+        """The kernel the next Adjoint call launches (fbstab_hip_mpc_adjoint_kernel_name)."""
+        if not hasattr(self._lib, "fbstab_hip_mpc_adjoint_kernel_name"):
+            # (an earlier build loaded for an A/B: its one-row record instances ran their own adjoint, every other
+            # handle the flat-vector one)
+            kn = self.kernel_name()
+            return kn.replace("r16_kernel", "r16_adjoint_kernel") if kn.startswith("fbstab_mpc_r16_kernel<12,4,") \
+                else "fbstab_mpc_adjoint_kernel<64>"
+        return self._lib.fbstab_hip_mpc_adjoint_kernel_name(self._h).decode()
 
     def refined_steps(self) -> int:
         """Newton steps of the last call that were refined (fbstab_hip_mpc_refined_steps)."""

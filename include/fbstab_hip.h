@@ -295,16 +295,22 @@ int fbstab_hip_mpc_debug_newton(fbstab_mpc_handle_t handle, const fbstab_mpc_bat
  *           It lives where solve_batch's `out` lives (host for host-pointer calls and with
  *           FBSTAB_HIP_OUT_ON_HOST, device otherwise).
  * Flags, streams and validation are those of fbstab_hip_mpc_solve_batch; every QP needs
- * its own slots in x, seed, grad and adj (stride >= length when batch > 1).  Kernels: the
- * one-row record instances (<12,4,20>, <12,4,32>: the headline and bounds shapes) run the
- * adjoint on their own records (fbstab_mpc_r16_adjoint_kernel, in the handle's scratch; the
- * slots' matrix copies are rebuilt by the next FBSTAB_HIP_KEEP_MATRICES solve); the row-pair
- * instances (<18,5,10>, <24,8,*>) and the flat-vector kernel's shapes run the flat-vector
- * adjoint (fbstab_mpc_adjoint_kernel).  On a row-pair handle the first call allocates that
- * kernel's scratch: MpcLayout::ws_doubles (fb_mpc.h; the iterate vectors and the per-stage
- * factor record: 58 k doubles = 463 KB at (N, nx, nu, nc) = (30, 18, 5, 10), 101 k at
- * (30, 24, 8, 16)) per workgroup, times the handle's workgroups, held until destroy and not
- * counted in fbstab_hip_mpc_query's scratch_bytes.
+ * its own slots in x, seed, grad and adj (stride >= length when batch > 1).  Kernels: every
+ * record instance (the one-row <12,4,20>, <12,4,32> and the row-pair <18,5,10>, <24,8,16>,
+ * <24,8,32>) has an adjoint on its own records (fbstab_mpc_r16_adjoint_kernel: in the handle's
+ * scratch, with the solve's LDS and grid; the slots' matrix copies are rebuilt by the next
+ * FBSTAB_HIP_KEEP_MATRICES solve); the flat-vector kernel's shapes run the flat-vector adjoint
+ * (fbstab_mpc_adjoint_kernel) in the handle's workspace.  Which of the two a RECORD handle
+ * runs is fixed when it is created: by default the one-row instances run their record
+ * adjoint and the row-pair instances the flat-vector adjoint (their record adjoint has not
+ * been timed against it on wide workloads yet); FBSTAB_HIP_FLAT_ADJOINT=0 in the environment
+ * at creation selects the record adjoint on every record handle, =1 the flat-vector adjoint.
+ * fbstab_hip_mpc_adjoint_kernel_name names the kernel the next call launches.
+ * A record handle on the flat-vector adjoint allocates that kernel's scratch at its first
+ * call: MpcLayout::ws_doubles (fb_mpc.h; the iterate vectors and the per-stage factor record:
+ * 58 k doubles = 463 KB at (N, nx, nu, nc) = (30, 18, 5, 10), 101 k at (30, 24, 8, 16)) per
+ * workgroup, times the handle's workgroups, held until destroy and not counted in
+ * fbstab_hip_mpc_query's scratch_bytes.  The record adjoint allocates nothing.
  * fbstab_hip_mpc_last_kernel_ms then reports this launch. */
 typedef struct fbstab_mpc_grad_batch_t {
   double* base[FBSTAB_MPC_NSEQ];
@@ -314,6 +320,8 @@ int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t handle, int batch, const fb
                                  const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
                                  const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj,
                                  int* status, int flags, void* stream);
+/* Name of the kernel the next fbstab_hip_mpc_adjoint_batch of this handle launches. */
+const char* fbstab_hip_mpc_adjoint_kernel_name(fbstab_mpc_handle_t handle);
 
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);

@@ -5,13 +5,21 @@ last_kernel_ms (HIP events around the one launch); the median of --reps launches
 
 usage: python tools/adjoint_bench.py [--batch 8192] [--reps 5] [--generic]
        python tools/adjoint_bench.py --dense [--batch 4096] [--reps 5]
+       python tools/adjoint_bench.py --wide [--reps 5]
 --generic: FBSTAB_HIP_GENERIC=1, forward and adjoint on the flat-vector kernels (default: the record instance
 <12,4,20> and its own adjoint).
 --dense: fbstab_hip_dense_adjoint_batch against fbstab_hip_dense_solve_batch on BASELINE configs[1] instead: 4096
-synthetic dense QPs of nz = 50, nl = 10, nv = 100 (the one-wavefront kernels)."""
+synthetic dense QPs of nz = 50, nl = 10, nv = 100 (the one-wavefront kernels).
+--wide: the two workloads of bench.py's `wide` block, built the way bench_wide builds them - the reference's
+reactor at N = 80 on <18,5,10> with 1024 QPs, and 2048 QPs of (30, 20, 6, 16) on <24,8,16> - on the row-pair record
+instances: the forward solve, the record adjoint (FBSTAB_HIP_FLAT_ADJOINT=0) and the flat-vector adjoint on a handle
+of the same shape (FBSTAB_HIP_FLAT_ADJOINT=1), every setting in a fresh process of its own.  One JSON line with both workloads and the
+library's sha256."""
 import argparse
+import hashlib
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -54,13 +62,118 @@ def dense(batch, reps):
                       "adjoint_status_nonzero": int((g["status"] != 0).sum().item())}))
 
 
+WIDE = ("reactor_N80", "ltv_30_20_6_16")
+CHILD_SECONDS = 300   # one child of --wide: set-up, six solves and six adjoints of one workload
+
+
+def wide_problem(name):
+    """bench.py: bench_wide's workloads."""
+    from tools import fixtures as fx
+    if name == "ltv_30_20_6_16":
+        one = fx.random_ltv_mpc(np.random.default_rng(5), 64, 30, 20, 6, 16)
+        p = fx.MpcProblem(30, 20, 6, 16)
+        p.arrays = {k: np.ascontiguousarray(np.tile(a, (32, 1))) for k, a in one.arrays.items()}
+        return p
+    gen = fx.OcpGenerator()
+    gen.CopolymerizationReactor(80)
+    one = gen.GetFBstabInput()
+    N, nx, nu, nc = one.sizes()
+    B = 1024
+    rng = np.random.default_rng(3)
+    p = fx.MpcProblem(N, nx, nu, nc)
+    p.arrays = {k: np.ascontiguousarray(np.broadcast_to(a, (B, a.shape[1]))).copy() for k, a in one.arrays.items()}
+    p.arrays["x0"] = p.arrays["x0"] * (1.0 + 0.2 * rng.standard_normal((B, nx)))
+    return p
+
+
+def wide_child(name, reps):
+    """One workload on one handle of this process (FBSTAB_HIP_FLAT_ADJOINT as the parent set it)."""
+    import torch
+    from fbstab_amd import hip_api
+    dev = torch.device("cuda:0")
+    p = wide_problem(name)
+    B = p.batch
+    data = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in p.arrays.items()}
+    s = hip_api.FBstabMpcBatch(*p.sizes(), max_batch=B)
+    zeros = lambda n: torch.zeros((B, n), dtype=torch.float64, device=dev)
+    rng = np.random.default_rng(0)
+    seeds = [torch.from_numpy(rng.standard_normal((B, n))).to(dev) for n in (p.nz, p.nl, p.nv)]
+    fwd, bwd = [], []
+    free0 = torch.cuda.mem_get_info(dev)[0]
+    for _ in range(reps + 1):
+        z, l, v, y = zeros(p.nz), zeros(p.nl), zeros(p.nv), zeros(p.nv)
+        out = s.Solve(data, z, l, v, y)
+        torch.cuda.synchronize()
+        fwd.append(s.last_kernel_ms())
+        g = s.Adjoint(data, z, l, v, *seeds)
+        torch.cuda.synchronize()
+        bwd.append(s.last_kernel_ms())
+    fwd, bwd = fwd[1:], bwd[1:]   # (the first pair warms the code objects and, with the knob, the adjoint's scratch)
+    eflag = hip_api.out_to_numpy(out)["eflag"]
+    st = g["status"].cpu().numpy()
+    dq = g["q"].cpu().numpy()
+    print(json.dumps({"workload": name, "shape": list(p.sizes()), "batch": B, "forward_kernel": s.kernel_name(),
+                      "adjoint_kernel": s.adjoint_kernel_name(), "forward_ms": round(float(np.median(fwd)), 3),
+                      "adjoint_ms": round(float(np.median(bwd)), 3),
+                      "forward_ms_all": [round(t, 3) for t in fwd], "adjoint_ms_all": [round(t, 3) for t in bwd],
+                      "success": int((eflag == 0).sum()), "adjoint_status_nonzero": int((st != 0).sum()),
+                      "grad_q_abs_sum_of_solved": float(np.abs(dq[eflag == 0]).sum()),
+                      "launch": s.query(),
+                      "device_bytes_taken_by_the_calls": int(free0 - torch.cuda.mem_get_info(dev)[0])}))
+
+
+def wide(reps):
+    from fbstab_amd import hip_api
+    hip_api.load_library()
+    with open(hip_api.current_library_path(), "rb") as f:
+        sha = hashlib.sha256(f.read()).hexdigest()
+    res = {"library_sha256": sha, "launches_timed": reps, "workloads": {}}
+    for name in WIDE:
+        runs = {}
+        for key, knob in (("record", "0"), ("flat", "1")):
+            env = dict(os.environ, FBSTAB_HIP_FLAT_ADJOINT=knob)
+            # every child under a time limit of its own; after one that failed, faulted or ran out of time no
+            # further child is started on the GPU
+            try:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--wide-child", name, "--reps", str(reps)],
+                                   env=env, capture_output=True, text=True, timeout=CHILD_SECONDS)
+            except subprocess.TimeoutExpired as e:
+                sys.stderr.write(str(e.stdout or "")[-2000:] + str(e.stderr or "")[-4000:])
+                raise SystemExit("adjoint_bench --wide: %s (%s) did not end within %d s; stopping" % (name, key, CHILD_SECONDS))
+            if r.returncode != 0:
+                sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+                raise SystemExit("adjoint_bench --wide: %s (%s) ended with status %d; stopping" % (name, key, r.returncode))
+            runs[key] = json.loads(r.stdout.strip().splitlines()[-1])
+        rec, flat = runs["record"], runs["flat"]
+        res["workloads"][name] = {
+            "shape": rec["shape"], "batch": rec["batch"], "forward_kernel": rec["forward_kernel"],
+            "forward_ms": rec["forward_ms"], "forward_ms_all": rec["forward_ms_all"],
+            "record_adjoint_kernel": rec["adjoint_kernel"], "record_adjoint_ms": rec["adjoint_ms"],
+            "record_adjoint_ms_all": rec["adjoint_ms_all"],
+            "flat_adjoint_kernel": flat["adjoint_kernel"], "flat_adjoint_ms": flat["adjoint_ms"],
+            "flat_adjoint_ms_all": flat["adjoint_ms_all"],
+            "flat_over_record": round(flat["adjoint_ms"] / rec["adjoint_ms"], 3),
+            "record_adjoint_over_forward": round(rec["adjoint_ms"] / rec["forward_ms"], 4),
+            "success": rec["success"], "adjoint_status_nonzero": [rec["adjoint_status_nonzero"], flat["adjoint_status_nonzero"]],
+            "grad_q_abs_sum_of_solved": [rec["grad_q_abs_sum_of_solved"], flat["grad_q_abs_sum_of_solved"]],
+            "launch": rec["launch"],
+            "device_bytes_taken_by_the_calls": [rec["device_bytes_taken_by_the_calls"], flat["device_bytes_taken_by_the_calls"]]}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--generic", action="store_true")
     ap.add_argument("--dense", action="store_true")
+    ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--wide-child", choices=WIDE, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.wide_child:
+        return wide_child(a.wide_child, a.reps)
+    if a.wide:
+        return wide(a.reps)
     if a.dense:
         return dense(a.batch or 4096, a.reps)
     a.batch = a.batch or 8192
@@ -88,9 +201,7 @@ def main():
     fwd, bwd = fwd[1:], bwd[1:]   # (the first pair warms the code objects and the adjoint's scratch)
     ok = int((hip_api.out_to_numpy(out)["eflag"] == 0).sum())
     f, b = float(np.median(fwd)), float(np.median(bwd))
-    kn = s.kernel_name()   # (the one-row record instances run their own adjoint; every other handle the flat-vector one)
-    adj_kernel = kn.replace("r16_kernel", "r16_adjoint_kernel") if kn.startswith("fbstab_mpc_r16_kernel<12,4,") \
-        else "fbstab_mpc_adjoint_kernel<64>"
+    adj_kernel = s.adjoint_kernel_name()
     print(json.dumps({"workload": "BASELINE configs[2]", "batch": a.batch, "forward_kernel": s.kernel_name(),
                       "adjoint_kernel": adj_kernel, "forward_ms": round(f, 3),
                       "backward_ms": round(b, 3), "backward_over_forward": round(b / f, 4),
