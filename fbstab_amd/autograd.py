@@ -20,6 +20,14 @@ The dense QP min 1/2 z'Hz + f'z s.t. Gz = h, Az <= b (the OptNet-style layer) wo
 
 with fbstab_hip_dense_adjoint_batch behind ``backward``.  The matrices are column-major images like the
 solver's inputs, and so are their gradients; with ``nl == 0``, ``G`` and ``h`` are ``(B, 0)`` tensors.
+
+Parameters shared by the batch (the matrices of an OptNet-style layer or of a differentiable MPC): an input of
+shape ``(len,)`` or ``(1, len)`` beside inputs of batch B > 1 is ONE array for all QPs.  The forward passes it to
+the solver with batch stride 0 (no B copies are made), and the backward asks fbstab_hip_*_adjoint_batch_reduced
+for its gradient: the sum over the batch, computed on the device from the points and the adjoint steps without
+the B per-QP images, in the input's own shape.  QPs that did not end in SUCCESS, or whose adjoint factorisation
+failed, are left out of the sum.  The sum is formed in a fixed order: the same inputs give the same bits.
+Per-QP inputs in the same call keep their per-QP gradients as above.
 """
 import torch
 
@@ -29,9 +37,13 @@ __all__ = ["MpcSolveFunction", "solve_mpc", "DenseSolveFunction", "solve_dense"]
 
 
 def _forward(names, ctx, solver, sigma, arrs):
-    data = {k: a.detach().contiguous() for k, a in zip(names, arrs)}
-    first = data[names[0]]  # (Q and H are never empty)
-    B, dev = first.shape[0], first.device
+    B = max(a.shape[0] if a.dim() == 2 else 1 for a in arrs)
+    # shared parameters: (len,) or (1, len) beside a batch of more than one QP; they travel as (1, len)
+    ctx.shared = tuple(k for k, a in zip(names, arrs) if B > 1 and (a.dim() == 1 or a.shape[0] == 1))
+    ctx.shapes = {k: a.shape for k, a in zip(names, arrs)}
+    data = {k: (a.detach().reshape(1, a.numel()) if k in ctx.shared else a.detach()).contiguous()
+            for k, a in zip(names, arrs)}
+    dev = data[names[0]].device  # (Q and H are never empty)
     z = torch.zeros((B, solver.nz), dtype=torch.float64, device=dev)
     l = torch.zeros((B, solver.nl), dtype=torch.float64, device=dev)
     v = torch.zeros((B, solver.nv), dtype=torch.float64, device=dev)
@@ -51,11 +63,23 @@ def _backward(names, ctx, gz, gl, gv, gout):
     saved = ctx.saved_tensors
     data = dict(zip(names, saved[:len(names)]))
     z, l, v, out = saved[len(names):]
-    g = ctx.solver.Adjoint(data, z, l, v, gz.contiguous(), gl.contiguous(), gv.contiguous(), sigma=ctx.sigma,
-                           want=want)
+    reduce = [k for k in want if k in ctx.shared]
+    if reduce:
+        g = ctx.solver.Adjoint(data, z, l, v, gz.contiguous(), gl.contiguous(), gv.contiguous(), sigma=ctx.sigma,
+                               want=want, reduce=reduce, out=out)
+    else:
+        g = ctx.solver.Adjoint(data, z, l, v, gz.contiguous(), gl.contiguous(), gv.contiguous(), sigma=ctx.sigma,
+                               want=want)
     eflag = out[:, 0:4].contiguous().view(torch.int32)[:, 0]  # SolverOut::eflag, on the device
     keep = ((eflag == 0) & (g["status"] == 0))[:, None]
-    grads = [torch.where(keep, g[k], torch.zeros_like(g[k])) if k in g else None for k in names]
+    grads = []
+    for k in names:
+        if k not in want:
+            grads.append(None)
+        elif k in reduce:  # (the library has left the same QPs out of the sum)
+            grads.append(g[k].reshape(ctx.shapes[k]))
+        else:
+            grads.append(torch.where(keep, g[k], torch.zeros_like(g[k])))
     return (None, None) + tuple(grads)
 
 
@@ -73,7 +97,8 @@ class MpcSolveFunction(torch.autograd.Function):
 
 def solve_mpc(solver, data, sigma: float = 0.0):
     """Differentiable batched solve: ``data`` maps the 12 names of MPC_SEQ to ``(B, len)`` float64 CUDA tensors
-    (any of them may require grad).  Returns ``(z, l, v, out)``; see the module docstring."""
+    (any of them may require grad; ``(len,)`` or ``(1, len)``: a parameter shared by the batch).  Returns
+    ``(z, l, v, out)``; see the module docstring."""
     return MpcSolveFunction.apply(solver, sigma, *[data[k] for k in MPC_SEQ])
 
 
@@ -91,5 +116,6 @@ class DenseSolveFunction(torch.autograd.Function):
 
 def solve_dense(solver, data, sigma: float = 0.0):
     """Differentiable batched dense solve: ``data`` maps the six names of DENSE_ARR to ``(B, len)`` float64 CUDA
-    tensors (any of them may require grad).  Returns ``(z, l, v, out)``; see the module docstring."""
+    tensors (any of them may require grad; ``(len,)`` or ``(1, len)``: a parameter shared by the batch).  Returns
+    ``(z, l, v, out)``; see the module docstring."""
     return DenseSolveFunction.apply(solver, sigma, *[data[k] for k in DENSE_ARR])

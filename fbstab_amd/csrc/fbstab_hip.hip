@@ -19,6 +19,7 @@
 #include "fb_dense.h"
 #include "fb_dense_wave.h"
 #include "fb_final_norms.h"
+#include "fb_grad_reduce.h"
 #include "fb_in_flight.h"
 #include "fb_mpc.h"
 #include "fb_mpc_r16.h"
@@ -495,6 +496,18 @@ struct SolverBase {
   }
   // workspace of the traced flat-vector MPC solve (kept from call to call)
   double* trace_ws = nullptr;
+  // fbstab_hip_*_adjoint_batch_reduced (fb_grad_reduce.h), allocated by the first such call and held until destroy:
+  // the adjoint steps of a caller who does not take them, max_batch x (nz + nl + nv) doubles, and the partial sums,
+  // grad_reduce_scratch_doubles(plan, max_batch)
+  double* red_adj = nullptr;
+  double* red_scratch = nullptr;
+  int ensure_reduce(const GradReducePlan& plan) {
+    if (!red_adj)
+      HIP_TRY(hipMalloc(&red_adj, sizeof(double) * (size_t)(var_len[0] + var_len[1] + var_len[2]) * max_batch));
+    if (!red_scratch)
+      HIP_TRY(hipMalloc(&red_scratch, sizeof(double) * (size_t)grad_reduce_scratch_doubles(plan, max_batch)));
+    return FBSTAB_HIP_OK;
+  }
 
   int release() {
     (void)hipSetDevice(device);
@@ -506,6 +519,8 @@ struct SolverBase {
     if (d_out_only) (void)hipFree(d_out_only);
     if (d_norms) (void)hipFree(d_norms);
     if (trace_ws) (void)hipFree(trace_ws);
+    if (red_adj) (void)hipFree(red_adj);
+    if (red_scratch) (void)hipFree(red_scratch);
     if (scratch) (void)hipFree(scratch);
     if (counter) (void)hipFree(counter);
     if (ev0) (void)hipEventDestroy(ev0);
@@ -744,17 +759,21 @@ struct AdjointStage {
   static_assert(FBSTAB_DENSE_NARR <= kMaxArrays, "one slot per problem array of either kind");
   const double* a_base[kMaxArrays];  // problem arrays
   long long a_stride[kMaxArrays];
-  double* g_base[kMaxArrays];  // their gradients (null: not asked for)
+  double* g_base[kMaxArrays];  // their gradients (null: not asked for, or summed over the batch)
   long long g_stride[kMaxArrays];
+  double* r_base[kMaxArrays];  // fbstab_hip_*_adjoint_batch_reduced: where the sum over the batch goes (null: per QP)
+  bool any_reduced = false;
   VarBatchArgs v, sd, ad;  // point, seeds, adjoints
   int* d_st = nullptr;     // status
   hipStream_t s = nullptr;
 
   // data, grad: base[] / stride[] of the caller's fbstab_*_batch_t and fbstab_*_grad_batch_t (h->arr_len.size()
-  // slots).  With batch == 0 nothing is staged and the caller returns.
+  // slots).  With batch == 0 nothing is staged and the caller returns.  `reduced`: a gradient slot of stride 0 is
+  // ONE array, the sum over the batch (otherwise refused like every stride below the length).
   int open(SolverBase* h, int batch, const double* const* data_base, const long long* data_stride,
            const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double* const* grad_base,
-           const long long* grad_stride, const fbstab_var_batch_t* adj, int* status, int flags, void* stream) {
+           const long long* grad_stride, const fbstab_var_batch_t* adj, int* status, int flags, void* stream,
+           bool reduced = false) {
     const int n = (int)h->arr_len.size();
     const long long* vlen = h->var_len;
     for (int i = 0; i < n; i++)
@@ -773,8 +792,9 @@ struct AdjointStage {
         return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
     }
     for (int i = 0; i < n; i++)
-      if (batch > 1 && grad_base[i] && grad_stride[i] < h->arr_len[i])
+      if (batch > 1 && grad_base[i] && grad_stride[i] < h->arr_len[i] && !(reduced && grad_stride[i] == 0))
         return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
+    for (int i = 0; i < kMaxArrays; i++) r_base[i] = nullptr;
     if (batch == 0) return FBSTAB_HIP_OK;
     HIP_TRY(hipSetDevice(h->device));
     s = stream ? (hipStream_t)stream : h->stream;
@@ -807,7 +827,16 @@ struct AdjointStage {
     }
     for (int i = 0; i < n; i++) {
       const bool asked = grad_base[i] && h->arr_len[i] > 0;  // (nl == 0: the G and h slots are ignored)
-      if (dev_ptrs) {
+      if (asked && reduced && grad_stride[i] == 0) {
+        // the adjoint kernel does not write this image: fb_grad_reduce.h forms its sum from (x, adj)
+        g_base[i] = nullptr; g_stride[i] = 0;
+        r_base[i] = grad_base[i];
+        if (!dev_ptrs) {
+          HIP_TRY(hipMalloc(&d_grad[i].p, sizeof(double) * (size_t)h->arr_len[i]));
+          r_base[i] = static_cast<double*>(d_grad[i].p);
+        }
+        any_reduced = true;
+      } else if (dev_ptrs) {
         g_base[i] = asked ? grad_base[i] : nullptr; g_stride[i] = grad_stride[i];
       } else if (asked) {
         HIP_TRY(hipMalloc(&d_grad[i].p, sizeof(double) * (size_t)h->arr_len[i] * batch));
@@ -824,6 +853,47 @@ struct AdjointStage {
     return FBSTAB_HIP_OK;
   }
 
+  // fbstab_hip_*_adjoint_batch_reduced with a slot to sum, before the adjoint's launch: the handle's buffers, and
+  // the adjoint steps the caller does not take go to the handle's own (the sums are formed from them).
+  int open_reduce(const GradReducePlan& plan) {
+    int rc = h_->ensure_reduce(plan);
+    if (rc != FBSTAB_HIP_OK) return rc;
+    double* own = h_->red_adj;
+    for (int i = 0; i < 3; i++) {
+      if (!ad.base[i] && h_->var_len[i] > 0) { ad.base[i] = own; ad.stride[i] = h_->var_len[i]; }
+      own += h_->var_len[i] * h_->max_batch;
+    }
+    return FBSTAB_HIP_OK;
+  }
+  // ... and after it, on the same stream: the partial sums, then the sums into the reduced slots.  `out`: null, or
+  // the solve's records, living where `status` lives.
+  int reduce(const GradReducePlan& plan, const fbstab_solver_out_t* out) {
+    GradReduceArgs ra;
+    ra.plan = plan;
+    for (int i = 0; i < 3; i++) {
+      ra.x[i] = v.base[i]; ra.xs[i] = v.stride[i];
+      ra.p[i] = ad.base[i]; ra.ps[i] = ad.stride[i];
+    }
+    ra.status = d_st;
+    ra.out = out;
+    if (out && SolverBase::out_on_host(flags_)) {
+      HIP_TRY(hipMalloc(&d_out.p, sizeof(fbstab_solver_out_t) * (size_t)batch_));
+      HIP_TRY(hipMemcpyAsync(d_out.p, out, sizeof(fbstab_solver_out_t) * (size_t)batch_, hipMemcpyHostToDevice, s));
+      ra.out = static_cast<const fbstab_solver_out_t*>(d_out.p);
+    }
+    ra.scratch = h_->red_scratch;
+    ra.batch = batch_;
+    GradReduceOut ro;
+    for (int i = 0; i < kGradReduceMaxSeq; i++) ro.base[i] = i < kMaxArrays ? r_base[i] : nullptr;
+    const int tiles = grad_reduce_tiles(plan), chunks = (int)grad_reduce_chunks(batch_);
+    hipLaunchKernelGGL(fbstab_grad_reduce_kernel, dim3(tiles * chunks), dim3(64), 0, s, ra);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(fbstab_grad_reduce_finish_kernel, dim3(tiles), dim3(256), 0, s, plan,
+                       static_cast<const double*>(h_->red_scratch), chunks, ro);
+    HIP_TRY(hipGetLastError());
+    return FBSTAB_HIP_OK;
+  }
+
   int close() {
     if (!(flags_ & FBSTAB_HIP_DEVICE_POINTERS)) {
       for (size_t i = 0; i < h_->arr_len.size(); i++)
@@ -831,9 +901,12 @@ struct AdjointStage {
           int rc = h_->download(grad_base_[i], grad_stride_[i] ? grad_stride_[i] : h_->arr_len[i], h_->arr_len[i],
                                 batch_, g_base[i], s);
           if (rc != FBSTAB_HIP_OK) return rc;
+        } else if (r_base[i]) {
+          int rc = h_->download(grad_base_[i], h_->arr_len[i], h_->arr_len[i], 1, r_base[i], s);
+          if (rc != FBSTAB_HIP_OK) return rc;
         }
       for (int i = 0; i < 3; i++)
-        if (ad.base[i]) {
+        if (ad.base[i] && adj_ && adj_->base[i]) {  // (a reduced call may have pointed the others at the handle's own)
           int rc = h_->download(adj_->base[i], adj_->stride[i] ? adj_->stride[i] : h_->var_len[i], h_->var_len[i],
                                 batch_, ad.base[i], s);
           if (rc != FBSTAB_HIP_OK) return rc;
@@ -846,7 +919,7 @@ struct AdjointStage {
   }
 
  private:
-  DevBuf d_seed[3], d_adj[3], d_grad[kMaxArrays], d_status;
+  DevBuf d_seed[3], d_adj[3], d_grad[kMaxArrays], d_status, d_out;
   // what `close` copies back to, and how
   SolverBase* h_ = nullptr;
   int batch_ = 0, flags_ = 0;
@@ -1347,18 +1420,26 @@ int fbstab_hip_mpc_debug_newton(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t*
 // Reverse-mode derivative of the solution map at returned points (include/fbstab_hip.h).  One launch of
 // fbstab_mpc_adjoint_kernel: the Newton matrix of RiccatiLinearSolver::Initialize at x = xbar = the point
 // (riccati_linear_solver.cc:77-210), one Solve (:212-344) with the adjoint's right-hand side, one contraction.
-int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
-                                 const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
-                                 const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
-                                 int flags, void* stream) {
+// `reduced`: fbstab_hip_mpc_adjoint_batch_reduced - gradient slots of stride 0 are summed over the batch by the
+// kernels of fb_grad_reduce.h behind the adjoint's launch (`out`: the solve's records, or null).
+static int mpc_adjoint_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                            const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                            const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
+                            const fbstab_solver_out_t* out, int flags, void* stream, bool reduced) {
   int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
   if (rc != FBSTAB_HIP_OK) return rc;
   if (!seed || !grad) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
   AdjointStage st;
-  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream);
+  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream,
+               reduced);
   if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
   hipStream_t s = st.s;
   const fbk::MpcLayout& L = h->lay;
+  const GradReducePlan plan = grad_reduce_plan_mpc(L.N, L.nx, L.nu, L.nc);
+  if (st.any_reduced) {
+    rc = st.open_reduce(plan);
+    if (rc != FBSTAB_HIP_OK) return rc;
+  }
   MpcBatchArgs a;
   MpcGradArgs g;
   for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
@@ -1429,7 +1510,25 @@ int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t h, int batch, const fbstab_
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(h->ev1, s));
   h->timed = true;
+  if (st.any_reduced) {
+    rc = st.reduce(plan, out);
+    if (rc != FBSTAB_HIP_OK) return rc;
+  }
   return st.close();
+}
+
+int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                 const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                                 const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
+                                 int flags, void* stream) {
+  return mpc_adjoint_impl(h, batch, data, x, seed, sigma, grad, adj, status, nullptr, flags, stream, false);
+}
+
+int fbstab_hip_mpc_adjoint_batch_reduced(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                         const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                                         const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj,
+                                         int* status, const fbstab_solver_out_t* out, int flags, void* stream) {
+  return mpc_adjoint_impl(h, batch, data, x, seed, sigma, grad, adj, status, out, flags, stream, true);
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;
@@ -1768,10 +1867,11 @@ int fbstab_hip_dense_debug_newton(fbstab_dense_handle_t h, const fbstab_dense_ba
 // adjoint kernel that matches the handle's solve kernel: the Newton matrix of DenseCholeskySolver::Initialize at
 // x = xbar = the point (dense_cholesky_solver.cc:32-79), one Solve (:81-127) with the adjoint's right-hand side,
 // one contraction.
-int fbstab_hip_dense_adjoint_batch(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
-                                   const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
-                                   const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
-                                   int flags, void* stream) {
+// `reduced`: fbstab_hip_dense_adjoint_batch_reduced, as mpc_adjoint_impl.
+static int dense_adjoint_impl(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
+                              const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                              const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
+                              const fbstab_solver_out_t* out, int flags, void* stream, bool reduced) {
   // what needs no handle comes first: the argument blocks, the one seed that is required, and strides that no
   // handle accepts (nz and nv are positive: z, v, H, f, A, b are never empty)
   if (!data || !x || !seed || !grad || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
@@ -1785,15 +1885,21 @@ int fbstab_hip_dense_adjoint_batch(fbstab_dense_handle_t h, int batch, const fbs
         return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
     }
     for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b})
-      if (grad->base[i] && grad->stride[i] < 1)
+      if (grad->base[i] && grad->stride[i] < 1 && !(reduced && grad->stride[i] == 0))
         return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
   }
   int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
   if (rc != FBSTAB_HIP_OK) return rc;
   AdjointStage st;
-  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream);
+  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream,
+               reduced);
   if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
   hipStream_t s = st.s;
+  const GradReducePlan plan = grad_reduce_plan_dense((int)h->var_len[0], (int)h->var_len[1], (int)h->var_len[2]);
+  if (st.any_reduced) {
+    rc = st.open_reduce(plan);
+    if (rc != FBSTAB_HIP_OK) return rc;
+  }
   DenseBatchArgs a;
   DenseGradArgs g;
   for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
@@ -1834,7 +1940,25 @@ int fbstab_hip_dense_adjoint_batch(fbstab_dense_handle_t h, int batch, const fbs
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(h->ev1, s));
   h->timed = true;
+  if (st.any_reduced) {
+    rc = st.reduce(plan, out);
+    if (rc != FBSTAB_HIP_OK) return rc;
+  }
   return st.close();
+}
+
+int fbstab_hip_dense_adjoint_batch(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
+                                   const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                                   const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
+                                   int flags, void* stream) {
+  return dense_adjoint_impl(h, batch, data, x, seed, sigma, grad, adj, status, nullptr, flags, stream, false);
+}
+
+int fbstab_hip_dense_adjoint_batch_reduced(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
+                                           const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                                           const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj,
+                                           int* status, const fbstab_solver_out_t* out, int flags, void* stream) {
+  return dense_adjoint_impl(h, batch, data, x, seed, sigma, grad, adj, status, out, flags, stream, true);
 }
 
 double fbstab_hip_dense_last_kernel_ms(fbstab_dense_handle_t h) { return h ? h->last_kernel_ms() : -1.0; }

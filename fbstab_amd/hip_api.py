@@ -166,6 +166,11 @@ def load_library() -> C.CDLL:
         lib.fbstab_hip_dense_adjoint_batch.argtypes = [
             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_int, C.c_void_p]
+    for kind in ("mpc", "dense"):  # (absent from a build of an earlier round loaded for an A/B)
+        if hasattr(lib, f"fbstab_hip_{kind}_adjoint_batch_reduced"):
+            getattr(lib, f"fbstab_hip_{kind}_adjoint_batch_reduced").argtypes = [
+                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -196,10 +201,11 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_last_kernel_ms", "fbstab_hip_mpc_query", "fbstab_hip_mpc_kernel_name",
     "fbstab_hip_mpc_refined_steps", "fbstab_hip_mpc_create_in_flight",
     "fbstab_hip_mpc_debug_newton", "fbstab_hip_mpc_adjoint_batch", "fbstab_hip_mpc_adjoint_kernel_name",
-    "fbstab_hip_debug_stamps",
+    "fbstab_hip_mpc_adjoint_batch_reduced", "fbstab_hip_debug_stamps",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",
     "fbstab_hip_dense_solve_traced", "fbstab_hip_dense_adjoint_batch",
+    "fbstab_hip_dense_adjoint_batch_reduced",
     "fbstab_hip_dense_debug_newton", "fbstab_hip_dense_last_kernel_ms", "fbstab_hip_dense_query",
     "fbstab_hip_dense_set_factorisation", "fbstab_hip_dense_get_factorisation",
     "fbstab_hip_shard_group_create", "fbstab_hip_shard_group_destroy", "fbstab_hip_shard_group_stats",
@@ -219,6 +225,13 @@ def _check(lib, rc):
 
 def _is_torch(a) -> bool:
     return type(a).__module__.startswith("torch")
+
+
+def _shared_stride(a, st: int, B: int) -> int:
+    """Batch stride of a problem array in a batch of ``B``: a ``(1, len)`` array beside B > 1 QPs is shared by all
+    of them (stride 0, include/fbstab_hip.h)."""
+    assert a.shape[0] == B or a.shape[0] == 1, (a.shape, B)
+    return 0 if (a.shape[0] == 1 and B > 1) else st
 
 
 def _ptr_stride(a, length: int):
@@ -276,7 +289,7 @@ class _SolverBase:
     def _solve(self, batch_struct, names: Sequence[str], lens: Sequence[int], arrays,
                var_lens, z, l, v, y, out, stream, async_, keep_matrices=False, norms=False):
         dev_flags = []
-        B = None
+        B = z.shape[0]
         for i, (k, n) in enumerate(zip(names, lens)):
             a = arrays[k]
             if n == 0:
@@ -285,9 +298,8 @@ class _SolverBase:
                 continue
             p, s, d = _ptr_stride(a, n)
             batch_struct.base[i] = p
-            batch_struct.stride[i] = s
+            batch_struct.stride[i] = _shared_stride(a, s, B)
             dev_flags.append(d)
-            B = a.shape[0] if B is None else B
         vb = _VarBatch()
         for i, (a, n) in enumerate(zip((z, l, v, y), var_lens)):
             if n == 0:
@@ -336,11 +348,15 @@ class _SolverBase:
         return out
 
     def _adjoint(self, fn, batch_struct, grad_struct, names: Sequence[str], lens: Sequence[int], data,
-                 z, l, v, gz, gl, gv, sigma, want, adj, stream, async_):
-        """fbstab_hip_*_adjoint_batch (``fn``) behind ``Adjoint``; an array of length 0 is a NULL slot."""
-        want = tuple(names if want is None else want)
-        unknown = set(want) - set(names)
+                 z, l, v, gz, gl, gv, sigma, want, adj, stream, async_, reduce=(), out=None):
+        """fbstab_hip_*_adjoint_batch (``fn``) behind ``Adjoint``; an array of length 0 is a NULL slot.  With names
+        in ``reduce`` the call goes to fbstab_hip_*_adjoint_batch_reduced, those slots with stride 0."""
+        reduce = tuple(reduce)
+        want = tuple(names if want is None else want) + tuple(k for k in reduce if want is not None and k not in want)
+        unknown = (set(want) | set(reduce)) - set(names)
         assert not unknown, unknown
+        if reduce:
+            fn = getattr(self._lib, f"fbstab_hip_{self._kind}_adjoint_batch_reduced")
         dev_flags = []
         B = z.shape[0]
         for i, (k, n) in enumerate(zip(names, lens)):
@@ -348,8 +364,7 @@ class _SolverBase:
                 batch_struct.base[i], batch_struct.stride[i] = None, 0
                 continue
             p, st, d = _ptr_stride(data[k], n)
-            assert data[k].shape[0] == B
-            batch_struct.base[i], batch_struct.stride[i] = p, st
+            batch_struct.base[i], batch_struct.stride[i] = p, _shared_stride(data[k], st, B)
             dev_flags.append(d)
         var_lens = (self.nz, self.nl, self.nv)
 
@@ -372,19 +387,23 @@ class _SolverBase:
         assert on_dev or not any(dev_flags), "mix of host and device arrays"
         if on_dev:
             import torch
-            zeros = lambda n, dt=torch.float64: torch.zeros((B, n), dtype=dt, device=z.device)
+            zeros = lambda n, dt=torch.float64, rows=B: torch.zeros((rows, n), dtype=dt, device=z.device)
             if not stream:
                 stream = torch.cuda.current_stream(z.device).cuda_stream
             flags = DEVICE_POINTERS | (ASYNC if async_ else 0)
             status = torch.zeros(B, dtype=torch.int32, device=z.device)
         else:
-            zeros = lambda n, dt=np.float64: np.zeros((B, n), dtype=dt)
+            zeros = lambda n, dt=np.float64, rows=B: np.zeros((rows, n), dtype=dt)
             flags = HOST_POINTERS
             status = np.zeros(B, dtype=np.int32)
         res = {}
         for i, (k, n) in enumerate(zip(names, lens)):
             grad_struct.base[i], grad_struct.stride[i] = None, 0
-            if k in want:
+            if k in reduce:
+                res[k] = zeros(n, rows=1)  # ONE array: the sum over the batch
+                if n > 0:
+                    grad_struct.base[i], grad_struct.stride[i] = _ptr_stride(res[k], n)[0], 0
+            elif k in want:
                 res[k] = zeros(n)
                 if n > 0:
                     grad_struct.base[i], grad_struct.stride[i] = _ptr_stride(res[k], n)[:2]
@@ -393,10 +412,19 @@ class _SolverBase:
             for k, n in zip(("dz", "dl", "dv"), var_lens):
                 res[k] = zeros(n)
             ab = var((res["dz"], res["dl"], res["dv"]), False)
-        _check(self._lib, fn(
-            self._h, B, C.byref(batch_struct), C.byref(xb), C.byref(sb), C.c_double(sigma), C.byref(grad_struct),
-            C.byref(ab) if ab is not None else None, C.c_void_p(status.data_ptr() if on_dev else status.ctypes.data),
-            flags, C.c_void_p(stream) if stream else None))
+        args = [self._h, B, C.byref(batch_struct), C.byref(xb), C.byref(sb), C.c_double(sigma), C.byref(grad_struct),
+                C.byref(ab) if ab is not None else None,
+                C.c_void_p(status.data_ptr() if on_dev else status.ctypes.data)]
+        if reduce:
+            # the SolverOut records of the solve, living where status lives (None: no QP is left out for its eflag)
+            if out is not None:
+                assert _is_torch(out) == on_dev and out.shape[0] == B, "out lives where the arrays live"
+                args.append(C.c_void_p(out.data_ptr() if on_dev else out.ctypes.data))
+            else:
+                args.append(None)
+        else:
+            assert out is None, "out= takes part in a reduced call only"
+        _check(self._lib, fn(*args, flags, C.c_void_p(stream) if stream else None))
         res["status"] = status
         return res
 
@@ -588,15 +616,19 @@ class FBstabMpcBatch(_SolverBase):
 
     def Adjoint(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0,
                 want: Optional[Sequence[str]] = None, adj: bool = False, stream: int = 0,
-                async_: bool = False) -> Dict[str, object]:
+                async_: bool = False, reduce: Sequence[str] = (), out=None) -> Dict[str, object]:
         """Reverse-mode derivative of the solution map (fbstab_hip_mpc_adjoint_batch): for a loss L with
         seeds ``gz, gl, gv`` = dL/d(z, l, v) at the returned point ``(z, l, v)`` (``(batch, n)`` arrays, all numpy
         or all torch CUDA tensors, like ``Solve``), returns a dict with dL/d(sequence) for every name of ``want``
         (default: all 12 of MPC_SEQ, each ``(batch, len)``), ``"status"`` (``(batch,)`` int32: 0, or 1 where
         the factorisation failed and the gradients are zero) and, with ``adj=True``, ``"dz", "dl", "dv"``.
-        ``gl``/``gv`` None: zero seeds.  ``sigma <= 0``: 1e-8."""
+        ``gl``/``gv`` None: zero seeds.  ``sigma <= 0``: 1e-8.
+        ``reduce``: names whose gradient comes back as ONE ``(1, len)`` array, the sum over the batch (for data
+        shared by the batch; fbstab_hip_mpc_adjoint_batch_reduced), leaving out QPs whose status is 1 and, with
+        ``out`` (the records ``Solve`` returned), QPs whose solve did not end in SUCCESS.  A ``(1, len)`` array in
+        ``data`` beside a batch of more than one QP is shared by all of them."""
         return self._adjoint(self._lib.fbstab_hip_mpc_adjoint_batch, _MpcBatch(), _MpcGradBatch(), MPC_SEQ,
-                             self.seq_len, data, z, l, v, gz, gl, gv, sigma, want, adj, stream, async_)
+                             self.seq_len, data, z, l, v, gz, gl, gv, sigma, want, adj, stream, async_, reduce, out)
 
 
 class FBstabDenseBatch(_SolverBase):
@@ -680,16 +712,17 @@ class FBstabDenseBatch(_SolverBase):
 
     def Adjoint(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0,
                 want: Optional[Sequence[str]] = None, adj: bool = False, stream: int = 0,
-                async_: bool = False) -> Dict[str, object]:
+                async_: bool = False, reduce: Sequence[str] = (), out=None) -> Dict[str, object]:
         """Reverse-mode derivative of the dense solution map (fbstab_hip_dense_adjoint_batch): for a loss L with
         seeds ``gz, gl, gv`` = dL/d(z, l, v) at the returned point ``(z, l, v)`` (``(batch, n)`` arrays, all numpy
         or all torch CUDA tensors, like ``Solve``), returns a dict with dL/d(array) for every name of ``want``
         (default: all six of DENSE_ARR, each ``(batch, len)``, the matrices column-major like the inputs),
         ``"status"`` (``(batch,)`` int32: 0, or 1 where the factorisation failed and the gradients are zero) and,
         with ``adj=True``, ``"dz", "dl", "dv"``.  ``gl``/``gv`` None: zero seeds.  ``sigma <= 0``: 1e-8.  With
-        ``nl == 0`` the G, h and l arrays are ``(batch, 0)`` (or None on input)."""
+        ``nl == 0`` the G, h and l arrays are ``(batch, 0)`` (or None on input).  ``reduce``, ``out`` and shared
+        ``(1, len)`` inputs: as FBstabMpcBatch.Adjoint (fbstab_hip_dense_adjoint_batch_reduced)."""
         return self._adjoint(self._lib.fbstab_hip_dense_adjoint_batch, _DenseBatch(), _DenseGradBatch(), DENSE_ARR,
-                             self.arr_len, data, z, l, v, gz, gl, gv, sigma, want, adj, stream, async_)
+                             self.arr_len, data, z, l, v, gz, gl, gv, sigma, want, adj, stream, async_, reduce, out)
 
 
 class ShardGroup:

@@ -322,6 +322,39 @@ int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t handle, int batch, const fb
                                  int* status, int flags, void* stream);
 /* Name of the kernel the next fbstab_hip_mpc_adjoint_batch of this handle launches. */
 const char* fbstab_hip_mpc_adjoint_kernel_name(fbstab_mpc_handle_t handle);
+/* fbstab_hip_mpc_adjoint_batch for data shared by the batch: gradients SUMMED over the batch.  The
+ * learning workloads these gradients exist for (a differentiable MPC, an OptNet-style layer) share
+ * the matrices among all QPs of a batch (a data stride of 0), and what they need is
+ * sum_b dL/d(data_b): ONE array, not `batch` images that are written and then read again for the sum.
+ * Everything is as in fbstab_hip_mpc_adjoint_batch - validation order, flags, streams, host staging,
+ * batch == 0, the adjoint kernel and fbstab_hip_mpc_last_kernel_ms, which reports the adjoint's
+ * launch as there - except:
+ *   grad:   a slot whose stride is at least the array length is a per-QP gradient, computed by the
+ *           same kernel and bitwise what fbstab_hip_mpc_adjoint_batch returns.  A slot whose stride
+ *           is 0 receives ONE array, the sum over the batch (a host-pointer call downloads one array).
+ *           Any mix is allowed; with batch > 1 a stride strictly between 0 and the length, or below
+ *           0, is FBSTAB_HIP_ERR_ARGUMENT.
+ *   out:    NULL, or the SolverOut records of the solve that produced x, living where `status` lives.
+ *           QPs whose eflag is not FBSTAB_SUCCESS are left out of every reduced slot, and so are QPs
+ *           whose adjoint status is 1, with or without `out` (their points may hold anything, NaN
+ *           included: they are not read into the sum).  Per-QP slots do not depend on `out`.
+ * The adjoint kernel runs with the reduced slots NULL, so it does not write those images, and with
+ * adj = the caller's, or where the caller takes none a buffer of the handle's.  Two more launches
+ * on the same stream then form the sums from (x, adj) on the matrix cores (fb_grad_reduce.h:
+ * fbstab_grad_reduce_kernel, v_mfma_f64_16x16x4, one wavefront per 16 x 16 tile of a stage's
+ * -(P'Z + X'DZ) and per chunk of 128 QPs; fbstab_grad_reduce_finish_kernel adds a tile's chunks).
+ * The order of every sum is fixed by the shape and the batch size alone - no atomics, nothing that
+ * depends on the grid, the CU count or the handle - so the same inputs give the same bits.
+ * Memory: the first reduced call of a handle allocates, and holds until destroy, max_batch x
+ * (nz + nl + nv) doubles for the adjoint steps (97.5 MB at (N, nx, nu, nc) = (30, 12, 4, 20) and
+ * max_batch 8192) and tiles x ceil(max_batch / 128) x 272 doubles for the partial sums (94 tiles
+ * there: 13.1 MB); as for the flat adjoint's scratch, fbstab_hip_mpc_query's scratch_bytes does
+ * not count them. */
+int fbstab_hip_mpc_adjoint_batch_reduced(fbstab_mpc_handle_t handle, int batch, const fbstab_mpc_batch_t* data,
+                                         const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed,
+                                         double sigma, const fbstab_mpc_grad_batch_t* grad,
+                                         const fbstab_var_batch_t* adj, int* status,
+                                         const fbstab_solver_out_t* out, int flags, void* stream);
 
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);
@@ -474,6 +507,22 @@ int fbstab_hip_dense_adjoint_batch(fbstab_dense_handle_t handle, int batch, cons
                                    const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
                                    const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj,
                                    int* status, int flags, void* stream);
+/* fbstab_hip_dense_adjoint_batch with gradients summed over the batch, for arrays the batch shares:
+ * fbstab_hip_mpc_adjoint_batch_reduced for the dense QP.  A grad slot of stride 0 receives ONE
+ * array, sum_b of the per-QP gradient (H_bar, G_bar, A_bar column-major as there); slots of stride
+ * >= length are per QP and bitwise those of fbstab_hip_dense_adjoint_batch; with batch > 1 any other
+ * stride is FBSTAB_HIP_ERR_ARGUMENT, checked where fbstab_hip_dense_adjoint_batch checks strides.
+ * `out` (NULL, or the solve's records, living where `status` lives) and the adjoint status leave QPs
+ * out of the sums as there.  Kernels, determinism and fbstab_hip_dense_last_kernel_ms: as there, the
+ * tiles those of M = -(P'Z + X'DZ), (nz + nl + nv) x nz.  Memory held from the first reduced call
+ * until destroy, not counted by fbstab_hip_dense_query: max_batch x (nz + nl + nv) doubles and
+ * tiles x ceil(max_batch / 128) x 272 doubles (at (50, 10, 100) and max_batch 4096: 5.2 MB and, with
+ * 40 tiles, 2.8 MB). */
+int fbstab_hip_dense_adjoint_batch_reduced(fbstab_dense_handle_t handle, int batch,
+                                           const fbstab_dense_batch_t* data, const fbstab_var_batch_t* x,
+                                           const fbstab_var_batch_t* seed, double sigma,
+                                           const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj,
+                                           int* status, const fbstab_solver_out_t* out, int flags, void* stream);
 double fbstab_hip_dense_last_kernel_ms(fbstab_dense_handle_t handle);
 int fbstab_hip_dense_query(fbstab_dense_handle_t handle, long long* scratch_bytes,
                            int* lds_bytes, int* workgroups, int* threads);

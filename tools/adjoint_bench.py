@@ -6,6 +6,7 @@ last_kernel_ms (HIP events around the one launch); the median of --reps launches
 usage: python tools/adjoint_bench.py [--batch 8192] [--reps 5] [--generic]
        python tools/adjoint_bench.py --dense [--batch 4096] [--reps 5]
        python tools/adjoint_bench.py --wide [--reps 5]
+       python tools/adjoint_bench.py --reduced [--reps 5]
 --generic: FBSTAB_HIP_GENERIC=1, forward and adjoint on the flat-vector kernels (default: the record instance
 <12,4,20> and its own adjoint).
 --dense: fbstab_hip_dense_adjoint_batch against fbstab_hip_dense_solve_batch on BASELINE configs[1] instead: 4096
@@ -14,7 +15,14 @@ synthetic dense QPs of nz = 50, nl = 10, nv = 100 (the one-wavefront kernels).
 reactor at N = 80 on <18,5,10> with 1024 QPs, and 2048 QPs of (30, 20, 6, 16) on <24,8,16> - on the row-pair record
 instances: the forward solve, the record adjoint (FBSTAB_HIP_FLAT_ADJOINT=0) and the flat-vector adjoint on a handle
 of the same shape (FBSTAB_HIP_FLAT_ADJOINT=1), every setting in a fresh process of its own.  One JSON line with both workloads and the
-library's sha256."""
+library's sha256.
+--reduced: the backward of a layer whose matrices are shared by the batch, on BASELINE configs[2] (8192 QPs, all twelve
+sequences wanted) and configs[1] (4096 dense QPs): fbstab_hip_*_adjoint_batch with per-QP slots followed by
+torch.sum(dim=0) of every matrix gradient, against ONE fbstab_hip_*_adjoint_batch_reduced call with the matrix slots
+reduced.  Times are torch events around the whole backward on torch's current stream (allocation of the outputs
+included, as a caller pays it), the median of --reps launches; the two ways alternate, each in a fresh process.  One
+JSON line (profiles/reduced_adjoint_bench.json) with the library's sha256; `not_slower` says whether the reduced call
+is within the spread of the launches of the per-QP way."""
 import argparse
 import hashlib
 import json
@@ -161,6 +169,89 @@ def wide(reps):
     print(json.dumps(res))
 
 
+REDUCED = {"mpc_30_12_4_20": 8192, "dense_50_10_100": 4096}
+REDUCED_WAYS = ("per_qp_then_sum", "reduced")
+
+
+def reduced_child(name, way, reps):
+    """One workload, one way, in this process: solve once, then reps + 1 backward passes (the first warms up)."""
+    import torch
+    from tools import fixtures as fx
+    from fbstab_amd import hip_api
+    dev = torch.device("cuda:0")
+    B = REDUCED[name]
+    if name.startswith("dense"):
+        p = fx.synthetic_dense_batch(B, 50, 10, 100)
+        s = hip_api.FBstabDenseBatch(50, 10, 100, max_batch=B)
+        names, matrices = hip_api.DENSE_ARR, ("H", "G", "A")
+    else:
+        p = fx.synthetic_mpc_batch(B)
+        s = hip_api.FBstabMpcBatch(*p.sizes(), max_batch=B)
+        names, matrices = hip_api.MPC_SEQ, ("Q", "R", "S", "A", "B", "E", "L")
+    data = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in p.arrays.items()}
+    zeros = lambda n: torch.zeros((B, n), dtype=torch.float64, device=dev)
+    z, l, v, y = zeros(p.nz), zeros(p.nl), zeros(p.nv), zeros(p.nv)
+    out = s.Solve(data, z, l, v, y)
+    rng = np.random.default_rng(0)
+    seeds = [torch.from_numpy(rng.standard_normal((B, n))).to(dev) for n in (p.nz, p.nl, p.nv)]
+    torch.cuda.synchronize()
+    ms, kernel_ms = [], []
+    for _ in range(reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if way == "reduced":
+            g = s.Adjoint(data, z, l, v, *seeds, reduce=matrices)
+            sums = {k: g[k] for k in matrices}
+        else:
+            g = s.Adjoint(data, z, l, v, *seeds)
+            sums = {k: torch.sum(g[k], dim=0, keepdim=True) for k in matrices}
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+        kernel_ms.append(s.last_kernel_ms())
+        check = float(sum(t.abs().sum().item() for t in sums.values()))
+        del g, sums
+    ms, kernel_ms = ms[1:], kernel_ms[1:]
+    print(json.dumps({"workload": name, "way": way, "batch": B, "ms": round(float(np.median(ms)), 3),
+                      "ms_all": [round(t, 3) for t in ms], "adjoint_kernel_ms": round(float(np.median(kernel_ms)), 3),
+                      "matrix_gradient_abs_sum": check,
+                      "success": int((hip_api.out_to_numpy(out)["eflag"] == 0).sum())}))
+
+
+def reduced(reps):
+    from fbstab_amd import hip_api
+    hip_api.load_library()
+    with open(hip_api.current_library_path(), "rb") as f:
+        sha = hashlib.sha256(f.read()).hexdigest()
+    res = {"library_sha256": sha, "launches_timed": reps, "workloads": {}}
+    for name in REDUCED:
+        runs = {}
+        for way in REDUCED_WAYS:
+            # every child under a time limit of its own; after one that failed, faulted or ran out of time no
+            # further child is started on the GPU
+            try:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--reduced-child", name, way, "--reps",
+                                    str(reps)], capture_output=True, text=True, timeout=CHILD_SECONDS)
+            except subprocess.TimeoutExpired as e:
+                sys.stderr.write(str(e.stdout or "")[-2000:] + str(e.stderr or "")[-4000:])
+                raise SystemExit("adjoint_bench --reduced: %s (%s) did not end within %d s; stopping" % (name, way, CHILD_SECONDS))
+            if r.returncode != 0:
+                sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+                raise SystemExit("adjoint_bench --reduced: %s (%s) ended with status %d; stopping" % (name, way, r.returncode))
+            runs[way] = json.loads(r.stdout.strip().splitlines()[-1])
+        par, red = runs["per_qp_then_sum"], runs["reduced"]
+        spread = max(par["ms_all"]) - min(par["ms_all"])
+        res["workloads"][name] = {
+            "batch": par["batch"], "per_qp_then_sum_ms": par["ms"], "per_qp_then_sum_ms_all": par["ms_all"],
+            "reduced_ms": red["ms"], "reduced_ms_all": red["ms_all"],
+            "adjoint_kernel_ms": [par["adjoint_kernel_ms"], red["adjoint_kernel_ms"]],
+            "reduced_over_per_qp_then_sum": round(red["ms"] / par["ms"], 4),
+            "spread_of_the_per_qp_launches_ms": round(spread, 3), "not_slower": red["ms"] <= par["ms"] + spread,
+            "matrix_gradient_abs_sum": [par["matrix_gradient_abs_sum"], red["matrix_gradient_abs_sum"]],
+            "success": par["success"]}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=None)
@@ -169,7 +260,13 @@ def main():
     ap.add_argument("--dense", action="store_true")
     ap.add_argument("--wide", action="store_true")
     ap.add_argument("--wide-child", choices=WIDE, help=argparse.SUPPRESS)
+    ap.add_argument("--reduced", action="store_true")
+    ap.add_argument("--reduced-child", nargs=2, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.reduced_child:
+        return reduced_child(a.reduced_child[0], a.reduced_child[1], a.reps)
+    if a.reduced:
+        return reduced(a.reps)
     if a.wide_child:
         return wide_child(a.wide_child, a.reps)
     if a.wide:
