@@ -28,6 +28,12 @@ for its gradient: the sum over the batch, computed on the device from the points
 the B per-QP images, in the input's own shape.  QPs that did not end in SUCCESS, or whose adjoint factorisation
 failed, are left out of the sum.  The sum is formed in a fixed order: the same inputs give the same bits.
 Per-QP inputs in the same call keep their per-QP gradients as above.
+
+Forward mode (``torch.autograd.forward_ad``): inside a ``dual_level``, inputs made dual with ``make_dual`` give
+``z, l, v`` their tangents J dtheta through ONE call of fbstab_hip_*_tangent_batch at the returned points, with
+the tangents that are present (a shared input's tangent travels with batch stride 0 like the input).  As in the
+backward, a QP whose solve did not end in SUCCESS, or whose factorisation failed, gets ZERO tangents.
+(``torch.func.jvp`` is not served: it needs a ``setup_context`` style function.)
 """
 import torch
 
@@ -51,6 +57,10 @@ def _forward(names, ctx, solver, sigma, arrs):
     out = solver.Solve(data, z, l, v, y)
     ctx.solver, ctx.sigma = solver, sigma
     ctx.save_for_backward(*[data[k] for k in names], z, l, v, out)
+    ctx.save_for_forward(*[data[k] for k in names], z, l, v, out)
+    # absent tangents reach `_jvp` as None instead of zeros (one Tangent call with the tangents that are present);
+    # `_backward` then makes its own zeros for seeds torch leaves out, which is what it was handed before
+    ctx.set_materialize_grads(False)
     ctx.mark_non_differentiable(out)
     return z, l, v, out
 
@@ -63,6 +73,7 @@ def _backward(names, ctx, gz, gl, gv, gout):
     saved = ctx.saved_tensors
     data = dict(zip(names, saved[:len(names)]))
     z, l, v, out = saved[len(names):]
+    gz, gl, gv = (torch.zeros_like(x) if g is None else g for g, x in zip((gz, gl, gv), (z, l, v)))
     reduce = [k for k in want if k in ctx.shared]
     if reduce:
         g = ctx.solver.Adjoint(data, z, l, v, gz.contiguous(), gl.contiguous(), gv.contiguous(), sigma=ctx.sigma,
@@ -83,6 +94,22 @@ def _backward(names, ctx, gz, gl, gv, gout):
     return (None, None) + tuple(grads)
 
 
+def _jvp(names, ctx, tangents):
+    saved = ctx.saved_tensors
+    data = dict(zip(names, saved[:len(names)]))
+    z, l, v, out = saved[len(names):]
+    ddata = {}
+    for k, t in zip(names, tangents):
+        if t is None or t.numel() == 0:
+            continue
+        t = t.detach()
+        ddata[k] = (t.reshape(1, t.numel()) if k in ctx.shared else t).contiguous()
+    res = ctx.solver.Tangent(data, z, l, v, ddata, sigma=ctx.sigma)
+    eflag = out[:, 0:4].contiguous().view(torch.int32)[:, 0]  # SolverOut::eflag, on the device
+    keep = ((eflag == 0) & (res["status"] == 0))[:, None]
+    return tuple(torch.where(keep, res[k], torch.zeros_like(res[k])) for k in ("dz", "dl", "dv")) + (None,)
+
+
 class MpcSolveFunction(torch.autograd.Function):
     """apply(solver, sigma, *sequences in MPC_SEQ order) -> (z, l, v, out)."""
 
@@ -93,6 +120,10 @@ class MpcSolveFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gz, gl, gv, gout):
         return _backward(MPC_SEQ, ctx, gz, gl, gv, gout)
+
+    @staticmethod
+    def jvp(ctx, solver_t, sigma_t, *tangents):
+        return _jvp(MPC_SEQ, ctx, tangents)
 
 
 def solve_mpc(solver, data, sigma: float = 0.0):
@@ -112,6 +143,10 @@ class DenseSolveFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gz, gl, gv, gout):
         return _backward(DENSE_ARR, ctx, gz, gl, gv, gout)
+
+    @staticmethod
+    def jvp(ctx, solver_t, sigma_t, *tangents):
+        return _jvp(DENSE_ARR, ctx, tangents)
 
 
 def solve_dense(solver, data, sigma: float = 0.0):

@@ -24,6 +24,7 @@
 #include "fb_mpc.h"
 #include "fb_mpc_r16.h"
 #include "fb_record_kernel.h"
+#include "fb_tangent.h"
 
 #if defined(FB_ANY_STAMP)
 namespace fbk { __device__ unsigned long long g_stamps[32]; }
@@ -448,6 +449,63 @@ __global__ __launch_bounds__(64, kDwMinWaves) void fbstab_dense_wave_adjoint_ker
   }
 }
 
+// The direction kernels of fbstab_hip_*_tangent_batch (fb_tangent.h): the seeds (gz, gl, gv) of the tangent system
+// from the perturbations `dir` (base / stride per array as in the data blocks: a null base is a zero perturbation,
+// stride 0 one direction for the whole batch) and the points `x`.  No queue and no scratch: a workgroup's QP (and
+// stage) is its index, so the bits of a QP's seeds depend on its own inputs only.
+// MPC: one wavefront per (QP, stage), the stage's images in its LDS (MpcTangentLds).
+constexpr int kDenseTangentThreads = 256;
+__global__ __launch_bounds__(64) void fbstab_tangent_rhs_kernel(int N, int nx, int nu, int nc, MpcTangentLds o,
+                                                                MpcBatchArgs dir, VarBatchArgs x, VarBatchArgs seed) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  typedef Ctx<64> C;
+  C ctx;
+  ctx.tid = threadIdx.x;
+  ctx.red = (lds_ptr)smem;  // (unused)
+  const long q = blockIdx.x / (N + 1);
+  const int i = blockIdx.x % (N + 1);
+  auto at = [q](const double* b, long long s) { return b ? b + q * s : nullptr; };
+  MpcDir D;
+  D.Q = at(dir.base[FBSTAB_MPC_Q], dir.stride[FBSTAB_MPC_Q]);
+  D.R = at(dir.base[FBSTAB_MPC_R], dir.stride[FBSTAB_MPC_R]);
+  D.S = at(dir.base[FBSTAB_MPC_S], dir.stride[FBSTAB_MPC_S]);
+  D.q = at(dir.base[FBSTAB_MPC_q], dir.stride[FBSTAB_MPC_q]);
+  D.r = at(dir.base[FBSTAB_MPC_r], dir.stride[FBSTAB_MPC_r]);
+  D.A = at(dir.base[FBSTAB_MPC_A], dir.stride[FBSTAB_MPC_A]);
+  D.B = at(dir.base[FBSTAB_MPC_B], dir.stride[FBSTAB_MPC_B]);
+  D.c = at(dir.base[FBSTAB_MPC_c], dir.stride[FBSTAB_MPC_c]);
+  D.E = at(dir.base[FBSTAB_MPC_E], dir.stride[FBSTAB_MPC_E]);
+  D.L = at(dir.base[FBSTAB_MPC_L], dir.stride[FBSTAB_MPC_L]);
+  D.d = at(dir.base[FBSTAB_MPC_d], dir.stride[FBSTAB_MPC_d]);
+  D.x0 = at(dir.base[FBSTAB_MPC_x0], dir.stride[FBSTAB_MPC_x0]);
+  mpc_tangent_stage(ctx, N, nx, nu, nc, i, D, x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
+                    x.base[2] + q * x.stride[2], o, (lds_ptr)smem, seed.base[0] + q * seed.stride[0],
+                    seed.base[1] + q * seed.stride[1], seed.base[2] + q * seed.stride[2]);
+}
+
+// Dense: one workgroup per QP, walking the images in blocks of columns (DenseTangentLds).
+__global__ __launch_bounds__(kDenseTangentThreads) void fbstab_dense_tangent_rhs_kernel(
+    int nz, int nl, int nv, DenseTangentLds o, DenseBatchArgs dir, VarBatchArgs x, VarBatchArgs seed) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  typedef Ctx<kDenseTangentThreads> C;
+  C ctx;
+  ctx.tid = threadIdx.x;
+  ctx.red = (lds_ptr)smem;  // (unused)
+  const long q = blockIdx.x;
+  auto at = [q](const double* b, long long s) { return b ? b + q * s : nullptr; };
+  DenseDir D;
+  D.H = at(dir.base[FBSTAB_DENSE_H], dir.stride[FBSTAB_DENSE_H]);
+  D.f = at(dir.base[FBSTAB_DENSE_f], dir.stride[FBSTAB_DENSE_f]);
+  D.G = at(dir.base[FBSTAB_DENSE_G], dir.stride[FBSTAB_DENSE_G]);
+  D.h = at(dir.base[FBSTAB_DENSE_h], dir.stride[FBSTAB_DENSE_h]);
+  D.A = at(dir.base[FBSTAB_DENSE_A], dir.stride[FBSTAB_DENSE_A]);
+  D.b = at(dir.base[FBSTAB_DENSE_b], dir.stride[FBSTAB_DENSE_b]);
+  auto var = [q](double* b, long long s) { return b ? b + q * s : nullptr; };  // (nl == 0: the l slots are null)
+  dense_tangent(ctx, nz, nl, nv, D, x.base[0] + q * x.stride[0], var(x.base[1], x.stride[1]),
+                x.base[2] + q * x.stride[2], o, (lds_ptr)smem, seed.base[0] + q * seed.stride[0],
+                var(seed.base[1], seed.stride[1]), seed.base[2] + q * seed.stride[2]);
+}
+
 // ---------------------------------------------------------------------------
 thread_local std::string g_error;
 
@@ -499,11 +557,20 @@ struct SolverBase {
   // fbstab_hip_*_adjoint_batch_reduced (fb_grad_reduce.h), allocated by the first such call and held until destroy:
   // the adjoint steps of a caller who does not take them, max_batch x (nz + nl + nv) doubles, and the partial sums,
   // grad_reduce_scratch_doubles(plan, max_batch)
+  // (red_adj is also where fbstab_hip_*_tangent_batch keeps the seeds between its two launches: ensure_seeds)
   double* red_adj = nullptr;
   double* red_scratch = nullptr;
-  int ensure_reduce(const GradReducePlan& plan) {
+  // the direction kernel's LDS attribute is set (to the limit: the attribute belongs to the kernel, not to the
+  // handle, and handles of other shapes launch the same kernel)
+  bool tan_ready = false;
+  int ensure_seeds() {
     if (!red_adj)
       HIP_TRY(hipMalloc(&red_adj, sizeof(double) * (size_t)(var_len[0] + var_len[1] + var_len[2]) * max_batch));
+    return FBSTAB_HIP_OK;
+  }
+  int ensure_reduce(const GradReducePlan& plan) {
+    int rc = ensure_seeds();
+    if (rc != FBSTAB_HIP_OK) return rc;
     if (!red_scratch)
       HIP_TRY(hipMalloc(&red_scratch, sizeof(double) * (size_t)grad_reduce_scratch_doubles(plan, max_batch)));
     return FBSTAB_HIP_OK;
@@ -769,7 +836,8 @@ struct AdjointStage {
 
   // data, grad: base[] / stride[] of the caller's fbstab_*_batch_t and fbstab_*_grad_batch_t (h->arr_len.size()
   // slots).  With batch == 0 nothing is staged and the caller returns.  `reduced`: a gradient slot of stride 0 is
-  // ONE array, the sum over the batch (otherwise refused like every stride below the length).
+  // ONE array, the sum over the batch (otherwise refused like every stride below the length).  `seed` null: the
+  // seeds are the library's own, device arrays that the caller puts into `sd` behind this call (TangentStage).
   int open(SolverBase* h, int batch, const double* const* data_base, const long long* data_stride,
            const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double* const* grad_base,
            const long long* grad_stride, const fbstab_var_batch_t* adj, int* status, int flags, void* stream,
@@ -781,12 +849,12 @@ struct AdjointStage {
     for (int i = 0; i < 3; i++)
       if (!x->base[i] && vlen[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
     // (the dense entry point has refused this one already)
-    if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null seed pointer (z)");
+    if (seed && !seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null seed pointer (z)");
     // strides: every QP its own slot (a gradient or adjoint shared by the batch would be written by all of them)
     for (int i = 0; i < 3; i++) {
       int rc = h->check_var_stride(x->stride, i, batch);
       if (rc != FBSTAB_HIP_OK) return rc;
-      if (batch > 1 && seed->base[i] && seed->stride[i] < vlen[i])
+      if (batch > 1 && seed && seed->base[i] && seed->stride[i] < vlen[i])
         return fail(FBSTAB_HIP_ERR_ARGUMENT, "seed stride smaller than the vector length");
       if (batch > 1 && adj && adj->base[i] && adj->stride[i] < vlen[i])
         return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
@@ -809,11 +877,11 @@ struct AdjointStage {
     for (int i = 0; i < 3; i++) {
       if (vlen[i] == 0) continue;
       if (dev_ptrs) {
-        sd.base[i] = seed->base[i]; sd.stride[i] = seed->stride[i];
+        if (seed) { sd.base[i] = seed->base[i]; sd.stride[i] = seed->stride[i]; }
         if (adj) { ad.base[i] = adj->base[i]; ad.stride[i] = adj->stride[i]; }
         continue;
       }
-      if (seed->base[i]) {
+      if (seed && seed->base[i]) {
         HIP_TRY(hipMalloc(&d_seed[i].p, sizeof(double) * (size_t)vlen[i] * batch));
         sd.base[i] = static_cast<double*>(d_seed[i].p);
         rc = h->upload(seed->base[i], seed->stride[i] ? seed->stride[i] : vlen[i], vlen[i], batch, sd.base[i],
@@ -927,6 +995,101 @@ struct AdjointStage {
   const long long* grad_stride_ = nullptr;
   const fbstab_var_batch_t* adj_ = nullptr;
   int* status_ = nullptr;
+};
+
+// Host side of fbstab_hip_*_tangent_batch around the direction kernel's launch, beside the AdjointStage that serves
+// the adjoint launch behind it (opened with no seeds, no gradients and adj = dx): `check` validates the
+// perturbations and the result blocks, `open` stages the perturbations and says where the seeds live (st->sd),
+// `close` brings a host caller's rhs back (before AdjointStage::close, which waits for the stream).
+struct TangentStage {
+  static constexpr int kMaxArrays = AdjointStage::kMaxArrays;
+  const double* p_base[kMaxArrays];  // perturbations, kernel side (null: zero)
+  long long p_stride[kMaxArrays];
+
+  // no gradient is asked of the adjoint launch
+  static double* const* no_grads() {
+    static double* const none[kMaxArrays] = {};
+    return none;
+  }
+  static const long long* no_strides() {
+    static const long long none[kMaxArrays] = {};
+    return none;
+  }
+
+  // Before any device call.  dir: base[] / stride[] of the caller's perturbation block (null slots: zero; with
+  // batch > 1 a stride of 0 is one direction for all QPs, anything else below the length is refused); dx: every
+  // slot of a vector that is not empty; rhs: null, or the same.
+  static int check(const SolverBase* h, int batch, const double* const* dir_base, const long long* dir_stride,
+                   const fbstab_var_batch_t* dx, const fbstab_var_batch_t* rhs) {
+    const int n = (int)h->arr_len.size();
+    for (int i = 0; i < n; i++)
+      if (batch > 1 && dir_base[i] && dir_stride[i] != 0 && dir_stride[i] < h->arr_len[i])
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "perturbation stride is neither 0 nor at least the array length");
+    for (int i = 0; i < 3; i++) {
+      if (h->var_len[i] == 0) continue;
+      if (!dx->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null tangent pointer (dx)");
+      if (rhs && !rhs->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null right-hand side pointer (rhs)");
+      if (batch > 1 && rhs && rhs->stride[i] < h->var_len[i])
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "right-hand side stride smaller than the vector length");
+    }
+    return FBSTAB_HIP_OK;
+  }
+
+  // Behind AdjointStage::open (same stream).  The seeds go to the caller's rhs where that is device memory, and to
+  // the handle's buffer (SolverBase::ensure_seeds) otherwise.
+  int open(SolverBase* h, int batch, const double* const* dir_base, const long long* dir_stride,
+           const fbstab_var_batch_t* rhs, int flags, AdjointStage* st) {
+    h_ = h; batch_ = batch; rhs_ = rhs; st_ = st;
+    host_ = !(flags & FBSTAB_HIP_DEVICE_POINTERS);
+    const int n = (int)h->arr_len.size();
+    for (int i = 0; i < kMaxArrays; i++) { p_base[i] = nullptr; p_stride[i] = 0; }
+    for (int i = 0; i < n; i++) {
+      if (!dir_base[i] || h->arr_len[i] == 0) continue;
+      // (one QP: its direction is at the base, whatever the stride says)
+      const long long stride = batch > 1 ? dir_stride[i] : h->arr_len[i];
+      if (!host_) {
+        p_base[i] = dir_base[i]; p_stride[i] = stride;
+        continue;
+      }
+      HIP_TRY(hipMalloc(&d_dir[i].p, sizeof(double) * (size_t)h->arr_len[i] * (stride == 0 ? 1 : batch)));
+      int rc = h->upload(dir_base[i], stride, h->arr_len[i], batch, static_cast<double*>(d_dir[i].p), &p_stride[i],
+                         st->s);
+      if (rc != FBSTAB_HIP_OK) return rc;
+      p_base[i] = static_cast<double*>(d_dir[i].p);
+    }
+    const bool own = host_ || !rhs;
+    if (own) {
+      int rc = h->ensure_seeds();
+      if (rc != FBSTAB_HIP_OK) return rc;
+    }
+    double* buf = h->red_adj;
+    for (int i = 0; i < 3; i++) {
+      if (h->var_len[i] > 0) {
+        st->sd.base[i] = own ? buf : rhs->base[i];
+        st->sd.stride[i] = own ? h->var_len[i] : rhs->stride[i];
+      }
+      buf += h->var_len[i] * h->max_batch;
+    }
+    return FBSTAB_HIP_OK;
+  }
+
+  int close() {
+    if (!host_ || !rhs_) return FBSTAB_HIP_OK;
+    for (int i = 0; i < 3; i++) {
+      int rc = h_->download(rhs_->base[i], rhs_->stride[i] ? rhs_->stride[i] : h_->var_len[i], h_->var_len[i], batch_,
+                            st_->sd.base[i], st_->s);
+      if (rc != FBSTAB_HIP_OK) return rc;
+    }
+    return FBSTAB_HIP_OK;
+  }
+
+ private:
+  DevBuf d_dir[kMaxArrays];
+  SolverBase* h_ = nullptr;
+  AdjointStage* st_ = nullptr;
+  const fbstab_var_batch_t* rhs_ = nullptr;
+  int batch_ = 0;
+  bool host_ = false;
 };
 
 int check_common(const void* handle, int batch, const void* data, const fbstab_var_batch_t* x,
@@ -1422,24 +1585,11 @@ int fbstab_hip_mpc_debug_newton(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t*
 // (riccati_linear_solver.cc:77-210), one Solve (:212-344) with the adjoint's right-hand side, one contraction.
 // `reduced`: fbstab_hip_mpc_adjoint_batch_reduced - gradient slots of stride 0 are summed over the batch by the
 // kernels of fb_grad_reduce.h behind the adjoint's launch (`out`: the solve's records, or null).
-static int mpc_adjoint_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
-                            const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
-                            const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
-                            const fbstab_solver_out_t* out, int flags, void* stream, bool reduced) {
-  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  if (!seed || !grad) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
-  AdjointStage st;
-  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream,
-               reduced);
-  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
+// mpc_adjoint_launch is the launch alone, on the staged arguments of `st` (fbstab_hip_mpc_tangent_batch runs it
+// behind its direction kernel).
+static int mpc_adjoint_launch(fbstab_mpc_handle_t h, int batch, AdjointStage& st, double sigma) {
   hipStream_t s = st.s;
   const fbk::MpcLayout& L = h->lay;
-  const GradReducePlan plan = grad_reduce_plan_mpc(L.N, L.nx, L.nu, L.nc);
-  if (st.any_reduced) {
-    rc = st.open_reduce(plan);
-    if (rc != FBSTAB_HIP_OK) return rc;
-  }
   MpcBatchArgs a;
   MpcGradArgs g;
   for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
@@ -1510,6 +1660,28 @@ static int mpc_adjoint_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_b
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(h->ev1, s));
   h->timed = true;
+  return FBSTAB_HIP_OK;
+}
+
+static int mpc_adjoint_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                            const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                            const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
+                            const fbstab_solver_out_t* out, int flags, void* stream, bool reduced) {
+  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  if (!seed || !grad) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
+  AdjointStage st;
+  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream,
+               reduced);
+  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
+  const fbk::MpcLayout& L = h->lay;
+  const GradReducePlan plan = grad_reduce_plan_mpc(L.N, L.nx, L.nu, L.nc);
+  if (st.any_reduced) {
+    rc = st.open_reduce(plan);
+    if (rc != FBSTAB_HIP_OK) return rc;
+  }
+  rc = mpc_adjoint_launch(h, batch, st, sigma);
+  if (rc != FBSTAB_HIP_OK) return rc;
   if (st.any_reduced) {
     rc = st.reduce(plan, out);
     if (rc != FBSTAB_HIP_OK) return rc;
@@ -1529,6 +1701,50 @@ int fbstab_hip_mpc_adjoint_batch_reduced(fbstab_mpc_handle_t h, int batch, const
                                          const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj,
                                          int* status, const fbstab_solver_out_t* out, int flags, void* stream) {
   return mpc_adjoint_impl(h, batch, data, x, seed, sigma, grad, adj, status, out, flags, stream, true);
+}
+
+// Forward-mode derivative of the solution map (include/fbstab_hip.h): fbstab_tangent_rhs_kernel forms the seeds
+// (gz, gl, gv) from the perturbations and the points, and the adjoint's launch, unchanged, solves
+// V (dz, dl, dv) = (gz, -gl, -C gv) for them on the same stream - no gradient slot, adj = dx.
+int fbstab_hip_mpc_tangent_batch(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                 const fbstab_var_batch_t* x, const fbstab_mpc_batch_t* ddata, double sigma,
+                                 const fbstab_var_batch_t* dx, const fbstab_var_batch_t* rhs, int* status, int flags,
+                                 void* stream) {
+  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  if (!ddata || !dx) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
+  rc = TangentStage::check(h, batch, ddata->base, ddata->stride, dx, rhs);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  const fbk::MpcLayout& L = h->lay;
+  MpcTangentLds o;
+  o.init(L.nx, L.nu, L.nc);
+  const int lds = o.total * (int)sizeof(double);
+  if (lds > kLdsLimitBytes)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "the perturbation images of one stage do not fit the LDS");
+  if ((long long)batch * (L.N + 1) > 0x7fffffffLL)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "batch x stages exceeds the grid limit");
+  AdjointStage st;
+  rc = st.open(h, batch, data->base, data->stride, x, nullptr, TangentStage::no_grads(), TangentStage::no_strides(), dx,
+               status, flags, stream);
+  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
+  TangentStage ts;
+  rc = ts.open(h, batch, ddata->base, ddata->stride, rhs, flags, &st);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  MpcBatchArgs dir;
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { dir.base[i] = ts.p_base[i]; dir.stride[i] = ts.p_stride[i]; }
+  if (!h->tan_ready) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fbstab_tangent_rhs_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
+    h->tan_ready = true;
+  }
+  hipLaunchKernelGGL(fbstab_tangent_rhs_kernel, dim3(batch * (L.N + 1)), dim3(64), (size_t)lds, st.s, L.N, L.nx, L.nu,
+                     L.nc, o, dir, st.v, st.sd);
+  HIP_TRY(hipGetLastError());
+  rc = mpc_adjoint_launch(h, batch, st, sigma);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = ts.close();
+  if (rc != FBSTAB_HIP_OK) return rc;
+  return st.close();
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;
@@ -1868,38 +2084,10 @@ int fbstab_hip_dense_debug_newton(fbstab_dense_handle_t h, const fbstab_dense_ba
 // x = xbar = the point (dense_cholesky_solver.cc:32-79), one Solve (:81-127) with the adjoint's right-hand side,
 // one contraction.
 // `reduced`: fbstab_hip_dense_adjoint_batch_reduced, as mpc_adjoint_impl.
-static int dense_adjoint_impl(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
-                              const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
-                              const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
-                              const fbstab_solver_out_t* out, int flags, void* stream, bool reduced) {
-  // what needs no handle comes first: the argument blocks, the one seed that is required, and strides that no
-  // handle accepts (nz and nv are positive: z, v, H, f, A, b are never empty)
-  if (!data || !x || !seed || !grad || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
-  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null seed pointer (z)");
-  if (batch > 1) {
-    for (int i = 0; i < 3; i += 2) {
-      if (x->stride[i] < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
-      if (seed->base[i] && seed->stride[i] < 1)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "seed stride smaller than the vector length");
-      if (adj && adj->base[i] && adj->stride[i] < 1)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
-    }
-    for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b})
-      if (grad->base[i] && grad->stride[i] < 1 && !(reduced && grad->stride[i] == 0))
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
-  }
-  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  AdjointStage st;
-  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream,
-               reduced);
-  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
+// dense_adjoint_launch is the launch alone, on the staged arguments of `st` (fbstab_hip_dense_tangent_batch runs it
+// behind its direction kernel).
+static int dense_adjoint_launch(fbstab_dense_handle_t h, int batch, AdjointStage& st, double sigma) {
   hipStream_t s = st.s;
-  const GradReducePlan plan = grad_reduce_plan_dense((int)h->var_len[0], (int)h->var_len[1], (int)h->var_len[2]);
-  if (st.any_reduced) {
-    rc = st.open_reduce(plan);
-    if (rc != FBSTAB_HIP_OK) return rc;
-  }
   DenseBatchArgs a;
   DenseGradArgs g;
   for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
@@ -1940,6 +2128,42 @@ static int dense_adjoint_impl(fbstab_dense_handle_t h, int batch, const fbstab_d
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(h->ev1, s));
   h->timed = true;
+  return FBSTAB_HIP_OK;
+}
+
+static int dense_adjoint_impl(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
+                              const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                              const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj, int* status,
+                              const fbstab_solver_out_t* out, int flags, void* stream, bool reduced) {
+  // what needs no handle comes first: the argument blocks, the one seed that is required, and strides that no
+  // handle accepts (nz and nv are positive: z, v, H, f, A, b are never empty)
+  if (!data || !x || !seed || !grad || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
+  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null seed pointer (z)");
+  if (batch > 1) {
+    for (int i = 0; i < 3; i += 2) {
+      if (x->stride[i] < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
+      if (seed->base[i] && seed->stride[i] < 1)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "seed stride smaller than the vector length");
+      if (adj && adj->base[i] && adj->stride[i] < 1)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
+    }
+    for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b})
+      if (grad->base[i] && grad->stride[i] < 1 && !(reduced && grad->stride[i] == 0))
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
+  }
+  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  AdjointStage st;
+  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream,
+               reduced);
+  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
+  const GradReducePlan plan = grad_reduce_plan_dense((int)h->var_len[0], (int)h->var_len[1], (int)h->var_len[2]);
+  if (st.any_reduced) {
+    rc = st.open_reduce(plan);
+    if (rc != FBSTAB_HIP_OK) return rc;
+  }
+  rc = dense_adjoint_launch(h, batch, st, sigma);
+  if (rc != FBSTAB_HIP_OK) return rc;
   if (st.any_reduced) {
     rc = st.reduce(plan, out);
     if (rc != FBSTAB_HIP_OK) return rc;
@@ -1959,6 +2183,57 @@ int fbstab_hip_dense_adjoint_batch_reduced(fbstab_dense_handle_t h, int batch, c
                                            const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj,
                                            int* status, const fbstab_solver_out_t* out, int flags, void* stream) {
   return dense_adjoint_impl(h, batch, data, x, seed, sigma, grad, adj, status, out, flags, stream, true);
+}
+
+// Forward-mode derivative of the dense solution map (include/fbstab_hip.h): as fbstab_hip_mpc_tangent_batch, with
+// fbstab_dense_tangent_rhs_kernel and the dense adjoint's launch.  What needs no handle is checked first, as there.
+int fbstab_hip_dense_tangent_batch(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
+                                   const fbstab_var_batch_t* x, const fbstab_dense_batch_t* ddata, double sigma,
+                                   const fbstab_var_batch_t* dx, const fbstab_var_batch_t* rhs, int* status,
+                                   int flags, void* stream) {
+  if (!data || !x || !ddata || !dx || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
+  if (batch > 1) {
+    for (int i = 0; i < 3; i += 2) {
+      if (x->stride[i] < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "variable stride smaller than the vector length");
+      if (dx->base[i] && dx->stride[i] < 1)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
+    }
+    for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b})
+      if (ddata->base[i] && ddata->stride[i] < 0)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "perturbation stride is neither 0 nor at least the array length");
+  }
+  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = TangentStage::check(h, batch, ddata->base, ddata->stride, dx, rhs);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  const int nz = (int)h->var_len[0], nl = (int)h->var_len[1], nv = (int)h->var_len[2];
+  DenseTangentLds o;
+  // (64 KB needs no attribute and leaves room for two workgroups per CU; shapes with more rows take what there is)
+  if (!o.init(nz, nl, nv, 64 * 1024 / (int)sizeof(double)) && !o.init(nz, nl, nv, kLdsLimitBytes / (int)sizeof(double)))
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "not one column of the perturbation images fits the LDS");
+  const int lds = o.total * (int)sizeof(double);
+  AdjointStage st;
+  rc = st.open(h, batch, data->base, data->stride, x, nullptr, TangentStage::no_grads(), TangentStage::no_strides(), dx,
+               status, flags, stream);
+  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
+  TangentStage ts;
+  rc = ts.open(h, batch, ddata->base, ddata->stride, rhs, flags, &st);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  DenseBatchArgs dir;
+  for (int i = 0; i < FBSTAB_DENSE_NARR; i++) { dir.base[i] = ts.p_base[i]; dir.stride[i] = ts.p_stride[i]; }
+  if (!h->tan_ready) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fbstab_dense_tangent_rhs_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
+    h->tan_ready = true;
+  }
+  hipLaunchKernelGGL(fbstab_dense_tangent_rhs_kernel, dim3(batch), dim3(kDenseTangentThreads), (size_t)lds, st.s, nz, nl,
+                     nv, o, dir, st.v, st.sd);
+  HIP_TRY(hipGetLastError());
+  rc = dense_adjoint_launch(h, batch, st, sigma);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = ts.close();
+  if (rc != FBSTAB_HIP_OK) return rc;
+  return st.close();
 }
 
 double fbstab_hip_dense_last_kernel_ms(fbstab_dense_handle_t h) { return h ? h->last_kernel_ms() : -1.0; }

@@ -171,6 +171,11 @@ def load_library() -> C.CDLL:
             getattr(lib, f"fbstab_hip_{kind}_adjoint_batch_reduced").argtypes = [
                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    for kind in ("mpc", "dense"):  # (absent from a build of an earlier round loaded for an A/B)
+        if hasattr(lib, f"fbstab_hip_{kind}_tangent_batch"):
+            getattr(lib, f"fbstab_hip_{kind}_tangent_batch").argtypes = [
+                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                C.c_void_p, C.c_int, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -201,11 +206,11 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_last_kernel_ms", "fbstab_hip_mpc_query", "fbstab_hip_mpc_kernel_name",
     "fbstab_hip_mpc_refined_steps", "fbstab_hip_mpc_create_in_flight",
     "fbstab_hip_mpc_debug_newton", "fbstab_hip_mpc_adjoint_batch", "fbstab_hip_mpc_adjoint_kernel_name",
-    "fbstab_hip_mpc_adjoint_batch_reduced", "fbstab_hip_debug_stamps",
+    "fbstab_hip_mpc_adjoint_batch_reduced", "fbstab_hip_mpc_tangent_batch", "fbstab_hip_debug_stamps",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",
     "fbstab_hip_dense_solve_traced", "fbstab_hip_dense_adjoint_batch",
-    "fbstab_hip_dense_adjoint_batch_reduced",
+    "fbstab_hip_dense_adjoint_batch_reduced", "fbstab_hip_dense_tangent_batch",
     "fbstab_hip_dense_debug_newton", "fbstab_hip_dense_last_kernel_ms", "fbstab_hip_dense_query",
     "fbstab_hip_dense_set_factorisation", "fbstab_hip_dense_get_factorisation",
     "fbstab_hip_shard_group_create", "fbstab_hip_shard_group_destroy", "fbstab_hip_shard_group_stats",
@@ -429,6 +434,68 @@ class _SolverBase:
         return res
 
 
+def _tangent(self, batch_struct, dir_struct, names, lens, data, z, l, v, ddata, sigma, rhs, stream, async_):
+    """fbstab_hip_*_tangent_batch behind ``Tangent``; an array of length 0, an absent name and None are NULL
+    slots of ``ddata``, a ``(1, len)`` direction beside B > 1 QPs has stride 0."""
+    unknown = set(ddata) - set(names)
+    assert not unknown, unknown
+    dev_flags = []
+    B = z.shape[0]
+    for i, (k, n) in enumerate(zip(names, lens)):
+        batch_struct.base[i], batch_struct.stride[i] = None, 0
+        dir_struct.base[i], dir_struct.stride[i] = None, 0
+        if n == 0:
+            continue
+        p, st, d = _ptr_stride(data[k], n)
+        batch_struct.base[i], batch_struct.stride[i] = p, _shared_stride(data[k], st, B)
+        dev_flags.append(d)
+        if ddata.get(k) is not None:
+            p, st, d = _ptr_stride(ddata[k], n)
+            dir_struct.base[i], dir_struct.stride[i] = p, _shared_stride(ddata[k], st, B)
+            dev_flags.append(d)
+    var_lens = (self.nz, self.nl, self.nv)
+
+    def var(arrs):
+        vb = _VarBatch()
+        for i, (a, n) in enumerate(zip(arrs, var_lens)):
+            vb.base[i], vb.stride[i] = None, 0
+            if n == 0:
+                continue
+            p, st, d = _ptr_stride(a, n)
+            assert a.shape[0] == B
+            vb.base[i], vb.stride[i] = p, st
+            dev_flags.append(d)
+        return vb
+
+    xb = var((z, l, v))
+    on_dev = all(dev_flags)
+    assert on_dev or not any(dev_flags), "mix of host and device arrays"
+    if on_dev:
+        import torch
+        zeros = lambda n: torch.zeros((B, n), dtype=torch.float64, device=z.device)
+        if not stream:
+            stream = torch.cuda.current_stream(z.device).cuda_stream
+        flags = DEVICE_POINTERS | (ASYNC if async_ else 0)
+        status = torch.zeros(B, dtype=torch.int32, device=z.device)
+    else:
+        zeros = lambda n: np.zeros((max(B, 1), n))[:B]   # (an empty batch keeps the strides of a row)
+        flags = HOST_POINTERS
+        status = np.zeros(B, dtype=np.int32)
+    res = {k: zeros(n) for k, n in zip(("dz", "dl", "dv"), var_lens)}
+    db = var((res["dz"], res["dl"], res["dv"]))
+    rb = None
+    if rhs:
+        res.update({k: zeros(n) for k, n in zip(("gz", "gl", "gv"), var_lens)})
+        rb = var((res["gz"], res["gl"], res["gv"]))
+    fn = getattr(self._lib, f"fbstab_hip_{self._kind}_tangent_batch")
+    _check(self._lib, fn(self._h, B, C.byref(batch_struct), C.byref(xb), C.byref(dir_struct), C.c_double(sigma),
+                         C.byref(db), C.byref(rb) if rb is not None else None,
+                         C.c_void_p(status.data_ptr() if on_dev else status.ctypes.data), flags,
+                         C.c_void_p(stream) if stream else None))
+    res["status"] = status
+    return res
+
+
 def _solve_traced(self, batch_struct, names, lens, arrays, var_lens, z, l, v, y, capacity):
     """fbstab_hip_*_solve_traced for ONE QP in (1, n) numpy arrays.  Returns
     ``(out, records)``; records is ``(n, 8)``: kind, i0, i1, v0..v4
@@ -630,6 +697,18 @@ class FBstabMpcBatch(_SolverBase):
         return self._adjoint(self._lib.fbstab_hip_mpc_adjoint_batch, _MpcBatch(), _MpcGradBatch(), MPC_SEQ,
                              self.seq_len, data, z, l, v, gz, gl, gv, sigma, want, adj, stream, async_, reduce, out)
 
+    def Tangent(self, data: Dict[str, object], z, l, v, ddata: Dict[str, object], sigma: float = 0.0,
+                rhs: bool = False, stream: int = 0, async_: bool = False) -> Dict[str, object]:
+        """Forward-mode derivative of the solution map (fbstab_hip_mpc_tangent_batch): the first-order change
+        ``dz, dl, dv`` (``(batch, n)``) of the solutions at the returned point ``(z, l, v)`` for the perturbation
+        ``ddata`` of the problem data: a dict name -> ``(batch, len)`` direction, or ``(1, len)`` for one direction
+        shared by the batch; absent names and None are zero perturbations.  dQ and dR enter through their symmetric
+        part.  All numpy or all torch CUDA tensors, like ``Adjoint``.  Returns a dict with ``"dz", "dl", "dv"``,
+        ``"status"`` (``(batch,)`` int32: 1 where the factorisation failed and the tangent is zero) and, with
+        ``rhs=True``, the seeds ``"gz", "gl", "gv"`` of the tangent system.  ``sigma <= 0``: 1e-8."""
+        return _tangent(self, _MpcBatch(), _MpcBatch(), MPC_SEQ, self.seq_len, data, z, l, v, ddata, sigma, rhs,
+                        stream, async_)
+
 
 class FBstabDenseBatch(_SolverBase):
     """Batched counterpart of ``fbstab::FBstabDense`` (fbstab/fbstab_dense.h:50-194)."""
@@ -723,6 +802,14 @@ class FBstabDenseBatch(_SolverBase):
         ``(1, len)`` inputs: as FBstabMpcBatch.Adjoint (fbstab_hip_dense_adjoint_batch_reduced)."""
         return self._adjoint(self._lib.fbstab_hip_dense_adjoint_batch, _DenseBatch(), _DenseGradBatch(), DENSE_ARR,
                              self.arr_len, data, z, l, v, gz, gl, gv, sigma, want, adj, stream, async_, reduce, out)
+
+    def Tangent(self, data: Dict[str, object], z, l, v, ddata: Dict[str, object], sigma: float = 0.0,
+                rhs: bool = False, stream: int = 0, async_: bool = False) -> Dict[str, object]:
+        """Forward-mode derivative of the dense solution map (fbstab_hip_dense_tangent_batch): as
+        FBstabMpcBatch.Tangent, ``ddata`` naming directions of H, f, G, h, A, b (the matrices column-major like the
+        inputs, dH through its symmetric part).  With ``nl == 0`` the G, h and l arrays are ``(batch, 0)``."""
+        return _tangent(self, _DenseBatch(), _DenseBatch(), DENSE_ARR, self.arr_len, data, z, l, v, ddata, sigma,
+                        rhs, stream, async_)
 
 
 class ShardGroup:

@@ -356,6 +356,44 @@ int fbstab_hip_mpc_adjoint_batch_reduced(fbstab_mpc_handle_t handle, int batch, 
                                          const fbstab_var_batch_t* adj, int* status,
                                          const fbstab_solver_out_t* out, int flags, void* stream);
 
+/* Forward mode of the same derivative: the tangent (dz, dl, dv) = J dtheta of the solutions for a perturbation
+ * dtheta of the problem data - the first-order update of a plan when the state or a forecast moves (a warm start
+ * for the next solve), a column of the feedback gain du0/dx0 per unit direction dx0, a disturbance direction
+ * through the controller.  At a returned point with xbar = x the matrix V above is the Jacobian of the inner
+ * residual F, and the tangent system is
+ *   V (dz, dl, dv) = -dF/dtheta dtheta = (gz, -gl, -C gv),
+ *   gz = -(dH z + df + dG' l + dA' v)      gl = dh - dG z      gv = db - dA z
+ * with dH the symmetric part of the perturbation: exactly the adjoint's system for the seeds (gz, gl, gv).  In
+ * MPC terms (the constant -I blocks of G have no perturbation), stage by stage,
+ *   gz[x_i u_i] = -( sym[dQ_i dS_i'; dS_i dR_i] (x_i, u_i) + (dq_i, dr_i) + d[A_i B_i]' l_(i+1) + d[E_i L_i]' v_i )
+ *   gl[l_0] = -dx0     gl[l_(i+1)] = -dc_i - d[A_i B_i] (x_i, u_i)     gv[v_i] = -dd_i - d[E_i L_i] (x_i, u_i)
+ * (stage N has no [A B] term).  Two launches on one stream: fbstab_tangent_rhs_kernel (fb_tangent.h: one
+ * wavefront per QP and stage; every perturbation image is read once, no atomics, every sum in an order fixed by
+ * the shape, so a QP's seeds do not depend on the batch or the grid) writes the seeds, and the launch of
+ * fbstab_hip_mpc_adjoint_batch - the same kernel selection, no gradient slot, adj = dx - solves for them.  dQ and
+ * dR enter through their symmetric part (dQ + dQ')/2, the part the adjoint returns the gradient of, so that
+ * <seed, J dtheta> = sum_k <grad_k, dtheta_k> for any direction; dS enters as dS x on the u rows and dS' u on
+ * the x rows.
+ *   x:      the points, (z, l, v) (the y slot is not read).
+ *   ddata:  the perturbations, one slot per sequence in the layout of `data`.  A NULL slot is a zero
+ *           perturbation (not read, not multiplied); stride 0 is one direction shared by the batch; stride >=
+ *           length is a direction per QP.  With batch > 1 any other stride is FBSTAB_HIP_ERR_ARGUMENT.
+ *   dx:     receives (dz, dl, dv); the y slot is unused.  Every QP needs its own slot, as for adj.
+ *   rhs:    NULL, or receives the seeds (gz, gl, gv) (all three slots, strides as for dx).  On a device-pointer
+ *           call the direction kernel writes them into the caller's arrays and the adjoint reads them there.
+ *   status: as fbstab_hip_mpc_adjoint_batch: 1 where a factorisation failed; that QP's dx is zero.
+ * sigma, flags, streams, host staging, batch == 0 and validation are those of fbstab_hip_mpc_adjoint_batch;
+ * fbstab_hip_mpc_last_kernel_ms reports the adjoint kernel's launch, as there; a FBSTAB_HIP_KEEP_MATRICES solve
+ * behind it rebuilds its copies as behind an adjoint call.  Memory: without a device rhs the seeds live in a
+ * buffer of the handle, max_batch x (nz + nl + nv) doubles, allocated by the first call that needs it and held
+ * until destroy - the SAME allocation as the adjoint steps of fbstab_hip_mpc_adjoint_batch_reduced (neither call
+ * needs it once it has returned), not counted by fbstab_hip_mpc_query.  A shape whose stage images (nx + nu +
+ * nc) x (nx + nu) + nx x (nx + nu) doubles exceed 160 KB of LDS is FBSTAB_HIP_ERR_UNSUPPORTED. */
+int fbstab_hip_mpc_tangent_batch(fbstab_mpc_handle_t handle, int batch, const fbstab_mpc_batch_t* data,
+                                 const fbstab_var_batch_t* x, const fbstab_mpc_batch_t* ddata, double sigma,
+                                 const fbstab_var_batch_t* dx, const fbstab_var_batch_t* rhs,
+                                 int* status, int flags, void* stream);
+
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);
 
@@ -523,6 +561,20 @@ int fbstab_hip_dense_adjoint_batch_reduced(fbstab_dense_handle_t handle, int bat
                                            const fbstab_var_batch_t* seed, double sigma,
                                            const fbstab_dense_grad_batch_t* grad, const fbstab_var_batch_t* adj,
                                            int* status, const fbstab_solver_out_t* out, int flags, void* stream);
+/* fbstab_hip_mpc_tangent_batch for the dense QP: (dz, dl, dv) = J dtheta for perturbations (dH, df, dG, dh, dA,
+ * db) in the layout of fbstab_dense_batch_t, from V (dz, dl, dv) = (gz, -gl, -C gv) with
+ *   gz = -(sym(dH) z + df + dG' l + dA' v)      gl = dh - dG z      gv = db - dA z
+ * (h and b enter the dense data directly).  fbstab_dense_tangent_rhs_kernel (fb_tangent.h: one workgroup per QP,
+ * the images walked once in blocks of columns, row and column sums from the same block in LDS; no atomics, sums
+ * in an order fixed by the shape) writes the seeds, the launch of fbstab_hip_dense_adjoint_batch solves for them.
+ * ddata, dx, rhs, status, sigma, flags, streams, host staging, batch == 0, the seed buffer (the allocation of
+ * fbstab_hip_dense_adjoint_batch_reduced's adjoint steps) and fbstab_hip_dense_last_kernel_ms: as there;
+ * validation as fbstab_hip_dense_adjoint_batch (what needs no handle first).  Handles with nl == 0 ignore the G
+ * and h slots and the l slots of x, dx and rhs. */
+int fbstab_hip_dense_tangent_batch(fbstab_dense_handle_t handle, int batch, const fbstab_dense_batch_t* data,
+                                   const fbstab_var_batch_t* x, const fbstab_dense_batch_t* ddata, double sigma,
+                                   const fbstab_var_batch_t* dx, const fbstab_var_batch_t* rhs,
+                                   int* status, int flags, void* stream);
 double fbstab_hip_dense_last_kernel_ms(fbstab_dense_handle_t handle);
 int fbstab_hip_dense_query(fbstab_dense_handle_t handle, long long* scratch_bytes,
                            int* lds_bytes, int* workgroups, int* threads);

@@ -7,6 +7,7 @@ usage: python tools/adjoint_bench.py [--batch 8192] [--reps 5] [--generic]
        python tools/adjoint_bench.py --dense [--batch 4096] [--reps 5]
        python tools/adjoint_bench.py --wide [--reps 5]
        python tools/adjoint_bench.py --reduced [--reps 5]
+       python tools/adjoint_bench.py --tangent [--dense] [--reps 5]
 --generic: FBSTAB_HIP_GENERIC=1, forward and adjoint on the flat-vector kernels (default: the record instance
 <12,4,20> and its own adjoint).
 --dense: fbstab_hip_dense_adjoint_batch against fbstab_hip_dense_solve_batch on BASELINE configs[1] instead: 4096
@@ -22,7 +23,17 @@ torch.sum(dim=0) of every matrix gradient, against ONE fbstab_hip_*_adjoint_batc
 reduced.  Times are torch events around the whole backward on torch's current stream (allocation of the outputs
 included, as a caller pays it), the median of --reps launches; the two ways alternate, each in a fresh process.  One
 JSON line (profiles/reduced_adjoint_bench.json) with the library's sha256; `not_slower` says whether the reduced call
-is within the spread of the launches of the per-QP way."""
+is within the spread of the launches of the per-QP way.
+--tangent: the forward mode against the reverse mode it mirrors, on BASELINE configs[2] (8192 QPs) or, with --dense,
+configs[1] (4096 dense QPs), each way in a fresh process, the median of --reps launches:
+  (a) fbstab_hip_*_adjoint_batch with all per-QP gradient slots wanted: the adjoint kernel's launch
+      (last_kernel_ms), and the whole call between torch events (the allocation of the gradients included);
+  (b) fbstab_hip_*_tangent_batch with per-QP perturbations of all arrays: the whole call between torch events
+      (direction kernel, queue reset and adjoint kernel; the three result vectors are allocated inside);
+  (c) the direction kernel alone: (b)'s call minus its adjoint kernel's launch - an upper bound, the queue reset
+      and the launch gaps are in it - and the bytes it reads and writes over that time.
+`not_slower`: (b) <= (a)'s kernel + the spread of (a)'s launches.  One JSON line (profiles/tangent_bench.json) with
+the library's sha256."""
 import argparse
 import hashlib
 import json
@@ -252,6 +263,104 @@ def reduced(reps):
     print(json.dumps(res))
 
 
+TANGENT_WAYS = ("adjoint_all_slots", "tangent_all_slots")
+
+
+def tangent_child(way, dense_, reps):
+    """One way in this process: solve once, then reps + 1 calls (the first warms up)."""
+    import torch
+    from tools import fixtures as fx
+    from fbstab_amd import hip_api
+    dev = torch.device("cuda:0")
+    if dense_:
+        B = 4096
+        p = fx.synthetic_dense_batch(B, 50, 10, 100)
+        s = hip_api.FBstabDenseBatch(50, 10, 100, max_batch=B)
+        lens = s.arr_len
+    else:
+        B = 8192
+        p = fx.synthetic_mpc_batch(B)
+        s = hip_api.FBstabMpcBatch(*p.sizes(), max_batch=B)
+        lens = s.seq_len
+    data = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in p.arrays.items()}
+    zeros = lambda n: torch.zeros((B, n), dtype=torch.float64, device=dev)
+    z, l, v, y = zeros(p.nz), zeros(p.nl), zeros(p.nv), zeros(p.nv)
+    out = s.Solve(data, z, l, v, y)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    rand = lambda n: torch.randn((B, n), dtype=torch.float64, device=dev, generator=gen)
+    seeds = [rand(n) for n in (p.nz, p.nl, p.nv)]
+    dirs = {k: rand(a.shape[1]) for k, a in data.items()} if way == "tangent_all_slots" else None
+    torch.cuda.synchronize()
+    ms, kernel_ms = [], []
+    for _ in range(reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if way == "tangent_all_slots":
+            g = s.Tangent(data, z, l, v, dirs)
+            check = g["dz"]
+        else:
+            g = s.Adjoint(data, z, l, v, *seeds, adj=True)
+            check = g["dz"]
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+        kernel_ms.append(s.last_kernel_ms())
+        status_nonzero = int((g["status"] != 0).sum().item())
+        check = float(check.abs().sum().item())
+        del g
+    ms, kernel_ms = ms[1:], kernel_ms[1:]
+    # what the direction kernel moves: every image once, the point, and the seeds it writes
+    image_bytes = 8 * sum(lens) * B
+    print(json.dumps({"way": way, "batch": B, "call_ms": round(float(np.median(ms)), 3),
+                      "call_ms_all": [round(t, 3) for t in ms], "adjoint_kernel_ms": round(float(np.median(kernel_ms)), 3),
+                      "adjoint_kernel_ms_all": [round(t, 3) for t in kernel_ms],
+                      "adjoint_kernel": s.adjoint_kernel_name() if not dense_ else "dense",
+                      "image_bytes_per_qp": 8 * sum(lens), "image_bytes": image_bytes,
+                      "vector_bytes": 8 * 2 * (p.nz + p.nl + p.nv) * B, "abs_sum_dz": check,
+                      "status_nonzero": status_nonzero,
+                      "success": int((hip_api.out_to_numpy(out)["eflag"] == 0).sum())}))
+
+
+def tangent(dense_, reps):
+    from fbstab_amd import hip_api
+    hip_api.load_library()
+    with open(hip_api.current_library_path(), "rb") as f:
+        sha = hashlib.sha256(f.read()).hexdigest()
+    runs = {}
+    for way in TANGENT_WAYS:
+        # every child under a time limit of its own; after one that failed, faulted or ran out of time no further
+        # child is started on the GPU
+        cmd = [sys.executable, os.path.abspath(__file__), "--tangent-child", way, "--reps", str(reps)]
+        try:
+            r = subprocess.run(cmd + (["--dense"] if dense_ else []), capture_output=True, text=True, timeout=CHILD_SECONDS)
+        except subprocess.TimeoutExpired as e:
+            sys.stderr.write(str(e.stdout or "")[-2000:] + str(e.stderr or "")[-4000:])
+            raise SystemExit("adjoint_bench --tangent: %s did not end within %d s; stopping" % (way, CHILD_SECONDS))
+        if r.returncode != 0:
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+            raise SystemExit("adjoint_bench --tangent: %s ended with status %d; stopping" % (way, r.returncode))
+        runs[way] = json.loads(r.stdout.strip().splitlines()[-1])
+    a, b = runs["adjoint_all_slots"], runs["tangent_all_slots"]
+    spread = max(a["adjoint_kernel_ms_all"]) - min(a["adjoint_kernel_ms_all"])
+    direction_ms = b["call_ms"] - b["adjoint_kernel_ms"]
+    moved = b["image_bytes"] + b["vector_bytes"]
+    print(json.dumps({
+        "library_sha256": sha, "launches_timed": reps,
+        "workload": "BASELINE configs[1]" if dense_ else "BASELINE configs[2]", "batch": a["batch"],
+        "adjoint_kernel": a["adjoint_kernel"],
+        "a_adjoint_all_slots_kernel_ms": a["adjoint_kernel_ms"], "a_kernel_ms_all": a["adjoint_kernel_ms_all"],
+        "a_call_ms": a["call_ms"], "a_call_ms_all": a["call_ms_all"],
+        "b_tangent_call_ms": b["call_ms"], "b_call_ms_all": b["call_ms_all"],
+        "b_adjoint_kernel_ms": b["adjoint_kernel_ms"],
+        "c_direction_ms_upper_bound": round(direction_ms, 3), "c_bytes": moved,
+        "c_tb_per_s_lower_bound": round(moved / (direction_ms * 1e-3) / 1e12, 3) if direction_ms > 0 else None,
+        "image_bytes_per_qp": b["image_bytes_per_qp"],
+        "spread_of_a_ms": round(spread, 3), "b_over_a": round(b["call_ms"] / a["adjoint_kernel_ms"], 4),
+        "not_slower": b["call_ms"] <= a["adjoint_kernel_ms"] + spread,
+        "status_nonzero": [a["status_nonzero"], b["status_nonzero"]], "abs_sum_dz": [a["abs_sum_dz"], b["abs_sum_dz"]],
+        "success": a["success"]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=None)
@@ -262,7 +371,13 @@ def main():
     ap.add_argument("--wide-child", choices=WIDE, help=argparse.SUPPRESS)
     ap.add_argument("--reduced", action="store_true")
     ap.add_argument("--reduced-child", nargs=2, help=argparse.SUPPRESS)
+    ap.add_argument("--tangent", action="store_true")
+    ap.add_argument("--tangent-child", choices=TANGENT_WAYS, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.tangent_child:
+        return tangent_child(a.tangent_child, a.dense, a.reps)
+    if a.tangent:
+        return tangent(a.dense, a.reps)
     if a.reduced_child:
         return reduced_child(a.reduced_child[0], a.reduced_child[1], a.reps)
     if a.reduced:
