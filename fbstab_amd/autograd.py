@@ -34,12 +34,28 @@ Forward mode (``torch.autograd.forward_ad``): inside a ``dual_level``, inputs ma
 the tangents that are present (a shared input's tangent travels with batch stride 0 like the input).  As in the
 backward, a QP whose solve did not end in SUCCESS, or whose factorisation failed, gets ZERO tangents.
 (``torch.func.jvp`` is not served: it needs a ``setup_context`` style function.)
+
+The closed loop (the receding-horizon sweep, x_(k+1) = A x_k + B u0(x_k; theta)) is differentiable as a whole:
+
+    u, x, out = closed_loop_mpc(solver, data, A, B, steps)   # u (steps, B, nu); x (steps, B, nx): x_1 .. x_steps
+    loss(u, x).backward()                                    # data[k].grad, A.grad, B.grad
+
+Forward: ONE logged sweep (fbstab_hip_mpc_receding_sweep_logged) on a clone of ``data["x0"]`` from a zero guess.
+Backward: ONE call of fbstab_hip_mpc_receding_sweep_adjoint, which takes the costate backwards through the logged
+steps and computes only the gradients torch asks for; ``data["x0"].grad`` is dL/dx_0 of every trajectory, and the
+plant's ``A.grad``, ``B.grad`` (``(nx, nx)`` / ``(nx, nu)`` torch tensors, row-major, shared by the trajectories)
+are formed from the logged costates.  A step whose solve did not end in SUCCESS passes the costate through the
+plant alone, and a retired trajectory (``retire=True``) is cut at its retirement step, as the sweep cuts it.  A
+shared input gets the sum of the per-trajectory gradients, formed in torch.  Not served: the batch-summed
+(reduced) path inside the library, forward mode through the sweep, and losses of anything but ``u`` and ``x`` (the
+rest of z_k, l_k, v_k).
 """
 import torch
 
 from .hip_api import DENSE_ARR, MPC_SEQ
 
-__all__ = ["MpcSolveFunction", "solve_mpc", "DenseSolveFunction", "solve_dense"]
+__all__ = ["MpcSolveFunction", "solve_mpc", "DenseSolveFunction", "solve_dense", "ClosedLoopMpcFunction",
+           "closed_loop_mpc"]
 
 
 def _forward(names, ctx, solver, sigma, arrs):
@@ -154,3 +170,68 @@ def solve_dense(solver, data, sigma: float = 0.0):
     tensors (any of them may require grad; ``(len,)`` or ``(1, len)``: a parameter shared by the batch).  Returns
     ``(z, l, v, out)``; see the module docstring."""
     return DenseSolveFunction.apply(solver, sigma, *[data[k] for k in DENSE_ARR])
+
+
+class ClosedLoopMpcFunction(torch.autograd.Function):
+    """apply(solver, steps, retire, sigma, A, B, *sequences in MPC_SEQ order) -> (u, x, out)."""
+
+    @staticmethod
+    def forward(ctx, solver, steps, retire, sigma, A, B, *seqs):
+        Bn = max(a.shape[0] if a.dim() == 2 else 1 for a in seqs)
+        ctx.shared = tuple(k for k, a in zip(MPC_SEQ, seqs) if Bn > 1 and (a.dim() == 1 or a.shape[0] == 1))
+        assert "x0" not in ctx.shared, "every trajectory has its own initial state"
+        ctx.shapes = {k: a.shape for k, a in zip(MPC_SEQ, seqs)}
+        data = {k: (a.detach().reshape(1, a.numel()) if k in ctx.shared else a.detach()).contiguous()
+                for k, a in zip(MPC_SEQ, seqs)}
+        dev = data["Q"].device
+        # (the sweep advances x0 in place and wants one copy of every sequence per trajectory)
+        run = {k: (a.expand(Bn, a.shape[1]).contiguous() if k in ctx.shared else a) for k, a in data.items()}
+        run["x0"] = data["x0"].clone()
+        mk = lambda n: torch.zeros((Bn, n), dtype=torch.float64, device=dev)
+        z, l, v, y = mk(solver.nz), mk(solver.nl), mk(solver.nv), mk(solver.nv)
+        r = solver.RecedingSweep(run, z, l, v, y, A.detach(), B.detach(), steps, retire=retire, log_inputs=True,
+                                 log=True)
+        u = r["u"]
+        x = torch.cat([r["x_log"][1:], run["x0"][None]], 0)
+        ctx.solver, ctx.steps, ctx.retire, ctx.sigma = solver, steps, retire, sigma
+        ctx.save_for_backward(A.detach(), B.detach(), u, *[r[k] for k in ("z_log", "l_log", "v_log", "x_log",
+                                                                           "eflag_log")],
+                              *[data[k] for k in MPC_SEQ])
+        ctx.mark_non_differentiable(r["out"])
+        return u, x, r["out"]
+
+    @staticmethod
+    def backward(ctx, gu, gx, gout):
+        need = ctx.needs_input_grad
+        want = [k for k, n in zip(MPC_SEQ, need[6:]) if n]
+        plant = need[4] or need[5]
+        if not want and not plant:
+            return (None,) * len(need)
+        A, B, u, zl, ll, vl, xl, el = ctx.saved_tensors[:8]
+        data = dict(zip(MPC_SEQ, ctx.saved_tensors[8:]))
+        log = dict(z_log=zl, l_log=ll, v_log=vl, eflag_log=el)
+        g = ctx.solver.RecedingSweepAdjoint(data, A, B, ctx.steps, log, gu=gu.contiguous(), gx=gx.contiguous(),
+                                            retire=ctx.retire, sigma=ctx.sigma, want=want, mu=plant)
+        gA = gB = None
+        if plant:
+            # x_(k+1) of a retired trajectory is the constant 0: its costates do not reach the plant
+            mu = torch.where((el == -1)[:, :, None], torch.zeros_like(g["mu"]), g["mu"])
+            gA = torch.einsum("kbi,kbj->ij", mu, xl) if need[4] else None
+            gB = torch.einsum("kbi,kbj->ij", mu, u) if need[5] else None
+        grads = []
+        for k in MPC_SEQ:
+            if k not in want:
+                grads.append(None)
+            elif k in ctx.shared:
+                grads.append(g[k].sum(0).reshape(ctx.shapes[k]))
+            else:
+                grads.append(g[k])
+        return (None, None, None, None, gA, gB) + tuple(grads)
+
+
+def closed_loop_mpc(solver, data, A, B, steps: int, retire: bool = True, sigma: float = 0.0):
+    """Differentiable receding-horizon sweep: ``data`` as for ``solve_mpc`` (``x0``: the trajectories' initial
+    states, ``(B, nx)``), ``A``/``B`` the plant x+ = A x + B u0 as ``(nx, nx)``/``(nx, nu)`` float64 CUDA tensors.
+    Returns ``(u, x, out)``: the inputs ``(steps, B, nu)``, the states after each step ``(steps, B, nx)`` and the last
+    step's SolverOut records; see the module docstring."""
+    return ClosedLoopMpcFunction.apply(solver, steps, retire, sigma, A, B, *[data[k] for k in MPC_SEQ])

@@ -21,8 +21,18 @@ struct MpcGrad {
 
 // Every slot of G that is not null is written; ok = false writes zeros there, and to (az, al, av) where they are
 // not null (which otherwise receive dz, dl, dv).  Threads c.tid, c.tid + C::nt, ... of every sequence; the
-// caller synchronises before and after.
-template <class C>
+// caller synchronises before and after.  ACC (fbstab_mpc_r16_sweep_adjoint_kernel): the slots of G are ADDED to
+// - by the thread that wrote the entry before, so a caller that zeroes them with the same thread mapping needs no
+// synchronisation between the steps it sums over.
+// One entry of a gradient slot: stored, or (ACC: the sweep adjoint's sum over the steps) added to what is there.
+// (A macro, so that the store of the instantiations without ACC is the statement it always was.)
+#define FB_ADJOINT_PUT(slot, val) \
+  do {                            \
+    if constexpr (ACC) slot += val; \
+    else slot = val;              \
+  } while (0)
+
+template <bool ACC = false, class C>
 FB_DEV void mpc_adjoint_contract(const C& c, int N, int nx, int nu, int nc, const double* z, const double* l,
                                  const double* v, const double* dz, const double* dl, const double* dv,
                                  const MpcGrad& G, bool ok, double* az, double* al, double* av) {
@@ -32,58 +42,58 @@ FB_DEV void mpc_adjoint_contract(const C& c, int N, int nx, int nu, int nc, cons
     for (int e = c.tid; e < (N + 1) * sq; e += C::nt) {
       const int i = e / sq, r = (e % sq) % nx, k = (e % sq) / nx;
       const double *x = z + (long)i * ns, *dx = dz + (long)i * ns;
-      G.Q[e] = ok ? -0.5 * (dx[r] * x[k] + x[r] * dx[k]) : 0.0;
+      FB_ADJOINT_PUT(G.Q[e], ok ? -0.5 * (dx[r] * x[k] + x[r] * dx[k]) : 0.0);
     }
   if (G.R)
     for (int e = c.tid; e < (N + 1) * sr; e += C::nt) {
       const int i = e / sr, r = (e % sr) % nu, k = (e % sr) / nu;
       const double *u = z + (long)i * ns + nx, *du = dz + (long)i * ns + nx;
-      G.R[e] = ok ? -0.5 * (du[r] * u[k] + u[r] * du[k]) : 0.0;
+      FB_ADJOINT_PUT(G.R[e], ok ? -0.5 * (du[r] * u[k] + u[r] * du[k]) : 0.0);
     }
   if (G.S)
     for (int e = c.tid; e < (N + 1) * su; e += C::nt) {
       const int i = e / su, r = (e % su) % nu, k = (e % su) / nu;
       const double *x = z + (long)i * ns, *dx = dz + (long)i * ns;
-      G.S[e] = ok ? -(dx[nx + r] * x[k] + x[nx + r] * dx[k]) : 0.0;
+      FB_ADJOINT_PUT(G.S[e], ok ? -(dx[nx + r] * x[k] + x[nx + r] * dx[k]) : 0.0);
     }
   if (G.q)
-    for (int e = c.tid; e < (N + 1) * nx; e += C::nt) G.q[e] = ok ? -dz[(long)(e / nx) * ns + e % nx] : 0.0;
+    for (int e = c.tid; e < (N + 1) * nx; e += C::nt) FB_ADJOINT_PUT(G.q[e], ok ? -dz[(long)(e / nx) * ns + e % nx] : 0.0);
   if (G.r)
-    for (int e = c.tid; e < (N + 1) * nu; e += C::nt) G.r[e] = ok ? -dz[(long)(e / nu) * ns + nx + e % nu] : 0.0;
+    for (int e = c.tid; e < (N + 1) * nu; e += C::nt) FB_ADJOINT_PUT(G.r[e], ok ? -dz[(long)(e / nu) * ns + nx + e % nu] : 0.0);
   if (G.A)
     for (int e = c.tid; e < N * sq; e += C::nt) {
       const int i = e / sq, r = (e % sq) % nx, k = (e % sq) / nx;
       const double *x = z + (long)i * ns, *dx = dz + (long)i * ns;
       const double *lp = l + (long)(i + 1) * nx, *dlp = dl + (long)(i + 1) * nx;
-      G.A[e] = ok ? -(dlp[r] * x[k] + lp[r] * dx[k]) : 0.0;
+      FB_ADJOINT_PUT(G.A[e], ok ? -(dlp[r] * x[k] + lp[r] * dx[k]) : 0.0);
     }
   if (G.B)
     for (int e = c.tid; e < N * sb; e += C::nt) {
       const int i = e / sb, r = (e % sb) % nx, k = (e % sb) / nx;
       const double *u = z + (long)i * ns + nx, *du = dz + (long)i * ns + nx;
       const double *lp = l + (long)(i + 1) * nx, *dlp = dl + (long)(i + 1) * nx;
-      G.B[e] = ok ? -(dlp[r] * u[k] + lp[r] * du[k]) : 0.0;
+      FB_ADJOINT_PUT(G.B[e], ok ? -(dlp[r] * u[k] + lp[r] * du[k]) : 0.0);
     }
   if (G.c)
-    for (int e = c.tid; e < N * nx; e += C::nt) G.c[e] = ok ? -dl[nx + e] : 0.0;
+    for (int e = c.tid; e < N * nx; e += C::nt) FB_ADJOINT_PUT(G.c[e], ok ? -dl[nx + e] : 0.0);
   if (G.E)
     for (int e = c.tid; e < (N + 1) * se; e += C::nt) {
       const int i = e / se, r = (e % se) % nc, k = (e % se) / nc;
       const double *x = z + (long)i * ns, *dx = dz + (long)i * ns;
       const double *vi = v + (long)i * nc, *dvi = dv + (long)i * nc;
-      G.E[e] = ok ? -(dvi[r] * x[k] + vi[r] * dx[k]) : 0.0;
+      FB_ADJOINT_PUT(G.E[e], ok ? -(dvi[r] * x[k] + vi[r] * dx[k]) : 0.0);
     }
   if (G.L)
     for (int e = c.tid; e < (N + 1) * sl; e += C::nt) {
       const int i = e / sl, r = (e % sl) % nc, k = (e % sl) / nc;
       const double *u = z + (long)i * ns + nx, *du = dz + (long)i * ns + nx;
       const double *vi = v + (long)i * nc, *dvi = dv + (long)i * nc;
-      G.L[e] = ok ? -(dvi[r] * u[k] + vi[r] * du[k]) : 0.0;
+      FB_ADJOINT_PUT(G.L[e], ok ? -(dvi[r] * u[k] + vi[r] * du[k]) : 0.0);
     }
   if (G.d)
-    for (int e = c.tid; e < (N + 1) * nc; e += C::nt) G.d[e] = ok ? -dv[e] : 0.0;
+    for (int e = c.tid; e < (N + 1) * nc; e += C::nt) FB_ADJOINT_PUT(G.d[e], ok ? -dv[e] : 0.0);
   if (G.x0)
-    for (int e = c.tid; e < nx; e += C::nt) G.x0[e] = ok ? -dl[e] : 0.0;
+    for (int e = c.tid; e < nx; e += C::nt) FB_ADJOINT_PUT(G.x0[e], ok ? -dl[e] : 0.0);
   const long nz = (long)(N + 1) * ns, nl = (long)(N + 1) * nx, nv = (long)(N + 1) * nc;
   if (az)
     for (long e = c.tid; e < nz; e += C::nt) az[e] = ok ? dz[e] : 0.0;
@@ -92,6 +102,8 @@ FB_DEV void mpc_adjoint_contract(const C& c, int N, int nx, int nu, int nc, cons
   if (av)
     for (long e = c.tid; e < nv; e += C::nt) av[e] = ok ? dv[e] : 0.0;
 }
+
+#undef FB_ADJOINT_PUT
 
 // ---- dense (fbstab_hip_dense_adjoint_batch) -------------------------------------------------------------
 // The same contraction for the dense data min 1/2 z'Hz + f'z s.t. Gz = h, Az <= b (h and b enter directly):

@@ -1,7 +1,8 @@
 // The record kernels' entry point and queue (fb_mpc_r16.h holds the numerics), shared by
 // the translation units of the library: every instance <NX, NU, NC, R> is compiled in a
 // file of its own (rec_*.hip, a minute or two each, in parallel under `make -j`) and
-// hands fbstab_hip.hip a RecordInstance with the addresses of its kernels (six of the solve, two of the adjoint).
+// hands fbstab_hip.hip a RecordInstance with the addresses of its kernels (six of the solve, two of the adjoint,
+// two of the sweep adjoint).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +28,9 @@ struct RecordInstance {
   // fbstab_hip_mpc_adjoint_batch on the record (fbstab_mpc_r16_adjoint_kernel) and the name it is reported under
   const void *adjoint, *adjoint_exact;
   const char* adjoint_name;
+  // fbstab_hip_mpc_receding_sweep_adjoint on the record (fbstab_mpc_r16_sweep_adjoint_kernel)
+  const void *sweep_adjoint, *sweep_adjoint_exact;
+  const char* sweep_adjoint_name;
 };
 
 // Arguments of the record adjoint kernel (fbstab_hip_mpc_adjoint_batch): the seeds (gz, gl, gv; gl and gv may be
@@ -40,6 +44,25 @@ struct AdjointArgs {
   double* adj[3];
   long long astride[3];
   int* status;
+  double sigma, alpha;
+};
+
+// Arguments of the sweep adjoint kernel (fbstab_hip_mpc_receding_sweep_adjoint): the plant, the log of the sweep
+// ([steps][batch][n] each), the seeds gu, gx (null: zero), the gradient slots (null: not wanted; the x0 slot
+// receives the final costate), mu_log (or null), the per-trajectory count of failed factorisations, and `seed`:
+// nz doubles per row slot of the grid, zero outside the u0 entries, where a row stages the seed vector of a step.
+struct SweepAdjointArgs {
+  const double *A, *B;  // column-major, as SweepArgs
+  long long sA, sB;
+  const double *lz, *ll, *lv;
+  const int* le;
+  const double *gu, *gx;
+  double* grad[FBSTAB_MPC_NSEQ];
+  long long gstride[FBSTAB_MPC_NSEQ];
+  double* mu_log;
+  int* status;
+  double* seed;
+  int steps;
   double sigma, alpha;
 };
 
@@ -130,6 +153,9 @@ struct SweepArgs {
   unsigned long long* stats;  // [steps][4]
   int steps, retire;
   int nx, nu, nz, nl, nv;
+  // fbstab_hip_mpc_receding_sweep_logged: NULL, or [steps][batch][nz | nl | nv | nx] and [steps][batch]
+  double *log_z, *log_l, *log_v, *log_x0;
+  int* log_eflag;
 };
 
 // Closed-loop step of trajectory q after its solve number `step`, by the lanes of its
@@ -163,6 +189,23 @@ __device__ __noinline__ bool receding_plant_step(const SweepArgs* sweep, const V
   }
   if (a.u_log && t < a.nu) a.u_log[((long long)step * batch + q) * a.nu + t] = gone ? 0.0 : z[a.nx + t];
   double* xs = a.x0 + q * a.sx0;
+  {
+    // the log of the backward pass: the point this step returned (zeros once retired), the state it was solved
+    // for and its eflag
+    const long long kq = (long long)step * batch + q;
+    if (a.log_z)
+      for (int i = t; i < a.nz; i += lpq) a.log_z[kq * a.nz + i] = gone ? 0.0 : z[i];
+    if (a.log_l) {
+      const double* l = x->base[1] + q * x->stride[1];
+      for (int i = t; i < a.nl; i += lpq) a.log_l[kq * a.nl + i] = gone ? 0.0 : l[i];
+    }
+    if (a.log_v) {
+      const double* v = x->base[2] + q * x->stride[2];
+      for (int i = t; i < a.nv; i += lpq) a.log_v[kq * a.nv + i] = gone ? 0.0 : v[i];
+    }
+    if (a.log_x0 && t < a.nx) a.log_x0[kq * a.nx + t] = xs[t];
+    if (a.log_eflag && t == 0) a.log_eflag[kq] = gone ? -1 : eflag;
+  }
   const double* Aq = a.A + q * a.sA;
   const double* Bq = a.B + q * a.sB;
   double acc = 0.0;  // (nx <= lanes of the row: one entry per lane)
@@ -376,6 +419,124 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_adjoint_
   }
 }
 
+// The adjoint of a whole receding-horizon sweep (fbstab_hip_mpc_receding_sweep_adjoint) on the record instances:
+// rows - row pairs - pull TRAJECTORIES from the counter, and the row that owns trajectory q takes the costate
+// backwards through its logged steps k = steps-1 .. 0 (include/fbstab_hip.h has the recursion): per step that
+// counts, the adjoint kernel's work at the logged point - bind, load_guess, choose_costate_form, adjoint_step with
+// the seed gu[k] + B'mu on the u0 entries - and the contraction ADDED into the trajectory's own gradient slots, by
+// the lanes that zeroed them.  Lane t < nx carries lambda_t and mu_t in registers (the other lanes' entries come
+// by shuffle within the row); the seed vector lives in the row slot's share of a.seed, which is zero outside the u0
+// entries from the host's memset on.  No atomics, one fixed order: the same inputs give the same bits.
+template <int NX, int NU, int NC, bool EXACT, int R>
+__global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_sweep_adjoint_kernel(
+    MpcBatchPtrs data, SweepAdjointArgs a, double* scratch, int* counter, int batch, int N) {
+  typedef MpcR16<NX, NU, NC, EXACT, false, R> P;
+  typename P::C ctx;
+  ctx.tid = threadIdx.x & (P::LPQ - 1);
+  P p;
+  VarBatchPtrs xk;  // the logged point of the step in hand
+  for (int i = 0; i < 4; i++) { xk.base[i] = nullptr; xk.stride[i] = 0; }
+  R16Queue<P, false> qu;
+  qu.data = &data;
+  qu.x = &xk;
+  qu.ctl = counter;
+  qu.scratch = scratch;
+  qu.batch = batch;
+  qu.N = N;
+  qu.reuse = false;
+  p.bind_idle(qu.lds(), qu.pack_lds(), qu.lpo(), N);
+  const int nx = EXACT ? NX : data.nx, nu = EXACT ? NU : data.nu, nc = EXACT ? NC : data.nc;
+  const long nz = (long)(N + 1) * (nx + nu), nl = (long)(N + 1) * nx, nv = (long)(N + 1) * nc;
+  const int t = ctx.tid;
+  for (;;) {
+    const long q = qu.fetch(p);
+    if (q < 0) break;
+    auto at = [q](double* b, long long s) { return b ? b + q * s : nullptr; };
+    MpcGrad G;
+    G.Q = at(a.grad[FBSTAB_MPC_Q], a.gstride[FBSTAB_MPC_Q]);
+    G.R = at(a.grad[FBSTAB_MPC_R], a.gstride[FBSTAB_MPC_R]);
+    G.S = at(a.grad[FBSTAB_MPC_S], a.gstride[FBSTAB_MPC_S]);
+    G.q = at(a.grad[FBSTAB_MPC_q], a.gstride[FBSTAB_MPC_q]);
+    G.r = at(a.grad[FBSTAB_MPC_r], a.gstride[FBSTAB_MPC_r]);
+    G.A = at(a.grad[FBSTAB_MPC_A], a.gstride[FBSTAB_MPC_A]);
+    G.B = at(a.grad[FBSTAB_MPC_B], a.gstride[FBSTAB_MPC_B]);
+    G.c = at(a.grad[FBSTAB_MPC_c], a.gstride[FBSTAB_MPC_c]);
+    G.E = at(a.grad[FBSTAB_MPC_E], a.gstride[FBSTAB_MPC_E]);
+    G.L = at(a.grad[FBSTAB_MPC_L], a.gstride[FBSTAB_MPC_L]);
+    G.d = at(a.grad[FBSTAB_MPC_d], a.gstride[FBSTAB_MPC_d]);
+    G.x0 = nullptr;  // (receives the final costate, below)
+    {
+      // zeros, by the lanes that add to the entries later (mpc_adjoint_contract's mapping)
+      const int sq = nx * nx, sr = nu * nu, su = nu * nx, se = nc * nx, sl = nc * nu;
+      auto zero = [t](double* g, long n) {
+        if (g)
+          for (long e = t; e < n; e += P::C::nt) g[e] = 0.0;
+      };
+      zero(G.Q, (long)(N + 1) * sq); zero(G.R, (long)(N + 1) * sr); zero(G.S, (long)(N + 1) * su);
+      zero(G.q, (long)(N + 1) * nx); zero(G.r, (long)(N + 1) * nu); zero(G.A, (long)N * sq);
+      zero(G.B, (long)N * su); zero(G.c, (long)N * nx); zero(G.E, (long)(N + 1) * se);
+      zero(G.L, (long)(N + 1) * sl); zero(G.d, (long)(N + 1) * nc);
+    }
+    const double* Aq = a.A + q * a.sA;
+    const double* Bq = a.B + q * a.sB;
+    double* const seed = a.seed + (long)qu.home() * nz;
+    double* const flat = qu.slot_ptr(qu.home()) + P::hdr_doubles(N);
+    double lam = 0.0;  // lambda_t on the lanes t < nx
+    int failed = 0;
+    for (int k = a.steps - 1; k >= 0; k--) {
+      const long long kq = (long long)k * batch + q;
+      double mu = 0.0;
+      if (t < nx) {
+        mu = (a.gx ? a.gx[kq * nx + t] : 0.0) + lam;
+        if (a.mu_log) a.mu_log[kq * nx + t] = mu;
+      }
+      const int e = a.le[kq];
+      if (e == -1) {  // retired at or before this step: x_(k+1) and u_k are the constant 0
+        lam = 0.0;
+        continue;
+      }
+      // A'mu on the lanes t < nx, B'mu on the lanes t < nu
+      double atm = 0.0, btm = 0.0;
+      for (int r = 0; r < nx; r++) {
+        const double mr = __shfl(mu, r, P::LPQ);
+        if (t < nx) atm = fma(Aq[r + t * nx], mr, atm);
+        if (t < nu) btm = fma(Bq[r + t * nx], mr, btm);
+      }
+      if (e != FBSTAB_SUCCESS) {  // the returned point is no solution: u_k is a constant
+        lam = atm;
+        continue;
+      }
+      if (t < nu) seed[nx + t] = (a.gu ? a.gu[kq * nu + t] : 0.0) + btm;
+      xk.base[0] = const_cast<double*>(a.lz) + (long long)k * batch * nz; xk.stride[0] = nz;
+      xk.base[1] = const_cast<double*>(a.ll) + (long long)k * batch * nl; xk.stride[1] = nl;
+      xk.base[2] = const_cast<double*>(a.lv) + (long long)k * batch * nv; xk.stride[2] = nv;
+      // the seed's stores are read by the row's other lanes
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      p.bind(qu.slot_ptr(qu.home()), qu.lds(), qu.pack_lds(), qu.lpo(), &data, &xk, q, N, t);
+      p.load_guess(ctx);
+      p.choose_costate_form(a.sigma);
+      const bool ok = p.adjoint_step(ctx, a.sigma, a.alpha, seed, nullptr, nullptr, flat);
+      // the lanes' stores of the step are read by the row's other lanes
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      if (ok) {
+        mpc_adjoint_contract<true>(ctx, N, nx, nu, nc, xk.base[0] + q * nz, xk.base[1] + q * nl, xk.base[2] + q * nv,
+                                   flat, flat + nz, flat + nz + nl, G, true, nullptr, nullptr, nullptr);
+        lam = t < nx ? atm - flat[nz + t] : 0.0;
+      } else {
+        failed++;
+        lam = atm;
+      }
+      // (the next step of this row packs its record over the flat step the contraction has read)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    if (a.grad[FBSTAB_MPC_x0] && t < nx) a.grad[FBSTAB_MPC_x0][q * a.gstride[FBSTAB_MPC_x0] + t] = lam;
+    if (t == 0) a.status[q] = failed;
+  }
+}
+
 template <int NX, int NU, int NC, int R>
 long long r16_ws_doubles(int N) { return fbk::MpcR16<NX, NU, NC, true, false, R>::ws_doubles(N); }
 template <int NX, int NU, int NC, int R>
@@ -386,10 +547,11 @@ int r16_lds_bytes(int N) {
 // R: 16-lane rows of the wavefront per QP (1: four QPs per wavefront, stage width
 // <= 16; 2: two QPs per wavefront, stage width <= 32)
 template <int NX, int NU, int NC, int R = 1>
-RecordInstance r16_instance(const char* name, const char* adjoint_name) {
+RecordInstance r16_instance(const char* name, const char* adjoint_name, const char* sweep_adjoint_name) {
   RecordInstance r;
   r.name = name;
   r.adjoint_name = adjoint_name;
+  r.sweep_adjoint_name = sweep_adjoint_name;
   r.nx = NX; r.nu = NU; r.nc = NC;
   r.qps_per_wg = 4 / R;
   r.lds_bytes = r16_lds_bytes<NX, NU, NC, R>;
@@ -402,6 +564,8 @@ RecordInstance r16_instance(const char* name, const char* adjoint_name) {
   r.probe_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, true, true, false, R>);
   r.adjoint = reinterpret_cast<const void*>(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, false, R>);
   r.adjoint_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, true, R>);
+  r.sweep_adjoint = reinterpret_cast<const void*>(fbstab_mpc_r16_sweep_adjoint_kernel<NX, NU, NC, false, R>);
+  r.sweep_adjoint_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_sweep_adjoint_kernel<NX, NU, NC, true, R>);
   return r;
 }
 
@@ -410,7 +574,8 @@ RecordInstance r16_instance(const char* name, const char* adjoint_name) {
 // Defines the factory of one instance (one per rec_*.hip); fbstab_hip.hip lists them.
 #define FB_RECORD_INSTANCE(NX, NU, NC, R, NAME)                                              \
   __attribute__((visibility("hidden"))) RecordInstance fbstab_record_instance_##NX##_##NU##_##NC##_##R() { \
-    return r16_instance<NX, NU, NC, R>(NAME, "fbstab_mpc_r16_adjoint_kernel<" #NX "," #NU "," #NC ">"); \
+    return r16_instance<NX, NU, NC, R>(NAME, "fbstab_mpc_r16_adjoint_kernel<" #NX "," #NU "," #NC ">", \
+                                       "fbstab_mpc_r16_sweep_adjoint_kernel<" #NX "," #NU "," #NC ">"); \
   }
 #define FB_RECORD_INSTANCE_DECL(NX, NU, NC, R) \
   __attribute__((visibility("hidden"))) RecordInstance fbstab_record_instance_##NX##_##NU##_##NC##_##R();

@@ -187,10 +187,16 @@ __global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_adjoint_kernel(
 // would: its QP is then solved by the zero vector in one proximal iteration.
 // stats[step] = {sum of Newton iterations, solves that ended in SUCCESS,
 // trajectories retired so far, largest Newton count}.
+// lg: this step's share of the sweep log (fbstab_hip_mpc_receding_sweep_logged; null slots are not logged).
+struct SweepLogStep {
+  double *z, *l, *v, *x0;
+  int* eflag;
+};
 __global__ void fbstab_receding_plant_kernel(int batch, int nx, int nu, int nz, int nl, int nv, const double* A,
                                              long long sA, const double* B, long long sB, double* x0, long long sx0,
                                              VarBatchArgs x, const fbstab_solver_out_t* out, int* retired,
-                                             int retire, double* u_log, unsigned long long* stats, double* xtmp) {
+                                             int retire, double* u_log, unsigned long long* stats, double* xtmp,
+                                             SweepLogStep lg) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = q < batch;
   fbstab_solver_out_t o;
@@ -232,6 +238,21 @@ __global__ void fbstab_receding_plant_kernel(int batch, int nx, int nu, int nz, 
   // registers up to 64 states, in the caller's per-trajectory buffer beyond)
   if (u_log)
     for (int j = 0; j < nu; j++) u_log[(long long)q * nu + j] = gone ? 0.0 : z[nx + j];
+  // the log of the backward pass: the point this step returned (zeros once retired), the state it was solved
+  // for and its eflag (what receding_plant_step logs in the one-launch sweep)
+  if (lg.z)
+    for (int i = 0; i < nz; i++) lg.z[(long long)q * nz + i] = gone ? 0.0 : z[i];
+  if (lg.l) {
+    const double* l = x.base[1] + q * x.stride[1];
+    for (int i = 0; i < nl; i++) lg.l[(long long)q * nl + i] = gone ? 0.0 : l[i];
+  }
+  if (lg.v) {
+    const double* v = x.base[2] + q * x.stride[2];
+    for (int i = 0; i < nv; i++) lg.v[(long long)q * nv + i] = gone ? 0.0 : v[i];
+  }
+  if (lg.x0)
+    for (int r = 0; r < nx; r++) lg.x0[(long long)q * nx + r] = xs[r];
+  if (lg.eflag) lg.eflag[q] = gone ? -1 : o.eflag;
   const double* Aq = A + q * sA;
   const double* Bq = B + q * sB;
   double xloc[64];
@@ -243,6 +264,81 @@ __global__ void fbstab_receding_plant_kernel(int batch, int nx, int nu, int nz, 
     xn[r] = gone ? 0.0 : acc;
   }
   for (int r = 0; r < nx; r++) xs[r] = xn[r];
+}
+
+// The per-step form of fbstab_hip_mpc_receding_sweep_adjoint (include/fbstab_hip.h has the recursion): between
+// the adjoint launches of the steps, one workgroup per trajectory.
+//   phase 0: zeros in the caller's gradient slots, lambda = 0, status = 0, a zero seed vector;
+//   phase 1 (before step k's adjoint launch): mu = gx[k] + lambda (kept where lambda was, and in mu_log), A'mu,
+//            and the seed gu[k] + B'mu on the u0 entries;
+//   phase 2 (after it): the step's gradients, which the launch left in the handle's per-QP image, are added to the
+//            slots and lambda <- A'mu - dl[0:nx] (the image's x0 slot is -dl[0:nx]) - or the step does not count:
+//            retired (lambda <- 0), no solution or a failed factorisation (lambda <- A'mu).  `last`: lambda goes
+//            to the x0 slot.
+// Every sum is formed in a fixed order by one thread: the same inputs give the same bits.
+struct SweepCostateArgs {
+  const double *A, *B;
+  long long sA, sB;
+  const int* eflag;       // step k's [batch]
+  const double *gu, *gx;  // step k's [batch][nu | nx], or null
+  double* mu_log;         // step k's [batch][nx], or null
+  double* grad[FBSTAB_MPC_NSEQ];
+  long long gstride[FBSTAB_MPC_NSEQ];
+  const double* tmp[FBSTAB_MPC_NSEQ];  // the image of one step (null where the slot is; x0 always)
+  long long len[FBSTAB_MPC_NSEQ];
+  double *seed, *lam, *atm;  // [batch][nz], [batch][nx], [batch][nx]
+  const int* tmp_status;
+  int* status;
+  int nx, nu, nz;
+};
+__global__ __launch_bounds__(64) void fbstab_sweep_costate_kernel(SweepCostateArgs a, int phase, int last) {
+  const long long q = blockIdx.x;
+  const int t = threadIdx.x, nt = 64;
+  const int nx = a.nx, nu = a.nu;
+  double* lam = a.lam + q * nx;
+  double* atm = a.atm + q * nx;
+  if (phase == 0) {
+    for (int s = 0; s < FBSTAB_MPC_NSEQ; s++)
+      if (a.grad[s])
+        for (long long e = t; e < a.len[s]; e += nt) a.grad[s][q * a.gstride[s] + e] = 0.0;
+    for (int i = t; i < nx; i += nt) lam[i] = 0.0;
+    for (long long i = t; i < a.nz; i += nt) a.seed[q * a.nz + i] = 0.0;
+    if (t == 0) a.status[q] = 0;
+    return;
+  }
+  if (phase == 1) {
+    for (int i = t; i < nx; i += nt) {
+      const double mu = (a.gx ? a.gx[q * nx + i] : 0.0) + lam[i];
+      lam[i] = mu;
+      if (a.mu_log) a.mu_log[q * nx + i] = mu;
+    }
+    __syncthreads();
+    const double* Aq = a.A + q * a.sA;
+    const double* Bq = a.B + q * a.sB;
+    for (int i = t; i < nx; i += nt) {
+      double acc = 0.0;
+      for (int r = 0; r < nx; r++) acc = fma(Aq[r + (long long)i * nx], lam[r], acc);
+      atm[i] = acc;
+    }
+    for (int j = t; j < nu; j += nt) {
+      double acc = 0.0;
+      for (int r = 0; r < nx; r++) acc = fma(Bq[r + (long long)j * nx], lam[r], acc);
+      a.seed[q * a.nz + nx + j] = (a.gu ? a.gu[q * nu + j] : 0.0) + acc;
+    }
+    return;
+  }
+  const int e = a.eflag[q];
+  const bool solved = e == FBSTAB_SUCCESS, ok = solved && a.tmp_status[q] == 0;
+  if (ok)
+    for (int s = 0; s < FBSTAB_MPC_NSEQ; s++)
+      if (a.grad[s] && s != FBSTAB_MPC_x0)
+        for (long long i = t; i < a.len[s]; i += nt) a.grad[s][q * a.gstride[s] + i] += a.tmp[s][q * a.len[s] + i];
+  for (int i = t; i < nx; i += nt) {
+    const double l = e == -1 ? 0.0 : (ok ? atm[i] + a.tmp[FBSTAB_MPC_x0][q * nx + i] : atm[i]);
+    lam[i] = l;
+    if (last && a.grad[FBSTAB_MPC_x0]) a.grad[FBSTAB_MPC_x0][q * a.gstride[FBSTAB_MPC_x0] + i] = l;
+  }
+  if (solved && !ok && t == 0) a.status[q] += 1;
 }
 
 // KGLOBAL: K in a per-workgroup global scratch (fb_dense.h); the argument is
@@ -1115,6 +1211,11 @@ struct fbstab_mpc_solver : SolverBase {
   bool flat_adjoint = false;
   double* adj_scratch = nullptr;
   bool adj_ready = false;
+  // fbstab_hip_mpc_receding_sweep_adjoint, allocated by the first call that needs them: the seed vectors of the
+  // one-launch kernel (nz doubles per row slot of the grid) and the per-step form's image of one step
+  double* sweep_seed = nullptr;
+  double* sweep_tmp = nullptr;
+  bool sweep_adj_ready = false;
 };
 
 namespace {
@@ -1313,6 +1414,8 @@ int fbstab_hip_mpc_destroy(fbstab_mpc_handle_t h) {
   if (!h) return FBSTAB_HIP_OK;
   h->release();
   if (h->adj_scratch) (void)hipFree(h->adj_scratch);
+  if (h->sweep_seed) (void)hipFree(h->sweep_seed);
+  if (h->sweep_tmp) (void)hipFree(h->sweep_tmp);
   delete h;
   return FBSTAB_HIP_OK;
 }
@@ -1437,10 +1540,12 @@ int fbstab_hip_mpc_solve_traced(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t*
 
 // BASELINE configs[4]: `steps` closed-loop steps without a host round trip in
 // between - solve, plant step, solve, ... queued on one stream.
-int fbstab_hip_mpc_receding_sweep(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
-                                  const fbstab_var_batch_t* x, fbstab_solver_out_t* out,
-                                  const fbstab_receding_plant_t* plant, int steps, int retire,
-                                  double* u_log, unsigned long long* stats, float* kernel_ms, void* stream) {
+// (`log`: fbstab_hip_mpc_receding_sweep_logged; null: nothing is logged)
+static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                   const fbstab_var_batch_t* x, fbstab_solver_out_t* out,
+                                   const fbstab_receding_plant_t* plant, int steps, int retire, double* u_log,
+                                   unsigned long long* stats, float* kernel_ms, void* stream,
+                                   const fbstab_sweep_log_t* log) {
   int rc = check_common(h, batch, data, x, out, h ? h->max_batch : 0);
   if (rc != FBSTAB_HIP_OK) return rc;
   if (!plant || !plant->A || !plant->B || steps < 0)
@@ -1490,6 +1595,8 @@ int fbstab_hip_mpc_receding_sweep(fbstab_mpc_handle_t h, int batch, const fbstab
     sa.u_log = u_log; sa.stats = static_cast<unsigned long long*>(d_stats.p);
     sa.steps = steps; sa.retire = retire;
     sa.nx = L.nx; sa.nu = L.nu; sa.nz = L.nz; sa.nl = L.nl; sa.nv = L.nv;
+    sa.log_z = log ? log->z : nullptr; sa.log_l = log ? log->l : nullptr; sa.log_v = log ? log->v : nullptr;
+    sa.log_x0 = log ? log->x0 : nullptr; sa.log_eflag = log ? log->eflag : nullptr;
     DevBuf d_sa;
     HIP_TRY(hipMalloc(&d_sa.p, sizeof(SweepArgs)));
     HIP_TRY(hipMemcpyAsync(d_sa.p, &sa, sizeof(SweepArgs), hipMemcpyHostToDevice, s));
@@ -1524,11 +1631,20 @@ int fbstab_hip_mpc_receding_sweep(fbstab_mpc_handle_t h, int batch, const fbstab
     rc = mpc_solve_impl(h, batch, data, x, out, flags, s, nullptr);
     if (rc != FBSTAB_HIP_OK) return rc;
     if (kernel_ms) HIP_TRY(hipEventRecord(ev[2 * k + 1], s));
+    SweepLogStep lg = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (log) {
+      const long long kb = (long long)k * batch;
+      lg.z = log->z ? log->z + kb * L.nz : nullptr;
+      lg.l = log->l ? log->l + kb * L.nl : nullptr;
+      lg.v = log->v ? log->v + kb * L.nv : nullptr;
+      lg.x0 = log->x0 ? log->x0 + kb * L.nx : nullptr;
+      lg.eflag = log->eflag ? log->eflag + kb : nullptr;
+    }
     hipLaunchKernelGGL(fbstab_receding_plant_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, batch, L.nx, L.nu,
                        L.nz, L.nl, L.nv, plant->A, plant->stride_A, plant->B, plant->stride_B, x0,
                        data->stride[FBSTAB_MPC_x0], v, out, static_cast<int*>(d_ret.p), retire,
                        u_log ? u_log + (long long)k * batch * L.nu : nullptr,
-                       static_cast<unsigned long long*>(d_stats.p) + 4 * k, static_cast<double*>(d_xtmp.p));
+                       static_cast<unsigned long long*>(d_stats.p) + 4 * k, static_cast<double*>(d_xtmp.p), lg);
   }
   HIP_TRY(hipGetLastError());
   if (stats)
@@ -1537,6 +1653,21 @@ int fbstab_hip_mpc_receding_sweep(fbstab_mpc_handle_t h, int batch, const fbstab
   if (kernel_ms)
     for (int k = 0; k < steps; k++) HIP_TRY(hipEventElapsedTime(&kernel_ms[k], ev[2 * k], ev[2 * k + 1]));
   return FBSTAB_HIP_OK;
+}
+
+int fbstab_hip_mpc_receding_sweep(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                  const fbstab_var_batch_t* x, fbstab_solver_out_t* out,
+                                  const fbstab_receding_plant_t* plant, int steps, int retire,
+                                  double* u_log, unsigned long long* stats, float* kernel_ms, void* stream) {
+  return mpc_receding_sweep_impl(h, batch, data, x, out, plant, steps, retire, u_log, stats, kernel_ms, stream, nullptr);
+}
+
+int fbstab_hip_mpc_receding_sweep_logged(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                         const fbstab_var_batch_t* x, fbstab_solver_out_t* out,
+                                         const fbstab_receding_plant_t* plant, int steps, int retire,
+                                         double* u_log, unsigned long long* stats, float* kernel_ms, void* stream,
+                                         const fbstab_sweep_log_t* log) {
+  return mpc_receding_sweep_impl(h, batch, data, x, out, plant, steps, retire, u_log, stats, kernel_ms, stream, log);
 }
 
 // Diagnostics for the tests: one Newton step of the device path at (x, xbar,
@@ -1701,6 +1832,153 @@ int fbstab_hip_mpc_adjoint_batch_reduced(fbstab_mpc_handle_t h, int batch, const
                                          const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj,
                                          int* status, const fbstab_solver_out_t* out, int flags, void* stream) {
   return mpc_adjoint_impl(h, batch, data, x, seed, sigma, grad, adj, status, out, flags, stream, true);
+}
+
+// Reverse mode through a logged receding-horizon sweep (include/fbstab_hip.h has the recursion).  Handles on a
+// record adjoint: one launch of fbstab_mpc_r16_sweep_adjoint_kernel; every other handle, and
+// FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP=1: per step the costate kernel, the handle's adjoint launch, the costate kernel.
+static bool sweep_adjoint_in_one_launch(const fbstab_mpc_solver* h) {
+  const char* per_step = getenv("FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP");
+  return h->rec && h->rec->sweep_adjoint && !h->flat_adjoint && !(per_step && atoi(per_step) != 0);
+}
+
+int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                          const fbstab_receding_plant_t* plant, int steps, int retire,
+                                          const fbstab_sweep_log_t* log, const double* gu, const double* gx,
+                                          double sigma, const fbstab_mpc_grad_batch_t* grad, double* mu_log,
+                                          int* status, void* stream) {
+  (void)retire;  // (what it did to the sweep is in the log: eflag -1)
+  // what needs no handle comes first
+  if (!log) return fail(FBSTAB_HIP_ERR_ARGUMENT, "sweep adjoint: null log");
+  if (!log->z || !log->l || !log->v || !log->eflag)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "sweep adjoint: the log's z, l, v and eflag are required");
+  if (steps < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "sweep adjoint: negative step count");
+  if (!data || !grad || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
+  if (!plant || !plant->A || !plant->B) return fail(FBSTAB_HIP_ERR_ARGUMENT, "sweep adjoint: plant matrices are required");
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
+    if (batch > 1 && grad->base[i] && grad->stride[i] == 0)
+      return fail(FBSTAB_HIP_ERR_ARGUMENT,
+                  "sweep adjoint: a gradient slot of stride 0 (summed over the batch) is not served");
+  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null solver handle");
+  if (batch < 0 || batch > h->max_batch)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "batch exceeds the max_batch the handle was created with");
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
+    if (i != FBSTAB_MPC_x0 && !data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
+    if (batch > 1 && i != FBSTAB_MPC_x0 && data->stride[i] != 0 && data->stride[i] < h->arr_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
+    if (batch > 1 && grad->base[i] && grad->stride[i] < h->arr_len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
+  }
+  if (batch == 0) return FBSTAB_HIP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const fbk::MpcLayout& L = h->lay;
+  const double sig = sigma > 0.0 ? sigma : 1e-8;
+  const long long nz = L.nz, nl = L.nl, nv = L.nv;
+  // the kernels' problem data: the x0 slot, which the Newton matrix at x = xbar does not depend on, points at the
+  // states of the logged z (the record packs read SOMETHING there)
+  const double* a_base[FBSTAB_MPC_NSEQ];
+  long long a_stride[FBSTAB_MPC_NSEQ];
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { a_base[i] = data->base[i]; a_stride[i] = batch > 1 ? data->stride[i] : 0; }
+  a_base[FBSTAB_MPC_x0] = log->z;
+  a_stride[FBSTAB_MPC_x0] = nz;
+  h->kept_batch = -1;  // the slots' matrix copies are overwritten
+  if (sweep_adjoint_in_one_launch(h)) {
+    const RecordInstance& r = *h->rec;
+    const void* kern = h->exact ? r.sweep_adjoint_exact : r.sweep_adjoint;
+    if (!h->sweep_adj_ready) {
+      HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
+      h->sweep_adj_ready = true;
+    }
+    const size_t seed_bytes = sizeof(double) * (size_t)nz * (size_t)h->workgroups * (size_t)h->qps_per_wg;
+    if (!h->sweep_seed) HIP_TRY(hipMalloc(&h->sweep_seed, seed_bytes));
+    HIP_TRY(hipMemsetAsync(h->sweep_seed, 0, seed_bytes, s));
+    HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
+    MpcBatchPtrs d;
+    SweepAdjointArgs aa;
+    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
+      d.base[i] = a_base[i]; d.stride[i] = a_stride[i];
+      aa.grad[i] = grad->base[i]; aa.gstride[i] = grad->stride[i];
+    }
+    d.nx = L.nx; d.nu = L.nu; d.nc = L.nc;
+    aa.A = plant->A; aa.B = plant->B; aa.sA = plant->stride_A; aa.sB = plant->stride_B;
+    aa.lz = log->z; aa.ll = log->l; aa.lv = log->v; aa.le = log->eflag;
+    aa.gu = gu; aa.gx = gx;
+    aa.mu_log = mu_log; aa.status = status; aa.seed = h->sweep_seed;
+    aa.steps = steps; aa.sigma = sig; aa.alpha = h->opts.alpha;
+    // (as the adjoint: a batch that does not outnumber the workgroups runs one trajectory per wavefront)
+    int grid = (batch + h->qps_per_wg - 1) / h->qps_per_wg;
+    if (batch <= h->workgroups) grid = batch;
+    if (grid > h->workgroups) grid = h->workgroups;
+    int N = L.N;
+    void* args[] = {&d, &aa, &h->scratch, &h->counter, &batch, &N};
+    HIP_TRY(hipEventRecord(h->ev0, s));
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)h->lds_bytes, s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev1, s));
+    h->timed = true;
+    HIP_TRY(hipStreamSynchronize(s));
+    return FBSTAB_HIP_OK;
+  }
+  // per step: the image of one step (every sequence), the seed vectors, lambda / mu, A'mu, the step's status
+  long long img = 0;
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) img += h->arr_len[i];
+  const long long per_qp = img + nz + 2 * L.nx + 1;  // (+ the status word, in a double's place)
+  if (!h->sweep_tmp) HIP_TRY(hipMalloc(&h->sweep_tmp, sizeof(double) * (size_t)per_qp * (size_t)h->max_batch));
+  SweepCostateArgs ca;
+  AdjointStage st;
+  double* w = h->sweep_tmp;
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
+    const bool wanted = grad->base[i] != nullptr || i == FBSTAB_MPC_x0;
+    ca.grad[i] = grad->base[i]; ca.gstride[i] = grad->stride[i];
+    ca.len[i] = h->arr_len[i];
+    ca.tmp[i] = wanted ? w : nullptr;
+    st.a_base[i] = a_base[i]; st.a_stride[i] = a_stride[i];
+    st.g_base[i] = wanted ? w : nullptr; st.g_stride[i] = h->arr_len[i];
+    w += h->arr_len[i] * h->max_batch;
+  }
+  ca.seed = w; w += nz * h->max_batch;
+  ca.lam = w; w += (long long)L.nx * h->max_batch;
+  ca.atm = w; w += (long long)L.nx * h->max_batch;
+  int* tmp_status = reinterpret_cast<int*>(w);
+  ca.tmp_status = tmp_status;
+  ca.status = status;
+  ca.A = plant->A; ca.B = plant->B; ca.sA = plant->stride_A; ca.sB = plant->stride_B;
+  ca.nx = L.nx; ca.nu = L.nu; ca.nz = L.nz;
+  ca.eflag = nullptr; ca.gu = ca.gx = nullptr; ca.mu_log = nullptr;
+  for (int i = 0; i < 4; i++) {
+    st.v.base[i] = st.sd.base[i] = st.ad.base[i] = nullptr;
+    st.v.stride[i] = st.sd.stride[i] = st.ad.stride[i] = 0;
+  }
+  st.sd.base[0] = ca.seed; st.sd.stride[0] = nz;
+  st.d_st = tmp_status;
+  st.s = s;
+  hipLaunchKernelGGL(fbstab_sweep_costate_kernel, dim3(batch), dim3(64), 0, s, ca, 0, 0);
+  HIP_TRY(hipGetLastError());
+  for (int k = steps - 1; k >= 0; k--) {
+    const long long kb = (long long)k * batch;
+    ca.eflag = log->eflag + kb;
+    ca.gu = gu ? gu + kb * L.nu : nullptr;
+    ca.gx = gx ? gx + kb * L.nx : nullptr;
+    ca.mu_log = mu_log ? mu_log + kb * L.nx : nullptr;
+    hipLaunchKernelGGL(fbstab_sweep_costate_kernel, dim3(batch), dim3(64), 0, s, ca, 1, 0);
+    HIP_TRY(hipGetLastError());
+    st.v.base[0] = log->z + kb * nz; st.v.stride[0] = nz;
+    st.v.base[1] = log->l + kb * nl; st.v.stride[1] = nl;
+    st.v.base[2] = log->v + kb * nv; st.v.stride[2] = nv;
+    int rc = mpc_adjoint_launch(h, batch, st, sig);
+    if (rc != FBSTAB_HIP_OK) return rc;
+    hipLaunchKernelGGL(fbstab_sweep_costate_kernel, dim3(batch), dim3(64), 0, s, ca, 2, k == 0 ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  return FBSTAB_HIP_OK;
+}
+
+// Name of what the next fbstab_hip_mpc_receding_sweep_adjoint of this handle launches (diagnostics, tests, tools).
+const char* fbstab_hip_mpc_sweep_adjoint_kernel_name(fbstab_mpc_handle_t h) {
+  if (!h) return "";
+  return sweep_adjoint_in_one_launch(h) ? h->rec->sweep_adjoint_name : "fbstab_sweep_costate_kernel";
 }
 
 // Forward-mode derivative of the solution map (include/fbstab_hip.h): fbstab_tangent_rhs_kernel forms the seeds

@@ -93,6 +93,10 @@ class _Plant(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("stride_A", C.c_longlong), ("stride_B", C.c_longlong)]
 
 
+class _SweepLog(C.Structure):
+    _fields_ = [("z", C.c_void_p), ("l", C.c_void_p), ("v", C.c_void_p), ("x0", C.c_void_p), ("eflag", C.c_void_p)]
+
+
 _libs: Dict[str, C.CDLL] = {}
 _current = LIB_PATH  # the library new solver objects bind to (see `library`)
 
@@ -181,6 +185,13 @@ def load_library() -> C.CDLL:
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_receding_sweep_logged"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_receding_sweep_logged.argtypes = lib.fbstab_hip_mpc_receding_sweep.argtypes + [C.c_void_p]
+        lib.fbstab_hip_mpc_receding_sweep_adjoint.argtypes = [
+            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.fbstab_hip_mpc_sweep_adjoint_kernel_name.restype = C.c_char_p
+        lib.fbstab_hip_mpc_sweep_adjoint_kernel_name.argtypes = [C.c_void_p]
     lib.fbstab_hip_shard_group_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     lib.fbstab_hip_shard_group_destroy.argtypes = [C.c_void_p]
     lib.fbstab_hip_shard_group_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -207,6 +218,8 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_refined_steps", "fbstab_hip_mpc_create_in_flight",
     "fbstab_hip_mpc_debug_newton", "fbstab_hip_mpc_adjoint_batch", "fbstab_hip_mpc_adjoint_kernel_name",
     "fbstab_hip_mpc_adjoint_batch_reduced", "fbstab_hip_mpc_tangent_batch", "fbstab_hip_debug_stamps",
+    "fbstab_hip_mpc_receding_sweep_logged", "fbstab_hip_mpc_receding_sweep_adjoint",
+    "fbstab_hip_mpc_sweep_adjoint_kernel_name",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",
     "fbstab_hip_dense_solve_traced", "fbstab_hip_dense_adjoint_batch",
@@ -604,14 +617,32 @@ class FBstabMpcBatch(_SolverBase):
         return _solve_traced(self, _MpcBatch(), MPC_SEQ, self.seq_len, data,
                              (self.nz, self.nl, self.nv, self.nv), z, l, v, y, capacity)
 
+    def sweep_adjoint_kernel_name(self) -> str:
+        """What the next RecedingSweepAdjoint call launches (fbstab_hip_mpc_sweep_adjoint_kernel_name)."""
+        return self._lib.fbstab_hip_mpc_sweep_adjoint_kernel_name(self._h).decode()
+
+    @staticmethod
+    def _plant(A, B, dev):
+        """(struct, tensors to keep alive): the column-major images of one plant shared by all trajectories, from
+        ``(nx, nx)`` / ``(nx, nu)`` row-major numpy arrays or torch tensors."""
+        import torch
+        img = lambda M: (M.detach().to(dev, torch.float64).t() if _is_torch(M)
+                         else torch.from_numpy(np.ascontiguousarray(np.asarray(M, dtype=np.float64))).to(dev).t()
+                         ).contiguous().reshape(-1)
+        Ad, Bd = img(A), img(B)
+        return _Plant(Ad.data_ptr(), Bd.data_ptr(), 0, 0), (Ad, Bd)
+
     def RecedingSweep(self, data, z, l, v, y, A, B, steps: int, retire: bool = True,
-                      log_inputs: bool = False, stream: int = 0):
+                      log_inputs: bool = False, stream: int = 0, log: bool = False):
         """fbstab_hip_mpc_receding_sweep: ``steps`` warm-started closed-loop steps on
         the device (torch CUDA tensors; ``data["x0"]`` is advanced in place, ``z, l,
         v, y`` hold the last solution).  ``A``/``B``: the simulation model as
         ``(nx, nx)``/``(nx, nu)`` numpy arrays shared by all trajectories.  Returns
         ``dict(out, stats, kernel_ms[, u])`` with ``stats`` a structured array per
-        step (newton_sum, success, retired_total, newton_max)."""
+        step (newton_sum, success, retired_total, newton_max).  ``log=True``
+        (fbstab_hip_mpc_receding_sweep_logged) adds what RecedingSweepAdjoint needs, per step: ``z_log, l_log,
+        v_log`` ``(steps, batch, n)`` - the point the step returned -, ``x_log`` ``(steps, batch, nx)`` - the state
+        it was solved for - and ``eflag_log`` ``(steps, batch)`` int32, -1 once a trajectory is retired."""
         import torch
         b = _MpcBatch()
         B_ = None
@@ -626,19 +657,25 @@ class FBstabMpcBatch(_SolverBase):
             assert d and a.shape[0] == B_
             vb.base[i], vb.stride[i] = p, st
         dev = z.device
-        Ad = torch.from_numpy(np.asfortranarray(A).T.copy().reshape(-1)).to(dev)   # column-major image
-        Bd = torch.from_numpy(np.asfortranarray(B).T.copy().reshape(-1)).to(dev)
-        plant = _Plant(Ad.data_ptr(), Bd.data_ptr(), 0, 0)
+        plant, plant_keep = self._plant(A, B, dev)   # column-major images
         out = torch.zeros((B_, 40), dtype=torch.uint8, device=dev)
         stats = np.zeros((steps, 4), dtype=np.uint64)
         kms = np.zeros(steps, dtype=np.float32)
         u = torch.zeros((steps, B_, self.nu), dtype=torch.float64, device=dev) if log_inputs else None
         if not stream:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(self._lib, self._lib.fbstab_hip_mpc_receding_sweep(
-            self._h, B_, C.byref(b), C.byref(vb), out.data_ptr(), C.byref(plant), steps, 1 if retire else 0,
-            u.data_ptr() if u is not None else None, stats.ctypes.data, kms.ctypes.data,
-            C.c_void_p(stream) if stream else None))
+        args = [self._h, B_, C.byref(b), C.byref(vb), out.data_ptr(), C.byref(plant), steps, 1 if retire else 0,
+                u.data_ptr() if u is not None else None, stats.ctypes.data, kms.ctypes.data,
+                C.c_void_p(stream) if stream else None]
+        logs = {}
+        if log:
+            for k, n in (("z_log", self.nz), ("l_log", self.nl), ("v_log", self.nv), ("x_log", self.nx)):
+                logs[k] = torch.zeros((steps, B_, n), dtype=torch.float64, device=dev)
+            logs["eflag_log"] = torch.zeros((steps, B_), dtype=torch.int32, device=dev)
+            lg = _SweepLog(*[logs[k].data_ptr() for k in ("z_log", "l_log", "v_log", "x_log", "eflag_log")])
+            _check(self._lib, self._lib.fbstab_hip_mpc_receding_sweep_logged(*args, C.byref(lg)))
+        else:
+            _check(self._lib, self._lib.fbstab_hip_mpc_receding_sweep(*args))
         st = np.zeros(steps, dtype=[("newton_sum", np.int64), ("success", np.int64),
                                     ("retired_total", np.int64), ("newton_max", np.int64)])
         for j, n in enumerate(st.dtype.names):
@@ -646,7 +683,71 @@ class FBstabMpcBatch(_SolverBase):
         r = dict(out=out, stats=st, kernel_ms=kms)
         if u is not None:
             r["u"] = u
+        r.update(logs)
         return r
+
+    def RecedingSweepAdjoint(self, data, A, B, steps: int, log, gu=None, gx=None, retire: bool = True,
+                             sigma: float = 0.0, want: Optional[Sequence[str]] = None, mu: bool = False,
+                             stream: int = 0) -> Dict[str, object]:
+        """Reverse mode through a logged sweep (fbstab_hip_mpc_receding_sweep_adjoint): ``log`` is what
+        ``RecedingSweep(..., log=True)`` returned (its ``z_log, l_log, v_log, eflag_log``), ``gu`` ``(steps, batch,
+        nu)`` = dL/du_k and ``gx`` ``(steps, batch, nx)`` = dL/dx_(k+1) the seeds (None: zero), ``A``/``B`` the plant
+        as in ``RecedingSweep`` (numpy or torch).  Torch CUDA tensors only.  Returns a dict with dL/d(sequence),
+        ``(batch, len)``, for every name of ``want`` (default: all 12 of MPC_SEQ; ``"x0"`` is dL/dx_0 of the
+        trajectory, every other one the sum over the steps), ``"status"`` (``(batch,)`` int32: steps whose
+        factorisation failed) and, with ``mu=True``, ``"mu"`` ``(steps, batch, nx)``: the costates from which the
+        plant's own gradients follow, ``A_bar = einsum("kbi,kbj->ij", mu, x_log)`` and ``B_bar`` likewise with u.
+        ``data["x0"]`` is not read."""
+        import torch
+        want = tuple(MPC_SEQ if want is None else want)
+        assert not set(want) - set(MPC_SEQ), want
+        zl = log["z_log"]
+        dev, B_ = zl.device, zl.shape[1]
+        assert zl.is_cuda and zl.shape == (steps, B_, self.nz), "the log of RecedingSweep(..., log=True) on the device"
+        b = _MpcBatch()
+        for i, (k, n) in enumerate(zip(MPC_SEQ, self.seq_len)):
+            if k == "x0":
+                b.base[i], b.stride[i] = None, 0
+                continue
+            p, st, d = _ptr_stride(data[k], n)
+            assert d, "device tensors only"
+            b.base[i], b.stride[i] = p, _shared_stride(data[k], st, B_)
+        keep = []
+
+        def arr(a, shape, dt):
+            if a is None:
+                return None
+            assert a.is_cuda and a.dtype == dt and tuple(a.shape) == shape, (tuple(a.shape), shape)
+            a = a.contiguous()
+            keep.append(a)
+            return a.data_ptr()
+
+        lg = _SweepLog(arr(log["z_log"], (steps, B_, self.nz), torch.float64),
+                       arr(log["l_log"], (steps, B_, self.nl), torch.float64),
+                       arr(log["v_log"], (steps, B_, self.nv), torch.float64), None,
+                       arr(log["eflag_log"], (steps, B_), torch.int32))
+        plant, plant_keep = self._plant(A, B, dev)
+        res = {}
+        g = _MpcGradBatch()
+        for i, (k, n) in enumerate(zip(MPC_SEQ, self.seq_len)):
+            g.base[i], g.stride[i] = None, 0
+            if k in want:
+                res[k] = torch.zeros((B_, n), dtype=torch.float64, device=dev)
+                g.base[i], g.stride[i] = res[k].data_ptr(), n
+        status = torch.zeros(B_, dtype=torch.int32, device=dev)
+        mu_log = torch.zeros((steps, B_, self.nx), dtype=torch.float64, device=dev) if mu else None
+        if not stream:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(self._lib, self._lib.fbstab_hip_mpc_receding_sweep_adjoint(
+            self._h, B_, C.byref(b), C.byref(plant), steps, 1 if retire else 0, C.byref(lg),
+            arr(gu, (steps, B_, self.nu), torch.float64), arr(gx, (steps, B_, self.nx), torch.float64),
+            C.c_double(sigma), C.byref(g), mu_log.data_ptr() if mu else None, status.data_ptr(),
+            C.c_void_p(stream) if stream else None))
+        del plant_keep
+        res["status"] = status
+        if mu:
+            res["mu"] = mu_log
+        return res
 
 
     def debug_newton(self, data, z, l, v, zb, lb, vb):

@@ -356,6 +356,58 @@ int fbstab_hip_mpc_adjoint_batch_reduced(fbstab_mpc_handle_t handle, int batch, 
                                          const fbstab_var_batch_t* adj, int* status,
                                          const fbstab_solver_out_t* out, int flags, void* stream);
 
+/* ---- the closed loop's derivative: a logged sweep and its adjoint through time ------------------------------
+ * fbstab_hip_mpc_receding_sweep_logged is fbstab_hip_mpc_receding_sweep (same arguments, same results bit for
+ * bit; log == NULL is that function) that also records what the backward pass needs, per step k and trajectory:
+ * the point (z_k, l_k, v_k) the step returned, the state x_k it was solved for and its eflag.  All DEVICE
+ * arrays; a NULL slot is not logged.  A retired trajectory (retire != 0) logs a zero point and eflag -1 at and
+ * after its retirement step.  The one-launch and the per-step form log bitwise-equal arrays.  Footprint:
+ * steps x batch x (nz + nl + nv + nx) doubles - 9.8 GB for 4096 trajectories x 200 steps at (N, nx, nu, nc) =
+ * (30, 12, 4, 20). */
+typedef struct fbstab_sweep_log_t {
+  double *z, *l, *v;   /* [steps][batch][nz | nl | nv] */
+  double* x0;          /* [steps][batch][nx]: x_k */
+  int* eflag;          /* [steps][batch]; -1 once the trajectory is retired */
+} fbstab_sweep_log_t;
+int fbstab_hip_mpc_receding_sweep_logged(fbstab_mpc_handle_t handle, int batch, const fbstab_mpc_batch_t* data,
+                                         const fbstab_var_batch_t* x, fbstab_solver_out_t* out,
+                                         const fbstab_receding_plant_t* plant, int steps, int retire,
+                                         double* u_log, unsigned long long* stats, float* kernel_ms,
+                                         void* stream, const fbstab_sweep_log_t* log);
+
+/* Reverse mode through the sweep.  With u_k = entries [nx, nx + nu) of z_k and x_(k+1) = A x_k + B u_k, the seeds
+ * gu[k] = dL/du_k ([steps][batch][nu]) and gx[k] = dL/dx_(k+1) ([steps][batch][nx]; either may be NULL: zero) are
+ * taken backwards along every trajectory.  Start with lambda = 0 and for k = steps-1 .. 0:
+ *   mu = gx[k] + lambda                             (mu_log[k] = mu where mu_log is given)
+ *   eflag_log[k] == -1 (retired):       lambda <- 0
+ *   eflag_log[k] != FBSTAB_SUCCESS:     lambda <- A'mu          (the point is no solution: u_k is a constant)
+ *   otherwise one adjoint (fbstab_hip_mpc_adjoint_batch's, same sigma rule) at the logged point with the seed
+ *   gu[k] + B'mu on the u0 entries of z and zero elsewhere:
+ *     factorisation failed:             status += 1, lambda <- A'mu
+ *     else every wanted sequence's gradient += that adjoint's gradient table, lambda <- A'mu - dl[0:nx].
+ * The x0 slot of `grad` receives the final lambda = dL/dx_0 (not a sum over the steps); every other slot is the
+ * sum over the steps, added last step first without atomics (the same inputs give the same bits).  The plant's
+ * own gradients are left to the caller: A_bar = sum_k mu_k x_k', B_bar = sum_k mu_k u_k' from mu_log and the logs.
+ * All pointers are DEVICE pointers.  Every non-NULL grad slot is written (zeros for a trajectory without a
+ * contributing step) and needs stride >= length when batch > 1 (stride 0 is FBSTAB_HIP_ERR_ARGUMENT: sums over
+ * the batch are the caller's).  data->base[FBSTAB_MPC_x0] is not read.  log->z, l, v and eflag are required.
+ * status: [batch], the number of steps whose factorisation failed.
+ * Handles whose fbstab_hip_mpc_adjoint_kernel_name is a record adjoint run ONE launch of
+ * fbstab_mpc_r16_sweep_adjoint_kernel, every row (pair) taking a trajectory through all its steps; it needs
+ * rows x nz doubles for the seed vectors, allocated at the first call and held until destroy.  Every other
+ * handle, and every handle with FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP=1 in the environment of the call, queues per
+ * step fbstab_sweep_costate_kernel, the handle's adjoint launch into a per-QP image of the handle's own
+ * (max_batch x (all 12 sequences + nz + 2 nx) doubles, allocated at the first call) and the costate kernel again.
+ * fbstab_hip_mpc_sweep_adjoint_kernel_name names what the next call launches.  Synchronous.
+ * Not served: gradients summed over the batch, forward mode through the sweep, seeds on the rest of z_k, l_k,
+ * v_k. */
+int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t handle, int batch, const fbstab_mpc_batch_t* data,
+                                          const fbstab_receding_plant_t* plant, int steps, int retire,
+                                          const fbstab_sweep_log_t* log, const double* gu, const double* gx,
+                                          double sigma, const fbstab_mpc_grad_batch_t* grad, double* mu_log,
+                                          int* status, void* stream);
+const char* fbstab_hip_mpc_sweep_adjoint_kernel_name(fbstab_mpc_handle_t handle);
+
 /* Forward mode of the same derivative: the tangent (dz, dl, dv) = J dtheta of the solutions for a perturbation
  * dtheta of the problem data - the first-order update of a plan when the state or a forecast moves (a warm start
  * for the next solve), a column of the feedback gain du0/dx0 per unit direction dx0, a disturbance direction

@@ -8,6 +8,7 @@ usage: python tools/adjoint_bench.py [--batch 8192] [--reps 5] [--generic]
        python tools/adjoint_bench.py --wide [--reps 5]
        python tools/adjoint_bench.py --reduced [--reps 5]
        python tools/adjoint_bench.py --tangent [--dense] [--reps 5]
+       python tools/adjoint_bench.py --sweep [--batch 4096] [--steps 50] [--reps 5]
 --generic: FBSTAB_HIP_GENERIC=1, forward and adjoint on the flat-vector kernels (default: the record instance
 <12,4,20> and its own adjoint).
 --dense: fbstab_hip_dense_adjoint_batch against fbstab_hip_dense_solve_batch on BASELINE configs[1] instead: 4096
@@ -33,7 +34,14 @@ configs[1] (4096 dense QPs), each way in a fresh process, the median of --reps l
   (c) the direction kernel alone: (b)'s call minus its adjoint kernel's launch - an upper bound, the queue reset
       and the launch gaps are in it - and the bytes it reads and writes over that time.
 `not_slower`: (b) <= (a)'s kernel + the spread of (a)'s launches.  One JSON line (profiles/tangent_bench.json) with
-the library's sha256."""
+the library's sha256.
+--sweep: the closed loop's derivative on BASELINE configs[4]'s shape, 4096 trajectories x 50 steps in one process, the
+four calls interleaved launch by launch: the unlogged sweep, the logged sweep (fbstab_hip_mpc_receding_sweep_logged),
+the one-launch backward of that log (fbstab_mpc_r16_sweep_adjoint_kernel, all twelve slots wanted and mu_log) and the
+per-step backward of the same log (FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP=1).  Wall time of each (synchronous) call, the
+median of --reps launches after one that warms the code objects and the handle's buffers.  One JSON line
+(profiles/sweep_adjoint_bench.json) with the library's sha256; `one_launch_faster`: the one-launch median is below
+the per-step median by more than the larger spread of the two."""
 import argparse
 import hashlib
 import json
@@ -361,6 +369,68 @@ def tangent(dense_, reps):
         "success": a["success"]}))
 
 
+def sweep(batch, steps, reps):
+    import time
+    import torch
+    from tools import fixtures as fx
+    from fbstab_amd import hip_api
+    dev = torch.device("cuda:0")
+    with open(hip_api.current_library_path(), "rb") as f:
+        sha = hashlib.sha256(f.read()).hexdigest()
+    p = fx.synthetic_mpc_batch(batch)
+    A, B = fx.quadrotor_model()
+    host = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in p.arrays.items()}
+    data = {k: t.to(dev) for k, t in host.items()}
+    s = hip_api.FBstabMpcBatch(*p.sizes(), max_batch=batch)
+    zeros = lambda n: torch.zeros((batch, n), dtype=torch.float64, device=dev)
+    rng = np.random.default_rng(0)
+    gu = torch.from_numpy(rng.standard_normal((steps, batch, p.nu))).to(dev)
+    gx = torch.from_numpy(rng.standard_normal((steps, batch, p.nx))).to(dev)
+    t = {"sweep": [], "sweep_logged": [], "adjoint_one_launch": [], "adjoint_per_step": []}
+    names, checks = {}, {}
+
+    def timed(key, fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        t[key].append((time.perf_counter() - t0) * 1e3)
+        return r
+
+    def forward(log):
+        data["x0"].copy_(host["x0"])
+        z, l, v, y = zeros(p.nz), zeros(p.nl), zeros(p.nv), zeros(p.nv)
+        return timed("sweep_logged" if log else "sweep",
+                     lambda: s.RecedingSweep(data, z, l, v, y, A, B, steps, retire=True, log=log))
+
+    for _ in range(reps + 1):
+        plain = forward(False)
+        r = forward(True)
+        for key, env in (("adjoint_one_launch", "0"), ("adjoint_per_step", "1")):
+            os.environ["FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP"] = env
+            names[key] = s.sweep_adjoint_kernel_name()
+            g = timed(key, lambda: s.RecedingSweepAdjoint(data, A, B, steps, r, gu=gu, gx=gx, mu=True))
+            checks[key] = [float(g["q"].abs().sum().item()), float(g["x0"].abs().sum().item()),
+                           int((g["status"] != 0).sum().item())]
+            del g
+    os.environ.pop("FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP")
+    t = {k: v[1:] for k, v in t.items()}
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    spread = {k: max(v) - min(v) for k, v in t.items()}
+    a, b = "adjoint_one_launch", "adjoint_per_step"
+    log_doubles = steps * batch * (p.nz + p.nl + p.nv + p.nx)
+    print(json.dumps({
+        "library_sha256": sha, "launches_timed": reps, "workload": "BASELINE configs[4] shape", "batch": batch,
+        "steps": steps, "forward_kernel": s.kernel_name(), "kernels": names,
+        "ms": {k: round(v, 3) for k, v in med.items()}, "ms_all": {k: [round(x, 3) for x in v] for k, v in t.items()},
+        "spread_ms": {k: round(v, 3) for k, v in spread.items()},
+        "logged_over_unlogged": round(med["sweep_logged"] / med["sweep"], 4),
+        "one_launch_over_per_step": round(med[a] / med[b], 4),
+        "one_launch_faster": med[a] + max(spread[a], spread[b]) < med[b],
+        "log_bytes": 8 * log_doubles, "retired": int(r["stats"]["retired_total"][-1]),
+        "success_last_step": int(r["stats"]["success"][-1]), "abs_sum_q_x0_status_nonzero": checks}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=None)
@@ -373,7 +443,11 @@ def main():
     ap.add_argument("--reduced-child", nargs=2, help=argparse.SUPPRESS)
     ap.add_argument("--tangent", action="store_true")
     ap.add_argument("--tangent-child", choices=TANGENT_WAYS, help=argparse.SUPPRESS)
+    ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--steps", type=int, default=50)
     a = ap.parse_args()
+    if a.sweep:
+        return sweep(a.batch or 4096, a.steps, a.reps)
     if a.tangent_child:
         return tangent_child(a.tangent_child, a.dense, a.reps)
     if a.tangent:
