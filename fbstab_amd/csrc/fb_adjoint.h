@@ -10,15 +10,11 @@
 // (Q and R get the gradient of their symmetric part: the reference assumes symmetric blocks.)
 #pragma once
 
-#include "fb_common.h"
+#include "fb_batch.h"
 
 namespace fbk {
 
-// Pointers to one QP's gradients of the 12 sequences (the order of fbstab_mpc_batch_t; nullptr: not wanted).
-struct MpcGrad {
-  double *Q, *R, *S, *q, *r, *A, *B, *c, *E, *L, *d, *x0;
-};
-
+// (MpcGrad, DenseGrad: fb_batch.h)
 // Every slot of G that is not null is written; ok = false writes zeros there, and to (az, al, av) where they are
 // not null (which otherwise receive dz, dl, dv).  Threads c.tid, c.tid + C::nt, ... of every sequence; the
 // caller synchronises before and after.  ACC (fbstab_mpc_r16_sweep_adjoint_kernel): the slots of G are ADDED to
@@ -110,10 +106,6 @@ FB_DEV void mpc_adjoint_contract(const C& c, int N, int nx, int nu, int nc, cons
 //   f: -dz      h: dl      b: dv
 //   H: -(dz z' + z dz')/2 (the gradient of the symmetric part)      G: -(dl z' + l dz')      A: -(dv z' + v dz')
 // column-major like the inputs (H_bar[r + c nz], G_bar[r + c nl], A_bar[r + c nv]).
-// Pointers to one QP's gradients of the six arrays (the order of fbstab_dense_batch_t; nullptr: not wanted).
-struct DenseGrad {
-  double *H, *f, *G, *h, *A, *b;
-};
 
 // out[r + k m] = s (a[r] z[k] + w[r] dz[k]), r < m, k < nz: thread c.tid takes entries c.tid, c.tid + C::nt, ...
 // of the column-major image, so that a wavefront's stores are one contiguous run; (r, k) follow the entry

@@ -28,10 +28,6 @@
 
 namespace fbk {
 
-struct DenseData {
-  const double *H, *f, *G, *h, *A, *b;
-};
-
 struct DenseLayout {
   int nz, nl, nv, nk;
   // LDS carve (offsets in doubles)

@@ -15,7 +15,9 @@
 #pragma once
 
 #include "../../include/fbstab_hip.h"
-#include "fb_common.h"
+#include <stddef.h>
+
+#include "fb_batch.h"
 
 namespace fbk {
 
@@ -27,12 +29,11 @@ FB_DEV double wave_sum(double x) {
 }
 
 struct MpcNormArgs {
-  const double* base[12];  // Q R S q r A B c E L d x0 (FBSTAB_MPC_*)
-  long long stride[12];
-  const double* x[4];      // z l v y
-  long long xstride[4];
+  fbstab_mpc_batch_t data;
+  fbstab_var_batch_t x;  // (read only)
   int N, nx, nu, nc;
 };
+static_assert(offsetof(MpcNormArgs, x) == 192 && offsetof(MpcNormArgs, N) == 256, "MpcNormArgs: the blocks, then N");
 
 // norms[4 q ..] = {|rz|, |rl|, |rv|, tolerance}; one 64-thread workgroup per QP.
 // rz = H z + f + G'l + A'v, rl = h - G z, rv = alpha min(y, v) + (1 - alpha) max(0, y) max(0, v)
@@ -42,14 +43,10 @@ __global__ __launch_bounds__(64) void fbstab_mpc_final_norms_kernel(MpcNormArgs 
   const long q = blockIdx.x;
   if (q >= batch) return;
   const int t = threadIdx.x, N = a.N, nx = a.nx, nu = a.nu, nc = a.nc, ns = nx + nu;
-  const double *Q = a.base[FBSTAB_MPC_Q] + q * a.stride[FBSTAB_MPC_Q], *R = a.base[FBSTAB_MPC_R] + q * a.stride[FBSTAB_MPC_R],
-               *S = a.base[FBSTAB_MPC_S] + q * a.stride[FBSTAB_MPC_S], *pq = a.base[FBSTAB_MPC_q] + q * a.stride[FBSTAB_MPC_q],
-               *pr = a.base[FBSTAB_MPC_r] + q * a.stride[FBSTAB_MPC_r], *A = a.base[FBSTAB_MPC_A] + q * a.stride[FBSTAB_MPC_A],
-               *B = a.base[FBSTAB_MPC_B] + q * a.stride[FBSTAB_MPC_B], *pc = a.base[FBSTAB_MPC_c] + q * a.stride[FBSTAB_MPC_c],
-               *E = a.base[FBSTAB_MPC_E] + q * a.stride[FBSTAB_MPC_E], *L = a.base[FBSTAB_MPC_L] + q * a.stride[FBSTAB_MPC_L],
-               *pd = a.base[FBSTAB_MPC_d] + q * a.stride[FBSTAB_MPC_d], *px0 = a.base[FBSTAB_MPC_x0] + q * a.stride[FBSTAB_MPC_x0];
-  const double *z = a.x[0] + q * a.xstride[0], *l = a.x[1] + q * a.xstride[1], *v = a.x[2] + q * a.xstride[2],
-               *y = a.x[3] + q * a.xstride[3];
+  const MpcData D = mpc_data_at(a.data, q);
+  const double *Q = D.Q, *R = D.R, *S = D.S, *pq = D.q, *pr = D.r, *A = D.A, *B = D.B, *pc = D.c, *E = D.E, *L = D.L,
+               *pd = D.d, *px0 = D.x0;
+  const double *z = var_at(a.x, 0, q), *l = var_at(a.x, 1, q), *v = var_at(a.x, 2, q), *y = var_at(a.x, 3, q);
   double sz = 0.0, sl = 0.0, sv = 0.0, sw = 0.0;
   for (int i = 0; i <= N; i++) {
     const double *zi = z + (long)i * ns, *li = l + (long)i * nx, *vi = v + (long)i * nc;
@@ -122,12 +119,11 @@ __global__ __launch_bounds__(64) void fbstab_mpc_final_norms_kernel(MpcNormArgs 
 }
 
 struct DenseNormArgs {
-  const double* base[6];  // H f G h A b (FBSTAB_DENSE_*)
-  long long stride[6];
-  const double* x[4];
-  long long xstride[4];
+  fbstab_dense_batch_t data;
+  fbstab_var_batch_t x;  // (read only)
   int nz, nl, nv;
 };
+static_assert(offsetof(DenseNormArgs, x) == 96 && offsetof(DenseNormArgs, nz) == 160, "DenseNormArgs: the blocks, then nz");
 
 // The dense analogue (dense_data.cc:12-41): column-major H (nz x nz), G (nl x nz), A (nv x nz).
 __global__ __launch_bounds__(64) void fbstab_dense_final_norms_kernel(DenseNormArgs a, fbstab_options_t opts,
@@ -135,11 +131,9 @@ __global__ __launch_bounds__(64) void fbstab_dense_final_norms_kernel(DenseNormA
   const long q = blockIdx.x;
   if (q >= batch) return;
   const int t = threadIdx.x, nz = a.nz, nl = a.nl, nv = a.nv;
-  const double *H = a.base[FBSTAB_DENSE_H] + q * a.stride[FBSTAB_DENSE_H], *f = a.base[FBSTAB_DENSE_f] + q * a.stride[FBSTAB_DENSE_f],
-               *G = a.base[FBSTAB_DENSE_G] + q * a.stride[FBSTAB_DENSE_G], *h = a.base[FBSTAB_DENSE_h] + q * a.stride[FBSTAB_DENSE_h],
-               *A = a.base[FBSTAB_DENSE_A] + q * a.stride[FBSTAB_DENSE_A], *b = a.base[FBSTAB_DENSE_b] + q * a.stride[FBSTAB_DENSE_b];
-  const double *z = a.x[0] + q * a.xstride[0], *l = a.x[1] + q * a.xstride[1], *v = a.x[2] + q * a.xstride[2],
-               *y = a.x[3] + q * a.xstride[3];
+  const DenseData D = dense_data_at(a.data, q);
+  const double *H = D.H, *f = D.f, *G = D.G, *h = D.h, *A = D.A, *b = D.b;
+  const double *z = var_at(a.x, 0, q), *l = var_at(a.x, 1, q), *v = var_at(a.x, 2, q), *y = var_at(a.x, 3, q);
   double sz = 0.0, sl = 0.0, sv = 0.0, sw = 0.0;
   for (int r = t; r < nz; r += 64) {
     double acc = f[r];

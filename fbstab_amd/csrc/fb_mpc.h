@@ -36,11 +36,6 @@
 
 namespace fbk {
 
-// Pointers to one QP's problem data (already offset to that QP).
-struct MpcData {
-  const double *Q, *R, *S, *q, *r, *A, *B, *c, *E, *L, *d, *x0;
-};
-
 // Sizes and derived offsets, identical on host (workspace sizing) and device.
 struct MpcLayout {
   int N, nx, nu, nc, ns, nz, nl, nv;

@@ -39,21 +39,24 @@
 //     [A B]'dl and the row triangle of inv(Lc) instead of reading W by columns.
 #pragma once
 
+#include <stddef.h>
+
+#include "fb_batch.h"
 #include "fb_row16.h"
 
 namespace fbk {
 
 
-// Batch descriptors as the kernel receives them (one base + stride per array).
+// The problem data as the record kernels receive them: the caller's block and the problem's own sizes.
 struct MpcBatchPtrs {
-  const double* base[12];
-  long long stride[12];
+  fbstab_mpc_batch_t seq;
   int nx, nu, nc;  // the problem's own sizes (<= the kernel instance's)
 };
-struct VarBatchPtrs {
-  double* base[4];
-  long long stride[4];
-};
+// (kernel-argument offsets are part of the instruction stream)
+static_assert(offsetof(MpcBatchPtrs, seq.base) == 0 && offsetof(MpcBatchPtrs, seq.stride) == 96 &&
+                  offsetof(MpcBatchPtrs, nx) == 192 && offsetof(MpcBatchPtrs, nu) == 196 &&
+                  offsetof(MpcBatchPtrs, nc) == 200 && sizeof(MpcBatchPtrs) == 208,
+              "MpcBatchPtrs: base[12], stride[12], nx, nu, nc");
 
 // EXACT: the problem has exactly the instance's shape (compile-time strides in
 // the passes over the caller's arrays); otherwise it may be smaller and runs
@@ -402,7 +405,7 @@ struct MpcR16 {
   lds_ptr lds;  // this QP's own LDS region (transpose buffer / triangle images, parked scalars)
   lds_ptr lpk;  // this QP's image in the wavefront's matrix-copy area (its lanes' offsets not included)
   const MpcBatchPtrs* data;  // kernel arguments (uniform)
-  const VarBatchPtrs* var;
+  const fbstab_var_batch_t* var;
   long q;  // QP index
   int N;
   // The problem's own sizes, nx <= NX, nu <= NU, nc <= NC: a smaller problem runs
@@ -420,7 +423,7 @@ struct MpcR16 {
   double pend_t;
 
   FB_DEV void bind(double* ws_row, lds_ptr lds_row, lds_ptr lpk_row, lds_iptr lpo_row, const MpcBatchPtrs* d,
-                   const VarBatchPtrs* x, long q_, int N_, int lane) {
+                   const fbstab_var_batch_t* x, long q_, int N_, int lane) {
     lpk = lpk_row;
     lds_off = -1;
     poff = reinterpret_cast<int*>(ws_row);
@@ -589,8 +592,8 @@ struct MpcR16 {
   }
 
   // ---- pointers into the caller's arrays ----------------------------------------
-  FB_DEV const double* arr(int a) const { return data->base[a] + q * data->stride[a]; }
-  FB_DEV double* xarr(int a) const { return var->base[a] + q * var->stride[a]; }
+  FB_DEV const double* arr(int a) const { return slot_at(data->seq.base[a], data->seq.stride[a], q); }
+  FB_DEV double* xarr(int a) const { return var_at(*var, a, q); }
 
   // ||(f,h,b)||_2 (mpc_data.h:88-97).
   FB_DEV double forcing_norm(const C& c) const {
@@ -1749,7 +1752,7 @@ struct MpcR16 {
   };
   static __device__ __attribute__((noinline)) LoadSums load_pass_coop(double* R0, double* P0, int* pog, lds_iptr lp,
                                                                       lds_ptr Cl, const MpcBatchPtrs* data,
-                                                                      const VarBatchPtrs* var, long qp, int N_,
+                                                                      const fbstab_var_batch_t* var, long qp, int N_,
                                                                       int nx_, int nu_, int nc_) {
     constexpr int QW = kQpPerWave;
     const int lane = threadIdx.x & 63;
@@ -1758,12 +1761,11 @@ struct MpcR16 {
     const bool rx = r < nx_;
     const bool rin = r >= NX && ru < nu_;
     const bool rs_ = rx || rin;
-    auto arr_ = [&](int a) { return data->base[a] + qp * data->stride[a]; };
+    auto arr_ = [&](int a) { return slot_at(data->seq.base[a], data->seq.stride[a], qp); };
     const double *Q = arr_(FBSTAB_MPC_Q), *Rm = arr_(FBSTAB_MPC_R), *S = arr_(FBSTAB_MPC_S), *pq = arr_(FBSTAB_MPC_q),
                  *pr = arr_(FBSTAB_MPC_r), *A = arr_(FBSTAB_MPC_A), *B = arr_(FBSTAB_MPC_B), *pc = arr_(FBSTAB_MPC_c),
                  *E = arr_(FBSTAB_MPC_E), *L = arr_(FBSTAB_MPC_L), *pd = arr_(FBSTAB_MPC_d), *px0 = arr_(FBSTAB_MPC_x0);
-    const double *uz = var->base[0] + qp * var->stride[0], *ul = var->base[1] + qp * var->stride[1],
-                 *uv = var->base[2] + qp * var->stride[2];
+    const double *uz = var_at(*var, 0, qp), *ul = var_at(*var, 1, qp), *uv = var_at(*var, 2, qp);
     C cc_;
     cc_.tid = r;
     int nzm = 0;
@@ -1930,7 +1932,7 @@ struct MpcR16 {
     double* P0w = reinterpret_cast<double*>(lane64((unsigned long long)pack)) + r2;
     int* pog = reinterpret_cast<int*>(lane64((unsigned long long)poff));
     const MpcBatchPtrs* d = reinterpret_cast<const MpcBatchPtrs*>(lane64((unsigned long long)data));
-    const VarBatchPtrs* x = reinterpret_cast<const VarBatchPtrs*>(lane64((unsigned long long)var));
+    const fbstab_var_batch_t* x = reinterpret_cast<const fbstab_var_batch_t*>(lane64((unsigned long long)var));
     const long qp = (long)lane64((unsigned long long)q);
     const int nx_ = EXACT ? NX : d->nx, nu_ = EXACT ? NU : d->nu, nc_ = EXACT ? NC : d->nc;
     const LoadSums o = load_pass_coop(ov.R0, P0w, pog, ov.po, lds, d, x, qp, ov.N, nx_, nu_, nc_);

@@ -5,6 +5,7 @@
 // two of the sweep adjoint).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 
 #include "../../include/fbstab_hip.h"
 #include "fb_adjoint.h"
@@ -39,13 +40,15 @@ struct RecordInstance {
 struct AdjointArgs {
   const double* seed[3];
   long long sstride[3];
-  double* grad[FBSTAB_MPC_NSEQ];
-  long long gstride[FBSTAB_MPC_NSEQ];
+  fbstab_mpc_grad_batch_t grad;
   double* adj[3];
   long long astride[3];
   int* status;
   double sigma, alpha;
 };
+// (kernel-argument offsets are part of the instruction stream)
+static_assert(offsetof(AdjointArgs, grad) == 48 && offsetof(AdjointArgs, adj) == 240 && sizeof(AdjointArgs) == 312,
+              "AdjointArgs: seed[3], sstride[3], the gradient block, adj[3], astride[3], status, sigma, alpha");
 
 // Arguments of the sweep adjoint kernel (fbstab_hip_mpc_receding_sweep_adjoint): the plant, the log of the sweep
 // ([steps][batch][n] each), the seeds gu, gx (null: zero), the gradient slots (null: not wanted; the x0 slot
@@ -57,14 +60,15 @@ struct SweepAdjointArgs {
   const double *lz, *ll, *lv;
   const int* le;
   const double *gu, *gx;
-  double* grad[FBSTAB_MPC_NSEQ];
-  long long gstride[FBSTAB_MPC_NSEQ];
+  fbstab_mpc_grad_batch_t grad;
   double* mu_log;
   int* status;
   double* seed;
   int steps;
   double sigma, alpha;
 };
+static_assert(offsetof(SweepAdjointArgs, grad) == 80 && offsetof(SweepAdjointArgs, mu_log) == 272,
+              "SweepAdjointArgs: the gradient block behind gx");
 
 namespace {
 
@@ -163,7 +167,7 @@ struct SweepArgs {
 // x0 <- A x0 + B u0 - what fbstab_receding_plant_kernel does for a whole batch between
 // two launches.  Returns the updated `retired` flag.  A real call: inlined into the
 // solver loop its temporaries cost the sweeps 60 spilled registers.
-__device__ __noinline__ bool receding_plant_step(const SweepArgs* sweep, const VarBatchPtrs* x,
+__device__ __noinline__ bool receding_plant_step(const SweepArgs* sweep, const fbstab_var_batch_t* x,
                                                  const fbstab_solver_out_t* out, int batch, int q, int step, int t,
                                                  int lpq, bool gone) {
   const SweepArgs& a = *sweep;
@@ -171,11 +175,11 @@ __device__ __noinline__ bool receding_plant_step(const SweepArgs* sweep, const V
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   const int eflag = out[q].eflag, newton = out[q].newton_iters;
-  double* z = x->base[0] + q * x->stride[0];
+  double* z = var_at(*x, 0, q);
   if (a.retire && !gone && eflag != FBSTAB_SUCCESS) {
     gone = true;
-    double* l = x->base[1] + q * x->stride[1];
-    double* v = x->base[2] + q * x->stride[2];
+    double* l = var_at(*x, 1, q);
+    double* v = var_at(*x, 2, q);
     for (int i = t; i < a.nz; i += lpq) z[i] = 0.0;
     for (int i = t; i < a.nl; i += lpq) l[i] = 0.0;
     for (int i = t; i < a.nv; i += lpq) v[i] = 0.0;
@@ -196,11 +200,11 @@ __device__ __noinline__ bool receding_plant_step(const SweepArgs* sweep, const V
     if (a.log_z)
       for (int i = t; i < a.nz; i += lpq) a.log_z[kq * a.nz + i] = gone ? 0.0 : z[i];
     if (a.log_l) {
-      const double* l = x->base[1] + q * x->stride[1];
+      const double* l = var_at(*x, 1, q);
       for (int i = t; i < a.nl; i += lpq) a.log_l[kq * a.nl + i] = gone ? 0.0 : l[i];
     }
     if (a.log_v) {
-      const double* v = x->base[2] + q * x->stride[2];
+      const double* v = var_at(*x, 2, q);
       for (int i = t; i < a.nv; i += lpq) a.log_v[kq * a.nv + i] = gone ? 0.0 : v[i];
     }
     if (a.log_x0 && t < a.nx) a.log_x0[kq * a.nx + t] = xs[t];
@@ -227,7 +231,7 @@ struct R16Queue {
   // to spare (a handful of VGPRs held across the Newton step turned 2 spilled
   // registers into 44).
   const MpcBatchPtrs* data;
-  const VarBatchPtrs* x;
+  const fbstab_var_batch_t* x;
   int* ctl;  // ctl[0]: next QP index
   double* scratch;
   int batch, N;
@@ -320,7 +324,7 @@ struct R16Queue {
 #endif
 template <int NX, int NU, int NC, bool DBG, bool EXACT, bool KEEP = false, int R = 1>
 __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_kernel(
-    MpcBatchPtrs data, VarBatchPtrs x, fbstab_solver_out_t* out, fbstab_options_t opts, double* scratch,
+    MpcBatchPtrs data, fbstab_var_batch_t x, fbstab_solver_out_t* out, fbstab_options_t opts, double* scratch,
     int* counter, int batch, int N, int reuse, double* dbg) {
   typedef MpcR16<NX, NU, NC, EXACT, KEEP, R> P;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -368,7 +372,7 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_kernel(
 // them (fbstab_hip.hip resets kept_batch).
 template <int NX, int NU, int NC, bool EXACT, int R>
 __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_adjoint_kernel(
-    MpcBatchPtrs data, VarBatchPtrs x, AdjointArgs a, double* scratch, int* counter, int batch, int N) {
+    MpcBatchPtrs data, fbstab_var_batch_t x, AdjointArgs a, double* scratch, int* counter, int batch, int N) {
   typedef MpcR16<NX, NU, NC, EXACT, false, R> P;
   typename P::C ctx;
   ctx.tid = threadIdx.x & (P::LPQ - 1);
@@ -387,6 +391,8 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_adjoint_
   for (;;) {
     const long q = qu.fetch(p);
     if (q < 0) break;
+    // (this kernel's slots stay written out: mpc_grad_or_null and slot_or_null in their place re-schedule the exact
+    // <12,4,32> and <24,8,32> instances - LABNOTES)
     auto at = [q](auto* b, long long s) { return b ? b + q * s : nullptr; };
     p.load_guess(ctx);
     p.choose_costate_form(a.sigma);
@@ -397,18 +403,18 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_adjoint_
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     MpcGrad G;
-    G.Q = at(a.grad[FBSTAB_MPC_Q], a.gstride[FBSTAB_MPC_Q]);
-    G.R = at(a.grad[FBSTAB_MPC_R], a.gstride[FBSTAB_MPC_R]);
-    G.S = at(a.grad[FBSTAB_MPC_S], a.gstride[FBSTAB_MPC_S]);
-    G.q = at(a.grad[FBSTAB_MPC_q], a.gstride[FBSTAB_MPC_q]);
-    G.r = at(a.grad[FBSTAB_MPC_r], a.gstride[FBSTAB_MPC_r]);
-    G.A = at(a.grad[FBSTAB_MPC_A], a.gstride[FBSTAB_MPC_A]);
-    G.B = at(a.grad[FBSTAB_MPC_B], a.gstride[FBSTAB_MPC_B]);
-    G.c = at(a.grad[FBSTAB_MPC_c], a.gstride[FBSTAB_MPC_c]);
-    G.E = at(a.grad[FBSTAB_MPC_E], a.gstride[FBSTAB_MPC_E]);
-    G.L = at(a.grad[FBSTAB_MPC_L], a.gstride[FBSTAB_MPC_L]);
-    G.d = at(a.grad[FBSTAB_MPC_d], a.gstride[FBSTAB_MPC_d]);
-    G.x0 = at(a.grad[FBSTAB_MPC_x0], a.gstride[FBSTAB_MPC_x0]);
+    G.Q = at(a.grad.base[FBSTAB_MPC_Q], a.grad.stride[FBSTAB_MPC_Q]);
+    G.R = at(a.grad.base[FBSTAB_MPC_R], a.grad.stride[FBSTAB_MPC_R]);
+    G.S = at(a.grad.base[FBSTAB_MPC_S], a.grad.stride[FBSTAB_MPC_S]);
+    G.q = at(a.grad.base[FBSTAB_MPC_q], a.grad.stride[FBSTAB_MPC_q]);
+    G.r = at(a.grad.base[FBSTAB_MPC_r], a.grad.stride[FBSTAB_MPC_r]);
+    G.A = at(a.grad.base[FBSTAB_MPC_A], a.grad.stride[FBSTAB_MPC_A]);
+    G.B = at(a.grad.base[FBSTAB_MPC_B], a.grad.stride[FBSTAB_MPC_B]);
+    G.c = at(a.grad.base[FBSTAB_MPC_c], a.grad.stride[FBSTAB_MPC_c]);
+    G.E = at(a.grad.base[FBSTAB_MPC_E], a.grad.stride[FBSTAB_MPC_E]);
+    G.L = at(a.grad.base[FBSTAB_MPC_L], a.grad.stride[FBSTAB_MPC_L]);
+    G.d = at(a.grad.base[FBSTAB_MPC_d], a.grad.stride[FBSTAB_MPC_d]);
+    G.x0 = at(a.grad.base[FBSTAB_MPC_x0], a.grad.stride[FBSTAB_MPC_x0]);
     mpc_adjoint_contract(ctx, N, nx, nu, nc, x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
                          x.base[2] + q * x.stride[2], flat, flat + nz, flat + nz + nl, G, ok, at(a.adj[0], a.astride[0]),
                          at(a.adj[1], a.astride[1]), at(a.adj[2], a.astride[2]));
@@ -434,7 +440,7 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_sweep_ad
   typename P::C ctx;
   ctx.tid = threadIdx.x & (P::LPQ - 1);
   P p;
-  VarBatchPtrs xk;  // the logged point of the step in hand
+  fbstab_var_batch_t xk;  // the logged point of the step in hand
   for (int i = 0; i < 4; i++) { xk.base[i] = nullptr; xk.stride[i] = 0; }
   R16Queue<P, false> qu;
   qu.data = &data;
@@ -451,19 +457,7 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_sweep_ad
   for (;;) {
     const long q = qu.fetch(p);
     if (q < 0) break;
-    auto at = [q](double* b, long long s) { return b ? b + q * s : nullptr; };
-    MpcGrad G;
-    G.Q = at(a.grad[FBSTAB_MPC_Q], a.gstride[FBSTAB_MPC_Q]);
-    G.R = at(a.grad[FBSTAB_MPC_R], a.gstride[FBSTAB_MPC_R]);
-    G.S = at(a.grad[FBSTAB_MPC_S], a.gstride[FBSTAB_MPC_S]);
-    G.q = at(a.grad[FBSTAB_MPC_q], a.gstride[FBSTAB_MPC_q]);
-    G.r = at(a.grad[FBSTAB_MPC_r], a.gstride[FBSTAB_MPC_r]);
-    G.A = at(a.grad[FBSTAB_MPC_A], a.gstride[FBSTAB_MPC_A]);
-    G.B = at(a.grad[FBSTAB_MPC_B], a.gstride[FBSTAB_MPC_B]);
-    G.c = at(a.grad[FBSTAB_MPC_c], a.gstride[FBSTAB_MPC_c]);
-    G.E = at(a.grad[FBSTAB_MPC_E], a.gstride[FBSTAB_MPC_E]);
-    G.L = at(a.grad[FBSTAB_MPC_L], a.gstride[FBSTAB_MPC_L]);
-    G.d = at(a.grad[FBSTAB_MPC_d], a.gstride[FBSTAB_MPC_d]);
+    MpcGrad G = mpc_grad_or_null(a.grad, q);
     G.x0 = nullptr;  // (receives the final costate, below)
     {
       // zeros, by the lanes that add to the entries later (mpc_adjoint_contract's mapping)
@@ -532,7 +526,7 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_sweep_ad
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     }
-    if (a.grad[FBSTAB_MPC_x0] && t < nx) a.grad[FBSTAB_MPC_x0][q * a.gstride[FBSTAB_MPC_x0] + t] = lam;
+    if (a.grad.base[FBSTAB_MPC_x0] && t < nx) a.grad.base[FBSTAB_MPC_x0][q * a.grad.stride[FBSTAB_MPC_x0] + t] = lam;
     if (t == 0) a.status[q] = failed;
   }
 }

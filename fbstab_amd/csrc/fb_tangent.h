@@ -15,18 +15,11 @@
 // neither loaded nor multiplied.
 #pragma once
 
-#include "fb_common.h"
+#include "fb_batch.h"
 
 namespace fbk {
 
-// Pointers to one QP's perturbations of the 12 sequences (the order of fbstab_mpc_batch_t; nullptr: zero).
-struct MpcDir {
-  const double *Q, *R, *S, *q, *r, *A, *B, *c, *E, *L, *d, *x0;
-};
-// ... and of the six dense arrays (the order of fbstab_dense_batch_t).
-struct DenseDir {
-  const double *H, *f, *G, *h, *A, *b;
-};
+// (MpcDir, DenseDir - one QP's perturbations, nullptr: zero - are MpcData and DenseData: fb_batch.h)
 
 // dst[0 .. len) = src[0 .. len): thread c.tid takes the 16-byte pairs c.tid, c.tid + C::nt, ... counted from the
 // first 16-byte boundary of src, so that a wavefront's loads are one contiguous run of 16 B per lane; the at most

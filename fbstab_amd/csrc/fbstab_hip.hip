@@ -41,19 +41,6 @@ constexpr int kLdsLimitBytes = 160 * 1024;
 // dense kernel counts the Newton steps it handed to the pivoted factorisation
 constexpr int kDenseFallbackSlot = 4;
 
-struct MpcBatchArgs {
-  const double* base[FBSTAB_MPC_NSEQ];
-  long long stride[FBSTAB_MPC_NSEQ];
-};
-struct DenseBatchArgs {
-  const double* base[FBSTAB_DENSE_NARR];
-  long long stride[FBSTAB_DENSE_NARR];
-};
-struct VarBatchArgs {
-  double* base[4];
-  long long stride[4];
-};
-
 // Next QP index for this workgroup (workgroup-uniform).
 template <int NT>
 __device__ __forceinline__ int next_qp(int* counter, lds_ptr slot) {
@@ -69,30 +56,13 @@ __device__ __forceinline__ int next_qp(int* counter, lds_ptr slot) {
   }
 }
 
-__device__ __forceinline__ MpcData mpc_data_of(const MpcBatchArgs& data, long q) {
-  MpcData D;
-  D.Q = data.base[FBSTAB_MPC_Q] + q * data.stride[FBSTAB_MPC_Q];
-  D.R = data.base[FBSTAB_MPC_R] + q * data.stride[FBSTAB_MPC_R];
-  D.S = data.base[FBSTAB_MPC_S] + q * data.stride[FBSTAB_MPC_S];
-  D.q = data.base[FBSTAB_MPC_q] + q * data.stride[FBSTAB_MPC_q];
-  D.r = data.base[FBSTAB_MPC_r] + q * data.stride[FBSTAB_MPC_r];
-  D.A = data.base[FBSTAB_MPC_A] + q * data.stride[FBSTAB_MPC_A];
-  D.B = data.base[FBSTAB_MPC_B] + q * data.stride[FBSTAB_MPC_B];
-  D.c = data.base[FBSTAB_MPC_c] + q * data.stride[FBSTAB_MPC_c];
-  D.E = data.base[FBSTAB_MPC_E] + q * data.stride[FBSTAB_MPC_E];
-  D.L = data.base[FBSTAB_MPC_L] + q * data.stride[FBSTAB_MPC_L];
-  D.d = data.base[FBSTAB_MPC_d] + q * data.stride[FBSTAB_MPC_d];
-  D.x0 = data.base[FBSTAB_MPC_x0] + q * data.stride[FBSTAB_MPC_x0];
-  return D;
-}
-
 constexpr int kMpcMinWaves = 1;  // wavefronts per SIMD the flat-vector MPC kernels are compiled for
 // DBG: the Newton-step probe; TRACE: `dbg` is the trace buffer of
 // fbstab_hip_mpc_solve_traced (see Solver in fb_algorithm.h); WG: the stage tile and the
 // work matrices in global scratch (MpcLayout::wglobal: shapes beyond the LDS).
 template <int NT, bool DBG, bool TRACE = false, bool WG = false>
-__global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_kernel(MpcLayout lay, MpcBatchArgs data,
-                                                        VarBatchArgs x,
+__global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_kernel(MpcLayout lay, fbstab_mpc_batch_t data,
+                                                        fbstab_var_batch_t x,
                                                         fbstab_solver_out_t* out,
                                                         fbstab_options_t opts, double* scratch,
                                                         int* counter, int batch, double* dbg) {
@@ -110,8 +80,7 @@ __global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_kernel(MpcLayout 
     typename MpcProblem<C, WG>::mptr mb;
     if constexpr (WG) mb = ws + lay.v_carve;
     else mb = lds;
-    p.bind(lay, mpc_data_of(data, q), x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
-           x.base[2] + q * x.stride[2], x.base[3] + q * x.stride[3], mb, ws);
+    p.bind(lay, mpc_data_at(data, q), var_at(x, 0, q), var_at(x, 1, q), var_at(x, 2, q), var_at(x, 3, q), mb, ws);
     if constexpr (DBG) {
       newton_probe(p, ctx, opts, dbg);
     } else {
@@ -129,13 +98,9 @@ __global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_kernel(MpcLayout 
 // kernel, and the record handles that FBSTAB_HIP_FLAT_ADJOINT or the row-pair instances' default keeps on it (they
 // give it a scratch of its own; the others run fbstab_mpc_r16_adjoint_kernel, fb_record_kernel.h).  `x`: the point
 // (z, l, v); `seed`: (gz, gl, gv), null l / v slots meaning zero; `adj`: null slots, or (dz, dl, dv).
-struct MpcGradArgs {
-  double* base[FBSTAB_MPC_NSEQ];
-  long long stride[FBSTAB_MPC_NSEQ];
-};
 template <int NT, bool WG>
 __global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_adjoint_kernel(
-    MpcLayout lay, MpcBatchArgs data, VarBatchArgs x, VarBatchArgs seed, MpcGradArgs grad, VarBatchArgs adj,
+    MpcLayout lay, fbstab_mpc_batch_t data, fbstab_var_batch_t x, fbstab_var_batch_t seed, fbstab_mpc_grad_batch_t grad, fbstab_var_batch_t adj,
     int* status, double sigma, double alpha, double* scratch, int* counter, int batch) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   lds_ptr lds = (lds_ptr)smem;
@@ -151,26 +116,14 @@ __global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_adjoint_kernel(
     typename MpcProblem<C, WG>::mptr mb;
     if constexpr (WG) mb = ws + lay.v_carve;
     else mb = lds;
-    p.bind(lay, mpc_data_of(data, q), x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
-           x.base[2] + q * x.stride[2], nullptr, mb, ws);
-    auto at = [q](double* b, long long s) { return b ? b + q * s : nullptr; };
-    const bool ok = mpc_adjoint(p, ctx, sigma, alpha, seed.base[0] + q * seed.stride[0],
-                                at(seed.base[1], seed.stride[1]), at(seed.base[2], seed.stride[2]));
-    MpcGrad G;
-    G.Q = at(grad.base[FBSTAB_MPC_Q], grad.stride[FBSTAB_MPC_Q]);
-    G.R = at(grad.base[FBSTAB_MPC_R], grad.stride[FBSTAB_MPC_R]);
-    G.S = at(grad.base[FBSTAB_MPC_S], grad.stride[FBSTAB_MPC_S]);
-    G.q = at(grad.base[FBSTAB_MPC_q], grad.stride[FBSTAB_MPC_q]);
-    G.r = at(grad.base[FBSTAB_MPC_r], grad.stride[FBSTAB_MPC_r]);
-    G.A = at(grad.base[FBSTAB_MPC_A], grad.stride[FBSTAB_MPC_A]);
-    G.B = at(grad.base[FBSTAB_MPC_B], grad.stride[FBSTAB_MPC_B]);
-    G.c = at(grad.base[FBSTAB_MPC_c], grad.stride[FBSTAB_MPC_c]);
-    G.E = at(grad.base[FBSTAB_MPC_E], grad.stride[FBSTAB_MPC_E]);
-    G.L = at(grad.base[FBSTAB_MPC_L], grad.stride[FBSTAB_MPC_L]);
-    G.d = at(grad.base[FBSTAB_MPC_d], grad.stride[FBSTAB_MPC_d]);
-    G.x0 = at(grad.base[FBSTAB_MPC_x0], grad.stride[FBSTAB_MPC_x0]);
-    mpc_adjoint_gradients(p, ctx, G, ok, at(adj.base[0], adj.stride[0]), at(adj.base[1], adj.stride[1]),
-                          at(adj.base[2], adj.stride[2]));
+    p.bind(lay, mpc_data_at(data, q), var_at(x, 0, q), var_at(x, 1, q), var_at(x, 2, q), nullptr, mb, ws);
+    // (the seed and adjoint slots one by one, the gradients named before the call: var_at / var_or_null on these
+    // two blocks, or the gradients formed among the call's arguments, re-schedule this kernel - LABNOTES)
+    const bool ok = mpc_adjoint(p, ctx, sigma, alpha, slot_at(seed.base[0], seed.stride[0], q),
+                                slot_or_null(seed.base[1], seed.stride[1], q), slot_or_null(seed.base[2], seed.stride[2], q));
+    const MpcGrad G = mpc_grad_or_null(grad, q);
+    mpc_adjoint_gradients(p, ctx, G, ok, slot_or_null(adj.base[0], adj.stride[0], q),
+                          slot_or_null(adj.base[1], adj.stride[1], q), slot_or_null(adj.base[2], adj.stride[2], q));
     if (ctx.tid == 0) status[q] = ok ? 0 : 1;
     ctx.sync();
   }
@@ -194,7 +147,7 @@ struct SweepLogStep {
 };
 __global__ void fbstab_receding_plant_kernel(int batch, int nx, int nu, int nz, int nl, int nv, const double* A,
                                              long long sA, const double* B, long long sB, double* x0, long long sx0,
-                                             VarBatchArgs x, const fbstab_solver_out_t* out, int* retired,
+                                             fbstab_var_batch_t x, const fbstab_solver_out_t* out, int* retired,
                                              int retire, double* u_log, unsigned long long* stats, double* xtmp,
                                              SweepLogStep lg) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -203,15 +156,15 @@ __global__ void fbstab_receding_plant_kernel(int batch, int nx, int nu, int nz, 
   o.eflag = FBSTAB_SUCCESS;
   o.newton_iters = 0;
   if (live) o = out[q];
-  double* z = x.base[0] + (live ? q : 0) * x.stride[0];
+  double* z = var_at(x, 0, live ? q : 0);
   double* xs = x0 + (live ? q : 0) * sx0;
   bool gone = live && retired[q] != 0;
   if (live && retire && !gone && o.eflag != FBSTAB_SUCCESS) {
     gone = true;
     retired[q] = 1;
     for (int i = 0; i < nz; i++) z[i] = 0.0;
-    double* l = x.base[1] + q * x.stride[1];
-    double* v = x.base[2] + q * x.stride[2];
+    double* l = var_at(x, 1, q);
+    double* v = var_at(x, 2, q);
     for (int i = 0; i < nl; i++) l[i] = 0.0;
     for (int i = 0; i < nv; i++) v[i] = 0.0;
   }
@@ -243,11 +196,11 @@ __global__ void fbstab_receding_plant_kernel(int batch, int nx, int nu, int nz, 
   if (lg.z)
     for (int i = 0; i < nz; i++) lg.z[(long long)q * nz + i] = gone ? 0.0 : z[i];
   if (lg.l) {
-    const double* l = x.base[1] + q * x.stride[1];
+    const double* l = var_at(x, 1, q);
     for (int i = 0; i < nl; i++) lg.l[(long long)q * nl + i] = gone ? 0.0 : l[i];
   }
   if (lg.v) {
-    const double* v = x.base[2] + q * x.stride[2];
+    const double* v = var_at(x, 2, q);
     for (int i = 0; i < nv; i++) lg.v[(long long)q * nv + i] = gone ? 0.0 : v[i];
   }
   if (lg.x0)
@@ -282,8 +235,7 @@ struct SweepCostateArgs {
   const int* eflag;       // step k's [batch]
   const double *gu, *gx;  // step k's [batch][nu | nx], or null
   double* mu_log;         // step k's [batch][nx], or null
-  double* grad[FBSTAB_MPC_NSEQ];
-  long long gstride[FBSTAB_MPC_NSEQ];
+  fbstab_mpc_grad_batch_t grad;
   const double* tmp[FBSTAB_MPC_NSEQ];  // the image of one step (null where the slot is; x0 always)
   long long len[FBSTAB_MPC_NSEQ];
   double *seed, *lam, *atm;  // [batch][nz], [batch][nx], [batch][nx]
@@ -299,8 +251,8 @@ __global__ __launch_bounds__(64) void fbstab_sweep_costate_kernel(SweepCostateAr
   double* atm = a.atm + q * nx;
   if (phase == 0) {
     for (int s = 0; s < FBSTAB_MPC_NSEQ; s++)
-      if (a.grad[s])
-        for (long long e = t; e < a.len[s]; e += nt) a.grad[s][q * a.gstride[s] + e] = 0.0;
+      if (a.grad.base[s])
+        for (long long e = t; e < a.len[s]; e += nt) a.grad.base[s][q * a.grad.stride[s] + e] = 0.0;
     for (int i = t; i < nx; i += nt) lam[i] = 0.0;
     for (long long i = t; i < a.nz; i += nt) a.seed[q * a.nz + i] = 0.0;
     if (t == 0) a.status[q] = 0;
@@ -331,12 +283,13 @@ __global__ __launch_bounds__(64) void fbstab_sweep_costate_kernel(SweepCostateAr
   const bool solved = e == FBSTAB_SUCCESS, ok = solved && a.tmp_status[q] == 0;
   if (ok)
     for (int s = 0; s < FBSTAB_MPC_NSEQ; s++)
-      if (a.grad[s] && s != FBSTAB_MPC_x0)
-        for (long long i = t; i < a.len[s]; i += nt) a.grad[s][q * a.gstride[s] + i] += a.tmp[s][q * a.len[s] + i];
+      if (a.grad.base[s] && s != FBSTAB_MPC_x0)
+        for (long long i = t; i < a.len[s]; i += nt)
+          a.grad.base[s][q * a.grad.stride[s] + i] += a.tmp[s][q * a.len[s] + i];
   for (int i = t; i < nx; i += nt) {
     const double l = e == -1 ? 0.0 : (ok ? atm[i] + a.tmp[FBSTAB_MPC_x0][q * nx + i] : atm[i]);
     lam[i] = l;
-    if (last && a.grad[FBSTAB_MPC_x0]) a.grad[FBSTAB_MPC_x0][q * a.gstride[FBSTAB_MPC_x0] + i] = l;
+    if (last && a.grad.base[FBSTAB_MPC_x0]) a.grad.base[FBSTAB_MPC_x0][q * a.grad.stride[FBSTAB_MPC_x0] + i] = l;
   }
   if (solved && !ok && t == 0) a.status[q] += 1;
 }
@@ -356,8 +309,8 @@ struct KScratchArg<true> {
 // VGLOBAL (with KGLOBAL): the iterate vectors too live in the workgroup's global scratch
 // (DenseLayout::v_global: nv beyond what the LDS holds).
 template <int NT, bool TRACE = false, bool KGLOBAL = false, bool VGLOBAL = false>
-__global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_kernel(DenseLayout lay, DenseBatchArgs data,
-                                                          VarBatchArgs x,
+__global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_kernel(DenseLayout lay, fbstab_dense_batch_t data,
+                                                          fbstab_var_batch_t x,
                                                           fbstab_solver_out_t* out,
                                                           fbstab_options_t opts, int* counter,
                                                           int batch, TraceArg<TRACE> trace,
@@ -372,18 +325,10 @@ __global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_kernel(Den
   for (;;) {
     const int q = next_qp<NT>(counter, lds + lay.o_slot);
     if (q >= batch) break;
-    DenseData D;
-    D.H = data.base[FBSTAB_DENSE_H] + q * data.stride[FBSTAB_DENSE_H];
-    D.f = data.base[FBSTAB_DENSE_f] + q * data.stride[FBSTAB_DENSE_f];
-    D.G = data.base[FBSTAB_DENSE_G] + q * data.stride[FBSTAB_DENSE_G];
-    D.h = data.base[FBSTAB_DENSE_h] + q * data.stride[FBSTAB_DENSE_h];
-    D.A = data.base[FBSTAB_DENSE_A] + q * data.stride[FBSTAB_DENSE_A];
-    D.b = data.base[FBSTAB_DENSE_b] + q * data.stride[FBSTAB_DENSE_b];
     DenseProblem<C, KGLOBAL, VGLOBAL> p;
     double* ks = nullptr;
     if constexpr (KGLOBAL) ks = kscratch.get() + (long)blockIdx.x * (lay.k_doubles + lay.v_doubles);
-    p.bind(lay, D, x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
-           x.base[2] + q * x.stride[2], x.base[3] + q * x.stride[3], lds, ks);
+    p.bind(lay, dense_data_at(data, q), var_at(x, 0, q), var_at(x, 1, q), var_at(x, 2, q), var_at(x, 3, q), lds, ks);
     Solver<DenseProblem<C, KGLOBAL, VGLOBAL>, C, TRACE> solver(p, ctx, opts, trace.get());
     solver.solve(out + q);
     ctx.sync();
@@ -393,8 +338,8 @@ __global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_kernel(Den
 // Diagnostic probe for the dense path (tests only): one Newton step at (x, xbar,
 // sigma0) for QP 0 of the batch arrays, see newton_probe.
 template <int NT>
-__global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_probe_kernel(DenseLayout lay, DenseBatchArgs data,
-                                                                                VarBatchArgs x,
+__global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_probe_kernel(DenseLayout lay, fbstab_dense_batch_t data,
+                                                                                fbstab_var_batch_t x,
                                                                                 fbstab_options_t opts, double* dbg) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   lds_ptr lds = (lds_ptr)smem;
@@ -402,15 +347,8 @@ __global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_probe_kern
   C ctx;
   ctx.tid = threadIdx.x;
   ctx.red = lds + lay.o_red;
-  DenseData D;
-  D.H = data.base[FBSTAB_DENSE_H];
-  D.f = data.base[FBSTAB_DENSE_f];
-  D.G = data.base[FBSTAB_DENSE_G];
-  D.h = data.base[FBSTAB_DENSE_h];
-  D.A = data.base[FBSTAB_DENSE_A];
-  D.b = data.base[FBSTAB_DENSE_b];
   DenseProblem<C, false> p;
-  p.bind(lay, D, x.base[0], x.base[1], x.base[2], x.base[3], lds, nullptr);
+  p.bind(lay, dense_data_at(data, 0), x.base[0], x.base[1], x.base[2], x.base[3], lds, nullptr);
   newton_probe(p, ctx, opts, dbg);
 }
 
@@ -419,8 +357,8 @@ __global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_probe_kern
 // lay.ws_doubles per workgroup (A' and the multipliers).  DBG: the Newton-step probe.
 constexpr int kDwMinWaves = 2;
 template <bool DBG>
-__global__ __launch_bounds__(64, kDwMinWaves) void fbstab_dense_wave_kernel(DenseWaveLayout lay, DenseBatchArgs data,
-                                                                   VarBatchArgs x, fbstab_solver_out_t* out,
+__global__ __launch_bounds__(64, kDwMinWaves) void fbstab_dense_wave_kernel(DenseWaveLayout lay, fbstab_dense_batch_t data,
+                                                                   fbstab_var_batch_t x, fbstab_solver_out_t* out,
                                                                    fbstab_options_t opts, int* counter, int batch,
                                                                    double* scratch, double* dbg) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -434,16 +372,9 @@ __global__ __launch_bounds__(64, kDwMinWaves) void fbstab_dense_wave_kernel(Dens
   for (;;) {
     const int q = DBG ? (int)blockIdx.x : next_qp<64>(counter, lds);
     if (q >= batch) break;
-    DenseData D;
-    D.H = data.base[FBSTAB_DENSE_H] + q * data.stride[FBSTAB_DENSE_H];
-    D.f = data.base[FBSTAB_DENSE_f] + q * data.stride[FBSTAB_DENSE_f];
-    D.G = data.base[FBSTAB_DENSE_G] + q * data.stride[FBSTAB_DENSE_G];
-    D.h = data.base[FBSTAB_DENSE_h] + q * data.stride[FBSTAB_DENSE_h];
-    D.A = data.base[FBSTAB_DENSE_A] + q * data.stride[FBSTAB_DENSE_A];
-    D.b = data.base[FBSTAB_DENSE_b] + q * data.stride[FBSTAB_DENSE_b];
     DenseWave p;
-    p.bind(lay, D, x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1], x.base[2] + q * x.stride[2],
-           x.base[3] + q * x.stride[3], lds, ws, counter + kDenseFallbackSlot);
+    p.bind(lay, dense_data_at(data, q), var_at(x, 0, q), var_at(x, 1, q), var_at(x, 2, q), var_at(x, 3, q), lds, ws,
+           counter + kDenseFallbackSlot);
     if constexpr (DBG) {
       newton_probe(p, ctx, opts, dbg);
       break;
@@ -458,37 +389,12 @@ __global__ __launch_bounds__(64, kDwMinWaves) void fbstab_dense_wave_kernel(Dens
 // The adjoint of fbstab_hip_dense_adjoint_batch (fb_dense.h: dense_adjoint, dense_adjoint_gradients; the
 // contraction of fb_adjoint.h), one QP per workgroup pulled from the queue like the solve.  `x`: the point
 // (z, l, v); `seed`: (gz, gl, gv), null l / v slots meaning zero; `adj`: null slots, or (dz, dl, dv).
-struct DenseGradArgs {
-  double* base[FBSTAB_DENSE_NARR];
-  long long stride[FBSTAB_DENSE_NARR];
-};
-__device__ __forceinline__ DenseData dense_data_of(const DenseBatchArgs& data, long q) {
-  DenseData D;
-  D.H = data.base[FBSTAB_DENSE_H] + q * data.stride[FBSTAB_DENSE_H];
-  D.f = data.base[FBSTAB_DENSE_f] + q * data.stride[FBSTAB_DENSE_f];
-  D.G = data.base[FBSTAB_DENSE_G] + q * data.stride[FBSTAB_DENSE_G];
-  D.h = data.base[FBSTAB_DENSE_h] + q * data.stride[FBSTAB_DENSE_h];
-  D.A = data.base[FBSTAB_DENSE_A] + q * data.stride[FBSTAB_DENSE_A];
-  D.b = data.base[FBSTAB_DENSE_b] + q * data.stride[FBSTAB_DENSE_b];
-  return D;
-}
-__device__ __forceinline__ DenseGrad dense_grad_of(const DenseGradArgs& grad, long q) {
-  auto at = [q](double* b, long long s) { return b ? b + q * s : nullptr; };
-  DenseGrad G;
-  G.H = at(grad.base[FBSTAB_DENSE_H], grad.stride[FBSTAB_DENSE_H]);
-  G.f = at(grad.base[FBSTAB_DENSE_f], grad.stride[FBSTAB_DENSE_f]);
-  G.G = at(grad.base[FBSTAB_DENSE_G], grad.stride[FBSTAB_DENSE_G]);
-  G.h = at(grad.base[FBSTAB_DENSE_h], grad.stride[FBSTAB_DENSE_h]);
-  G.A = at(grad.base[FBSTAB_DENSE_A], grad.stride[FBSTAB_DENSE_A]);
-  G.b = at(grad.base[FBSTAB_DENSE_b], grad.stride[FBSTAB_DENSE_b]);
-  return G;
-}
 
 // The four-wavefront policy (fb_dense.h), the instances of fbstab_dense_kernel: K in LDS, K in global scratch
 // (KGLOBAL), the iterate vectors there too (VGLOBAL), and NT = 64.  Its factorisation always pivots.
 template <int NT, bool KGLOBAL = false, bool VGLOBAL = false>
 __global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_adjoint_kernel(
-    DenseLayout lay, DenseBatchArgs data, VarBatchArgs x, VarBatchArgs seed, DenseGradArgs grad, VarBatchArgs adj,
+    DenseLayout lay, fbstab_dense_batch_t data, fbstab_var_batch_t x, fbstab_var_batch_t seed, fbstab_dense_grad_batch_t grad, fbstab_var_batch_t adj,
     int* status, double sigma, double alpha, int* counter, int batch, KScratchArg<KGLOBAL> kscratch) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   lds_ptr lds = (lds_ptr)smem;
@@ -502,13 +408,14 @@ __global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_adjoint_ke
     DenseProblem<C, KGLOBAL, VGLOBAL> p;
     double* ks = nullptr;
     if constexpr (KGLOBAL) ks = kscratch.get() + (long)blockIdx.x * (lay.k_doubles + lay.v_doubles);
-    p.bind(lay, dense_data_of(data, q), x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
-           x.base[2] + q * x.stride[2], nullptr, lds, ks);
+    p.bind(lay, dense_data_at(data, q), var_at(x, 0, q), var_at(x, 1, q), var_at(x, 2, q), nullptr, lds, ks);
+    // (the seed and adjoint slots stay written out: slot_or_null in their place re-schedules the
+    // <kDenseThreads, true, true> instance - LABNOTES)
     auto at = [q](double* b, long long s) { return b ? b + q * s : nullptr; };
     const bool ok = dense_adjoint(p, ctx, sigma, alpha, seed.base[0] + q * seed.stride[0],
                                   at(seed.base[1], seed.stride[1]), at(seed.base[2], seed.stride[2]));
     ctx.sync();
-    dense_adjoint_gradients(p, ctx, dense_grad_of(grad, q), ok, at(adj.base[0], adj.stride[0]),
+    dense_adjoint_gradients(p, ctx, dense_grad_or_null(grad, q), ok, at(adj.base[0], adj.stride[0]),
                             at(adj.base[1], adj.stride[1]), at(adj.base[2], adj.stride[2]));
     if (ctx.tid == 0) status[q] = ok ? 0 : 1;
     ctx.sync();
@@ -519,7 +426,7 @@ __global__ __launch_bounds__(NT, (NT > 64 ? 2 : 1)) void fbstab_dense_adjoint_ke
 // handle's own scratch region per workgroup.  newton_step<true> factors by the pivoted rule whatever the handle's
 // order, and the fallback counters of the last solve are neither passed nor reset.
 __global__ __launch_bounds__(64, kDwMinWaves) void fbstab_dense_wave_adjoint_kernel(
-    DenseWaveLayout lay, DenseBatchArgs data, VarBatchArgs x, VarBatchArgs seed, DenseGradArgs grad, VarBatchArgs adj,
+    DenseWaveLayout lay, fbstab_dense_batch_t data, fbstab_var_batch_t x, fbstab_var_batch_t seed, fbstab_dense_grad_batch_t grad, fbstab_var_batch_t adj,
     int* status, double sigma, double alpha, int* counter, int batch, double* scratch) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   lds_ptr lds = (lds_ptr)smem;
@@ -532,14 +439,11 @@ __global__ __launch_bounds__(64, kDwMinWaves) void fbstab_dense_wave_adjoint_ker
     const int q = next_qp<64>(counter, lds);
     if (q >= batch) break;
     DenseWave p;
-    p.bind(lay, dense_data_of(data, q), x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
-           x.base[2] + q * x.stride[2], nullptr, lds, ws, nullptr);
-    auto at = [q](double* b, long long s) { return b ? b + q * s : nullptr; };
-    const bool ok = dense_adjoint(p, ctx, sigma, alpha, seed.base[0] + q * seed.stride[0],
-                                  at(seed.base[1], seed.stride[1]), at(seed.base[2], seed.stride[2]));
+    p.bind(lay, dense_data_at(data, q), var_at(x, 0, q), var_at(x, 1, q), var_at(x, 2, q), nullptr, lds, ws, nullptr);
+    const bool ok = dense_adjoint(p, ctx, sigma, alpha, var_at(seed, 0, q), var_or_null(seed, 1, q), var_or_null(seed, 2, q));
     ctx.sync();
-    dense_adjoint_gradients(p, ctx, dense_grad_of(grad, q), ok, at(adj.base[0], adj.stride[0]),
-                            at(adj.base[1], adj.stride[1]), at(adj.base[2], adj.stride[2]));
+    dense_adjoint_gradients(p, ctx, dense_grad_or_null(grad, q), ok, var_or_null(adj, 0, q), var_or_null(adj, 1, q),
+                            var_or_null(adj, 2, q));
     if (ctx.tid == 0) status[q] = ok ? 0 : 1;
     ctx.sync();
   }
@@ -552,7 +456,7 @@ __global__ __launch_bounds__(64, kDwMinWaves) void fbstab_dense_wave_adjoint_ker
 // MPC: one wavefront per (QP, stage), the stage's images in its LDS (MpcTangentLds).
 constexpr int kDenseTangentThreads = 256;
 __global__ __launch_bounds__(64) void fbstab_tangent_rhs_kernel(int N, int nx, int nu, int nc, MpcTangentLds o,
-                                                                MpcBatchArgs dir, VarBatchArgs x, VarBatchArgs seed) {
+                                                                fbstab_mpc_batch_t dir, fbstab_var_batch_t x, fbstab_var_batch_t seed) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   typedef Ctx<64> C;
   C ctx;
@@ -560,46 +464,22 @@ __global__ __launch_bounds__(64) void fbstab_tangent_rhs_kernel(int N, int nx, i
   ctx.red = (lds_ptr)smem;  // (unused)
   const long q = blockIdx.x / (N + 1);
   const int i = blockIdx.x % (N + 1);
-  auto at = [q](const double* b, long long s) { return b ? b + q * s : nullptr; };
-  MpcDir D;
-  D.Q = at(dir.base[FBSTAB_MPC_Q], dir.stride[FBSTAB_MPC_Q]);
-  D.R = at(dir.base[FBSTAB_MPC_R], dir.stride[FBSTAB_MPC_R]);
-  D.S = at(dir.base[FBSTAB_MPC_S], dir.stride[FBSTAB_MPC_S]);
-  D.q = at(dir.base[FBSTAB_MPC_q], dir.stride[FBSTAB_MPC_q]);
-  D.r = at(dir.base[FBSTAB_MPC_r], dir.stride[FBSTAB_MPC_r]);
-  D.A = at(dir.base[FBSTAB_MPC_A], dir.stride[FBSTAB_MPC_A]);
-  D.B = at(dir.base[FBSTAB_MPC_B], dir.stride[FBSTAB_MPC_B]);
-  D.c = at(dir.base[FBSTAB_MPC_c], dir.stride[FBSTAB_MPC_c]);
-  D.E = at(dir.base[FBSTAB_MPC_E], dir.stride[FBSTAB_MPC_E]);
-  D.L = at(dir.base[FBSTAB_MPC_L], dir.stride[FBSTAB_MPC_L]);
-  D.d = at(dir.base[FBSTAB_MPC_d], dir.stride[FBSTAB_MPC_d]);
-  D.x0 = at(dir.base[FBSTAB_MPC_x0], dir.stride[FBSTAB_MPC_x0]);
-  mpc_tangent_stage(ctx, N, nx, nu, nc, i, D, x.base[0] + q * x.stride[0], x.base[1] + q * x.stride[1],
-                    x.base[2] + q * x.stride[2], o, (lds_ptr)smem, seed.base[0] + q * seed.stride[0],
-                    seed.base[1] + q * seed.stride[1], seed.base[2] + q * seed.stride[2]);
+  mpc_tangent_stage(ctx, N, nx, nu, nc, i, mpc_data_or_null(dir, q), var_at(x, 0, q), var_at(x, 1, q), var_at(x, 2, q),
+                    o, (lds_ptr)smem, var_at(seed, 0, q), var_at(seed, 1, q), var_at(seed, 2, q));
 }
 
 // Dense: one workgroup per QP, walking the images in blocks of columns (DenseTangentLds).
 __global__ __launch_bounds__(kDenseTangentThreads) void fbstab_dense_tangent_rhs_kernel(
-    int nz, int nl, int nv, DenseTangentLds o, DenseBatchArgs dir, VarBatchArgs x, VarBatchArgs seed) {
+    int nz, int nl, int nv, DenseTangentLds o, fbstab_dense_batch_t dir, fbstab_var_batch_t x, fbstab_var_batch_t seed) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   typedef Ctx<kDenseTangentThreads> C;
   C ctx;
   ctx.tid = threadIdx.x;
   ctx.red = (lds_ptr)smem;  // (unused)
   const long q = blockIdx.x;
-  auto at = [q](const double* b, long long s) { return b ? b + q * s : nullptr; };
-  DenseDir D;
-  D.H = at(dir.base[FBSTAB_DENSE_H], dir.stride[FBSTAB_DENSE_H]);
-  D.f = at(dir.base[FBSTAB_DENSE_f], dir.stride[FBSTAB_DENSE_f]);
-  D.G = at(dir.base[FBSTAB_DENSE_G], dir.stride[FBSTAB_DENSE_G]);
-  D.h = at(dir.base[FBSTAB_DENSE_h], dir.stride[FBSTAB_DENSE_h]);
-  D.A = at(dir.base[FBSTAB_DENSE_A], dir.stride[FBSTAB_DENSE_A]);
-  D.b = at(dir.base[FBSTAB_DENSE_b], dir.stride[FBSTAB_DENSE_b]);
-  auto var = [q](double* b, long long s) { return b ? b + q * s : nullptr; };  // (nl == 0: the l slots are null)
-  dense_tangent(ctx, nz, nl, nv, D, x.base[0] + q * x.stride[0], var(x.base[1], x.stride[1]),
-                x.base[2] + q * x.stride[2], o, (lds_ptr)smem, seed.base[0] + q * seed.stride[0],
-                var(seed.base[1], seed.stride[1]), seed.base[2] + q * seed.stride[2]);
+  // (nl == 0: the l slots are null)
+  dense_tangent(ctx, nz, nl, nv, dense_data_or_null(dir, q), var_at(x, 0, q), var_or_null(x, 1, q), var_at(x, 2, q), o,
+                (lds_ptr)smem, var_at(seed, 0, q), var_or_null(seed, 1, q), var_at(seed, 2, q));
 }
 
 // ---------------------------------------------------------------------------
@@ -616,6 +496,17 @@ int fail(int code, const std::string& msg) {
     if (e_ != hipSuccess)                                                              \
       return fail(FBSTAB_HIP_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
+
+#define RC_TRY(expr)                        \
+  do {                                      \
+    int rc_ = (expr);                       \
+    if (rc_ != FBSTAB_HIP_OK) return rc_;   \
+  } while (0)
+
+// sigma of the derivative entry points: what the caller gave, or the reference's default sigma0
+// (fbstab_algorithm-impl.h:34), whatever the handle's options say
+constexpr double kDefaultSigma = 1e-8;
+double sigma_or_default(double sigma) { return sigma > 0.0 ? sigma : kDefaultSigma; }
 
 // State shared by both solver kinds.
 struct SolverBase {
@@ -793,8 +684,8 @@ struct SolverBase {
   // through; host vectors go to d_var, z, l, v uploaded (y is output only).  `check`: the solves' stride rule, on
   // host vectors only (the adjoints have checked theirs on both paths by now).
   int stage_vars(double* const* base, const long long* stride, int n, bool check, int batch, bool dev_ptrs,
-                 hipStream_t s, VarBatchArgs* v) {
-    for (int i = 0; i < 4; i++) { v->base[i] = nullptr; v->stride[i] = 0; }
+                 hipStream_t s, fbstab_var_batch_t* v) {
+    *v = fbstab_var_batch_t{};
     if (dev_ptrs) {
       for (int i = 0; i < n; i++) { v->base[i] = base[i]; v->stride[i] = stride[i]; }
       return FBSTAB_HIP_OK;
@@ -867,6 +758,19 @@ struct SolverBase {
     return FBSTAB_HIP_OK;
   }
 
+  // The bracket of the launch that last_kernel_ms reports: ev0 in front of it; behind it the launch's error,
+  // ev1, and the mark that there is a time to report.
+  int begin_timed(hipStream_t s) {
+    HIP_TRY(hipEventRecord(ev0, s));
+    return FBSTAB_HIP_OK;
+  }
+  int end_timed(hipStream_t s) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev1, s));
+    timed = true;
+    return FBSTAB_HIP_OK;
+  }
+
   double last_kernel_ms() {
     if (!timed) return -1.0;
     (void)hipSetDevice(device);
@@ -920,13 +824,12 @@ struct TraceBuf {
 struct AdjointStage {
   static constexpr int kMaxArrays = FBSTAB_MPC_NSEQ;
   static_assert(FBSTAB_DENSE_NARR <= kMaxArrays, "one slot per problem array of either kind");
-  const double* a_base[kMaxArrays];  // problem arrays
-  long long a_stride[kMaxArrays];
-  double* g_base[kMaxArrays];  // their gradients (null: not asked for, or summed over the batch)
-  long long g_stride[kMaxArrays];
+  // (the 12-slot blocks serve both kinds: a dense launch takes their first six slots, `narrowed`)
+  fbstab_mpc_batch_t a;       // problem arrays
+  fbstab_mpc_grad_batch_t g;  // their gradients (null: not asked for, or summed over the batch)
   double* r_base[kMaxArrays];  // fbstab_hip_*_adjoint_batch_reduced: where the sum over the batch goes (null: per QP)
   bool any_reduced = false;
-  VarBatchArgs v, sd, ad;  // point, seeds, adjoints
+  fbstab_var_batch_t v, sd, ad;  // point, seeds, adjoints
   int* d_st = nullptr;     // status
   hipStream_t s = nullptr;
 
@@ -965,11 +868,11 @@ struct AdjointStage {
     h_ = h; batch_ = batch; grad_base_ = grad_base; grad_stride_ = grad_stride; adj_ = adj; status_ = status;
     flags_ = flags;
     const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
-    int rc = h->stage_arrays(data_base, data_stride, batch, dev_ptrs, s, a_base, a_stride);
+    int rc = h->stage_arrays(data_base, data_stride, batch, dev_ptrs, s, a.base, a.stride);
     if (rc != FBSTAB_HIP_OK) return rc;
     rc = h->stage_vars(x->base, x->stride, 3, false, batch, dev_ptrs, s, &v);
     if (rc != FBSTAB_HIP_OK) return rc;
-    for (int i = 0; i < 4; i++) { sd.base[i] = ad.base[i] = nullptr; sd.stride[i] = ad.stride[i] = 0; }
+    sd = ad = fbstab_var_batch_t{};
     for (int i = 0; i < 3; i++) {
       if (vlen[i] == 0) continue;
       if (dev_ptrs) {
@@ -993,7 +896,7 @@ struct AdjointStage {
       const bool asked = grad_base[i] && h->arr_len[i] > 0;  // (nl == 0: the G and h slots are ignored)
       if (asked && reduced && grad_stride[i] == 0) {
         // the adjoint kernel does not write this image: fb_grad_reduce.h forms its sum from (x, adj)
-        g_base[i] = nullptr; g_stride[i] = 0;
+        g.base[i] = nullptr; g.stride[i] = 0;
         r_base[i] = grad_base[i];
         if (!dev_ptrs) {
           HIP_TRY(hipMalloc(&d_grad[i].p, sizeof(double) * (size_t)h->arr_len[i]));
@@ -1001,12 +904,12 @@ struct AdjointStage {
         }
         any_reduced = true;
       } else if (dev_ptrs) {
-        g_base[i] = asked ? grad_base[i] : nullptr; g_stride[i] = grad_stride[i];
+        g.base[i] = asked ? grad_base[i] : nullptr; g.stride[i] = grad_stride[i];
       } else if (asked) {
         HIP_TRY(hipMalloc(&d_grad[i].p, sizeof(double) * (size_t)h->arr_len[i] * batch));
-        g_base[i] = static_cast<double*>(d_grad[i].p); g_stride[i] = h->arr_len[i];
+        g.base[i] = static_cast<double*>(d_grad[i].p); g.stride[i] = h->arr_len[i];
       } else {
-        g_base[i] = nullptr; g_stride[i] = 0;
+        g.base[i] = nullptr; g.stride[i] = 0;
       }
     }
     d_st = status;
@@ -1061,9 +964,9 @@ struct AdjointStage {
   int close() {
     if (!(flags_ & FBSTAB_HIP_DEVICE_POINTERS)) {
       for (size_t i = 0; i < h_->arr_len.size(); i++)
-        if (g_base[i]) {
+        if (g.base[i]) {
           int rc = h_->download(grad_base_[i], grad_stride_[i] ? grad_stride_[i] : h_->arr_len[i], h_->arr_len[i],
-                                batch_, g_base[i], s);
+                                batch_, g.base[i], s);
           if (rc != FBSTAB_HIP_OK) return rc;
         } else if (r_base[i]) {
           int rc = h_->download(grad_base_[i], h_->arr_len[i], h_->arr_len[i], 1, r_base[i], s);
@@ -1099,8 +1002,7 @@ struct AdjointStage {
 // `close` brings a host caller's rhs back (before AdjointStage::close, which waits for the stream).
 struct TangentStage {
   static constexpr int kMaxArrays = AdjointStage::kMaxArrays;
-  const double* p_base[kMaxArrays];  // perturbations, kernel side (null: zero)
-  long long p_stride[kMaxArrays];
+  fbstab_mpc_batch_t p;  // perturbations, kernel side (null: zero)
 
   // no gradient is asked of the adjoint launch
   static double* const* no_grads() {
@@ -1138,20 +1040,20 @@ struct TangentStage {
     h_ = h; batch_ = batch; rhs_ = rhs; st_ = st;
     host_ = !(flags & FBSTAB_HIP_DEVICE_POINTERS);
     const int n = (int)h->arr_len.size();
-    for (int i = 0; i < kMaxArrays; i++) { p_base[i] = nullptr; p_stride[i] = 0; }
+    p = fbstab_mpc_batch_t{};
     for (int i = 0; i < n; i++) {
       if (!dir_base[i] || h->arr_len[i] == 0) continue;
       // (one QP: its direction is at the base, whatever the stride says)
       const long long stride = batch > 1 ? dir_stride[i] : h->arr_len[i];
       if (!host_) {
-        p_base[i] = dir_base[i]; p_stride[i] = stride;
+        p.base[i] = dir_base[i]; p.stride[i] = stride;
         continue;
       }
       HIP_TRY(hipMalloc(&d_dir[i].p, sizeof(double) * (size_t)h->arr_len[i] * (stride == 0 ? 1 : batch)));
-      int rc = h->upload(dir_base[i], stride, h->arr_len[i], batch, static_cast<double*>(d_dir[i].p), &p_stride[i],
+      int rc = h->upload(dir_base[i], stride, h->arr_len[i], batch, static_cast<double*>(d_dir[i].p), &p.stride[i],
                          st->s);
       if (rc != FBSTAB_HIP_OK) return rc;
-      p_base[i] = static_cast<double*>(d_dir[i].p);
+      p.base[i] = static_cast<double*>(d_dir[i].p);
     }
     const bool own = host_ || !rhs;
     if (own) {
@@ -1187,6 +1089,57 @@ struct TangentStage {
   int batch_ = 0;
   bool host_ = false;
 };
+
+// The dense launches' view of a stage's 12-slot block: its first six slots.
+template <class Narrow, class Wide>
+Narrow narrowed(const Wide& w) {
+  Narrow n;
+  for (int i = 0; i < FBSTAB_DENSE_NARR; i++) { n.base[i] = w.base[i]; n.stride[i] = w.stride[i]; }
+  return n;
+}
+
+// What fbstab_hip_*_adjoint_batch[_reduced] of both kinds do behind their own argument checks: stage, launch
+// (`launch`: mpc_adjoint_launch or dense_adjoint_launch), with a slot to sum the reduction around the launch, and
+// bring the results back.
+template <class Handle, class Data, class Grad>
+int adjoint_run(Handle h, int batch, const Data* data, const fbstab_var_batch_t* x,
+                       const fbstab_var_batch_t* seed, double sigma, const Grad* grad, const fbstab_var_batch_t* adj,
+                       int* status, const fbstab_solver_out_t* out, int flags, void* stream, bool reduced,
+                       const GradReducePlan& plan, int (*launch)(Handle, int, AdjointStage&, double)) {
+  AdjointStage st;
+  int rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream,
+                   reduced);
+  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
+  if (st.any_reduced) RC_TRY(st.open_reduce(plan));
+  RC_TRY(launch(h, batch, st, sigma));
+  if (st.any_reduced) RC_TRY(st.reduce(plan, out));
+  return st.close();
+}
+
+// ... and fbstab_hip_*_tangent_batch behind their checks and their LDS layout: the adjoint's staging with no seeds,
+// no gradients and adj = dx, the perturbations, the direction kernel (`kern`, launched by `launch_dir` on the staged
+// perturbations, points and seeds), the adjoint's launch behind it, and the results back.
+template <class Handle, class Data, class LaunchDir>
+int tangent_run(Handle h, int batch, const Data* data, const fbstab_var_batch_t* x, const Data* ddata,
+                       double sigma, const fbstab_var_batch_t* dx, const fbstab_var_batch_t* rhs, int* status, int flags,
+                       void* stream, const void* kern, LaunchDir launch_dir,
+                       int (*launch)(Handle, int, AdjointStage&, double)) {
+  AdjointStage st;
+  int rc = st.open(h, batch, data->base, data->stride, x, nullptr, TangentStage::no_grads(), TangentStage::no_strides(),
+                   dx, status, flags, stream);
+  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
+  TangentStage ts;
+  RC_TRY(ts.open(h, batch, ddata->base, ddata->stride, rhs, flags, &st));
+  if (!h->tan_ready) {
+    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
+    h->tan_ready = true;
+  }
+  launch_dir(ts.p, st);
+  HIP_TRY(hipGetLastError());
+  RC_TRY(launch(h, batch, st, sigma));
+  RC_TRY(ts.close());
+  return st.close();
+}
 
 int check_common(const void* handle, int batch, const void* data, const fbstab_var_batch_t* x,
                  const void* out, int max_batch) {
@@ -1264,16 +1217,26 @@ const RecordInstance* record_instance_for(int nx, int nu, int nc) {
   return nullptr;
 }
 
+// The problem data of a record kernel: the block and the problem's own sizes.
+MpcBatchPtrs record_data(const fbstab_mpc_solver* h, const fbstab_mpc_batch_t& a) {
+  return MpcBatchPtrs{a, h->lay.nx, h->lay.nu, h->lay.nc};
+}
+
+// Grid of a batch launch.  Record kernels, a batch of no more QPs than the handle has workgroups: one QP per
+// WAVEFRONT (row 0 of each; fb_record_kernel.h, R16Queue::fetch) instead of four - the rows of a wavefront share its
+// program counter and its cooperative passes, so four QPs on one wavefront finish with the slowest of them and
+// queue for each other's passes, while the chip has SIMDs to spare (round 6: batch 16, 7.9 -> ms below).  (The
+// flat-vector kernel runs one QP per workgroup: the same rule gives it min(batch, workgroups).)
+int batch_grid(const fbstab_mpc_solver* h, int batch) {
+  int grid = (batch + h->qps_per_wg - 1) / h->qps_per_wg;
+  if (batch <= h->workgroups) grid = batch;
+  return grid > h->workgroups ? h->workgroups : grid;
+}
+
 // Launches one kernel of a record instance (same argument list for all of them).
-int launch_record(fbstab_mpc_solver* h, const void* kern, int grid, hipStream_t s, const MpcBatchArgs& a,
-                  const VarBatchArgs& v, fbstab_solver_out_t* out, int batch, double* dbg, bool reuse) {
-  MpcBatchPtrs d;
-  VarBatchPtrs x;
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { d.base[i] = a.base[i]; d.stride[i] = a.stride[i]; }
-  for (int i = 0; i < 4; i++) { x.base[i] = v.base[i]; x.stride[i] = v.stride[i]; }
-  d.nx = h->lay.nx;
-  d.nu = h->lay.nu;
-  d.nc = h->lay.nc;
+int launch_record(fbstab_mpc_solver* h, const void* kern, int grid, hipStream_t s, const fbstab_mpc_batch_t& a,
+                  fbstab_var_batch_t x, fbstab_solver_out_t* out, int batch, double* dbg, bool reuse) {
+  MpcBatchPtrs d = record_data(h, a);
   int N = h->lay.N, ru = reuse ? 1 : 0;
   void* args[] = {&d, &x, &out, &h->opts, &h->scratch, &h->counter, &batch, &N, &ru, &dbg};
   HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)h->lds_bytes, s));
@@ -1450,8 +1413,8 @@ static int mpc_solve_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_bat
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
   const auto t0 = std::chrono::high_resolution_clock::now();
-  MpcBatchArgs a;
-  VarBatchArgs v;
+  fbstab_mpc_batch_t a;
+  fbstab_var_batch_t v;
   fbstab_solver_out_t* d_out;
   rc = h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride);
   if (rc != FBSTAB_HIP_OK) return rc;
@@ -1460,14 +1423,8 @@ static int mpc_solve_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_bat
   rc = h->stage_out(out, flags, &d_out);
   if (rc != FBSTAB_HIP_OK) return rc;
   HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
-  int grid = (batch + h->qps_per_wg - 1) / h->qps_per_wg;
-  // Record kernels, a batch of no more QPs than the handle has workgroups: one QP per WAVEFRONT (row 0 of
-  // each; fb_record_kernel.h, R16Queue::fetch) instead of four - the rows of a wavefront share its program
-  // counter and its cooperative passes, so four QPs on one wavefront finish with the slowest of them and
-  // queue for each other's passes, while the chip has SIMDs to spare (round 6: batch 16, 7.9 -> ms below).
-  if (h->rec && batch <= h->workgroups) grid = batch;
-  if (grid > h->workgroups) grid = h->workgroups;
-  HIP_TRY(hipEventRecord(h->ev0, s));
+  const int grid = batch_grid(h, batch);
+  RC_TRY(h->begin_timed(s));
   if (d_trace) {
     const int lds = h->lay.launch_lds_doubles * (int)sizeof(double);
     const void* kern = h->lay.wglobal
@@ -1496,17 +1453,12 @@ static int mpc_solve_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_bat
     void* args[] = {&h->lay, &a, &v, &d_out, &h->opts, &h->scratch, &h->counter, &batch, &no_dbg};
     HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(h->threads), args, (size_t)h->lds_bytes, s));
   }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev1, s));
-  h->timed = true;
+  RC_TRY(h->end_timed(s));
   if (norms) {
     double* dn;
     rc = h->stage_norms(norms, flags, &dn);
     if (rc != FBSTAB_HIP_OK) return rc;
-    MpcNormArgs na;
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { na.base[i] = a.base[i]; na.stride[i] = a.stride[i]; }
-    for (int i = 0; i < 4; i++) { na.x[i] = v.base[i]; na.xstride[i] = v.stride[i]; }
-    na.N = h->lay.N; na.nx = h->lay.nx; na.nu = h->lay.nu; na.nc = h->lay.nc;
+    const MpcNormArgs na = {a, v, h->lay.N, h->lay.nx, h->lay.nu, h->lay.nc};
     hipLaunchKernelGGL(fbstab_mpc_final_norms_kernel, dim3(batch), dim3(64), 0, s, na, h->opts, dn, batch);
     HIP_TRY(hipGetLastError());
   }
@@ -1578,8 +1530,6 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
     ev.resize(2 * (size_t)steps, nullptr);
     for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
   }
-  VarBatchArgs v;
-  for (int i = 0; i < 4; i++) { v.base[i] = x->base[i]; v.stride[i] = x->stride[i]; }
   const fbk::MpcLayout& L = h->lay;
   double* x0 = const_cast<double*>(data->base[FBSTAB_MPC_x0]);
   // Record kernels: the whole sweep is ONE launch of the KEEP instance, every row
@@ -1600,17 +1550,12 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
     DevBuf d_sa;
     HIP_TRY(hipMalloc(&d_sa.p, sizeof(SweepArgs)));
     HIP_TRY(hipMemcpyAsync(d_sa.p, &sa, sizeof(SweepArgs), hipMemcpyHostToDevice, s));
-    MpcBatchArgs a;
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { a.base[i] = data->base[i]; a.stride[i] = data->stride[i]; }
     HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
-    HIP_TRY(hipEventRecord(h->ev0, s));
+    RC_TRY(h->begin_timed(s));
     const RecordInstance& r = *h->rec;
-    rc = launch_record(h, h->exact ? r.solve_keep_exact : r.solve_keep, (batch + h->qps_per_wg - 1) / h->qps_per_wg, s,
-                       a, v, out, batch, static_cast<double*>(d_sa.p), false);
-    if (rc != FBSTAB_HIP_OK) return rc;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev1, s));
-    h->timed = true;
+    RC_TRY(launch_record(h, h->exact ? r.solve_keep_exact : r.solve_keep, (batch + h->qps_per_wg - 1) / h->qps_per_wg, s,
+                         *data, *x, out, batch, static_cast<double*>(d_sa.p), false));
+    RC_TRY(h->end_timed(s));
     h->kept_batch = batch;
     if (stats)
       HIP_TRY(hipMemcpyAsync(stats, d_stats.p, sizeof(unsigned long long) * 4 * (size_t)steps, hipMemcpyDeviceToHost, s));
@@ -1642,7 +1587,7 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
     }
     hipLaunchKernelGGL(fbstab_receding_plant_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, batch, L.nx, L.nu,
                        L.nz, L.nl, L.nv, plant->A, plant->stride_A, plant->B, plant->stride_B, x0,
-                       data->stride[FBSTAB_MPC_x0], v, out, static_cast<int*>(d_ret.p), retire,
+                       data->stride[FBSTAB_MPC_x0], *x, out, static_cast<int*>(d_ret.p), retire,
                        u_log ? u_log + (long long)k * batch * L.nu : nullptr,
                        static_cast<unsigned long long*>(d_stats.p) + 4 * k, static_cast<double*>(d_xtmp.p), lg);
   }
@@ -1679,8 +1624,8 @@ int fbstab_hip_mpc_debug_newton(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t*
   if (!h || !data || !x || !io) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  MpcBatchArgs a;
-  VarBatchArgs v;
+  fbstab_mpc_batch_t a;
+  fbstab_var_batch_t v;
   // (one packed QP whatever strides the caller wrote: the lengths stand in for them)
   int rc = h->stage_arrays(data->base, h->arr_len.data(), 1, false, s, a.base, a.stride);
   if (rc != FBSTAB_HIP_OK) return rc;
@@ -1721,15 +1666,9 @@ int fbstab_hip_mpc_debug_newton(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t*
 static int mpc_adjoint_launch(fbstab_mpc_handle_t h, int batch, AdjointStage& st, double sigma) {
   hipStream_t s = st.s;
   const fbk::MpcLayout& L = h->lay;
-  MpcBatchArgs a;
-  MpcGradArgs g;
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-    a.base[i] = st.a_base[i]; a.stride[i] = st.a_stride[i];
-    g.base[i] = st.g_base[i]; g.stride[i] = st.g_stride[i];
-  }
-  VarBatchArgs &v = st.v, &sd = st.sd, &ad = st.ad;
+  fbstab_var_batch_t &v = st.v, &sd = st.sd, &ad = st.ad;
   int* d_st = st.d_st;
-  double sig = sigma > 0.0 ? sigma : 1e-8;  // the reference's default sigma0 (fbstab_algorithm-impl.h:34)
+  double sig = sigma_or_default(sigma);
   double alpha = h->opts.alpha;
   HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
   if (h->rec && h->rec->adjoint && !h->flat_adjoint) {
@@ -1742,30 +1681,20 @@ static int mpc_adjoint_launch(fbstab_mpc_handle_t h, int batch, AdjointStage& st
       h->adj_ready = true;
     }
     h->kept_batch = -1;
-    MpcBatchPtrs d;
-    VarBatchPtrs xp;
+    MpcBatchPtrs d = record_data(h, st.a);
     AdjointArgs aa;
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-      d.base[i] = a.base[i]; d.stride[i] = a.stride[i];
-      aa.grad[i] = g.base[i]; aa.gstride[i] = g.stride[i];
-    }
-    d.nx = L.nx; d.nu = L.nu; d.nc = L.nc;
-    for (int i = 0; i < 4; i++) { xp.base[i] = v.base[i]; xp.stride[i] = v.stride[i]; }
-    for (int i = 0; i < 3; i++) {
+    aa.grad = st.g;
+    for (int i = 0; i < 3; i++) {  // (three slots wide: no y)
       aa.seed[i] = sd.base[i]; aa.sstride[i] = sd.stride[i];
       aa.adj[i] = ad.base[i]; aa.astride[i] = ad.stride[i];
     }
     aa.status = d_st;
     aa.sigma = sig;
     aa.alpha = alpha;
-    // (as the solve: a batch that does not outnumber the workgroups runs one QP per wavefront)
-    int grid = (batch + h->qps_per_wg - 1) / h->qps_per_wg;
-    if (batch <= h->workgroups) grid = batch;
-    if (grid > h->workgroups) grid = h->workgroups;
     int N = L.N;
-    void* args[] = {&d, &xp, &aa, &h->scratch, &h->counter, &batch, &N};
-    HIP_TRY(hipEventRecord(h->ev0, s));
-    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)h->lds_bytes, s));
+    void* args[] = {&d, &v, &aa, &h->scratch, &h->counter, &batch, &N};
+    RC_TRY(h->begin_timed(s));
+    HIP_TRY(hipLaunchKernel(kern, dim3(batch_grid(h, batch)), dim3(64), args, (size_t)h->lds_bytes, s));
   } else {
     // the flat-vector kernel: the handle's own workspace on flat-vector handles; on record handles (`flat_adjoint`)
     // one of its own, L.ws_doubles x workgroups doubles (fbstab_hip_mpc_query does not count it), allocated once
@@ -1783,15 +1712,12 @@ static int mpc_adjoint_launch(fbstab_mpc_handle_t h, int batch, AdjointStage& st
       HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       h->adj_ready = true;
     }
-    void* args[] = {const_cast<fbk::MpcLayout*>(&L), &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &scratch, &h->counter,
-                    &batch};
-    HIP_TRY(hipEventRecord(h->ev0, s));
+    void* args[] = {const_cast<fbk::MpcLayout*>(&L), &st.a, &v, &sd, &st.g, &ad, &d_st, &sig, &alpha, &scratch,
+                    &h->counter, &batch};
+    RC_TRY(h->begin_timed(s));
     HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(kMpcThreads), args, (size_t)lds, s));
   }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev1, s));
-  h->timed = true;
-  return FBSTAB_HIP_OK;
+  return h->end_timed(s);
 }
 
 static int mpc_adjoint_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
@@ -1801,23 +1727,9 @@ static int mpc_adjoint_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_b
   int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
   if (rc != FBSTAB_HIP_OK) return rc;
   if (!seed || !grad) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
-  AdjointStage st;
-  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream,
-               reduced);
-  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
   const fbk::MpcLayout& L = h->lay;
-  const GradReducePlan plan = grad_reduce_plan_mpc(L.N, L.nx, L.nu, L.nc);
-  if (st.any_reduced) {
-    rc = st.open_reduce(plan);
-    if (rc != FBSTAB_HIP_OK) return rc;
-  }
-  rc = mpc_adjoint_launch(h, batch, st, sigma);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  if (st.any_reduced) {
-    rc = st.reduce(plan, out);
-    if (rc != FBSTAB_HIP_OK) return rc;
-  }
-  return st.close();
+  return adjoint_run(h, batch, data, x, seed, sigma, grad, adj, status, out, flags, stream, reduced,
+                     grad_reduce_plan_mpc(L.N, L.nx, L.nu, L.nc), mpc_adjoint_launch);
 }
 
 int fbstab_hip_mpc_adjoint_batch(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
@@ -1873,15 +1785,15 @@ int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, cons
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const fbk::MpcLayout& L = h->lay;
-  const double sig = sigma > 0.0 ? sigma : 1e-8;
+  const double sig = sigma_or_default(sigma);
   const long long nz = L.nz, nl = L.nl, nv = L.nv;
   // the kernels' problem data: the x0 slot, which the Newton matrix at x = xbar does not depend on, points at the
   // states of the logged z (the record packs read SOMETHING there)
-  const double* a_base[FBSTAB_MPC_NSEQ];
-  long long a_stride[FBSTAB_MPC_NSEQ];
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { a_base[i] = data->base[i]; a_stride[i] = batch > 1 ? data->stride[i] : 0; }
-  a_base[FBSTAB_MPC_x0] = log->z;
-  a_stride[FBSTAB_MPC_x0] = nz;
+  fbstab_mpc_batch_t a = *data;
+  if (batch == 1)
+    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) a.stride[i] = 0;
+  a.base[FBSTAB_MPC_x0] = log->z;
+  a.stride[FBSTAB_MPC_x0] = nz;
   h->kept_batch = -1;  // the slots' matrix copies are overwritten
   if (sweep_adjoint_in_one_launch(h)) {
     const RecordInstance& r = *h->rec;
@@ -1894,29 +1806,20 @@ int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, cons
     if (!h->sweep_seed) HIP_TRY(hipMalloc(&h->sweep_seed, seed_bytes));
     HIP_TRY(hipMemsetAsync(h->sweep_seed, 0, seed_bytes, s));
     HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
-    MpcBatchPtrs d;
+    MpcBatchPtrs d = record_data(h, a);
     SweepAdjointArgs aa;
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-      d.base[i] = a_base[i]; d.stride[i] = a_stride[i];
-      aa.grad[i] = grad->base[i]; aa.gstride[i] = grad->stride[i];
-    }
-    d.nx = L.nx; d.nu = L.nu; d.nc = L.nc;
+    aa.grad = *grad;
     aa.A = plant->A; aa.B = plant->B; aa.sA = plant->stride_A; aa.sB = plant->stride_B;
     aa.lz = log->z; aa.ll = log->l; aa.lv = log->v; aa.le = log->eflag;
     aa.gu = gu; aa.gx = gx;
     aa.mu_log = mu_log; aa.status = status; aa.seed = h->sweep_seed;
     aa.steps = steps; aa.sigma = sig; aa.alpha = h->opts.alpha;
     // (as the adjoint: a batch that does not outnumber the workgroups runs one trajectory per wavefront)
-    int grid = (batch + h->qps_per_wg - 1) / h->qps_per_wg;
-    if (batch <= h->workgroups) grid = batch;
-    if (grid > h->workgroups) grid = h->workgroups;
     int N = L.N;
     void* args[] = {&d, &aa, &h->scratch, &h->counter, &batch, &N};
-    HIP_TRY(hipEventRecord(h->ev0, s));
-    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)h->lds_bytes, s));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev1, s));
-    h->timed = true;
+    RC_TRY(h->begin_timed(s));
+    HIP_TRY(hipLaunchKernel(kern, dim3(batch_grid(h, batch)), dim3(64), args, (size_t)h->lds_bytes, s));
+    RC_TRY(h->end_timed(s));
     HIP_TRY(hipStreamSynchronize(s));
     return FBSTAB_HIP_OK;
   }
@@ -1928,13 +1831,13 @@ int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, cons
   SweepCostateArgs ca;
   AdjointStage st;
   double* w = h->sweep_tmp;
+  ca.grad = *grad;
+  st.a = a;
   for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
     const bool wanted = grad->base[i] != nullptr || i == FBSTAB_MPC_x0;
-    ca.grad[i] = grad->base[i]; ca.gstride[i] = grad->stride[i];
     ca.len[i] = h->arr_len[i];
     ca.tmp[i] = wanted ? w : nullptr;
-    st.a_base[i] = a_base[i]; st.a_stride[i] = a_stride[i];
-    st.g_base[i] = wanted ? w : nullptr; st.g_stride[i] = h->arr_len[i];
+    st.g.base[i] = wanted ? w : nullptr; st.g.stride[i] = h->arr_len[i];
     w += h->arr_len[i] * h->max_batch;
   }
   ca.seed = w; w += nz * h->max_batch;
@@ -1946,10 +1849,7 @@ int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, cons
   ca.A = plant->A; ca.B = plant->B; ca.sA = plant->stride_A; ca.sB = plant->stride_B;
   ca.nx = L.nx; ca.nu = L.nu; ca.nz = L.nz;
   ca.eflag = nullptr; ca.gu = ca.gx = nullptr; ca.mu_log = nullptr;
-  for (int i = 0; i < 4; i++) {
-    st.v.base[i] = st.sd.base[i] = st.ad.base[i] = nullptr;
-    st.v.stride[i] = st.sd.stride[i] = st.ad.stride[i] = 0;
-  }
+  st.v = st.sd = st.ad = fbstab_var_batch_t{};
   st.sd.base[0] = ca.seed; st.sd.stride[0] = nz;
   st.d_st = tmp_status;
   st.s = s;
@@ -2001,28 +1901,12 @@ int fbstab_hip_mpc_tangent_batch(fbstab_mpc_handle_t h, int batch, const fbstab_
     return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "the perturbation images of one stage do not fit the LDS");
   if ((long long)batch * (L.N + 1) > 0x7fffffffLL)
     return fail(FBSTAB_HIP_ERR_ARGUMENT, "batch x stages exceeds the grid limit");
-  AdjointStage st;
-  rc = st.open(h, batch, data->base, data->stride, x, nullptr, TangentStage::no_grads(), TangentStage::no_strides(), dx,
-               status, flags, stream);
-  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
-  TangentStage ts;
-  rc = ts.open(h, batch, ddata->base, ddata->stride, rhs, flags, &st);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  MpcBatchArgs dir;
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { dir.base[i] = ts.p_base[i]; dir.stride[i] = ts.p_stride[i]; }
-  if (!h->tan_ready) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fbstab_tangent_rhs_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
-    h->tan_ready = true;
-  }
-  hipLaunchKernelGGL(fbstab_tangent_rhs_kernel, dim3(batch * (L.N + 1)), dim3(64), (size_t)lds, st.s, L.N, L.nx, L.nu,
-                     L.nc, o, dir, st.v, st.sd);
-  HIP_TRY(hipGetLastError());
-  rc = mpc_adjoint_launch(h, batch, st, sigma);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  rc = ts.close();
-  if (rc != FBSTAB_HIP_OK) return rc;
-  return st.close();
+  auto launch_dir = [&](const fbstab_mpc_batch_t& dir, const AdjointStage& st) {
+    hipLaunchKernelGGL(fbstab_tangent_rhs_kernel, dim3(batch * (L.N + 1)), dim3(64), (size_t)lds, st.s, L.N, L.nx, L.nu,
+                       L.nc, o, dir, st.v, st.sd);
+  };
+  return tangent_run(h, batch, data, x, ddata, sigma, dx, rhs, status, flags, stream,
+                     reinterpret_cast<const void*>(fbstab_tangent_rhs_kernel), launch_dir, mpc_adjoint_launch);
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;
@@ -2217,8 +2101,8 @@ static int dense_solve_impl(fbstab_dense_handle_t h, int batch, const fbstab_den
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
   const auto t0 = std::chrono::high_resolution_clock::now();
-  DenseBatchArgs a;
-  VarBatchArgs v;
+  fbstab_dense_batch_t a;
+  fbstab_var_batch_t v;
   fbstab_solver_out_t* d_out;
   rc = h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride);
   if (rc != FBSTAB_HIP_OK) return rc;
@@ -2228,7 +2112,7 @@ static int dense_solve_impl(fbstab_dense_handle_t h, int batch, const fbstab_den
   if (rc != FBSTAB_HIP_OK) return rc;
   HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));  // (the queue word and the kDenseFallbackSlot counters)
   int grid = h->workgroups < batch ? h->workgroups : batch;
-  HIP_TRY(hipEventRecord(h->ev0, s));
+  RC_TRY(h->begin_timed(s));
   if (d_trace && h->lay.v_global) {
     auto kern = fbstab_dense_kernel<kDenseThreads, true, true, true>;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -2272,17 +2156,12 @@ static int dense_solve_impl(fbstab_dense_handle_t h, int batch, const fbstab_den
                        h->lay, a, v, d_out, h->opts, h->counter, batch, TraceArg<false>(),
                        KScratchArg<false>());
   }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev1, s));
-  h->timed = true;
+  RC_TRY(h->end_timed(s));
   if (norms) {
     double* dn;
     rc = h->stage_norms(norms, flags, &dn);
     if (rc != FBSTAB_HIP_OK) return rc;
-    DenseNormArgs na;
-    for (int i = 0; i < FBSTAB_DENSE_NARR; i++) { na.base[i] = a.base[i]; na.stride[i] = a.stride[i]; }
-    for (int i = 0; i < 4; i++) { na.x[i] = v.base[i]; na.xstride[i] = v.stride[i]; }
-    na.nz = h->lay.nz; na.nl = h->lay.nl; na.nv = h->lay.nv;
+    const DenseNormArgs na = {a, v, h->lay.nz, h->lay.nl, h->lay.nv};
     hipLaunchKernelGGL(fbstab_dense_final_norms_kernel, dim3(batch), dim3(64), 0, s, na, h->opts, dn, batch);
     HIP_TRY(hipGetLastError());
   }
@@ -2324,8 +2203,8 @@ int fbstab_hip_dense_debug_newton(fbstab_dense_handle_t h, const fbstab_dense_ba
   if (!h->wave && h->lay.k_global) return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "dense probe: K must fit the LDS");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  DenseBatchArgs a;
-  VarBatchArgs v;
+  fbstab_dense_batch_t a;
+  fbstab_var_batch_t v;
   // (one packed QP whatever strides the caller wrote: the lengths stand in for them)
   int rc = h->stage_arrays(data->base, h->arr_len.data(), 1, false, s, a.base, a.stride);
   if (rc != FBSTAB_HIP_OK) return rc;
@@ -2366,15 +2245,11 @@ int fbstab_hip_dense_debug_newton(fbstab_dense_handle_t h, const fbstab_dense_ba
 // behind its direction kernel).
 static int dense_adjoint_launch(fbstab_dense_handle_t h, int batch, AdjointStage& st, double sigma) {
   hipStream_t s = st.s;
-  DenseBatchArgs a;
-  DenseGradArgs g;
-  for (int i = 0; i < FBSTAB_DENSE_NARR; i++) {
-    a.base[i] = st.a_base[i]; a.stride[i] = st.a_stride[i];
-    g.base[i] = st.g_base[i]; g.stride[i] = st.g_stride[i];
-  }
-  VarBatchArgs &v = st.v, &sd = st.sd, &ad = st.ad;
+  fbstab_dense_batch_t a = narrowed<fbstab_dense_batch_t>(st.a);
+  fbstab_dense_grad_batch_t g = narrowed<fbstab_dense_grad_batch_t>(st.g);
+  fbstab_var_batch_t &v = st.v, &sd = st.sd, &ad = st.ad;
   int* d_st = st.d_st;
-  double sig = sigma > 0.0 ? sigma : 1e-8;  // the reference's default sigma0 (fbstab_algorithm-impl.h:34)
+  double sig = sigma_or_default(sigma);
   double alpha = h->opts.alpha;
   // the queue word alone: the words from kDenseFallbackSlot on still describe the last solve
   // (fbstab_hip_dense_get_factorisation)
@@ -2390,7 +2265,7 @@ static int dense_adjoint_launch(fbstab_dense_handle_t h, int batch, AdjointStage
     HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
     h->adj_ready = true;
   }
-  HIP_TRY(hipEventRecord(h->ev0, s));
+  RC_TRY(h->begin_timed(s));
   if (h->wave) {
     void* args[] = {&h->wlay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch, &h->scratch};
     HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)h->lds_bytes, s));
@@ -2403,10 +2278,7 @@ static int dense_adjoint_launch(fbstab_dense_handle_t h, int batch, AdjointStage
     void* args[] = {&h->lay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch, &ks};
     HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(h->threads), args, (size_t)h->lds_bytes, s));
   }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev1, s));
-  h->timed = true;
-  return FBSTAB_HIP_OK;
+  return h->end_timed(s);
 }
 
 static int dense_adjoint_impl(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
@@ -2431,22 +2303,9 @@ static int dense_adjoint_impl(fbstab_dense_handle_t h, int batch, const fbstab_d
   }
   int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
   if (rc != FBSTAB_HIP_OK) return rc;
-  AdjointStage st;
-  rc = st.open(h, batch, data->base, data->stride, x, seed, grad->base, grad->stride, adj, status, flags, stream,
-               reduced);
-  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
-  const GradReducePlan plan = grad_reduce_plan_dense((int)h->var_len[0], (int)h->var_len[1], (int)h->var_len[2]);
-  if (st.any_reduced) {
-    rc = st.open_reduce(plan);
-    if (rc != FBSTAB_HIP_OK) return rc;
-  }
-  rc = dense_adjoint_launch(h, batch, st, sigma);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  if (st.any_reduced) {
-    rc = st.reduce(plan, out);
-    if (rc != FBSTAB_HIP_OK) return rc;
-  }
-  return st.close();
+  return adjoint_run(h, batch, data, x, seed, sigma, grad, adj, status, out, flags, stream, reduced,
+                     grad_reduce_plan_dense((int)h->var_len[0], (int)h->var_len[1], (int)h->var_len[2]),
+                     dense_adjoint_launch);
 }
 
 int fbstab_hip_dense_adjoint_batch(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
@@ -2490,28 +2349,12 @@ int fbstab_hip_dense_tangent_batch(fbstab_dense_handle_t h, int batch, const fbs
   if (!o.init(nz, nl, nv, 64 * 1024 / (int)sizeof(double)) && !o.init(nz, nl, nv, kLdsLimitBytes / (int)sizeof(double)))
     return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "not one column of the perturbation images fits the LDS");
   const int lds = o.total * (int)sizeof(double);
-  AdjointStage st;
-  rc = st.open(h, batch, data->base, data->stride, x, nullptr, TangentStage::no_grads(), TangentStage::no_strides(), dx,
-               status, flags, stream);
-  if (rc != FBSTAB_HIP_OK || batch == 0) return rc;
-  TangentStage ts;
-  rc = ts.open(h, batch, ddata->base, ddata->stride, rhs, flags, &st);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  DenseBatchArgs dir;
-  for (int i = 0; i < FBSTAB_DENSE_NARR; i++) { dir.base[i] = ts.p_base[i]; dir.stride[i] = ts.p_stride[i]; }
-  if (!h->tan_ready) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fbstab_dense_tangent_rhs_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
-    h->tan_ready = true;
-  }
-  hipLaunchKernelGGL(fbstab_dense_tangent_rhs_kernel, dim3(batch), dim3(kDenseTangentThreads), (size_t)lds, st.s, nz, nl,
-                     nv, o, dir, st.v, st.sd);
-  HIP_TRY(hipGetLastError());
-  rc = dense_adjoint_launch(h, batch, st, sigma);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  rc = ts.close();
-  if (rc != FBSTAB_HIP_OK) return rc;
-  return st.close();
+  auto launch_dir = [&](const fbstab_mpc_batch_t& dir, const AdjointStage& st) {
+    hipLaunchKernelGGL(fbstab_dense_tangent_rhs_kernel, dim3(batch), dim3(kDenseTangentThreads), (size_t)lds, st.s, nz,
+                       nl, nv, o, narrowed<fbstab_dense_batch_t>(dir), st.v, st.sd);
+  };
+  return tangent_run(h, batch, data, x, ddata, sigma, dx, rhs, status, flags, stream,
+                     reinterpret_cast<const void*>(fbstab_dense_tangent_rhs_kernel), launch_dir, dense_adjoint_launch);
 }
 
 double fbstab_hip_dense_last_kernel_ms(fbstab_dense_handle_t h) { return h ? h->last_kernel_ms() : -1.0; }

@@ -98,6 +98,7 @@ class _SweepLog(C.Structure):
 
 
 _libs: Dict[str, C.CDLL] = {}
+_torch = None  # the torch module, once load_library has imported it (device arrays need a loaded library anyway)
 _current = LIB_PATH  # the library new solver objects bind to (see `library`)
 
 
@@ -137,8 +138,10 @@ def load_library() -> C.CDLL:
     # torch (device memory / streams / torch.distributed plumbing) bundles its
     # own HIP runtime: import it first so this process ends up with ONE
     # libamdhip64 (loading ours first makes torch see "No HIP GPUs").
+    global _torch
     try:
-        import torch  # noqa: F401
+        import torch
+        _torch = torch
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
@@ -266,6 +269,92 @@ def _ptr_stride(a, length: int):
     return a.ctypes.data, (a.strides[0] // 8 if a.shape[0] > 1 else length), False
 
 
+def _fill_block(block, names, lens, arrays, B, dev_flags, optional=False, shared=True):
+    """Fills a batch, direction or gradient block (``base[i]``, ``stride[i]`` per name) from a dict of ``(rows, len)``
+    arrays and returns ``B``.  A slot of length 0 is NULL with stride 0.  ``optional``: so is an absent name or None
+    (otherwise the name is required).  ``shared``: a ``(1, len)`` array beside B > 1 QPs is shared by all of them,
+    stride 0 (otherwise the array's own row stride stands, and B = None takes the rows of the first array).  The
+    device flag of every array read goes to ``dev_flags``."""
+    for i, (k, n) in enumerate(zip(names, lens)):
+        a = None if n == 0 else (arrays.get(k) if optional else arrays[k])
+        if a is None:
+            assert n == 0 or optional, f"{k} is required"
+            block.base[i], block.stride[i] = None, 0
+            continue
+        p, st, d = _ptr_stride(a, n)
+        if B is None:
+            B = a.shape[0]
+        block.base[i], block.stride[i] = p, (_shared_stride(a, st, B) if shared else st)
+        dev_flags.append(d)
+    return B
+
+
+def _fill_vars(arrs, var_lens, B, dev_flags, optional=False, vb=None):
+    """A _VarBatch of the ``(B, n)`` arrays ``arrs`` (z, l, v[, y] or seeds, adjoints, ...); a vector of length 0 is
+    NULL.  Every other slot is required, except that with ``optional`` the slots behind the first may be None.
+    B = None: rows are not compared (the root block of a sharded call)."""
+    vb = _VarBatch() if vb is None else vb
+    for i, (a, n) in enumerate(zip(arrs, var_lens)):
+        if a is None or n == 0:
+            assert n == 0 or (optional and i > 0), "z, l, v and gz are required"
+            vb.base[i], vb.stride[i] = None, 0
+            continue
+        p, st, d = _ptr_stride(a, n)
+        assert B is None or a.shape[0] == B
+        vb.base[i], vb.stride[i] = p, st
+        dev_flags.append(d)
+    return vb
+
+
+class _Host:
+    """Allocators for what a host-pointer call returns (numpy)."""
+    on_dev = False
+
+    @staticmethod
+    def zeros(like, shape, dtype="f8"):
+        return np.zeros(shape, dtype=dtype)
+
+    @staticmethod
+    def out(like, B):
+        return np.zeros(B, dtype=OUT_DTYPE)
+
+    @staticmethod
+    def ptr(a):
+        return a.ctypes.data
+
+
+class _Device:
+    """... and a device-pointer call (torch tensors on the device of ``like``)."""
+    on_dev = True
+
+    @staticmethod
+    def zeros(like, shape, dtype="f8"):
+        return _torch.zeros(shape, dtype={"f8": _torch.float64, "i4": _torch.int32}[dtype], device=like.device)
+
+    @staticmethod
+    def out(like, B):
+        return _torch.zeros((B, 40), dtype=_torch.uint8, device=like.device)
+
+    @staticmethod
+    def ptr(a):
+        return a.data_ptr()
+
+
+def _placement(dev_flags, like, stream=0, async_=False, keep_matrices=False):
+    """Host or device?  From the device flags collected while the call's blocks were filled: ``(where, flags,
+    stream)`` - ``where`` is _Host or _Device, whose ``zeros`` / ``out`` / ``ptr`` make status, SolverOut records and
+    zero arrays where the data lives; ``flags`` the flags word of the C call; ``stream`` the caller's, or for device
+    arrays torch's current stream: the arrays were produced there (0 is the null stream, which the handle's own
+    blocking stream is ordered with)."""
+    on_dev = all(dev_flags)
+    assert on_dev or not any(dev_flags), "mix of host and device arrays"
+    if not on_dev:
+        return _Host, HOST_POINTERS, stream
+    if not stream:
+        stream = _torch.cuda.current_stream(like.device).cuda_stream
+    return _Device, DEVICE_POINTERS | (ASYNC if async_ else 0) | (KEEP_MATRICES if keep_matrices else 0), stream
+
+
 class _SolverBase:
     _kind = ""
 
@@ -308,52 +397,16 @@ class _SolverBase:
                var_lens, z, l, v, y, out, stream, async_, keep_matrices=False, norms=False):
         dev_flags = []
         B = z.shape[0]
-        for i, (k, n) in enumerate(zip(names, lens)):
-            a = arrays[k]
-            if n == 0:
-                batch_struct.base[i] = None
-                batch_struct.stride[i] = 0
-                continue
-            p, s, d = _ptr_stride(a, n)
-            batch_struct.base[i] = p
-            batch_struct.stride[i] = _shared_stride(a, s, B)
-            dev_flags.append(d)
-        vb = _VarBatch()
-        for i, (a, n) in enumerate(zip((z, l, v, y), var_lens)):
-            if n == 0:
-                vb.base[i] = None
-                vb.stride[i] = 0
-                continue
-            p, s, d = _ptr_stride(a, n)
-            assert a.shape[0] == B
-            vb.base[i] = p
-            vb.stride[i] = s
-            dev_flags.append(d)
-        on_dev = all(dev_flags)
-        assert on_dev or not any(dev_flags), "mix of host and device arrays"
-        if on_dev:
-            import torch
-            if out is None:
-                out = torch.zeros((B, 40), dtype=torch.uint8, device=z.device)
-            out_ptr = out.data_ptr()
-            if not stream:
-                # the arrays were produced on torch's current stream: run there (0 is
-                # the null stream, which the handle's own blocking stream is ordered with)
-                stream = torch.cuda.current_stream(z.device).cuda_stream
-            flags = DEVICE_POINTERS | (ASYNC if async_ else 0) | (KEEP_MATRICES if keep_matrices else 0)
-        else:
-            if out is None:
-                out = np.zeros(B, dtype=OUT_DTYPE)
-            out_ptr = out.ctypes.data
-            flags = HOST_POINTERS
+        _fill_block(batch_struct, names, lens, arrays, B, dev_flags)
+        vb = _fill_vars((z, l, v, y), var_lens, B, dev_flags)
+        where, flags, stream = _placement(dev_flags, z, stream, async_, keep_matrices)
+        if out is None:
+            out = where.out(z, B)
+        out_ptr = where.ptr(out)
         if norms:
             # fbstab_hip_*_solve_batch_final: (B, 4) |rz| |rl| |rv| tolerance, living where out lives
-            if on_dev:
-                nrm = torch.zeros((B, 4), dtype=torch.float64, device=z.device)
-                nptr = nrm.data_ptr()
-            else:
-                nrm = np.zeros((B, 4))
-                nptr = nrm.ctypes.data
+            nrm = where.zeros(z, (B, 4))
+            nptr = where.ptr(nrm)
             rc = getattr(self._lib, f"fbstab_hip_{self._kind}_solve_batch_final")(
                 self._h, B, C.byref(batch_struct), C.byref(vb), out_ptr, C.c_void_p(nptr), flags,
                 C.c_void_p(stream) if stream else None)
@@ -377,67 +430,31 @@ class _SolverBase:
             fn = getattr(self._lib, f"fbstab_hip_{self._kind}_adjoint_batch_reduced")
         dev_flags = []
         B = z.shape[0]
-        for i, (k, n) in enumerate(zip(names, lens)):
-            if n == 0:
-                batch_struct.base[i], batch_struct.stride[i] = None, 0
-                continue
-            p, st, d = _ptr_stride(data[k], n)
-            batch_struct.base[i], batch_struct.stride[i] = p, _shared_stride(data[k], st, B)
-            dev_flags.append(d)
+        _fill_block(batch_struct, names, lens, data, B, dev_flags)
         var_lens = (self.nz, self.nl, self.nv)
-
-        def var(arrs, allow_none):
-            vb = _VarBatch()
-            for i, (a, n) in enumerate(zip(arrs, var_lens)):
-                if a is None or n == 0:
-                    assert n == 0 or (allow_none and i > 0), "z, l, v and gz are required"
-                    vb.base[i], vb.stride[i] = None, 0
-                    continue
-                p, st, d = _ptr_stride(a, n)
-                assert a.shape[0] == B
-                vb.base[i], vb.stride[i] = p, st
-                dev_flags.append(d)
-            return vb
-
-        xb = var((z, l, v), False)
-        sb = var((gz, gl, gv), True)
-        on_dev = all(dev_flags)
-        assert on_dev or not any(dev_flags), "mix of host and device arrays"
-        if on_dev:
-            import torch
-            zeros = lambda n, dt=torch.float64, rows=B: torch.zeros((rows, n), dtype=dt, device=z.device)
-            if not stream:
-                stream = torch.cuda.current_stream(z.device).cuda_stream
-            flags = DEVICE_POINTERS | (ASYNC if async_ else 0)
-            status = torch.zeros(B, dtype=torch.int32, device=z.device)
-        else:
-            zeros = lambda n, dt=np.float64, rows=B: np.zeros((rows, n), dtype=dt)
-            flags = HOST_POINTERS
-            status = np.zeros(B, dtype=np.int32)
-        res = {}
-        for i, (k, n) in enumerate(zip(names, lens)):
-            grad_struct.base[i], grad_struct.stride[i] = None, 0
-            if k in reduce:
-                res[k] = zeros(n, rows=1)  # ONE array: the sum over the batch
-                if n > 0:
-                    grad_struct.base[i], grad_struct.stride[i] = _ptr_stride(res[k], n)[0], 0
-            elif k in want:
-                res[k] = zeros(n)
-                if n > 0:
-                    grad_struct.base[i], grad_struct.stride[i] = _ptr_stride(res[k], n)[:2]
+        xb = _fill_vars((z, l, v), var_lens, B, dev_flags)
+        sb = _fill_vars((gz, gl, gv), var_lens, B, dev_flags, optional=True)
+        where, flags, stream = _placement(dev_flags, z, stream, async_)
+        on_dev = where.on_dev
+        status = where.zeros(z, B, "i4")
+        # a name in `reduce` gets ONE array, the sum over the batch: stride 0 whatever B is
+        res = {k: where.zeros(z, (1 if k in reduce else B, n)) for k, n in zip(names, lens) if k in reduce or k in want}
+        _fill_block(grad_struct, names, lens, res, B, [], optional=True)
+        for k in reduce:
+            grad_struct.stride[names.index(k)] = 0
         ab = None
         if adj:
             for k, n in zip(("dz", "dl", "dv"), var_lens):
-                res[k] = zeros(n)
-            ab = var((res["dz"], res["dl"], res["dv"]), False)
+                res[k] = where.zeros(z, (B, n))
+            ab = _fill_vars((res["dz"], res["dl"], res["dv"]), var_lens, B, [])
         args = [self._h, B, C.byref(batch_struct), C.byref(xb), C.byref(sb), C.c_double(sigma), C.byref(grad_struct),
                 C.byref(ab) if ab is not None else None,
-                C.c_void_p(status.data_ptr() if on_dev else status.ctypes.data)]
+                C.c_void_p(where.ptr(status))]
         if reduce:
             # the SolverOut records of the solve, living where status lives (None: no QP is left out for its eflag)
             if out is not None:
                 assert _is_torch(out) == on_dev and out.shape[0] == B, "out lives where the arrays live"
-                args.append(C.c_void_p(out.data_ptr() if on_dev else out.ctypes.data))
+                args.append(C.c_void_p(where.ptr(out)))
             else:
                 args.append(None)
         else:
@@ -454,57 +471,26 @@ def _tangent(self, batch_struct, dir_struct, names, lens, data, z, l, v, ddata, 
     assert not unknown, unknown
     dev_flags = []
     B = z.shape[0]
-    for i, (k, n) in enumerate(zip(names, lens)):
-        batch_struct.base[i], batch_struct.stride[i] = None, 0
-        dir_struct.base[i], dir_struct.stride[i] = None, 0
-        if n == 0:
-            continue
-        p, st, d = _ptr_stride(data[k], n)
-        batch_struct.base[i], batch_struct.stride[i] = p, _shared_stride(data[k], st, B)
-        dev_flags.append(d)
-        if ddata.get(k) is not None:
-            p, st, d = _ptr_stride(ddata[k], n)
-            dir_struct.base[i], dir_struct.stride[i] = p, _shared_stride(ddata[k], st, B)
-            dev_flags.append(d)
+    _fill_block(batch_struct, names, lens, data, B, dev_flags)
+    _fill_block(dir_struct, names, lens, ddata, B, dev_flags, optional=True)
     var_lens = (self.nz, self.nl, self.nv)
-
-    def var(arrs):
-        vb = _VarBatch()
-        for i, (a, n) in enumerate(zip(arrs, var_lens)):
-            vb.base[i], vb.stride[i] = None, 0
-            if n == 0:
-                continue
-            p, st, d = _ptr_stride(a, n)
-            assert a.shape[0] == B
-            vb.base[i], vb.stride[i] = p, st
-            dev_flags.append(d)
-        return vb
-
-    xb = var((z, l, v))
-    on_dev = all(dev_flags)
-    assert on_dev or not any(dev_flags), "mix of host and device arrays"
-    if on_dev:
-        import torch
-        zeros = lambda n: torch.zeros((B, n), dtype=torch.float64, device=z.device)
-        if not stream:
-            stream = torch.cuda.current_stream(z.device).cuda_stream
-        flags = DEVICE_POINTERS | (ASYNC if async_ else 0)
-        status = torch.zeros(B, dtype=torch.int32, device=z.device)
+    xb = _fill_vars((z, l, v), var_lens, B, dev_flags)
+    where, flags, stream = _placement(dev_flags, z, stream, async_)
+    if where.on_dev:
+        zeros = lambda n: where.zeros(z, (B, n))
     else:
         zeros = lambda n: np.zeros((max(B, 1), n))[:B]   # (an empty batch keeps the strides of a row)
-        flags = HOST_POINTERS
-        status = np.zeros(B, dtype=np.int32)
+    status = where.zeros(z, B, "i4")
     res = {k: zeros(n) for k, n in zip(("dz", "dl", "dv"), var_lens)}
-    db = var((res["dz"], res["dl"], res["dv"]))
+    db = _fill_vars((res["dz"], res["dl"], res["dv"]), var_lens, B, [])
     rb = None
     if rhs:
         res.update({k: zeros(n) for k, n in zip(("gz", "gl", "gv"), var_lens)})
-        rb = var((res["gz"], res["gl"], res["gv"]))
+        rb = _fill_vars((res["gz"], res["gl"], res["gv"]), var_lens, B, [])
     fn = getattr(self._lib, f"fbstab_hip_{self._kind}_tangent_batch")
     _check(self._lib, fn(self._h, B, C.byref(batch_struct), C.byref(xb), C.byref(dir_struct), C.c_double(sigma),
                          C.byref(db), C.byref(rb) if rb is not None else None,
-                         C.c_void_p(status.data_ptr() if on_dev else status.ctypes.data), flags,
-                         C.c_void_p(stream) if stream else None))
+                         C.c_void_p(where.ptr(status)), flags, C.c_void_p(stream) if stream else None))
     res["status"] = status
     return res
 
@@ -513,21 +499,10 @@ def _solve_traced(self, batch_struct, names, lens, arrays, var_lens, z, l, v, y,
     """fbstab_hip_*_solve_traced for ONE QP in (1, n) numpy arrays.  Returns
     ``(out, records)``; records is ``(n, 8)``: kind, i0, i1, v0..v4
     (fbstab_trace_record_t, include/fbstab_types.h)."""
-    for i, (k, n) in enumerate(zip(names, lens)):
-        if n == 0:
-            batch_struct.base[i], batch_struct.stride[i] = None, 0
-            continue
-        p, st, d = _ptr_stride(arrays[k], n)
-        assert not d and arrays[k].shape[0] == 1
-        batch_struct.base[i], batch_struct.stride[i] = p, st
-    vb = _VarBatch()
-    for i, (a, n) in enumerate(zip((z, l, v, y), var_lens)):
-        if n == 0:
-            vb.base[i], vb.stride[i] = None, 0
-            continue
-        p, st, d = _ptr_stride(a, n)
-        assert not d and a.shape[0] == 1
-        vb.base[i], vb.stride[i] = p, st
+    dev_flags = []
+    B = _fill_block(batch_struct, names, lens, arrays, None, dev_flags, shared=False)
+    vb = _fill_vars((z, l, v, y), var_lens, 1, dev_flags)
+    assert B == 1 and not any(dev_flags)
     out = np.zeros(1, dtype=OUT_DTYPE)
     rec = np.zeros((capacity, 8))
     count = C.c_int(0)
@@ -536,6 +511,28 @@ def _solve_traced(self, batch_struct, names, lens, arrays, var_lens, z, l, v, y,
         C.byref(count))
     _check(self._lib, rc)
     return out, rec[:min(count.value, capacity)].copy()
+
+
+def _debug_newton(self, batch_struct, names, lens, data, z, l, v, zb, lb, vb):
+    """fbstab_hip_*_debug_newton behind ``debug_newton``: ONE QP, whatever shape its numpy arrays have."""
+    lib = self._lib
+    fn = getattr(lib, f"fbstab_hip_{self._kind}_debug_newton")
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    row = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(1, -1))
+    nz, nl, nv = self.nz, self.nl, self.nv
+    rows = {k: row(data[k]) for k, n in zip(names, lens) if n > 0}
+    _fill_block(batch_struct, names, lens, rows, 1, [])
+    xs = (row(z), row(l), row(v), np.zeros((1, nv)))
+    vb_ = _fill_vars(xs, (nz, nl, nv, nv), 1, [])
+    io = np.zeros(3 * nz + 3 * nl + 2 * nv + 1)
+    io[:nz + nl + nv] = np.concatenate([np.ravel(zb), np.ravel(lb), np.ravel(vb)])
+    _check(lib, fn(self._h, C.byref(batch_struct), C.byref(vb_), io.ctypes.data))
+    out, o = {}, 0
+    for n, sz in zip(("dz", "dl", "dv", "adz", "wz", "wl", "rz", "rl"), (nz, nl, nv, nv, nz, nl, nz, nl)):
+        out[n] = io[o:o + sz].copy()
+        o += sz
+    out["ok"] = bool(io[o] > 0.5)
+    return out
 
 
 def out_to_numpy(out) -> np.ndarray:
@@ -643,35 +640,25 @@ class FBstabMpcBatch(_SolverBase):
         (fbstab_hip_mpc_receding_sweep_logged) adds what RecedingSweepAdjoint needs, per step: ``z_log, l_log,
         v_log`` ``(steps, batch, n)`` - the point the step returned -, ``x_log`` ``(steps, batch, nx)`` - the state
         it was solved for - and ``eflag_log`` ``(steps, batch)`` int32, -1 once a trajectory is retired."""
-        import torch
-        b = _MpcBatch()
-        B_ = None
-        for i, (k, n) in enumerate(zip(MPC_SEQ, self.seq_len)):
-            p, st, d = _ptr_stride(data[k], n)
-            assert d, "device tensors only"
-            b.base[i], b.stride[i] = p, st
-            B_ = data[k].shape[0] if B_ is None else B_
-        vb = _VarBatch()
-        for i, (a, n) in enumerate(zip((z, l, v, y), (self.nz, self.nl, self.nv, self.nv))):
-            p, st, d = _ptr_stride(a, n)
-            assert d and a.shape[0] == B_
-            vb.base[i], vb.stride[i] = p, st
+        b, dev_flags = _MpcBatch(), []
+        B_ = _fill_block(b, MPC_SEQ, self.seq_len, data, None, dev_flags, shared=False)
+        vb = _fill_vars((z, l, v, y), (self.nz, self.nl, self.nv, self.nv), B_, dev_flags)
+        assert all(dev_flags), "device tensors only"
+        where, _, stream = _placement(dev_flags, z, stream)
         dev = z.device
         plant, plant_keep = self._plant(A, B, dev)   # column-major images
-        out = torch.zeros((B_, 40), dtype=torch.uint8, device=dev)
+        out = where.out(z, B_)
         stats = np.zeros((steps, 4), dtype=np.uint64)
         kms = np.zeros(steps, dtype=np.float32)
-        u = torch.zeros((steps, B_, self.nu), dtype=torch.float64, device=dev) if log_inputs else None
-        if not stream:
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        u = where.zeros(z, (steps, B_, self.nu)) if log_inputs else None
         args = [self._h, B_, C.byref(b), C.byref(vb), out.data_ptr(), C.byref(plant), steps, 1 if retire else 0,
                 u.data_ptr() if u is not None else None, stats.ctypes.data, kms.ctypes.data,
                 C.c_void_p(stream) if stream else None]
         logs = {}
         if log:
             for k, n in (("z_log", self.nz), ("l_log", self.nl), ("v_log", self.nv), ("x_log", self.nx)):
-                logs[k] = torch.zeros((steps, B_, n), dtype=torch.float64, device=dev)
-            logs["eflag_log"] = torch.zeros((steps, B_), dtype=torch.int32, device=dev)
+                logs[k] = where.zeros(z, (steps, B_, n))
+            logs["eflag_log"] = where.zeros(z, (steps, B_), "i4")
             lg = _SweepLog(*[logs[k].data_ptr() for k in ("z_log", "l_log", "v_log", "x_log", "eflag_log")])
             _check(self._lib, self._lib.fbstab_hip_mpc_receding_sweep_logged(*args, C.byref(lg)))
         else:
@@ -704,14 +691,11 @@ class FBstabMpcBatch(_SolverBase):
         zl = log["z_log"]
         dev, B_ = zl.device, zl.shape[1]
         assert zl.is_cuda and zl.shape == (steps, B_, self.nz), "the log of RecedingSweep(..., log=True) on the device"
-        b = _MpcBatch()
-        for i, (k, n) in enumerate(zip(MPC_SEQ, self.seq_len)):
-            if k == "x0":
-                b.base[i], b.stride[i] = None, 0
-                continue
-            p, st, d = _ptr_stride(data[k], n)
-            assert d, "device tensors only"
-            b.base[i], b.stride[i] = p, _shared_stride(data[k], st, B_)
+        b, dev_flags = _MpcBatch(), []
+        # (the x0 slot stays NULL: it is not read)
+        _fill_block(b, MPC_SEQ[:-1], self.seq_len[:-1], data, B_, dev_flags)
+        assert all(dev_flags), "device tensors only"
+        where, _, stream = _placement(dev_flags, zl, stream)
         keep = []
 
         def arr(a, shape, dt):
@@ -727,17 +711,11 @@ class FBstabMpcBatch(_SolverBase):
                        arr(log["v_log"], (steps, B_, self.nv), torch.float64), None,
                        arr(log["eflag_log"], (steps, B_), torch.int32))
         plant, plant_keep = self._plant(A, B, dev)
-        res = {}
+        res = {k: where.zeros(zl, (B_, n)) for k, n in zip(MPC_SEQ, self.seq_len) if k in want}
         g = _MpcGradBatch()
-        for i, (k, n) in enumerate(zip(MPC_SEQ, self.seq_len)):
-            g.base[i], g.stride[i] = None, 0
-            if k in want:
-                res[k] = torch.zeros((B_, n), dtype=torch.float64, device=dev)
-                g.base[i], g.stride[i] = res[k].data_ptr(), n
-        status = torch.zeros(B_, dtype=torch.int32, device=dev)
-        mu_log = torch.zeros((steps, B_, self.nx), dtype=torch.float64, device=dev) if mu else None
-        if not stream:
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        _fill_block(g, MPC_SEQ, self.seq_len, res, B_, [], optional=True, shared=False)
+        status = where.zeros(zl, B_, "i4")
+        mu_log = where.zeros(zl, (steps, B_, self.nx)) if mu else None
         _check(self._lib, self._lib.fbstab_hip_mpc_receding_sweep_adjoint(
             self._h, B_, C.byref(b), C.byref(plant), steps, 1 if retire else 0, C.byref(lg),
             arr(gu, (steps, B_, self.nu), torch.float64), arr(gx, (steps, B_, self.nx), torch.float64),
@@ -754,33 +732,7 @@ class FBstabMpcBatch(_SolverBase):
         """Tests only: one Newton step of the device path at (x, xbar,
         sigma0, alpha of the current options) for ONE QP (numpy arrays).
         Returns dict(dz, dl, dv, adz, wz, wl, rz, rl, ok)."""
-        lib = self._lib
-        lib.fbstab_hip_mpc_debug_newton.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        b = _MpcBatch()
-        keep = []
-        for i, k in enumerate(MPC_SEQ):
-            a = np.ascontiguousarray(np.asarray(data[k], dtype=np.float64).reshape(-1))
-            keep.append(a)
-            b.base[i] = a.ctypes.data
-            b.stride[i] = a.size
-        vb_ = _VarBatch()
-        xs = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)) for a in (z, l, v)]
-        xs.append(np.zeros(self.nv))
-        for i, a in enumerate(xs):
-            vb_.base[i] = a.ctypes.data
-            vb_.stride[i] = a.size
-        nz, nl, nv = self.nz, self.nl, self.nv
-        io = np.zeros(3 * nz + 3 * nl + 2 * nv + 1)
-        io[:nz + nl + nv] = np.concatenate([np.ravel(zb), np.ravel(lb), np.ravel(vb)])
-        _check(lib, lib.fbstab_hip_mpc_debug_newton(self._h, C.byref(b), C.byref(vb_), io.ctypes.data))
-        names = ("dz", "dl", "dv", "adz", "wz", "wl", "rz", "rl")
-        sizes = (nz, nl, nv, nv, nz, nl, nz, nl)
-        out, o = {}, 0
-        for n, s in zip(names, sizes):
-            out[n] = io[o:o + s].copy()
-            o += s
-        out["ok"] = bool(io[o] > 0.5)
-        return out
+        return _debug_newton(self, _MpcBatch(), MPC_SEQ, self.seq_len, data, z, l, v, zb, lb, vb)
 
     def Adjoint(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0,
                 want: Optional[Sequence[str]] = None, adj: bool = False, stream: int = 0,
@@ -852,37 +804,7 @@ class FBstabDenseBatch(_SolverBase):
         """Tests only: one Newton step of the dense device path at (x, xbar, sigma0,
         alpha of the current options) for ONE QP (numpy arrays).  Returns
         dict(dz, dl, dv, adz, wz, wl, rz, rl, ok)."""
-        lib = self._lib
-        lib.fbstab_hip_dense_debug_newton.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        b = _DenseBatch()
-        keep = []
-        for i, k in enumerate(DENSE_ARR):
-            a = np.ascontiguousarray(np.asarray(data[k], dtype=np.float64).reshape(-1))
-            if a.size == 0:
-                a = np.zeros(1)
-            keep.append(a)
-            b.base[i] = a.ctypes.data
-            b.stride[i] = a.size
-        vb_ = _VarBatch()
-        xs = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)) for a in (z, l, v)]
-        xs.append(np.zeros(self.nv))
-        for i, a in enumerate(xs):
-            if a.size == 0:
-                a = xs[i] = np.zeros(1)
-            vb_.base[i] = a.ctypes.data
-            vb_.stride[i] = a.size
-        nz, nl, nv = self.nz, self.nl, self.nv
-        io = np.zeros(3 * nz + 3 * nl + 2 * nv + 1)
-        io[:nz + nl + nv] = np.concatenate([np.ravel(zb), np.ravel(lb), np.ravel(vb)])
-        _check(lib, lib.fbstab_hip_dense_debug_newton(self._h, C.byref(b), C.byref(vb_), io.ctypes.data))
-        names = ("dz", "dl", "dv", "adz", "wz", "wl", "rz", "rl")
-        sizes = (nz, nl, nv, nv, nz, nl, nz, nl)
-        out, o = {}, 0
-        for n, sz in zip(names, sizes):
-            out[n] = io[o:o + sz].copy()
-            o += sz
-        out["ok"] = bool(io[o] > 0.5)
-        return out
+        return _debug_newton(self, _DenseBatch(), DENSE_ARR, self.arr_len, data, z, l, v, zb, lb, vb)
 
     def SolveTraced(self, data, z, l, v, y, capacity: int = 4096):
         """One QP (``(1, n)`` numpy arrays) with the reference's per-iteration
@@ -953,17 +875,10 @@ class ShardGroup:
         op = (C.c_void_p * n)()
         var_lens = (solvers[0].nz, solvers[0].nl, solvers[0].nv, solvers[0].nv)
         for d in range(n):
-            B = None
-            for i, (k, ln) in enumerate(zip(names, lens)):
-                if ln == 0:
-                    bs[d].base[i], bs[d].stride[i] = None, 0
-                    continue
-                p, st, dev = _ptr_stride(data[d][k], ln)
-                assert dev
-                bs[d].base[i], bs[d].stride[i] = p, st
-                B = data[d][k].shape[0] if B is None else B
-            _fill_var(vs[d], xs[d], var_lens)
-            counts[d] = B
+            dev_flags = []
+            counts[d] = _fill_block(bs[d], names, lens, data[d], None, dev_flags, shared=False)
+            _fill_vars(xs[d], var_lens, counts[d], dev_flags, vb=vs[d])
+            assert all(dev_flags)
             op[d] = outs[d].data_ptr()
         return kind, bs, vs, counts, hs, op, var_lens
 
@@ -973,8 +888,9 @@ class ShardGroup:
         on ``devices[root]``."""
         names, lens = (MPC_SEQ, solvers[0].seq_len) if solvers[0]._kind == "mpc" else (DENSE_ARR, solvers[0].arr_len)
         kind, bs, vs, counts, hs, op, var_lens = self._shards(solvers, names, lens, data, xs, outs)
-        rv = _VarBatch()
-        _fill_var(rv, root_x, var_lens)
+        dev_flags = []
+        rv = _fill_vars(root_x, var_lens, None, dev_flags)
+        assert all(dev_flags)
         _check(self._lib, getattr(self._lib, f"fbstab_hip_{kind}_solve_batch_sharded")(
             self._g, hs, counts, bs, vs, op, root, C.byref(rv), C.c_void_p(root_out.data_ptr())))
 
@@ -1000,12 +916,3 @@ class ShardGroup:
             C.c_void_p(root_u_log.data_ptr()), stats.ctypes.data))
         return stats
 
-
-def _fill_var(vb, x, var_lens):
-    for i, (a, n) in enumerate(zip(x, var_lens)):
-        if n == 0:
-            vb.base[i], vb.stride[i] = None, 0
-            continue
-        p, st, dev = _ptr_stride(a, n)
-        assert dev
-        vb.base[i], vb.stride[i] = p, st

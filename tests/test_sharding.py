@@ -459,8 +459,7 @@ def test_sharded_entry_rejects_a_bad_shard_before_anything_is_queued(monkeypatch
     g = hip_api.ShardGroup([0, 0])
     solvers = [hip_api.FBstabMpcBatch(*p.sizes(), max_batch=B) for _ in range(2)]
     kind, bs, vs, counts, hs, op, var_lens = g._shards(solvers, hip_api.MPC_SEQ, solvers[0].seq_len, shard, xs, outs)
-    rv = hip_api._VarBatch()
-    hip_api._fill_var(rv, root_x, var_lens)
+    rv = hip_api._fill_vars(root_x, var_lens, 2 * B, [])
     lib = hip_api.load_library()
     bs[1].base[3] = None  # shard 1's q sequence
     rc = lib.fbstab_hip_mpc_solve_batch_sharded(g._g, hs, counts, bs, vs, op, 0, C.byref(rv), C.c_void_p(root_out.data_ptr()))
