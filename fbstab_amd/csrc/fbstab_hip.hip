@@ -614,13 +614,15 @@ struct SolverBase {
     return FBSTAB_HIP_OK;
   }
 
-  // Host batch array -> packed device array (stride = len); stride 0 is kept.
+  // Host batch array -> packed device array (stride = len); stride 0 is kept.  One QP is at the base whatever the
+  // stride says (include/fbstab_hip.h): the length stands in for it, here and in `download`.
   int upload(const double* host, long long stride, long long len, int batch, double* dev,
              long long* dev_stride, hipStream_t s) {
     if (len == 0) {
       *dev_stride = 0;
       return FBSTAB_HIP_OK;
     }
+    if (batch == 1) stride = len;
     if (stride == 0) {
       HIP_TRY(hipMemcpyAsync(dev, host, sizeof(double) * len, hipMemcpyHostToDevice, s));
       *dev_stride = 0;
@@ -637,6 +639,7 @@ struct SolverBase {
   int download(double* host, long long stride, long long len, int batch, const double* dev,
                hipStream_t s) {
     if (len == 0) return FBSTAB_HIP_OK;
+    if (batch == 1) stride = len;
     if (stride == len) {
       HIP_TRY(hipMemcpyAsync(host, dev, sizeof(double) * len * batch, hipMemcpyDeviceToHost, s));
     } else {
@@ -652,8 +655,25 @@ struct SolverBase {
     return !(flags & FBSTAB_HIP_DEVICE_POINTERS) || (flags & FBSTAB_HIP_OUT_ON_HOST);
   }
 
-  // Problem arrays in: the caller's arr_len.size() base / stride pairs -> the kernel-side ones.  Device pointers
-  // pass through; host arrays are checked and packed into d_arr.
+  // The stride rule of the caller's problem arrays, on both pointer paths: with batch > 1 an array is shared by the
+  // batch (stride 0) or every QP has its own (stride >= length; a negative stride is neither).  `skip`: a slot with
+  // a rule of its own (the sweeps' x0), or -1.
+  int check_data_strides(const long long* stride, int batch, int skip = -1) const {
+    for (int i = 0; i < (int)arr_len.size(); i++)
+      if (batch > 1 && i != skip && stride[i] != 0 && stride[i] < arr_len[i])
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
+    return FBSTAB_HIP_OK;
+  }
+
+  // The stride rule of a solve, before any device call: the problem arrays, and all of (z, l, v, y).
+  int check_solve_strides(const long long* data_stride, const long long* var_stride, int batch, int skip = -1) const {
+    int rc = check_data_strides(data_stride, batch, skip);
+    for (int i = 0; i < 4 && rc == FBSTAB_HIP_OK; i++) rc = check_var_stride(var_stride, i, batch);
+    return rc;
+  }
+
+  // Problem arrays in: the caller's arr_len.size() base / stride pairs -> the kernel-side ones (the caller has
+  // checked the strides).  Device pointers pass through; host arrays are packed into d_arr.
   int stage_arrays(const double* const* base, const long long* stride, int batch, bool dev_ptrs, hipStream_t s,
                    const double** kbase, long long* kstride) {
     const int n = (int)arr_len.size();
@@ -664,8 +684,6 @@ struct SolverBase {
     int rc = ensure_staging();
     if (rc != FBSTAB_HIP_OK) return rc;
     for (int i = 0; i < n; i++) {
-      if (stride[i] != 0 && stride[i] < arr_len[i] && batch > 1)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
       rc = upload(base[i], stride[i], arr_len[i], batch, d_arr[i], &kstride[i], s);
       if (rc != FBSTAB_HIP_OK) return rc;
       kbase[i] = d_arr[i];
@@ -681,9 +699,8 @@ struct SolverBase {
   }
 
   // Variables in: the first n vectors of the caller's (z, l, v, y) -> v (the others null).  Device pointers pass
-  // through; host vectors go to d_var, z, l, v uploaded (y is output only).  `check`: the solves' stride rule, on
-  // host vectors only (the adjoints have checked theirs on both paths by now).
-  int stage_vars(double* const* base, const long long* stride, int n, bool check, int batch, bool dev_ptrs,
+  // through; host vectors go to d_var, z, l, v uploaded (y is output only).  The caller has checked the strides.
+  int stage_vars(double* const* base, const long long* stride, int n, int batch, bool dev_ptrs,
                  hipStream_t s, fbstab_var_batch_t* v) {
     *v = fbstab_var_batch_t{};
     if (dev_ptrs) {
@@ -693,10 +710,6 @@ struct SolverBase {
     int rc = ensure_staging();
     if (rc != FBSTAB_HIP_OK) return rc;
     for (int i = 0; i < n; i++) {
-      if (check) {
-        rc = check_var_stride(stride, i, batch);
-        if (rc != FBSTAB_HIP_OK) return rc;
-      }
       if (i < 3) {
         long long st;
         rc = upload(base[i], stride[i] ? stride[i] : var_len[i], var_len[i], batch, d_var[i], &st, s);
@@ -858,6 +871,10 @@ struct AdjointStage {
       if (batch > 1 && adj && adj->base[i] && adj->stride[i] < vlen[i])
         return fail(FBSTAB_HIP_ERR_ARGUMENT, "adjoint stride smaller than the vector length");
     }
+    {
+      int rc = h->check_data_strides(data_stride, batch);
+      if (rc != FBSTAB_HIP_OK) return rc;
+    }
     for (int i = 0; i < n; i++)
       if (batch > 1 && grad_base[i] && grad_stride[i] < h->arr_len[i] && !(reduced && grad_stride[i] == 0))
         return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
@@ -870,7 +887,7 @@ struct AdjointStage {
     const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
     int rc = h->stage_arrays(data_base, data_stride, batch, dev_ptrs, s, a.base, a.stride);
     if (rc != FBSTAB_HIP_OK) return rc;
-    rc = h->stage_vars(x->base, x->stride, 3, false, batch, dev_ptrs, s, &v);
+    rc = h->stage_vars(x->base, x->stride, 3, batch, dev_ptrs, s, &v);
     if (rc != FBSTAB_HIP_OK) return rc;
     sd = ad = fbstab_var_batch_t{};
     for (int i = 0; i < 3; i++) {
@@ -1408,6 +1425,8 @@ static int mpc_solve_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_bat
     if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
   for (int i = 0; i < 4; i++)
     if (!x->base[i] && h->var_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
+  rc = h->check_solve_strides(data->stride, x->stride, batch);
+  if (rc != FBSTAB_HIP_OK) return rc;
   if (batch == 0) return FBSTAB_HIP_OK;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -1418,7 +1437,7 @@ static int mpc_solve_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_bat
   fbstab_solver_out_t* d_out;
   rc = h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride);
   if (rc != FBSTAB_HIP_OK) return rc;
-  rc = h->stage_vars(x->base, x->stride, 4, true, batch, dev_ptrs, s, &v);
+  rc = h->stage_vars(x->base, x->stride, 4, batch, dev_ptrs, s, &v);
   if (rc != FBSTAB_HIP_OK) return rc;
   rc = h->stage_out(out, flags, &d_out);
   if (rc != FBSTAB_HIP_OK) return rc;
@@ -1509,10 +1528,8 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
   // x0 is advanced in place, one state per trajectory: a shared x0 would be written by all of them
   if (batch > 1 && data->stride[FBSTAB_MPC_x0] < h->lay.nx)
     return fail(FBSTAB_HIP_ERR_ARGUMENT, "receding sweep: every trajectory needs its own x0 (stride >= nx)");
-  for (int i = 0; i < 4; i++) {
-    rc = h->check_var_stride(x->stride, i, batch);
-    if (rc != FBSTAB_HIP_OK) return rc;
-  }
+  rc = h->check_solve_strides(data->stride, x->stride, batch, FBSTAB_MPC_x0);
+  if (rc != FBSTAB_HIP_OK) return rc;
   if (batch == 0 || steps == 0) return FBSTAB_HIP_OK;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -1629,7 +1646,7 @@ int fbstab_hip_mpc_debug_newton(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t*
   // (one packed QP whatever strides the caller wrote: the lengths stand in for them)
   int rc = h->stage_arrays(data->base, h->arr_len.data(), 1, false, s, a.base, a.stride);
   if (rc != FBSTAB_HIP_OK) return rc;
-  rc = h->stage_vars(x->base, h->var_len, 4, false, 1, false, s, &v);
+  rc = h->stage_vars(x->base, h->var_len, 4, 1, false, s, &v);
   if (rc != FBSTAB_HIP_OK) return rc;
   const fbk::MpcLayout& L = h->lay;
   const size_t n_io = (size_t)(3 * L.nz + 3 * L.nl + 2 * L.nv + 1);
@@ -2096,6 +2113,8 @@ static int dense_solve_impl(fbstab_dense_handle_t h, int batch, const fbstab_den
       return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
   for (int i = 0; i < 4; i++)
     if (!x->base[i] && h->var_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
+  rc = h->check_solve_strides(data->stride, x->stride, batch);
+  if (rc != FBSTAB_HIP_OK) return rc;
   if (batch == 0) return FBSTAB_HIP_OK;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -2106,7 +2125,7 @@ static int dense_solve_impl(fbstab_dense_handle_t h, int batch, const fbstab_den
   fbstab_solver_out_t* d_out;
   rc = h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride);
   if (rc != FBSTAB_HIP_OK) return rc;
-  rc = h->stage_vars(x->base, x->stride, 4, true, batch, dev_ptrs, s, &v);
+  rc = h->stage_vars(x->base, x->stride, 4, batch, dev_ptrs, s, &v);
   if (rc != FBSTAB_HIP_OK) return rc;
   rc = h->stage_out(out, flags, &d_out);
   if (rc != FBSTAB_HIP_OK) return rc;
@@ -2208,7 +2227,7 @@ int fbstab_hip_dense_debug_newton(fbstab_dense_handle_t h, const fbstab_dense_ba
   // (one packed QP whatever strides the caller wrote: the lengths stand in for them)
   int rc = h->stage_arrays(data->base, h->arr_len.data(), 1, false, s, a.base, a.stride);
   if (rc != FBSTAB_HIP_OK) return rc;
-  rc = h->stage_vars(x->base, h->var_len, 4, false, 1, false, s, &v);
+  rc = h->stage_vars(x->base, h->var_len, 4, 1, false, s, &v);
   if (rc != FBSTAB_HIP_OK) return rc;
   const fbk::DenseLayout& L = h->lay;
   const size_t n_io = (size_t)(3 * L.nz + 3 * L.nl + 2 * L.nv + 1);

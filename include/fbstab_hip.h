@@ -34,6 +34,9 @@
  * and one stride (in doubles) per array: QP b lives at base + b*stride, so both
  * "array of structures" (all sequences of a QP contiguous) and "structure of
  * arrays" placements work, and a stride of 0 shares an array across the batch.
+ * A batch of one QP lives at the base pointers: no entry point reads a stride
+ * when batch == 1 (but for the gradient slots of fbstab_hip_*_adjoint_batch_reduced,
+ * where a stride of 0 asks for the sum over the batch at every batch size).
  *
  * Error behaviour: no exception crosses this boundary.  Functions return
  * FBSTAB_HIP_OK or an error code and fbstab_hip_last_error() describes the
@@ -165,7 +168,16 @@ int fbstab_hip_mpc_get_options(fbstab_mpc_handle_t handle, fbstab_options_t* opt
 /* stream: a hipStream_t, or NULL for the handle's own stream, which is a blocking
  * stream (ordered against the device's null stream both ways).  With
  * FBSTAB_HIP_DEVICE_POINTERS the caller's arrays must be ready on the stream the
- * call runs on: work queued on another non-blocking stream needs an event. */
+ * call runs on: work queued on another non-blocking stream needs an event.
+ * Strides, with batch > 1 (host and device pointers alike, checked before anything
+ * is queued; the same rule holds for fbstab_hip_mpc_solve_batch_final, the receding
+ * sweeps, the dense solves and the sharded entry points, which call these):
+ *   x:    every QP has its own z, l, v and y: a stride below the vector length is
+ *         FBSTAB_HIP_ERR_ARGUMENT.
+ *   data: a stride of 0 shares the array, a stride of at least the array length gives
+ *         every QP its own; any other stride, a negative one included, is
+ *         FBSTAB_HIP_ERR_ARGUMENT.  (The sweeps advance x0 in place: its stride is at
+ *         least nx.) */
 int fbstab_hip_mpc_solve_batch(fbstab_mpc_handle_t handle, int batch,
                                const fbstab_mpc_batch_t* data, const fbstab_var_batch_t* x,
                                fbstab_solver_out_t* out, int flags, void* stream);
