@@ -1,8 +1,8 @@
 // The record kernels' entry point and queue (fb_mpc_r16.h holds the numerics), shared by
 // the translation units of the library: every instance <NX, NU, NC, R> is compiled in a
 // file of its own (rec_*.hip, a minute or two each, in parallel under `make -j`) and
-// hands fbstab_hip.hip a RecordInstance with the addresses of its kernels (six of the solve, two of the adjoint,
-// two of the sweep adjoint).
+// hands fbstab_hip.hip a RecordInstance with the addresses of its kernels (a padded and an exact set: three of
+// the solve, the adjoint and the sweep adjoint each).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -16,21 +16,23 @@
 #define FB_ANY_STAMP 1
 #endif
 
-// One compiled instance of the record kernel family: its entry points (batch,
-// FBSTAB_HIP_KEEP_MATRICES, Newton-step probe) and its footprint.
+// The kernels of one flavour of an instance: batch solve, FBSTAB_HIP_KEEP_MATRICES solve, Newton-step probe,
+// fbstab_hip_mpc_adjoint_batch on the record (fbstab_mpc_r16_adjoint_kernel) and
+// fbstab_hip_mpc_receding_sweep_adjoint on the record (fbstab_mpc_r16_sweep_adjoint_kernel).
+struct RecordKernels {
+  const void *solve, *solve_keep, *probe, *adjoint, *sweep_adjoint;
+};
+
+// One compiled instance of the record kernel family: its entry points and its footprint.
 struct RecordInstance {
   const char* name;
   int nx, nu, nc;        // largest problem it runs (smaller ones zero-padded)
   int qps_per_wg;
   int (*lds_bytes)(int N);
   long long (*ws_doubles)(int N);
-  const void *solve, *solve_keep, *probe;  // kernels of the padded instance
-  const void *solve_exact, *solve_keep_exact, *probe_exact;  // problem == instance shape
-  // fbstab_hip_mpc_adjoint_batch on the record (fbstab_mpc_r16_adjoint_kernel) and the name it is reported under
-  const void *adjoint, *adjoint_exact;
-  const char* adjoint_name;
-  // fbstab_hip_mpc_receding_sweep_adjoint on the record (fbstab_mpc_r16_sweep_adjoint_kernel)
-  const void *sweep_adjoint, *sweep_adjoint_exact;
+  RecordKernels padded;  // kernels of the padded instance
+  RecordKernels exact;   // problem == instance shape
+  const char* adjoint_name;        // the names the adjoint and the sweep adjoint are reported under
   const char* sweep_adjoint_name;
 };
 
@@ -538,6 +540,17 @@ int r16_lds_bytes(int N) {
   typedef fbk::MpcR16<NX, NU, NC, true, false, R> P;
   return (P::kPackArea + P::kQpPerWave * P::kLdsPerRow) * (int)sizeof(double) + P::kQpPerWave * P::lpo_ints(N) * (int)sizeof(int);
 }
+// The address of a kernel as the launch API and the handles' tables take it.
+template <class Kernel>
+const void* kernel_ptr(Kernel* k) { return reinterpret_cast<const void*>(k); }
+
+// The solve kernels of one flavour.
+template <int NX, int NU, int NC, int R, bool EXACT>
+void r16_solve_kernels(RecordKernels* k) {
+  k->solve = kernel_ptr(fbstab_mpc_r16_kernel<NX, NU, NC, false, EXACT, false, R>);
+  k->solve_keep = kernel_ptr(fbstab_mpc_r16_kernel<NX, NU, NC, false, EXACT, true, R>);
+  k->probe = kernel_ptr(fbstab_mpc_r16_kernel<NX, NU, NC, true, EXACT, false, R>);
+}
 // R: 16-lane rows of the wavefront per QP (1: four QPs per wavefront, stage width
 // <= 16; 2: two QPs per wavefront, stage width <= 32)
 template <int NX, int NU, int NC, int R = 1>
@@ -550,16 +563,15 @@ RecordInstance r16_instance(const char* name, const char* adjoint_name, const ch
   r.qps_per_wg = 4 / R;
   r.lds_bytes = r16_lds_bytes<NX, NU, NC, R>;
   r.ws_doubles = r16_ws_doubles<NX, NU, NC, R>;
-  r.solve = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, false, false, false, R>);
-  r.solve_keep = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, false, false, true, R>);
-  r.probe = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, true, false, false, R>);
-  r.solve_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, false, true, false, R>);
-  r.solve_keep_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, false, true, true, R>);
-  r.probe_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_kernel<NX, NU, NC, true, true, false, R>);
-  r.adjoint = reinterpret_cast<const void*>(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, false, R>);
-  r.adjoint_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, true, R>);
-  r.sweep_adjoint = reinterpret_cast<const void*>(fbstab_mpc_r16_sweep_adjoint_kernel<NX, NU, NC, false, R>);
-  r.sweep_adjoint_exact = reinterpret_cast<const void*>(fbstab_mpc_r16_sweep_adjoint_kernel<NX, NU, NC, true, R>);
+  // (the kernels are named in the order the compiler has always met them - the solve kernels of both flavours, the
+  // adjoints, the sweep adjoints: the code of some solve kernels, and the build's register report, depend on it;
+  // tools/diff_device_code.py)
+  r16_solve_kernels<NX, NU, NC, R, false>(&r.padded);
+  r16_solve_kernels<NX, NU, NC, R, true>(&r.exact);
+  r.padded.adjoint = kernel_ptr(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, false, R>);
+  r.exact.adjoint = kernel_ptr(fbstab_mpc_r16_adjoint_kernel<NX, NU, NC, true, R>);
+  r.padded.sweep_adjoint = kernel_ptr(fbstab_mpc_r16_sweep_adjoint_kernel<NX, NU, NC, false, R>);
+  r.exact.sweep_adjoint = kernel_ptr(fbstab_mpc_r16_sweep_adjoint_kernel<NX, NU, NC, true, R>);
   return r;
 }
 

@@ -508,6 +508,31 @@ int fail(int code, const std::string& msg) {
 constexpr double kDefaultSigma = 1e-8;
 double sigma_or_default(double sigma) { return sigma > 0.0 ? sigma : kDefaultSigma; }
 
+// One operation of a handle (solve, traced solve, probe, adjoint, ...) as the handle's creation resolved it
+// (mpc_resolve_kernels, dense_resolve_kernels): the launch sites read the entry, and none of them asks the layout,
+// the record instance or the environment again which compiled kernel serves the handle.
+struct KernelEntry {
+  const void* kern = nullptr;  // null: this handle does not run the operation
+  const char* name = "";       // what the *_kernel_name functions report (the operations that have one)
+  int block = 0;
+  int lds = 0;           // dynamic LDS bytes of the launch
+  bool lds_set = false;  // this handle has set the kernel's LDS attribute to `lds` (as tan_ready below: the attribute
+                         // belongs to the kernel, and the value of the handle that set it last stands)
+};
+
+hipError_t set_lds_attribute(KernelEntry& e) {
+  const hipError_t err = hipFuncSetAttribute(e.kern, hipFuncAttributeMaxDynamicSharedMemorySize, e.lds);
+  e.lds_set = err == hipSuccess;
+  return err;
+}
+
+// Launches an entry; the first launch of a handle's entry sets the LDS attribute.
+int launch_entry(KernelEntry& e, int grid, void** args, hipStream_t s) {
+  if (!e.lds_set) HIP_TRY(set_lds_attribute(e));
+  HIP_TRY(hipLaunchKernel(e.kern, dim3(grid), dim3(e.block), args, (size_t)e.lds, s));
+  return FBSTAB_HIP_OK;
+}
+
 // State shared by both solver kinds.
 struct SolverBase {
   int device = 0;
@@ -599,6 +624,20 @@ struct SolverBase {
     HIP_TRY(hipEventCreate(&ev0));
     HIP_TRY(hipEventCreate(&ev1));
     HIP_TRY(hipMalloc(&counter, kQueueBytes));  // queue counter
+    return FBSTAB_HIP_OK;
+  }
+
+  // Creation: the resident workgroups per CU (1..8) of the kernel batches are launched with - its LDS attribute
+  // set; the handle's other kernels get theirs with their first launch - and the device's CUs.
+  int occupancy(KernelEntry& e, int* per_cu, int* cus) {
+    hipError_t err = set_lds_attribute(e);
+    if (err == hipSuccess) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, e.kern, e.block, e.lds);
+    hipDeviceProp_t prop;
+    if (err == hipSuccess) err = hipGetDeviceProperties(&prop, device);
+    if (err != hipSuccess)
+      return fail(FBSTAB_HIP_ERR_DEVICE, std::string("occupancy query: ") + hipGetErrorString(err));
+    *cus = prop.multiProcessorCount;
+    *per_cu = *per_cu < 1 ? 1 : *per_cu > 8 ? 8 : *per_cu;
     return FBSTAB_HIP_OK;
   }
 
@@ -1158,6 +1197,69 @@ int tangent_run(Handle h, int batch, const Data* data, const fbstab_var_batch_t*
   return st.close();
 }
 
+// ... the solves of both kinds (batch, batch_final, traced): the argument checks, the staging, the queue block zeroed
+// (the queue word, the refinement count, the dense kDenseFallbackSlot counters), the timed launch
+// (`launch(s, a, v, d_out)`), with `norms` the final-norms kernel behind it (`launch_norms(s, a, v, d_norms)`), and
+// the results back.
+template <class Handle, class Data, class Launch, class LaunchNorms>
+int solve_run(Handle h, int batch, const Data* data, const fbstab_var_batch_t* x, fbstab_solver_out_t* out, int flags,
+              void* stream, double* norms, Launch launch, LaunchNorms launch_norms) {
+  int rc = check_common(h, batch, data, x, out, h ? h->max_batch : 0);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  for (size_t i = 0; i < h->arr_len.size(); i++)  // (nl == 0: the G and h slots of a dense handle are empty)
+    if (!data->base[i] && h->arr_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
+  for (int i = 0; i < 4; i++)
+    if (!x->base[i] && h->var_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
+  rc = h->check_solve_strides(data->stride, x->stride, batch);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  if (batch == 0) return FBSTAB_HIP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
+  const auto t0 = std::chrono::high_resolution_clock::now();
+  Data a;
+  fbstab_var_batch_t v;
+  fbstab_solver_out_t* d_out;
+  RC_TRY(h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride));
+  RC_TRY(h->stage_vars(x->base, x->stride, 4, batch, dev_ptrs, s, &v));
+  RC_TRY(h->stage_out(out, flags, &d_out));
+  HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
+  RC_TRY(h->begin_timed(s));
+  RC_TRY(launch(s, a, v, d_out));
+  RC_TRY(h->end_timed(s));
+  if (norms) {
+    double* dn;
+    RC_TRY(h->stage_norms(norms, flags, &dn));
+    launch_norms(s, a, v, dn);
+    HIP_TRY(hipGetLastError());
+  }
+  return h->finish_solve(x, out, d_out, norms, batch, flags, t0, s);
+}
+
+// ... and fbstab_hip_*_debug_newton: ONE QP given by host pointers is staged, io goes in, `launch(a, v, d_io)` puts
+// the probe on the handle's stream, io comes back.
+template <class Data, class Launch>
+int probe_run(SolverBase* h, const Data* data, const fbstab_var_batch_t* x, double* io, Launch launch) {
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  Data a;
+  fbstab_var_batch_t v;
+  // (one packed QP whatever strides the caller wrote: the lengths stand in for them)
+  RC_TRY(h->stage_arrays(data->base, h->arr_len.data(), 1, false, s, a.base, a.stride));
+  RC_TRY(h->stage_vars(x->base, h->var_len, 4, 1, false, s, &v));
+  const long long nz = h->var_len[0], nl = h->var_len[1], nv = h->var_len[2];
+  const size_t n_io = (size_t)(3 * nz + 3 * nl + 2 * nv + 1);
+  DevBuf d_io_buf;
+  HIP_TRY(hipMalloc(&d_io_buf.p, n_io * sizeof(double)));
+  double* d_io = static_cast<double*>(d_io_buf.p);
+  HIP_TRY(hipMemcpyAsync(d_io, io, sizeof(double) * (nz + nl + nv), hipMemcpyHostToDevice, s));
+  RC_TRY(launch(a, v, d_io));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(io, d_io, sizeof(double) * n_io, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FBSTAB_HIP_OK;
+}
+
 int check_common(const void* handle, int batch, const void* data, const fbstab_var_batch_t* x,
                  const void* out, int max_batch) {
   if (!handle) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null solver handle");
@@ -1169,6 +1271,13 @@ int check_common(const void* handle, int batch, const void* data, const fbstab_v
 
 }  // namespace
 
+// An entry of an MPC handle's table.  The kernels of a record instance share one argument list and run in the
+// handle's scratch; the flat-vector kernels share another (the adjoint a third) and run in `ws`.
+struct MpcKernel : KernelEntry {
+  bool record = false;
+  enum Ws { kHandle, kTrace, kAdjoint } ws = kHandle;  // (flat_workspace)
+};
+
 struct fbstab_mpc_solver : SolverBase {
   fbk::MpcLayout lay;
   const RecordInstance* rec = nullptr;  // record kernel (fb_mpc_r16.h) serving this shape, or the flat-vector kernel
@@ -1177,22 +1286,23 @@ struct fbstab_mpc_solver : SolverBase {
   int qps_per_wg = 1;
   // fbstab_hip_mpc_adjoint_batch: a record handle on the flat-vector adjoint (FBSTAB_HIP_FLAT_ADJOINT at creation;
   // the row-pair instances' default) - then with a scratch of the flat kernel's own (the handle's is laid out for
-  // the record kernel), allocated by the first call; the LDS attribute set once
+  // the record kernel), allocated by the first call
   bool flat_adjoint = false;
   double* adj_scratch = nullptr;
-  bool adj_ready = false;
   // fbstab_hip_mpc_receding_sweep_adjoint, allocated by the first call that needs them: the seed vectors of the
   // one-launch kernel (nz doubles per row slot of the grid) and the per-step form's image of one step
   double* sweep_seed = nullptr;
   double* sweep_tmp = nullptr;
-  bool sweep_adj_ready = false;
+  // What this handle launches (mpc_resolve_kernels).  solve_keep: record handles only; adjoint: on the record or
+  // the flat-vector kernel (`record`); sweep_adjoint: null where the sweep adjoint runs per step.
+  struct {
+    MpcKernel solve, solve_keep, traced, probe, adjoint, sweep_adjoint;
+  } kern;
 };
 
-namespace {
 // The record-kernel instances compiled into the library (one translation unit each),
 // smallest first: a shape runs on the first one it fits (zero-padded unless it is that
 // instance's own).
-}  // namespace
 FB_RECORD_INSTANCE_DECL(12, 4, 20, 1)
 // the same stage width with up to two constraint rows per stage variable (two-sided
 // bounds on all of x and u written as 32 rows); a third of its registers' worth of
@@ -1239,35 +1349,175 @@ MpcBatchPtrs record_data(const fbstab_mpc_solver* h, const fbstab_mpc_batch_t& a
   return MpcBatchPtrs{a, h->lay.nx, h->lay.nu, h->lay.nc};
 }
 
-// Grid of a batch launch.  Record kernels, a batch of no more QPs than the handle has workgroups: one QP per
-// WAVEFRONT (row 0 of each; fb_record_kernel.h, R16Queue::fetch) instead of four - the rows of a wavefront share its
-// program counter and its cooperative passes, so four QPs on one wavefront finish with the slowest of them and
+// Grid of a batch launch of entry `e`.  Record kernels, a batch of no more QPs than the handle has workgroups: one QP
+// per WAVEFRONT (row 0 of each; fb_record_kernel.h, R16Queue::fetch) instead of four - the rows of a wavefront share
+// its program counter and its cooperative passes, so four QPs on one wavefront finish with the slowest of them and
 // queue for each other's passes, while the chip has SIMDs to spare (round 6: batch 16, 7.9 -> ms below).  (The
-// flat-vector kernel runs one QP per workgroup: the same rule gives it min(batch, workgroups).)
-int batch_grid(const fbstab_mpc_solver* h, int batch) {
-  int grid = (batch + h->qps_per_wg - 1) / h->qps_per_wg;
+// flat-vector kernels run one QP per workgroup, on record handles too: the same rule gives them
+// min(batch, workgroups).)
+int batch_grid(const fbstab_mpc_solver* h, const MpcKernel& e, int batch) {
+  const int per_wg = e.record ? h->qps_per_wg : 1;
+  int grid = (batch + per_wg - 1) / per_wg;
   if (batch <= h->workgroups) grid = batch;
   return grid > h->workgroups ? h->workgroups : grid;
 }
+// ... and of a FBSTAB_HIP_KEEP_MATRICES launch, the one-launch sweep included: QP q in slot q, every row taken.
+int keep_grid(const fbstab_mpc_solver* h, int batch) { return (batch + h->qps_per_wg - 1) / h->qps_per_wg; }
 
-// Launches one kernel of a record instance (same argument list for all of them).
-int launch_record(fbstab_mpc_solver* h, const void* kern, int grid, hipStream_t s, const fbstab_mpc_batch_t& a,
-                  fbstab_var_batch_t x, fbstab_solver_out_t* out, int batch, double* dbg, bool reuse) {
-  MpcBatchPtrs d = record_data(h, a);
-  int N = h->lay.N, ru = reuse ? 1 : 0;
-  void* args[] = {&d, &x, &out, &h->opts, &h->scratch, &h->counter, &batch, &N, &ru, &dbg};
-  HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)h->lds_bytes, s));
+// The workspace of a flat-vector kernel: the handle's own, the traced solve's (one QP's, kept from call to call), or
+// that of the flat-vector adjoint on a record handle (lay.ws_doubles x workgroups doubles; fbstab_hip_mpc_query does
+// not count it) - the last two allocated by the first launch that needs them.
+int flat_workspace(fbstab_mpc_solver* h, const MpcKernel& e, double** ws) {
+  double** own = e.ws == MpcKernel::kTrace ? &h->trace_ws : e.ws == MpcKernel::kAdjoint ? &h->adj_scratch : &h->scratch;
+  const size_t slots = e.ws == MpcKernel::kAdjoint ? (size_t)h->workgroups : 1;
+  if (!*own) HIP_TRY(hipMalloc(own, sizeof(double) * (size_t)h->lay.ws_doubles * slots));
+  *ws = *own;
   return FBSTAB_HIP_OK;
 }
+
+// Launches a solve, traced solve or probe entry: one argument list for the kernels of a record instance, one for
+// the flat-vector kernels.
+int launch_mpc(fbstab_mpc_solver* h, MpcKernel& e, int grid, hipStream_t s, const fbstab_mpc_batch_t& a,
+               fbstab_var_batch_t x, fbstab_solver_out_t* out, int batch, double* dbg, bool reuse) {
+  if (e.record) {
+    MpcBatchPtrs d = record_data(h, a);
+    int N = h->lay.N, ru = reuse ? 1 : 0;
+    void* args[] = {&d, &x, &out, &h->opts, &h->scratch, &h->counter, &batch, &N, &ru, &dbg};
+    return launch_entry(e, grid, args, s);
+  }
+  double* ws;
+  RC_TRY(flat_workspace(h, e, &ws));
+  void* args[] = {&h->lay, const_cast<fbstab_mpc_batch_t*>(&a), &x, &out, &h->opts, &ws, &h->counter, &batch, &dbg};
+  return launch_entry(e, grid, args, s);
+}
+
+// The one place that knows which compiled kernel serves which operation of an MPC handle, with what block, LDS
+// size and workspace: read once, when the handle is created, behind the layout and the knobs that choose
+// (FBSTAB_HIP_GENERIC, FBSTAB_HIP_FLAT_ADJOINT, FBSTAB_HIP_LDS_PAD_BYTES).
+void mpc_resolve_kernels(fbstab_mpc_solver* h) {
+  // the flat-vector kernels, [0] with the stage tile and the work matrices in global scratch (MpcLayout::wglobal),
+  // [1] with everything in LDS.  (Named in the order the compiler has always met them: the code of some kernels
+  // of this file depends on it - tools/diff_device_code.py.)
+  const void* const solve_probe[2][2] = {{kernel_ptr(fbstab_mpc_kernel<kMpcThreads, false, false, true>),
+                                          kernel_ptr(fbstab_mpc_kernel<kMpcThreads, true, false, true>)},
+                                         {kernel_ptr(fbstab_mpc_kernel<kMpcThreads, false>),
+                                          kernel_ptr(fbstab_mpc_kernel<kMpcThreads, true>)}};
+  const void* const traced[2] = {kernel_ptr(fbstab_mpc_kernel<kMpcThreads, false, true, true>),
+                                 kernel_ptr(fbstab_mpc_kernel<kMpcThreads, false, true, false>)};
+  const void* const adjoint[2] = {kernel_ptr(fbstab_mpc_adjoint_kernel<kMpcThreads, true>),
+                                  kernel_ptr(fbstab_mpc_adjoint_kernel<kMpcThreads, false>)};
+  const int f = h->lay.wglobal ? 0 : 1;
+  const char* const flat_name = "fbstab_mpc_kernel<64>";
+  // what the flat-vector kernels ask for, whatever the handle's lds_bytes (a record instance's, or padded) says
+  const int flat_lds = h->lay.launch_lds_doubles * (int)sizeof(double);
+  const int lds = h->lds_bytes;
+  auto& k = h->kern;
+  if (h->rec) {
+    const RecordInstance& r = *h->rec;
+    const RecordKernels& rk = h->exact ? r.exact : r.padded;
+    k.solve = {{rk.solve, r.name, kMpcThreads, lds}, true, MpcKernel::kHandle};
+    k.solve_keep = {{rk.solve_keep, r.name, kMpcThreads, lds}, true, MpcKernel::kHandle};
+    k.probe = {{rk.probe, r.name, kMpcThreads, lds}, true, MpcKernel::kHandle};
+    if (!h->flat_adjoint) {
+      k.adjoint = {{rk.adjoint, r.adjoint_name, kMpcThreads, lds}, true, MpcKernel::kHandle};
+      k.sweep_adjoint = {{rk.sweep_adjoint, r.sweep_adjoint_name, kMpcThreads, lds}, true, MpcKernel::kHandle};
+    }
+  } else {
+    k.solve = {{solve_probe[f][0], flat_name, kMpcThreads, lds}, false, MpcKernel::kHandle};
+    k.probe = {{solve_probe[f][1], flat_name, kMpcThreads, lds}, false, MpcKernel::kHandle};
+  }
+  // the traced solve runs on the flat-vector kernel on every handle
+  k.traced = {{traced[f], flat_name, kMpcThreads, flat_lds}, false, MpcKernel::kTrace};
+  if (!k.adjoint.kern)
+    k.adjoint = {{adjoint[f], "fbstab_mpc_adjoint_kernel<64>", kMpcThreads, flat_lds}, false,
+                 h->rec ? MpcKernel::kAdjoint : MpcKernel::kHandle};
+}
 }  // namespace
+
+// An entry of a dense handle's table.  `wave`: a one-wavefront kernel (the wave layout, the handle's scratch as a
+// plain pointer); otherwise a four-wavefront kernel on the layout `lay`, the handle's scratch in its KScratchArg
+// where the instance keeps K there (`kscratch`).
+struct DenseKernel : KernelEntry {
+  bool wave = false, kscratch = false;
+  const fbk::DenseLayout* lay = nullptr;
+};
+
 struct fbstab_dense_solver : SolverBase {
   fbk::DenseLayout lay;
   // one wavefront per QP with the KKT matrix in registers (fb_dense_wave.h): the
   // kernel batches of nz + nl <= 64 run on; `lay` then only serves the traced solve
   bool wave = false;
   fbk::DenseWaveLayout wlay;
-  bool adj_ready = false;  // fbstab_hip_dense_adjoint_batch: the LDS attribute of its kernel, set once
+  fbk::DenseLayout trace_lay;  // the traced solve's own layout, where the handle's K fits the LDS
+  // What this handle launches (dense_resolve_kernels).  traced, probe: null where the layout does not serve them.
+  struct {
+    DenseKernel solve, traced, probe, adjoint;
+  } kern;
 };
+
+namespace {
+// Grid of a batch launch: one QP per workgroup at a time.
+int dense_grid(const fbstab_dense_solver* h, int batch) { return h->workgroups < batch ? h->workgroups : batch; }
+
+// The one place that knows which compiled kernel serves which operation of a dense handle, with what block, LDS
+// size, layout and scratch: read once, when the handle is created, behind the layouts and FBSTAB_HIP_DENSE_THREADS.
+void dense_resolve_kernels(fbstab_dense_solver* h) {
+  const fbk::DenseLayout& L = h->lay;
+  // [0] the one-wavefront policy; the four-wavefront policy with [1] NT = 64, [2] K and the iterate vectors in global
+  // scratch (DenseLayout::v_global), [3] K there (k_global), [4] everything in LDS.  The probe: K in LDS only; the
+  // traced solve: [2], [3], or the LDS instance on a layout of its own.  (Named in the order the compiler has always
+  // met them: the code of some kernels of this file depends on it - tools/diff_device_code.py.)
+  const int i = h->wave ? 0 : h->threads == 64 ? 1 : L.v_global ? 2 : L.k_global ? 3 : 4;
+  const void* const solve[] = {kernel_ptr(fbstab_dense_wave_kernel<false>), kernel_ptr(fbstab_dense_kernel<64>),
+                               kernel_ptr(fbstab_dense_kernel<kDenseThreads, false, true, true>),
+                               kernel_ptr(fbstab_dense_kernel<kDenseThreads, false, true>),
+                               kernel_ptr(fbstab_dense_kernel<kDenseThreads>)};
+  const void* const wave_probe = kernel_ptr(fbstab_dense_wave_kernel<true>);
+  const void* const traced[] = {kernel_ptr(fbstab_dense_kernel<kDenseThreads, true, true, true>),
+                                kernel_ptr(fbstab_dense_kernel<kDenseThreads, true, true>),
+                                kernel_ptr(fbstab_dense_kernel<kDenseThreads, true>)};
+  const void* const probe[] = {wave_probe, kernel_ptr(fbstab_dense_probe_kernel<64>), nullptr, nullptr,
+                               kernel_ptr(fbstab_dense_probe_kernel<kDenseThreads>)};
+  const void* const adjoint[] = {kernel_ptr(fbstab_dense_wave_adjoint_kernel),
+                                 kernel_ptr(fbstab_dense_adjoint_kernel<64>),
+                                 kernel_ptr(fbstab_dense_adjoint_kernel<kDenseThreads, true, true>),
+                                 kernel_ptr(fbstab_dense_adjoint_kernel<kDenseThreads, true>),
+                                 kernel_ptr(fbstab_dense_adjoint_kernel<kDenseThreads>)};
+  const fbk::DenseLayout* lay = h->wave ? nullptr : &h->lay;
+  const bool ks = L.k_global != 0;  // (never on a one-wavefront handle: its K is 64 x 64 at the most)
+  h->kern.solve = {{solve[i], "", h->threads, h->lds_bytes}, h->wave, ks, lay};
+  h->kern.probe = {{probe[i], "", h->threads, h->lds_bytes}, h->wave, ks, lay};
+  h->kern.adjoint = {{adjoint[i], "", h->threads, h->lds_bytes}, h->wave, ks, lay};
+  if (L.k_global) {
+    h->kern.traced = {{traced[L.v_global ? 0 : 1], "", h->threads, h->lds_bytes}, false, true, &h->lay};
+  } else {
+    // the traced instance is the four-wavefront kernel with a layout of its own (left null where that one does
+    // not fit: the traced solve refuses the call)
+    h->trace_lay.init(L.nz, L.nl, L.nv, kDenseThreads);
+    const int tlds = h->trace_lay.lds_doubles * (int)sizeof(double);
+    if (!h->trace_lay.k_global && tlds <= kLdsLimitBytes)
+      h->kern.traced = {{traced[2], "", kDenseThreads, tlds}, false, false, &h->trace_lay};
+  }
+}
+
+// Launches a solve, traced solve or (one-wavefront handles) probe entry: one argument list for the one-wavefront
+// kernels - `dbg`: the probe's io, or null -, one for the four-wavefront kernels - `dbg`: the trace buffer, or null.
+int launch_dense(fbstab_dense_solver* h, DenseKernel& e, int grid, hipStream_t s, fbstab_dense_batch_t a,
+                 fbstab_var_batch_t x, fbstab_solver_out_t* out, int batch, double* dbg) {
+  if (e.wave) {
+    void* args[] = {&h->wlay, &a, &x, &out, &h->opts, &h->counter, &batch, &h->scratch, &dbg};
+    return launch_entry(e, grid, args, s);
+  }
+  // (the untraced instances take an empty TraceArg, the ones with K in LDS an empty KScratchArg)
+  TraceArg<true> trace{dbg};
+  TraceArg<false> no_trace;
+  KScratchArg<true> ks{h->scratch};
+  KScratchArg<false> no_ks;
+  void* args[] = {const_cast<fbk::DenseLayout*>(e.lay), &a, &x, &out, &h->opts, &h->counter, &batch,
+                  dbg ? (void*)&trace : (void*)&no_trace, e.kscratch ? (void*)&ks : (void*)&no_ks};
+  return launch_entry(e, grid, args, s);
+}
+}  // namespace
 
 extern "C" {
 
@@ -1325,36 +1575,10 @@ int fbstab_hip_mpc_create_in_flight(int N, int nx, int nu, int nc, int max_batch
   }
   int rc = s->common_init(device, max_batch);
   if (rc != FBSTAB_HIP_OK) { s->release(); delete s; return rc; }
-  // every kernel this handle can launch gets the LDS attribute; the occupancy
-  // query runs on the one batches are launched with
-  std::vector<const void*> kerns;
-  if (s->rec) {
-    const RecordInstance& r = *s->rec;
-    if (s->exact) kerns = {r.solve_exact, r.solve_keep_exact, r.probe_exact};
-    else kerns = {r.solve, r.solve_keep, r.probe};
-  } else {
-    if (s->lay.wglobal)
-      kerns = {reinterpret_cast<const void*>(fbstab_mpc_kernel<kMpcThreads, false, false, true>),
-               reinterpret_cast<const void*>(fbstab_mpc_kernel<kMpcThreads, true, false, true>)};
-    else
-      kerns = {reinterpret_cast<const void*>(fbstab_mpc_kernel<kMpcThreads, false>),
-               reinterpret_cast<const void*>(fbstab_mpc_kernel<kMpcThreads, true>)};
-  }
-  hipError_t e = hipSuccess;
-  for (const void* k : kerns)
-    if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, s->lds_bytes);
+  mpc_resolve_kernels(s);
   int per_cu = 0, cus = 0;
-  if (e == hipSuccess)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kerns[0], s->threads, s->lds_bytes);
-  hipDeviceProp_t prop;
-  if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-  if (e != hipSuccess) {
-    s->release(); delete s;
-    return fail(FBSTAB_HIP_ERR_DEVICE, std::string("occupancy query: ") + hipGetErrorString(e));
-  }
-  cus = prop.multiProcessorCount;
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 8) per_cu = 8;
+  rc = s->occupancy(s->kern.solve, &per_cu, &cus);
+  if (rc != FBSTAB_HIP_OK) { s->release(); delete s; return rc; }
   // a handle that shares the device with others takes its share of the resident workgroups (and of the
   // scratch memory that goes with them), at least one per CU: the launches that can really run beside it - no
   // more than the process has hardware queues - want twice the resident slots between them, so that waiting
@@ -1374,7 +1598,7 @@ int fbstab_hip_mpc_create_in_flight(int N, int nx, int nu, int nc, int max_batch
   if (cap && atoi(cap) > 0 && s->workgroups > atoi(cap)) s->workgroups = atoi(cap);
   const long long ws_doubles = s->rec ? s->rec->ws_doubles(N) : (long long)s->lay.ws_doubles;
   s->scratch_bytes = ws_doubles * sizeof(double) * s->workgroups * s->qps_per_wg;
-  e = hipMalloc(&s->scratch, (size_t)s->scratch_bytes);
+  hipError_t e = hipMalloc(&s->scratch, (size_t)s->scratch_bytes);
   if (e != hipSuccess) {
     s->release(); delete s;
     return fail(FBSTAB_HIP_ERR_DEVICE, std::string("scratch allocation: ") + hipGetErrorString(e));
@@ -1419,69 +1643,24 @@ int fbstab_hip_mpc_get_options(fbstab_mpc_handle_t h, fbstab_options_t* o) {
 static int mpc_solve_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
                           const fbstab_var_batch_t* x, fbstab_solver_out_t* out, int flags,
                           void* stream, double* d_trace, double* norms = nullptr) {
-  int rc = check_common(h, batch, data, x, out, h ? h->max_batch : 0);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
-    if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
-  for (int i = 0; i < 4; i++)
-    if (!x->base[i] && h->var_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
-  rc = h->check_solve_strides(data->stride, x->stride, batch);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  if (batch == 0) return FBSTAB_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
-  const auto t0 = std::chrono::high_resolution_clock::now();
-  fbstab_mpc_batch_t a;
-  fbstab_var_batch_t v;
-  fbstab_solver_out_t* d_out;
-  rc = h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  rc = h->stage_vars(x->base, x->stride, 4, batch, dev_ptrs, s, &v);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  rc = h->stage_out(out, flags, &d_out);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
-  const int grid = batch_grid(h, batch);
-  RC_TRY(h->begin_timed(s));
-  if (d_trace) {
-    const int lds = h->lay.launch_lds_doubles * (int)sizeof(double);
-    const void* kern = h->lay.wglobal
-                           ? reinterpret_cast<const void*>(fbstab_mpc_kernel<kMpcThreads, false, true, true>)
-                           : reinterpret_cast<const void*>(fbstab_mpc_kernel<kMpcThreads, false, true, false>);
-    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if (!h->trace_ws) HIP_TRY(hipMalloc(&h->trace_ws, sizeof(double) * (size_t)h->lay.ws_doubles));
-    int one = 1;
-    void* args[] = {&h->lay, &a, &v, &d_out, &h->opts, &h->trace_ws, &h->counter, &one, &d_trace};
-    HIP_TRY(hipLaunchKernel(kern, dim3(1), dim3(kMpcThreads), args, (size_t)lds, s));
-  } else if (h->rec) {
-    // FBSTAB_HIP_KEEP_MATRICES: one QP per slot, slot = QP index
-    const bool keep = (flags & FBSTAB_HIP_KEEP_MATRICES) && dev_ptrs && batch <= h->workgroups * h->qps_per_wg;
+  auto launch = [=](hipStream_t s, const fbstab_mpc_batch_t& a, const fbstab_var_batch_t& v,
+                    fbstab_solver_out_t* d_out) -> int {
+    // FBSTAB_HIP_KEEP_MATRICES (record handles): one QP per slot, slot = QP index
+    const bool keep = !d_trace && h->rec && (flags & FBSTAB_HIP_KEEP_MATRICES) &&
+                      (flags & FBSTAB_HIP_DEVICE_POINTERS) && batch <= h->workgroups * h->qps_per_wg;
     const bool reuse = keep && h->kept_batch == batch;
-    const RecordInstance& r = *h->rec;
-    const void* kern = keep ? (h->exact ? r.solve_keep_exact : r.solve_keep) : (h->exact ? r.solve_exact : r.solve);
-    rc = launch_record(h, kern, keep ? (batch + h->qps_per_wg - 1) / h->qps_per_wg : grid, s, a, v, d_out, batch,
-                       nullptr, reuse);
-    if (rc != FBSTAB_HIP_OK) return rc;
-    h->kept_batch = keep ? batch : -1;
-  } else {
-    const void* kern = h->lay.wglobal
-                           ? reinterpret_cast<const void*>(fbstab_mpc_kernel<kMpcThreads, false, false, true>)
-                           : reinterpret_cast<const void*>(fbstab_mpc_kernel<kMpcThreads, false, false, false>);
-    double* no_dbg = nullptr;
-    void* args[] = {&h->lay, &a, &v, &d_out, &h->opts, &h->scratch, &h->counter, &batch, &no_dbg};
-    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(h->threads), args, (size_t)h->lds_bytes, s));
-  }
-  RC_TRY(h->end_timed(s));
-  if (norms) {
-    double* dn;
-    rc = h->stage_norms(norms, flags, &dn);
-    if (rc != FBSTAB_HIP_OK) return rc;
+    MpcKernel& e = d_trace ? h->kern.traced : keep ? h->kern.solve_keep : h->kern.solve;
+    // (the traced solve: the call's one QP on one workgroup, `d_trace` in the probe's place)
+    const int grid = keep ? keep_grid(h, batch) : batch_grid(h, e, batch);
+    RC_TRY(launch_mpc(h, e, grid, s, a, v, d_out, batch, d_trace, reuse));
+    if (!d_trace) h->kept_batch = keep ? batch : -1;  // (the traced solve leaves the slots alone)
+    return FBSTAB_HIP_OK;
+  };
+  auto launch_norms = [=](hipStream_t s, const fbstab_mpc_batch_t& a, const fbstab_var_batch_t& v, double* dn) {
     const MpcNormArgs na = {a, v, h->lay.N, h->lay.nx, h->lay.nu, h->lay.nc};
     hipLaunchKernelGGL(fbstab_mpc_final_norms_kernel, dim3(batch), dim3(64), 0, s, na, h->opts, dn, batch);
-    HIP_TRY(hipGetLastError());
-  }
-  return h->finish_solve(x, out, d_out, norms, batch, flags, t0, s);
+  };
+  return solve_run(h, batch, data, x, out, flags, stream, norms, launch, launch_norms);
 }
 
 int fbstab_hip_mpc_solve_batch_final(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
@@ -1554,8 +1733,6 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
   // launch per step below, which the flat-vector kernel always uses).
   const char* per_step = getenv("FBSTAB_HIP_SWEEP_PER_STEP");
   if (h->rec && batch <= h->workgroups * h->qps_per_wg && steps < 0xffff && !(per_step && atoi(per_step) != 0)) {
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
-      if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
     SweepArgs sa;
     sa.A = plant->A; sa.B = plant->B; sa.sA = plant->stride_A; sa.sB = plant->stride_B;
     sa.x0 = x0; sa.sx0 = data->stride[FBSTAB_MPC_x0];
@@ -1569,9 +1746,8 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
     HIP_TRY(hipMemcpyAsync(d_sa.p, &sa, sizeof(SweepArgs), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
     RC_TRY(h->begin_timed(s));
-    const RecordInstance& r = *h->rec;
-    RC_TRY(launch_record(h, h->exact ? r.solve_keep_exact : r.solve_keep, (batch + h->qps_per_wg - 1) / h->qps_per_wg, s,
-                         *data, *x, out, batch, static_cast<double*>(d_sa.p), false));
+    RC_TRY(launch_mpc(h, h->kern.solve_keep, keep_grid(h, batch), s, *data, *x, out, batch,
+                      static_cast<double*>(d_sa.p), false));
     RC_TRY(h->end_timed(s));
     h->kept_batch = batch;
     if (stats)
@@ -1639,38 +1815,12 @@ int fbstab_hip_mpc_receding_sweep_logged(fbstab_mpc_handle_t h, int batch, const
 int fbstab_hip_mpc_debug_newton(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t* data,
                                 const fbstab_var_batch_t* x, double* io) {
   if (!h || !data || !x || !io) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  fbstab_mpc_batch_t a;
-  fbstab_var_batch_t v;
-  // (one packed QP whatever strides the caller wrote: the lengths stand in for them)
-  int rc = h->stage_arrays(data->base, h->arr_len.data(), 1, false, s, a.base, a.stride);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  rc = h->stage_vars(x->base, h->var_len, 4, 1, false, s, &v);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  const fbk::MpcLayout& L = h->lay;
-  const size_t n_io = (size_t)(3 * L.nz + 3 * L.nl + 2 * L.nv + 1);
-  DevBuf d_io_buf;
-  HIP_TRY(hipMalloc(&d_io_buf.p, n_io * sizeof(double)));
-  double* d_io = static_cast<double*>(d_io_buf.p);
-  HIP_TRY(hipMemcpyAsync(d_io, io, sizeof(double) * (L.nz + L.nl + L.nv), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
-  h->kept_batch = -1;  // the probe runs in slot 0 and overwrites its matrix copies
-  if (h->rec) {
-    rc = launch_record(h, h->exact ? h->rec->probe_exact : h->rec->probe, 1, s, a, v, h->d_out, 1, d_io, false);
-    if (rc != FBSTAB_HIP_OK) return rc;
-  } else {
-    const void* kern = h->lay.wglobal
-                           ? reinterpret_cast<const void*>(fbstab_mpc_kernel<kMpcThreads, true, false, true>)
-                           : reinterpret_cast<const void*>(fbstab_mpc_kernel<kMpcThreads, true, false, false>);
-    int one = 1;
-    void* args[] = {&h->lay, &a, &v, &h->d_out, &h->opts, &h->scratch, &h->counter, &one, &d_io};
-    HIP_TRY(hipLaunchKernel(kern, dim3(1), dim3(h->threads), args, (size_t)h->lds_bytes, s));
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(io, d_io, sizeof(double) * n_io, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return FBSTAB_HIP_OK;
+  auto launch = [h](const fbstab_mpc_batch_t& a, const fbstab_var_batch_t& v, double* d_io) -> int {
+    HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, h->stream));
+    h->kept_batch = -1;  // the probe runs in slot 0 and overwrites its matrix copies
+    return launch_mpc(h, h->kern.probe, 1, h->stream, a, v, h->d_out, 1, d_io, false);
+  };
+  return probe_run(h, data, x, io, launch);
 }
 
 // Reverse-mode derivative of the solution map at returned points (include/fbstab_hip.h).  One launch of
@@ -1688,52 +1838,29 @@ static int mpc_adjoint_launch(fbstab_mpc_handle_t h, int batch, AdjointStage& st
   double sig = sigma_or_default(sigma);
   double alpha = h->opts.alpha;
   HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
-  if (h->rec && h->rec->adjoint && !h->flat_adjoint) {
-    // record instances: the adjoint on the record, in the handle's own slots (their matrix copies are
-    // overwritten: the next FBSTAB_HIP_KEEP_MATRICES solve rebuilds them)
-    const RecordInstance& r = *h->rec;
-    const void* kern = h->exact ? r.adjoint_exact : r.adjoint;
-    if (!h->adj_ready) {
-      HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-      h->adj_ready = true;
-    }
-    h->kept_batch = -1;
-    MpcBatchPtrs d = record_data(h, st.a);
-    AdjointArgs aa;
-    aa.grad = st.g;
-    for (int i = 0; i < 3; i++) {  // (three slots wide: no y)
-      aa.seed[i] = sd.base[i]; aa.sstride[i] = sd.stride[i];
-      aa.adj[i] = ad.base[i]; aa.astride[i] = ad.stride[i];
-    }
-    aa.status = d_st;
-    aa.sigma = sig;
-    aa.alpha = alpha;
-    int N = L.N;
-    void* args[] = {&d, &v, &aa, &h->scratch, &h->counter, &batch, &N};
-    RC_TRY(h->begin_timed(s));
-    HIP_TRY(hipLaunchKernel(kern, dim3(batch_grid(h, batch)), dim3(64), args, (size_t)h->lds_bytes, s));
-  } else {
-    // the flat-vector kernel: the handle's own workspace on flat-vector handles; on record handles (`flat_adjoint`)
-    // one of its own, L.ws_doubles x workgroups doubles (fbstab_hip_mpc_query does not count it), allocated once
-    const int grid = batch < h->workgroups ? batch : h->workgroups;
-    double* scratch = h->scratch;
-    if (h->rec) {
-      if (!h->adj_scratch)
-        HIP_TRY(hipMalloc(&h->adj_scratch, sizeof(double) * (size_t)L.ws_doubles * (size_t)h->workgroups));
-      scratch = h->adj_scratch;
-    }
-    const void* kern = L.wglobal ? reinterpret_cast<const void*>(fbstab_mpc_adjoint_kernel<kMpcThreads, true>)
-                                 : reinterpret_cast<const void*>(fbstab_mpc_adjoint_kernel<kMpcThreads, false>);
-    const int lds = L.launch_lds_doubles * (int)sizeof(double);
-    if (!h->adj_ready) {
-      HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      h->adj_ready = true;
-    }
-    void* args[] = {const_cast<fbk::MpcLayout*>(&L), &st.a, &v, &sd, &st.g, &ad, &d_st, &sig, &alpha, &scratch,
-                    &h->counter, &batch};
-    RC_TRY(h->begin_timed(s));
-    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(kMpcThreads), args, (size_t)lds, s));
+  MpcKernel& e = h->kern.adjoint;
+  // record instances: the adjoint on the record, in the handle's own slots (their matrix copies are
+  // overwritten: the next FBSTAB_HIP_KEEP_MATRICES solve rebuilds them)
+  if (e.record) h->kept_batch = -1;
+  MpcBatchPtrs d = record_data(h, st.a);
+  AdjointArgs aa;
+  aa.grad = st.g;
+  for (int i = 0; i < 3; i++) {  // (three slots wide: no y)
+    aa.seed[i] = sd.base[i]; aa.sstride[i] = sd.stride[i];
+    aa.adj[i] = ad.base[i]; aa.astride[i] = ad.stride[i];
   }
+  aa.status = d_st;
+  aa.sigma = sig;
+  aa.alpha = alpha;
+  int N = L.N;
+  void* record_args[] = {&d, &v, &aa, &h->scratch, &h->counter, &batch, &N};
+  // the flat-vector kernel, one QP per workgroup
+  double* scratch;
+  RC_TRY(flat_workspace(h, e, &scratch));
+  void* flat_args[] = {const_cast<fbk::MpcLayout*>(&L), &st.a, &v, &sd, &st.g, &ad, &d_st, &sig, &alpha, &scratch,
+                       &h->counter, &batch};
+  RC_TRY(h->begin_timed(s));
+  RC_TRY(launch_entry(e, batch_grid(h, e, batch), e.record ? record_args : flat_args, s));
   return h->end_timed(s);
 }
 
@@ -1768,7 +1895,7 @@ int fbstab_hip_mpc_adjoint_batch_reduced(fbstab_mpc_handle_t h, int batch, const
 // FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP=1: per step the costate kernel, the handle's adjoint launch, the costate kernel.
 static bool sweep_adjoint_in_one_launch(const fbstab_mpc_solver* h) {
   const char* per_step = getenv("FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP");
-  return h->rec && h->rec->sweep_adjoint && !h->flat_adjoint && !(per_step && atoi(per_step) != 0);
+  return h->kern.sweep_adjoint.kern && !(per_step && atoi(per_step) != 0);
 }
 
 int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
@@ -1813,12 +1940,7 @@ int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, cons
   a.stride[FBSTAB_MPC_x0] = nz;
   h->kept_batch = -1;  // the slots' matrix copies are overwritten
   if (sweep_adjoint_in_one_launch(h)) {
-    const RecordInstance& r = *h->rec;
-    const void* kern = h->exact ? r.sweep_adjoint_exact : r.sweep_adjoint;
-    if (!h->sweep_adj_ready) {
-      HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-      h->sweep_adj_ready = true;
-    }
+    MpcKernel& e = h->kern.sweep_adjoint;
     const size_t seed_bytes = sizeof(double) * (size_t)nz * (size_t)h->workgroups * (size_t)h->qps_per_wg;
     if (!h->sweep_seed) HIP_TRY(hipMalloc(&h->sweep_seed, seed_bytes));
     HIP_TRY(hipMemsetAsync(h->sweep_seed, 0, seed_bytes, s));
@@ -1835,7 +1957,7 @@ int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, cons
     int N = L.N;
     void* args[] = {&d, &aa, &h->scratch, &h->counter, &batch, &N};
     RC_TRY(h->begin_timed(s));
-    HIP_TRY(hipLaunchKernel(kern, dim3(batch_grid(h, batch)), dim3(64), args, (size_t)h->lds_bytes, s));
+    RC_TRY(launch_entry(e, batch_grid(h, e, batch), args, s));
     RC_TRY(h->end_timed(s));
     HIP_TRY(hipStreamSynchronize(s));
     return FBSTAB_HIP_OK;
@@ -1895,7 +2017,7 @@ int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, cons
 // Name of what the next fbstab_hip_mpc_receding_sweep_adjoint of this handle launches (diagnostics, tests, tools).
 const char* fbstab_hip_mpc_sweep_adjoint_kernel_name(fbstab_mpc_handle_t h) {
   if (!h) return "";
-  return sweep_adjoint_in_one_launch(h) ? h->rec->sweep_adjoint_name : "fbstab_sweep_costate_kernel";
+  return sweep_adjoint_in_one_launch(h) ? h->kern.sweep_adjoint.name : "fbstab_sweep_costate_kernel";
 }
 
 // Forward-mode derivative of the solution map (include/fbstab_hip.h): fbstab_tangent_rhs_kernel forms the seeds
@@ -1958,14 +2080,13 @@ int fbstab_hip_mpc_query(fbstab_mpc_handle_t h, long long* scratch_bytes, int* l
 // Name of the kernel batches of this handle run on (diagnostics, tests).
 const char* fbstab_hip_mpc_kernel_name(fbstab_mpc_handle_t h) {
   if (!h) return "";
-  return h->rec ? h->rec->name : "fbstab_mpc_kernel<64>";
+  return h->kern.solve.name;
 }
 
 // Name of the kernel the next fbstab_hip_mpc_adjoint_batch of this handle launches (diagnostics, tests, tools).
 const char* fbstab_hip_mpc_adjoint_kernel_name(fbstab_mpc_handle_t h) {
   if (!h) return "";
-  if (!h->rec || !h->rec->adjoint || h->flat_adjoint) return "fbstab_mpc_adjoint_kernel<64>";
-  return h->rec->adjoint_name;
+  return h->kern.adjoint.name;
 }
 
 int fbstab_hip_mpc_refined_steps(fbstab_mpc_handle_t h, long long* steps) {
@@ -2035,30 +2156,13 @@ int fbstab_hip_dense_create(int nz, int nl, int nv, int max_batch, int device,
   }
   int rc = s->common_init(device, max_batch);
   if (rc != FBSTAB_HIP_OK) { s->release(); delete s; return rc; }
-  const void* kern = s->wave ? reinterpret_cast<const void*>(fbstab_dense_wave_kernel<false>)
-                     : s->threads == 64 ? reinterpret_cast<const void*>(fbstab_dense_kernel<64>)
-                     : s->lay.v_global
-                         ? reinterpret_cast<const void*>(fbstab_dense_kernel<kDenseThreads, false, true, true>)
-                     : s->lay.k_global
-                         ? reinterpret_cast<const void*>(fbstab_dense_kernel<kDenseThreads, false, true>)
-                         : reinterpret_cast<const void*>(fbstab_dense_kernel<kDenseThreads>);
-  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, s->lds_bytes);
-  if (e == hipSuccess && s->wave)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(fbstab_dense_wave_kernel<true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, s->lds_bytes);
-  int per_cu = 0;
-  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, s->threads, s->lds_bytes);
-  hipDeviceProp_t prop;
-  if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-  if (e != hipSuccess) {
-    s->release(); delete s;
-    return fail(FBSTAB_HIP_ERR_DEVICE, std::string("occupancy query: ") + hipGetErrorString(e));
-  }
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 8) per_cu = 8;
+  dense_resolve_kernels(s);
+  int per_cu = 0, cus = 0;
+  rc = s->occupancy(s->kern.solve, &per_cu, &cus);
+  if (rc != FBSTAB_HIP_OK) { s->release(); delete s; return rc; }
   const char* env = getenv("FBSTAB_HIP_WGS_PER_CU");
   if (env && atoi(env) > 0) per_cu = atoi(env);
-  s->workgroups = prop.multiProcessorCount * per_cu;
+  s->workgroups = cus * per_cu;
   if (s->workgroups > max_batch) s->workgroups = max_batch;
   // test knob: FBSTAB_HIP_MAX_WORKGROUPS=n caps the grid, so that one workgroup solves several QPs in turn
   const char* cap = getenv("FBSTAB_HIP_MAX_WORKGROUPS");
@@ -2069,7 +2173,7 @@ int fbstab_hip_dense_create(int nz, int nl, int nv, int max_batch, int device,
   else if (s->lay.k_global)  // K (and, v_global, the iterate vectors) of every resident workgroup (fb_dense.h)
     s->scratch_bytes = (long long)sizeof(double) * (s->lay.k_doubles + s->lay.v_doubles) * s->workgroups;
   if (s->scratch_bytes > 0) {
-    e = hipMalloc(&s->scratch, (size_t)s->scratch_bytes);
+    hipError_t e = hipMalloc(&s->scratch, (size_t)s->scratch_bytes);
     // (fb_dense_wave.h relies on the multiplier rows past nz + nl being zero)
     if (e == hipSuccess && s->wave) e = hipMemset(s->scratch, 0, (size_t)s->scratch_bytes);
     if (e != hipSuccess) {
@@ -2106,85 +2210,17 @@ int fbstab_hip_dense_get_options(fbstab_dense_handle_t h, fbstab_options_t* o) {
 static int dense_solve_impl(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
                             const fbstab_var_batch_t* x, fbstab_solver_out_t* out, int flags,
                             void* stream, double* d_trace, double* norms = nullptr) {
-  int rc = check_common(h, batch, data, x, out, h ? h->max_batch : 0);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  for (int i = 0; i < FBSTAB_DENSE_NARR; i++)
-    if (!data->base[i] && h->arr_len[i] > 0)
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
-  for (int i = 0; i < 4; i++)
-    if (!x->base[i] && h->var_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
-  rc = h->check_solve_strides(data->stride, x->stride, batch);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  if (batch == 0) return FBSTAB_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
-  const auto t0 = std::chrono::high_resolution_clock::now();
-  fbstab_dense_batch_t a;
-  fbstab_var_batch_t v;
-  fbstab_solver_out_t* d_out;
-  rc = h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  rc = h->stage_vars(x->base, x->stride, 4, batch, dev_ptrs, s, &v);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  rc = h->stage_out(out, flags, &d_out);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));  // (the queue word and the kDenseFallbackSlot counters)
-  int grid = h->workgroups < batch ? h->workgroups : batch;
-  RC_TRY(h->begin_timed(s));
-  if (d_trace && h->lay.v_global) {
-    auto kern = fbstab_dense_kernel<kDenseThreads, true, true, true>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(1), dim3(h->threads), h->lds_bytes, s, h->lay, a, v, d_out, h->opts,
-                       h->counter, 1, TraceArg<true>{d_trace}, KScratchArg<true>{h->scratch});
-  } else if (d_trace && h->lay.k_global) {
-    auto kern = fbstab_dense_kernel<kDenseThreads, true, true>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(1), dim3(h->threads), h->lds_bytes, s, h->lay, a, v, d_out, h->opts,
-                       h->counter, 1, TraceArg<true>{d_trace}, KScratchArg<true>{h->scratch});
-  } else if (d_trace) {
-    // the traced instance is the four-wavefront kernel with a layout of its own
-    fbk::DenseLayout tl;
-    tl.init(h->lay.nz, h->lay.nl, h->lay.nv, kDenseThreads);
-    const int tlds = tl.lds_doubles * (int)sizeof(double);
-    if (tl.k_global || tlds > kLdsLimitBytes)
-      return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "traced dense solve: layout does not fit");
-    auto kern = fbstab_dense_kernel<kDenseThreads, true>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, tlds));
-    hipLaunchKernelGGL(kern, dim3(1), dim3(kDenseThreads), tlds, s, tl, a, v, d_out, h->opts,
-                       h->counter, 1, TraceArg<true>{d_trace}, KScratchArg<false>());
-  } else if (h->wave) {
-    hipLaunchKernelGGL(fbstab_dense_wave_kernel<false>, dim3(grid), dim3(64), h->lds_bytes, s, h->wlay, a, v, d_out,
-                       h->opts, h->counter, batch, h->scratch, (double*)nullptr);
-  } else if (h->threads == 64) {
-    hipLaunchKernelGGL(fbstab_dense_kernel<64>, dim3(grid), dim3(64), h->lds_bytes, s, h->lay, a, v, d_out,
-                       h->opts, h->counter, batch, TraceArg<false>(), KScratchArg<false>());
-  } else if (h->lay.v_global) {
-    hipLaunchKernelGGL((fbstab_dense_kernel<kDenseThreads, false, true, true>), dim3(grid), dim3(h->threads),
-                       h->lds_bytes, s, h->lay, a, v, d_out, h->opts, h->counter, batch, TraceArg<false>(),
-                       KScratchArg<true>{h->scratch});
-  } else if (h->lay.k_global) {
-    hipLaunchKernelGGL((fbstab_dense_kernel<kDenseThreads, false, true>), dim3(grid), dim3(h->threads),
-                       h->lds_bytes, s, h->lay, a, v, d_out, h->opts, h->counter, batch, TraceArg<false>(),
-                       KScratchArg<true>{h->scratch});
-  } else {
-    hipLaunchKernelGGL(fbstab_dense_kernel<kDenseThreads>, dim3(grid), dim3(h->threads), h->lds_bytes, s,
-                       h->lay, a, v, d_out, h->opts, h->counter, batch, TraceArg<false>(),
-                       KScratchArg<false>());
-  }
-  RC_TRY(h->end_timed(s));
-  if (norms) {
-    double* dn;
-    rc = h->stage_norms(norms, flags, &dn);
-    if (rc != FBSTAB_HIP_OK) return rc;
+  auto launch = [=](hipStream_t s, const fbstab_dense_batch_t& a, const fbstab_var_batch_t& v,
+                    fbstab_solver_out_t* d_out) -> int {
+    DenseKernel& e = d_trace ? h->kern.traced : h->kern.solve;
+    if (!e.kern) return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "traced dense solve: layout does not fit");
+    return launch_dense(h, e, dense_grid(h, batch), s, a, v, d_out, batch, d_trace);
+  };
+  auto launch_norms = [=](hipStream_t s, const fbstab_dense_batch_t& a, const fbstab_var_batch_t& v, double* dn) {
     const DenseNormArgs na = {a, v, h->lay.nz, h->lay.nl, h->lay.nv};
     hipLaunchKernelGGL(fbstab_dense_final_norms_kernel, dim3(batch), dim3(64), 0, s, na, h->opts, dn, batch);
-    HIP_TRY(hipGetLastError());
-  }
-  return h->finish_solve(x, out, d_out, norms, batch, flags, t0, s);
+  };
+  return solve_run(h, batch, data, x, out, flags, stream, norms, launch, launch_norms);
 }
 
 int fbstab_hip_dense_solve_batch_final(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
@@ -2220,39 +2256,14 @@ int fbstab_hip_dense_debug_newton(fbstab_dense_handle_t h, const fbstab_dense_ba
                                   const fbstab_var_batch_t* x, double* io) {
   if (!h || !data || !x || !io) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
   if (!h->wave && h->lay.k_global) return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "dense probe: K must fit the LDS");
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  fbstab_dense_batch_t a;
-  fbstab_var_batch_t v;
-  // (one packed QP whatever strides the caller wrote: the lengths stand in for them)
-  int rc = h->stage_arrays(data->base, h->arr_len.data(), 1, false, s, a.base, a.stride);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  rc = h->stage_vars(x->base, h->var_len, 4, 1, false, s, &v);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  const fbk::DenseLayout& L = h->lay;
-  const size_t n_io = (size_t)(3 * L.nz + 3 * L.nl + 2 * L.nv + 1);
-  DevBuf d_io_buf;
-  HIP_TRY(hipMalloc(&d_io_buf.p, n_io * sizeof(double)));
-  double* d_io = static_cast<double*>(d_io_buf.p);
-  HIP_TRY(hipMemcpyAsync(d_io, io, sizeof(double) * (L.nz + L.nl + L.nv), hipMemcpyHostToDevice, s));
-  if (h->wave) {
-    hipLaunchKernelGGL(fbstab_dense_wave_kernel<true>, dim3(1), dim3(64), h->lds_bytes, s, h->wlay, a, v,
-                       (fbstab_solver_out_t*)nullptr, h->opts, h->counter, 1, h->scratch, d_io);
-  } else if (h->threads == 64) {
-    auto kern = fbstab_dense_probe_kernel<64>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                h->lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(1), dim3(64), h->lds_bytes, s, h->lay, a, v, h->opts, d_io);
-  } else {
-    auto kern = fbstab_dense_probe_kernel<kDenseThreads>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                h->lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(1), dim3(kDenseThreads), h->lds_bytes, s, h->lay, a, v, h->opts, d_io);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(io, d_io, sizeof(double) * n_io, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return FBSTAB_HIP_OK;
+  auto launch = [h](const fbstab_dense_batch_t& a, const fbstab_var_batch_t& v, double* d_io) -> int {
+    DenseKernel& e = h->kern.probe;
+    if (e.wave) return launch_dense(h, e, 1, h->stream, a, v, nullptr, 1, d_io);
+    void* args[] = {const_cast<fbk::DenseLayout*>(e.lay), const_cast<fbstab_dense_batch_t*>(&a),
+                    const_cast<fbstab_var_batch_t*>(&v), &h->opts, &d_io};
+    return launch_entry(e, 1, args, h->stream);
+  };
+  return probe_run(h, data, x, io, launch);
 }
 
 // Reverse-mode derivative of the dense solution map at returned points (include/fbstab_hip.h).  One launch of the
@@ -2273,30 +2284,14 @@ static int dense_adjoint_launch(fbstab_dense_handle_t h, int batch, AdjointStage
   // the queue word alone: the words from kDenseFallbackSlot on still describe the last solve
   // (fbstab_hip_dense_get_factorisation)
   HIP_TRY(hipMemsetAsync(h->counter, 0, sizeof(int) * kDenseFallbackSlot, s));
-  const int grid = h->workgroups < batch ? h->workgroups : batch;
-  const void* kern;
-  if (h->wave) kern = reinterpret_cast<const void*>(fbstab_dense_wave_adjoint_kernel);
-  else if (h->threads == 64) kern = reinterpret_cast<const void*>(fbstab_dense_adjoint_kernel<64>);
-  else if (h->lay.v_global) kern = reinterpret_cast<const void*>(fbstab_dense_adjoint_kernel<kDenseThreads, true, true>);
-  else if (h->lay.k_global) kern = reinterpret_cast<const void*>(fbstab_dense_adjoint_kernel<kDenseThreads, true>);
-  else kern = reinterpret_cast<const void*>(fbstab_dense_adjoint_kernel<kDenseThreads>);
-  if (!h->adj_ready) {
-    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-    h->adj_ready = true;
-  }
+  DenseKernel& e = h->kern.adjoint;
+  KScratchArg<true> ks{h->scratch};
+  KScratchArg<false> no_ks;
+  void* wave_args[] = {&h->wlay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch, &h->scratch};
+  void* args[] = {&h->lay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch,
+                  e.kscratch ? (void*)&ks : (void*)&no_ks};
   RC_TRY(h->begin_timed(s));
-  if (h->wave) {
-    void* args[] = {&h->wlay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch, &h->scratch};
-    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)h->lds_bytes, s));
-  } else if (h->lay.k_global) {
-    KScratchArg<true> ks{h->scratch};
-    void* args[] = {&h->lay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch, &ks};
-    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(h->threads), args, (size_t)h->lds_bytes, s));
-  } else {
-    KScratchArg<false> ks;
-    void* args[] = {&h->lay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch, &ks};
-    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(h->threads), args, (size_t)h->lds_bytes, s));
-  }
+  RC_TRY(launch_entry(e, dense_grid(h, batch), e.wave ? wave_args : args, s));
   return h->end_timed(s);
 }
 
