@@ -46,7 +46,14 @@ steps and computes only the gradients torch asks for; ``data["x0"].grad`` is dL/
 plant's ``A.grad``, ``B.grad`` (``(nx, nx)`` / ``(nx, nu)`` torch tensors, row-major, shared by the trajectories)
 are formed from the logged costates.  A step whose solve did not end in SUCCESS passes the costate through the
 plant alone, and a retired trajectory (``retire=True``) is cut at its retirement step, as the sweep cuts it.  A
-shared input gets the sum of the per-trajectory gradients, formed in torch.  Not served: the batch-summed
+shared input gets the sum of the per-trajectory gradients, formed in torch.
+
+Scenarios: ``closed_loop_mpc(..., w=w)`` runs the disturbed plant x_(k+1) = A x_k + B u0 + w_k (``w``: ``(steps, B,
+nx)``, one realisation per trajectory - Monte-Carlo over disturbances in one launch), and ``shift=True`` moves every
+returned point one stage towards the present before it is the next guess (fbstab_hip_mpc_receding_sweep_scenario;
+fewer Newton steps on time-invariant horizons, more on random time-varying ones).  The backward is the same call:
+the recursion does not change, and ``w.grad`` is the logged costate, dL/dw_k = mu_k, zero at and after a
+trajectory's retirement step.  Not served: the batch-summed
 (reduced) path inside the library, forward mode through the sweep, and losses of anything but ``u`` and ``x`` (the
 rest of z_k, l_k, v_k).
 """
@@ -173,10 +180,11 @@ def solve_dense(solver, data, sigma: float = 0.0):
 
 
 class ClosedLoopMpcFunction(torch.autograd.Function):
-    """apply(solver, steps, retire, sigma, A, B, *sequences in MPC_SEQ order) -> (u, x, out)."""
+    """apply(solver, steps, retire, sigma, A, B, *sequences in MPC_SEQ order[, w, shift]) -> (u, x, out)."""
 
     @staticmethod
-    def forward(ctx, solver, steps, retire, sigma, A, B, *seqs):
+    def forward(ctx, solver, steps, retire, sigma, A, B, *rest):
+        seqs, (w, shift) = rest[:len(MPC_SEQ)], (rest[len(MPC_SEQ):] or (None, False))
         Bn = max(a.shape[0] if a.dim() == 2 else 1 for a in seqs)
         ctx.shared = tuple(k for k, a in zip(MPC_SEQ, seqs) if Bn > 1 and (a.dim() == 1 or a.shape[0] == 1))
         assert "x0" not in ctx.shared, "every trajectory has its own initial state"
@@ -189,8 +197,12 @@ class ClosedLoopMpcFunction(torch.autograd.Function):
         run["x0"] = data["x0"].clone()
         mk = lambda n: torch.zeros((Bn, n), dtype=torch.float64, device=dev)
         z, l, v, y = mk(solver.nz), mk(solver.nl), mk(solver.nv), mk(solver.nv)
-        r = solver.RecedingSweep(run, z, l, v, y, A.detach(), B.detach(), steps, retire=retire, log_inputs=True,
-                                 log=True)
+        if w is None and not shift:
+            r = solver.RecedingSweep(run, z, l, v, y, A.detach(), B.detach(), steps, retire=retire, log_inputs=True,
+                                     log=True)
+        else:
+            r = solver.RecedingSweep(run, z, l, v, y, A.detach(), B.detach(), steps, retire=retire, log_inputs=True,
+                                     log=True, w=None if w is None else w.detach(), shift=bool(shift))
         u = r["u"]
         x = torch.cat([r["x_log"][1:], run["x0"][None]], 0)
         ctx.solver, ctx.steps, ctx.retire, ctx.sigma = solver, steps, retire, sigma
@@ -203,18 +215,19 @@ class ClosedLoopMpcFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gu, gx, gout):
         need = ctx.needs_input_grad
-        want = [k for k, n in zip(MPC_SEQ, need[6:]) if n]
+        want = [k for k, n in zip(MPC_SEQ, need[6:6 + len(MPC_SEQ)]) if n]
         plant = need[4] or need[5]
-        if not want and not plant:
+        noise = len(need) > 6 + len(MPC_SEQ) and need[6 + len(MPC_SEQ)]
+        if not want and not plant and not noise:
             return (None,) * len(need)
         A, B, u, zl, ll, vl, xl, el = ctx.saved_tensors[:8]
         data = dict(zip(MPC_SEQ, ctx.saved_tensors[8:]))
         log = dict(z_log=zl, l_log=ll, v_log=vl, eflag_log=el)
         g = ctx.solver.RecedingSweepAdjoint(data, A, B, ctx.steps, log, gu=gu.contiguous(), gx=gx.contiguous(),
-                                            retire=ctx.retire, sigma=ctx.sigma, want=want, mu=plant)
+                                            retire=ctx.retire, sigma=ctx.sigma, want=want, mu=plant or noise)
         gA = gB = None
-        if plant:
-            # x_(k+1) of a retired trajectory is the constant 0: its costates do not reach the plant
+        if plant or noise:
+            # x_(k+1) of a retired trajectory is the constant 0: its costates reach neither the plant nor w_k
             mu = torch.where((el == -1)[:, :, None], torch.zeros_like(g["mu"]), g["mu"])
             gA = torch.einsum("kbi,kbj->ij", mu, xl) if need[4] else None
             gB = torch.einsum("kbi,kbj->ij", mu, u) if need[5] else None
@@ -226,12 +239,19 @@ class ClosedLoopMpcFunction(torch.autograd.Function):
                 grads.append(g[k].sum(0).reshape(ctx.shapes[k]))
             else:
                 grads.append(g[k])
-        return (None, None, None, None, gA, gB) + tuple(grads)
+        tail = (mu if noise else None, None)[:len(need) - 6 - len(MPC_SEQ)]
+        return (None, None, None, None, gA, gB) + tuple(grads) + tail
 
 
-def closed_loop_mpc(solver, data, A, B, steps: int, retire: bool = True, sigma: float = 0.0):
+def closed_loop_mpc(solver, data, A, B, steps: int, retire: bool = True, sigma: float = 0.0, w=None,
+                    shift: bool = False):
     """Differentiable receding-horizon sweep: ``data`` as for ``solve_mpc`` (``x0``: the trajectories' initial
     states, ``(B, nx)``), ``A``/``B`` the plant x+ = A x + B u0 as ``(nx, nx)``/``(nx, nu)`` float64 CUDA tensors.
+    ``w``: None, or the disturbances ``(steps, B, nx)`` of x+ = A x + B u0 + w_k (may require grad: ``w.grad`` is the
+    costate of every step, zero once the trajectory is retired); ``shift``: the shifted warm start.
     Returns ``(u, x, out)``: the inputs ``(steps, B, nu)``, the states after each step ``(steps, B, nx)`` and the last
     step's SolverOut records; see the module docstring."""
-    return ClosedLoopMpcFunction.apply(solver, steps, retire, sigma, A, B, *[data[k] for k in MPC_SEQ])
+    seqs = [data[k] for k in MPC_SEQ]
+    if w is None and not shift:
+        return ClosedLoopMpcFunction.apply(solver, steps, retire, sigma, A, B, *seqs)
+    return ClosedLoopMpcFunction.apply(solver, steps, retire, sigma, A, B, *seqs, w, bool(shift))

@@ -162,13 +162,48 @@ struct SweepArgs {
   // fbstab_hip_mpc_receding_sweep_logged: NULL, or [steps][batch][nz | nl | nv | nx] and [steps][batch]
   double *log_z, *log_l, *log_v, *log_x0;
   int* log_eflag;
+  // fbstab_hip_mpc_receding_sweep_scenario: NULL, or the disturbances [steps][batch][nx] (x+ = A x + B u0 + w_k),
+  // and whether the point a step returned is moved one stage towards the present before it is the next guess
+  // (N, nc: the stage blocks of z, l and v are nx + nu, nx and nc long).  What the move needs it finds HERE, not
+  // in registers held across the plant step (receding_plant_step: its register footprint): the lanes of a row,
+  // the (z, l, v) slots of the caller's x once more, and cnt, [batch] ints zeroed before the launch, the number
+  // of steps each trajectory has behind it.
+  const double* w;
+  int shift, N, nc, lpq;
+  int* cnt;
+  double* xb[3];
+  long long sxb[3];
 };
+
+// Blocks 1 .. N of `a` (b doubles each) moved onto blocks 0 .. N-1, in place, by the lanes of a row: lane t takes the
+// entries e = t, t + lpq, ... of a block and walks each of them through the stages in ascending order, so that an
+// address is overwritten by the lane that read it, after it read it (one loop: no exec mask nests in another).
+__device__ __forceinline__ void shift_stage_blocks(double* a, int b, int N, int t, int lpq) {
+  int e = t, i = 0;
+  while (e < b && N > 0) {
+    a[i * b + e] = a[(i + 1) * b + e];
+    if (++i == N) {
+      i = 0;
+      e += lpq;
+    }
+  }
+}
 
 // Closed-loop step of trajectory q after its solve number `step`, by the lanes of its
 // row (t = lane within the row, lpq = lanes per row): retirement, statistics, u0 and
 // x0 <- A x0 + B u0 - what fbstab_receding_plant_kernel does for a whole batch between
 // two launches.  Returns the updated `retired` flag.  A real call: inlined into the
 // solver loop its temporaries cost the sweeps 60 spilled registers.
+// Scenario sweeps: w_k is added behind the fma chain (not for a parked trajectory, which stays at the origin), and
+// with `shift` the returned point becomes the next step's guess moved by one stage, z_i <- z_(i+1), l_i <- l_(i+1),
+// v_i <- v_(i+1) for i < N (stage N keeps its values; not behind the last step: x holds what that step returned).
+// The copy is in place, stage by stage through a register: entry e of a stage block belongs to lane e mod lpq in
+// EVERY stage, so the one lane that reads an address is the one that overwrites it, later in its own program order.
+// REGISTER FOOTPRINT: the solve kernels are compiled knowing which registers this function writes (inter-procedural
+// register allocation: values they hold across the call sit in the others), so their instructions change when the
+// set does.  It is v0-v31, s0-s11, s30-s31 and vcc, and stays that: the columns of A and of B are summed on either
+// side of a fence (B's pointers are loaded when A's are dead), the shift keeps nothing in registers across the
+// plant step (SweepArgs), and v29, which the allocator now happens to leave out, is named as written.
 __device__ __noinline__ bool receding_plant_step(const SweepArgs* sweep, const fbstab_var_batch_t* x,
                                                  const fbstab_solver_out_t* out, int batch, int q, int step, int t,
                                                  int lpq, bool gone) {
@@ -212,18 +247,32 @@ __device__ __noinline__ bool receding_plant_step(const SweepArgs* sweep, const f
     if (a.log_x0 && t < a.nx) a.log_x0[kq * a.nx + t] = xs[t];
     if (a.log_eflag && t == 0) a.log_eflag[kq] = gone ? -1 : eflag;
   }
-  const double* Aq = a.A + q * a.sA;
-  const double* Bq = a.B + q * a.sB;
   double acc = 0.0;  // (nx <= lanes of the row: one entry per lane)
   if (t < a.nx) {
+    const double* Aq = a.A + q * a.sA;
     for (int c = 0; c < a.nx; c++) acc = fma(Aq[t + c * a.nx], xs[c], acc);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  if (t < a.nx) {
+    const double* Bq = a.B + q * a.sB;
     for (int j = 0; j < a.nu; j++) acc = fma(Bq[t + j * a.nx], gone ? 0.0 : z[a.nx + j], acc);
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // every lane has read x0
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // every lane has read x0 (and u0, and logged the point)
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  if (t < a.nx) xs[t] = gone ? 0.0 : acc;
+  if (t < a.nx) {
+    if (a.w) acc = acc + a.w[((long long)step * batch + q) * a.nx + t];
+    xs[t] = gone ? 0.0 : acc;
+  }
+  const int count = a.cnt[q] + 1;  // (= step + 1)
+  if (a.shift != 0 & count < a.steps) {
+    shift_stage_blocks(a.xb[0] + q * a.sxb[0], a.nx + a.nu, a.N, t, a.lpq);
+    shift_stage_blocks(a.xb[1] + q * a.sxb[1], a.nx, a.N, t, a.lpq);
+    shift_stage_blocks(a.xb[2] + q * a.sxb[2], a.nc, a.N, t, a.lpq);
+  }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  if (t == 0) a.cnt[q] = count;  // (every lane has read it)
+  asm volatile("" ::: "v29");
   return gone;
 }
 

@@ -134,13 +134,17 @@ __global__ __launch_bounds__(NT, kMpcMinWaves) void fbstab_mpc_adjoint_kernel(
 // x0 <- A x0 + B u0 (the SimulationInputs of the reference's generator,
 // fbstab/test/ocp_generator.h:31-38); (z, l, v) stay where they are and are the
 // next step's initial guess, unshifted (the reference has no shift logic;
-// fbstab_algorithm-impl.h:140 starts from whatever the caller's Variable holds).
+// fbstab_algorithm-impl.h:140 starts from whatever the caller's Variable holds) unless
+// fbstab_hip_mpc_receding_sweep_scenario asks for the shift (shift_stages below).
 // With `retire`, a trajectory whose solve did not end in SUCCESS is parked at the
 // origin for the rest of the sweep (x0 = 0, guess 0), as a controller's fallback
 // would: its QP is then solved by the zero vector in one proximal iteration.
 // stats[step] = {sum of Newton iterations, solves that ended in SUCCESS,
 // trajectories retired so far, largest Newton count}.
 // lg: this step's share of the sweep log (fbstab_hip_mpc_receding_sweep_logged; null slots are not logged).
+// w: null, or this step's disturbances [batch][nx], added behind the fma chain (fbstab_hip_mpc_receding_sweep_scenario;
+// a parked trajectory stays at the origin).  shift_stages: 0, or N: (z, l, v) are then moved one stage towards the
+// present, block i <- block i + 1 for i < N in ascending order, stage N keeping its values (receding_plant_step).
 struct SweepLogStep {
   double *z, *l, *v, *x0;
   int* eflag;
@@ -149,7 +153,7 @@ __global__ void fbstab_receding_plant_kernel(int batch, int nx, int nu, int nz, 
                                              long long sA, const double* B, long long sB, double* x0, long long sx0,
                                              fbstab_var_batch_t x, const fbstab_solver_out_t* out, int* retired,
                                              int retire, double* u_log, unsigned long long* stats, double* xtmp,
-                                             SweepLogStep lg) {
+                                             SweepLogStep lg, const double* w, int shift_stages, int nc) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = q < batch;
   fbstab_solver_out_t o;
@@ -214,9 +218,18 @@ __global__ void fbstab_receding_plant_kernel(int batch, int nx, int nu, int nz, 
     double acc = 0.0;
     for (int c = 0; c < nx; c++) acc = fma(Aq[r + c * nx], xs[c], acc);
     for (int j = 0; j < nu; j++) acc = fma(Bq[r + j * nx], gone ? 0.0 : z[nx + j], acc);
+    if (w) acc = acc + w[(long long)q * nx + r];
     xn[r] = gone ? 0.0 : acc;
   }
   for (int r = 0; r < nx; r++) xs[r] = xn[r];
+  if (shift_stages > 0) {
+    double* l = var_at(x, 1, q);
+    double* v = var_at(x, 2, q);
+    const int bz = nx + nu;
+    for (int i = 0; i < shift_stages * bz; i++) z[i] = z[i + bz];
+    for (int i = 0; i < shift_stages * nx; i++) l[i] = l[i + nx];
+    for (int i = 0; i < shift_stages * nc; i++) v[i] = v[i + nc];
+  }
 }
 
 // The per-step form of fbstab_hip_mpc_receding_sweep_adjoint (include/fbstab_hip.h has the recursion): between
@@ -1690,16 +1703,21 @@ int fbstab_hip_mpc_solve_traced(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t*
 
 // BASELINE configs[4]: `steps` closed-loop steps without a host round trip in
 // between - solve, plant step, solve, ... queued on one stream.
-// (`log`: fbstab_hip_mpc_receding_sweep_logged; null: nothing is logged)
+// (`log`: fbstab_hip_mpc_receding_sweep_logged; null: nothing is logged.  `sc`:
+// fbstab_hip_mpc_receding_sweep_scenario; null: no disturbance, no shift)
 static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
                                    const fbstab_var_batch_t* x, fbstab_solver_out_t* out,
                                    const fbstab_receding_plant_t* plant, int steps, int retire, double* u_log,
                                    unsigned long long* stats, float* kernel_ms, void* stream,
-                                   const fbstab_sweep_log_t* log) {
+                                   const fbstab_sweep_log_t* log, const fbstab_sweep_scenario_t* sc = nullptr) {
   int rc = check_common(h, batch, data, x, out, h ? h->max_batch : 0);
   if (rc != FBSTAB_HIP_OK) return rc;
   if (!plant || !plant->A || !plant->B || steps < 0)
     return fail(FBSTAB_HIP_ERR_ARGUMENT, "plant matrices and a non-negative step count are required");
+  if (sc && sc->shift != 0 && sc->shift != 1)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "receding sweep scenario: shift is 0 or 1");
+  const double* w = sc ? sc->w : nullptr;
+  const bool shift = sc && sc->shift == 1;
   for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
     if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
   for (int i = 0; i < 4; i++)
@@ -1741,6 +1759,9 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
     sa.nx = L.nx; sa.nu = L.nu; sa.nz = L.nz; sa.nl = L.nl; sa.nv = L.nv;
     sa.log_z = log ? log->z : nullptr; sa.log_l = log ? log->l : nullptr; sa.log_v = log ? log->v : nullptr;
     sa.log_x0 = log ? log->x0 : nullptr; sa.log_eflag = log ? log->eflag : nullptr;
+    sa.w = w; sa.shift = shift ? 1 : 0; sa.N = L.N; sa.nc = L.nc;
+    sa.lpq = 64 / h->qps_per_wg; sa.cnt = static_cast<int*>(d_ret.p);
+    for (int i = 0; i < 3; i++) { sa.xb[i] = x->base[i]; sa.sxb[i] = x->stride[i]; }
     DevBuf d_sa;
     HIP_TRY(hipMalloc(&d_sa.p, sizeof(SweepArgs)));
     HIP_TRY(hipMemcpyAsync(d_sa.p, &sa, sizeof(SweepArgs), hipMemcpyHostToDevice, s));
@@ -1782,7 +1803,8 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
                        L.nz, L.nl, L.nv, plant->A, plant->stride_A, plant->B, plant->stride_B, x0,
                        data->stride[FBSTAB_MPC_x0], *x, out, static_cast<int*>(d_ret.p), retire,
                        u_log ? u_log + (long long)k * batch * L.nu : nullptr,
-                       static_cast<unsigned long long*>(d_stats.p) + 4 * k, static_cast<double*>(d_xtmp.p), lg);
+                       static_cast<unsigned long long*>(d_stats.p) + 4 * k, static_cast<double*>(d_xtmp.p), lg,
+                       w ? w + (long long)k * batch * L.nx : nullptr, shift && k + 1 < steps ? L.N : 0, L.nc);
   }
   HIP_TRY(hipGetLastError());
   if (stats)
@@ -1806,6 +1828,15 @@ int fbstab_hip_mpc_receding_sweep_logged(fbstab_mpc_handle_t h, int batch, const
                                          double* u_log, unsigned long long* stats, float* kernel_ms, void* stream,
                                          const fbstab_sweep_log_t* log) {
   return mpc_receding_sweep_impl(h, batch, data, x, out, plant, steps, retire, u_log, stats, kernel_ms, stream, log);
+}
+
+int fbstab_hip_mpc_receding_sweep_scenario(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                           const fbstab_var_batch_t* x, fbstab_solver_out_t* out,
+                                           const fbstab_receding_plant_t* plant, int steps, int retire,
+                                           double* u_log, unsigned long long* stats, float* kernel_ms, void* stream,
+                                           const fbstab_sweep_log_t* log, const fbstab_sweep_scenario_t* scenario) {
+  return mpc_receding_sweep_impl(h, batch, data, x, out, plant, steps, retire, u_log, stats, kernel_ms, stream, log,
+                                 scenario);
 }
 
 // Diagnostics for the tests: one Newton step of the device path at (x, xbar,

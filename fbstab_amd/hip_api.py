@@ -97,6 +97,11 @@ class _SweepLog(C.Structure):
     _fields_ = [("z", C.c_void_p), ("l", C.c_void_p), ("v", C.c_void_p), ("x0", C.c_void_p), ("eflag", C.c_void_p)]
 
 
+class _SweepScenario(C.Structure):
+    """fbstab_sweep_scenario_t: the disturbances (device pointer or NULL) and the shift flag."""
+    _fields_ = [("w", C.c_void_p), ("shift", C.c_int)]
+
+
 _libs: Dict[str, C.CDLL] = {}
 _torch = None  # the torch module, once load_library has imported it (device arrays need a loaded library anyway)
 _current = LIB_PATH  # the library new solver objects bind to (see `library`)
@@ -195,6 +200,9 @@ def load_library() -> C.CDLL:
             C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.fbstab_hip_mpc_sweep_adjoint_kernel_name.restype = C.c_char_p
         lib.fbstab_hip_mpc_sweep_adjoint_kernel_name.argtypes = [C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_receding_sweep_scenario"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_receding_sweep_scenario.argtypes = lib.fbstab_hip_mpc_receding_sweep.argtypes + [
+            C.c_void_p, C.c_void_p]
     lib.fbstab_hip_shard_group_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     lib.fbstab_hip_shard_group_destroy.argtypes = [C.c_void_p]
     lib.fbstab_hip_shard_group_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -222,7 +230,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_debug_newton", "fbstab_hip_mpc_adjoint_batch", "fbstab_hip_mpc_adjoint_kernel_name",
     "fbstab_hip_mpc_adjoint_batch_reduced", "fbstab_hip_mpc_tangent_batch", "fbstab_hip_debug_stamps",
     "fbstab_hip_mpc_receding_sweep_logged", "fbstab_hip_mpc_receding_sweep_adjoint",
-    "fbstab_hip_mpc_sweep_adjoint_kernel_name",
+    "fbstab_hip_mpc_sweep_adjoint_kernel_name", "fbstab_hip_mpc_receding_sweep_scenario",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",
     "fbstab_hip_dense_solve_traced", "fbstab_hip_dense_adjoint_batch",
@@ -630,7 +638,7 @@ class FBstabMpcBatch(_SolverBase):
         return _Plant(Ad.data_ptr(), Bd.data_ptr(), 0, 0), (Ad, Bd)
 
     def RecedingSweep(self, data, z, l, v, y, A, B, steps: int, retire: bool = True,
-                      log_inputs: bool = False, stream: int = 0, log: bool = False):
+                      log_inputs: bool = False, stream: int = 0, log: bool = False, w=None, shift: bool = False):
         """fbstab_hip_mpc_receding_sweep: ``steps`` warm-started closed-loop steps on
         the device (torch CUDA tensors; ``data["x0"]`` is advanced in place, ``z, l,
         v, y`` hold the last solution).  ``A``/``B``: the simulation model as
@@ -639,7 +647,12 @@ class FBstabMpcBatch(_SolverBase):
         step (newton_sum, success, retired_total, newton_max).  ``log=True``
         (fbstab_hip_mpc_receding_sweep_logged) adds what RecedingSweepAdjoint needs, per step: ``z_log, l_log,
         v_log`` ``(steps, batch, n)`` - the point the step returned -, ``x_log`` ``(steps, batch, nx)`` - the state
-        it was solved for - and ``eflag_log`` ``(steps, batch)`` int32, -1 once a trajectory is retired."""
+        it was solved for - and ``eflag_log`` ``(steps, batch)`` int32, -1 once a trajectory is retired.
+        ``w``: ``(steps, batch, nx)`` float64 CUDA tensor of disturbances, x_(k+1) = A x_k + B u_k + w_k (a parked
+        trajectory stays at the origin); ``shift=True``: the point a step returned is moved one stage towards the
+        present before it is the next step's guess (stage N keeps its values; not behind the last step) - fewer
+        Newton steps on time-invariant horizons, MORE on random time-varying ones (include/fbstab_hip.h).  Either
+        one makes the call fbstab_hip_mpc_receding_sweep_scenario; with neither it is exactly the call above."""
         b, dev_flags = _MpcBatch(), []
         B_ = _fill_block(b, MPC_SEQ, self.seq_len, data, None, dev_flags, shared=False)
         vb = _fill_vars((z, l, v, y), (self.nz, self.nl, self.nv, self.nv), B_, dev_flags)
@@ -655,11 +668,22 @@ class FBstabMpcBatch(_SolverBase):
                 u.data_ptr() if u is not None else None, stats.ctypes.data, kms.ctypes.data,
                 C.c_void_p(stream) if stream else None]
         logs = {}
+        lg = None
         if log:
             for k, n in (("z_log", self.nz), ("l_log", self.nl), ("v_log", self.nv), ("x_log", self.nx)):
                 logs[k] = where.zeros(z, (steps, B_, n))
             logs["eflag_log"] = where.zeros(z, (steps, B_), "i4")
             lg = _SweepLog(*[logs[k].data_ptr() for k in ("z_log", "l_log", "v_log", "x_log", "eflag_log")])
+        if w is not None or shift:
+            import torch
+            if w is not None:
+                assert _is_torch(w) and w.is_cuda and w.dtype == torch.float64 and \
+                    tuple(w.shape) == (steps, B_, self.nx), "w: a (steps, batch, nx) float64 CUDA tensor"
+                w = w.detach().contiguous()
+            sc = _SweepScenario(w.data_ptr() if w is not None else None, 1 if shift else 0)
+            _check(self._lib, self._lib.fbstab_hip_mpc_receding_sweep_scenario(
+                *args, C.byref(lg) if lg is not None else None, C.byref(sc)))
+        elif log:
             _check(self._lib, self._lib.fbstab_hip_mpc_receding_sweep_logged(*args, C.byref(lg)))
         else:
             _check(self._lib, self._lib.fbstab_hip_mpc_receding_sweep(*args))

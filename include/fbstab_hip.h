@@ -387,6 +387,38 @@ int fbstab_hip_mpc_receding_sweep_logged(fbstab_mpc_handle_t handle, int batch, 
                                          double* u_log, unsigned long long* stats, float* kernel_ms,
                                          void* stream, const fbstab_sweep_log_t* log);
 
+/* ---- closed-loop scenarios: a disturbed plant and a shifted warm start -----------------------------------------
+ * fbstab_hip_mpc_receding_sweep_scenario is fbstab_hip_mpc_receding_sweep_logged with two options of the step
+ * between two solves.  scenario == NULL, or w == NULL with shift == 0, IS that function: the same launches, the
+ * same bits.  Everything else - arguments, validation, retirement, statistics, the log, the two forms of the
+ * sweep (bitwise equal to each other here as well) - is as there.
+ *   w:     Monte-Carlo over disturbance realisations: x_(k+1) = A x_k + B u_k + w_k, one addition behind the sum
+ *          over the columns of A and B.  A parked trajectory (retire != 0) stays at the origin: w is not added.
+ *          A failed step of an unretired trajectory advances with the u_0 it returned, as ever, plus w_k.
+ *          log->x0[k] remains the state step k was solved for; w_(steps-1) enters the x0 left in `data`.
+ *   shift: 1 moves the point step k returned one stage towards the present before it is step k + 1's guess, as
+ *          receding-horizon controllers do: z_i <- z_(i+1) in blocks of nx + nu, l_i <- l_(i+1) in blocks of nx,
+ *          v_i <- v_(i+1) in blocks of nc for i = 0 .. N-1; stage N keeps its values; y is ignored on input and
+ *          is not touched.  The move follows the step's retirement handling, statistics, u_log and log writes -
+ *          the log and u_log hold returned points, unshifted - and does not follow the last step: x on return is
+ *          the last step's solution as it was returned.  Values other than 0 and 1 are FBSTAB_HIP_ERR_ARGUMENT,
+ *          before anything is queued.
+ * Which way the shift cuts is a property of the problem.  On a time-invariant horizon under a persistent
+ * disturbance it saves most of the Newton steps (the tables of DESIGN.md 4.3: a quarter to a half of the
+ * unshifted count); on random time-varying horizons, whose stage i + 1 says nothing about stage i, the shifted
+ * point is the WORSE guess (two to three times the count).  Hence an option, off by default. */
+typedef struct fbstab_sweep_scenario_t {
+  const double* w;  /* NULL, or DEVICE array [steps][batch][nx]: x_(k+1) = A x_k + B u_k + w_k */
+  int shift;        /* 0: the previous point is the next guess as it stands
+                       1: it is moved one stage towards the present first */
+} fbstab_sweep_scenario_t;
+int fbstab_hip_mpc_receding_sweep_scenario(fbstab_mpc_handle_t handle, int batch, const fbstab_mpc_batch_t* data,
+                                           const fbstab_var_batch_t* x, fbstab_solver_out_t* out,
+                                           const fbstab_receding_plant_t* plant, int steps, int retire,
+                                           double* u_log, unsigned long long* stats, float* kernel_ms,
+                                           void* stream, const fbstab_sweep_log_t* log,
+                                           const fbstab_sweep_scenario_t* scenario);
+
 /* Reverse mode through the sweep.  With u_k = entries [nx, nx + nu) of z_k and x_(k+1) = A x_k + B u_k, the seeds
  * gu[k] = dL/du_k ([steps][batch][nu]) and gx[k] = dL/dx_(k+1) ([steps][batch][nx]; either may be NULL: zero) are
  * taken backwards along every trajectory.  Start with lambda = 0 and for k = steps-1 .. 0:
@@ -411,6 +443,9 @@ int fbstab_hip_mpc_receding_sweep_logged(fbstab_mpc_handle_t handle, int batch, 
  * step fbstab_sweep_costate_kernel, the handle's adjoint launch into a per-QP image of the handle's own
  * (max_batch x (all 12 sequences + nz + 2 nx) doubles, allocated at the first call) and the costate kernel again.
  * fbstab_hip_mpc_sweep_adjoint_kernel_name names what the next call launches.  Synchronous.
+ * The recursion holds as it stands for the disturbed plant x_(k+1) = A x_k + B u_k + w_k of
+ * fbstab_hip_mpc_receding_sweep_scenario (w_k enters x_(k+1) with the identity), and for the shifted warm start
+ * (the guess is not an argument of the solution map): dL/dw_k = mu_log[k] where eflag_log[k] != -1, zero otherwise.
  * Not served: gradients summed over the batch, forward mode through the sweep, seeds on the rest of z_k, l_k,
  * v_k. */
 int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t handle, int batch, const fbstab_mpc_batch_t* data,
