@@ -1,4 +1,4 @@
-"""Shared helpers for the parity tests."""
+"""Shared helpers of the tests (and of the developer tools under tools/)."""
 import os
 
 import numpy as np
@@ -370,3 +370,93 @@ def handle_free_call(lib, kind, entry, batch=1, null=(), zero=(), seed_z=True):
     else:
         rc = fn(None, batch, ref("data"), ref("x"), outp, 0, None)
     return rc, lib.fbstab_hip_last_error().decode()
+
+
+# -- what more than one GPU test module (and tools/) uses -------------------------------------------------------
+OUT_FIELDS = ("eflag", "residual", "initial_residual", "newton_iters", "prox_iters")
+
+
+def is_mpc(p):
+    return hasattr(p, "N")
+
+
+def cold_solve(hip, p, o=None):
+    """``p`` solved on the device from a zero guess with host arrays: (solver handle, (z, l, v), out)."""
+    s = hip.FBstabMpcBatch(*p.sizes(), max_batch=p.batch) if is_mpc(p) else hip.FBstabDenseBatch(p.nz, p.nl, p.nv, max_batch=p.batch)
+    if o is not None:
+        s.UpdateOptions(_opts(hip, o))
+    z, l, v, y = (np.zeros((p.batch, n)) for n in (p.nz, p.nl, p.nv, p.nv))
+    out = s.Solve({k: np.ascontiguousarray(a) for k, a in p.arrays.items()}, z, l, v, y)
+    return s, (z, l, v), out
+
+
+def solve_dense_host(hip, p, opts, guess=None, order=None):
+    s = hip.FBstabDenseBatch(p.nz, p.nl, p.nv, max_batch=p.batch)
+    if order is not None:  # fbstab_hip_dense_set_factorisation (default: the reference's order)
+        s.SetFactorisation({"pivoted": s.ORDER_PIVOTED, "auto": s.ORDER_AUTO, "natural": s.ORDER_NATURAL}[order])
+    s.UpdateOptions(_opts(hip, opts))
+    B = p.batch
+    z = np.zeros((B, p.nz)); l = np.zeros((B, p.nl)); v = np.zeros((B, p.nv)); y = np.full((B, p.nv), 7.0)
+    if guess is not None:
+        z[:], l[:], v[:] = guess
+    data = {k: np.ascontiguousarray(a) for k, a in p.arrays.items()}
+    out = s.Solve(data, z, l, v, y)
+    s.close()
+    return z, l, v, y, out
+
+
+def lqr_gain(p):
+    """-K_0 of the finite-horizon Riccati recursion of QP 0 (stage cost 1/2 [x;u]'[Q S';S R][x;u], the
+    terminal stage's input eliminated)."""
+    N, nx, nu, nc = p.sizes()
+    a = {k: v[0] for k, v in p.arrays.items()}
+    mat = lambda key, i, r, c: a[key][i * r * c:(i + 1) * r * c].reshape(c, r).T
+    Q, R, S = (lambda i: mat("Q", i, nx, nx)), (lambda i: mat("R", i, nu, nu)), (lambda i: mat("S", i, nu, nx))
+    P = Q(N) - S(N).T @ np.linalg.solve(R(N), S(N))
+    K = None
+    for i in range(N - 1, -1, -1):
+        A, B = mat("A", i, nx, nx), mat("B", i, nx, nu)
+        Quu, Qux, Qxx = R(i) + B.T @ P @ B, S(i) + B.T @ P @ A, Q(i) + A.T @ P @ A
+        K = np.linalg.solve(Quu, Qux)
+        P = Qxx - Qux.T @ K
+    return -K
+
+
+def pfb_gradient(ys, v, alpha, sigma):
+    """(gamma, mus) of riccati_linear_solver.cc:346-365 / :91-99, in numpy."""
+    r = np.sqrt(ys * ys + v * v)
+    d = alpha * (1.0 - 1.0 / np.sqrt(2.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = np.where(r < 1e-13, d, alpha * (1.0 - ys / r))
+        m = np.where(r < 1e-13, d, alpha * (1.0 - v / r))
+    both = (r >= 1e-13) & (ys > 0) & (v > 0)
+    g = g + np.where(both, (1.0 - alpha) * v, 0.0)
+    m = m + np.where(both, (1.0 - alpha) * ys, 0.0)
+    return g, m + sigma * g
+
+
+def pfb(a, b, alpha):
+    return alpha * (a + b - np.sqrt(a * a + b * b)) + (1.0 - alpha) * np.maximum(a, 0) * np.maximum(b, 0)
+
+
+def records_agree(dev, ref, what):
+    assert len(dev) == len(ref), (what, len(dev), len(ref))
+    assert np.array_equal(dev[:, :3], ref[:, :3]), what  # kinds, iteration numbers
+    # FP tolerance: the device evaluates the same formulas in a different order
+    # (DESIGN.md 3): 1e-6 relative, 1e-7 of the largest residual of the solve
+    # absolute (the linear blocks of the inner residual are rounding noise of
+    # that size after every Newton step).  Residuals below 1e-3 of that scale
+    # are what a converged Newton iteration leaves behind - quadratic convergence
+    # squares the rounding difference of the step before - and only have to
+    # agree within a factor of two.
+    d, r = dev[:, 3:], ref[:, 3:]
+    scale = records_scale(ref)
+    err = np.abs(d - r)
+    tight = err <= 1e-7 * scale + 1e-6 * np.abs(r)
+    loose = (np.abs(r) < 1e-3 * scale) & (err <= 0.5 * np.maximum(np.abs(d), np.abs(r)))
+    bad = ~(tight | loose).all(axis=1)
+    assert not bad.any(), (what, dev[bad], ref[bad])
+
+
+def records_scale(rec):
+    return max(1.0, float(np.abs(rec[:, 3:]).max()))

@@ -1,5 +1,5 @@
-"""TEST INFRASTRUCTURE ONLY: loader for the single-threaded host compilation of
-the device solver logic (see hostsim.cc)."""
+"""TEST INFRASTRUCTURE ONLY: the single-threaded host compilations of the device logic (hostsim.cc, adjoint.cc,
+dense_adjoint.cc, tangent.cc, against the <hip/hip_runtime.h> of shim/) and their ctypes wrappers."""
 import ctypes as C
 import os
 import subprocess
@@ -7,26 +7,29 @@ import subprocess
 import numpy as np
 
 from oracle.oracle_py import SolverOut, Options, default_options, _out_to_numpy, _p
+from tests.linear_reference import SIGMA, is_mpc, names_of, lengths_of
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "libhostsim.so")
+_CSRC = os.path.join(_HERE, "..", "..", "fbstab_amd", "csrc")
+NO_CONTRACTION = "-ffp-contract=off"   # host builds of the device headers round every product (no fused multiply-adds)
 
 
-def build():
-    src = os.path.join(_HERE, "hostsim.cc")
+def build(so_name, source, headers):
+    """Compiles ``source`` (of this directory) into ``so_name`` beside it unless that is newer than the source,
+    the shim and the ``headers`` of fbstab_amd/csrc it includes.  Returns the library's path."""
+    so = os.path.join(_HERE, so_name)
+    src = os.path.join(_HERE, source)
     shim = os.path.join(_HERE, "shim")  # <hip/hip_runtime.h> for a host of one thread
-    deps = [src, os.path.join(shim, "hip", "hip_runtime.h")] + [
-        os.path.join(_HERE, "..", "..", "fbstab_amd", "csrc", f) for f in ("fb_common.h", "fb_algorithm.h", "fb_mpc.h", "fb_dense.h")]
-    if os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps):
-        return
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + shim,
-                           "-Wno-attributes", "-Wno-unknown-pragmas", "-o", _SO, src])
+    deps = [src, os.path.join(shim, "hip", "hip_runtime.h")] + [os.path.join(_CSRC, f) for f in headers]
+    if not (os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(d) for d in deps)):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", NO_CONTRACTION, "-I" + shim,
+                               "-Wno-attributes", "-Wno-unknown-pragmas", "-o", so, src])
+    return so
 
 
 class HostSim:
     def __init__(self):
-        build()
-        self.lib = C.CDLL(_SO)
+        self.lib = C.CDLL(build("libhostsim.so", "hostsim.cc", ("fb_common.h", "fb_algorithm.h", "fb_mpc.h", "fb_dense.h")))
 
     def solve_mpc(self, prob, x0guess=None, opts=None):
         opts = opts or default_options()
@@ -88,3 +91,78 @@ class HostSim:
             o += n
         r["lin2_before"], r["lin2_after"] = out[o], out[o + 1]
         return r
+
+
+def _pad(a):
+    return a if a.size else np.zeros(1)
+
+
+class HostAdjoint:
+    """The adjoint of one QP on one host thread, ``kind`` "mpc": the flat-vector adjoint of fb_mpc.h (adjoint.cc);
+    "dense": DenseProblem<Ctx<1>> of fb_dense.h and dense_adjoint_contract of fb_adjoint.h (dense_adjoint.cc)."""
+
+    def __init__(self, kind="mpc"):
+        if kind == "mpc":
+            self.lib = C.CDLL(build("libhostsim_adjoint.so", "adjoint.cc", ("fb_common.h", "fb_mpc.h")))
+            self.entry, nsize = self.lib.hostsim_mpc_adjoint, 4
+        else:
+            self.lib = C.CDLL(build("libhostsim_dense_adjoint.so", "dense_adjoint.cc",
+                                    ("fb_common.h", "fb_adjoint.h", "fb_mpc.h", "fb_dense.h")))
+            self.entry, nsize = self.lib.hostsim_dense_adjoint, 3
+            self.lib.hostsim_dense_layout.argtypes = [C.c_int] * 4 + [C.c_void_p]
+        self.entry.argtypes = [C.c_int] * nsize + [C.c_void_p] * 7 + [C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+
+    def layout(self, nz, nl, nv, nthreads=256):
+        """Dense: DenseLayout::init(nz, nl, nv, nthreads): dict(wave, k_global, v_global, a_lds, lds_doubles)."""
+        out = (C.c_int * 5)()
+        self.lib.hostsim_dense_layout(nz, nl, nv, nthreads, out)
+        return dict(zip(("wave", "k_global", "v_global", "a_lds", "lds_doubles"), list(out)))
+
+    def adjoint(self, p, q, x, seeds, sigma=SIGMA, alpha=0.95, want=None):
+        """Adjoint of QP ``q`` at x = (z, l, v) for seeds (gz, gl, gv) (gl / gv may be None): (status, (dz, dl,
+        dv), gradients) - those of ``want`` (default: all)."""
+        names, lens = names_of(p), lengths_of(p)
+        sizes = p.sizes() if is_mpc(p) else (p.nz, p.nl, p.nv)
+        keep = [_pad(np.ascontiguousarray(p.arrays[k][q], dtype=np.float64)) for k in names]
+        data = (C.c_void_p * len(names))(*[a.ctypes.data for a in keep])
+        grads = {k: np.full(lens[k], np.nan) for k in (names if want is None else want)}
+        bufs = {k: _pad(g) for k, g in grads.items()}
+        gptr = (C.c_void_p * len(names))(*[bufs[k].ctypes.data if k in bufs else None for k in names])
+        f64 = lambda a: None if a is None else _pad(np.ascontiguousarray(a, dtype=np.float64))
+        z, l, v = (f64(t) for t in x)
+        gz, gl, gv = (f64(t) for t in seeds)
+        adj = np.full(p.nz + p.nl + p.nv, np.nan)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        st = self.entry(*sizes, data, ptr(z), ptr(l), ptr(v), ptr(gz), ptr(gl), ptr(gv), sigma, alpha,
+                        adj.ctypes.data, gptr)
+        for k in grads:
+            if grads[k].size:
+                grads[k] = bufs[k]
+        return st, (adj[:p.nz], adj[p.nz:p.nz + p.nl], adj[p.nz + p.nl:]), grads
+
+
+class HostTangent:
+    """mpc_tangent_stage / dense_tangent of fb_tangent.h on one host thread (tangent.cc)."""
+
+    def __init__(self):
+        self.lib = C.CDLL(build("libhostsim_tangent.so", "tangent.cc", ("fb_common.h", "fb_tangent.h")))
+        self.lib.hostsim_mpc_tangent_rhs.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7
+        self.lib.hostsim_dense_tangent_rhs.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7
+
+    def rhs(self, p, x, d, budget=8192):
+        """(gz, gl, gv) of one QP at x = (z, l, v) for the perturbations ``d`` (name -> flat array or None).
+        Dense: ``budget`` doubles of LDS decide the column block; ``self.cb`` is what came of it."""
+        names = names_of(p)
+        keep = [None if d.get(k) is None else _pad(np.ascontiguousarray(d[k], dtype=np.float64)) for k in names]
+        ptrs = (C.c_void_p * len(names))(*[None if a is None else a.ctypes.data for a in keep])
+        z, l, v = (_pad(np.ascontiguousarray(t, dtype=np.float64)) for t in x)
+        gz, gl, gv = (np.full(max(n, 1), np.nan) for n in (p.nz, p.nl, p.nv))
+        if is_mpc(p):
+            self.lib.hostsim_mpc_tangent_rhs(p.N, p.nx, p.nu, p.nc, ptrs, z.ctypes.data, l.ctypes.data,
+                                             v.ctypes.data, gz.ctypes.data, gl.ctypes.data, gv.ctypes.data)
+        else:
+            self.cb = self.lib.hostsim_dense_tangent_rhs(p.nz, p.nl, p.nv, budget, ptrs, z.ctypes.data,
+                                                         l.ctypes.data, v.ctypes.data, gz.ctypes.data,
+                                                         gl.ctypes.data, gv.ctypes.data)
+            assert self.cb >= 1, "not one column fits the budget"
+        return gz[:p.nz], gl[:p.nl], gv[:p.nv]

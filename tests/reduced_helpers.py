@@ -6,14 +6,15 @@ import re
 
 import numpy as np
 
+from fbstab_amd.hip_api import MPC_SEQ, DENSE_ARR
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fbstab_amd", "csrc")
 PLAN_HEADER = os.path.join(CSRC, "fb_grad_reduce_plan.h")
 
-MPC_SEQ = ("Q", "R", "S", "q", "r", "A", "B", "c", "E", "L", "d", "x0")
-DENSE_ARR = ("H", "f", "G", "h", "A", "b")
-MPC_MATRICES = ("Q", "R", "S", "A", "B", "E", "L")
-DENSE_MATRICES = ("H", "G", "A")
+# (the matrices are the names in capitals: Q R S A B E L, and H G A)
+MPC_MATRICES = tuple(k for k in MPC_SEQ if k.isupper())
+DENSE_MATRICES = tuple(k for k in DENSE_ARR if k.isupper())
 
 DENSE_SHAPES = ((50, 10, 100), (30, 0, 40), (5, 2, 9))
 MPC_SHAPES = ((3, 12, 4, 20), (4, 5, 2, 7), (3, 18, 5, 10), (2, 34, 3, 5))

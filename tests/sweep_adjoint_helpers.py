@@ -1,6 +1,7 @@
 """Shared helpers of the sweep-adjoint tests (fbstab_hip_mpc_receding_sweep_adjoint): the backward recursion
 through a logged receding-horizon sweep in numpy, with the per-step adjoint pluggable (the oracle's linear solver,
-or the device's own ``Adjoint`` at the logged points), and the oracle's closed loop with a log.
+or the device's own ``Adjoint`` at the logged points), over the log of tests/closed_loop.logged_closed_loop or the
+device's, and the bars and the problem the CPU and GPU tests share.
 
 The recursion (include/fbstab_hip.h): with u_k = z_k[nx:nx+nu] and x_(k+1) = A x_k + B u_k, start with lambda = 0
 and for k = T-1 .. 0:  mu = gx[k] + lambda;  eflag -1: lambda <- 0;  eflag != 0: lambda <- A'mu;  otherwise one
@@ -9,10 +10,10 @@ adjoint at the logged point with the seed gu[k] + B'mu on the u0 entries of z: a
 lambda <- A'mu - dl[0:nx].  The x0 slot is the final lambda."""
 import numpy as np
 
+from fbstab_amd.hip_api import MPC_SEQ
 from tools import fixtures as fx
-from tests import adjoint_helpers as AH
-
-MPC_SEQ = AH.MPC_SEQ
+from tests import helpers as H
+from tests import linear_reference as LR
 
 
 def reference_sweep_adjoint(adjoint_fn, p, A, B, log, gu, gx, retire=True):
@@ -57,7 +58,7 @@ def reference_sweep_adjoint(adjoint_fn, p, A, B, log, gu, gx, retire=True):
     return grads, status, mu_log
 
 
-def oracle_step_adjoint(oracle, p, sigma=AH.SIGMA):
+def oracle_step_adjoint(oracle, p, sigma=LR.SIGMA):
     """The per-step adjoint from the oracle's RiccatiLinearSolver and the gradient table in numpy."""
     lens = p.seq_lengths()
 
@@ -65,8 +66,8 @@ def oracle_step_adjoint(oracle, p, sigma=AH.SIGMA):
         grads = {name: np.zeros((p.batch, lens[name])) for name in MPC_SEQ}
         for q in np.flatnonzero(active):
             xq = tuple(t[q] for t in x)
-            step = AH.oracle_adjoint(oracle, p, q, xq, (gz[q], np.zeros(p.nl), np.zeros(p.nv)), sigma)
-            tab = AH.gradient_table(AH.one_qp(p, q), xq, step)
+            step = LR.oracle_adjoint(oracle, p, q, xq, (gz[q], np.zeros(p.nl), np.zeros(p.nv)), sigma)
+            tab = LR.mpc_gradient_table(LR.one_qp(p, q), xq, step)
             for name in MPC_SEQ:
                 grads[name][q] = tab[name]
         return np.zeros(p.batch, dtype=np.int32), grads
@@ -81,37 +82,30 @@ def device_step_adjoint(solver, p, sigma=0.0):
     return fn
 
 
-def oracle_closed_loop(oracle, p, A, B, steps, opts=None, retire=True):
-    """The sweep run with the oracle (warm-started, unshifted, retirement as the device's): the log as
-    ``reference_sweep_adjoint`` takes it plus ``x`` ``(T, batch, nx)`` (the states the steps were solved for),
-    ``u`` ``(T, batch, nu)`` and ``x_end``."""
-    N, nx, nu, nc = p.sizes()
-    Bn = p.batch
-    x0 = p.arrays["x0"].copy()
-    z, l, v = np.zeros((Bn, p.nz)), np.zeros((Bn, p.nl)), np.zeros((Bn, p.nv))
-    gone = np.zeros(Bn, dtype=bool)
-    log = dict(z=[], l=[], v=[], eflag=[], x=[], u=[])
-    for k in range(steps):
-        arr = dict(p.arrays)
-        arr["x0"] = x0
-        z, l, v, y, out = oracle.solve_mpc(fx.MpcProblem(N, nx, nu, nc, arr), x0guess=(z, l, v), opts=opts)
-        if retire:
-            gone = gone | (out["eflag"] != 0)
-        z[gone] = 0.0; l[gone] = 0.0; v[gone] = 0.0
-        u = z[:, nx:nx + nu].copy()
-        log["z"].append(z.copy()); log["l"].append(l.copy()); log["v"].append(v.copy())
-        log["eflag"].append(np.where(gone, -1, out["eflag"]).astype(np.int32))
-        log["x"].append(x0.copy()); log["u"].append(u)
-        x0 = x0 @ A.T + u @ B.T
-        x0[gone] = 0.0
-    res = {k: np.stack(a) for k, a in log.items()}
-    res["x_end"] = x0
-    return res
+def spread_bars(oracle, oracle_fma, p, A, B, log, gu, gx):
+    """Per sequence: ten times the spread between the two roundings of the reference (the oracle and its
+    fused-multiply-add build as per-step adjoints of the same recursion at the same logged points), relative to
+    the gradient's largest entry, the largest over the trajectories.  Returns (bars, spreads)."""
+    a = reference_sweep_adjoint(oracle_step_adjoint(oracle, p), p, A, B, log, gu, gx)[0]
+    b = reference_sweep_adjoint(oracle_step_adjoint(oracle_fma, p), p, A, B, log, gu, gx)[0]
+    spread = {}
+    for k in MPC_SEQ:
+        top = np.abs(a[k]).max(axis=1)
+        rel = np.abs(a[k] - b[k]).max(axis=1) / np.where(top > 0, top, 1.0)
+        spread[k] = float(rel.max())
+    return {k: 10.0 * s for k, s in spread.items()}, spread
+
+
+def assert_within(got, ref, bars, what, rows=None):
+    for k in MPC_SEQ:
+        for q in (range(ref[k].shape[0]) if rows is None else rows):
+            top = np.abs(ref[k][q]).max()
+            err = np.abs(got[k][q] - ref[k][q]).max() / (top if top > 0 else 1.0)
+            assert err <= bars[k], (what, k, q, err, bars[k])
 
 
 def strictly_complementary(p, log, tol=1e-3):
     """Trajectories whose every step ended in SUCCESS at a point with max(y, v) >= tol on every row."""
-    from tests import helpers as H
     T, Bn = log["eflag"].shape
     N, nx, nu, nc = p.sizes()
     good = []

@@ -1,21 +1,9 @@
 """Shared helpers of the tangent tests (fbstab_hip_*_tangent_batch): the numpy reference of the right-hand side
-(gz, gl, gv) in extended precision with its rounding bound, random directions, and the host build of the direction
-arithmetic of fb_tangent.h (tests/hostsim/tangent.cc)."""
-import ctypes as C
-import os
-import subprocess
-
+(gz, gl, gv) in extended precision with its rounding bound, and random directions."""
 import numpy as np
 
-from tools import fixtures as fx
-from tests import helpers as H
+from tests.linear_reference import LD, is_mpc, names_of, lengths_of, explicit, problem_like
 
-MPC_SEQ = ("Q", "R", "S", "q", "r", "A", "B", "c", "E", "L", "d", "x0")
-DENSE_ARR = ("H", "f", "G", "h", "A", "b")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOSTSIM = os.path.join(ROOT, "tests", "hostsim")
-_SO = os.path.join(HOSTSIM, "libhostsim_tangent.so")
-LD = np.longdouble
 U = 2.0 ** -53
 # Duality of the tangent with the adjoint, |<g, J dtheta> - sum_k <grad_k, dtheta_k>| over the sum of the magnitudes
 # of the terms of <g, J dtheta>: 10 x the largest disagreement of the two numbers when both steps come from the
@@ -25,20 +13,6 @@ U = 2.0 ** -53
 DUALITY_BAR = 3.6e-8
 
 
-def is_mpc(p):
-    return hasattr(p, "N")
-
-
-def names_of(p):
-    return MPC_SEQ if is_mpc(p) else DENSE_ARR
-
-
-def lengths_of(p):
-    if is_mpc(p):
-        return p.seq_lengths()
-    return dict(H=p.nz * p.nz, f=p.nz, G=p.nl * p.nz, h=p.nl, A=p.nv * p.nz, b=p.nv)
-
-
 def _carrier(p, arrays):
     """A one-QP problem of p's shape whose data are ``arrays`` (name -> flat array; absent or None: zeros)."""
     lens = lengths_of(p)
@@ -46,19 +20,14 @@ def _carrier(p, arrays):
     for k, a in arrays.items():
         if a is not None:
             full[k] = np.asarray(a, dtype=np.float64).reshape(1, lens[k])
-    if is_mpc(p):
-        return fx.MpcProblem(p.N, p.nx, p.nu, p.nc, full)
-    one = fx.DenseProblem(p.nz, p.nl, p.nv)
-    one.arrays = full
-    return one
+    return problem_like(p, full)
 
 
 def _explicit(p, arrays):
     """(dH, df, dG, dh, dA, db) of the perturbations ``arrays`` in longdouble: the explicit QP of a problem that
     carries them, minus that of the all-zero problem (which removes the constant -I blocks of the MPC's G)."""
-    ex = H.mpc_explicit if is_mpc(p) else H.dense_explicit
-    a = ex(_carrier(p, arrays), 0)
-    b = ex(_carrier(p, {}), 0)
+    a = explicit(_carrier(p, arrays), 0)
+    b = explicit(_carrier(p, {}), 0)
     return tuple(np.asarray(s).astype(LD) - np.asarray(t).astype(LD) for s, t in zip(a, b))
 
 
@@ -137,44 +106,3 @@ def pairing(names, grads, d, q):
         if d.get(k) is not None and d[k].size:
             s += np.asarray(grads[k][q] if np.ndim(grads[k]) == 2 else grads[k]).astype(LD) @ one_direction(d, q)[k].astype(LD)
     return s
-
-
-# -- the host build of the direction arithmetic ----------------------------------------------------------------
-def _build():
-    src = os.path.join(HOSTSIM, "tangent.cc")
-    shim = os.path.join(HOSTSIM, "shim")
-    deps = [src, os.path.join(shim, "hip", "hip_runtime.h")] + [
-        os.path.join(ROOT, "fbstab_amd", "csrc", f) for f in ("fb_common.h", "fb_tangent.h")]
-    if os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps):
-        return
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + shim,
-                           "-Wno-attributes", "-Wno-unknown-pragmas", "-o", _SO, src])
-
-
-class HostTangent:
-    """mpc_tangent_stage / dense_tangent of fb_tangent.h on one host thread."""
-
-    def __init__(self):
-        _build()
-        self.lib = C.CDLL(_SO)
-        self.lib.hostsim_mpc_tangent_rhs.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7
-        self.lib.hostsim_dense_tangent_rhs.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7
-
-    def rhs(self, p, x, d, budget=8192):
-        """(gz, gl, gv) of one QP at x = (z, l, v) for the perturbations ``d`` (name -> flat array or None).
-        Dense: ``budget`` doubles of LDS decide the column block; ``self.cb`` is what came of it."""
-        names = names_of(p)
-        pad = lambda a: a if a.size else np.zeros(1)
-        keep = [None if d.get(k) is None else pad(np.ascontiguousarray(d[k], dtype=np.float64)) for k in names]
-        ptrs = (C.c_void_p * len(names))(*[None if a is None else a.ctypes.data for a in keep])
-        z, l, v = (pad(np.ascontiguousarray(t, dtype=np.float64)) for t in x)
-        gz, gl, gv = (np.full(max(n, 1), np.nan) for n in (p.nz, p.nl, p.nv))
-        if is_mpc(p):
-            self.lib.hostsim_mpc_tangent_rhs(p.N, p.nx, p.nu, p.nc, ptrs, z.ctypes.data, l.ctypes.data,
-                                             v.ctypes.data, gz.ctypes.data, gl.ctypes.data, gv.ctypes.data)
-        else:
-            self.cb = self.lib.hostsim_dense_tangent_rhs(p.nz, p.nl, p.nv, budget, ptrs, z.ctypes.data,
-                                                         l.ctypes.data, v.ctypes.data, gz.ctypes.data,
-                                                         gl.ctypes.data, gv.ctypes.data)
-            assert self.cb >= 1, "not one column fits the budget"
-        return gz[:p.nz], gl[:p.nl], gv[:p.nv]

@@ -2,56 +2,15 @@
 the C-ABI without a GPU, and the flat-vector adjoint of fb_mpc.h compiled single-threaded for the host
 (tests/hostsim/adjoint.cc, against the shim hostsim.cc uses) against the oracle's linear solver."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from fbstab_amd.hip_api import MPC_SEQ
 from tools import fixtures as fx
 from tests import helpers as H
-from tests import adjoint_helpers as AH
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOSTSIM = os.path.join(ROOT, "tests", "hostsim")
-_SO = os.path.join(HOSTSIM, "libhostsim_adjoint.so")
-
-
-def _build():
-    src = os.path.join(HOSTSIM, "adjoint.cc")
-    shim = os.path.join(HOSTSIM, "shim")
-    deps = [src, os.path.join(shim, "hip", "hip_runtime.h")] + [
-        os.path.join(ROOT, "fbstab_amd", "csrc", f) for f in ("fb_common.h", "fb_mpc.h")]
-    if os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps):
-        return
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + shim,
-                           "-Wno-attributes", "-Wno-unknown-pragmas", "-o", _SO, src])
-
-
-class HostAdjoint:
-    def __init__(self):
-        _build()
-        self.lib = C.CDLL(_SO)
-        self.lib.hostsim_mpc_adjoint.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7 + [C.c_double, C.c_double,
-                                                                                     C.c_void_p, C.c_void_p]
-
-    def adjoint(self, p, q, x, seeds, sigma=AH.SIGMA, alpha=0.95, want=AH.MPC_SEQ):
-        """Adjoint of QP ``q`` at x = (z, l, v) for seeds (gz, gl, gv) (gl / gv may be None): (status, (dz, dl,
-        dv), gradients)."""
-        keep = [np.ascontiguousarray(p.arrays[k][q]) for k in AH.MPC_SEQ]
-        data = (C.c_void_p * 12)(*[a.ctypes.data for a in keep])
-        lens = p.seq_lengths()
-        grads = {k: np.full(lens[k], np.nan) for k in want}
-        gptr = (C.c_void_p * 12)(*[grads[k].ctypes.data if k in grads else None for k in AH.MPC_SEQ])
-        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-        z, l, v = (f64(t) for t in x)
-        gz, gl, gv = (f64(t) for t in seeds)
-        adj = np.full(p.nz + p.nl + p.nv, np.nan)
-        ptr = lambda a: None if a is None else a.ctypes.data
-        st = self.lib.hostsim_mpc_adjoint(p.N, p.nx, p.nu, p.nc, data, ptr(z), ptr(l), ptr(v), ptr(gz), ptr(gl),
-                                          ptr(gv), sigma, alpha, adj.ctypes.data, gptr)
-        return st, (adj[:p.nz], adj[p.nz:p.nz + p.nl], adj[p.nz + p.nl:]), grads
-
+from tests import linear_reference as LR
+from tests.hostsim import HostAdjoint
 
 @pytest.fixture(scope="module")
 def host():
@@ -75,17 +34,17 @@ def test_adjoint_residual_and_gradient_table_on_the_host(host, oracle, kats):
         for q in range(p.batch):
             points = [(sol[0][q], sol[1][q], sol[2][q]), (np.zeros(p.nz), np.zeros(p.nl), np.zeros(p.nv))]
             for x in points:
-                seeds = tuple(t[0] for t in AH.random_seeds(rng, p, 1))
+                seeds = tuple(t[0] for t in LR.random_seeds(rng, p, 1))
                 st, step, grads = host.adjoint(p, q, x, seeds)
                 assert st == 0
-                ref = AH.oracle_adjoint(oracle, p, q, x, seeds)
-                r_dev = AH.adjoint_residual(p, q, x, step, seeds)
-                r_orc = AH.adjoint_residual(p, q, x, ref, seeds)
+                ref = LR.oracle_adjoint(oracle, p, q, x, seeds)
+                r_dev = LR.adjoint_residual(p, q, x, step, seeds)
+                r_orc = LR.adjoint_residual(p, q, x, ref, seeds)
                 assert r_dev <= 3 * r_orc, (q, r_dev, r_orc)
                 scale = max(np.abs(np.concatenate(step)).max(), 1.0)
                 assert np.abs(np.concatenate(step) - np.concatenate(ref)).max() <= 1e-5 * scale  # (forward error: cond(V) ~ 1e11 at sigma = 1e-8)
-                tab = AH.gradient_table(AH.one_qp(p, q), x, step)
-                for k in AH.MPC_SEQ:
+                tab = LR.mpc_gradient_table(LR.one_qp(p, q), x, step)
+                for k in MPC_SEQ:
                     np.testing.assert_allclose(grads[k], tab[k], rtol=1e-14, atol=1e-14 * scale, err_msg=k)
                 checked += 1
     assert checked >= 2 * 7
@@ -115,7 +74,7 @@ def test_factorisation_failure_gives_status_1_and_zero_gradients(host):
     assert st == 1
     for t in step:
         assert np.array_equal(t, np.zeros_like(t))
-    for k in AH.MPC_SEQ:
+    for k in MPC_SEQ:
         assert np.array_equal(grads[k], np.zeros_like(grads[k])), k
 
 

@@ -7,9 +7,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from fbstab_amd.hip_api import DENSE_ARR
 from tools import fixtures as fx
 from tests import helpers as H
-from tests import dense_adjoint_helpers as DH
+from tests import linear_reference as LR
+from tests.hostsim import HostAdjoint
 
 SHAPES = [(20, 5, 40), (30, 0, 40), (90, 20, 150)]
 # the shapes on which the formulas were checked against central differences: with a quarter of the rows active
@@ -19,7 +21,7 @@ FD_SHAPES = [(20, 5, 40), (50, 10, 100), (30, 0, 40), (40, 8, 60), (56, 8, 128),
 
 @pytest.fixture(scope="module")
 def host():
-    return DH.HostDenseAdjoint()
+    return HostAdjoint("dense")
 
 
 def _problems(oracle, kats):
@@ -45,11 +47,11 @@ def test_adjoint_residual_and_gradient_table_on_the_host(host, oracle, kats):
         for q in range(p.batch):
             points = [(sol[0][q], sol[1][q], sol[2][q]), (np.zeros(p.nz), np.zeros(p.nl), np.zeros(p.nv))]
             for x in points:
-                seeds = tuple(t[0] for t in DH.random_seeds(rng, p, 1))
+                seeds = tuple(t[0] for t in LR.random_seeds(rng, p, 1))
                 st, step, grads = host.adjoint(p, q, x, seeds)
                 assert st == 0
-                ref = DH.oracle_adjoint(oracle, p, q, x, seeds)
-                DH.check_step_and_table(p, q, x, seeds, step, grads, ref)
+                ref = LR.oracle_adjoint(oracle, p, q, x, seeds)
+                LR.check_step_and_table(p, q, x, seeds, step, grads, ref)
                 checked += 1
     assert checked >= 2 * (3 + 4 * len(SHAPES))
 
@@ -79,7 +81,7 @@ def test_factorisation_failure_gives_status_1_and_zero_gradients(host, shape):
     assert st == 1
     for t in step:
         assert np.array_equal(t, np.zeros_like(t))
-    for k in DH.DENSE_ARR:
+    for k in DENSE_ARR:
         assert np.array_equal(grads[k], np.zeros_like(grads[k])), k
 
 
@@ -92,25 +94,25 @@ def test_central_differences_of_the_active_set_solution_map(host, shape):
     nz, nl, nv = shape
     p = fx.synthetic_dense_batch(16, nz, nl, nv)
     z, l, v = (p.solution[k] for k in ("z", "l", "v"))
-    strict = DH.strict_qps(p, z, v)
+    strict = LR.strict_qps(p, z, v)
     assert len(strict) >= 8, len(strict)
     rng = np.random.default_rng(97)
-    seeds = DH.random_seeds(rng, p)
+    seeds = LR.random_seeds(rng, p)
     h = 1e-6
     worst = 0.0
     for q, act in strict:
-        arr = {k: p.arrays[k][q] for k in DH.DENSE_ARR}
-        x0 = DH.active_set_solve(arr, nz, nl, nv, act)   # (the known solution, to rounding)
+        arr = {k: p.arrays[k][q] for k in DENSE_ARR}
+        x0 = LR.active_set_solve(arr, nz, nl, nv, act)   # (the known solution, to rounding)
         assert max(np.abs(x0[0] - z[q]).max(), np.abs(x0[2] - v[q]).max()) <= 1e-9
         st, _, grads = host.adjoint(p, q, (z[q], l[q], v[q]), tuple(t[q] for t in seeds))
         assert st == 0
-        dirs = DH.directions(rng, nz, nl, nv)
+        dirs = LR.directions(rng, nz, nl, nv)
         loss = lambda x: sum(float(seeds[t][q] @ x[t]) for t in range(3))
-        for k in DH.DENSE_ARR:
+        for k in DENSE_ARR:
             if dirs[k].size == 0:
                 continue
-            lp = loss(DH.active_set_solve({**arr, k: arr[k] + h * dirs[k]}, nz, nl, nv, act))
-            lm = loss(DH.active_set_solve({**arr, k: arr[k] - h * dirs[k]}, nz, nl, nv, act))
+            lp = loss(LR.active_set_solve({**arr, k: arr[k] + h * dirs[k]}, nz, nl, nv, act))
+            lm = loss(LR.active_set_solve({**arr, k: arr[k] - h * dirs[k]}, nz, nl, nv, act))
             fd = (lp - lm) / (2 * h)
             ad = float(grads[k] @ dirs[k])
             bar = max(abs(ad), 1e-2 * np.abs(grads[k]).sum())

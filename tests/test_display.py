@@ -66,29 +66,6 @@ def _device_trace(kind, p):
     return out[0], rec, (z, l, v, y)
 
 
-def _records_agree(dev, ref, what):
-    assert len(dev) == len(ref), (what, len(dev), len(ref))
-    assert np.array_equal(dev[:, :3], ref[:, :3]), what  # kinds, iteration numbers
-    # FP tolerance: the device evaluates the same formulas in a different order
-    # (DESIGN.md 3): 1e-6 relative, 1e-7 of the largest residual of the solve
-    # absolute (the linear blocks of the inner residual are rounding noise of
-    # that size after every Newton step).  Residuals below 1e-3 of that scale
-    # are what a converged Newton iteration leaves behind - quadratic convergence
-    # squares the rounding difference of the step before - and only have to
-    # agree within a factor of two.
-    d, r = dev[:, 3:], ref[:, 3:]
-    scale = _scale(ref)
-    err = np.abs(d - r)
-    tight = err <= 1e-7 * scale + 1e-6 * np.abs(r)
-    loose = (np.abs(r) < 1e-3 * scale) & (err <= 0.5 * np.maximum(np.abs(d), np.abs(r)))
-    bad = ~(tight | loose).all(axis=1)
-    assert not bad.any(), (what, dev[bad], ref[bad])
-
-
-def _scale(rec):
-    return max(1.0, float(np.abs(rec[:, 3:]).max()))
-
-
 @pytest.mark.gpu
 def test_device_trace_matches_the_oracle_on_the_known_answer_problems(oracle, kats, display_golden):
     done = set()
@@ -102,13 +79,13 @@ def test_device_trace_matches_the_oracle_on_the_known_answer_problems(oracle, ka
         out, rec, x = _device_trace(case["kind"], p)
         assert (out["eflag"], out["newton_iters"], out["prox_iters"]) == (
             case["eflag"], case["newton_iters"], case["prox_iters"]), case["name"]
-        _records_agree(rec, ref[6], case["name"])
+        H.records_agree(rec, ref[6], case["name"])
         # and the formatted text is the reference's, number for number
         for level in (2, 3):
             g = [c for c in display_golden if (c["kind"], c["index"], c["level"]) == (*key, level)][0]
             o = default_options(display_level=level)
             ok, why = H.display_texts_agree(H.format_display(rec, level, out, o), g["text"],
-                                            atol=1e-7 * _scale(ref[6]))
+                                            atol=1e-7 * H.records_scale(ref[6]))
             assert ok, (case["name"], level, why)
 
 
@@ -127,7 +104,7 @@ def test_device_trace_on_the_synthetic_workloads(oracle):
         assert out["eflag"] == ref[4]["eflag"][0] == 0
         assert out["prox_iters"] == ref[4]["prox_iters"][0]
         assert int(out["newton_iters"]) == int(ref[4]["newton_iters"][0])
-        _records_agree(rec, ref[6], kind)
+        H.records_agree(rec, ref[6], kind)
         assert rec[-1, 0] == 5 and rec[-1, 1] == 0  # FINAL record, SUCCESS
         assert np.hypot.reduce(rec[-1, 3:6]) == pytest.approx(out["residual"], rel=1e-9, abs=1e-15)
         for a, b in zip(x[:3], ref[:3]):
@@ -184,7 +161,7 @@ def test_final_summary_numbers_from_the_batch_kernels(oracle, kats, display_gold
             case["eflag"], case["newton_iters"], case["prox_iters"]), case["name"]
         fin = ref[6][-1]
         assert fin[0] == 5  # FBSTAB_TRACE_FINAL
-        _records_agree(np.concatenate([fin[:3], nrm[0], [0.0]])[None, :], fin[None, :], case["name"])
+        H.records_agree(np.concatenate([fin[:3], nrm[0], [0.0]])[None, :], fin[None, :], case["name"])
         assert nrm[0, 3] == pytest.approx(fin[6], rel=1e-12)
     # batches on the record kernel and the one-wavefront dense kernel, device memory
     import torch

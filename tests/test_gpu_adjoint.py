@@ -5,11 +5,12 @@ invariance under the queue, and torch autograd."""
 import numpy as np
 import pytest
 
+from fbstab_amd.hip_api import MPC_SEQ
 from tools import fixtures as fx
 from oracle.oracle_py import default_options
 from tests import helpers as H
-from tests import adjoint_helpers as AH
-from tests.test_gpu_components import _MPC_SHAPES
+from tests import linear_reference as LR
+from tests.shapes import MPC_SHAPES
 
 pytestmark = pytest.mark.gpu
 
@@ -23,84 +24,42 @@ def hip():
     return hip_api
 
 
-def _solve(hip, p, o=None):
-    s = hip.FBstabMpcBatch(*p.sizes(), max_batch=p.batch)
-    if o is not None:
-        s.UpdateOptions(H._opts(hip, o))
-    z, l, v, y = (np.zeros((p.batch, n)) for n in (p.nz, p.nl, p.nv, p.nv))
-    out = s.Solve(p.arrays, z, l, v, y)
-    return s, (z, l, v), out
-
-
-def _check_residual_and_table(oracle, p, x, seeds, res):
-    """Per QP: the device's residual within 3 x the oracle's, its step within the forward error of the oracle's,
-    the residual's own (C, mus) those of the oracle's RiccatiLinearSolver, and the gradient table."""
-    assert (res["status"] == 0).all()
-    for q in range(p.batch):
-        xq = tuple(t[q] for t in x)
-        sq = tuple(t[q] for t in seeds)
-        step = tuple(res[k][q] for k in ("dz", "dl", "dv"))
-        ref = AH.oracle_adjoint(oracle, p, q, xq, sq)
-        z, l, v = xq
-        pr = oracle.probe(AH.one_qp(p, q), z, l, v, z, l, v, AH.SIGMA, 0.95, r=np.zeros(p.nz + p.nl + p.nv), want_dx=True)
-        C, mus = AH.fb_derivatives(p, q, xq)
-        # (rows where both precisions take the same branch of the FB function: away from its switch at |(y, v)| =
-        # 1e-13, and y of the same sign - on an active row y is zero to rounding, and the penalty term's kink at
-        # y = 0 moves C by (1 - alpha) v with its sign)
-        Am, bv = (m.astype(np.longdouble) for m in H.mpc_explicit(p, q)[4:])
-        ys = bv - Am @ z.astype(np.longdouble)
-        rr = np.hypot(pr["x_y"], v)
-        far = ((rr >= 1e-12) | (rr < 1e-14)) & (np.sign(pr["x_y"]) == np.sign(ys.astype(np.float64)))
-        assert far.sum() >= len(far) // 2
-        np.testing.assert_allclose(C.astype(np.float64)[far], pr["gamma"][far], rtol=1e-12, atol=1e-13)
-        np.testing.assert_allclose(mus.astype(np.float64)[far], pr["mus"][far], rtol=1e-12, atol=1e-13)
-        r_dev = AH.adjoint_residual(p, q, xq, step, sq)
-        r_orc = AH.adjoint_residual(p, q, xq, ref, sq)
-        assert r_dev <= 3 * r_orc, (q, r_dev, r_orc)
-        smax = max(np.abs(np.concatenate(step)).max(), 1.0)
-        assert np.abs(np.concatenate(step) - np.concatenate(ref)).max() <= 1e-5 * smax, q  # (forward error, cond(V) ~ 1e11)
-        scale = smax * max(np.abs(np.concatenate(xq)).max(), 1.0)
-        tab = AH.gradient_table(AH.one_qp(p, q), xq, step)
-        for k in AH.MPC_SEQ:
-            np.testing.assert_allclose(res[k][q], tab[k], rtol=1e-13, atol=1e-15 * scale, err_msg=k)
-
-
-_ONE_PER_KERNEL = [next(i for i, (_, n) in enumerate(_MPC_SHAPES) if n == name)
-                   for name in dict.fromkeys(n for _, n in _MPC_SHAPES)]
+_ONE_PER_KERNEL = [next(i for i, (_, n) in enumerate(MPC_SHAPES) if n == name)
+                   for name in dict.fromkeys(n for _, n in MPC_SHAPES)]
 
 
 ONE_ROW = ("fbstab_mpc_r16_kernel<12,4,20>", "fbstab_mpc_r16_kernel<12,4,32>")
 
 
-@pytest.mark.parametrize("idx", _ONE_PER_KERNEL, ids=[_MPC_SHAPES[i][1] for i in _ONE_PER_KERNEL])
+@pytest.mark.parametrize("idx", _ONE_PER_KERNEL, ids=[MPC_SHAPES[i][1] for i in _ONE_PER_KERNEL])
 def test_adjoint_residual_against_the_oracle_on_one_shape_per_solve_kernel(hip, oracle, monkeypatch, idx):
     """At the device's solutions of random LTV QPs, on one shape per solve kernel: V (dz, dl, dv) = (gz, -gl, -C.gv)
     within 3 x the oracle's residual (longdouble), and the gradients are the table applied to the returned adjoint.
     The one-row record instances' handles run the RECORD adjoint (fbstab_mpc_r16_adjoint_kernel) - a kernel of
     its own: its bits are not the flat-vector adjoint's, which the same QPs are put through as well (FBSTAB_HIP_GENERIC)
     and checked by the same rule; the other handles run the flat-vector adjoint."""
-    shape, kern = _MPC_SHAPES[idx]
+    shape, kern = MPC_SHAPES[idx]
     monkeypatch.setenv("FBSTAB_HIP_GENERIC", "1" if kern == "fbstab_mpc_kernel<64>" else "0")
     p = fx.random_ltv_mpc(np.random.default_rng(7100 + idx), 3, *shape)
-    s, x, out = _solve(hip, p)
+    s, x, out = H.cold_solve(hip, p)
     assert s.kernel_name() == kern
-    seeds = AH.random_seeds(np.random.default_rng(idx), p)
+    seeds = LR.random_seeds(np.random.default_rng(idx), p)
     res = s.Adjoint(p.arrays, *x, *seeds, adj=True)
-    _check_residual_and_table(oracle, p, x, seeds, res)
+    LR.check_mpc_batch(oracle, p, x, seeds, res)
     if kern in ONE_ROW:
         monkeypatch.setenv("FBSTAB_HIP_GENERIC", "1")
         flat = hip.FBstabMpcBatch(*p.sizes(), max_batch=p.batch).Adjoint(p.arrays, *x, *seeds, adj=True)
-        _check_residual_and_table(oracle, p, x, seeds, flat)
+        LR.check_mpc_batch(oracle, p, x, seeds, flat)
         assert not all(np.array_equal(res[k], flat[k]) for k in ("dz", "dl", "dv"))
 
 
 def test_adjoint_residual_against_the_oracle_on_the_baseline_batch(hip, oracle):
     p = fx.synthetic_mpc_batch(8)
-    s, x, out = _solve(hip, p)
+    s, x, out = H.cold_solve(hip, p)
     assert (out["eflag"] == 0).all()
-    seeds = AH.random_seeds(np.random.default_rng(3), p)
+    seeds = LR.random_seeds(np.random.default_rng(3), p)
     res = s.Adjoint(p.arrays, *x, *seeds, adj=True)
-    _check_residual_and_table(oracle, p, x, seeds, res)
+    LR.check_mpc_batch(oracle, p, x, seeds, res)
 
 
 def _sym_direction(rng, n, stages):
@@ -116,12 +75,12 @@ def test_central_differences_of_the_solution_map(hip):
     shape = (6, 4, 2, 6)
     base = fx.random_ltv_mpc(rng, 8, *shape)
     o = default_options(abs_tol=1e-11)
-    s, x, out = _solve(hip, base, o)
+    s, x, out = H.cold_solve(hip, base, o)
     assert (out["eflag"] == 0).all()
     y = np.stack([H.mpc_explicit(base, q)[5] - H.mpc_explicit(base, q)[4] @ x[0][q] for q in range(base.batch)])
     strict = [q for q in range(base.batch) if np.maximum(y[q], x[2][q]).min() >= 1e-3]
     assert len(strict) >= 3, strict
-    seeds = AH.random_seeds(rng, base)
+    seeds = LR.random_seeds(rng, base)
     grad = s.Adjoint(base.arrays, *x, *seeds)
     N, nx, nu, nc = shape
     h = 1e-5
@@ -134,11 +93,11 @@ def test_central_differences_of_the_solution_map(hip):
         else:
             dirs[k] = rng.standard_normal(n)
     # one batch: QP q, sequence k, sign
-    cases = [(q, k, sg) for q in strict for k in AH.MPC_SEQ for sg in (1.0, -1.0)]
+    cases = [(q, k, sg) for q in strict for k in MPC_SEQ for sg in (1.0, -1.0)]
     arr = {k: np.ascontiguousarray(np.stack([base.arrays[k][q] + (sg * h * dirs[k] if kk == k else 0.0)
-                                             for q, kk, sg in cases])) for k in AH.MPC_SEQ}
+                                             for q, kk, sg in cases])) for k in MPC_SEQ}
     pert = fx.MpcProblem(N, nx, nu, nc, arr)
-    _, xp, outp = _solve(hip, pert, o)
+    _, xp, outp = H.cold_solve(hip, pert, o)
     assert (outp["eflag"] == 0).all()
     loss = lambda j: sum(float(seeds[t][cases[j][0]] @ xp[t][j]) for t in range(3))
     for j in range(0, len(cases), 2):
@@ -146,23 +105,6 @@ def test_central_differences_of_the_solution_map(hip):
         fd = (loss(j) - loss(j + 1)) / (2 * h)
         ad = float(grad[k][q] @ dirs[k])
         assert abs(fd - ad) <= 1e-4 * max(abs(ad), 1e-2 * np.abs(grad[k][q]).sum()), (q, k, fd, ad)
-
-
-def _lqr_gain(p):
-    """-K_0 of the finite-horizon Riccati recursion of QP 0 (stage cost 1/2 [x;u]'[Q S';S R][x;u], the
-    terminal stage's input eliminated)."""
-    N, nx, nu, nc = p.sizes()
-    a = {k: v[0] for k, v in p.arrays.items()}
-    mat = lambda key, i, r, c: a[key][i * r * c:(i + 1) * r * c].reshape(c, r).T
-    Q, R, S = (lambda i: mat("Q", i, nx, nx)), (lambda i: mat("R", i, nu, nu)), (lambda i: mat("S", i, nu, nx))
-    P = Q(N) - S(N).T @ np.linalg.solve(R(N), S(N))
-    K = None
-    for i in range(N - 1, -1, -1):
-        A, B = mat("A", i, nx, nx), mat("B", i, nx, nu)
-        Quu, Qux, Qxx = R(i) + B.T @ P @ B, S(i) + B.T @ P @ A, Q(i) + A.T @ P @ A
-        K = np.linalg.solve(Quu, Qux)
-        P = Qxx - Qux.T @ K
-    return -K
 
 
 def test_lqr_gain_from_seeded_input_rows(hip):
@@ -175,7 +117,7 @@ def test_lqr_gain_from_seeded_input_rows(hip):
     p.arrays["E"][:] = 0.0
     p.arrays["L"][:] = 0.0
     p.arrays["d"][:] = -1.0   # 0 <= 1 on every row: inactive, y = 1, v = 0
-    K = _lqr_gain(p)
+    K = H.lqr_gain(p)
     u0 = K @ p.arrays["x0"][0]
     if u0[0] < 0:
         p.arrays["x0"][:] *= -1.0
@@ -184,7 +126,7 @@ def test_lqr_gain_from_seeded_input_rows(hip):
     def rows(prob):
         rep = fx.MpcProblem(N, nx, nu, nc, {k: np.ascontiguousarray(np.repeat(v, nu, axis=0)) for k, v in prob.arrays.items()})
         o = default_options(abs_tol=1e-11)
-        s, x, out = _solve(hip, rep, o)
+        s, x, out = H.cold_solve(hip, rep, o)
         assert (out["eflag"] == 0).all()
         gz = np.zeros((nu, rep.nz))
         for j in range(nu):
@@ -208,8 +150,8 @@ def test_gradients_are_bitwise_the_same_alone_packed_and_queued(hip, monkeypatch
     """QP gradients do not depend on where the queue puts them: alone, in a batch on two workgroups (every
     workgroup re-fetching), and in a batch on the whole grid."""
     p = fx.random_ltv_mpc(np.random.default_rng(5150), 24, 5, 6, 3, 8)
-    s, x, out = _solve(hip, p)
-    seeds = AH.random_seeds(np.random.default_rng(9), p)
+    s, x, out = H.cold_solve(hip, p)
+    seeds = LR.random_seeds(np.random.default_rng(9), p)
     full = s.Adjoint(p.arrays, *x, *seeds, adj=True)
     monkeypatch.setenv(CAP, "2")
     packed_h = hip.FBstabMpcBatch(*p.sizes(), max_batch=p.batch)
@@ -220,9 +162,9 @@ def test_gradients_are_bitwise_the_same_alone_packed_and_queued(hip, monkeypatch
     for q in (0, 7, 23):
         one = {k: np.ascontiguousarray(a[q:q + 1]) for k, a in p.arrays.items()}
         alone = alone_h.Adjoint(one, *(t[q:q + 1] for t in x), *(t[q:q + 1] for t in seeds), adj=True)
-        for k in AH.MPC_SEQ + ("dz", "dl", "dv"):
+        for k in MPC_SEQ + ("dz", "dl", "dv"):
             assert np.array_equal(alone[k][0], full[k][q]), (q, k)
-    for k in AH.MPC_SEQ + ("dz", "dl", "dv"):
+    for k in MPC_SEQ + ("dz", "dl", "dv"):
         assert np.array_equal(packed[k], full[k]), k
 
 
@@ -248,12 +190,12 @@ def test_autograd_matches_the_c_abi_and_zeroes_unsolved_qps(hip):
     eflag = hip.out_to_numpy(out)["eflag"]
     assert eflag[1] != 0 and (np.delete(eflag, 1) == 0).all(), eflag
     rng = np.random.default_rng(12)
-    a, b, c = (torch.from_numpy(t).to(dev) for t in AH.random_seeds(rng, p))
+    a, b, c = (torch.from_numpy(t).to(dev) for t in LR.random_seeds(rng, p))
     loss = (a * z).sum() + (b * l).sum() + (c * v).sum()
     loss.backward()
     ref = solver.Adjoint({k: t.detach() for k, t in data.items()}, z.detach(), l.detach(), v.detach(), a, b, c)
     torch.cuda.synchronize()
-    for k in AH.MPC_SEQ:
+    for k in MPC_SEQ:
         if k not in want:
             assert data[k].grad is None, k
             continue

@@ -14,8 +14,7 @@ import numpy as np
 import pytest
 
 from tools import fixtures as fx
-from tests import adjoint_helpers as AH
-from tests import dense_adjoint_helpers as DH
+from tests import linear_reference as LR
 from tests import reduced_helpers as R
 
 pytestmark = pytest.mark.gpu
@@ -45,12 +44,12 @@ class Case:
             self.names, self.matrices = R.DENSE_ARR, R.DENSE_MATRICES
             self.p = problem or fx.synthetic_dense_batch(B, *shape, first_id=1000)
             self.make = lambda mb=B: hip.FBstabDenseBatch(*shape, max_batch=mb)
-            self.seeds = DH.random_seeds(np.random.default_rng(B), self.p)
+            self.seeds = LR.random_seeds(np.random.default_rng(B), self.p)
         else:
             self.names, self.matrices = R.MPC_SEQ, R.MPC_MATRICES
             self.p = problem or fx.random_ltv_mpc(np.random.default_rng(9000 + shape[1]), B, *shape)
             self.make = lambda mb=B: hip.FBstabMpcBatch(*shape, max_batch=mb)
-            self.seeds = AH.random_seeds(np.random.default_rng(B), self.p)
+            self.seeds = LR.random_seeds(np.random.default_rng(B), self.p)
         self.vectors = tuple(k for k in self.names if k not in self.matrices)
         self.data = {k: np.ascontiguousarray(a) for k, a in self.p.arrays.items()}
         self.s = self.make()
@@ -277,7 +276,7 @@ def test_autograd_dense_shared_matrices(hip):
     z, l, v, out = solve_dense(solver, data)
     eflag = hip.out_to_numpy(out)["eflag"]
     assert eflag[q] != 0 and (np.delete(eflag, q) == 0).all(), eflag
-    seeds = [t(s) for s in DH.random_seeds(np.random.default_rng(12), p)]
+    seeds = [t(s) for s in LR.random_seeds(np.random.default_rng(12), p)]
     (sum((a * w).sum() for a, w in zip(seeds, (z, l, v)))).backward()
     # the existing per-QP path on expanded and cloned inputs
     wide = {k: (a.detach().expand(B, -1).clone() if k in shared else a.detach().clone()).requires_grad_(True)
@@ -337,7 +336,7 @@ def test_autograd_mpc_shared_matrices(hip):
     z, l, v, out = solve_mpc(solver, data)
     eflag = hip.out_to_numpy(out)["eflag"]
     assert eflag[q] != 0 and (np.delete(eflag, q) == 0).all(), eflag
-    seeds = [t(s) for s in AH.random_seeds(np.random.default_rng(12), p)]
+    seeds = [t(s) for s in LR.random_seeds(np.random.default_rng(12), p)]
     (sum((a * w).sum() for a, w in zip(seeds, (z, l, v)))).backward()
     wide = {k: (a.detach().reshape(1, -1).expand(B, -1).clone() if k in shared + ("S",) else a.detach().clone())
             .requires_grad_(a.requires_grad) for k, a in data.items()}

@@ -4,14 +4,15 @@ step and against the flat-vector adjoint of the same QPs (FBSTAB_HIP_FLAT_ADJOIN
 the re-fetch, the rebuild of kept matrix copies, torch autograd on a wide shape, and the status of a QP whose
 factorisation fails.  Handles are created under FBSTAB_HIP_FLAT_ADJOINT=0, which selects the record adjoint: a
 row-pair handle's default stays the flat-vector adjoint until the two have been timed on the wide workloads
-(test_the_knob_and_the_defaults).  The bars are those of tests/test_gpu_adjoint.py (_check_residual_and_table): residual within
+(test_the_knob_and_the_defaults).  The bars are those of tests/linear_reference.py (check_mpc_batch): residual within
 3 x the oracle's, step within 1e-5 of the oracle's, the gradient table at rtol 1e-13."""
 import numpy as np
 import pytest
 
+from fbstab_amd.hip_api import MPC_SEQ
 from tools import fixtures as fx
-from tests import adjoint_helpers as AH
-from tests.test_gpu_adjoint import _check_residual_and_table, _solve
+from tests import helpers as H
+from tests import linear_reference as LR
 
 pytestmark = pytest.mark.gpu
 
@@ -85,15 +86,15 @@ def test_record_adjoint_against_the_oracle_and_the_flat_adjoint(hip, oracle, mon
     inst, shape, _, family, seed = case
     monkeypatch.setenv(FLAT, "0")
     p = _FAMILIES[family](np.random.default_rng(seed), 3, *shape)
-    s, x, out = _solve(hip, p)
+    s, x, out = H.cold_solve(hip, p)
     assert s.kernel_name() == "fbstab_mpc_r32_kernel" + inst
     assert s.adjoint_kernel_name().startswith(RECORD_ADJOINT)
     assert (out["eflag"] == 0).all(), out["eflag"]
-    seeds = AH.random_seeds(np.random.default_rng(seed + 1000), p)
+    seeds = LR.random_seeds(np.random.default_rng(seed + 1000), p)
     flat = _flat_handle(hip, monkeypatch, p).Adjoint(p.arrays, *x, *seeds, adj=True)
-    _check_residual_and_table(oracle, p, x, seeds, flat)
+    LR.check_mpc_batch(oracle, p, x, seeds, flat)
     res = s.Adjoint(p.arrays, *x, *seeds, adj=True)
-    _check_residual_and_table(oracle, p, x, seeds, res)
+    LR.check_mpc_batch(oracle, p, x, seeds, res)
     assert not all(np.array_equal(res[k], flat[k]) for k in STEP)
 
 
@@ -105,10 +106,10 @@ def test_both_qps_of_a_wavefront_refetch_and_queue_invariance(hip, oracle, monke
     QPs of the packed run pass the rule against the oracle."""
     monkeypatch.setenv(FLAT, "0")
     p = fx.random_ltv_mpc(np.random.default_rng(5200 + shape[1]), 24, *shape)
-    s, x, out = _solve(hip, p)
+    s, x, out = H.cold_solve(hip, p)
     assert s.kernel_name() == "fbstab_mpc_r32_kernel" + inst
     assert s.adjoint_kernel_name().startswith(RECORD_ADJOINT)
-    seeds = AH.random_seeds(np.random.default_rng(10), p)
+    seeds = LR.random_seeds(np.random.default_rng(10), p)
     full = s.Adjoint(p.arrays, *x, *seeds, adj=True)
     monkeypatch.setenv(CAP, "2")
     packed_h = hip.FBstabMpcBatch(*p.sizes(), max_batch=p.batch)
@@ -120,12 +121,12 @@ def test_both_qps_of_a_wavefront_refetch_and_queue_invariance(hip, oracle, monke
     for q in (0, 7, 23):
         one = {k: np.ascontiguousarray(a[q:q + 1]) for k, a in p.arrays.items()}
         alone = alone_h.Adjoint(one, *(t[q:q + 1] for t in x), *(t[q:q + 1] for t in seeds), adj=True)
-        for k in AH.MPC_SEQ + STEP:
+        for k in MPC_SEQ + STEP:
             assert np.array_equal(alone[k][0], full[k][q]), (q, k)
-    for k in AH.MPC_SEQ + STEP:
+    for k in MPC_SEQ + STEP:
         assert np.array_equal(packed[k], full[k]), k
     assert (out["eflag"] == 0).all(), out["eflag"]
-    _check_residual_and_table(oracle, p, x, seeds, packed)
+    LR.check_mpc_batch(oracle, p, x, seeds, packed)
 
 
 @pytest.mark.parametrize("cap", [None, "1"], ids=["one_qp_per_wavefront", "one_wavefront"])
@@ -138,7 +139,7 @@ def test_failed_factorisation_is_reported_through_status(hip, monkeypatch, inst,
     the step early while the other carries on - and QP 2 is fetched after the failure."""
     monkeypatch.setenv(FLAT, "0")
     ref = fx.random_ltv_mpc(np.random.default_rng(5400 + shape[1]), 3, *shape)
-    s0, x, out = _solve(hip, ref)
+    s0, x, out = H.cold_solve(hip, ref)
     assert s0.kernel_name() == "fbstab_mpc_r32_kernel" + inst and (out["eflag"] == 0).all()
     bad = fx.MpcProblem(ref.N, ref.nx, ref.nu, ref.nc, {k: a.copy() for k, a in ref.arrays.items()})
     bad.arrays["Q"][1, 0] = np.nan
@@ -149,11 +150,11 @@ def test_failed_factorisation_is_reported_through_status(hip, monkeypatch, inst,
         monkeypatch.delenv(CAP)
         assert s.query()["workgroups"] == 1
     assert s.adjoint_kernel_name().startswith(RECORD_ADJOINT)
-    seeds = AH.random_seeds(np.random.default_rng(14), ref)
+    seeds = LR.random_seeds(np.random.default_rng(14), ref)
     res = s.Adjoint(bad.arrays, *x, *seeds, adj=True)
     good = s.Adjoint(ref.arrays, *x, *seeds, adj=True)
     assert res["status"].tolist() == [0, 1, 0] and good["status"].tolist() == [0, 0, 0]
-    for k in AH.MPC_SEQ + STEP:
+    for k in MPC_SEQ + STEP:
         assert np.array_equal(res[k][1], np.zeros_like(res[k][1])), k
         assert np.array_equal(res[k][[0, 2]], good[k][[0, 2]]) and np.abs(good[k][1]).max() > 0, k
 
@@ -167,7 +168,7 @@ def test_kept_matrices_are_rebuilt_after_an_adjoint(hip, monkeypatch):
     dev = torch.device("cuda:0")
     p = fx.random_ltv_mpc(np.random.default_rng(5301), 6, 4, 18, 5, 10)
     data = {k: torch.from_numpy(a).to(dev) for k, a in p.arrays.items()}
-    seeds = [torch.from_numpy(t).to(dev) for t in AH.random_seeds(np.random.default_rng(11), p)]
+    seeds = [torch.from_numpy(t).to(dev) for t in LR.random_seeds(np.random.default_rng(11), p)]
     mk = lambda n: torch.zeros((p.batch, n), dtype=torch.float64, device=dev)
 
     def keep_solve(s):
@@ -218,12 +219,12 @@ def test_autograd_on_a_wide_shape_matches_the_c_abi_and_zeroes_unsolved_qps(hip,
     z, l, v, out = solve_mpc(solver, data)
     eflag = hip.out_to_numpy(out)["eflag"]
     assert eflag[1] != 0 and (np.delete(eflag, 1) == 0).all(), eflag
-    a, b, c = (torch.from_numpy(t).to(dev) for t in AH.random_seeds(np.random.default_rng(13), p))
+    a, b, c = (torch.from_numpy(t).to(dev) for t in LR.random_seeds(np.random.default_rng(13), p))
     loss = (a * z).sum() + (b * l).sum() + (c * v).sum()
     loss.backward()
     ref = solver.Adjoint({k: t.detach() for k, t in data.items()}, z.detach(), l.detach(), v.detach(), a, b, c)
     torch.cuda.synchronize()
-    for k in AH.MPC_SEQ:
+    for k in MPC_SEQ:
         if k not in want:
             assert data[k].grad is None, k
             continue

@@ -13,6 +13,7 @@ import pytest
 from tools import fixtures as fx
 from oracle.oracle_py import default_options
 from tests import helpers as H
+from tests.shapes import MPC_SHAPES, DEGENERATE_SHAPES, fuzz_dense_instances
 
 pytestmark = pytest.mark.gpu
 
@@ -29,23 +30,6 @@ def _opts(hip, o):
     for name, _ in h._fields_:
         setattr(h, name, getattr(o, name))
     return h
-
-
-def _pfb_gradient(ys, v, alpha, sigma):
-    """(gamma, mus) of riccati_linear_solver.cc:346-365 / :91-99, in numpy."""
-    r = np.sqrt(ys * ys + v * v)
-    d = alpha * (1.0 - 1.0 / np.sqrt(2.0))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        g = np.where(r < 1e-13, d, alpha * (1.0 - ys / r))
-        m = np.where(r < 1e-13, d, alpha * (1.0 - v / r))
-    both = (r >= 1e-13) & (ys > 0) & (v > 0)
-    g = g + np.where(both, (1.0 - alpha) * v, 0.0)
-    m = m + np.where(both, (1.0 - alpha) * ys, 0.0)
-    return g, m + sigma * g
-
-
-def _pfb(a, b, alpha):
-    return alpha * (a + b - np.sqrt(a * a + b * b)) + (1.0 - alpha) * np.maximum(a, 0) * np.maximum(b, 0)
 
 
 @pytest.mark.parametrize("kernel", ["r16", "generic"])
@@ -90,9 +74,9 @@ def test_mpc_component_goldens_through_the_hip_probe(hip, kats, monkeypatch, ker
     # rv = phi(y + sigma (v - vbar), v): the third block row of the Newton system,
     # -gamma (A dz) + mus dv = -rv, gives it back from the device's step
     y = b - A @ z
-    gam, mus = _pfb_gradient(y + 1.0 * (v - vb), v, alpha, 1.0)
+    gam, mus = H.pfb_gradient(y + 1.0 * (v - vb), v, alpha, 1.0)
     np.testing.assert_allclose(gam * g["adz"] - mus * g["dv"], gi["rv"], rtol=0, atol=1e-12)
-    np.testing.assert_allclose(_pfb(y + (v - vb), v, alpha), gi["rv"], rtol=0, atol=1e-13)
+    np.testing.assert_allclose(H.pfb(y + (v - vb), v, alpha), gi["rv"], rtol=0, atol=1e-13)
 
     # ---- the Riccati golden's point: x = (1,2,4), xbar = (2,1,3), sigma = 1 (:386-461):
     # every block of V dx - r vanishes (r = -inner residual here), W = (H dz + G'dl + A'dv, -G dz)
@@ -101,10 +85,10 @@ def test_mpc_component_goldens_through_the_hip_probe(hip, kats, monkeypatch, ker
     g = s.debug_newton(data, z, l, v, zb, lb, vb)
     assert g["ok"]
     y = b - A @ z
-    gam, mus = _pfb_gradient(y + (v - vb), v, alpha, 1.0)
+    gam, mus = H.pfb_gradient(y + (v - vb), v, alpha, 1.0)
     rz = -(g["rz"] + (z - zb))
     rl = -(g["rl"] + (l - lb))
-    rv = -_pfb(y + (v - vb), v, alpha)
+    rv = -H.pfb(y + (v - vb), v, alpha)
     e1 = Hm @ g["dz"] + g["dz"] + G.T @ g["dl"] + A.T @ g["dv"] - rz
     e2 = -G @ g["dz"] + g["dl"] - rl
     e3 = -gam * (A @ g["dz"]) + mus * g["dv"] - rv
@@ -139,44 +123,25 @@ def test_dense_component_goldens_through_the_hip_probe(hip, kats, monkeypatch, t
     np.testing.assert_allclose(g["rz"] + sigma * (z - zb), gi["rz"], rtol=0, atol=1e-13)
     y = b - A @ z
     np.testing.assert_allclose(np.minimum(y, v), gn["rv"], rtol=0, atol=1e-14)
-    gam, mus = _pfb_gradient(y + sigma * (v - vb), v, alpha, sigma)
+    gam, mus = H.pfb_gradient(y + sigma * (v - vb), v, alpha, sigma)
     np.testing.assert_allclose(gam * (A @ g["dz"]) - mus * g["dv"], gi["rv"], rtol=0, atol=1e-12)
     # linear solver (:169-208): both block rows of the eliminated-free system vanish
     rz = -(g["rz"] + sigma * (z - zb))
-    rv = -_pfb(y + sigma * (v - vb), v, alpha)
+    rv = -H.pfb(y + sigma * (v - vb), v, alpha)
     e1 = Hm @ g["dz"] + sigma * g["dz"] + A.T @ g["dv"] - rz
     e3 = -gam * (A @ g["dz"]) + mus * g["dv"] - rv
     assert np.sqrt(e1 @ e1 + e3 @ e3) <= gl["tol"]
     s.close()
 
 
-# ---- seeded random shapes over every MPC instance ---------------------------------
-# (N, nx, nu, nc) -> the kernel fbstab_hip_mpc_create must pick (fbstab_hip.hip:
-# record_instance_for); four shapes per instance, exact and padded.
-_MPC_SHAPES = [
-    ((6, 12, 4, 20), "fbstab_mpc_r16_kernel<12,4,20>"), ((9, 5, 2, 7), "fbstab_mpc_r16_kernel<12,4,20>"),
-    ((3, 12, 1, 17), "fbstab_mpc_r16_kernel<12,4,20>"), ((11, 1, 4, 1), "fbstab_mpc_r16_kernel<12,4,20>"),
-    ((5, 12, 4, 32), "fbstab_mpc_r16_kernel<12,4,32>"), ((8, 7, 3, 21), "fbstab_mpc_r16_kernel<12,4,32>"),
-    ((2, 11, 4, 27), "fbstab_mpc_r16_kernel<12,4,32>"), ((12, 3, 1, 30), "fbstab_mpc_r16_kernel<12,4,32>"),
-    ((7, 18, 5, 10), "fbstab_mpc_r32_kernel<18,5,10>"), ((4, 13, 2, 6), "fbstab_mpc_r32_kernel<18,5,10>"),
-    ((10, 16, 5, 9), "fbstab_mpc_r32_kernel<18,5,10>"), ((3, 12, 5, 3), "fbstab_mpc_r32_kernel<18,5,10>"),
-    ((5, 24, 8, 16), "fbstab_mpc_r32_kernel<24,8,16>"), ((6, 20, 6, 16), "fbstab_mpc_r32_kernel<24,8,16>"),
-    ((9, 19, 2, 12), "fbstab_mpc_r32_kernel<24,8,16>"), ((2, 14, 7, 11), "fbstab_mpc_r32_kernel<24,8,16>"),
-    ((4, 24, 8, 32), "fbstab_mpc_r32_kernel<24,8,32>"), ((7, 20, 6, 30), "fbstab_mpc_r32_kernel<24,8,32>"),
-    ((3, 22, 3, 17), "fbstab_mpc_r32_kernel<24,8,32>"), ((8, 13, 8, 25), "fbstab_mpc_r32_kernel<24,8,32>"),
-    ((4, 26, 3, 9), "fbstab_mpc_kernel<64>"), ((3, 10, 9, 12), "fbstab_mpc_kernel<64>"),
-    ((5, 8, 2, 33), "fbstab_mpc_kernel<64>"), ((2, 25, 9, 5), "fbstab_mpc_kernel<64>"),
-]
-
-
-@pytest.mark.parametrize("idx", range(len(_MPC_SHAPES)))
+@pytest.mark.parametrize("idx", range(len(MPC_SHAPES)))
 def test_random_shapes_on_every_mpc_instance(hip, oracle, idx):
     """tools/fuzz_shapes.py, a fixed subset: random time-varying problems (dense
     constraint rows, S != 0) of shapes chosen to land on each of the five record
     instances and on the flat-vector kernel, a third of them with a restricted line
     search.  Exit flags and proximal counts equal the oracle's; Newton counts differ
     by at most 2; solutions within the parity tolerance."""
-    (N, nx, nu, nc), kern = _MPC_SHAPES[idx]
+    (N, nx, nu, nc), kern = MPC_SHAPES[idx]
     rng = np.random.default_rng(7000 + idx)
     B = int(rng.integers(2, 12))
     o = default_options()
@@ -201,12 +166,12 @@ def test_random_shapes_on_every_mpc_instance(hip, oracle, idx):
         assert (np.abs(z - c[0])[good] <= 10 * o.abs_tol * scale[good]).all()
 
 
-@pytest.mark.parametrize("idx", range(0, len(_MPC_SHAPES), 2))
+@pytest.mark.parametrize("idx", range(0, len(MPC_SHAPES), 2))
 def test_random_shapes_with_bound_constraints_on_every_mpc_instance(hip, oracle, idx):
     """The same with BOUND constraints (fixtures.random_ltv_mpc_bounds: one +-1 entry per row) - the
     constraints that take the record kernels' row form of the costate step, on the one-row instances
     (explicit inverse of Lc) and the row-pair ones (substitution) alike: every count equal to the oracle's."""
-    (N, nx, nu, nc), kern = _MPC_SHAPES[idx]
+    (N, nx, nu, nc), kern = MPC_SHAPES[idx]
     rng = np.random.default_rng(7500 + idx)
     B = int(rng.integers(2, 10))
     o = default_options()
@@ -228,12 +193,12 @@ def test_random_shapes_with_bound_constraints_on_every_mpc_instance(hip, oracle,
         assert (np.abs(z - c[0])[good] <= 10 * o.abs_tol * scale[good]).all()
 
 
-@pytest.mark.parametrize("idx", range(1, len(_MPC_SHAPES), 2))
+@pytest.mark.parametrize("idx", range(1, len(MPC_SHAPES), 2))
 def test_random_shapes_with_sparse_constraint_rows_on_every_mpc_instance(hip, oracle, idx):
     """The same with SPARSE rows (fixtures.random_ltv_mpc_sparse_rows: two or three entries of 0.3 .. 0.8 per
     row) - rows that take the row form of the costate step without being bounds (choose_costate_form:
     nonzeros per row x column sums of C'C <= 8), like the bench line's time-varying workload."""
-    (N, nx, nu, nc), kern = _MPC_SHAPES[idx]
+    (N, nx, nu, nc), kern = MPC_SHAPES[idx]
     rng = np.random.default_rng(7700 + idx)
     B = int(rng.integers(2, 10))
     o = default_options()
@@ -255,7 +220,7 @@ def test_random_shapes_with_sparse_constraint_rows_on_every_mpc_instance(hip, or
         assert (np.abs(z - c[0])[good] <= 10 * o.abs_tol * scale[good]).all()
 
 
-@pytest.mark.parametrize("idx", range(0, len(_MPC_SHAPES), 2))
+@pytest.mark.parametrize("idx", range(0, len(MPC_SHAPES), 2))
 def test_warm_started_second_solve_on_every_mpc_instance(hip, oracle, oracle_fma, idx):
     """tools/fuzz_shapes.py ... warm, a fixed subset (the tool's twelve seeds:
     profiles/r06_*_fuzz_warm_start_family_12_seeds.txt): every shape is solved, then solved AGAIN with x0 moved
@@ -272,7 +237,7 @@ def test_warm_started_second_solve_on_every_mpc_instance(hip, oracle, oracle_fma
     Newton system behind (the oracle's substitution: 2e-8) and took a second proximal iteration.  That form
     substitutes since (fb_mpc_r16.h: newton_core; LABNOTES R6.5) and the shape passes as it is, with
     no step refined."""
-    (N, nx, nu, nc), kern = _MPC_SHAPES[idx]
+    (N, nx, nu, nc), kern = MPC_SHAPES[idx]
     rng = np.random.default_rng(9000 + idx)
     B = int(rng.integers(3, 12))
     o = default_options()
@@ -381,7 +346,7 @@ def test_pattern_initialised_build_agrees_bitwise_on_every_record_instance(hip, 
     cases = []
     for j in range(4):
         idx = 4 * inst + j
-        shape, kern = _MPC_SHAPES[idx]
+        shape, kern = MPC_SHAPES[idx]
         rng = np.random.default_rng(7000 + idx)
         B = int(rng.integers(2, 12))
         o = default_options()
@@ -390,7 +355,7 @@ def test_pattern_initialised_build_agrees_bitwise_on_every_record_instance(hip, 
                                 nonmonotone_linesearch=int(rng.random() < 0.5))
         cases.append((shape, kern, fx.random_ltv_mpc(rng, B, *shape), o, None))
     for j in (0, 1):  # exact and padded shape of the instance, tiny batches, spread and on one workgroup
-        shape, kern = _MPC_SHAPES[4 * inst + j]
+        shape, kern = MPC_SHAPES[4 * inst + j]
         for B in (1, 2, 3, 5, 7):
             rng = np.random.default_rng(9000 + 100 * inst + 10 * j + B)
             p = fx.random_ltv_mpc(rng, B, *shape)
@@ -746,43 +711,15 @@ def test_overflowed_and_nan_guesses_end_where_the_reference_ends(hip, oracle, mo
         assert np.abs(z[q] - r[0][0]).max() <= 1e-5 * (1 + np.abs(r[0][0]).max())
 
 
-# ---- the degenerate dense family --------------------------------------
-# tools/fuzz_dense.py 200 <seed> 64: random shapes with up to 239 inequality rows over at
-# most 64 variables.  The shapes below are the ones on which the NATURAL elimination order
-# of the one-wavefront kernel took a different number of proximal or Newton iterations than
-# the oracle (seed 11: the seven shapes of profiles/r03_af_dense_factorisation_orders.txt;
-# seeds 12 and 13: profiles/r04_a_dense_order_choice.txt); the instances are regenerated from
-# the tool's own random stream.
-_DEGENERATE_SHAPES = {11: [(38, 20, 172), (46, 16, 205), (52, 11, 226), (36, 6, 196), (41, 22, 200), (31, 15, 106),
-                           (25, 5, 170)],
-                      12: [(30, 2, 130), (35, 17, 144), (31, 12, 170), (41, 19, 179), (40, 20, 152), (34, 3, 205),
-                           (42, 17, 137)],
-                      13: [(38, 20, 109), (41, 22, 87), (45, 19, 167), (51, 12, 234), (43, 6, 231), (35, 17, 168),
-                           (33, 14, 232), (34, 15, 171)]}
-
-
-def _fuzz_dense_instances(seed, wanted, n=200, kmax=64):
-    rng = np.random.default_rng(seed)
-    out = []
-    for _ in range(n):
-        nz = int(rng.integers(1, 160)); nl = int(rng.integers(0, min(nz, 24) + 1)); nv = int(rng.integers(1, 240))
-        nz = int(rng.integers(1, kmax + 1)); nl = int(rng.integers(0, min(nz, 24, kmax - nz) + 1))
-        B = int(rng.integers(1, 10))
-        first_id = int(rng.integers(0, 1 << 20))
-        if (nz, nl, nv) in wanted:
-            out.append((nz, nl, nv, B, first_id))
-    return out
-
-
-@pytest.mark.parametrize("seed", sorted(_DEGENERATE_SHAPES))
+@pytest.mark.parametrize("seed", sorted(DEGENERATE_SHAPES))
 def test_degenerate_dense_shapes_in_the_default_order(hip, oracle, seed):
     """The default (Eigen's) elimination order on the shapes where the natural order parts
     from the oracle: exit flags, proximal AND Newton counts equal on every QP, solutions
     and multipliers' image G'l + A'v within the parity tolerance.  The opt-in orders on the
     same QPs: same exit flags (all converge) and the same z to the tolerance - their
     iteration counts are allowed to differ, that is what the option's documentation says."""
-    inst = _fuzz_dense_instances(seed, set(_DEGENERATE_SHAPES[seed]))
-    assert len(inst) == len(_DEGENERATE_SHAPES[seed]), inst
+    inst = fuzz_dense_instances(seed, set(DEGENERATE_SHAPES[seed]))
+    assert len(inst) == len(DEGENERATE_SHAPES[seed]), inst
     o = default_options()
     handed_over = 0
     for nz, nl, nv, B, first_id in inst:

@@ -6,41 +6,28 @@ through `status`, torch autograd, and host against device pointers."""
 import numpy as np
 import pytest
 
+from fbstab_amd.hip_api import DENSE_ARR
 from tools import fixtures as fx
 from oracle.oracle_py import default_options
 from tests import helpers as H
-from tests import dense_adjoint_helpers as DH
+from tests import linear_reference as LR
+from tests.hostsim import HostAdjoint
+from tests.shapes import DENSE_KERNEL_SHAPES, RELAX_FROM, RELAX
 
 pytestmark = pytest.mark.gpu
 
 CAP = "FBSTAB_HIP_MAX_WORKGROUPS"
 THREADS = "FBSTAB_HIP_DENSE_THREADS"
-KEYS = DH.DENSE_ARR + ("dz", "dl", "dv")
+KEYS = DENSE_ARR + ("dz", "dl", "dv")
 
 # Forward error of the step against the oracle's: |step - oracle's step|_inf / max(|step|_inf, 1).  Two roundings
-# of the reference's own solver - Oracle() and Oracle(fma=True) - differ by `spread` (last column below) on the
-# three QPs of each shape at their solutions with this file's seeds (measured on the CPU at the oracle's
-# solutions; the test prints the same figure at the device's).  The bar is FWD_FACTOR x that: the factor covers
-# the device's different elimination arithmetic (right-looking updates, MFMA sums).  cond(V) differs by shape, so
-# each shape carries its own figure.  The residual rule is the binding check; this one catches a step that solves
-# a neighbouring system.
+# of the reference's own solver - Oracle() and Oracle(fma=True) - differ by `spread` (last column of
+# shapes.DENSE_KERNEL_SHAPES) on the three QPs of each shape at their solutions with this file's seeds (measured on
+# the CPU at the oracle's solutions; the test prints the same figure at the device's).  The bar is FWD_FACTOR x
+# that: the factor covers the device's different elimination arithmetic (right-looking updates, MFMA sums).
+# cond(V) differs by shape, so each shape carries its own figure.  The residual rule is the binding check; this one
+# catches a step that solves a neighbouring system.
 FWD_FACTOR = 10
-
-# (nz, nl, nv), threads per QP, what DenseLayout::init must say (k_global, v_global), spread: one shape per dense
-# kernel - the one-wavefront kernel (twice, and once without equalities), four wavefronts with K in LDS, K in
-# global scratch, and the smallest nv at (20, 5) that moves the iterate vectors to global scratch too
-_KERNEL_SHAPES = [
-    ((50, 10, 100), 64, (0, 0), 1.09e-6), ((60, 4, 131), 64, (0, 0), 1.15e-6), ((30, 0, 40), 64, (0, 0), 6.06e-7),
-    ((90, 12, 77), 256, (0, 0), 1.62e-6), ((159, 24, 239), 256, (1, 0), 4.44e-6),
-    ((20, 5, 2534), 256, (1, 1), 2.59e-7),
-]
-# The generator makes a quarter of the rows active: at (20, 5, 2534) that is 630 active rows on 20 variables, a
-# degenerate vertex at which the multipliers are not unique and V is singular but for sigma.  There the
-# reference's own two roundings part by more than the residual rule allows (Oracle(fma=True) leaves 4.5 x the
-# residual of Oracle() on QP 2 of these three, and their steps differ by 1.6e-3), so the rule has nothing to
-# compare against.  The v_global shape therefore relaxes every row from RELAX_FROM on by RELAX (they become
-# inactive; 15 rows stay active): same kernel, same vector lengths, a QP with a unique answer.
-RELAX_FROM, RELAX = 40, 10.0
 
 
 @pytest.fixture(scope="module")
@@ -54,15 +41,6 @@ def _arrays(p):
     return {k: np.ascontiguousarray(a) for k, a in p.arrays.items()}
 
 
-def _solve(hip, p, o=None):
-    s = hip.FBstabDenseBatch(p.nz, p.nl, p.nv, max_batch=p.batch)
-    if o is not None:
-        s.UpdateOptions(H._opts(hip, o))
-    z, l, v, y = (np.zeros((p.batch, n)) for n in (p.nz, p.nl, p.nv, p.nv))
-    out = s.Solve(_arrays(p), z, l, v, y)
-    return s, (z, l, v), out
-
-
 def _check(oracle, oracle_fma, p, x, seeds, res, fwd_bar):
     """Per QP: status 0, the residual within 3 x the oracle's, the gradient table, and the forward error of the
     step.  Returns the largest relative difference between the two roundings of the oracle's step."""
@@ -72,9 +50,9 @@ def _check(oracle, oracle_fma, p, x, seeds, res, fwd_bar):
         xq = tuple(t[q] for t in x)
         sq = tuple(t[q] for t in seeds)
         step = tuple(res[k][q] for k in ("dz", "dl", "dv"))
-        ref = DH.oracle_adjoint(oracle, p, q, xq, sq)
-        ref_fma = DH.oracle_adjoint(oracle_fma, p, q, xq, sq)
-        DH.check_step_and_table(p, q, xq, sq, step, {k: res[k][q] for k in DH.DENSE_ARR}, ref)
+        ref = LR.oracle_adjoint(oracle, p, q, xq, sq)
+        ref_fma = LR.oracle_adjoint(oracle_fma, p, q, xq, sq)
+        LR.check_step_and_table(p, q, xq, sq, step, {k: res[k][q] for k in DENSE_ARR}, ref)
         smax = max(np.abs(np.concatenate(step)).max(), 1.0)
         spread = max(spread, np.abs(np.concatenate(ref) - np.concatenate(ref_fma)).max() / smax)
         err = np.abs(np.concatenate(step) - np.concatenate(ref)).max() / smax
@@ -83,26 +61,26 @@ def _check(oracle, oracle_fma, p, x, seeds, res, fwd_bar):
     return spread
 
 
-@pytest.mark.parametrize("idx", range(len(_KERNEL_SHAPES)), ids=["x".join(map(str, s[0])) for s in _KERNEL_SHAPES])
+@pytest.mark.parametrize("idx", range(len(DENSE_KERNEL_SHAPES)), ids=["x".join(map(str, s[0])) for s in DENSE_KERNEL_SHAPES])
 def test_adjoint_residual_table_and_forward_error_on_every_dense_kernel(hip, oracle, oracle_fma, monkeypatch, idx):
     """At the device's solutions with random seeds, on one shape per dense kernel: status 0, V (dz, dl, dv) =
     (gz, -gl, -C.gv) within 3 x the oracle's residual (longdouble), the gradients the table applied to the returned
     adjoint (rtol 1e-13), and the step within FWD_FACTOR x the shape's spread of the oracle's.  The one-wavefront
     shapes are also put through the four-wavefront kernel (FBSTAB_HIP_DENSE_THREADS=256): the same rule, and not
     the same bits - they are two kernels."""
-    (nz, nl, nv), threads, (kg, vg), spread0 = _KERNEL_SHAPES[idx]
-    lay = DH.HostDenseAdjoint().layout(nz, nl, nv)
+    (nz, nl, nv), threads, (kg, vg), spread0 = DENSE_KERNEL_SHAPES[idx]
+    lay = HostAdjoint("dense").layout(nz, nl, nv)
     assert (lay["k_global"], lay["v_global"]) == (kg, vg)
     if vg:
-        assert not DH.HostDenseAdjoint().layout(nz, nl, nv - 1)["v_global"]  # (the smallest such nv)
+        assert not HostAdjoint("dense").layout(nz, nl, nv - 1)["v_global"]  # (the smallest such nv)
     p = fx.synthetic_dense_batch(3, nz, nl, nv, first_id=500 + 10 * idx)
     if vg:
         p.arrays["b"] = p.arrays["b"].copy()
         p.arrays["b"][:, RELAX_FROM:] += RELAX
-    s, x, out = _solve(hip, p)
+    s, x, out = H.cold_solve(hip, p)
     assert s.query()["threads"] == threads
     assert (out["eflag"] == 0).all()
-    seeds = DH.random_seeds(np.random.default_rng(idx), p)
+    seeds = LR.random_seeds(np.random.default_rng(idx), p)
     res = s.Adjoint(_arrays(p), *x, *seeds, adj=True)
     spread = _check(oracle, oracle_fma, p, x, seeds, res, FWD_FACTOR * spread0)
     print("oracle / oracle_fma step spread on", (nz, nl, nv), "%.3e" % spread)
@@ -117,7 +95,7 @@ def test_adjoint_residual_table_and_forward_error_on_every_dense_kernel(hip, ora
         monkeypatch.setenv(THREADS, "64")
         s1 = hip.FBstabDenseBatch(nz, nl, nv, max_batch=p.batch)
         # (where A does not fit the LDS beside K that instance is not offered: four wavefronts again)
-        a_lds = DH.HostDenseAdjoint().layout(nz, nl, nv, nthreads=64)["a_lds"]
+        a_lds = HostAdjoint("dense").layout(nz, nl, nv, nthreads=64)["a_lds"]
         assert s1.query()["threads"] == (64 if a_lds else 256) and s1.query()["lds_bytes"] > s.query()["lds_bytes"]
         res1 = s1.Adjoint(_arrays(p), *x, *seeds, adj=True)
         _check(oracle, oracle_fma, p, x, seeds, res1, FWD_FACTOR * spread0)
@@ -132,21 +110,21 @@ def test_central_differences_through_the_device_solver(hip):
     nz, nl, nv = 20, 5, 40
     base = fx.synthetic_dense_batch(16, nz, nl, nv)
     o = default_options(abs_tol=1e-11)
-    s, x, out = _solve(hip, base, o)
+    s, x, out = H.cold_solve(hip, base, o)
     assert (out["eflag"] == 0).all()
-    strict = [q for q, _ in DH.strict_qps(base, x[0], x[2])]
+    strict = [q for q, _ in LR.strict_qps(base, x[0], x[2])]
     assert len(strict) >= 8, strict
     rng = np.random.default_rng(8802)
-    seeds = DH.random_seeds(rng, base)
+    seeds = LR.random_seeds(rng, base)
     grad = s.Adjoint(_arrays(base), *x, *seeds)
     assert (grad["status"] == 0).all()
     h = 1e-5
-    dirs = DH.directions(rng, nz, nl, nv)
-    cases = [(q, k, sg) for q in strict for k in DH.DENSE_ARR for sg in (1.0, -1.0)]
+    dirs = LR.directions(rng, nz, nl, nv)
+    cases = [(q, k, sg) for q in strict for k in DENSE_ARR for sg in (1.0, -1.0)]
     pert = fx.DenseProblem(nz, nl, nv)
     pert.arrays = {k: np.ascontiguousarray(np.stack([base.arrays[k][q] + (sg * h * dirs[k] if kk == k else 0.0)
-                                                     for q, kk, sg in cases])) for k in DH.DENSE_ARR}
-    _, xp, outp = _solve(hip, pert, o)
+                                                     for q, kk, sg in cases])) for k in DENSE_ARR}
+    _, xp, outp = H.cold_solve(hip, pert, o)
     assert (outp["eflag"] == 0).all()
     loss = lambda j: sum(float(seeds[t][cases[j][0]] @ xp[t][j]) for t in range(3))
     for j in range(0, len(cases), 2):
@@ -167,7 +145,7 @@ def _rows(hip, Hm, f, A, b, gz):
     p = fx.DenseProblem(nz, 0, nv)
     rep = lambda a: np.ascontiguousarray(np.tile(np.asarray(a, dtype=np.float64).reshape(1, -1), (B, 1)))
     p.arrays = dict(H=rep(Hm.T), f=rep(f), G=np.zeros((B, 0)), h=np.zeros((B, 0)), A=rep(A.T), b=rep(b))
-    s, x, out = _solve(hip, p, default_options(abs_tol=1e-11))
+    s, x, out = H.cold_solve(hip, p, default_options(abs_tol=1e-11))
     assert (out["eflag"] == 0).all()
     g = s.Adjoint(_arrays(p), *x, gz, want=("f", "b"))
     assert (g["status"] == 0).all()
@@ -206,7 +184,7 @@ def test_gradients_do_not_depend_on_the_factorisation_option(hip):
     """The one-wavefront adjoint always pivots: NATURAL and AUTO handles give the bits of a PIVOTED one, and the
     adjoint leaves pivoted_steps describing the last solve."""
     p = fx.synthetic_dense_batch(8, 50, 10, 100, first_id=40)
-    seeds = DH.random_seeds(np.random.default_rng(5), p)
+    seeds = LR.random_seeds(np.random.default_rng(5), p)
     res = {}
     for order in ("ORDER_PIVOTED", "ORDER_NATURAL", "ORDER_AUTO"):
         s = hip.FBstabDenseBatch(p.nz, p.nl, p.nv, max_batch=p.batch)
@@ -233,9 +211,9 @@ def test_gradients_are_bitwise_the_same_alone_packed_and_queued(hip, monkeypatch
     """QP gradients do not depend on where the queue puts them: alone, in a batch on two workgroups (every
     workgroup re-fetching), and in a batch on the whole grid - on the one-wavefront and the four-wavefront kernel."""
     p = fx.synthetic_dense_batch(24, *shape, first_id=900)
-    s, x, out = _solve(hip, p)
+    s, x, out = H.cold_solve(hip, p)
     assert s.query()["threads"] == threads
-    seeds = DH.random_seeds(np.random.default_rng(9), p)
+    seeds = LR.random_seeds(np.random.default_rng(9), p)
     full = s.Adjoint(_arrays(p), *x, *seeds, adj=True)
     assert (full["status"] == 0).all()
     monkeypatch.setenv(CAP, "2")
@@ -266,7 +244,7 @@ def test_failed_factorisation_is_reported_through_status(hip, monkeypatch, threa
     s = hip.FBstabDenseBatch(p.nz, p.nl, p.nv, max_batch=3)
     assert s.query()["threads"] == threads
     x = tuple(np.ascontiguousarray(ref.solution[k]) for k in ("z", "l", "v"))
-    seeds = DH.random_seeds(np.random.default_rng(1), p)
+    seeds = LR.random_seeds(np.random.default_rng(1), p)
     res = s.Adjoint(_arrays(p), *x, *seeds, adj=True)
     good = s.Adjoint(_arrays(ref), *x, *seeds, adj=True)
     assert res["status"].tolist() == [0, 1, 0] and good["status"].tolist() == [0, 0, 0]
@@ -299,12 +277,12 @@ def test_autograd_matches_the_c_abi_and_zeroes_unsolved_qps(hip, shape):
     assert l.shape == (4, nl) and not out.requires_grad
     eflag = hip.out_to_numpy(out)["eflag"]
     assert eflag[1] != 0 and (np.delete(eflag, 1) == 0).all(), eflag
-    a, b, c = (torch.from_numpy(t).to(dev) for t in DH.random_seeds(np.random.default_rng(12), p))
+    a, b, c = (torch.from_numpy(t).to(dev) for t in LR.random_seeds(np.random.default_rng(12), p))
     loss = (a * z).sum() + (b * l).sum() + (c * v).sum()
     loss.backward()
     ref = solver.Adjoint({k: t.detach() for k, t in data.items()}, z.detach(), l.detach(), v.detach(), a, b, c)
     torch.cuda.synchronize()
-    for k in DH.DENSE_ARR:
+    for k in DENSE_ARR:
         if k not in want:
             assert data[k].grad is None, k
             continue
@@ -322,8 +300,8 @@ def test_host_pointers_equal_device_pointers(hip):
     import torch
     dev = torch.device("cuda:0")
     p = fx.synthetic_dense_batch(5, 50, 10, 100, first_id=300)
-    s, x, out = _solve(hip, p)
-    seeds = DH.random_seeds(np.random.default_rng(4), p)
+    s, x, out = H.cold_solve(hip, p)
+    seeds = LR.random_seeds(np.random.default_rng(4), p)
     host = s.Adjoint(_arrays(p), *x, *seeds, adj=True)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     on_dev = s.Adjoint({k: t(a) for k, a in p.arrays.items()}, *(t(a) for a in x), *(t(a) for a in seeds), adj=True)

@@ -8,10 +8,9 @@ import numpy as np
 import pytest
 
 from oracle.oracle_py import default_options
-from tests import adjoint_helpers as AH
-from tests import dense_adjoint_helpers as DH
-from tests.test_display import _records_agree
-from tests.test_gpu_adjoint import _check_residual_and_table
+from tests import helpers as H
+from tests import linear_reference as LR
+from tests.hostsim import HostAdjoint
 from tools import fixtures as fx
 
 pytestmark = pytest.mark.gpu
@@ -81,7 +80,7 @@ def _assert_traces(oracle, s, p, one_qp, x, qps=range(B)):
         out, rec = s.SolveTraced(_arrays(one), z, l, v, y)
         assert out["eflag"][0] == ref[4]["eflag"][0] == 0
         assert out["prox_iters"][0] == ref[4]["prox_iters"][0]
-        _records_agree(rec, ref[6], (p.nz, p.nl, p.nv, q))
+        H.records_agree(rec, ref[6], (p.nz, p.nl, p.nv, q))
         assert rec[-1, 0] == 5 and rec[-1, 1] == 0
         assert np.abs(z[0] - x[0][q]).max() <= 1e-5 * (1 + np.abs(x[0][q]).max())
 
@@ -102,10 +101,10 @@ def test_adjoint_and_traced_solve_of_a_stage_that_does_not_fit_the_lds(hip, orac
     assert s.query()["lds_bytes"] < 4096
     x, out = _solve_batch(s, p)
     assert (out["eflag"] == 0).all()
-    seeds = AH.random_seeds(np.random.default_rng(53), p)
+    seeds = LR.random_seeds(np.random.default_rng(53), p)
     res = s.Adjoint(p.arrays, *x[:3], *seeds, adj=True)
-    _check_residual_and_table(oracle, p, x[:3], seeds, res)
-    _assert_traces(oracle, s, p, AH.one_qp, x)
+    LR.check_mpc_batch(oracle, p, x[:3], seeds, res)
+    _assert_traces(oracle, s, p, LR.one_qp, x)
     s.close()
 
 
@@ -132,7 +131,7 @@ def test_traced_solve_with_k_and_the_vectors_in_global_scratch(hip, oracle, shap
     is refused (K must fit the LDS).  (v_global: the batch call solves the three QPs, the traced one QP 0 alone -
     one workgroup with everything in global memory: tracing all three made the case 6 s.)"""
     nz, nl, nv = shape
-    layout = DH.HostDenseAdjoint().layout
+    layout = HostAdjoint("dense").layout
     assert (layout(nz, nl, nv)["k_global"], layout(nz, nl, nv)["v_global"]) == flags
     smaller = layout(nz, nl, nv - 1) if flags[1] else layout(nz - 1, nl, nv)
     assert (smaller["k_global"], smaller["v_global"]) != flags

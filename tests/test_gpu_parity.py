@@ -12,6 +12,7 @@ import pytest
 
 from tools import fixtures as fx
 from oracle.oracle_py import default_options, reliable_options
+from tests import closed_loop as rh
 from tests import helpers as H
 from tests.helpers import _opts, _unique_duals, _assert_parity
 
@@ -39,21 +40,6 @@ def _solve_mpc_host(hip, p, opts, guess=None):
     return z, l, v, y, out
 
 
-def _solve_dense_host(hip, p, opts, guess=None, order=None):
-    s = hip.FBstabDenseBatch(p.nz, p.nl, p.nv, max_batch=p.batch)
-    if order is not None:  # fbstab_hip_dense_set_factorisation (default: the reference's order)
-        s.SetFactorisation({"pivoted": s.ORDER_PIVOTED, "auto": s.ORDER_AUTO, "natural": s.ORDER_NATURAL}[order])
-    s.UpdateOptions(_opts(hip, opts))
-    B = p.batch
-    z = np.zeros((B, p.nz)); l = np.zeros((B, p.nl)); v = np.zeros((B, p.nv)); y = np.full((B, p.nv), 7.0)
-    if guess is not None:
-        z[:], l[:], v[:] = guess
-    data = {k: np.ascontiguousarray(a) for k, a in p.arrays.items()}
-    out = s.Solve(data, z, l, v, y)
-    s.close()
-    return z, l, v, y, out
-
-
 # -- reference end-to-end tests through the C-ABI ------------------------------
 @pytest.mark.parametrize("idx", range(5))
 def test_dense_reference_tests(hip, oracle, kats, idx):
@@ -61,7 +47,7 @@ def test_dense_reference_tests(hip, oracle, kats, idx):
     k = kats["dense_end_to_end"][idx]
     p = H.dense_from_kat(k)
     o = default_options(abs_tol=k["abs_tol"])
-    z, l, v, y, out = _solve_dense_host(hip, p, o)
+    z, l, v, y, out = H.solve_dense_host(hip, p, o)
     assert out["eflag"][0] == k["eflag"]
     if "zopt" in k:
         np.testing.assert_allclose(z[0], k["zopt"], atol=k["tol"], rtol=0)
@@ -332,7 +318,7 @@ def test_dense_synthetic_batch_parity(hip, oracle):
     for (nz, nl, nv, B) in ((20, 5, 40, 64), (50, 10, 100, 256)):
         p = fx.synthetic_dense_batch(B, nz, nl, nv)
         o = default_options()
-        gpu = _solve_dense_host(hip, p, o)
+        gpu = H.solve_dense_host(hip, p, o)
         cpu = oracle.solve_dense(p, opts=o, nthreads=oracle.num_threads())
         _assert_parity(gpu, cpu, o.abs_tol, exact_frac=1.0, max_dn=0)
         assert np.abs(gpu[0] - p.solution["z"]).max() < 1e-5
@@ -352,7 +338,7 @@ def test_dense_odd_shapes(hip, oracle, monkeypatch, shape, order):
     nz, nl, nv = shape
     p = fx.synthetic_dense_batch(48, nz, nl, nv, first_id=7000 + nz)
     o = default_options()
-    gpu = _solve_dense_host(hip, p, o, order=None if order == "default" else order)
+    gpu = H.solve_dense_host(hip, p, o, order=None if order == "default" else order)
     cpu = oracle.solve_dense(p, opts=o, nthreads=oracle.num_threads())
     if order == "default":
         _assert_parity(gpu, cpu, o.abs_tol, exact_frac=1.0, max_dn=0)
@@ -377,12 +363,12 @@ def test_dense_one_wavefront_kernel_is_selected_and_agrees_with_the_four_wavefro
     q = s.query()
     s.close()
     assert q["threads"] == 64 and q["scratch_bytes"] > 0 and q["lds_bytes"] <= 40 * 1024, q
-    wave = _solve_dense_host(hip, p, o)
+    wave = H.solve_dense_host(hip, p, o)
     monkeypatch.setenv("FBSTAB_HIP_DENSE_THREADS", "256")
     s = hip.FBstabDenseBatch(nz, nl, nv, max_batch=40)
     assert s.query()["threads"] == 256
     s.close()
-    four = _solve_dense_host(hip, p, o)
+    four = H.solve_dense_host(hip, p, o)
     monkeypatch.delenv("FBSTAB_HIP_DENSE_THREADS")
     cpu = oracle.solve_dense(p, opts=o, nthreads=oracle.num_threads())
     # (both kernels pivot like Eigen by default: every multiplier entry by entry)
@@ -401,7 +387,7 @@ def test_dense_many_constraints_fall_back_to_the_four_wavefront_kernel(hip, orac
     assert q["threads"] == 256, q
     p = fx.synthetic_dense_batch(12, nz, nl, nv, first_id=4100)
     o = default_options()
-    gpu = _solve_dense_host(hip, p, o)
+    gpu = H.solve_dense_host(hip, p, o)
     cpu = oracle.solve_dense(p, opts=o, nthreads=oracle.num_threads())
     _assert_parity(gpu, cpu, o.abs_tol)
 
@@ -419,7 +405,7 @@ def test_dense_kkt_matrix_larger_than_lds(hip, oracle, shape):
     q = s.query()
     assert (q["scratch_bytes"] > 0) == ((nz + nl) > 140), q
     assert q["lds_bytes"] <= 160 * 1024
-    gpu = _solve_dense_host(hip, p, o)
+    gpu = H.solve_dense_host(hip, p, o)
     cpu = oracle.solve_dense(p, opts=o, nthreads=oracle.num_threads())
     _assert_parity(gpu, cpu, o.abs_tol)
     assert np.abs(gpu[0] - p.solution["z"]).max() < 1e-5
@@ -494,7 +480,6 @@ def test_keep_matrices_flag_changes_nothing_but_time(hip):
     also after an unflagged call in between and after a change of the matrices
     that is announced by dropping the flag once."""
     import torch
-    from tests import closed_loop as rh
     T, S = 96, 5
     p = fx.synthetic_mpc_batch(T, first_id=31000)
     N, nx, nu, nc = p.sizes()
@@ -581,7 +566,7 @@ def test_reliable_options_and_no_feasibility_check(hip, oracle):
     p = fx.synthetic_dense_batch(32, 20, 5, 40, first_id=9)
     for o in (reliable_options(), default_options(check_feasibility=0),
               default_options(nonmonotone_linesearch=0, abs_tol=1e-9)):
-        gpu = _solve_dense_host(hip, p, o)
+        gpu = H.solve_dense_host(hip, p, o)
         cpu = oracle.solve_dense(p, opts=o)
         _assert_parity(gpu, cpu, max(o.abs_tol, 1e-8))
 
@@ -595,7 +580,7 @@ def test_mixed_outcome_batch(hip, oracle, kats):
     p.arrays = {k: np.concatenate([deg.arrays[k], inf.arrays[k], deg.arrays[k], inf.arrays[k]])
                 for k in deg.arrays}
     o = default_options(abs_tol=1e-8)
-    gpu = _solve_dense_host(hip, p, o)
+    gpu = H.solve_dense_host(hip, p, o)
     cpu = oracle.solve_dense(p, opts=o)
     assert gpu[4]["eflag"].tolist() == [0, 3, 0, 3] == cpu[4]["eflag"].tolist()
     assert np.array_equal(gpu[4]["newton_iters"], cpu[4]["newton_iters"])
@@ -719,7 +704,6 @@ def test_closed_loop_with_the_generator_simulation_inputs(hip, oracle, problem, 
     loop x+ = A x + B u0* from its x0 and from seven perturbed copies, eight MPC
     steps, warm-started unshifted, device path against the oracle run in the same
     loop: equal exit flags, inputs applied equal to 1e-6 of the input scale."""
-    from tests import closed_loop as rh
     gen = fx.OcpGenerator()
     getattr(gen, problem)(N)
     one = gen.GetFBstabInput()
@@ -764,7 +748,6 @@ def test_receding_horizon_sweep_matches_oracle(hip, oracle):
     rounding of its tolerance: at most one proximal / two Newton iterations on
     at most 2% of the 240 solves."""
     import torch
-    from tests import closed_loop as rh
     T, S = 24, 10
     p = fx.synthetic_mpc_batch(T, first_id=4000)
     N, nx, nu, nc = p.sizes()
@@ -809,33 +792,6 @@ def test_receding_horizon_sweep_matches_oracle(hip, oracle):
     assert g[-1]["out"]["newton_iters"].mean() < g[0]["out"]["newton_iters"].mean()
 
 
-def _oracle_closed_loop(oracle, p, A, B, steps, retire=True):
-    """The sweep fbstab_hip_mpc_receding_sweep runs, restated with the oracle as the
-    solver: warm start unshifted, x0 <- A x0 + B u0, failed trajectories parked at
-    the origin.  Returns per-step dicts (u0, out, retired)."""
-    N, nx, nu, nc = p.sizes()
-    T = p.batch
-    x0 = p.arrays["x0"].copy()
-    z, l, v = np.zeros((T, p.nz)), np.zeros((T, p.nl)), np.zeros((T, p.nv))
-    gone = np.zeros(T, dtype=bool)
-    log = []
-    for _ in range(steps):
-        q = fx.MpcProblem(N, nx, nu, nc)
-        q.arrays = dict(p.arrays)
-        q.arrays["x0"] = np.ascontiguousarray(x0)
-        z, l, v, y, out = oracle.solve_mpc(q, (z, l, v), nthreads=oracle.num_threads())
-        if retire:
-            new = ~gone & (out["eflag"] != 0)
-            gone |= new
-            z[new] = 0.0
-            l[new] = 0.0
-            v[new] = 0.0
-        u0 = np.where(gone[:, None], 0.0, z[:, nx:nx + nu])
-        log.append(dict(u0=u0.copy(), out=out.copy(), retired=gone.copy()))
-        x0 = np.where(gone[:, None], 0.0, x0 @ A.T + u0 @ B.T)
-    return log, x0
-
-
 def test_receding_sweep_on_the_device_matches_the_oracle_loop(hip, oracle):
     """fbstab_hip_mpc_receding_sweep (plant step, warm start and retirement on the
     device, no host round trip between steps) against the same loop run with the
@@ -854,19 +810,20 @@ def test_receding_sweep_on_the_device_matches_the_oracle_loop(hip, oracle):
     mk = lambda n: torch.zeros((T, n), dtype=torch.float64, device=dev)
     z, l, v, y = mk(p.nz), mk(p.nl), mk(p.nv), mk(p.nv)
     r = s.RecedingSweep(data, z, l, v, y, A, B, S, retire=True, log_inputs=True)
-    ref, x_end = _oracle_closed_loop(oracle, p, A, B, S)
+    ref = rh.logged_closed_loop(rh.oracle_solve(oracle, p), p, A, B, S)
+    retired = ref["eflag"] == -1
     u = r["u"].cpu().numpy()
-    assert ref[-1]["retired"].sum() >= 1, "the test wants at least one retired trajectory"
+    assert retired[-1].sum() >= 1, "the test wants at least one retired trajectory"
     for k in range(S):
-        assert r["stats"]["retired_total"][k] == ref[k]["retired"].sum(), k
-        assert r["stats"]["success"][k] == (ref[k]["out"]["eflag"] == 0).sum(), k
+        assert r["stats"]["retired_total"][k] == retired[k].sum(), k
+        assert r["stats"]["success"][k] == (ref["raw_eflag"][k] == 0).sum(), k
         # (a QP on its way to an infeasibility verdict may take a few dozen iterations
         # more or less than the oracle's; the feasible ones agree to a handful)
-        good = ref[k]["out"]["eflag"] == 0
-        slack = max(4, T // 8) + int(ref[k]["out"]["newton_iters"][~good].sum())
-        assert abs(int(r["stats"]["newton_sum"][k]) - int(ref[k]["out"]["newton_iters"].sum())) <= slack, k
-        np.testing.assert_allclose(u[k], ref[k]["u0"], atol=2e-5)
-    np.testing.assert_allclose(data["x0"].cpu().numpy(), x_end, atol=2e-5)
+        good = ref["raw_eflag"][k] == 0
+        slack = max(4, T // 8) + int(ref["newton"][k][~good].sum())
+        assert abs(int(r["stats"]["newton_sum"][k]) - int(ref["newton"][k].sum())) <= slack, k
+        np.testing.assert_allclose(u[k], ref["u"][k], atol=2e-5)
+    np.testing.assert_allclose(data["x0"].cpu().numpy(), ref["x_end"], atol=2e-5)
     assert (r["kernel_ms"] > 0).all()
     s.close()
 
@@ -955,10 +912,11 @@ def test_receding_sweep_on_padded_and_two_row_instances(hip, oracle, monkeypatch
         assert np.array_equal(one_launch["stats"][k], per_step["stats"][k]), k
     for k in ("eflag", "newton_iters", "prox_iters", "residual"):
         assert np.array_equal(one_launch["out"][k], per_step["out"][k]), k
-    ref, x_end = _oracle_closed_loop(oracle, p, A, B, S, retire=False)
+    ref = rh.logged_closed_loop(rh.oracle_solve(oracle, p), p, A, B, S, retire=False)
+    x_end = ref["x_end"]
     for k in range(S):
-        us = 1.0 + np.abs(ref[k]["u0"]).max()
-        assert np.abs(one_launch["u"][k] - ref[k]["u0"]).max() <= 1e-6 * us, (problem, k)
+        us = 1.0 + np.abs(ref["u"][k]).max()
+        assert np.abs(one_launch["u"][k] - ref["u"][k]).max() <= 1e-6 * us, (problem, k)
     assert np.abs(one_launch["x0"] - x_end).max() <= 1e-6 * (1.0 + np.abs(x_end).max())
 
 
@@ -992,13 +950,14 @@ def test_config5_full_sweep_with_an_oracle_subset(hip, oracle):
     sub = np.arange(0, T, 64)
     q = fx.MpcProblem(N, nx, nu, nc)
     q.arrays = {k: np.ascontiguousarray(a[sub]) for k, a in p.arrays.items()}
-    ref, x_end = _oracle_closed_loop(oracle, q, A, B, S)
+    ref = rh.logged_closed_loop(rh.oracle_solve(oracle, q), q, A, B, S)
+    retired = ref["eflag"][-1] == -1
     u = r["u"][:, torch.from_numpy(sub).to(dev)].cpu().numpy()
     gone_gpu = np.abs(data["x0"].cpu().numpy()[sub]).max(axis=1) == 0.0
-    assert np.array_equal(gone_gpu, ref[-1]["retired"]) or ref[-1]["retired"].sum() == 0
+    assert np.array_equal(gone_gpu, retired) or retired.sum() == 0
     for k in range(S):
-        np.testing.assert_allclose(u[k], ref[k]["u0"], atol=2e-5, err_msg=f"step {k}")
-    np.testing.assert_allclose(data["x0"].cpu().numpy()[sub], x_end, atol=2e-5)
+        np.testing.assert_allclose(u[k], ref["u"][k], atol=2e-5, err_msg=f"step {k}")
+    np.testing.assert_allclose(data["x0"].cpu().numpy()[sub], ref["x_end"], atol=2e-5)
     s.close()
     # ---- warm-start COUNT parity at every one of the 200 steps --------------------
     # Two closed loops drift apart after the first flip (each applies its own input), so the counts are
@@ -1135,7 +1094,7 @@ def test_saturate_error_is_exit_flag_6(hip, oracle, monkeypatch):
     o = default_options(inner_tol_min=1e-2, inner_tol_max=1e-3)
     with pytest.raises(RuntimeError, match="saturate"):
         oracle.solve_dense(d, opts=o)
-    assert (_solve_dense_host(hip, d, o)[4]["eflag"] == 6).all()
+    assert (H.solve_dense_host(hip, d, o)[4]["eflag"] == 6).all()
 
 
 def test_config4_all_eight_shards(hip, oracle):

@@ -20,16 +20,17 @@ import functools
 import numpy as np
 import pytest
 
+from fbstab_amd.hip_api import MPC_SEQ, DENSE_ARR
 from tools import fixtures as fx
 from oracle.oracle_py import default_options
 from tests import helpers as H
 from tests import placement_helpers as P
-from tests import adjoint_helpers as AH
-from tests import dense_adjoint_helpers as DH
+from tests import linear_reference as LR
 from tests import tangent_helpers as TH
 from tests import reduced_helpers as R
 from tests import sweep_adjoint_helpers as SH
-from tests.test_gpu_queue import OUT_FIELDS
+from tests.helpers import OUT_FIELDS
+from tests.hostsim import HostAdjoint
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +38,6 @@ CAP, GENERIC, THREADS, FLAT = ("FBSTAB_HIP_MAX_WORKGROUPS", "FBSTAB_HIP_GENERIC"
                                "FBSTAB_HIP_FLAT_ADJOINT")
 SWEEP_STEP, SWEEP_ADJ_STEP = "FBSTAB_HIP_SWEEP_PER_STEP", "FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP"
 ERR_ARGUMENT = 1
-MPC_SEQ, DENSE_ARR = AH.MPC_SEQ, DH.DENSE_ARR
 STEP, RHS = ("dz", "dl", "dv"), ("gz", "gl", "gv")
 R16, R32, FLAT_KERNEL = "fbstab_mpc_r16_kernel", "fbstab_mpc_r32_kernel", "fbstab_mpc_kernel<64>"
 REC_ADJ, FLAT_ADJ = "fbstab_mpc_r16_adjoint_kernel", "fbstab_mpc_adjoint_kernel<64>"
@@ -148,7 +148,7 @@ def _setenv(monkeypatch, env, cap=None):
 
 @functools.lru_cache(maxsize=None)
 def _dense_layout(shape):
-    return DH.HostDenseAdjoint().layout(*shape)
+    return HostAdjoint("dense").layout(*shape)
 
 
 def _handle(hip, case, B, cap=None):
@@ -412,7 +412,7 @@ def test_placed_solves_with_kept_matrices(hip, monkeypatch, case, layout):
 
 # ---- b. shared data on the solve -------------------------------------------------------------------------------
 _SHARED = [(c, n) for c in ("r16-12-4-20-padded", "r32-18-5-10", "flat")
-           for n in (("Q", "R", "S", "A", "B", "E", "L"), MPC_SEQ[:-1])] + \
+           for n in (R.MPC_MATRICES, MPC_SEQ[:-1])] + \
           [(c, ("H", "G", "A")) for c in ("dense-wave", "dense-four")]
 
 
@@ -446,7 +446,7 @@ def _points(case, B):
     p = _problem(kind, shape, B)
     z, l, v = _oracle_solution(case, B)[:3]
     x = tuple(np.where(np.isfinite(t), t, 0.0) for t in (z, l, v))
-    seeds = (AH if kind == "mpc" else DH).random_seeds(np.random.default_rng(31 + B), p)
+    seeds = LR.random_seeds(np.random.default_rng(31 + B), p)
     return p, x, seeds
 
 
@@ -468,17 +468,16 @@ def _deriv_blocks(layout, kind, shape, p, x, seeds, B, dev, seed_names=RHS):
 
 def _anchor_adjoint(kind, p, x, seeds, res, oracle):
     """The bar of the adjoint tests for the QPs of status 0: residual within 3 x the oracle's, the gradient table."""
-    from tests.test_gpu_adjoint import _check_residual_and_table
     ok = [q for q in range(p.batch) if res["status"][q] == 0 and q != 1]
     if kind == "mpc":
         sub = fx.MpcProblem(p.N, p.nx, p.nu, p.nc, {k: np.ascontiguousarray(a[ok]) for k, a in p.arrays.items()})
-        _check_residual_and_table(oracle, sub, tuple(t[ok] for t in x), tuple(t[ok] for t in seeds),
-                                  {k: a[ok] for k, a in res.items()})
+        LR.check_mpc_batch(oracle, sub, tuple(t[ok] for t in x), tuple(t[ok] for t in seeds),
+                           {k: a[ok] for k, a in res.items()})
         return
     for q in ok:
         xq, sq = tuple(t[q] for t in x), tuple(t[q] for t in seeds)
-        DH.check_step_and_table(p, q, xq, sq, tuple(res[k][q] for k in STEP), {k: res[k][q] for k in DENSE_ARR},
-                                DH.oracle_adjoint(oracle, p, q, xq, sq))
+        LR.check_step_and_table(p, q, xq, sq, tuple(res[k][q] for k in STEP), {k: res[k][q] for k in DENSE_ARR},
+                                LR.oracle_adjoint(oracle, p, q, xq, sq))
 
 
 @pytest.mark.parametrize("where", WHERE)
@@ -753,11 +752,10 @@ def test_placed_sweeps_and_their_adjoints(hip, oracle, oracle_fma, monkeypatch, 
             got = res[-1][1]
             log = dict(z=got["z_log"].reshape(steps, B, -1), l=got["l_log"].reshape(steps, B, -1),
                        v=got["v_log"].reshape(steps, B, -1), eflag=got["eflag_log"])
-            from tests.test_gpu_sweep_adjoint import _spread_bars, _assert_within
-            bars, _ = _spread_bars(oracle, oracle_fma, p, A, Bm, log, gu, gx)
+            bars, _ = SH.spread_bars(oracle, oracle_fma, p, A, Bm, log, gu, gx)
             ref, rst, _ = SH.reference_sweep_adjoint(SH.device_step_adjoint(s, p), p, A, Bm, log, gu, gx)
             assert np.array_equal(got["status"], rst)
-            _assert_within({k: got["grad_" + k] for k in MPC_SEQ}, ref, bars, case)
+            SH.assert_within({k: got["grad_" + k] for k in MPC_SEQ}, ref, bars, case)
         s.close()
     assert res[0][0] == (0, 0) and res[1][0] == (0, 0), (res[0][0], res[1][0])
     _assert_same(res[1][1], res[0][1], case)

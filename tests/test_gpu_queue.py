@@ -15,13 +15,12 @@ import pytest
 
 from tools import fixtures as fx
 from oracle.oracle_py import default_options
-from tests.helpers import _opts, _assert_parity
-from tests.test_gpu_components import _MPC_SHAPES, _DEGENERATE_SHAPES, _fuzz_dense_instances
+from tests.helpers import _opts, _assert_parity, OUT_FIELDS
+from tests.shapes import MPC_SHAPES, DEGENERATE_SHAPES, fuzz_dense_instances
 
 pytestmark = pytest.mark.gpu
 
 CAP = "FBSTAB_HIP_MAX_WORKGROUPS"
-OUT_FIELDS = ("eflag", "residual", "initial_residual", "newton_iters", "prox_iters")
 HEADLINE = "fbstab_mpc_r16_kernel<12,4,20>"
 FLAT = "fbstab_mpc_kernel<64>"
 
@@ -122,7 +121,7 @@ def _mixed_mpc(shape, seed, per_family, dyn_noise=0.15):
 _PACKED_MPC = [(i, None) for i in (0, 1, 4, 5, 8, 9, 12, 13, 16, 17)] + [("flat", (3, 10, 9, 12)), ("flat", (10, 80, 10, 40))]
 
 
-@pytest.mark.parametrize("case", _PACKED_MPC, ids=lambda c: ("%s-%s" % (_MPC_SHAPES[c[0]][1], "exact" if c[0] % 4 == 0 else "padded")
+@pytest.mark.parametrize("case", _PACKED_MPC, ids=lambda c: ("%s-%s" % (MPC_SHAPES[c[0]][1], "exact" if c[0] % 4 == 0 else "padded")
                                                               if c[1] is None else "flat-%s" % "x".join(map(str, c[1]))))
 def test_packed_rows_match_the_spread_solve_and_the_oracle_on_every_mpc_kernel(hip, oracle, monkeypatch, case):
     """Two workgroups solve a batch of the three random families (dense, bound and sparse constraint rows): every
@@ -132,7 +131,7 @@ def test_packed_rows_match_the_spread_solve_and_the_oracle_on_every_mpc_kernel(h
     of test_mpc_stage_wider_than_the_lds (its matrices in the workgroup's global scratch)."""
     idx, shape = case
     if shape is None:
-        shape, kern = _MPC_SHAPES[idx]
+        shape, kern = MPC_SHAPES[idx]
         monkeypatch.setenv("FBSTAB_HIP_GENERIC", "0")
         seed = 12000 + idx
     else:
@@ -160,7 +159,7 @@ def test_packed_rows_match_the_spread_solve_and_the_oracle_on_every_mpc_kernel(h
 
 def _degenerate_mix():
     """The first instance of the degenerate dense family (seed 11) beside synthetic QPs of its shape."""
-    nz, nl, nv, B, first_id = _fuzz_dense_instances(11, {_DEGENERATE_SHAPES[11][0]})[0]
+    nz, nl, nv, B, first_id = fuzz_dense_instances(11, {DEGENERATE_SHAPES[11][0]})[0]
     deg = fx.synthetic_dense_batch(B, nz, nl, nv, first_id=first_id)
     syn = fx.synthetic_dense_batch(max(12 - B, 4), nz, nl, nv, first_id=41000)
     return _concat([syn, deg])
@@ -309,14 +308,14 @@ def test_poisoned_guesses_leave_their_wavefront_neighbours_alone(hip, oracle, mo
 _EXACT = [0, 4, 8, 12, 16]
 
 
-@pytest.mark.parametrize("idx", _EXACT, ids=[_MPC_SHAPES[i][1] for i in _EXACT])
+@pytest.mark.parametrize("idx", _EXACT, ids=[MPC_SHAPES[i][1] for i in _EXACT])
 def test_iteration_limits_and_warm_starts_on_packed_rows(hip, oracle, oracle_fma, monkeypatch, idx):
     """On the exact shape of each record instance, two workgroups: (1) max_newton_iters at the median count of
     the batch, so that half of each wavefront stops at the limit while its neighbours go on, (2) a second solve
     warm-started from the first one's solution with x0 moved (load_guess_coop for a packed owner).  The oracle
     rules of test_warm_start_and_iteration_limits and test_warm_started_second_solve_on_every_mpc_instance;
     every capped run bitwise equal to the uncapped one."""
-    shape, kern = _MPC_SHAPES[idx]
+    shape, kern = MPC_SHAPES[idx]
     monkeypatch.setenv("FBSTAB_HIP_GENERIC", "0")
     rng = np.random.default_rng(12500 + idx)
     cap = 2
@@ -371,7 +370,7 @@ def test_refinement_on_packed_rows(hip, oracle, monkeypatch, case):
         p, o = H.fuzz_stream_shape(42, 127)
         kern, cap = "fbstab_mpc_r32_kernel<24,8,16>", 1
     else:
-        shape, kern = _MPC_SHAPES[4]
+        shape, kern = MPC_SHAPES[4]
         cap = 2
         p, o = fx.random_ltv_mpc(np.random.default_rng(12600), 32, *shape), default_options()
     B = p.batch
@@ -393,7 +392,7 @@ def test_refinement_on_packed_rows(hip, oracle, monkeypatch, case):
 
 
 # ---- the real spread boundary, no knob ------------------------------------------------------------------------
-_BOUNDARY = [((2,) + _MPC_SHAPES[i][0][1:], _MPC_SHAPES[i][1]) for i in _EXACT] + [((30, 12, 4, 20), HEADLINE)]
+_BOUNDARY = [((2,) + MPC_SHAPES[i][0][1:], MPC_SHAPES[i][1]) for i in _EXACT] + [((30, 12, 4, 20), HEADLINE)]
 
 
 @pytest.mark.parametrize("shape,kern", _BOUNDARY, ids=["%s-N%d" % (k, s[0]) for s, k in _BOUNDARY])

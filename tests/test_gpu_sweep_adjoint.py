@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle.oracle_py import default_options
-from tests import adjoint_helpers as AH
+from fbstab_amd.hip_api import MPC_SEQ
 from tests import helpers as H
 from tests import sweep_adjoint_helpers as SH
 from tools import fixtures as fx
@@ -71,28 +71,6 @@ def _plant(rng, nx, nu):
     """A random plant near the identity with a small input gain: the states stay near the x0 the random QPs were
     made feasible for, so that most steps end in SUCCESS."""
     return np.eye(nx) + 0.03 * rng.standard_normal((nx, nx)), 0.1 * rng.standard_normal((nx, nu))
-
-
-def _spread_bars(oracle, oracle_fma, p, A, B, log, gu, gx):
-    """Per sequence: ten times the spread between the two roundings of the reference (the oracle and its
-    fused-multiply-add build as per-step adjoints of the same recursion at the same logged points), relative to
-    the gradient's largest entry, the largest over the trajectories.  Returns (bars, spreads)."""
-    a = SH.reference_sweep_adjoint(SH.oracle_step_adjoint(oracle, p), p, A, B, log, gu, gx)[0]
-    b = SH.reference_sweep_adjoint(SH.oracle_step_adjoint(oracle_fma, p), p, A, B, log, gu, gx)[0]
-    spread = {}
-    for k in AH.MPC_SEQ:
-        top = np.abs(a[k]).max(axis=1)
-        rel = np.abs(a[k] - b[k]).max(axis=1) / np.where(top > 0, top, 1.0)
-        spread[k] = float(rel.max())
-    return {k: 10.0 * s for k, s in spread.items()}, spread
-
-
-def _assert_within(got, ref, bars, what, rows=None):
-    for k in AH.MPC_SEQ:
-        for q in (range(ref[k].shape[0]) if rows is None else rows):
-            top = np.abs(ref[k][q]).max()
-            err = np.abs(got[k][q] - ref[k][q]).max() / (top if top > 0 else 1.0)
-            assert err <= bars[k], (what, k, q, err, bars[k])
 
 
 def test_logged_sweep_is_the_sweep_and_logs_what_it_returned(hip, monkeypatch):
@@ -172,7 +150,7 @@ def test_one_step_is_the_adjoint(hip, monkeypatch, idx):
     gz[:, nx:nx + nu] = gu[0]
     ref = s.Adjoint(p.arrays, r["z_log"][0], r["l_log"][0], r["v_log"][0], gz)
     assert np.array_equal(g["status"], ref["status"]) and (ref["status"] == 0).all()
-    for k in AH.MPC_SEQ:
+    for k in MPC_SEQ:
         assert np.abs(ref[k]).max() > 0, k
         assert np.array_equal(g[k], ref[k]), k
 
@@ -193,22 +171,22 @@ def test_several_steps_against_the_composed_reference(hip, oracle, oracle_fma, m
     assert (r["eflag_log"] == 0).sum() >= 3 * T
     gu, gx = rng.standard_normal((T, p.batch, nu)), rng.standard_normal((T, p.batch, nx))
     log = _np_log(r)
-    bars, spread = _spread_bars(oracle, oracle_fma, p, A, B, log, gu, gx)
+    bars, spread = SH.spread_bars(oracle, oracle_fma, p, A, B, log, gu, gx)
     print("spread", shape, {k: "%.1e" % v for k, v in spread.items()})
     ref, rst, rmu = SH.reference_sweep_adjoint(SH.device_step_adjoint(s, p), p, A, B, log, gu, gx)
     g = _adjoint(s, p, A, B, r, gu, gx, mu=True)
     again = _adjoint(s, p, A, B, r, gu, gx, mu=True)
-    for k in AH.MPC_SEQ + ("status", "mu"):
+    for k in MPC_SEQ + ("status", "mu"):
         assert np.array_equal(g[k], again[k]), k
     assert np.array_equal(g["status"], rst)
-    _assert_within(g, ref, bars, name)
+    SH.assert_within(g, ref, bars, name)
     np.testing.assert_allclose(g["mu"], rmu, rtol=0, atol=max(bars["x0"], 1e-12) * np.abs(rmu).max())
     if name != PER_STEP:
         monkeypatch.setenv("FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP", "1")
         assert s.sweep_adjoint_kernel_name() == PER_STEP
         per = _adjoint(s, p, A, B, r, gu, gx)
         assert np.array_equal(per["status"], rst)
-        _assert_within(per, ref, bars, PER_STEP)
+        SH.assert_within(per, ref, bars, PER_STEP)
 
 
 @pytest.mark.parametrize("retire", [True, False], ids=["retire", "keep"])
@@ -234,19 +212,19 @@ def test_retirement_and_failed_steps(hip, oracle, oracle_fma, retire):
     rng = np.random.default_rng(77)
     gu, gx = rng.standard_normal((S, T, nu)), rng.standard_normal((S, T, nx))
     log = _np_log(r)
-    bars, spread = _spread_bars(oracle, oracle_fma, p, A, B, log, gu, gx)
+    bars, spread = SH.spread_bars(oracle, oracle_fma, p, A, B, log, gu, gx)
     print("spread", p.sizes(), retire, {k: "%.1e" % v for k, v in spread.items()})
     ref, rst, _ = SH.reference_sweep_adjoint(SH.device_step_adjoint(s, p), p, A, B, log, gu, gx, retire)
     g = _adjoint(s, p, A, B, r, gu, gx, retire=retire)
     assert np.array_equal(g["status"], rst)
-    _assert_within(g, ref, bars, "retire" if retire else "keep")
+    SH.assert_within(g, ref, bars, "retire" if retire else "keep")
     if retire:
         for q in bad:
             k0 = int(np.flatnonzero(e[:, q] == -1)[0])   # retirement step
             gu0, gx0 = gu.copy(), gx.copy()
             gu0[:k0], gx0[:k0] = 0.0, 0.0
             late = _adjoint(s, p, A, B, r, gu0, gx0)
-            for k in AH.MPC_SEQ:
+            for k in MPC_SEQ:
                 assert not late[k][q].any(), (q, k)
 
 
@@ -254,7 +232,6 @@ def test_known_answer_without_active_constraints(hip):
     """All constraints inactive ((8, 4, 2, 1), the plant = the QP's stage-0 model, T = 5): the closed loop is
     x+ = (A + B K_0) x with K_0 of the Riccati recursion, so dL/dx_0 = lambda_0 of
     lambda_k = (A + B K_0)'(gx_k + lambda_(k+1)) + K_0'gu_k."""
-    from tests.test_gpu_adjoint import _lqr_gain
     N, nx, nu, nc = 8, 4, 2, 1
     T = 5
     p = fx.random_ltv_mpc(np.random.default_rng(4401), 1, N, nx, nu, nc)
@@ -263,7 +240,7 @@ def test_known_answer_without_active_constraints(hip):
     p.arrays["E"][:] = 0.0
     p.arrays["L"][:] = 0.0
     p.arrays["d"][:] = -1.0
-    K = _lqr_gain(p)
+    K = H.lqr_gain(p)
     A = p.arrays["A"][0][:nx * nx].reshape(nx, nx).T.copy()
     B = p.arrays["B"][0][:nx * nu].reshape(nu, nx).T.copy()
     s = hip.FBstabMpcBatch(N, nx, nu, nc, max_batch=1)
@@ -338,7 +315,7 @@ def test_closed_loop_autograd(hip, monkeypatch):
     gu, gx = wu.cpu().numpy() * r["u"], wx.cpu().numpy() * xs
     g = _adjoint(solver, p, An, Bm, r, gu, gx, want=want, mu=True)
     assert (g["status"] == 0).all()
-    for k in AH.MPC_SEQ:
+    for k in MPC_SEQ:
         if k not in want:
             assert data[k].grad is None, k
             continue

@@ -11,6 +11,7 @@ import pytest
 
 from oracle.oracle_py import default_options
 from tests import helpers as H
+from tests import closed_loop as CL
 from tests import scenario_helpers as SC
 from tests import sweep_adjoint_helpers as SH
 from tools import fixtures as fx
@@ -174,7 +175,7 @@ def _stepwise(pid, rows):
         r = s.RecedingSweep(data, *X, A, B, 1, retire=False, log_inputs=True, log=True, w=wd[k:k + 1], shift=False)
         parts.append(_numpy(hip, r, data, X))
         if k + 1 < S:
-            SC.shift_point(X[0], X[1], X[2], p.sizes())
+            CL.shift_point(X[0], X[1], X[2], p.sizes())
     s.close()
     per = {k: np.concatenate([q[k] for q in parts], 0) for k in ("u",) + LOGS}
     per.update({k: parts[-1][k] for k in ("x0", "z", "l", "v") + OUT_FIELDS})

@@ -5,14 +5,13 @@ statuses, and torch.autograd.forward_ad."""
 import numpy as np
 import pytest
 
+from fbstab_amd.hip_api import MPC_SEQ, DENSE_ARR
 from tools import fixtures as fx
 from oracle.oracle_py import default_options
 from tests import helpers as H
-from tests import adjoint_helpers as AH
-from tests import dense_adjoint_helpers as DH
+from tests import linear_reference as LR
 from tests import tangent_helpers as TH
-from tests.test_gpu_components import _MPC_SHAPES
-from tests.test_gpu_dense_adjoint import _KERNEL_SHAPES, RELAX_FROM, RELAX
+from tests.shapes import MPC_SHAPES, DENSE_KERNEL_SHAPES, RELAX_FROM, RELAX
 
 pytestmark = pytest.mark.gpu
 
@@ -34,16 +33,6 @@ def _arrays(p):
     return {k: np.ascontiguousarray(a) for k, a in p.arrays.items()}
 
 
-def _solve(hip, p, o=None):
-    mpc = TH.is_mpc(p)
-    s = hip.FBstabMpcBatch(*p.sizes(), max_batch=p.batch) if mpc else hip.FBstabDenseBatch(p.nz, p.nl, p.nv, max_batch=p.batch)
-    if o is not None:
-        s.UpdateOptions(H._opts(hip, o))
-    z, l, v, y = (np.zeros((p.batch, n)) for n in (p.nz, p.nl, p.nv, p.nv))
-    out = s.Solve(_arrays(p), z, l, v, y)
-    return s, (z, l, v), out
-
-
 def _check_rhs_and_step(s, p, x, d, res):
     """``res`` = Tangent(..., rhs=True): status 0, the seeds within the bound of tangent_helpers.tangent_rhs for every
     QP, and (dz, dl, dv) bitwise what Adjoint(adj=True) returns for those seeds.  Returns the worst error / bound."""
@@ -60,21 +49,21 @@ def _check_rhs_and_step(s, p, x, d, res):
     return worst
 
 
-_FIRST = [next(i for i, (_, n) in enumerate(_MPC_SHAPES) if n == name) for name in dict.fromkeys(n for _, n in _MPC_SHAPES)]
-_MPC_RUNS = [(i, f) for i in _FIRST for f in (("0", "1") if _MPC_SHAPES[i][1] != GENERIC else (None,))]
+_FIRST = [next(i for i, (_, n) in enumerate(MPC_SHAPES) if n == name) for name in dict.fromkeys(n for _, n in MPC_SHAPES)]
+_MPC_RUNS = [(i, f) for i in _FIRST for f in (("0", "1") if MPC_SHAPES[i][1] != GENERIC else (None,))]
 
 
-@pytest.mark.parametrize("idx,flat", _MPC_RUNS, ids=["%s-%s" % (_MPC_SHAPES[i][1], {"0": "record", "1": "flat", None: "flat"}[f])
+@pytest.mark.parametrize("idx,flat", _MPC_RUNS, ids=["%s-%s" % (MPC_SHAPES[i][1], {"0": "record", "1": "flat", None: "flat"}[f])
                                                       for i, f in _MPC_RUNS])
 def test_tangent_on_one_shape_per_mpc_solve_kernel(hip, monkeypatch, idx, flat):
     """Three random LTV QPs at the device's solutions, per-QP random directions on all twelve sequences; the record
     instances once on their record adjoint (FBSTAB_HIP_FLAT_ADJOINT=0) and once on the flat-vector one (=1)."""
-    shape, kern = _MPC_SHAPES[idx]
+    shape, kern = MPC_SHAPES[idx]
     monkeypatch.setenv("FBSTAB_HIP_GENERIC", "1" if kern == GENERIC else "0")
     if flat is not None:
         monkeypatch.setenv(FLAT, flat)
     p = fx.random_ltv_mpc(np.random.default_rng(7100 + idx), 3, *shape)
-    s, x, out = _solve(hip, p)
+    s, x, out = H.cold_solve(hip, p)
     assert s.kernel_name() == kern
     assert s.adjoint_kernel_name().startswith("fbstab_mpc_r16_adjoint_kernel" if flat == "0" else "fbstab_mpc_adjoint_kernel")
     d = TH.random_directions(np.random.default_rng(100 + idx), p, p.batch)
@@ -83,15 +72,15 @@ def test_tangent_on_one_shape_per_mpc_solve_kernel(hip, monkeypatch, idx, flat):
     assert s.last_kernel_ms() > 0
 
 
-@pytest.mark.parametrize("idx", range(len(_KERNEL_SHAPES)), ids=["x".join(map(str, s[0])) for s in _KERNEL_SHAPES])
+@pytest.mark.parametrize("idx", range(len(DENSE_KERNEL_SHAPES)), ids=["x".join(map(str, s[0])) for s in DENSE_KERNEL_SHAPES])
 def test_tangent_on_every_dense_kernel(hip, idx):
     """The same on one shape per dense kernel (the v_global shape with the relaxation of the adjoint's test)."""
-    (nz, nl, nv), threads, (kg, vg), _ = _KERNEL_SHAPES[idx]
+    (nz, nl, nv), threads, (kg, vg), _ = DENSE_KERNEL_SHAPES[idx]
     p = fx.synthetic_dense_batch(3, nz, nl, nv, first_id=500 + 10 * idx)
     if vg:
         p.arrays["b"] = p.arrays["b"].copy()
         p.arrays["b"][:, RELAX_FROM:] += RELAX
-    s, x, out = _solve(hip, p)
+    s, x, out = H.cold_solve(hip, p)
     assert s.query()["threads"] == threads and (out["eflag"] == 0).all()
     d = TH.random_directions(np.random.default_rng(200 + idx), p, p.batch)
     res = s.Tangent(_arrays(p), *x, d, rhs=True)
@@ -106,7 +95,7 @@ def test_bits_are_the_same_alone_packed_and_on_the_full_grid(hip, monkeypatch, s
     if flat is not None:
         monkeypatch.setenv(FLAT, flat)
     p = fx.random_ltv_mpc(np.random.default_rng(5150 + shape[1]), 24, *shape)
-    s, x, out = _solve(hip, p)
+    s, x, out = H.cold_solve(hip, p)
     if flat == "0":
         assert s.kernel_name().startswith("fbstab_mpc_r32_kernel") and s.adjoint_kernel_name().startswith("fbstab_mpc_r16_adjoint_kernel")
     d = TH.random_directions(np.random.default_rng(11), p, p.batch)
@@ -148,15 +137,15 @@ def test_duality_with_the_adjoint_on_the_device_mpc(hip):
     rng = np.random.default_rng(8801)
     p8 = fx.random_ltv_mpc(rng, 8, 6, 4, 2, 6)
     p = fx.MpcProblem(*p8.sizes(), {k: np.ascontiguousarray(a[:3]) for k, a in p8.arrays.items()})
-    s, x, out = _solve(hip, p, default_options(abs_tol=1e-11))
+    s, x, out = H.cold_solve(hip, p, default_options(abs_tol=1e-11))
     assert (out["eflag"] == 0).all()
     d = TH.random_directions(rng, p, p.batch)
-    g = AH.random_seeds(rng, p)
+    g = LR.random_seeds(rng, p)
     res = s.Tangent(_arrays(p), *x, d)
     grads = s.Adjoint(_arrays(p), *x, *g)
     assert (res["status"] == 0).all() and (grads["status"] == 0).all()
     for q in range(p.batch):
-        gap = _duality(TH.MPC_SEQ, g, res, grads, d, q)
+        gap = _duality(MPC_SEQ, g, res, grads, d, q)
         print("duality gap %.2e (bar %.1e)" % (gap, TH.DUALITY_BAR))
         assert gap <= TH.DUALITY_BAR, (q, gap)
 
@@ -164,35 +153,18 @@ def test_duality_with_the_adjoint_on_the_device_mpc(hip):
 def test_duality_with_the_adjoint_on_the_device_dense(hip):
     """The same for the dense QP, three (20, 5, 40) QPs."""
     p = fx.synthetic_dense_batch(3, 20, 5, 40, first_id=40)
-    s, x, out = _solve(hip, p)
+    s, x, out = H.cold_solve(hip, p)
     assert (out["eflag"] == 0).all()
     rng = np.random.default_rng(2054)
     d = TH.random_directions(rng, p, p.batch)
-    g = DH.random_seeds(rng, p)
+    g = LR.random_seeds(rng, p)
     res = s.Tangent(_arrays(p), *x, d)
     grads = s.Adjoint(_arrays(p), *x, *g)
     assert (res["status"] == 0).all() and (grads["status"] == 0).all()
     for q in range(p.batch):
-        gap = _duality(TH.DENSE_ARR, g, res, grads, d, q)
+        gap = _duality(DENSE_ARR, g, res, grads, d, q)
         print("duality gap %.2e (bar %.1e)" % (gap, TH.DUALITY_BAR))
         assert gap <= TH.DUALITY_BAR, (q, gap)
-
-
-def _lqr_gain(p):
-    """-K_0 of the finite-horizon Riccati recursion of QP 0 (stage cost 1/2 [x;u]'[Q S';S R][x;u], the
-    terminal stage's input eliminated)."""
-    N, nx, nu, nc = p.sizes()
-    a = {k: v[0] for k, v in p.arrays.items()}
-    mat = lambda key, i, r, c: a[key][i * r * c:(i + 1) * r * c].reshape(c, r).T
-    Q, R, S = (lambda i: mat("Q", i, nx, nx)), (lambda i: mat("R", i, nu, nu)), (lambda i: mat("S", i, nu, nx))
-    P = Q(N) - S(N).T @ np.linalg.solve(R(N), S(N))
-    K = None
-    for i in range(N - 1, -1, -1):
-        A, B = mat("A", i, nx, nx), mat("B", i, nx, nu)
-        Quu, Qux, Qxx = R(i) + B.T @ P @ B, S(i) + B.T @ P @ A, Q(i) + A.T @ P @ A
-        K = np.linalg.solve(Quu, Qux)
-        P = Qxx - Qux.T @ K
-    return -K
 
 
 def test_lqr_gain_from_unit_directions_of_the_initial_state(hip):
@@ -205,8 +177,8 @@ def test_lqr_gain_from_unit_directions_of_the_initial_state(hip):
     p.arrays["E"][:] = 0.0
     p.arrays["L"][:] = 0.0
     p.arrays["d"][:] = -1.0   # 0 <= 1 on every row: inactive, y = 1, v = 0
-    K = _lqr_gain(p)
-    s, x, out = _solve(hip, p, default_options(abs_tol=1e-11))
+    K = H.lqr_gain(p)
+    s, x, out = H.cold_solve(hip, p, default_options(abs_tol=1e-11))
     assert (out["eflag"] == 0).all()
     np.testing.assert_allclose(x[0][0][nx:nx + nu], K @ p.arrays["x0"][0], rtol=1e-6, atol=1e-9)
     wide = hip.FBstabMpcBatch(N, nx, nu, nc, max_batch=nx)
@@ -248,7 +220,7 @@ def test_failed_factorisation_host_and_device_pointers_and_an_empty_batch(hip):
         assert np.array_equal(good[k], no_rhs[k].cpu().numpy()), k
     # the same on an MPC handle, with half of the slots null
     m = fx.random_ltv_mpc(np.random.default_rng(31), 3, 4, 5, 2, 6)
-    ms, mx, _ = _solve(hip, m)
+    ms, mx, _ = H.cold_solve(hip, m)
     md = TH.random_directions(np.random.default_rng(2), m, m.batch, names=("Q", "S", "A", "c", "L", "x0"))
     host = ms.Tangent(_arrays(m), *mx, md, rhs=True)
     mdev = ms.Tangent({k: t(a) for k, a in m.arrays.items()}, *(t(a) for a in mx), {k: t(a) for k, a in md.items()}, rhs=True)

@@ -10,7 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import dense_adjoint_helpers as DA
+from fbstab_amd.hip_api import MPC_SEQ, DENSE_ARR
+from tests import linear_reference as LR
+from tests.hostsim import NO_CONTRACTION
 from tests import reduced_helpers as R
 
 DRIVER = r'''
@@ -82,7 +84,7 @@ def driver(tmp_path_factory):
     src = d / "walk.cc"
     src.write_text(DRIVER)
     exe = str(d / "walk")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-O1", "-ffp-contract=off",
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-O1", NO_CONTRACTION,
                            "-I" + R.CSRC, "-o", exe, str(src)])
     return exe, d
 
@@ -129,15 +131,15 @@ def _check_plan_line(plan, batch):
 def test_dense_table_walk_matches_the_numpy_table_and_covers_every_entry_once(driver, shape):
     nz, nl, nv = shape
     lens = R.dense_lens(*shape)
-    plan, got, count, x, step = _walk(driver, "dense", shape, lens, R.DENSE_ARR)
+    plan, got, count, x, step = _walk(driver, "dense", shape, lens, DENSE_ARR)
     tiles = _check_plan_line(plan, BATCH)
     assert tiles == -(-(nz + nl + nv) // 16) * -(-nz // 16)
-    ref = {k: np.zeros(lens[k]) for k in R.DENSE_ARR}
+    ref = {k: np.zeros(lens[k]) for k in DENSE_ARR}
     for b in range(BATCH):
-        tab = DA.gradient_table(nz, nl, nv, [t[b] for t in x], [t[b] for t in step])
-        for k in R.DENSE_ARR:
+        tab = LR.dense_gradient_table(nz, nl, nv, [t[b] for t in x], [t[b] for t in step])
+        for k in DENSE_ARR:
             ref[k] += tab[k]
-    for k in R.DENSE_ARR:
+    for k in DENSE_ARR:
         assert (count[k] == 1).all(), (k, count[k].min(), count[k].max())
         np.testing.assert_allclose(got[k], ref[k], rtol=1e-13, err_msg=k)
         # ... and the extended-precision table of the GPU tests says the same, within their bound
@@ -150,7 +152,7 @@ def _mpc_table_one_qp(N, nx, nu, nc, x, step):
     dz, dl, dv = step
     ns = nx + nu
     lens = R.mpc_lens(N, nx, nu, nc)
-    G = {k: np.zeros(lens[k]) for k in R.MPC_SEQ}
+    G = {k: np.zeros(lens[k]) for k in MPC_SEQ}
     for i in range(N + 1):
         xs, dxs, us, dus = z[i * ns:i * ns + nx], dz[i * ns:i * ns + nx], z[i * ns + nx:(i + 1) * ns], dz[i * ns + nx:(i + 1) * ns]
         vi, dvi = v[i * nc:(i + 1) * nc], dv[i * nc:(i + 1) * nc]
@@ -185,17 +187,17 @@ def _mpc_table_one_qp(N, nx, nu, nc, x, step):
 def test_mpc_table_walk_matches_the_numpy_table_and_covers_every_entry_once(driver, shape):
     N, nx, nu, nc = shape
     lens = R.mpc_lens(*shape)
-    plan, got, count, x, step = _walk(driver, "mpc", shape, lens, R.MPC_SEQ)
+    plan, got, count, x, step = _walk(driver, "mpc", shape, lens, MPC_SEQ)
     tiles = _check_plan_line(plan, BATCH)
     ns, up = nx + nu, lambda a: -(-a // 16)
     assert tiles == N * up(ns + nx + nc) * up(ns) + up(ns + nc) * up(ns) + up(nx)
-    ref = {k: np.zeros(lens[k]) for k in R.MPC_SEQ}
+    ref = {k: np.zeros(lens[k]) for k in MPC_SEQ}
     for b in range(BATCH):
         tab = _mpc_table_one_qp(N, nx, nu, nc, [t[b] for t in x], [t[b] for t in step])
-        for k in R.MPC_SEQ:
+        for k in MPC_SEQ:
             ref[k] += tab[k]
     summed = R.mpc_sum_table(N, nx, nu, nc, x, step)
-    for k in R.MPC_SEQ:
+    for k in MPC_SEQ:
         assert (count[k] == 1).all(), (k, count[k].min(), count[k].max())
         np.testing.assert_allclose(got[k], ref[k], rtol=1e-13, err_msg=k)
         R.check_sum(k, got[k], summed[k], BATCH)
@@ -204,13 +206,13 @@ def test_mpc_table_walk_matches_the_numpy_table_and_covers_every_entry_once(driv
 def test_scratch_sizes_are_the_documented_ones(driver):
     """include/fbstab_hip.h: 94 tiles and 13.1 MB of partial sums at the headline shape and max_batch 8192, 40
     tiles and 2.8 MB at (50, 10, 100) and 4096 (and 97.5 MB / 5.2 MB of adjoint steps, max_batch x (nz + nl + nv))."""
-    plan, *_ = _walk(driver, "mpc", (30, 12, 4, 20), R.mpc_lens(30, 12, 4, 20), R.MPC_SEQ, batch=1)
+    plan, *_ = _walk(driver, "mpc", (30, 12, 4, 20), R.mpc_lens(30, 12, 4, 20), MPC_SEQ, batch=1)
     assert plan[0] == 94 and round(94 * (8192 // 128) * 272 * 8 / 1e6, 1) == 13.1
     assert round(8192 * 31 * (16 + 12 + 20) * 8 / 1e6, 1) == 97.5
-    plan, *_ = _walk(driver, "dense", (50, 10, 100), R.dense_lens(50, 10, 100), R.DENSE_ARR, batch=1)
+    plan, *_ = _walk(driver, "dense", (50, 10, 100), R.dense_lens(50, 10, 100), DENSE_ARR, batch=1)
     assert plan[0] == 40 and round(40 * (4096 // 128) * 272 * 8 / 1e6, 1) == 2.8
     # a batch that is no multiple of the chunk: the last chunk is short, not dropped
-    plan, *_ = _walk(driver, "dense", (5, 2, 9), R.dense_lens(5, 2, 9), R.DENSE_ARR, batch=129)
+    plan, *_ = _walk(driver, "dense", (5, 2, 9), R.dense_lens(5, 2, 9), DENSE_ARR, batch=129)
     assert plan[3] == 2 and plan[4] == plan[0] * 2 * 272
 
 

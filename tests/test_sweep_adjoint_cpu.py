@@ -73,7 +73,7 @@ def test_reference_recursion_against_central_differences_of_the_oracles_closed_l
     p, A, B, cu, cx, dirs = SH.fd_problem()
     N, nx, nu, nc = p.sizes()
     o = default_options(abs_tol=1e-11)
-    log = SH.oracle_closed_loop(oracle, p, A, B, SH.FD_STEPS, opts=o)
+    log = CL.logged_closed_loop(CL.oracle_solve(oracle, p, o), p, A, B, SH.FD_STEPS)
     good = SH.strictly_complementary(p, log)
     assert len(good) >= 3, good
     grads, status, mu = SH.reference_sweep_adjoint(SH.oracle_step_adjoint(oracle, p), p, A, B, log, cu, cx)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from oracle.oracle_py import default_options
-from tests import scenario_helpers as SC
+from tests import closed_loop as CL
 from tests import sweep_adjoint_helpers as SH
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -67,8 +67,8 @@ def test_costate_is_the_disturbance_gradient_on_the_oracles_loop(oracle, shift):
     rng = np.random.default_rng(77)
     w = 1e-2 * rng.standard_normal((SH.FD_STEPS, SH.FD_TRAJ, nx))
     dw = rng.standard_normal(w.shape)
-    solve = SC.oracle_solve(oracle, p, o)
-    log = SC.closed_loop(solve, p, A, B, SH.FD_STEPS, w=w, shift=shift)
+    solve = CL.oracle_solve(oracle, p, o)
+    log = CL.logged_closed_loop(solve, p, A, B, SH.FD_STEPS, w=w, shift=shift)
     good = SH.strictly_complementary(p, log)
     assert len(good) == 7, good
     grads, status, mu = SH.reference_sweep_adjoint(SH.oracle_step_adjoint(oracle, p), p, A, B, log, cu, cx)
@@ -76,7 +76,7 @@ def test_costate_is_the_disturbance_gradient_on_the_oracles_loop(oracle, shift):
     gw = np.where((log["eflag"] == -1)[:, :, None], 0.0, mu)
 
     def loss(wk):
-        r = SC.closed_loop(solve, p, A, B, SH.FD_STEPS, w=wk, shift=shift)
+        r = CL.logged_closed_loop(solve, p, A, B, SH.FD_STEPS, w=wk, shift=shift)
         x = np.concatenate([r["x"][1:], r["x_end"][None]], 0)
         return (cu * r["u"]).sum(axis=(0, 2)) + (cx * x).sum(axis=(0, 2))
 

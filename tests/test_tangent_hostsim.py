@@ -8,13 +8,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from fbstab_amd.hip_api import MPC_SEQ, DENSE_ARR
 from oracle.oracle_py import default_options
 from tools import fixtures as fx
 from tests import helpers as H
-from tests import adjoint_helpers as AH
-from tests import dense_adjoint_helpers as DH
+from tests import linear_reference as LR
 from tests import tangent_helpers as TH
-import tests.test_adjoint_hostsim as TA   # (the host build of the MPC adjoint lives there)
+from tests.hostsim import HostAdjoint, HostTangent
 
 MPC_SHAPES = [(1, 2, 1, 1), (2, 3, 2, 4), (3, 12, 4, 20), (2, 34, 3, 5)]
 DENSE_SHAPES = [(5, 2, 9), (30, 0, 40)]
@@ -22,7 +22,7 @@ DENSE_SHAPES = [(5, 2, 9), (30, 0, 40)]
 
 @pytest.fixture(scope="module")
 def host():
-    return TH.HostTangent()
+    return HostTangent()
 
 
 # -- export and validation --------------------------------------------------------------------------------------
@@ -76,14 +76,14 @@ def _mpc_shape_problem(shape):
 
 def _dense_shape_problem(shape):
     p = fx.DenseProblem(*shape)
-    p.arrays = {k: np.zeros((1, n)) for k, n in TH.lengths_of(p).items()}
+    p.arrays = {k: np.zeros((1, n)) for k, n in LR.lengths_of(p).items()}
     return p
 
 
 def _cases(rng, p):
     """(label, perturbations): every array alone, all together (the matrices not symmetric), half of the slots
     null, and none."""
-    names = [k for k in TH.names_of(p) if TH.lengths_of(p)[k] > 0]
+    names = [k for k in LR.names_of(p) if LR.lengths_of(p)[k] > 0]
     every = {k: a[0] for k, a in TH.random_directions(rng, p, 1, names).items()}
     out = [("only " + k, {k: every[k]}) for k in names]
     out.append(("all", every))
@@ -158,8 +158,8 @@ def _duality_gap(p, q, x, gq, rhs, dq, adjoint):
     ``adjoint(seeds)``."""
     LD = np.longdouble
     gg, dx = np.concatenate(gq).astype(LD), np.concatenate(adjoint(rhs)).astype(LD)
-    tab = AH.gradient_table(AH.one_qp(p, q), x, adjoint(gq))
-    other = sum(np.asarray(tab[k]).astype(LD) @ dq[k].astype(LD) for k in TH.MPC_SEQ)
+    tab = LR.mpc_gradient_table(LR.one_qp(p, q), x, adjoint(gq))
+    other = sum(np.asarray(tab[k]).astype(LD) @ dq[k].astype(LD) for k in MPC_SEQ)
     return float(abs(gg @ dx - other) / np.abs(gg * dx).sum())
 
 
@@ -180,12 +180,12 @@ def test_tangent_end_to_end_on_the_host(host, oracle, oracle_fma):
     assert (out["eflag"] == 0).all()
     assert all(_strict(p, q, z, v) for q in range(p.batch))
     d = _symmetrised(p, TH.random_directions(rng, p, p.batch))
-    g = AH.random_seeds(rng, p)
-    hadj = TA.HostAdjoint()
+    g = LR.random_seeds(rng, p)
+    hadj = HostAdjoint()
     # central differences of the oracle's solves along d
     h = 1e-5
-    plus = fx.MpcProblem(*p.sizes(), {k: p.arrays[k] + h * d[k] for k in TH.MPC_SEQ})
-    minus = fx.MpcProblem(*p.sizes(), {k: p.arrays[k] - h * d[k] for k in TH.MPC_SEQ})
+    plus = fx.MpcProblem(*p.sizes(), {k: p.arrays[k] + h * d[k] for k in MPC_SEQ})
+    minus = fx.MpcProblem(*p.sizes(), {k: p.arrays[k] - h * d[k] for k in MPC_SEQ})
     sp, sm = oracle.solve_mpc(plus, opts=opts), oracle.solve_mpc(minus, opts=opts)
     assert (sp[4]["eflag"] == 0).all() and (sm[4]["eflag"] == 0).all()
     worst_fd = worst_dual = oracle_dual = 0.0
@@ -196,8 +196,8 @@ def test_tangent_end_to_end_on_the_host(host, oracle, oracle_fma):
         TH.assert_rhs(p, q, x, dq, rhs)
         st, step, _ = hadj.adjoint(p, q, x, rhs, want=())
         assert st == 0
-        ref = AH.oracle_adjoint(oracle, p, q, x, rhs)
-        r_dev, r_orc = AH.adjoint_residual(p, q, x, step, rhs), AH.adjoint_residual(p, q, x, ref, rhs)
+        ref = LR.oracle_adjoint(oracle, p, q, x, rhs)
+        r_dev, r_orc = LR.adjoint_residual(p, q, x, step, rhs), LR.adjoint_residual(p, q, x, ref, rhs)
         assert r_dev <= 3 * r_orc, (q, r_dev, r_orc)
         fd = np.concatenate([(sp[i][q] - sm[i][q]) / (2 * h) for i in range(3)])
         dx = np.concatenate(step)
@@ -208,7 +208,7 @@ def test_tangent_end_to_end_on_the_host(host, oracle, oracle_fma):
         gq = tuple(t[q] for t in g)
         for orc in (oracle, oracle_fma):
             oracle_dual = max(oracle_dual, _duality_gap(p, q, x, gq, rhs, dq,
-                                                        lambda s: AH.oracle_adjoint(orc, p, q, x, s)))
+                                                        lambda s: LR.oracle_adjoint(orc, p, q, x, s)))
         worst_dual = max(worst_dual, _duality_gap(p, q, x, gq, rhs, dq,
                                                   lambda s: hadj.adjoint(p, q, x, s, want=())[1]))
     print("tangent end to end: central differences %.2e, duality oracles %.2e host %.2e" % (worst_fd, oracle_dual,
@@ -224,12 +224,12 @@ def test_dense_tangent_step_meets_the_residual_rule_on_the_host(host, oracle):
     assert (sol[4]["eflag"] == 0).all()
     rng = np.random.default_rng(20540)
     d = TH.random_directions(rng, p, p.batch)
-    hadj = DH.HostDenseAdjoint()
+    hadj = HostAdjoint("dense")
     for q in range(p.batch):
         x = (sol[0][q], sol[1][q], sol[2][q])
         rhs = host.rhs(p, x, TH.one_direction(d, q))
         st, step, _ = hadj.adjoint(p, q, x, rhs, want=())
         assert st == 0
-        ref = DH.oracle_adjoint(oracle, p, q, x, rhs)
-        r_dev, r_orc = DH.adjoint_residual(p, q, x, step, rhs), DH.adjoint_residual(p, q, x, ref, rhs)
+        ref = LR.oracle_adjoint(oracle, p, q, x, rhs)
+        r_dev, r_orc = LR.adjoint_residual(p, q, x, step, rhs), LR.adjoint_residual(p, q, x, ref, rhs)
         assert r_dev <= 3 * r_orc, (q, r_dev, r_orc)

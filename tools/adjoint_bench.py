@@ -202,11 +202,12 @@ def reduced_child(name, way, reps):
     if name.startswith("dense"):
         p = fx.synthetic_dense_batch(B, 50, 10, 100)
         s = hip_api.FBstabDenseBatch(50, 10, 100, max_batch=B)
-        names, matrices = hip_api.DENSE_ARR, ("H", "G", "A")
+        names = hip_api.DENSE_ARR
     else:
         p = fx.synthetic_mpc_batch(B)
         s = hip_api.FBstabMpcBatch(*p.sizes(), max_batch=B)
-        names, matrices = hip_api.MPC_SEQ, ("Q", "R", "S", "A", "B", "E", "L")
+        names = hip_api.MPC_SEQ
+    matrices = tuple(k for k in names if k.isupper())   # (the matrices are the names in capitals)
     data = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in p.arrays.items()}
     zeros = lambda n: torch.zeros((B, n), dtype=torch.float64, device=dev)
     z, l, v, y = zeros(p.nz), zeros(p.nl), zeros(p.nv), zeros(p.nv)

@@ -6,14 +6,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from tools import fixtures as fx
 from fbstab_amd import hip_api
-from oracle.oracle_py import Oracle
-from tests.test_gpu_parity import _solve_dense_host, default_options
+from oracle.oracle_py import Oracle, default_options
+from tests.helpers import solve_dense_host
 nz, nl, nv, fid = (int(a) for a in sys.argv[1:5])
 B = int(sys.argv[5]) if len(sys.argv) > 5 else 48
 p = fx.synthetic_dense_batch(B, nz, nl, nv, first_id=fid)
 o = default_options()
 orc = Oracle()
-gpu = _solve_dense_host(hip_api, p, o)
+gpu = solve_dense_host(hip_api, p, o)
 cpu = orc.solve_dense(p, opts=o, nthreads=orc.num_threads())
 for name, g, c in zip("zlvy", gpu[:4], cpu[:4]):
     if c.size:

@@ -12,7 +12,6 @@ from tools import fixtures as fx
 from fbstab_amd import hip_api as hip
 from oracle.oracle_py import Oracle, default_options
 from tests import helpers as H
-from tests.test_gpu_components import _pfb_gradient, _pfb
 mp.mp.dps = 40
 nz, nl, nv, fid = (int(a) for a in sys.argv[1:5])
 B = int(sys.argv[5]) if len(sys.argv) > 5 else 4
@@ -35,10 +34,10 @@ for i in range(B):
     assert g["ok"]
     y = b - A @ z
     ysv = y + sigma * (v - vb)
-    gam, mus = _pfb_gradient(ysv, v, alpha, sigma)
+    gam, mus = H.pfb_gradient(ysv, v, alpha, sigma)
     r1 = -(Hm @ z + f + G.T @ l + A.T @ v + sigma * (z - zb))
     r2 = (h - G @ z) + sigma * (l - lb)
-    r3 = -_pfb(ysv, v, alpha)
+    r3 = -H.pfb(ysv, v, alpha)
     n = nz + nl + nv
     K = mp.zeros(n, n); rhs = mp.zeros(n, 1)
     for a_ in range(nz):

@@ -23,8 +23,7 @@ from typing import Dict, List
 
 import numpy as np
 
-_MPC_SEQ = ("Q", "R", "S", "q", "r", "A", "B", "c", "E", "L", "d", "x0")
-_DENSE_SEQ = ("H", "f", "G", "h", "A", "b")
+from fbstab_amd.hip_api import MPC_SEQ as _MPC_SEQ
 
 
 def _colmajor(mats: List[np.ndarray]) -> np.ndarray:
