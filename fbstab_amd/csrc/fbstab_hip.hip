@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -21,6 +22,7 @@
 #include "fb_final_norms.h"
 #include "fb_grad_reduce.h"
 #include "fb_in_flight.h"
+#include "fb_launch_plan.h"
 #include "fb_mpc.h"
 #include "fb_mpc_r16.h"
 #include "fb_record_kernel.h"
@@ -601,7 +603,12 @@ struct SolverBase {
     return FBSTAB_HIP_OK;
   }
 
-  int release() {
+  SolverBase() = default;
+  SolverBase(const SolverBase&) = delete;
+  SolverBase& operator=(const SolverBase&) = delete;
+  // Everything the handle holds on the device, whichever call allocated it (a handle whose creation failed half
+  // way included).
+  ~SolverBase() {
     (void)hipSetDevice(device);
     for (double* p : d_arr)
       if (p) (void)hipFree(p);
@@ -618,7 +625,6 @@ struct SolverBase {
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (stream) (void)hipStreamDestroy(stream);
-    return FBSTAB_HIP_OK;
   }
 
   int common_init(int dev, int maxb) {
@@ -640,8 +646,8 @@ struct SolverBase {
     return FBSTAB_HIP_OK;
   }
 
-  // Creation: the resident workgroups per CU (1..8) of the kernel batches are launched with - its LDS attribute
-  // set; the handle's other kernels get theirs with their first launch - and the device's CUs.
+  // Creation: the resident workgroups per CU of the kernel batches are launched with - its LDS attribute set; the
+  // handle's other kernels get theirs with their first launch - and the device's CUs.
   int occupancy(KernelEntry& e, int* per_cu, int* cus) {
     hipError_t err = set_lds_attribute(e);
     if (err == hipSuccess) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, e.kern, e.block, e.lds);
@@ -650,7 +656,6 @@ struct SolverBase {
     if (err != hipSuccess)
       return fail(FBSTAB_HIP_ERR_DEVICE, std::string("occupancy query: ") + hipGetErrorString(err));
     *cus = prop.multiProcessorCount;
-    *per_cu = *per_cu < 1 ? 1 : *per_cu > 8 ? 8 : *per_cu;
     return FBSTAB_HIP_OK;
   }
 
@@ -1311,6 +1316,17 @@ struct fbstab_mpc_solver : SolverBase {
   struct {
     MpcKernel solve, solve_keep, traced, probe, adjoint, sweep_adjoint;
   } kern;
+
+  ~fbstab_mpc_solver() {
+    (void)hipSetDevice(device);
+    if (adj_scratch) (void)hipFree(adj_scratch);
+    if (sweep_seed) (void)hipFree(sweep_seed);
+    if (sweep_tmp) (void)hipFree(sweep_tmp);
+  }
+  // Grid of a batch launch of entry `e` (fbk::batch_grid: a record kernel's small batches are spread)
+  int batch_grid(const MpcKernel& e, int batch) const {
+    return fbk::batch_grid(batch, workgroups, e.record ? qps_per_wg : 1);
+  }
 };
 
 // The record-kernel instances compiled into the library (one translation unit each),
@@ -1361,21 +1377,6 @@ const RecordInstance* record_instance_for(int nx, int nu, int nc) {
 MpcBatchPtrs record_data(const fbstab_mpc_solver* h, const fbstab_mpc_batch_t& a) {
   return MpcBatchPtrs{a, h->lay.nx, h->lay.nu, h->lay.nc};
 }
-
-// Grid of a batch launch of entry `e`.  Record kernels, a batch of no more QPs than the handle has workgroups: one QP
-// per WAVEFRONT (row 0 of each; fb_record_kernel.h, R16Queue::fetch) instead of four - the rows of a wavefront share
-// its program counter and its cooperative passes, so four QPs on one wavefront finish with the slowest of them and
-// queue for each other's passes, while the chip has SIMDs to spare (round 6: batch 16, 7.9 -> ms below).  (The
-// flat-vector kernels run one QP per workgroup, on record handles too: the same rule gives them
-// min(batch, workgroups).)
-int batch_grid(const fbstab_mpc_solver* h, const MpcKernel& e, int batch) {
-  const int per_wg = e.record ? h->qps_per_wg : 1;
-  int grid = (batch + per_wg - 1) / per_wg;
-  if (batch <= h->workgroups) grid = batch;
-  return grid > h->workgroups ? h->workgroups : grid;
-}
-// ... and of a FBSTAB_HIP_KEEP_MATRICES launch, the one-launch sweep included: QP q in slot q, every row taken.
-int keep_grid(const fbstab_mpc_solver* h, int batch) { return (batch + h->qps_per_wg - 1) / h->qps_per_wg; }
 
 // The workspace of a flat-vector kernel: the handle's own, the traced solve's (one QP's, kept from call to call), or
 // that of the flat-vector adjoint on a record handle (lay.ws_doubles x workgroups doubles; fbstab_hip_mpc_query does
@@ -1469,9 +1470,6 @@ struct fbstab_dense_solver : SolverBase {
 };
 
 namespace {
-// Grid of a batch launch: one QP per workgroup at a time.
-int dense_grid(const fbstab_dense_solver* h, int batch) { return h->workgroups < batch ? h->workgroups : batch; }
-
 // The one place that knows which compiled kernel serves which operation of a dense handle, with what block, LDS
 // size, layout and scratch: read once, when the handle is created, behind the layouts and FBSTAB_HIP_DENSE_THREADS.
 void dense_resolve_kernels(fbstab_dense_solver* h) {
@@ -1557,65 +1555,33 @@ int fbstab_hip_mpc_create_in_flight(int N, int nx, int nu, int nc, int max_batch
   if (N < 1 || nx < 1 || nu < 1 || nc < 1)
     return fail(FBSTAB_HIP_ERR_ARGUMENT, "In FBstabMpc::FBstabMpc: problem sizes must be positive.");
   if (max_batch < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "max_batch must be positive");
-  fbstab_mpc_solver* s = new (std::nothrow) fbstab_mpc_solver();
+  std::unique_ptr<fbstab_mpc_solver> s(new (std::nothrow) fbstab_mpc_solver());
   if (!s) return fail(FBSTAB_HIP_ERR_DEVICE, "out of host memory");
+  const fbk::CreateKnobs knobs = fbk::create_knobs();
   s->threads = kMpcThreads;
   s->lay.init(N, nx, nu, nc, s->threads);
   s->lds_bytes = s->lay.launch_lds_doubles * (int)sizeof(double);
-  // FBSTAB_HIP_GENERIC=1 forces the flat-vector kernel (comparisons, tests)
-  const char* force_generic = getenv("FBSTAB_HIP_GENERIC");
-  if (!(force_generic && atoi(force_generic) > 0)) s->rec = record_instance_for(nx, nu, nc);
-  s->flat_adjoint = false;
+  if (!knobs.generic) s->rec = record_instance_for(nx, nu, nc);
   if (s->rec) {
     s->exact = nx == s->rec->nx && nu == s->rec->nu && nc == s->rec->nc;
     s->qps_per_wg = s->rec->qps_per_wg;
-    // FBSTAB_HIP_FLAT_ADJOINT, read here: 1 - the flat-vector adjoint on this record handle; 0 - its record adjoint;
-    // unset - the record adjoint on the one-row instances and the flat-vector adjoint on the row-pair instances,
-    // whose record adjoint has not been timed against it on the wide workloads yet
-    const char* flat_adj = getenv("FBSTAB_HIP_FLAT_ADJOINT");
-    s->flat_adjoint = (flat_adj && *flat_adj) ? atoi(flat_adj) > 0 : s->rec->qps_per_wg != 4;
+    s->flat_adjoint = knobs.flat_adjoint >= 0 ? knobs.flat_adjoint > 0 : s->rec->qps_per_wg != 4;
     s->lds_bytes = s->rec->lds_bytes(N);
   }
-  {
-    // developer knob: extra (unused) LDS per workgroup, to lower the number of
-    // resident wavefronts in occupancy experiments
-    const char* pad = getenv("FBSTAB_HIP_LDS_PAD_BYTES");
-    if (pad && atoi(pad) > 0) s->lds_bytes += atoi(pad) & ~15;
-  }
-  if (s->lds_bytes > kLdsLimitBytes) {  // (not reached: the flat-vector layout moves to global scratch first)
-    delete s;
+  s->lds_bytes += knobs.lds_pad_bytes;
+  if (s->lds_bytes > kLdsLimitBytes)  // (not reached: the flat-vector layout moves to global scratch first)
     return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "stage vectors do not fit the 160 KiB LDS budget");
-  }
-  int rc = s->common_init(device, max_batch);
-  if (rc != FBSTAB_HIP_OK) { s->release(); delete s; return rc; }
-  mpc_resolve_kernels(s);
-  int per_cu = 0, cus = 0;
-  rc = s->occupancy(s->kern.solve, &per_cu, &cus);
-  if (rc != FBSTAB_HIP_OK) { s->release(); delete s; return rc; }
-  // a handle that shares the device with others takes its share of the resident workgroups (and of the
-  // scratch memory that goes with them), at least one per CU: the launches that can really run beside it - no
-  // more than the process has hardware queues - want twice the resident slots between them, so that waiting
-  // workgroups fill the SIMDs a launch frees in its tail (fb_in_flight.h)
-  per_cu = fbk::in_flight_wgs_per_cu(per_cu, handles_in_flight, fbk::hw_queues_hint());
-  const char* env = getenv("FBSTAB_HIP_WGS_PER_CU");
-  if (env && atoi(env) > 0) per_cu = atoi(env);
-  s->workgroups = cus * per_cu;
-  {
-    // (record kernels: a batch that does not outnumber the grid is SPREAD, one QP per wavefront - below -, so a
-    // handle for a small max_batch keeps one workgroup per QP rather than one per four)
-    const int need = s->rec ? max_batch : (max_batch + s->qps_per_wg - 1) / s->qps_per_wg;
-    if (s->workgroups > need) s->workgroups = need;
-  }
-  // test knob: FBSTAB_HIP_MAX_WORKGROUPS=n caps the grid, so that small batches pack every row and re-fetch
-  const char* cap = getenv("FBSTAB_HIP_MAX_WORKGROUPS");
-  if (cap && atoi(cap) > 0 && s->workgroups > atoi(cap)) s->workgroups = atoi(cap);
-  const long long ws_doubles = s->rec ? s->rec->ws_doubles(N) : (long long)s->lay.ws_doubles;
-  s->scratch_bytes = ws_doubles * sizeof(double) * s->workgroups * s->qps_per_wg;
+  RC_TRY(s->common_init(device, max_batch));
+  mpc_resolve_kernels(s.get());
+  int occupancy = 0, cus = 0;
+  RC_TRY(s->occupancy(s->kern.solve, &occupancy, &cus));
+  const fbk::LaunchPlan plan =
+      fbk::mpc_plan(cus, occupancy, handles_in_flight, fbk::hw_queues_hint(), s->rec != nullptr, s->qps_per_wg, max_batch,
+                    s->rec ? s->rec->ws_doubles(N) : (long long)s->lay.ws_doubles, knobs);
+  s->workgroups = plan.workgroups;
+  s->scratch_bytes = plan.scratch_bytes;
   hipError_t e = hipMalloc(&s->scratch, (size_t)s->scratch_bytes);
-  if (e != hipSuccess) {
-    s->release(); delete s;
-    return fail(FBSTAB_HIP_ERR_DEVICE, std::string("scratch allocation: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(FBSTAB_HIP_ERR_DEVICE, std::string("scratch allocation: ") + hipGetErrorString(e));
   const fbk::MpcLayout& L = s->lay;
   s->arr_len = {(long long)(N + 1) * nx * nx, (long long)(N + 1) * nu * nu,
                 (long long)(N + 1) * nu * nx, (long long)(N + 1) * nx, (long long)(N + 1) * nu,
@@ -1623,16 +1589,11 @@ int fbstab_hip_mpc_create_in_flight(int N, int nx, int nu, int nc, int max_batch
                 (long long)(N + 1) * nc * nx, (long long)(N + 1) * nc * nu,
                 (long long)(N + 1) * nc, (long long)nx};
   s->var_len[0] = L.nz; s->var_len[1] = L.nl; s->var_len[2] = L.nv; s->var_len[3] = L.nv;
-  *handle = s;
+  *handle = s.release();
   return FBSTAB_HIP_OK;
 }
 
 int fbstab_hip_mpc_destroy(fbstab_mpc_handle_t h) {
-  if (!h) return FBSTAB_HIP_OK;
-  h->release();
-  if (h->adj_scratch) (void)hipFree(h->adj_scratch);
-  if (h->sweep_seed) (void)hipFree(h->sweep_seed);
-  if (h->sweep_tmp) (void)hipFree(h->sweep_tmp);
   delete h;
   return FBSTAB_HIP_OK;
 }
@@ -1660,11 +1621,11 @@ static int mpc_solve_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_bat
                     fbstab_solver_out_t* d_out) -> int {
     // FBSTAB_HIP_KEEP_MATRICES (record handles): one QP per slot, slot = QP index
     const bool keep = !d_trace && h->rec && (flags & FBSTAB_HIP_KEEP_MATRICES) &&
-                      (flags & FBSTAB_HIP_DEVICE_POINTERS) && batch <= h->workgroups * h->qps_per_wg;
+                      (flags & FBSTAB_HIP_DEVICE_POINTERS) && fbk::slots_hold(batch, h->workgroups, h->qps_per_wg);
     const bool reuse = keep && h->kept_batch == batch;
     MpcKernel& e = d_trace ? h->kern.traced : keep ? h->kern.solve_keep : h->kern.solve;
     // (the traced solve: the call's one QP on one workgroup, `d_trace` in the probe's place)
-    const int grid = keep ? keep_grid(h, batch) : batch_grid(h, e, batch);
+    const int grid = keep ? fbk::keep_grid(batch, h->qps_per_wg) : h->batch_grid(e, batch);
     RC_TRY(launch_mpc(h, e, grid, s, a, v, d_out, batch, d_trace, reuse));
     if (!d_trace) h->kept_batch = keep ? batch : -1;  // (the traced solve leaves the slots alone)
     return FBSTAB_HIP_OK;
@@ -1749,8 +1710,7 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
   // Record kernels: the whole sweep is ONE launch of the KEEP instance, every row
   // looping over its own trajectory (SweepArgs; FBSTAB_HIP_SWEEP_PER_STEP=1 keeps the
   // launch per step below, which the flat-vector kernel always uses).
-  const char* per_step = getenv("FBSTAB_HIP_SWEEP_PER_STEP");
-  if (h->rec && batch <= h->workgroups * h->qps_per_wg && steps < 0xffff && !(per_step && atoi(per_step) != 0)) {
+  if (fbk::sweep_in_one_launch(h->rec != nullptr, batch, h->workgroups, h->qps_per_wg, steps, fbk::sweep_per_step())) {
     SweepArgs sa;
     sa.A = plant->A; sa.B = plant->B; sa.sA = plant->stride_A; sa.sB = plant->stride_B;
     sa.x0 = x0; sa.sx0 = data->stride[FBSTAB_MPC_x0];
@@ -1767,7 +1727,7 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
     HIP_TRY(hipMemcpyAsync(d_sa.p, &sa, sizeof(SweepArgs), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
     RC_TRY(h->begin_timed(s));
-    RC_TRY(launch_mpc(h, h->kern.solve_keep, keep_grid(h, batch), s, *data, *x, out, batch,
+    RC_TRY(launch_mpc(h, h->kern.solve_keep, fbk::keep_grid(batch, h->qps_per_wg), s, *data, *x, out, batch,
                       static_cast<double*>(d_sa.p), false));
     RC_TRY(h->end_timed(s));
     h->kept_batch = batch;
@@ -1891,7 +1851,7 @@ static int mpc_adjoint_launch(fbstab_mpc_handle_t h, int batch, AdjointStage& st
   void* flat_args[] = {const_cast<fbk::MpcLayout*>(&L), &st.a, &v, &sd, &st.g, &ad, &d_st, &sig, &alpha, &scratch,
                        &h->counter, &batch};
   RC_TRY(h->begin_timed(s));
-  RC_TRY(launch_entry(e, batch_grid(h, e, batch), e.record ? record_args : flat_args, s));
+  RC_TRY(launch_entry(e, h->batch_grid(e, batch), e.record ? record_args : flat_args, s));
   return h->end_timed(s);
 }
 
@@ -1925,8 +1885,7 @@ int fbstab_hip_mpc_adjoint_batch_reduced(fbstab_mpc_handle_t h, int batch, const
 // record adjoint: one launch of fbstab_mpc_r16_sweep_adjoint_kernel; every other handle, and
 // FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP=1: per step the costate kernel, the handle's adjoint launch, the costate kernel.
 static bool sweep_adjoint_in_one_launch(const fbstab_mpc_solver* h) {
-  const char* per_step = getenv("FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP");
-  return h->kern.sweep_adjoint.kern && !(per_step && atoi(per_step) != 0);
+  return h->kern.sweep_adjoint.kern && !fbk::sweep_adjoint_per_step();
 }
 
 int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
@@ -1972,7 +1931,7 @@ int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, cons
   h->kept_batch = -1;  // the slots' matrix copies are overwritten
   if (sweep_adjoint_in_one_launch(h)) {
     MpcKernel& e = h->kern.sweep_adjoint;
-    const size_t seed_bytes = sizeof(double) * (size_t)nz * (size_t)h->workgroups * (size_t)h->qps_per_wg;
+    const size_t seed_bytes = fbk::sweep_seed_bytes(nz, h->workgroups, h->qps_per_wg);
     if (!h->sweep_seed) HIP_TRY(hipMalloc(&h->sweep_seed, seed_bytes));
     HIP_TRY(hipMemsetAsync(h->sweep_seed, 0, seed_bytes, s));
     HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
@@ -1988,7 +1947,7 @@ int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, cons
     int N = L.N;
     void* args[] = {&d, &aa, &h->scratch, &h->counter, &batch, &N};
     RC_TRY(h->begin_timed(s));
-    RC_TRY(launch_entry(e, batch_grid(h, e, batch), args, s));
+    RC_TRY(launch_entry(e, h->batch_grid(e, batch), args, s));
     RC_TRY(h->end_timed(s));
     HIP_TRY(hipStreamSynchronize(s));
     return FBSTAB_HIP_OK;
@@ -2142,8 +2101,9 @@ int fbstab_hip_dense_create(int nz, int nl, int nv, int max_batch, int device,
   if (nz < 1 || nv < 1 || nl < 0)
     return fail(FBSTAB_HIP_ERR_ARGUMENT, "In FBstabDense::FBstabDense: nz and nv must be positive, nl nonnegative.");
   if (max_batch < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "max_batch must be positive");
-  fbstab_dense_solver* s = new (std::nothrow) fbstab_dense_solver();
+  std::unique_ptr<fbstab_dense_solver> s(new (std::nothrow) fbstab_dense_solver());
   if (!s) return fail(FBSTAB_HIP_ERR_DEVICE, "out of host memory");
+  const fbk::CreateKnobs knobs = fbk::create_knobs();
   // nz + nl <= 64: one wavefront per QP for every phase, the KKT matrix in registers,
   // up to eight QPs per CU (fb_dense_wave.h).  Otherwise four wavefronts per QP with
   // K in LDS or, beyond nz + nl ~ 140, in global scratch (fb_dense.h).
@@ -2152,24 +2112,18 @@ int fbstab_hip_dense_create(int nz, int nl, int nv, int max_batch, int device,
   s->threads = kDenseThreads;
   s->wlay.init(nz, nl, nv);
   s->wave = s->wlay.fits();
-  {
-    const char* th = getenv("FBSTAB_HIP_DENSE_THREADS");
-    if (th && atoi(th) == 256) s->wave = false;
-    if (th && atoi(th) == 64 && nz + nl <= 64) { s->threads = 64; s->wave = false; }
-    // Initial value of what fbstab_hip_dense_set_factorisation sets per handle (developer
-    // switches; the default is the reference's order): FBSTAB_HIP_DENSE_ORDER=pivoted | auto |
-    // natural, FBSTAB_HIP_DENSE_SPREAD_BITS, FBSTAB_HIP_DENSE_ACT_BITS, FBSTAB_HIP_DENSE_STICKY.
-    const char* od = getenv("FBSTAB_HIP_DENSE_ORDER");
-    if (od && !strcmp(od, "auto")) s->wlay.order = FBSTAB_HIP_DENSE_ORDER_AUTO;
-    if (od && !strcmp(od, "natural")) s->wlay.order = FBSTAB_HIP_DENSE_ORDER_NATURAL;
-    if (od && !strcmp(od, "pivoted")) s->wlay.order = FBSTAB_HIP_DENSE_ORDER_PIVOTED;
-    const char* sb = getenv("FBSTAB_HIP_DENSE_SPREAD_BITS");
-    if (sb && atoi(sb) > 0) s->wlay.spread_bits = atoi(sb);
-    const char* sk = getenv("FBSTAB_HIP_DENSE_STICKY");
-    if (sk) s->wlay.sticky = atoi(sk) != 0 ? 1 : 0;
-    const char* ab = getenv("FBSTAB_HIP_DENSE_ACT_BITS");
-    if (ab && atoi(ab) >= 0 && atoi(ab) < 1000) s->wlay.act_bits = atoi(ab);
-  }
+  const int forced_threads = fbk::dense_threads_choice(knobs, nz, nl);
+  if (forced_threads) s->wave = false;
+  if (forced_threads == 64) s->threads = 64;
+  // (initial values of what fbstab_hip_dense_set_factorisation sets per handle)
+  static_assert(fbk::kDenseOrderAuto == FBSTAB_HIP_DENSE_ORDER_AUTO &&
+                    fbk::kDenseOrderPivoted == FBSTAB_HIP_DENSE_ORDER_PIVOTED &&
+                    fbk::kDenseOrderNatural == FBSTAB_HIP_DENSE_ORDER_NATURAL,
+                "fb_launch_plan.h names the public header's orders");
+  if (knobs.dense_order >= 0) s->wlay.order = knobs.dense_order;
+  if (knobs.dense_spread_bits > 0) s->wlay.spread_bits = knobs.dense_spread_bits;
+  if (knobs.dense_sticky >= 0) s->wlay.sticky = knobs.dense_sticky;
+  if (knobs.dense_act_bits >= 0) s->wlay.act_bits = knobs.dense_act_bits;
   s->lay.init(nz, nl, nv, s->threads);
   if (s->threads == 64 && (s->lay.k_global || !s->lay.a_lds)) {  // does not fit that way
     s->threads = kDenseThreads;
@@ -2181,47 +2135,30 @@ int fbstab_hip_dense_create(int nz, int nl, int nv, int max_batch, int device,
     s->lay.init(nz, nl, nv, kDenseThreads);  // (the traced solve's layout)
     s->lds_bytes = s->wlay.lds_doubles * (int)sizeof(double);
   }
-  if (s->lds_bytes > kLdsLimitBytes) {  // (not reached: the vectors move to global scratch first)
-    delete s;
+  if (s->lds_bytes > kLdsLimitBytes)  // (not reached: the vectors move to global scratch first)
     return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "the iterate vectors do not fit the 160 KiB LDS budget");
-  }
-  int rc = s->common_init(device, max_batch);
-  if (rc != FBSTAB_HIP_OK) { s->release(); delete s; return rc; }
-  dense_resolve_kernels(s);
-  int per_cu = 0, cus = 0;
-  rc = s->occupancy(s->kern.solve, &per_cu, &cus);
-  if (rc != FBSTAB_HIP_OK) { s->release(); delete s; return rc; }
-  const char* env = getenv("FBSTAB_HIP_WGS_PER_CU");
-  if (env && atoi(env) > 0) per_cu = atoi(env);
-  s->workgroups = cus * per_cu;
-  if (s->workgroups > max_batch) s->workgroups = max_batch;
-  // test knob: FBSTAB_HIP_MAX_WORKGROUPS=n caps the grid, so that one workgroup solves several QPs in turn
-  const char* cap = getenv("FBSTAB_HIP_MAX_WORKGROUPS");
-  if (cap && atoi(cap) > 0 && s->workgroups > atoi(cap)) s->workgroups = atoi(cap);
-  s->scratch_bytes = 0;
-  if (s->wave)  // A' and the multipliers of every resident workgroup (fb_dense_wave.h)
-    s->scratch_bytes = (long long)sizeof(double) * s->wlay.ws_doubles * s->workgroups;
-  else if (s->lay.k_global)  // K (and, v_global, the iterate vectors) of every resident workgroup (fb_dense.h)
-    s->scratch_bytes = (long long)sizeof(double) * (s->lay.k_doubles + s->lay.v_doubles) * s->workgroups;
+  RC_TRY(s->common_init(device, max_batch));
+  dense_resolve_kernels(s.get());
+  int occupancy = 0, cus = 0;
+  RC_TRY(s->occupancy(s->kern.solve, &occupancy, &cus));
+  const fbk::LaunchPlan plan = fbk::dense_plan(cus, occupancy, max_batch, s->wave, s->wlay.ws_doubles, s->lay.k_global != 0,
+                                               (long long)s->lay.k_doubles + s->lay.v_doubles, knobs);
+  s->workgroups = plan.workgroups;
+  s->scratch_bytes = plan.scratch_bytes;
   if (s->scratch_bytes > 0) {
     hipError_t e = hipMalloc(&s->scratch, (size_t)s->scratch_bytes);
     // (fb_dense_wave.h relies on the multiplier rows past nz + nl being zero)
     if (e == hipSuccess && s->wave) e = hipMemset(s->scratch, 0, (size_t)s->scratch_bytes);
-    if (e != hipSuccess) {
-      s->release(); delete s;
-      return fail(FBSTAB_HIP_ERR_DEVICE, std::string("scratch allocation: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(FBSTAB_HIP_ERR_DEVICE, std::string("scratch allocation: ") + hipGetErrorString(e));
   }
   s->arr_len = {(long long)nz * nz, (long long)nz, (long long)nl * nz, (long long)nl,
                 (long long)nv * nz, (long long)nv};
   s->var_len[0] = nz; s->var_len[1] = nl; s->var_len[2] = nv; s->var_len[3] = nv;
-  *handle = s;
+  *handle = s.release();
   return FBSTAB_HIP_OK;
 }
 
 int fbstab_hip_dense_destroy(fbstab_dense_handle_t h) {
-  if (!h) return FBSTAB_HIP_OK;
-  h->release();
   delete h;
   return FBSTAB_HIP_OK;
 }
@@ -2245,7 +2182,7 @@ static int dense_solve_impl(fbstab_dense_handle_t h, int batch, const fbstab_den
                     fbstab_solver_out_t* d_out) -> int {
     DenseKernel& e = d_trace ? h->kern.traced : h->kern.solve;
     if (!e.kern) return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "traced dense solve: layout does not fit");
-    return launch_dense(h, e, dense_grid(h, batch), s, a, v, d_out, batch, d_trace);
+    return launch_dense(h, e, fbk::dense_grid(batch, h->workgroups), s, a, v, d_out, batch, d_trace);
   };
   auto launch_norms = [=](hipStream_t s, const fbstab_dense_batch_t& a, const fbstab_var_batch_t& v, double* dn) {
     const DenseNormArgs na = {a, v, h->lay.nz, h->lay.nl, h->lay.nv};
@@ -2322,7 +2259,7 @@ static int dense_adjoint_launch(fbstab_dense_handle_t h, int batch, AdjointStage
   void* args[] = {&h->lay, &a, &v, &sd, &g, &ad, &d_st, &sig, &alpha, &h->counter, &batch,
                   e.kscratch ? (void*)&ks : (void*)&no_ks};
   RC_TRY(h->begin_timed(s));
-  RC_TRY(launch_entry(e, dense_grid(h, batch), e.wave ? wave_args : args, s));
+  RC_TRY(launch_entry(e, fbk::dense_grid(batch, h->workgroups), e.wave ? wave_args : args, s));
   return h->end_timed(s);
 }
 
