@@ -56,13 +56,20 @@ the recursion does not change, and ``w.grad`` is the logged costate, dL/dw_k = m
 trajectory's retirement step.  Not served: the batch-summed
 (reduced) path inside the library, forward mode through the sweep, and losses of anything but ``u`` and ``x`` (the
 rest of z_k, l_k, v_k).
+
+Jacobians of the solution map with respect to the initial state, as matrices:
+
+    J = mpc_x0_sensitivity(solver, data, z, l, v)   # J["gain"] (B, nu, nx) = du0/dx0, J["dz"] (B, nx, nz), ...
+
+ONE call of fbstab_hip_mpc_x0_sensitivity_batch, one factorisation per QP for all nx columns.  The result is
+DETACHED: plain tensors that carry no graph.
 """
 import torch
 
 from .hip_api import DENSE_ARR, MPC_SEQ
 
 __all__ = ["MpcSolveFunction", "solve_mpc", "DenseSolveFunction", "solve_dense", "ClosedLoopMpcFunction",
-           "closed_loop_mpc"]
+           "closed_loop_mpc", "mpc_x0_sensitivity"]
 
 
 def _forward(names, ctx, solver, sigma, arrs):
@@ -154,6 +161,23 @@ def solve_mpc(solver, data, sigma: float = 0.0):
     (any of them may require grad; ``(len,)`` or ``(1, len)``: a parameter shared by the batch).  Returns
     ``(z, l, v, out)``; see the module docstring."""
     return MpcSolveFunction.apply(solver, sigma, *[data[k] for k in MPC_SEQ])
+
+
+def mpc_x0_sensitivity(solver, data, z, l, v, sigma: float = 0.0):
+    """The local feedback law and the plan's sensitivity to the initial state at the returned points ``(z, l, v)``
+    (``FBstabMpcBatch.X0Sensitivity``: one factorisation per QP, nx right-hand sides): a dict of torch tensors on the
+    inputs' device, ``gain (B, nu, nx)`` = du0/dx0, ``dz (B, nx, nz)``, ``dl (B, nx, nl)``, ``dv (B, nx, nv)`` - row
+    j the tangent for dx0 = e_j - and ``status (B,)``.  The result is DETACHED: the inputs' graphs are not read and
+    none is recorded (differentiate through ``solve_mpc`` for gradients of a loss)."""
+    with torch.no_grad():
+        det = lambda t: t.detach()
+        arrs = {k: det(data[k]) for k in MPC_SEQ}
+        B = z.shape[0]
+        arrs = {k: (a.reshape(1, -1) if a.dim() == 1 else a) for k, a in arrs.items()}
+        assert all(a.shape[0] in (1, B) for a in arrs.values())
+        res = solver.X0Sensitivity(arrs, det(z).contiguous(), det(l).contiguous(), det(v).contiguous(), sigma=sigma,
+                                   want=("dz", "dl", "dv", "gain"))
+    return res
 
 
 class DenseSolveFunction(torch.autograd.Function):

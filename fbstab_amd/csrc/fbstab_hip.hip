@@ -1312,9 +1312,10 @@ struct fbstab_mpc_solver : SolverBase {
   double* sweep_seed = nullptr;
   double* sweep_tmp = nullptr;
   // What this handle launches (mpc_resolve_kernels).  solve_keep: record handles only; adjoint: on the record or
-  // the flat-vector kernel (`record`); sweep_adjoint: null where the sweep adjoint runs per step.
+  // the flat-vector kernel (`record`); sweep_adjoint: null where the sweep adjoint runs per step; kkt_multi: the
+  // flat-vector kernel of fb_kkt_multi.hip on every handle.
   struct {
-    MpcKernel solve, solve_keep, traced, probe, adjoint, sweep_adjoint;
+    MpcKernel solve, solve_keep, traced, probe, adjoint, sweep_adjoint, kkt_multi;
   } kern;
 
   ~fbstab_mpc_solver() {
@@ -1345,6 +1346,9 @@ FB_RECORD_INSTANCE_DECL(18, 5, 10, 2)
 // spilled registers), three to four times the flat-vector kernel all the same
 FB_RECORD_INSTANCE_DECL(24, 8, 16, 2)
 FB_RECORD_INSTANCE_DECL(24, 8, 32, 2)
+// fbstab_mpc_kkt_multi_kernel (fb_kkt_multi.hip, a translation unit of its own): [wglobal != 0] the stage tile and the
+// work matrices in global scratch, or everything in LDS
+__attribute__((visibility("hidden"))) const void* fbstab_kkt_multi_kernel(int wglobal);
 #if defined(FB_SINGLE_TU)
 // (diagnostic builds with device-side counters: one translation unit, one g_stamps)
 #include "rec_12_4_20.hip"
@@ -1352,6 +1356,7 @@ FB_RECORD_INSTANCE_DECL(24, 8, 32, 2)
 #include "rec_18_5_10.hip"
 #include "rec_24_8_16.hip"
 #include "rec_24_8_32.hip"
+#include "fb_kkt_multi.hip"
 #endif
 namespace {
 const RecordInstance* record_instances(int* count) {
@@ -1445,6 +1450,10 @@ void mpc_resolve_kernels(fbstab_mpc_solver* h) {
   if (!k.adjoint.kern)
     k.adjoint = {{adjoint[f], "fbstab_mpc_adjoint_kernel<64>", kMpcThreads, flat_lds}, false,
                  h->rec ? MpcKernel::kAdjoint : MpcKernel::kHandle};
+  // many right-hand sides on one factorisation: the flat-vector layout on every handle, a record handle in the
+  // flat adjoint's scratch (its own is laid out for the record kernel and is not touched)
+  k.kkt_multi = {{fbstab_kkt_multi_kernel(h->lay.wglobal), "fbstab_mpc_kkt_multi_kernel<64>", kMpcThreads, flat_lds},
+                 false, h->rec ? MpcKernel::kAdjoint : MpcKernel::kHandle};
 }
 }  // namespace
 
@@ -2036,6 +2045,177 @@ int fbstab_hip_mpc_tangent_batch(fbstab_mpc_handle_t h, int batch, const fbstab_
   };
   return tangent_run(h, batch, data, x, ddata, sigma, dx, rhs, status, flags, stream,
                      reinterpret_cast<const void*>(fbstab_tangent_rhs_kernel), launch_dir, mpc_adjoint_launch);
+}
+
+// ---- many right-hand sides on one factorisation (include/fbstab_hip.h; fb_kkt_multi.h) --------------------------
+namespace {
+// The stride rule of a seed or step block, slot by slot: with batch > 1 or nrhs > 1, rhs_stride >= len[i] and
+// stride >= (nrhs - 1) rhs_stride + len[i], or for a seed stride 0.  len == nullptr: before the handle is looked at,
+// with the one length that no slot undercuts (1) - what fails here fails for every handle.
+int check_multi_strides(const fbstab_multi_var_batch_t* b, const long long* len, int batch, int nrhs, bool seed) {
+  for (int i = 0; i < 3; i++) {
+    if (!b->base[i]) continue;
+    const long long n = len ? len[i] : 1;
+    if (nrhs > 1 && b->rhs_stride[i] < n)
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, seed ? "seed rhs_stride smaller than the vector length"
+                                                : "step rhs_stride smaller than the vector length");
+    const long long span = (nrhs > 1 ? (nrhs - 1) * b->rhs_stride[i] : 0) + n;
+    if (batch > 1 && b->stride[i] < span && !(seed && b->stride[i] == 0))
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, seed ? "seed stride smaller than the right-hand sides of one QP"
+                                                : "step stride smaller than the right-hand sides of one QP");
+  }
+  return FBSTAB_HIP_OK;
+}
+
+// Kernel side of a caller's seed or step block.  Device pointers pass through (one QP: it is at the base; one
+// right-hand side: rhs_stride is not read).  A host block is staged packed, [QP][rhs][len], in allocations of the call:
+// `open` uploads a seed block (upload = true) or only allocates, `download` brings a step block back, vector by
+// vector, so that the doubles between a QP's vectors stay as they are.
+struct MultiStage {
+  fbstab_multi_var_batch_t k{};
+  DevBuf buf[3];
+
+  static int copy(double* dst, long long dpitch, const double* src, long long spitch, long long len, long long rows,
+                  hipMemcpyKind kind, hipStream_t s) {
+    HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * dpitch, src, sizeof(double) * spitch, sizeof(double) * len, rows,
+                             kind, s));
+    return FBSTAB_HIP_OK;
+  }
+  int open(const fbstab_multi_var_batch_t* b, const long long* len, int batch, int nrhs, bool dev_ptrs, bool upload,
+           hipStream_t s) {
+    for (int i = 0; i < 3; i++) {
+      if (!b || !b->base[i] || len[i] == 0) continue;
+      const long long rs = nrhs > 1 ? b->rhs_stride[i] : len[i];
+      const long long st = batch > 1 ? b->stride[i] : 0;
+      if (dev_ptrs) {
+        k.base[i] = b->base[i]; k.stride[i] = st; k.rhs_stride[i] = rs;
+        continue;
+      }
+      const long long nq = st == 0 ? 1 : batch;
+      HIP_TRY(hipMalloc(&buf[i].p, sizeof(double) * (size_t)(len[i] * nrhs * nq)));
+      k.base[i] = static_cast<double*>(buf[i].p);
+      k.stride[i] = st == 0 ? 0 : len[i] * nrhs;
+      k.rhs_stride[i] = len[i];
+      if (!upload) continue;
+      if (nq == 1 || st == nrhs * rs) {
+        RC_TRY(copy(k.base[i], len[i], b->base[i], rs, len[i], nq * nrhs, hipMemcpyHostToDevice, s));
+      } else {
+        for (long long q = 0; q < nq; q++)
+          RC_TRY(copy(k.base[i] + q * len[i] * nrhs, len[i], b->base[i] + q * st, rs, len[i], nrhs,
+                      hipMemcpyHostToDevice, s));
+      }
+    }
+    return FBSTAB_HIP_OK;
+  }
+  int download(const fbstab_multi_var_batch_t* b, const long long* len, int batch, int nrhs, hipStream_t s) {
+    for (int i = 0; i < 3; i++) {
+      if (!buf[i].p) continue;
+      const long long rs = nrhs > 1 ? b->rhs_stride[i] : len[i];
+      const long long st = batch > 1 ? b->stride[i] : 0;
+      if (batch == 1 || st == nrhs * rs) {
+        RC_TRY(copy(b->base[i], rs, k.base[i], len[i], len[i], (long long)batch * nrhs, hipMemcpyDeviceToHost, s));
+      } else {
+        for (long long q = 0; q < batch; q++)
+          RC_TRY(copy(b->base[i] + q * st, rs, k.base[i] + q * len[i] * nrhs, len[i], len[i], nrhs,
+                      hipMemcpyDeviceToHost, s));
+      }
+    }
+    return FBSTAB_HIP_OK;
+  }
+};
+
+// Both entry points behind what needs no handle.  seed == nullptr: the x0 mode (nrhs = nx, the seeds generated in the
+// kernel); step may be null there, and gain (null, or nu x nx per QP) is served there only.
+int kkt_multi_run(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data, const fbstab_var_batch_t* x,
+                  int nrhs, const fbstab_multi_var_batch_t* seed, double sigma, const fbstab_multi_var_batch_t* step,
+                  double* gain, long long gain_stride, int* status, int flags, void* stream) {
+  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  const fbk::MpcLayout& L = h->lay;
+  const bool x0_mode = seed == nullptr;
+  if (x0_mode) nrhs = L.nx;
+  const long long* vlen = h->var_len;
+  const long long glen = (long long)L.nu * L.nx;
+  for (size_t i = 0; i < h->arr_len.size(); i++)
+    if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
+  for (int i = 0; i < 3; i++)
+    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
+  for (int i = 0; i < 3; i++) RC_TRY(h->check_var_stride(x->stride, i, batch));
+  if (seed) RC_TRY(check_multi_strides(seed, vlen, batch, nrhs, true));
+  if (step) RC_TRY(check_multi_strides(step, vlen, batch, nrhs, false));
+  if (batch > 1 && gain && gain_stride < glen)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "gain stride smaller than nu x nx");
+  RC_TRY(h->check_data_strides(data->stride, batch));
+  if (batch == 0) return FBSTAB_HIP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
+  fbstab_mpc_batch_t a;
+  fbstab_var_batch_t v;
+  RC_TRY(h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride));
+  RC_TRY(h->stage_vars(x->base, x->stride, 3, batch, dev_ptrs, s, &v));
+  MultiStage sd, st;
+  RC_TRY(sd.open(seed, vlen, batch, nrhs, dev_ptrs, true, s));
+  RC_TRY(st.open(step, vlen, batch, nrhs, dev_ptrs, false, s));
+  DevBuf d_gain, d_status;
+  double* k_gain = gain;
+  long long k_gain_stride = batch > 1 ? gain_stride : 0;
+  if (gain && !dev_ptrs) {
+    HIP_TRY(hipMalloc(&d_gain.p, sizeof(double) * (size_t)glen * batch));
+    k_gain = static_cast<double*>(d_gain.p);
+    k_gain_stride = glen;
+  }
+  int* d_st = status;
+  const bool status_host = SolverBase::out_on_host(flags);
+  if (status_host) {
+    HIP_TRY(hipMalloc(&d_status.p, sizeof(int) * (size_t)batch));
+    d_st = static_cast<int*>(d_status.p);
+  }
+  double sig = sigma_or_default(sigma);
+  double alpha = h->opts.alpha;
+  int x0m = x0_mode ? 1 : 0;
+  HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
+  MpcKernel& e = h->kern.kkt_multi;
+  // (the flat adjoint's scratch on a record handle, allocated here by the first call that needs it; the handle's
+  // own scratch and kept_batch stay as they are)
+  double* scratch;
+  RC_TRY(flat_workspace(h, e, &scratch));
+  void* args[] = {const_cast<fbk::MpcLayout*>(&L), &a, &v, &sd.k, &st.k, &k_gain, &k_gain_stride, &d_st, &nrhs, &x0m,
+                  &sig, &alpha, &scratch, &h->counter, &batch};
+  RC_TRY(h->begin_timed(s));
+  RC_TRY(launch_entry(e, h->batch_grid(e, batch), args, s));
+  RC_TRY(h->end_timed(s));
+  if (!dev_ptrs) {
+    RC_TRY(st.download(step, vlen, batch, nrhs, s));
+    if (gain) RC_TRY(h->download(gain, gain_stride, glen, batch, k_gain, s));
+  }
+  if (status_host) HIP_TRY(hipMemcpyAsync(status, d_st, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
+  if (status_host || !(flags & FBSTAB_HIP_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
+  return FBSTAB_HIP_OK;
+}
+}  // namespace
+
+int fbstab_hip_mpc_kkt_solve_batch(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                   const fbstab_var_batch_t* x, int nrhs, const fbstab_multi_var_batch_t* seed,
+                                   double sigma, const fbstab_multi_var_batch_t* step, int* status, int flags,
+                                   void* stream) {
+  // what needs no handle comes first
+  if (nrhs < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "kkt solve: fewer than one right-hand side");
+  if (!seed || !step) return fail(FBSTAB_HIP_ERR_ARGUMENT, "kkt solve: null seed or step block");
+  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null seed pointer (z)");
+  int rc = check_multi_strides(seed, nullptr, batch, nrhs, true);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = check_multi_strides(step, nullptr, batch, nrhs, false);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  return kkt_multi_run(h, batch, data, x, nrhs, seed, sigma, step, nullptr, 0, status, flags, stream);
+}
+
+int fbstab_hip_mpc_x0_sensitivity_batch(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
+                                        const fbstab_var_batch_t* x, double sigma,
+                                        const fbstab_multi_var_batch_t* step, double* gain, long long gain_stride,
+                                        int* status, int flags, void* stream) {
+  // (nrhs = nx takes the handle: every stride is checked behind it)
+  return kkt_multi_run(h, batch, data, x, 0, nullptr, sigma, step, gain, gain_stride, status, flags, stream);
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;

@@ -89,6 +89,11 @@ class _DenseGradBatch(C.Structure):
     _fields_ = [("base", C.c_void_p * 6), ("stride", C.c_longlong * 6)]
 
 
+class _MultiVarBatch(C.Structure):
+    """fbstab_multi_var_batch_t: nrhs vectors (z, l, v) per QP."""
+    _fields_ = [("base", C.c_void_p * 3), ("stride", C.c_longlong * 3), ("rhs_stride", C.c_longlong * 3)]
+
+
 class _Plant(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("stride_A", C.c_longlong), ("stride_B", C.c_longlong)]
 
@@ -188,6 +193,13 @@ def load_library() -> C.CDLL:
             getattr(lib, f"fbstab_hip_{kind}_tangent_batch").argtypes = [
                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                 C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_kkt_solve_batch"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_kkt_solve_batch.argtypes = [
+            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+            C.c_int, C.c_void_p]
+        lib.fbstab_hip_mpc_x0_sensitivity_batch.argtypes = [
+            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_longlong,
+            C.c_void_p, C.c_int, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -231,6 +243,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_adjoint_batch_reduced", "fbstab_hip_mpc_tangent_batch", "fbstab_hip_debug_stamps",
     "fbstab_hip_mpc_receding_sweep_logged", "fbstab_hip_mpc_receding_sweep_adjoint",
     "fbstab_hip_mpc_sweep_adjoint_kernel_name", "fbstab_hip_mpc_receding_sweep_scenario",
+    "fbstab_hip_mpc_kkt_solve_batch", "fbstab_hip_mpc_x0_sensitivity_batch",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",
     "fbstab_hip_dense_solve_traced", "fbstab_hip_dense_adjoint_batch",
@@ -312,6 +325,29 @@ def _fill_vars(arrs, var_lens, B, dev_flags, optional=False, vb=None):
         vb.base[i], vb.stride[i] = p, st
         dev_flags.append(d)
     return vb
+
+
+def _fill_multi(arrs, var_lens, B, K, dev_flags, optional=False, first_required=True):
+    """A _MultiVarBatch of the ``(B, K, n)`` arrays ``arrs`` (seeds or steps of K right-hand sides per QP); a
+    ``(K, n)`` array is one block shared by the batch (stride 0).  None is a NULL slot (``optional``; the first
+    slot only without ``first_required``)."""
+    mb = _MultiVarBatch()
+    for i, (a, n) in enumerate(zip(arrs, var_lens)):
+        if a is None:
+            assert optional and (i > 0 or not first_required), "gz is required"
+            mb.base[i], mb.stride[i], mb.rhs_stride[i] = None, 0, 0
+            continue
+        tor = _is_torch(a)
+        assert a.dtype == (_torch.float64 if tor else np.float64), a.dtype
+        shape = tuple(a.shape)
+        assert shape == (B, K, n) or shape == (K, n), (shape, (B, K, n))
+        st = tuple(a.stride()) if tor else tuple(t // 8 for t in a.strides)
+        assert st[-1] == 1 or n <= 1
+        mb.base[i] = a.data_ptr() if tor else a.ctypes.data
+        mb.stride[i] = (st[0] if B > 1 else K * n) if len(shape) == 3 else 0
+        mb.rhs_stride[i] = st[-2] if K > 1 else n
+        dev_flags.append(a.is_cuda if tor else False)
+    return mb
 
 
 class _Host:
@@ -785,6 +821,64 @@ class FBstabMpcBatch(_SolverBase):
         ``rhs=True``, the seeds ``"gz", "gl", "gv"`` of the tangent system.  ``sigma <= 0``: 1e-8."""
         return _tangent(self, _MpcBatch(), _MpcBatch(), MPC_SEQ, self.seq_len, data, z, l, v, ddata, sigma, rhs,
                         stream, async_)
+
+
+    def _multi_call(self, data, z, l, v, K, seeds, sigma, want, gain, stream, async_):
+        """fbstab_hip_mpc_kkt_solve_batch (``seeds``: (gz, gl, gv)) or fbstab_hip_mpc_x0_sensitivity_batch (None)."""
+        dev_flags = []
+        B = z.shape[0]
+        batch_struct = _MpcBatch()
+        _fill_block(batch_struct, MPC_SEQ, self.seq_len, data, B, dev_flags)
+        var_lens = (self.nz, self.nl, self.nv)
+        xb = _fill_vars((z, l, v), var_lens, B, dev_flags)
+        sb = _fill_multi(seeds, var_lens, B, K, dev_flags, optional=True) if seeds is not None else None
+        where, flags, stream = _placement(dev_flags, z, stream, async_)
+        status = where.zeros(z, B, "i4")
+        if where.on_dev:
+            zeros = lambda *shape: where.zeros(z, (B,) + shape)
+        else:
+            zeros = lambda *shape: np.zeros((max(B, 1),) + shape)[:B]   # (an empty batch keeps the strides of a row)
+        res = {k: zeros(K, n) for k, n in zip(("dz", "dl", "dv"), var_lens) if k in want}
+        ob = _fill_multi(tuple(res.get(k) for k in ("dz", "dl", "dv")), var_lens, B, K, [], optional=True,
+                         first_required=False) if res else None
+        tail = (C.c_void_p(where.ptr(status)), flags, C.c_void_p(stream) if stream else None)
+        if seeds is not None:
+            rc = self._lib.fbstab_hip_mpc_kkt_solve_batch(self._h, B, C.byref(batch_struct), C.byref(xb), K,
+                                                          C.byref(sb), C.c_double(sigma), C.byref(ob), *tail)
+        else:
+            if gain:
+                res["gain"] = zeros(self.nx, self.nu)   # (nu x nx column-major per QP)
+            rc = self._lib.fbstab_hip_mpc_x0_sensitivity_batch(
+                self._h, B, C.byref(batch_struct), C.byref(xb), C.c_double(sigma),
+                C.byref(ob) if ob is not None else None,
+                C.c_void_p(where.ptr(res["gain"])) if gain else None, self.nu * self.nx, *tail)
+        _check(self._lib, rc)
+        if gain:
+            res["gain"] = res["gain"].transpose(1, 2) if where.on_dev else res["gain"].transpose(0, 2, 1)
+        res["status"] = status
+        return res
+
+    def KktSolve(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0, stream: int = 0,
+                 async_: bool = False) -> Dict[str, object]:
+        """Several right-hand sides on ONE factorisation per QP (fbstab_hip_mpc_kkt_solve_batch): ``gz`` of shape
+        ``(batch, K, nz)``, or ``(K, nz)`` for one block of K seeds shared by the batch; ``gl``, ``gv`` the same
+        (None: zero).  Returns a dict with ``dz (batch, K, nz)``, ``dl``, ``dv`` - slot k what ``Adjoint(...,
+        adj=True)`` returns for seed k - and ``status`` (``(batch,)`` int32: 1 where the factorisation failed and
+        every right-hand side's step is zero).  All numpy or all torch CUDA tensors, like ``Adjoint``.
+        ``sigma <= 0``: 1e-8."""
+        assert len(gz.shape) in (2, 3), gz.shape
+        return self._multi_call(data, z, l, v, gz.shape[-2], (gz, gl, gv), sigma, ("dz", "dl", "dv"), False, stream,
+                                async_)
+
+    def X0Sensitivity(self, data: Dict[str, object], z, l, v, sigma: float = 0.0,
+                      want: Sequence[str] = ("dz", "gain"), stream: int = 0, async_: bool = False) -> Dict[str, object]:
+        """The solutions' sensitivity to the initial state on ONE factorisation per QP
+        (fbstab_hip_mpc_x0_sensitivity_batch): those of ``want`` among ``dz (batch, nx, nz)``, ``dl``, ``dv`` - row j
+        what ``Tangent`` returns for the direction x0 = e_j - and ``gain (batch, nu, nx)`` = du0/dx0, the local
+        feedback law, plus ``status``.  All numpy or all torch CUDA tensors, like ``Adjoint``."""
+        unknown = set(want) - {"dz", "dl", "dv", "gain"}
+        assert not unknown, unknown
+        return self._multi_call(data, z, l, v, self.nx, None, sigma, want, "gain" in want, stream, async_)
 
 
 class FBstabDenseBatch(_SolverBase):

@@ -493,6 +493,57 @@ int fbstab_hip_mpc_tangent_batch(fbstab_mpc_handle_t handle, int batch, const fb
                                  const fbstab_var_batch_t* dx, const fbstab_var_batch_t* rhs,
                                  int* status, int flags, void* stream);
 
+/* ---- many right-hand sides: factor V once, solve for nrhs of them -----------------------------------------------
+ * The adjoint and the tangent above return one vector per factorisation of V.  The matrices their users ask for -
+ * the local feedback law du0/dx0 (nu x nx) and the whole plan's sensitivity dz/dx0, or several loss seeds at the
+ * same solutions - cost them one factorisation per column or row.  In the Riccati solver the factorisation of a
+ * stage is the O(nx^3) part and the vector recursions of a Solve are O(nx^2); these two calls factor V once per QP
+ * and run the recursions once per right-hand side (fb_kkt_multi.h; fbstab_mpc_kkt_multi_kernel, one QP per
+ * workgroup on the flat-vector layout, on EVERY handle).
+ *
+ * fbstab_hip_mpc_kkt_solve_batch: slot k of `step` is what fbstab_hip_mpc_adjoint_batch(..., adj) returns for
+ * seed k, V (dz, dl, dv) = (gz, -gl, -C gv).  Right-hand side 0 is that call's arithmetic to the bit; the others run
+ * the same recursions on the same factors, without the matrix work.
+ *   nrhs:   right-hand sides per QP, >= 1 (below: FBSTAB_HIP_ERR_ARGUMENT).
+ *   seed:   nrhs vectors (gz, gl, gv) per QP: vector k of QP q of slot i at base[i] + q stride[i] + k rhs_stride[i].
+ *           The l and v slots may be NULL (zero).  A slot with stride 0 is ONE block of nrhs vectors shared by the
+ *           batch (the identity on the u0 rows, say).
+ *   step:   nrhs vectors (dz, dl, dv) per QP, laid out the same way; NULL slots are skipped.  Every QP needs its own.
+ *   strides, with batch > 1 or nrhs > 1: rhs_stride >= length, and stride >= (nrhs - 1) rhs_stride + length (or 0
+ *           for a seed slot); anything else is FBSTAB_HIP_ERR_ARGUMENT.  The doubles between a QP's vectors
+ *           (rhs_stride > length) are not written.
+ *   status: per QP, 0, or 1 where the factorisation failed: every right-hand side's step of that QP is zero.
+ * fbstab_hip_mpc_x0_sensitivity_batch: nrhs = nx, right-hand side j the tangent's for dx0 = e_j (gz = 0, gl = -e_j
+ * in the l_0 block, gv = 0), generated in the kernel: slot j of `step` is fbstab_hip_mpc_tangent_batch's dx for the
+ * direction x0 = e_j, bitwise what fbstab_hip_mpc_kkt_solve_batch returns for those seeds.
+ *   step:   NULL, or as above with nrhs = nx; NULL slots are skipped.
+ *   gain:   NULL, or nu x nx doubles per QP (QP q at gain + q gain_stride, gain_stride >= nu nx when batch > 1),
+ *           column-major: du0/dx0, the u0 rows of stage 0 of the dz columns, written by the kernel whether or not
+ *           the dz slot is taken.  At a point where no constraint is active this is -K_0 of the Riccati recursion.
+ * sigma, flags, streams, host-pointer staging (a host-pointer call stages the seed and step blocks packed, in
+ * allocations of the call), where `status` lives, batch == 0 (OK, nothing is queued) are those of
+ * fbstab_hip_mpc_adjoint_batch.  Validation: what needs no handle comes first - nrhs, the NULL blocks, a NULL z seed,
+ * strides no length could satisfy - then the handle and what takes its lengths; everything before any device call.
+ * Memory: the kernel runs in the flat-vector workspace (MpcLayout::ws_doubles per workgroup).  A flat-vector handle
+ * has it.  A record handle runs it in the scratch of the flat-vector adjoint, which a record handle whose adjoint is
+ * on the record (fbstab_hip_mpc_adjoint_kernel_name) has not allocated yet: the first call then allocates it, as
+ * documented for the flat adjoint above (ws_doubles x the handle's workgroups, held until destroy, not counted in
+ * fbstab_hip_mpc_query's scratch_bytes).  The record handle's own scratch is not touched: the matrix copies of a
+ * FBSTAB_HIP_KEEP_MATRICES solve stay valid across these calls.  fbstab_hip_mpc_last_kernel_ms reports the launch. */
+typedef struct fbstab_multi_var_batch_t { /* nrhs vectors (z, l, v) per QP */
+  double* base[3];
+  long long stride[3];     /* between QPs */
+  long long rhs_stride[3]; /* between the vectors of one QP */
+} fbstab_multi_var_batch_t;
+int fbstab_hip_mpc_kkt_solve_batch(fbstab_mpc_handle_t handle, int batch, const fbstab_mpc_batch_t* data,
+                                   const fbstab_var_batch_t* x, int nrhs, const fbstab_multi_var_batch_t* seed,
+                                   double sigma, const fbstab_multi_var_batch_t* step, int* status, int flags,
+                                   void* stream);
+int fbstab_hip_mpc_x0_sensitivity_batch(fbstab_mpc_handle_t handle, int batch, const fbstab_mpc_batch_t* data,
+                                        const fbstab_var_batch_t* x, double sigma,
+                                        const fbstab_multi_var_batch_t* step, double* gain, long long gain_stride,
+                                        int* status, int flags, void* stream);
+
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);
 
