@@ -24,23 +24,6 @@
 
 namespace fbk {
 
-struct GradReduceArgs {
-  GradReducePlan plan;
-  const double* x[3];  // z, l, v
-  long long xs[3];
-  const double* p[3];  // dz, dl, dv
-  long long ps[3];
-  const int* status;               // the adjoint's, per QP
-  const fbstab_solver_out_t* out;  // the solve's records, or null
-  double* scratch;                 // grad_reduce_scratch_doubles(plan, batch)
-  int batch;
-};
-
-constexpr int kGradReduceMaxSeq = 12;
-struct GradReduceOut {
-  double* base[kGradReduceMaxSeq];  // where the reduced array of each sequence goes (null: not reduced)
-};
-
 constexpr int kGradReduceUnroll = 4;  // (kGradReduceChunk is a multiple of 4 x this)
 static_assert(kGradReduceChunk % (4 * kGradReduceUnroll) == 0, "whole trips per chunk");
 

@@ -22,6 +22,8 @@
 // adds the slots of a tile in ascending chunk order and applies the sign and the 1/2.
 #pragma once
 
+#include "../../include/fbstab_types.h"  // fbstab_solver_out_t (GradReduceArgs)
+
 #if defined(__HIPCC__)
 #define FB_PLAN_FN __host__ __device__ inline
 #else
@@ -178,5 +180,23 @@ FB_PLAN_FN bool grad_reduce_vector_entry(const GradReducePlan& p, int g, int r, 
   *seq = 10; *idx = i * nc + r;                                                               // d
   return true;
 }
+
+// What the two kernels take, filled on the host (fb_host_stage.h: AdjointStage::reduce).
+struct GradReduceArgs {
+  GradReducePlan plan;
+  const double* x[3];  // z, l, v
+  long long xs[3];
+  const double* p[3];  // dz, dl, dv
+  long long ps[3];
+  const int* status;               // the adjoint's, per QP
+  const fbstab_solver_out_t* out;  // the solve's records, or null
+  double* scratch;                 // grad_reduce_scratch_doubles(plan, batch)
+  int batch;
+};
+
+constexpr int kGradReduceMaxSeq = 12;
+struct GradReduceOut {
+  double* base[kGradReduceMaxSeq];  // where the reduced array of each sequence goes (null: not reduced)
+};
 
 }  // namespace fbk

@@ -16,6 +16,16 @@
 
 namespace fbk {
 
+// What the host staging (fb_host_stage.h) and the launch sites share with the kernels of the C-ABI unit:
+// the queue block of a handle (the queue word, the refinement count, the dense counters below), allocated at
+// creation and zeroed before every launch ...
+constexpr size_t kQueueBytes = 8 * sizeof(int);
+// ... the word of it in which the one-wavefront dense kernel counts the Newton steps it handed to the pivoted
+// factorisation ...
+constexpr int kDenseFallbackSlot = 4;
+// ... and the dynamic LDS a workgroup may ask for.
+constexpr int kLdsLimitBytes = 160 * 1024;
+
 // ---------------------------------------------------------------------------------------------------------------
 // The knobs: every FBSTAB_HIP_* variable the C-ABI unit reads (the shard knobs are fb_shard.h's own).  DESIGN.md
 // section 4.6 has the table.  All of them are developer and test switches; each is parsed by the expression its

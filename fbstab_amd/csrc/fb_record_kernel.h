@@ -141,7 +141,7 @@ __device__ __forceinline__ void newton_probe(P& p, const C& ctx, const fbstab_op
 // QP indices from the shared counter.  scratch: rows * ws_doubles(N).
 // One queue object per 16-lane row; every function is called by the whole row and
 // returns row-uniform values.  Nothing in here waits for another wavefront.
-constexpr size_t kQueueBytes = 8 * sizeof(int);
+// (The queue block is kQueueBytes long: fb_launch_plan.h.)
 
 // The receding-horizon sweep as ONE launch of a KEEP instance (fbstab_hip_mpc_receding_sweep):
 // a row then solves ITS trajectory `steps` times, advancing the plant in between, and

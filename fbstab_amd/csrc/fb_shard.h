@@ -234,6 +234,55 @@ int check_shards(fbstab_shard_group* g, Handle* const* handles, const int* count
   return FBSTAB_HIP_OK;
 }
 
+// fbstab_hip_mpc_solve_batch_sharded and fbstab_hip_dense_solve_batch_sharded (`solve`: the kind's solve_batch).
+template <class Handle, class Data>
+int solve_sharded(fbstab_shard_group* g, Handle* const* handles, const int* counts, const Data* data,
+                  const fbstab_var_batch_t* x, fbstab_solver_out_t* const* out, int root,
+                  const fbstab_var_batch_t* root_x, fbstab_solver_out_t* root_out,
+                  int (*solve)(Handle*, int, const Data*, const fbstab_var_batch_t*, fbstab_solver_out_t*, int, void*)) {
+  long long total = 0;
+  int rc = check_shards(g, handles, counts, root, &total);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  if (!data || !x || !out || !root_x || !root_out) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
+  const int ndev = (int)g->devices.size();
+  std::vector<hipStream_t> streams(ndev);
+  std::vector<std::vector<GatherPiece>> pieces(ndev);
+  long long first = 0;
+  // every shard's arguments are checked before the first shard is queued (an empty shard
+  // needs no arrays and is skipped)
+  for (int d = 0; d < ndev; d++) {
+    streams[d] = handles[d]->stream;
+    if (counts[d] == 0) continue;
+    if (!out[d]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null SolverOut pointer of a non-empty shard");
+    for (size_t i = 0; i < handles[d]->arr_len.size(); i++)
+      if (!data[d].base[i] && handles[d]->arr_len[i] > 0)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer of a non-empty shard");
+    for (int i = 0; i < 4; i++)
+      if (!x[d].base[i] && handles[d]->var_len[i] > 0)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer of a non-empty shard");
+  }
+  for (int i = 0; i < 4; i++)
+    if (!root_x->base[i] && handles[0]->var_len[i] > 0 && total > 0)
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer on the root");
+  for (int d = 0; d < ndev; d++) {
+    if (counts[d] > 0) {
+      rc = solution_pieces(handles[d]->var_len, x[d], *root_x, first, counts[d], &pieces[d]);
+      if (rc != FBSTAB_HIP_OK) return rc;
+      pieces[d].push_back({out[d], root_out + first, sizeof(fbstab_solver_out_t) * (size_t)counts[d]});
+    }
+    first += counts[d];
+  }
+  // every shard is queued on its device (nothing waits for another device), then the gather
+  for (int d = 0; d < ndev; d++) {
+    if (counts[d] == 0) continue;
+    rc = solve(handles[d], counts[d], &data[d], &x[d], out[d], FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC, nullptr);
+    if (rc != FBSTAB_HIP_OK) return drain_and_fail(g, streams, rc);
+  }
+  rc = shard_gather(g, root, pieces, streams);
+  if (rc != FBSTAB_HIP_OK) return drain_and_fail(g, streams, rc);
+  return sync_all(g, streams);
+}
+
 }  // namespace
 
 extern "C" {
@@ -287,95 +336,14 @@ int fbstab_hip_mpc_solve_batch_sharded(fbstab_shard_group_t g, const fbstab_mpc_
                                        const fbstab_mpc_batch_t* data, const fbstab_var_batch_t* x,
                                        fbstab_solver_out_t* const* out, int root, const fbstab_var_batch_t* root_x,
                                        fbstab_solver_out_t* root_out) {
-  long long total = 0;
-  int rc = check_shards(g, handles, counts, root, &total);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  if (!data || !x || !out || !root_x || !root_out) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
-  const int ndev = (int)g->devices.size();
-  std::vector<hipStream_t> streams(ndev);
-  std::vector<std::vector<GatherPiece>> pieces(ndev);
-  long long first = 0;
-  // every shard's arguments are checked before the first shard is queued (an empty shard
-  // needs no arrays and is skipped)
-  for (int d = 0; d < ndev; d++) {
-    streams[d] = handles[d]->stream;
-    if (counts[d] == 0) continue;
-    if (!out[d]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null SolverOut pointer of a non-empty shard");
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
-      if (!data[d].base[i] && handles[d]->arr_len[i] > 0)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer of a non-empty shard");
-    for (int i = 0; i < 4; i++)
-      if (!x[d].base[i] && handles[d]->var_len[i] > 0)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer of a non-empty shard");
-  }
-  for (int i = 0; i < 4; i++)
-    if (!root_x->base[i] && handles[0]->var_len[i] > 0 && total > 0)
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer on the root");
-  for (int d = 0; d < ndev; d++) {
-    if (counts[d] > 0) {
-      rc = solution_pieces(handles[d]->var_len, x[d], *root_x, first, counts[d], &pieces[d]);
-      if (rc != FBSTAB_HIP_OK) return rc;
-      pieces[d].push_back({out[d], root_out + first, sizeof(fbstab_solver_out_t) * (size_t)counts[d]});
-    }
-    first += counts[d];
-  }
-  // every shard is queued on its device (nothing waits for another device), then the gather
-  for (int d = 0; d < ndev; d++) {
-    if (counts[d] == 0) continue;
-    rc = fbstab_hip_mpc_solve_batch(handles[d], counts[d], &data[d], &x[d], out[d],
-                                    FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC, nullptr);
-    if (rc != FBSTAB_HIP_OK) return drain_and_fail(g, streams, rc);
-  }
-  rc = shard_gather(g, root, pieces, streams);
-  if (rc != FBSTAB_HIP_OK) return drain_and_fail(g, streams, rc);
-  return sync_all(g, streams);
+  return solve_sharded(g, handles, counts, data, x, out, root, root_x, root_out, fbstab_hip_mpc_solve_batch);
 }
 
 int fbstab_hip_dense_solve_batch_sharded(fbstab_shard_group_t g, const fbstab_dense_handle_t* handles,
                                          const int* counts, const fbstab_dense_batch_t* data,
                                          const fbstab_var_batch_t* x, fbstab_solver_out_t* const* out, int root,
                                          const fbstab_var_batch_t* root_x, fbstab_solver_out_t* root_out) {
-  long long total = 0;
-  int rc = check_shards(g, handles, counts, root, &total);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  if (!data || !x || !out || !root_x || !root_out) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
-  const int ndev = (int)g->devices.size();
-  std::vector<hipStream_t> streams(ndev);
-  std::vector<std::vector<GatherPiece>> pieces(ndev);
-  long long first = 0;
-  // every shard's arguments are checked before the first shard is queued (an empty shard
-  // needs no arrays and is skipped)
-  for (int d = 0; d < ndev; d++) {
-    streams[d] = handles[d]->stream;
-    if (counts[d] == 0) continue;
-    if (!out[d]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null SolverOut pointer of a non-empty shard");
-    for (int i = 0; i < FBSTAB_DENSE_NARR; i++)
-      if (!data[d].base[i] && handles[d]->arr_len[i] > 0)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer of a non-empty shard");
-    for (int i = 0; i < 4; i++)
-      if (!x[d].base[i] && handles[d]->var_len[i] > 0)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer of a non-empty shard");
-  }
-  for (int i = 0; i < 4; i++)
-    if (!root_x->base[i] && handles[0]->var_len[i] > 0 && total > 0)
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer on the root");
-  for (int d = 0; d < ndev; d++) {
-    if (counts[d] > 0) {
-      rc = solution_pieces(handles[d]->var_len, x[d], *root_x, first, counts[d], &pieces[d]);
-      if (rc != FBSTAB_HIP_OK) return rc;
-      pieces[d].push_back({out[d], root_out + first, sizeof(fbstab_solver_out_t) * (size_t)counts[d]});
-    }
-    first += counts[d];
-  }
-  for (int d = 0; d < ndev; d++) {
-    if (counts[d] == 0) continue;
-    rc = fbstab_hip_dense_solve_batch(handles[d], counts[d], &data[d], &x[d], out[d],
-                                      FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC, nullptr);
-    if (rc != FBSTAB_HIP_OK) return drain_and_fail(g, streams, rc);
-  }
-  rc = shard_gather(g, root, pieces, streams);
-  if (rc != FBSTAB_HIP_OK) return drain_and_fail(g, streams, rc);
-  return sync_all(g, streams);
+  return solve_sharded(g, handles, counts, data, x, out, root, root_x, root_out, fbstab_hip_dense_solve_batch);
 }
 
 // BASELINE configs[4] over the GPUs of a node: every device sweeps its own trajectories

@@ -1,5 +1,8 @@
 """TEST INFRASTRUCTURE ONLY: the single-threaded host compilations of the device logic (hostsim.cc, adjoint.cc,
-dense_adjoint.cc, tangent.cc, against the <hip/hip_runtime.h> of shim/) and their ctypes wrappers."""
+dense_adjoint.cc, tangent.cc, against the <hip/hip_runtime.h> of shim/) and their ctypes wrappers.  Beside them,
+with no wrapper here: runtime_shim/ (a heap-backed <hip/hip_runtime.h>: the runtime calls, not the device environment)
+and stage_driver.cc, the stand-alone program over fbstab_amd/csrc/fb_host_stage.h that tests/test_host_stage.py
+builds and runs."""
 import ctypes as C
 import os
 import subprocess
