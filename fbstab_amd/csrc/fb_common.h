@@ -240,9 +240,17 @@ FB_DEV double sat(double x, double lo, double hi) {
 // sqrt(x) for x >= 0 inside the Fischer-Burmeister function, where half of the
 // passes' instructions used to be the IEEE sqrt sequence (two residual steps,
 // range scaling and special-case selects around v_rsq_f64): hardware seed, one
-// coupled Goldschmidt step and ONE residual correction - within an ulp - and no
+// coupled Goldschmidt step and ONE residual correction - within an ulp on +normal
+// arguments (tests/test_gpu_row_primitives.py holds it to that on the device) - and no
 // scaling (a^2 + b^2 has underflowed or overflowed long before the scaling would
-// matter).  Zero, infinity and NaN come back as they are (sqrt(0) = 0 exactly; an
+// matter).  NOT within an ulp on +denormal arguments, as this comment once claimed: the
+// residual e = x - g^2 is about x 2^-48, under 2^-1021 it is rounded to a multiple of
+// 2^-1074 and the correction is lost or halved.  What comes back then is a root with
+// the coupled step's accuracy, 3/2 eps^2 of the seed's eps <= 2^-23 at the worst (6.9 ulp
+// measured); scaling such arguments by 2^128 restores the ulp and was measured at -1.9 %
+// of the headline (LABNOTES, "Row primitives on the device"): not built, a sum of squares
+// that small sits 140 decades under every tolerance.
+// Zero, infinity and NaN come back as they are (sqrt(0) = 0 exactly; an
 // overflowed or NaN iterate then propagates as it does through the reference's sqrt and
 // ends where the reference's solve ends - in a failed factorisation, impl:263-267).
 // PRECONDITION x >= 0 (or NaN): every caller passes a sum of squares.  A negative argument

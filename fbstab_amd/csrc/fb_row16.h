@@ -438,10 +438,15 @@ FB_DEV void tri_inv_cols_solve(const double (&a)[N], double (&x)[N], double (&w)
 // the diagonal select that parks 1 / L[j][j] in lane j's a[j] (three instructions per pivot), the
 // broadcast that fetches it back (one), and - with the negation as the multiplier's source modifier - the
 // copies -lj, -x[k], -w[k] (two each).  Same operations on the same values in the same order per
-// accumulator: bitwise the results of chol_rows + tri_inv_cols_solve.  On return a[k] = L[r][k] for k < r
-// (the diagonal slot is NOT the reciprocal here: nothing reads it), x = column r of inv(L), w = row r of
-// B inv(L)'.  The next pivot's dependent chain is spread over three times as many independent
-// instructions as in chol_rows.
+// accumulator: bitwise the results of chol_rows + tri_inv_cols_solve.  On return x = column r of inv(L), w =
+// row r of B inv(L)'.  WITHOUT PARK a IS NOT THE FACTOR: the scaled column goes to the streams' source
+// register only, and a[k] keeps what it held when pivot k was taken - the UNSCALED entry
+// A[r][k] - sum_{m<k} L[r][m] L[k][m] = L[r][k] L[k][k] for k < r, the pivot before diag_add for k = r
+// (an earlier version of this comment promised a[k] = L[r][k]; no caller reads a after the pass, and
+// tests/test_gpu_row_primitives.py asserts what holds: a[k] times chol_rows' reciprocal 1 / L[k][k], rounded
+// once, IS chol_rows' L[r][k] bit for bit).  With PARK a is the factor exactly as chol_rows leaves it.
+// The next pivot's dependent chain is spread over three times as many independent instructions as in
+// chol_rows.
 // WITH_X / WITH_W: which of the two riders of the factorisation run (the inverse's column, the right-solve).
 // PARK: lane j's a[j] receives 1 / L[j][j] as chol_rows leaves it - for callers that go on to SUBSTITUTE with
 // the rows of the factor (the row-pair instances: subst_rows reads the reciprocal out of the row).
