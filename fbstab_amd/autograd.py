@@ -62,14 +62,18 @@ Jacobians of the solution map with respect to the initial state, as matrices:
     J = mpc_x0_sensitivity(solver, data, z, l, v)   # J["gain"] (B, nu, nx) = du0/dx0, J["dz"] (B, nx, nz), ...
 
 ONE call of fbstab_hip_mpc_x0_sensitivity_batch, one factorisation per QP for all nx columns.  The result is
-DETACHED: plain tensors that carry no graph.
+DETACHED: plain tensors that carry no graph.  The dense QP's counterpart, for the arrays that enter it as vectors:
+
+    J = dense_jacobian(solver, data, z, l, v, wrt="b")   # J["dz"] (B, nv, nz): row k = dz/db_k, J["dl"], J["dv"]
+
+ONE call of fbstab_hip_dense_jacobian_batch (``wrt``: "f", "h" or "b"), DETACHED like the other.
 """
 import torch
 
 from .hip_api import DENSE_ARR, MPC_SEQ
 
 __all__ = ["MpcSolveFunction", "solve_mpc", "DenseSolveFunction", "solve_dense", "ClosedLoopMpcFunction",
-           "closed_loop_mpc", "mpc_x0_sensitivity"]
+           "closed_loop_mpc", "mpc_x0_sensitivity", "dense_jacobian"]
 
 
 def _forward(names, ctx, solver, sigma, arrs):
@@ -177,6 +181,23 @@ def mpc_x0_sensitivity(solver, data, z, l, v, sigma: float = 0.0):
         assert all(a.shape[0] in (1, B) for a in arrs.values())
         res = solver.X0Sensitivity(arrs, det(z).contiguous(), det(l).contiguous(), det(v).contiguous(), sigma=sigma,
                                    want=("dz", "dl", "dv", "gain"))
+    return res
+
+
+def dense_jacobian(solver, data, z, l, v, wrt: str = "b", sigma: float = 0.0):
+    """The dense solutions' sensitivity to one of the arrays f, h, b at the returned points ``(z, l, v)``
+    (``FBstabDenseBatch.Jacobian``: one factorisation per QP, one right-hand side per entry of the array): a dict of
+    torch tensors on the inputs' device, ``dz (B, nrhs, nz)``, ``dl (B, nrhs, nl)``, ``dv (B, nrhs, nv)`` - row k the
+    tangent for the perturbation e_k of ``wrt`` - and ``status (B,)``.  The result is DETACHED: the inputs' graphs
+    are not read and none is recorded (differentiate through ``solve_dense`` for gradients of a loss)."""
+    with torch.no_grad():
+        det = lambda t: t.detach()
+        arrs = {k: det(data[k]) for k in DENSE_ARR}
+        B = z.shape[0]
+        arrs = {k: (a.reshape(1, -1) if a.dim() == 1 else a) for k, a in arrs.items()}
+        assert all(a.shape[0] in (1, B) for a in arrs.values())
+        res = solver.Jacobian(arrs, det(z).contiguous(), det(l).contiguous(), det(v).contiguous(), wrt=wrt,
+                              want=("dz", "dl", "dv"), sigma=sigma)
     return res
 
 

@@ -18,6 +18,7 @@
 #include "../../include/fbstab_hip.h"
 #include "fb_algorithm.h"
 #include "fb_dense.h"
+#include "fb_dense_kkt_multi.h"  // (kDenseKktSeeded; its kernels are fb_dense_kkt_multi.hip's)
 #include "fb_dense_wave.h"
 #include "fb_final_norms.h"
 #include "fb_grad_reduce.h"
@@ -558,6 +559,9 @@ FB_RECORD_INSTANCE_DECL(24, 8, 32, 2)
 // fbstab_mpc_kkt_multi_kernel (fb_kkt_multi.hip, a translation unit of its own): [wglobal != 0] the stage tile and the
 // work matrices in global scratch, or everything in LDS
 __attribute__((visibility("hidden"))) const void* fbstab_kkt_multi_kernel(int wglobal);
+// fbstab_dense_kkt_multi_kernel / fbstab_dense_wave_kkt_multi_kernel (fb_dense_kkt_multi.hip, a translation unit of its
+// own): the kernel beside adjoint kernel `which` of dense_resolve_kernels
+__attribute__((visibility("hidden"))) const void* fbstab_dense_kkt_multi_kernel_for(int which);
 #if defined(FB_SINGLE_TU)
 // (diagnostic builds with device-side counters: one translation unit, one g_stamps)
 #include "rec_12_4_20.hip"
@@ -566,6 +570,7 @@ __attribute__((visibility("hidden"))) const void* fbstab_kkt_multi_kernel(int wg
 #include "rec_24_8_16.hip"
 #include "rec_24_8_32.hip"
 #include "fb_kkt_multi.hip"
+#include "fb_dense_kkt_multi.hip"
 #endif
 namespace {
 const RecordInstance* record_instances(int* count) {
@@ -681,9 +686,10 @@ struct fbstab_dense_solver : SolverBase {
   bool wave = false;
   fbk::DenseWaveLayout wlay;
   fbk::DenseLayout trace_lay;  // the traced solve's own layout, where the handle's K fits the LDS
-  // What this handle launches (dense_resolve_kernels).  traced, probe: null where the layout does not serve them.
+  // What this handle launches (dense_resolve_kernels).  traced, probe: null where the layout does not serve them;
+  // kkt_multi: the many-right-hand-side kernel beside the adjoint kernel (fb_dense_kkt_multi.hip).
   struct {
-    DenseKernel solve, traced, probe, adjoint;
+    DenseKernel solve, traced, probe, adjoint, kkt_multi;
   } kern;
 };
 
@@ -717,6 +723,7 @@ void dense_resolve_kernels(fbstab_dense_solver* h) {
   h->kern.solve = {{solve[i], "", h->threads, h->lds_bytes}, h->wave, ks, lay};
   h->kern.probe = {{probe[i], "", h->threads, h->lds_bytes}, h->wave, ks, lay};
   h->kern.adjoint = {{adjoint[i], "", h->threads, h->lds_bytes}, h->wave, ks, lay};
+  h->kern.kkt_multi = {{fbstab_dense_kkt_multi_kernel_for(i), "", h->threads, h->lds_bytes}, h->wave, ks, lay};
   if (L.k_global) {
     h->kern.traced = {{traced[L.v_global ? 0 : 1], "", h->threads, h->lds_bytes}, false, true, &h->lay};
   } else {
@@ -1663,6 +1670,102 @@ int fbstab_hip_dense_tangent_batch(fbstab_dense_handle_t h, int batch, const fbs
   };
   return tangent_run(h, batch, data, x, ddata, sigma, dx, rhs, status, flags, stream,
                      reinterpret_cast<const void*>(fbstab_dense_tangent_rhs_kernel), launch_dir, dense_adjoint_launch);
+}
+
+// ---- many right-hand sides on one factorisation of the dense Newton matrix (include/fbstab_hip.h;
+// fb_dense_kkt_multi.h) ----------------------------------------------------------------------------------------
+namespace {
+// Both entry points behind what needs no handle.  seed == nullptr: the Jacobian mode (nrhs = the length of f, h or
+// b, the seeds generated in the kernel).  One launch of the kernel beside the handle's adjoint kernel, in the
+// handle's own scratch, around the staging the MPC calls use (MultiStage).
+int dense_kkt_multi_run(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
+                        const fbstab_var_batch_t* x, int nrhs, const fbstab_multi_var_batch_t* seed, int wrt,
+                        double sigma, const fbstab_multi_var_batch_t* step, int* status, int flags, void* stream) {
+  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  const long long* vlen = h->var_len;
+  if (!seed) {
+    if (wrt == FBSTAB_DENSE_h && vlen[1] == 0)
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "dense jacobian: wrt = h on a handle without equality constraints");
+    nrhs = (int)(wrt == FBSTAB_DENSE_f ? vlen[0] : wrt == FBSTAB_DENSE_h ? vlen[1] : vlen[2]);
+  } else {
+    wrt = fbk::kDenseKktSeeded;
+  }
+  for (size_t i = 0; i < h->arr_len.size(); i++)  // (nl == 0: the G and h slots are empty)
+    if (!data->base[i] && h->arr_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
+  for (int i = 0; i < 3; i++)
+    if (!x->base[i] && vlen[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
+  for (int i = 0; i < 3; i++) RC_TRY(h->check_var_stride(x->stride, i, batch));
+  // (nl == 0: the l slots are ignored, whatever they hold)
+  fbstab_multi_var_batch_t sd_in{}, st_in = *step;
+  if (seed) sd_in = *seed;
+  if (vlen[1] == 0) sd_in.base[1] = st_in.base[1] = nullptr;
+  if (seed) RC_TRY(check_multi_strides(&sd_in, vlen, batch, nrhs, true));
+  RC_TRY(check_multi_strides(&st_in, vlen, batch, nrhs, false));
+  RC_TRY(h->check_data_strides(data->stride, batch));
+  if (batch == 0) return FBSTAB_HIP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
+  fbstab_dense_batch_t a;
+  fbstab_var_batch_t v;
+  RC_TRY(h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride));
+  RC_TRY(h->stage_vars(x->base, x->stride, 3, batch, dev_ptrs, s, &v));
+  MultiStage sd, st;
+  RC_TRY(sd.open(seed ? &sd_in : nullptr, vlen, batch, nrhs, dev_ptrs, true, s));
+  RC_TRY(st.open(&st_in, vlen, batch, nrhs, dev_ptrs, false, s));
+  DevBuf d_status;
+  int* d_st = status;
+  const bool status_host = SolverBase::out_on_host(flags);
+  if (status_host) {
+    HIP_TRY(hipMalloc(&d_status.p, sizeof(int) * (size_t)batch));
+    d_st = static_cast<int*>(d_status.p);
+  }
+  double sig = sigma_or_default(sigma);
+  double alpha = h->opts.alpha;
+  // the queue word alone, as the dense adjoint: the words from kDenseFallbackSlot on still describe the last solve
+  HIP_TRY(hipMemsetAsync(h->counter, 0, sizeof(int) * kDenseFallbackSlot, s));
+  DenseKernel& e = h->kern.kkt_multi;
+  void* wave_args[] = {&h->wlay, &a, &v, &sd.k, &st.k, &d_st, &nrhs, &wrt, &sig, &alpha, &h->counter, &batch, &h->scratch};
+  void* args[] = {&h->lay, &a, &v, &sd.k, &st.k, &d_st, &nrhs, &wrt, &sig, &alpha, &h->counter, &batch, &h->scratch};
+  RC_TRY(h->begin_timed(s));
+  RC_TRY(launch_entry(e, fbk::dense_grid(batch, h->workgroups), e.wave ? wave_args : args, s));
+  RC_TRY(h->end_timed(s));
+  if (!dev_ptrs) RC_TRY(st.download(&st_in, vlen, batch, nrhs, s));
+  if (status_host) HIP_TRY(hipMemcpyAsync(status, d_st, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
+  if (status_host || !(flags & FBSTAB_HIP_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
+  return FBSTAB_HIP_OK;
+}
+}  // namespace
+
+int fbstab_hip_dense_kkt_solve_batch(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
+                                     const fbstab_var_batch_t* x, int nrhs, const fbstab_multi_var_batch_t* seed,
+                                     double sigma, const fbstab_multi_var_batch_t* step, int* status, int flags,
+                                     void* stream) {
+  // what needs no handle comes first
+  if (nrhs < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "dense kkt solve: fewer than one right-hand side");
+  if (!seed || !step) return fail(FBSTAB_HIP_ERR_ARGUMENT, "dense kkt solve: null seed or step block");
+  if (!data || !x || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
+  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null seed pointer (z)");
+  int rc = check_multi_strides(seed, nullptr, batch, nrhs, true);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  rc = check_multi_strides(step, nullptr, batch, nrhs, false);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  return dense_kkt_multi_run(h, batch, data, x, nrhs, seed, 0, sigma, step, status, flags, stream);
+}
+
+int fbstab_hip_dense_jacobian_batch(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
+                                    const fbstab_var_batch_t* x, int wrt, double sigma,
+                                    const fbstab_multi_var_batch_t* step, int* status, int flags, void* stream) {
+  // what needs no handle comes first (nrhs takes the handle: the step strides are checked behind it)
+  if (wrt != FBSTAB_DENSE_f && wrt != FBSTAB_DENSE_h && wrt != FBSTAB_DENSE_b)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "dense jacobian: wrt must be FBSTAB_DENSE_f, FBSTAB_DENSE_h or FBSTAB_DENSE_b");
+  if (!step) return fail(FBSTAB_HIP_ERR_ARGUMENT, "dense jacobian: null step block");
+  if (!data || !x || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
+  // (every Jacobian has at least one column: a stride that fails for one vector of length 1 fails for every handle)
+  int rc = check_multi_strides(step, nullptr, batch, 1, false);
+  if (rc != FBSTAB_HIP_OK) return rc;
+  return dense_kkt_multi_run(h, batch, data, x, 0, nullptr, wrt, sigma, step, status, flags, stream);
 }
 
 double fbstab_hip_dense_last_kernel_ms(fbstab_dense_handle_t h) { return h ? h->last_kernel_ms() : -1.0; }

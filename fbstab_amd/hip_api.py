@@ -200,6 +200,13 @@ def load_library() -> C.CDLL:
         lib.fbstab_hip_mpc_x0_sensitivity_batch.argtypes = [
             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_longlong,
             C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(lib, "fbstab_hip_dense_kkt_solve_batch"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_dense_kkt_solve_batch.argtypes = [
+            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+            C.c_int, C.c_void_p]
+        lib.fbstab_hip_dense_jacobian_batch.argtypes = [
+            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
+            C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -244,6 +251,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_receding_sweep_logged", "fbstab_hip_mpc_receding_sweep_adjoint",
     "fbstab_hip_mpc_sweep_adjoint_kernel_name", "fbstab_hip_mpc_receding_sweep_scenario",
     "fbstab_hip_mpc_kkt_solve_batch", "fbstab_hip_mpc_x0_sensitivity_batch",
+    "fbstab_hip_dense_kkt_solve_batch", "fbstab_hip_dense_jacobian_batch",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",
     "fbstab_hip_dense_solve_traced", "fbstab_hip_dense_adjoint_batch",
@@ -951,6 +959,65 @@ class FBstabDenseBatch(_SolverBase):
         inputs, dH through its symmetric part).  With ``nl == 0`` the G, h and l arrays are ``(batch, 0)``."""
         return _tangent(self, _DenseBatch(), _DenseBatch(), DENSE_ARR, self.arr_len, data, z, l, v, ddata, sigma,
                         rhs, stream, async_)
+
+    WRT = {"f": DENSE_ARR.index("f"), "h": DENSE_ARR.index("h"), "b": DENSE_ARR.index("b")}   # FBSTAB_DENSE_f, _h, _b
+
+    def _multi_call(self, data, z, l, v, K, seeds, wrt, sigma, want, stream, async_):
+        """fbstab_hip_dense_kkt_solve_batch (``seeds``: (gz, gl, gv)) or fbstab_hip_dense_jacobian_batch (None, with
+        ``wrt`` the array's index)."""
+        dev_flags = []
+        B = z.shape[0]
+        batch_struct = _DenseBatch()
+        _fill_block(batch_struct, DENSE_ARR, self.arr_len, data, B, dev_flags)
+        var_lens = (self.nz, self.nl, self.nv)
+        xb = _fill_vars((z, l, v), var_lens, B, dev_flags)
+        # (a vector of length 0 - the l slots with nl == 0 - travels as a NULL slot)
+        live = lambda arrs: tuple(None if n == 0 else a for a, n in zip(arrs, var_lens))
+        sb = _fill_multi(live(seeds), var_lens, B, K, dev_flags, optional=True) if seeds is not None else None
+        where, flags, stream = _placement(dev_flags, z, stream, async_)
+        status = where.zeros(z, B, "i4")
+        if where.on_dev:
+            zeros = lambda *shape: where.zeros(z, (B,) + shape)
+        else:
+            zeros = lambda *shape: np.zeros((max(B, 1),) + shape)[:B]   # (an empty batch keeps the strides of a row)
+        res = {k: zeros(K, n) for k, n in zip(("dz", "dl", "dv"), var_lens) if k in want}
+        ob = _fill_multi(live(tuple(res.get(k) for k in ("dz", "dl", "dv"))), var_lens, B, K, [], optional=True,
+                         first_required=False)
+        tail = (C.byref(ob), C.c_void_p(where.ptr(status)), flags, C.c_void_p(stream) if stream else None)
+        if seeds is not None:
+            rc = self._lib.fbstab_hip_dense_kkt_solve_batch(self._h, B, C.byref(batch_struct), C.byref(xb), K,
+                                                            C.byref(sb), C.c_double(sigma), *tail)
+        else:
+            rc = self._lib.fbstab_hip_dense_jacobian_batch(self._h, B, C.byref(batch_struct), C.byref(xb), wrt,
+                                                           C.c_double(sigma), *tail)
+        _check(self._lib, rc)
+        res["status"] = status
+        return res
+
+    def KktSolve(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0, stream: int = 0,
+                 async_: bool = False) -> Dict[str, object]:
+        """Several right-hand sides on ONE factorisation per QP (fbstab_hip_dense_kkt_solve_batch): ``gz`` of shape
+        ``(batch, K, nz)``, or ``(K, nz)`` for one block of K seeds shared by the batch; ``gl``, ``gv`` the same
+        (None: zero).  Returns a dict with ``dz (batch, K, nz)``, ``dl``, ``dv`` - slot k the step ``Adjoint(...,
+        adj=True)`` solves for seed k - and ``status`` (``(batch,)`` int32: 1 where the factorisation failed and
+        every right-hand side's step is zero).  All numpy or all torch CUDA tensors, like ``Adjoint``.
+        ``sigma <= 0``: 1e-8.  With ``nl == 0`` ``gl`` is None or ``(batch, K, 0)``."""
+        assert len(gz.shape) in (2, 3), gz.shape
+        return self._multi_call(data, z, l, v, gz.shape[-2], (gz, gl, gv), 0, sigma, ("dz", "dl", "dv"), stream,
+                                async_)
+
+    def Jacobian(self, data: Dict[str, object], z, l, v, wrt: str = "b", want: Sequence[str] = ("dz",),
+                 sigma: float = 0.0, stream: int = 0, async_: bool = False) -> Dict[str, object]:
+        """The solutions' sensitivity to one of the arrays ``f``, ``h``, ``b`` on ONE factorisation per QP
+        (fbstab_hip_dense_jacobian_batch): those of ``want`` among ``dz (batch, nrhs, nz)``, ``dl``, ``dv`` with
+        nrhs the array's length - row k what ``Tangent`` returns for the perturbation e_k of ``wrt`` - plus
+        ``status``.  The slots not in ``want`` are neither allocated nor written: ``want=("dz",)`` with ``wrt="b"``
+        is dz/db alone.  All numpy or all torch CUDA tensors, like ``Adjoint``."""
+        unknown = set(want) - {"dz", "dl", "dv"}
+        assert not unknown and len(want) > 0, want
+        assert wrt in self.WRT, wrt
+        K = {"f": self.nz, "h": self.nl, "b": self.nv}[wrt]
+        return self._multi_call(data, z, l, v, K, None, self.WRT[wrt], sigma, want, stream, async_)
 
 
 class ShardGroup:

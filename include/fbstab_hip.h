@@ -725,6 +725,49 @@ int fbstab_hip_dense_tangent_batch(fbstab_dense_handle_t handle, int batch, cons
                                    const fbstab_var_batch_t* x, const fbstab_dense_batch_t* ddata, double sigma,
                                    const fbstab_var_batch_t* dx, const fbstab_var_batch_t* rhs,
                                    int* status, int flags, void* stream);
+/* ---- many right-hand sides on the dense QP: factor V once, solve for nrhs of them ---------------------------------
+ * fbstab_hip_mpc_kkt_solve_batch and fbstab_hip_mpc_x0_sensitivity_batch for the dense QP.  The matrices a user of
+ * the layer asks for - dz/db, dz/df, dz/dh, or several loss seeds at the same solutions - cost one factorisation per
+ * column through the adjoint and the tangent above.  DenseCholeskySolver::Initialize is O(nz^2 nv + n^3) (A'Gamma A
+ * and the LDL' of the n = nz + nl matrix K), a Solve O(n^2 + nz nv); these two calls factor once per QP and run the
+ * vector part of the step once per right-hand side (fb_dense_kkt_multi.h).
+ *
+ * fbstab_hip_dense_kkt_solve_batch: slot k of `step` is the solution of V (dz, dl, dv) = (gz_k, -gl_k, -C gv_k) at
+ * x = xbar = the point, what fbstab_hip_dense_adjoint_batch(..., adj) solves for seed k.
+ *   nrhs, seed, step, their strides and `status`: those of fbstab_hip_mpc_kkt_solve_batch, word for word - vector k
+ *   of QP q of slot i at base[i] + q stride[i] + k rhs_stride[i]; NULL l and v seed slots are zero; a seed slot of
+ *   stride 0 is one block shared by the batch; NULL step slots are skipped; with batch > 1 or nrhs > 1
+ *   rhs_stride >= length and stride >= (nrhs - 1) rhs_stride + length, anything else FBSTAB_HIP_ERR_ARGUMENT; the
+ *   doubles between a QP's vectors are not written; nrhs < 1 is FBSTAB_HIP_ERR_ARGUMENT; status[q] = 1 where the
+ *   factorisation failed, and every right-hand side's step of that QP is then zero.
+ * fbstab_hip_dense_jacobian_batch: the right-hand sides are the unit seeds of one array, generated in the kernel with
+ * the tangent's signs (gz = -df, gl = dh, gv = db), so that row k of `step` is fbstab_hip_dense_tangent_batch's dx for
+ * the perturbation e_k of that array - bitwise what fbstab_hip_dense_kkt_solve_batch returns for those seeds:
+ *   wrt = FBSTAB_DENSE_f: nrhs = nz, gz = -e_k;   FBSTAB_DENSE_h: nrhs = nl, gl = e_k;   FBSTAB_DENSE_b: nrhs = nv,
+ *   gv = e_k.  A matrix index (H, G, A) or anything else is FBSTAB_HIP_ERR_ARGUMENT, and so is FBSTAB_DENSE_h on a
+ *   handle with nl == 0.
+ *   step: as above with that nrhs.  A caller who wants only dz/db (nv x nz per QP) passes NULL for the l and v
+ *   slots: the dv slot of wrt = b alone is nv x nv doubles per QP, which at large nv (the shapes whose iterate
+ *   vectors already live in global scratch) is most of the memory and the write traffic of the call.
+ * Kernels: fbstab_dense_wave_kkt_multi_kernel and fbstab_dense_kkt_multi_kernel<NT, KGLOBAL, VGLOBAL>, the instance
+ * beside the handle's adjoint kernel, picked by the same handle state, in the handle's own scratch.  On the
+ * four-wavefront instances right-hand side 0 is the adjoint's own arithmetic and the others re-run its vector part
+ * on the stored factors.  On the one-wavefront kernel (nz + nl <= 64) every right-hand side, number 0 included, takes
+ * one path behind one pivoted factorisation (whatever fbstab_hip_dense_set_factorisation says, pivoted_steps left
+ * alone): a seed's step depends neither on its slot nor on the other seeds, and is the adjoint kernel's to the
+ * same accuracy, not to the bit.
+ * sigma (<= 0 selects 1e-8), flags, streams, where `status` lives, nl == 0 (the l slots are ignored), batch == 0 (OK,
+ * nothing is queued) are those of fbstab_hip_dense_adjoint_batch; a host-pointer call stages the seed and step blocks
+ * packed, in allocations of the call, as the MPC calls do.  Validation: what needs no handle comes first - nrhs or
+ * wrt, the NULL blocks, a NULL z seed, strides no length could satisfy - then the handle and what takes its lengths;
+ * everything before any device call.  fbstab_hip_dense_last_kernel_ms reports the launch. */
+int fbstab_hip_dense_kkt_solve_batch(fbstab_dense_handle_t handle, int batch, const fbstab_dense_batch_t* data,
+                                     const fbstab_var_batch_t* x, int nrhs, const fbstab_multi_var_batch_t* seed,
+                                     double sigma, const fbstab_multi_var_batch_t* step, int* status, int flags,
+                                     void* stream);
+int fbstab_hip_dense_jacobian_batch(fbstab_dense_handle_t handle, int batch, const fbstab_dense_batch_t* data,
+                                    const fbstab_var_batch_t* x, int wrt, double sigma,
+                                    const fbstab_multi_var_batch_t* step, int* status, int flags, void* stream);
 double fbstab_hip_dense_last_kernel_ms(fbstab_dense_handle_t handle);
 int fbstab_hip_dense_query(fbstab_dense_handle_t handle, long long* scratch_bytes,
                            int* lds_bytes, int* workgroups, int* threads);
