@@ -1,0 +1,175 @@
+"""Condensed MPC: the states of an MPC QP eliminated on the device, the dense QP in the inputs solved by a
+``FBstabDenseBatch`` and the MPC point rebuilt (include/fbstab_hip.h: fbstab_hip_mpc_condense_batch,
+fbstab_hip_mpc_expand_batch).  The route for state-heavy shapes that no record kernel takes (nx above 24 with few
+inputs and a short horizon): after elimination the cost of a solve no longer depends on nx.  It is the caller's
+choice; ``FBstabMpcBatch`` never takes it by itself."""
+import ctypes as C
+from typing import Dict
+
+import numpy as np
+
+from . import hip_api
+from .hip_api import (DENSE_ARR, MPC_SEQ, FBstabDenseBatch, _DenseOutBatch, _MpcBatch, _VarBatch, _check,
+                      _fill_block, _is_torch)
+
+MATRICES, VECTORS, ALL = 1, 2, 3
+_WHAT = {"matrices": MATRICES, "vectors": VECTORS, "all": ALL}
+_MATRIX_SEQ = ("Q", "R", "S", "A", "B", "E", "L")
+
+
+def condensed_sizes(N: int, nx: int, nu: int, nc: int) -> Dict[str, int]:
+    """fbstab_hip_mpc_condensed_sizes: ``nz``, ``nv`` of the condensed QP and the ``lds_bytes`` one workgroup of
+    the condensing kernels needs; raises where the shape does not fit the LDS rule."""
+    lib = hip_api.load_library()
+    nz, nv, lds = C.c_int(), C.c_int(), C.c_longlong()
+    _check(lib, lib.fbstab_hip_mpc_condensed_sizes(N, nx, nu, nc, C.byref(nz), C.byref(nv), C.byref(lds)))
+    return dict(nz=nz.value, nv=nv.value, lds_bytes=lds.value)
+
+
+class CondensedMpc:
+    """``CondensedMpc(N, nx, nu, nc, max_batch)``: owns ``.dense``, a ``FBstabDenseBatch((N + 1) nu, 0, (N + 1) nc)``
+    (public: ``SetFactorisation``, ``UpdateOptions`` ... apply to it), and the condensed images ``H, f, A, b`` as
+    torch tensors on the device.  Inputs are torch tensors on ``device``; numpy inputs are uploaded through torch
+    by this class and the results copied back."""
+
+    def __init__(self, N: int, nx: int, nu: int, nc: int, max_batch: int = 1, device: int = 0):
+        self._lib = hip_api.load_library()
+        import torch
+        self._torch = torch
+        self.N, self.nx, self.nu, self.nc = N, nx, nu, nc
+        self.device, self.max_batch = device, max_batch
+        s = condensed_sizes(N, nx, nu, nc)
+        self.nzc, self.nv, self.lds_bytes = s["nz"], s["nv"], s["lds_bytes"]
+        self.nz, self.nl = (N + 1) * (nx + nu), (N + 1) * nx
+        self.seq_len = [(N + 1) * nx * nx, (N + 1) * nu * nu, (N + 1) * nu * nx, (N + 1) * nx, (N + 1) * nu,
+                        N * nx * nx, N * nx * nu, N * nx, (N + 1) * nc * nx, (N + 1) * nc * nu, (N + 1) * nc, nx]
+        self.dense = FBstabDenseBatch(self.nzc, 0, self.nv, max_batch, device)
+        self._dev = torch.device("cuda", device)
+        self._len = dict(H=self.nzc * self.nzc, f=self.nzc, A=self.nv * self.nzc, b=self.nv)
+        self._img = {}      # the condensed images of the last Condense: name -> (rows, len) tensor
+
+    def close(self):
+        self.dense.close()
+
+    # ---- placement -------------------------------------------------------------------------------------------
+    def _to_dev(self, a):
+        t = self._torch
+        if _is_torch(a):
+            assert a.is_cuda and a.device.index == self.device, "tensors live on the solver's device"
+            return a
+        return t.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self._dev)
+
+    def _data(self, data):
+        return {k: self._to_dev(data[k]) for k in MPC_SEQ}
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self._dev).cuda_stream
+
+    def _mpc_block(self, data, B):
+        blk, flags = _MpcBatch(), []
+        _fill_block(blk, MPC_SEQ, self.seq_len, data, B, flags)
+        assert all(flags)
+        return blk
+
+    def _images(self, names, rows_of):
+        for k in names:
+            rows = rows_of(k)
+            t = self._img.get(k)
+            if t is None or t.shape[0] != rows:
+                self._img[k] = self._torch.empty((rows, self._len[k]), dtype=self._torch.float64, device=self._dev)
+
+    # ---- the maps --------------------------------------------------------------------------------------------
+    def _condense(self, data, what):
+        B = data["x0"].shape[0]
+        assert 1 <= B <= self.max_batch, (B, self.max_batch)
+        w = _WHAT[what] if isinstance(what, str) else int(what)
+        shared = B > 1 and all(data[k].shape[0] == 1 for k in _MATRIX_SEQ)
+        names = [k for k, bit in (("H", MATRICES), ("f", VECTORS), ("A", MATRICES), ("b", VECTORS)) if w & bit]
+        self._images(names, lambda k: 1 if (shared and k in ("H", "A")) else B)
+        out = _DenseOutBatch()
+        for k in names:
+            t = self._img[k]
+            i = DENSE_ARR.index(k)
+            out.base[i], out.stride[i] = t.data_ptr(), (0 if (t.shape[0] == 1 and B > 1) else self._len[k])
+        blk = self._mpc_block(data, B)
+        s = self._stream()
+        _check(self._lib, self._lib.fbstab_hip_mpc_condense_batch(
+            self.N, self.nx, self.nu, self.nc, B, C.byref(blk), w, C.byref(out), self.device,
+            C.c_void_p(s) if s else None))
+        return B
+
+    def Condense(self, data: Dict[str, object], what="all") -> Dict[str, object]:
+        """Condenses ``data`` (the 12 sequences, ``(batch, len)`` or ``(1, len)`` for a shared one) and returns the
+        dict ``H, f, A, b`` of this object's image tensors (column-major images, ``(batch, len)``).  ``what``:
+        "all", "matrices" (H and A only) or "vectors" (f and b only: x0, q, r, c, d moved; the other two keep what
+        an earlier call wrote).  H and A are ONE ``(1, len)`` image where every matrix sequence of ``data`` is
+        shared.  Queued on torch's current stream."""
+        self._condense(self._data(data), what)
+        return {k: self._img[k] for k in ("H", "f", "A", "b") if k in self._img}
+
+    def _expand(self, data, U, v, y, z, l, vo, yo):
+        B = U.shape[0]
+        xc, x = _VarBatch(), _VarBatch()
+        for i, (a, n) in enumerate(((U, self.nzc), (None, 0), (v, self.nv), (y, self.nv))):
+            if a is not None:
+                assert a.shape == (B, n) and a.stride(1) == 1 and a.is_cuda
+                xc.base[i], xc.stride[i] = a.data_ptr(), (a.stride(0) if B > 1 else n)
+        for i, (a, n) in enumerate(((z, self.nz), (l, self.nl), (vo, self.nv), (yo, self.nv))):
+            if a is not None:
+                assert a.shape == (B, n) and (a.stride(1) == 1 or n <= 1) and a.is_cuda
+                x.base[i], x.stride[i] = a.data_ptr(), (a.stride(0) if B > 1 else n)
+        blk = self._mpc_block(data, B)
+        s = self._stream()
+        _check(self._lib, self._lib.fbstab_hip_mpc_expand_batch(
+            self.N, self.nx, self.nu, self.nc, B, C.byref(blk), C.byref(xc), C.byref(x), self.device,
+            C.c_void_p(s) if s else None))
+
+    def Expand(self, data: Dict[str, object], U, v, y):
+        """``(z, l, v, y)`` of the MPC QP from the condensed point ``(U, v, y)``: the states by the dynamics, the
+        costates from the stationarity condition, ``v`` and ``y`` copied.  Certificates of an infeasibility exit are
+        NOT translated.  Returns numpy arrays where ``U`` is one."""
+        host = not _is_torch(U)
+        t = self._torch
+        d = self._data(data)
+        U, v, y = (self._to_dev(a) for a in (U, v, y))
+        B = U.shape[0]
+        out = [t.empty((B, n), dtype=t.float64, device=self._dev) for n in (self.nz, self.nl, self.nv, self.nv)]
+        self._expand(d, U, v, y, *out)
+        return tuple(a.cpu().numpy() for a in out) if host else tuple(out)
+
+    def Solve(self, data: Dict[str, object], z, l, v, y, out=None, recondense="all"):
+        """The signature and in-place semantics of ``FBstabMpcBatch.Solve``: the guess is read from ``(z, l, v)`` -
+        U is the u blocks of z, v is v; l does not enter - and ``(z, l, v, y)`` are overwritten with the point of
+        the MPC QP.  ``recondense``: "all" condenses ``data`` first, "vectors" only f and b (only x0, q, r, c, d
+        moved since the last call), "none" solves on the images as they stand.  Returns ``out``, the DENSE solver's
+        records (a torch uint8 tensor ``(batch, 40)``; ``hip_api.out_to_numpy``; a numpy record array for numpy
+        arguments): exit flags and residuals are those of the condensed QP, and the Newton and proximal counts are
+        those of the condensed solve - not comparable with the counts of the MPC kernels."""
+        assert recondense in ("all", "vectors", "none"), recondense
+        t = self._torch
+        host = not _is_torch(z)
+        d = self._data(data)
+        zd, ld, vd, yd = (self._to_dev(a) for a in (z, l, v, y))
+        B = zd.shape[0]
+        if recondense != "none":
+            self._condense(d, recondense)
+        img = self._img
+        assert all(k in img for k in ("H", "f", "A", "b")), "Solve(recondense=...) before anything was condensed"
+        assert img["f"].shape[0] == B and img["H"].shape[0] in (1, B), "the images are those of another batch"
+        U = zd.view(B, self.N + 1, self.nx + self.nu)[:, :, self.nx:].reshape(B, self.nzc).contiguous()
+        l0 = t.empty((B, 0), dtype=t.float64, device=self._dev)
+        vc = vd.clone() if host or vd.stride(1) != 1 else vd
+        yc = t.empty((B, self.nv), dtype=t.float64, device=self._dev)
+        dout = None if (out is None or host) else out
+        dout = self.dense.Solve(dict(H=img["H"], f=img["f"], A=img["A"], b=img["b"]), U, l0, vc, yc, out=dout,
+                                async_=True)
+        self._expand(d, U, vc, yc, zd, ld, vd, yd)
+        if not host:
+            return dout
+        for dst, src in ((z, zd), (l, ld), (v, vd), (y, yd)):
+            dst[...] = src.cpu().numpy()
+        rec = hip_api.out_to_numpy(dout)
+        if out is not None:
+            out[...] = rec
+            return out
+        return rec

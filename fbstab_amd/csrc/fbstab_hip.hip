@@ -19,6 +19,7 @@
 #include "fb_algorithm.h"
 #include "fb_dense.h"
 #include "fb_dense_kkt_multi.h"  // (kDenseKktSeeded; its kernels are fb_dense_kkt_multi.hip's)
+#include "fb_condense.h"         // (CondenseLds; its kernels are fb_condense.hip's)
 #include "fb_dense_wave.h"
 #include "fb_final_norms.h"
 #include "fb_grad_reduce.h"
@@ -562,6 +563,9 @@ __attribute__((visibility("hidden"))) const void* fbstab_kkt_multi_kernel(int wg
 // fbstab_dense_kkt_multi_kernel / fbstab_dense_wave_kkt_multi_kernel (fb_dense_kkt_multi.hip, a translation unit of its
 // own): the kernel beside adjoint kernel `which` of dense_resolve_kernels
 __attribute__((visibility("hidden"))) const void* fbstab_dense_kkt_multi_kernel_for(int which);
+// The kernels of fbstab_hip_mpc_condense_batch / fbstab_hip_mpc_expand_batch (fb_condense.hip, a translation unit of
+// its own): which = 0 - H_c and A_c, 1 - f_c and b_c, 2 - expand; *threads: their workgroup size
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(int which, int* threads);
 #if defined(FB_SINGLE_TU)
 // (diagnostic builds with device-side counters: one translation unit, one g_stamps)
 #include "rec_12_4_20.hip"
@@ -571,6 +575,7 @@ __attribute__((visibility("hidden"))) const void* fbstab_dense_kkt_multi_kernel_
 #include "rec_24_8_32.hip"
 #include "fb_kkt_multi.hip"
 #include "fb_dense_kkt_multi.hip"
+#include "fb_condense.hip"
 #endif
 namespace {
 const RecordInstance* record_instances(int* count) {
@@ -1369,6 +1374,148 @@ int fbstab_hip_mpc_x0_sensitivity_batch(fbstab_mpc_handle_t h, int batch, const 
                                         int* status, int flags, void* stream) {
   // (nrhs = nx takes the handle: every stride is checked behind it)
   return kkt_multi_run(h, batch, data, x, 0, nullptr, sigma, step, gain, gain_stride, status, flags, stream);
+}
+
+// ---- condensing (include/fbstab_hip.h; fb_condense.h) -----------------------------------------------------------
+namespace {
+struct CondenseShape {
+  int N, nx, nu, nc;
+  long long len[FBSTAB_MPC_NSEQ];
+  long long nz, nv;
+};
+// What both calls check before any device call: the sizes, the batch, the data block and its strides.
+int condense_check(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data, CondenseShape* sh) {
+  if (N < 1 || nx < 1 || nu < 1 || nc < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: problem sizes must be positive");
+  if (batch < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: negative batch");
+  if (!data) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: null problem data block");
+  const long long n1 = N + 1;
+  const long long len[FBSTAB_MPC_NSEQ] = {n1 * nx * nx, n1 * nu * nu, n1 * nu * nx, n1 * nx, n1 * nu,
+                                          (long long)N * nx * nx, (long long)N * nx * nu, (long long)N * nx,
+                                          n1 * nc * nx, n1 * nc * nu, n1 * nc, nx};
+  *sh = CondenseShape{N, nx, nu, nc, {}, n1 * nu, n1 * nc};
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
+    sh->len[i] = len[i];
+    if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: null problem data pointer");
+    if (batch > 1 && data->stride[i] != 0 && data->stride[i] < len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: problem data stride smaller than the array length");
+  }
+  return FBSTAB_HIP_OK;
+}
+// ... and after it: the device, then the LDS rule.  *lds: the dynamic LDS bytes of a launch.
+int condense_device(const CondenseShape& sh, int device, fbk::CondenseLds* o, int* lds) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(FBSTAB_HIP_ERR_DEVICE, "condense: no HIP device");
+  if (device < 0 || device >= n) return fail(FBSTAB_HIP_ERR_DEVICE, "condense: no such device");
+  o->init(sh.N, sh.nx, sh.nu, sh.nc);
+  if ((long long)o->total * 8 > kLdsLimitBytes)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the stage images and dx/du of a horizon do not fit the 160 KiB LDS budget");
+  *lds = o->total * 8;
+  HIP_TRY(hipSetDevice(device));
+  return FBSTAB_HIP_OK;
+}
+int condense_launch(int which, int grid, int lds, void** args, hipStream_t s) {
+  int threads = 0;
+  const void* kern = fbstab_condense_kernel(which, &threads);
+  if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
+  HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(threads), args, (size_t)lds, s));
+  return FBSTAB_HIP_OK;
+}
+}  // namespace
+
+int fbstab_hip_mpc_condensed_sizes(int N, int nx, int nu, int nc, int* nz, int* nv, long long* lds_bytes) {
+  if (nz) *nz = 0;
+  if (nv) *nv = 0;
+  if (lds_bytes) *lds_bytes = 0;
+  if (N < 1 || nx < 1 || nu < 1 || nc < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: problem sizes must be positive");
+  if ((long long)(N + 1) * nu > 0x7fffffff || (long long)(N + 1) * nc > 0x7fffffff)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the condensed sizes do not fit an int");
+  if (nz) *nz = (N + 1) * nu;
+  if (nv) *nv = (N + 1) * nc;
+  fbk::CondenseLds o;
+  o.init(N, nx, nu, nc);
+  if ((long long)o.total * 8 > kLdsLimitBytes)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the stage images and dx/du of a horizon do not fit the 160 KiB LDS budget");
+  if (lds_bytes) *lds_bytes = (long long)o.total * 8;
+  return FBSTAB_HIP_OK;
+}
+
+int fbstab_hip_mpc_condense_batch(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data, int what,
+                                  const fbstab_dense_out_batch_t* dense, int device, void* stream) {
+  CondenseShape sh;
+  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
+  if (what < FBSTAB_CONDENSE_MATRICES || what > FBSTAB_CONDENSE_ALL)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: `what` must be MATRICES (1), VECTORS (2) or ALL (3)");
+  if (!dense) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: null output block");
+  const bool mats = (what & FBSTAB_CONDENSE_MATRICES) != 0, vecs = (what & FBSTAB_CONDENSE_VECTORS) != 0;
+  static const int kMatrixSeq[] = {FBSTAB_MPC_Q, FBSTAB_MPC_R, FBSTAB_MPC_S, FBSTAB_MPC_A,
+                                   FBSTAB_MPC_B, FBSTAB_MPC_E, FBSTAB_MPC_L};
+  bool shared_model = true;
+  for (int i : kMatrixSeq) shared_model = shared_model && data->stride[i] == 0;
+  const long long olen[FBSTAB_DENSE_NARR] = {sh.nz * sh.nz, sh.nz, 0, 0, sh.nv * sh.nz, sh.nv};
+  fbstab_dense_out_batch_t out = {};
+  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
+    const bool matrix = i == FBSTAB_DENSE_H || i == FBSTAB_DENSE_A;
+    if (matrix ? !mats : !vecs) continue;
+    if (!dense->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: null pointer in a selected output slot");
+    if (batch > 1 && dense->stride[i] < olen[i]) {
+      if (!matrix || dense->stride[i] != 0)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: output stride smaller than the array length");
+      if (!shared_model)
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: output stride 0 needs stride 0 on every one of Q, R, S, A, B, E, L");
+    }
+    out.base[i] = dense->base[i];
+    out.stride[i] = batch > 1 ? dense->stride[i] : olen[i];
+  }
+  if (batch == 0) return FBSTAB_HIP_OK;
+  fbk::CondenseLds o;
+  int lds = 0;
+  RC_TRY(condense_device(sh, device, &o, &lds));
+  hipStream_t s = (hipStream_t)stream;
+  fbstab_mpc_batch_t a = *data;
+  if (mats) {
+    // (one image of each for a batch that shares its model: QP 0 alone is launched)
+    const bool one = out.stride[FBSTAB_DENSE_H] == 0 && out.stride[FBSTAB_DENSE_A] == 0;
+    void* args[] = {&N, &nx, &nu, &nc, &o, &a, &out};
+    RC_TRY(condense_launch(0, (one ? 1 : batch) * (N + 1), lds, args, s));
+  }
+  if (vecs) {
+    void* args[] = {&N, &nx, &nu, &nc, &o, &a, &out};
+    RC_TRY(condense_launch(1, batch, lds, args, s));
+  }
+  return FBSTAB_HIP_OK;
+}
+
+int fbstab_hip_mpc_expand_batch(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+                                const fbstab_var_batch_t* xc, const fbstab_var_batch_t* x, int device, void* stream) {
+  CondenseShape sh;
+  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
+  if (!xc || !x) return fail(FBSTAB_HIP_ERR_ARGUMENT, "expand: null variable block");
+  if (!xc->base[0] || !xc->base[2]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "expand: null U or v pointer");
+  if (x->base[3] && !xc->base[3]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "expand: y is wanted and the condensed y is null");
+  const long long clen[4] = {sh.nz, 0, sh.nv, sh.nv};
+  const long long xlen[4] = {(long long)(N + 1) * (nx + nu), (long long)(N + 1) * nx, sh.nv, sh.nv};
+  fbstab_var_batch_t in = {}, outv = {};
+  for (int i = 0; i < 4; i++) {
+    if (i != 1 && xc->base[i]) {
+      if (batch > 1 && xc->stride[i] < clen[i])
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "expand: stride of the condensed point smaller than the vector length");
+      in.base[i] = xc->base[i];
+      in.stride[i] = batch > 1 ? xc->stride[i] : clen[i];
+    }
+    if (x->base[i]) {
+      if (batch > 1 && x->stride[i] < xlen[i])
+        return fail(FBSTAB_HIP_ERR_ARGUMENT, "expand: variable stride smaller than the vector length");
+      outv.base[i] = x->base[i];
+      outv.stride[i] = batch > 1 ? x->stride[i] : xlen[i];
+    }
+  }
+  if (batch == 0) return FBSTAB_HIP_OK;
+  fbk::CondenseLds o;
+  int lds = 0;
+  RC_TRY(condense_device(sh, device, &o, &lds));
+  fbstab_mpc_batch_t a = *data;
+  void* args[] = {&N, &nx, &nu, &nc, &o, &a, &in, &outv};
+  return condense_launch(2, batch, lds, args, (hipStream_t)stream);
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;

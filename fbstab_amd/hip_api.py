@@ -89,6 +89,11 @@ class _DenseGradBatch(C.Structure):
     _fields_ = [("base", C.c_void_p * 6), ("stride", C.c_longlong * 6)]
 
 
+class _DenseOutBatch(C.Structure):
+    """fbstab_dense_out_batch_t: where fbstab_hip_mpc_condense_batch writes H, f, A, b (the G and h slots unused)."""
+    _fields_ = [("base", C.c_void_p * 6), ("stride", C.c_longlong * 6)]
+
+
 class _MultiVarBatch(C.Structure):
     """fbstab_multi_var_batch_t: nrhs vectors (z, l, v) per QP."""
     _fields_ = [("base", C.c_void_p * 3), ("stride", C.c_longlong * 3), ("rhs_stride", C.c_longlong * 3)]
@@ -207,6 +212,12 @@ def load_library() -> C.CDLL:
         lib.fbstab_hip_dense_jacobian_batch.argtypes = [
             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
             C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_condense_batch"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_condensed_sizes.argtypes = [C.c_int] * 4 + [C.c_void_p] * 3
+        lib.fbstab_hip_mpc_condense_batch.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                      C.c_void_p]
+        lib.fbstab_hip_mpc_expand_batch.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                    C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -251,6 +262,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_receding_sweep_logged", "fbstab_hip_mpc_receding_sweep_adjoint",
     "fbstab_hip_mpc_sweep_adjoint_kernel_name", "fbstab_hip_mpc_receding_sweep_scenario",
     "fbstab_hip_mpc_kkt_solve_batch", "fbstab_hip_mpc_x0_sensitivity_batch",
+    "fbstab_hip_mpc_condensed_sizes", "fbstab_hip_mpc_condense_batch", "fbstab_hip_mpc_expand_batch",
     "fbstab_hip_dense_kkt_solve_batch", "fbstab_hip_dense_jacobian_batch",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",

@@ -544,6 +544,59 @@ int fbstab_hip_mpc_x0_sensitivity_batch(fbstab_mpc_handle_t handle, int batch, c
                                         const fbstab_multi_var_batch_t* step, double* gain, long long gain_stride,
                                         int* status, int flags, void* stream);
 
+/* ---- condensing: an MPC QP as a dense QP in its inputs, on the device --------------------------------------
+ * For state-heavy shapes (nx above what a record instance takes, few inputs, a short horizon) the states can be
+ * eliminated through the dynamics: with U = (u_0 .. u_N), u_i at [i nu, (i + 1) nu) - the u entries of z in their
+ * order - and z = T U + t (xbar_0 = x0, xbar_(i+1) = A_i xbar_i + c_i, x_i = xbar_i + sum_(j<i) A_(i-1) .. A_(j+1)
+ * B_j u_j) the MPC QP (H, f, G, h, A, b of mpc_data.cc) becomes the dense QP
+ *   H_c = T'HT (nz x nz, column-major)   f_c = T'(Ht + f)   A_c = AT (nv x nz, column-major)   b_c = b - At
+ * with nz = (N + 1) nu variables, no equalities and the nv = (N + 1) nc inequalities of the MPC QP in their order
+ * (v_c = v and y_c = b_c - A_c U = b - Az, entry for entry), which a dense handle (nz, 0, nv) solves.  The
+ * constant of the cost is dropped.  H_c is symmetric bit for bit: the blocks on and below the diagonal are
+ * computed (Q_i and R_i are taken as symmetric, the diagonal blocks read the lower triangle of R_i) and mirrored.
+ * The calls need no handle.  EVERY pointer is a DEVICE pointer (there is no host staging); the work is queued on
+ * `stream` (NULL: the null stream of `device`) and the call returns, as a solve does under FBSTAB_HIP_ASYNC.
+ *
+ * fbstab_hip_mpc_condensed_sizes: nz and nv, and the dynamic LDS one workgroup of the kernels needs,
+ *   lds_bytes = 8 (2 e(ldx nx) + e(ldx nu) + e(ldc nx) + e(ldu nx) + e(ldc nu) + e(ldu nu)
+ *                  + e(max((N + 2) e(ldx nu), (N + 1)(nx + nu + nc) + 2 nx + 8)))
+ *   with ldx = nx | 1, ldc = nc | 1, ldu = nu | 1 and e(n) = n rounded up to an even number:
+ *   the images of one stage, and X_k = dx/du_k of a horizon.  A shape that needs more than 160 KB is
+ *   FBSTAB_HIP_ERR_UNSUPPORTED (lds_bytes = 0), here and in the two calls below.  Output pointers may be NULL.
+ * fbstab_hip_mpc_condense_batch:
+ *   data:  as for fbstab_hip_mpc_solve_batch (all 12 sequences, a stride of 0 or at least the length).
+ *   what:  FBSTAB_CONDENSE_MATRICES writes H and A only, FBSTAB_CONDENSE_VECTORS f and b only - the receding-
+ *          horizon case, where only x0, q, r, c, d moved: a kernel of its own, O(N nx^2) per QP - and
+ *          FBSTAB_CONDENSE_ALL all four; what VECTORS writes is bitwise what ALL writes into f and b.
+ *   dense: the slots of H, f, A, b that `what` selects (the G and h slots are ignored: nl = 0; slots not
+ *          selected may be NULL and are not touched).  A stride is at least the array length, except that H
+ *          and A may have stride 0 when every one of Q, R, S, A, B, E, L has stride 0: ONE image is then
+ *          computed, for a batch that shares its model (fbstab_hip_dense_solve_batch takes such a block).
+ *          Anything else is FBSTAB_HIP_ERR_ARGUMENT.  The doubles between two QPs' images are not written.
+ * fbstab_hip_mpc_expand_batch: the point of the MPC QP from the one of the condensed QP.
+ *   xc:    base[0] = U, base[2] = v_c, base[3] = y_c (needed where x->base[3] is given); the l slot is unused.
+ *   x:     receives (z, l, v, y): x_0 = x0, x_(i+1) = A_i x_i + B_i u_i + c_i, z the interleaved (x_i, u_i),
+ *          v = v_c and y = y_c bit for bit, and the costates from the x rows of Hz + f + G'l + A'v = 0:
+ *          l_i = Q_i x_i + S_i'u_i + q_i + E_i'v_i + A_i'l_(i+1), i = N .. 0.  NULL slots are skipped.
+ *   The map is applied to whatever the dense solve returned.  It does NOT translate certificates: after an
+ *   infeasibility exit of the condensed solve, v and y are the dense solve's and z and l certify nothing.
+ * Both: sizes below 1, batch < 0, a NULL block or a NULL pointer that is needed, a stride outside the rules (with
+ * batch > 1) and `what` outside 1..3 are FBSTAB_HIP_ERR_ARGUMENT, all checked before any device call; then the
+ * device is checked (FBSTAB_HIP_ERR_DEVICE where there is none), then the LDS rule.  batch == 0 returns OK and
+ * queues nothing.  Deterministic: one thread owns each output entry and sums it in an order the shape alone
+ * fixes; a QP's bits do not depend on the batch it is in.  Not here: host pointers, sharded calls, partial
+ * condensing, the C++ facade. */
+enum fbstab_condense_what { FBSTAB_CONDENSE_MATRICES = 1, FBSTAB_CONDENSE_VECTORS = 2, FBSTAB_CONDENSE_ALL = 3 };
+typedef struct fbstab_dense_out_batch_t {
+  double* base[FBSTAB_DENSE_NARR];
+  long long stride[FBSTAB_DENSE_NARR];
+} fbstab_dense_out_batch_t;
+int fbstab_hip_mpc_condensed_sizes(int N, int nx, int nu, int nc, int* nz, int* nv, long long* lds_bytes);
+int fbstab_hip_mpc_condense_batch(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data, int what,
+                                  const fbstab_dense_out_batch_t* dense, int device, void* stream);
+int fbstab_hip_mpc_expand_batch(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+                                const fbstab_var_batch_t* xc, const fbstab_var_batch_t* x, int device, void* stream);
+
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);
 
