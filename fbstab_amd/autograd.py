@@ -67,13 +67,26 @@ DETACHED: plain tensors that carry no graph.  The dense QP's counterpart, for th
     J = dense_jacobian(solver, data, z, l, v, wrt="b")   # J["dz"] (B, nv, nz): row k = dz/db_k, J["dl"], J["dv"]
 
 ONE call of fbstab_hip_dense_jacobian_batch (``wrt``: "f", "h" or "b"), DETACHED like the other.
+
+The condensed route (``fbstab_amd.condense.CondensedMpc``, for state-heavy shapes) is differentiable too:
+
+    cm = CondensedMpc(N, nx, nu, nc, max_batch=B)
+    z, l, v, out = solve_condensed_mpc(cm, data)  # data as for solve_mpc; out: the DENSE solver's records
+
+Forward: ``cm.Solve`` from a zero guess, condensing ``data`` first.  Backward: ONE call of ``cm.Adjoint``
+(fbstab_hip_mpc_condensed_adjoint_batch: the seeds condensed, the dense adjoint, the step expanded and contracted)
+with the gradients torch asks for; QPs whose condensed solve did not end in SUCCESS, or whose factorisation failed,
+get zero gradients.  A shared ``(len,)`` or ``(1, len)`` input gets the torch sum over the batch of the per-QP
+gradients: the device-side reduced form is not served on this route, and neither are forward mode, Jacobians and
+x0 sensitivities.
 """
 import torch
 
 from .hip_api import DENSE_ARR, MPC_SEQ
 
 __all__ = ["MpcSolveFunction", "solve_mpc", "DenseSolveFunction", "solve_dense", "ClosedLoopMpcFunction",
-           "closed_loop_mpc", "mpc_x0_sensitivity", "dense_jacobian"]
+           "closed_loop_mpc", "mpc_x0_sensitivity", "dense_jacobian", "CondensedMpcSolveFunction",
+           "solve_condensed_mpc"]
 
 
 def _forward(names, ctx, solver, sigma, arrs):
@@ -300,3 +313,57 @@ def closed_loop_mpc(solver, data, A, B, steps: int, retire: bool = True, sigma: 
     if w is None and not shift:
         return ClosedLoopMpcFunction.apply(solver, steps, retire, sigma, A, B, *seqs)
     return ClosedLoopMpcFunction.apply(solver, steps, retire, sigma, A, B, *seqs, w, bool(shift))
+
+
+class CondensedMpcSolveFunction(torch.autograd.Function):
+    """apply(cm, sigma, *sequences in MPC_SEQ order) -> (z, l, v, out); ``cm``: a ``condense.CondensedMpc``."""
+
+    @staticmethod
+    def forward(ctx, cm, sigma, *seqs):
+        B = max(a.shape[0] if a.dim() == 2 else 1 for a in seqs)
+        ctx.shared = tuple(k for k, a in zip(MPC_SEQ, seqs) if B > 1 and (a.dim() == 1 or a.shape[0] == 1))
+        assert "x0" not in ctx.shared, "every QP has its own initial state"
+        ctx.shapes = {k: a.shape for k, a in zip(MPC_SEQ, seqs)}
+        data = {k: (a.detach().reshape(1, a.numel()) if (k in ctx.shared or a.dim() == 1) else a.detach()).contiguous()
+                for k, a in zip(MPC_SEQ, seqs)}
+        dev = data["Q"].device
+        mk = lambda n: torch.zeros((B, n), dtype=torch.float64, device=dev)
+        z, l, v, y = mk(cm.nz), mk(cm.nl), mk(cm.nv), mk(cm.nv)
+        out = cm.Solve(data, z, l, v, y, recondense="all")
+        ctx.cm, ctx.sigma, ctx.generation = cm, sigma, cm.generation
+        ctx.save_for_backward(*[data[k] for k in MPC_SEQ], z, l, v, out)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(out)
+        return z, l, v, out
+
+    @staticmethod
+    def backward(ctx, gz, gl, gv, gout):
+        want = [k for k, n in zip(MPC_SEQ, ctx.needs_input_grad[2:]) if n]
+        if not want:
+            return (None, None) + (None,) * len(MPC_SEQ)
+        saved = ctx.saved_tensors
+        data = dict(zip(MPC_SEQ, saved[:len(MPC_SEQ)]))
+        z, l, v, out = saved[len(MPC_SEQ):]
+        gz = torch.zeros_like(z) if gz is None else gz.contiguous()
+        gl, gv = (None if g is None else g.contiguous() for g in (gl, gv))
+        if ctx.cm.generation != ctx.generation:  # another Condense or Solve has replaced the forward's images
+            ctx.cm.Condense(data)
+        g = ctx.cm.Adjoint(data, z, l, v, gz, gl, gv, sigma=ctx.sigma, want=want)
+        eflag = out[:, 0:4].contiguous().view(torch.int32)[:, 0]  # SolverOut::eflag, on the device
+        keep = ((eflag == 0) & (g["status"] == 0))[:, None]
+        grads = []
+        for k in MPC_SEQ:
+            if k not in want:
+                grads.append(None)
+                continue
+            gk = torch.where(keep, g[k], torch.zeros_like(g[k]))
+            grads.append(gk.sum(0).reshape(ctx.shapes[k]) if k in ctx.shared else gk.reshape(ctx.shapes[k]))
+        return (None, None) + tuple(grads)
+
+
+def solve_condensed_mpc(cm, data, sigma: float = 0.0):
+    """Differentiable batched solve on the condensed route: ``cm`` a ``condense.CondensedMpc``, ``data`` as for
+    ``solve_mpc`` (``(len,)`` or ``(1, len)``: a parameter shared by the batch; its gradient is the sum over the
+    batch, formed in torch).  Returns ``(z, l, v, out)`` with ``out`` the dense solver's records; see the module
+    docstring."""
+    return CondensedMpcSolveFunction.apply(cm, sigma, *[data[k] for k in MPC_SEQ])

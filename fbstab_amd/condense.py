@@ -4,13 +4,13 @@ fbstab_hip_mpc_expand_batch).  The route for state-heavy shapes that no record k
 inputs and a short horizon): after elimination the cost of a solve no longer depends on nx.  It is the caller's
 choice; ``FBstabMpcBatch`` never takes it by itself."""
 import ctypes as C
-from typing import Dict
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 
 from . import hip_api
-from .hip_api import (DENSE_ARR, MPC_SEQ, FBstabDenseBatch, _DenseOutBatch, _MpcBatch, _VarBatch, _check,
-                      _fill_block, _is_torch)
+from .hip_api import (DENSE_ARR, MPC_SEQ, FBstabDenseBatch, _DenseBatch, _DenseOutBatch, _MpcBatch, _MpcGradBatch,
+                      _VarBatch, _check, _fill_block, _is_torch)
 
 MATRICES, VECTORS, ALL = 1, 2, 3
 _WHAT = {"matrices": MATRICES, "vectors": VECTORS, "all": ALL}
@@ -47,6 +47,7 @@ class CondensedMpc:
         self._dev = torch.device("cuda", device)
         self._len = dict(H=self.nzc * self.nzc, f=self.nzc, A=self.nv * self.nzc, b=self.nv)
         self._img = {}      # the condensed images of the last Condense: name -> (rows, len) tensor
+        self.generation = 0  # counts the calls that wrote into them (autograd: are the forward's images still there?)
 
     def close(self):
         self.dense.close()
@@ -93,6 +94,7 @@ class CondensedMpc:
             out.base[i], out.stride[i] = t.data_ptr(), (0 if (t.shape[0] == 1 and B > 1) else self._len[k])
         blk = self._mpc_block(data, B)
         s = self._stream()
+        self.generation += 1
         _check(self._lib, self._lib.fbstab_hip_mpc_condense_batch(
             self.N, self.nx, self.nu, self.nc, B, C.byref(blk), w, C.byref(out), self.device,
             C.c_void_p(s) if s else None))
@@ -136,6 +138,59 @@ class CondensedMpc:
         out = [t.empty((B, n), dtype=t.float64, device=self._dev) for n in (self.nz, self.nl, self.nv, self.nv)]
         self._expand(d, U, v, y, *out)
         return tuple(a.cpu().numpy() for a in out) if host else tuple(out)
+
+    def Adjoint(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0,
+                want: Optional[Sequence[str]] = None, adj: bool = False) -> Dict[str, object]:
+        """Reverse-mode derivative of the solution map on this route (fbstab_hip_mpc_condensed_adjoint_batch): what
+        ``FBstabMpcBatch.Adjoint`` returns - dL/d(sequence) for every name of ``want`` (default: all 12 of MPC_SEQ,
+        ``(batch, len)``), ``"status"`` (``(batch,)`` int32: 1 where the dense factorisation failed and the gradients
+        are zero) and, with ``adj=True``, ``"dz", "dl", "dv"`` - for the seeds ``gz, gl, gv`` = dL/d(z, l, v) at the
+        point ``(z, l, v)`` (``gl``/``gv`` None: zero).  It runs on the condensed images of the last ``Condense`` or
+        ``Solve``, which must be those of ``data``: the seeds are condensed, the dense handle's adjoint solves and
+        is refined once on its own residual, the step is expanded and contracted - six launches on torch's current
+        stream.  The step carries the O(sigma)
+        bias of a regularisation in the condensed variables (include/fbstab_hip.h); ``sigma <= 0``: 1e-8.  A shared
+        ``(1, len)`` sequence gets per-QP gradients like every other.  Returns numpy arrays where ``z`` is one."""
+        t = self._torch
+        host = not _is_torch(z)
+        want = tuple(MPC_SEQ if want is None else want)
+        assert not set(want) - set(MPC_SEQ), set(want) - set(MPC_SEQ)
+        d = self._data(data)
+        zd, ld, vd, gzd = (self._to_dev(a) for a in (z, l, v, gz))
+        gld, gvd = (None if a is None else self._to_dev(a) for a in (gl, gv))
+        B = zd.shape[0]
+        assert 1 <= B <= self.max_batch, (B, self.max_batch)
+        img = self._img
+        assert all(k in img for k in ("H", "f", "A", "b")), "Adjoint before anything was condensed"
+        assert img["f"].shape[0] == B and img["H"].shape[0] in (1, B), "the images are those of another batch"
+        var_lens = (self.nz, self.nl, self.nv)
+        xb = hip_api._fill_vars((zd, ld, vd), var_lens, B, [])
+        sb = hip_api._fill_vars((gzd, gld, gvd), var_lens, B, [], optional=True)
+        dense = _DenseBatch()
+        for k in ("H", "f", "A", "b"):
+            a, i = img[k], DENSE_ARR.index(k)
+            dense.base[i], dense.stride[i] = a.data_ptr(), (0 if (a.shape[0] == 1 and B > 1) else self._len[k])
+        mk = lambda shape, dtype=t.float64: t.zeros(shape, dtype=dtype, device=self._dev)
+        res = {k: mk((B, n)) for k, n in zip(MPC_SEQ, self.seq_len) if k in want}
+        grad = _MpcGradBatch()
+        _fill_block(grad, MPC_SEQ, self.seq_len, res, B, [], optional=True, shared=False)
+        ab = None
+        if adj:
+            for k, n in zip(("dz", "dl", "dv"), var_lens):
+                res[k] = mk((B, n))
+            ab = hip_api._fill_vars((res["dz"], res["dl"], res["dv"]), var_lens, B, [])
+        work = t.empty((B, 5 * self.nzc + 3 * self.nv), dtype=t.float64, device=self._dev)
+        status = mk((B,), t.int32)
+        blk = self._mpc_block(d, B)
+        s = self._stream()
+        _check(self._lib, self._lib.fbstab_hip_mpc_condensed_adjoint_batch(
+            self.dense._h, self.N, self.nx, self.nu, self.nc, B, C.byref(blk), C.byref(dense), C.byref(xb),
+            C.byref(sb), C.c_double(sigma), C.byref(grad), C.byref(ab) if ab is not None else None,
+            C.c_void_p(work.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(s) if s else None))
+        res["status"] = status
+        if host:
+            res = {k: a.cpu().numpy() for k, a in res.items()}
+        return res
 
     def Solve(self, data: Dict[str, object], z, l, v, y, out=None, recondense="all"):
         """The signature and in-place semantics of ``FBstabMpcBatch.Solve``: the guess is read from ``(z, l, v)`` -

@@ -20,6 +20,7 @@
 #include "fb_dense.h"
 #include "fb_dense_kkt_multi.h"  // (kDenseKktSeeded; its kernels are fb_dense_kkt_multi.hip's)
 #include "fb_condense.h"         // (CondenseLds; its kernels are fb_condense.hip's)
+#include "fb_condense_adjoint.h" // (CondenseAdjointWork; its kernels are fb_condense_adjoint.hip's)
 #include "fb_dense_wave.h"
 #include "fb_final_norms.h"
 #include "fb_grad_reduce.h"
@@ -566,6 +567,9 @@ __attribute__((visibility("hidden"))) const void* fbstab_dense_kkt_multi_kernel_
 // The kernels of fbstab_hip_mpc_condense_batch / fbstab_hip_mpc_expand_batch (fb_condense.hip, a translation unit of
 // its own): which = 0 - H_c and A_c, 1 - f_c and b_c, 2 - expand; *threads: their workgroup size
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(int which, int* threads);
+// The kernels of fbstab_hip_mpc_condensed_adjoint_batch (fb_condense_adjoint.hip, a translation unit of its own):
+// which = 0 - the seeds of the dense adjoint, 1 - the finish; *threads: their workgroup size
+__attribute__((visibility("hidden"))) const void* fbstab_condense_adjoint_kernel(int which, int* threads);
 #if defined(FB_SINGLE_TU)
 // (diagnostic builds with device-side counters: one translation unit, one g_stamps)
 #include "rec_12_4_20.hip"
@@ -576,6 +580,7 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(int whi
 #include "fb_kkt_multi.hip"
 #include "fb_dense_kkt_multi.hip"
 #include "fb_condense.hip"
+#include "fb_condense_adjoint.hip"
 #endif
 namespace {
 const RecordInstance* record_instances(int* count) {
@@ -1516,6 +1521,117 @@ int fbstab_hip_mpc_expand_batch(int N, int nx, int nu, int nc, int batch, const 
   fbstab_mpc_batch_t a = *data;
   void* args[] = {&N, &nx, &nu, &nc, &o, &a, &in, &outv};
   return condense_launch(2, batch, lds, args, (hipStream_t)stream);
+}
+
+// Reverse-mode derivative of the condensed route (include/fbstab_hip.h; fb_condense_adjoint.h): the seed kernel, the
+// dense handle's own adjoint launch on the condensed QP, one step of iterative refinement of that step (the residual
+// kernel, the dense adjoint again, the correction kernel), the finish kernel - six launches on one stream.
+int fbstab_hip_mpc_condensed_adjoint_batch(fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch,
+                                           const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                           const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
+                                           const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj,
+                                           double* work, int* status, void* stream) {
+  // what needs no handle comes first, in the order of fbstab_hip_mpc_condense_batch
+  CondenseShape sh;
+  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
+  if (!dense || !x || !seed || !grad || !work || !status)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: null argument");
+  const long long dlen[FBSTAB_DENSE_NARR] = {sh.nz * sh.nz, sh.nz, 0, 0, sh.nv * sh.nz, sh.nv};
+  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
+    const bool matrix = i == FBSTAB_DENSE_H || i == FBSTAB_DENSE_A;
+    if (!dense->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: null pointer in the condensed images");
+    if (batch > 1 && dense->stride[i] < dlen[i] && !(matrix && dense->stride[i] == 0))
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: stride of a condensed image smaller than the array length");
+  }
+  const long long xlen[3] = {(long long)(N + 1) * (nx + nu), (long long)(N + 1) * nx, sh.nv};
+  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: null seed pointer (z)");
+  for (int i = 0; i < 3; i++) {
+    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: null variable pointer");
+    if (batch > 1 && x->stride[i] < xlen[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: variable stride smaller than the vector length");
+    if (batch > 1 && seed->base[i] && seed->stride[i] < xlen[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: seed stride smaller than the vector length");
+    if (batch > 1 && adj && adj->base[i] && adj->stride[i] < xlen[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: adjoint stride smaller than the vector length");
+  }
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
+    if (batch > 1 && grad->base[i] && grad->stride[i] < sh.len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: gradient stride smaller than the array length");
+  // ... then the handle
+  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: null dense solver handle");
+  if (h->var_len[0] != sh.nz || h->var_len[1] != 0 || h->var_len[2] != sh.nv)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: the dense handle is not one of ((N + 1) nu, 0, (N + 1) nc)");
+  if (batch > h->max_batch)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: batch exceeds the max_batch the handle was created with");
+  if (batch == 0) return FBSTAB_HIP_OK;
+  fbk::CondenseLds o;
+  int lds = 0;
+  RC_TRY(condense_device(sh, h->device, &o, &lds));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  // the blocks as the kernels take them: with batch == 1 the strides are not read by the caller's rule
+  fbstab_mpc_batch_t a = *data;
+  fbstab_var_batch_t xv = {}, sd = {}, ad = {};
+  for (int i = 0; i < 3; i++) {
+    xv.base[i] = x->base[i]; xv.stride[i] = batch > 1 ? x->stride[i] : xlen[i];
+    sd.base[i] = seed->base[i]; sd.stride[i] = batch > 1 ? seed->stride[i] : xlen[i];
+    if (adj) { ad.base[i] = adj->base[i]; ad.stride[i] = batch > 1 ? adj->stride[i] : xlen[i]; }
+  }
+  fbstab_mpc_grad_batch_t g = *grad;
+  fbk::CondenseAdjointWork wk;
+  wk.U = work;
+  wk.gU = wk.U + sh.nz * batch;
+  wk.dU = wk.gU + sh.nz * batch;
+  wk.gv = wk.dU + sh.nz * batch;
+  wk.dv = wk.gv + sh.nv * batch;
+  wk.rU = wk.dv + sh.nv * batch;
+  wk.eU = wk.rU + sh.nz * batch;
+  wk.ev = wk.eU + sh.nz * batch;
+  auto launch = [&](int which, void** args, int bytes) -> int {
+    int threads = 0;
+    const void* kern = fbstab_condense_adjoint_kernel(which, &threads);
+    if (bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
+    HIP_TRY(hipLaunchKernel(kern, dim3(batch), dim3(threads), args, (size_t)bytes, s));
+    return FBSTAB_HIP_OK;
+  };
+  {
+    void* args[] = {&N, &nx, &nu, &nc, &o, &a, &xv, &sd, &wk};
+    RC_TRY(launch(0, args, lds));
+  }
+  {
+    // the dense adjoint at (U, v): no gradients of the condensed data.  First the seeds (gU, gv_c), adj = (dU, dv);
+    // then, behind the residual kernel, the seeds (rU, 0), adj = (eU, ev), which the correction kernel adds.
+    fbstab_var_batch_t xc = {}, sc = {}, ac = {};
+    xc.base[0] = wk.U; xc.stride[0] = sh.nz;
+    xc.base[2] = xv.base[2]; xc.stride[2] = xv.stride[2];
+    sc.base[0] = wk.gU; sc.stride[0] = sh.nz;
+    sc.base[2] = wk.gv; sc.stride[2] = sh.nv;
+    ac.base[0] = wk.dU; ac.stride[0] = sh.nz;
+    ac.base[2] = wk.dv; ac.stride[2] = sh.nv;
+    fbstab_dense_batch_t dc = {};
+    for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
+      dc.base[i] = dense->base[i];
+      dc.stride[i] = batch > 1 ? dense->stride[i] : dlen[i];
+    }
+    const fbstab_dense_grad_batch_t none = {};
+    const int flags = FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC;
+    RC_TRY(fbstab_hip_dense_adjoint_batch(h, batch, &dc, &xc, &sc, sigma, &none, &ac, status, flags, (void*)s));
+    int nzc = (int)sh.nz, nvc = (int)sh.nv;
+    const double *Hc = dc.base[FBSTAB_DENSE_H], *Ac = dc.base[FBSTAB_DENSE_A];
+    long long sH = dc.stride[FBSTAB_DENSE_H], sA = dc.stride[FBSTAB_DENSE_A];
+    double sg = sigma > 0.0 ? sigma : 1e-8;  // (the rule of fbstab_hip_dense_adjoint_batch)
+    void* rargs[] = {&nzc, &nvc, &Hc, &sH, &Ac, &sA, &sg, &wk};
+    RC_TRY(launch(2, rargs, 0));
+    sc.base[0] = wk.rU;
+    sc.base[2] = nullptr;
+    ac.base[0] = wk.eU;
+    ac.base[2] = wk.ev;
+    RC_TRY(fbstab_hip_dense_adjoint_batch(h, batch, &dc, &xc, &sc, sigma, &none, &ac, status, flags, (void*)s));
+    void* cargs[] = {&nzc, &nvc, &wk};
+    RC_TRY(launch(3, cargs, 0));
+  }
+  const int* st = status;
+  void* args[] = {&N, &nx, &nu, &nc, &o, &a, &xv, &sd, &wk, &g, &ad, &st};
+  return launch(1, args, lds);
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;

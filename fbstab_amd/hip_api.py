@@ -218,6 +218,9 @@ def load_library() -> C.CDLL:
                                                       C.c_void_p]
         lib.fbstab_hip_mpc_expand_batch.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                     C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_condensed_adjoint_batch"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_condensed_adjoint_batch.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [
+            C.c_double] + [C.c_void_p] * 5
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -263,6 +266,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_sweep_adjoint_kernel_name", "fbstab_hip_mpc_receding_sweep_scenario",
     "fbstab_hip_mpc_kkt_solve_batch", "fbstab_hip_mpc_x0_sensitivity_batch",
     "fbstab_hip_mpc_condensed_sizes", "fbstab_hip_mpc_condense_batch", "fbstab_hip_mpc_expand_batch",
+    "fbstab_hip_mpc_condensed_adjoint_batch",
     "fbstab_hip_dense_kkt_solve_batch", "fbstab_hip_dense_jacobian_batch",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",

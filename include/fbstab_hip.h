@@ -597,6 +597,58 @@ int fbstab_hip_mpc_condense_batch(int N, int nx, int nu, int nc, int batch, cons
 int fbstab_hip_mpc_expand_batch(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
                                 const fbstab_var_batch_t* xc, const fbstab_var_batch_t* x, int device, void* stream);
 
+/* ---- the derivative of the condensed route -------------------------------------------------------------------
+ * fbstab_hip_mpc_adjoint_batch for points that the condensed route returned, at the cost of that route: the adjoint
+ * system V (dz, dl, dv) = (gz, -gl, -C gv) is the QP's own optimality system with the same matrices and the vectors
+ *   q_i := -gz_x_i   r_i := -gz_u_i   x0 := -gl_0   c_i := -gl_(i+1)   d_i := -gv_i,
+ * so it condenses as the QP does.  Six launches on one stream:
+ *   1. fbstab_mpc_condense_seed_kernel: (f~, b~) = what FBSTAB_CONDENSE_VECTORS computes for those vectors; the
+ *      seeds of the dense adjoint are gU = -f~ and gv_c = b~.  It also writes U, the u blocks of z.
+ *   2. the launch of fbstab_hip_dense_adjoint_batch on the condensed QP (H_c, f_c, A_c, b_c) at (U, v) with the
+ *      seeds (gU, gv_c): (dU, dv).  (y_c = y and v_c = v entry for entry: C and mus are those of the MPC QP.)
+ *      Then one step of iterative refinement of that step: the dense adjoint eliminates dv into a matrix that
+ *      carries 1 / sigma on active rows, so the z rows of its system come back with a residual at eps / sigma.
+ *      fbstab_mpc_condensed_adjoint_residual_kernel computes rU = gU - (H_c dU + sigma dU + A_c'dv), the dense
+ *      adjoint runs again with the seeds (rU, 0), and fbstab_mpc_condensed_adjoint_correct_kernel adds its step
+ *      (eU, ev) to (dU, dv): what is left is eps / sigma of the correction.
+ *   3. fbstab_mpc_condensed_adjoint_finish_kernel: (dz, dl) = what fbstab_hip_mpc_expand_batch computes for those
+ *      vectors at (dU, dv) - dx_0 = -gl_0, dx_(i+1) = A_i dx_i + B_i du_i - gl_(i+1),
+ *      dl_i = Q_i dx_i + S_i'du_i - gz_x_i + E_i'dv_i + A_i'dl_(i+1) - and the contraction of
+ *      fbstab_hip_mpc_adjoint_batch: the gradients of the 12 sequences in the layout of fbstab_mpc_batch_t.
+ * The step satisfies the u rows and the v rows of the MPC system exactly; the x rows are off by sigma dx and the
+ * equality rows by sigma dl, so its residual is sigma ||(dx, dl)||_2: the derivative of the solution map with V
+ * regularised in the condensed variables, a bias of O(sigma) like that of fbstab_hip_mpc_adjoint_batch (the two
+ * agree to O(sigma), not bit for bit).
+ *   handle: the dense handle ((N + 1) nu, 0, (N + 1) nc) that solves the condensed QP; the work runs on its device.
+ *   data:   the MPC data, as for fbstab_hip_mpc_condense_batch.
+ *   dense:  the condensed images H_c, f_c, A_c, b_c (the G and h slots are ignored); H_c and A_c may have stride
+ *           0 for a batch that shares its model, as in the solve.
+ *   x:      the point (z, l, v) of the MPC QP (the y slot is not read).
+ *   seed:   (gz, gl, gv) in the MPC layout; the l and v slots may be NULL (zero).
+ *   sigma:  as for fbstab_hip_dense_adjoint_batch (<= 0 selects 1e-8).
+ *   grad:   one slot per sequence; a NULL slot is not computed, every other slot is written.
+ *   adj:    NULL, or (dz, dl, dv) (its NULL slots are skipped).
+ *   work:   caller-provided DEVICE memory, batch x (5 (N + 1) nu + 3 (N + 1) nc) doubles: U, gU, dU of
+ *           (N + 1) nu and gv_c, dv of (N + 1) nc doubles per QP, then the refinement's rU, eU of (N + 1) nu and ev
+ *           of (N + 1) nc, each one packed array of the batch in this order.  Nothing is allocated by the call.
+ *   status: per QP, DEVICE memory: the dense adjoint's, 0, or 1 where its factorisation failed (the gradients
+ *           and adj of that QP are zero).
+ * EVERY pointer is a DEVICE pointer; the work is queued on `stream` (NULL: the handle's stream) and the call
+ * returns.  All of these are FBSTAB_HIP_ERR_ARGUMENT and checked before any device call, what needs no handle
+ * first, in the order of fbstab_hip_mpc_condense_batch: sizes below 1, batch < 0, a NULL block or a NULL pointer
+ * that is needed, a stride below the length with batch > 1 (0 is allowed on the data and on H_c, A_c); then a NULL
+ * handle, a handle whose (nz, nl, nv) is not ((N + 1) nu, 0, (N + 1) nc), and a batch above its max_batch.  Then
+ * the device is checked, then the LDS rule of fbstab_hip_mpc_condensed_sizes (the seed and finish kernels run in that
+ * layout; the two kernels of the refinement step use no LDS).
+ * batch == 0 returns OK and queues nothing.  Deterministic as the condensing kernels are.  Not here: sums over the
+ * batch on the device (the _reduced form), forward mode, Jacobians and x0 sensitivities on this route, the C++
+ * facade, sharded calls, and certificates of infeasibility, which this route does not translate. */
+int fbstab_hip_mpc_condensed_adjoint_batch(fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch,
+                                           const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                           const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed,
+                                           double sigma, const fbstab_mpc_grad_batch_t* grad,
+                                           const fbstab_var_batch_t* adj, double* work, int* status, void* stream);
+
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);
 
