@@ -197,6 +197,22 @@ def mpc_x0_sensitivity(solver, data, z, l, v, sigma: float = 0.0):
     return res
 
 
+def condensed_mpc_x0_sensitivity(cm, data, z, l, v, sigma: float = 0.0):
+    """``mpc_x0_sensitivity`` on the condensed route (``CondensedMpc.X0Sensitivity`` of ``cm``, on the images its last
+    ``Condense`` / ``Solve`` / ``solve_condensed_mpc`` left, which must be those of ``data``): the same dict -
+    ``gain (B, nu, nx)``, ``dz (B, nx, nz)``, ``dl``, ``dv`` and ``status (B,)`` - with the O(sigma) bias of the
+    condensed chain.  The result is DETACHED: the inputs' graphs are not read and none is recorded."""
+    with torch.no_grad():
+        det = lambda t: t.detach()
+        arrs = {k: det(data[k]) for k in MPC_SEQ}
+        B = z.shape[0]
+        arrs = {k: (a.reshape(1, -1) if a.dim() == 1 else a) for k, a in arrs.items()}
+        assert all(a.shape[0] in (1, B) for a in arrs.values())
+        res = cm.X0Sensitivity(arrs, det(z).contiguous(), det(l).contiguous(), det(v).contiguous(), sigma=sigma,
+                               want=("dz", "dl", "dv", "gain"))
+    return res
+
+
 def dense_jacobian(solver, data, z, l, v, wrt: str = "b", sigma: float = 0.0):
     """The dense solutions' sensitivity to one of the arrays f, h, b at the returned points ``(z, l, v)``
     (``FBstabDenseBatch.Jacobian``: one factorisation per QP, one right-hand side per entry of the array): a dict of

@@ -26,6 +26,18 @@ def condensed_sizes(N: int, nx: int, nu: int, nc: int) -> Dict[str, int]:
     return dict(nz=nz.value, nv=nv.value, lds_bytes=lds.value)
 
 
+def condensed_multi_sizes(N: int, nx: int, nu: int, nc: int, nrhs: int, rhs_per_group: int = 0) -> Dict[str, int]:
+    """fbstab_hip_mpc_condensed_multi_sizes: what the many-right-hand-side calls of the condensed route use for
+    ``nrhs`` right-hand sides (``nx`` of them in x0 mode) - ``rhs_per_group`` (0 asks for the library's rule), the
+    ``lds_bytes`` of a workgroup and the ``work_doubles_per_qp`` of the caller's work array; raises where the LDS
+    rule refuses."""
+    lib = hip_api.load_library()
+    used, lds, work = C.c_int(), C.c_longlong(), C.c_longlong()
+    _check(lib, lib.fbstab_hip_mpc_condensed_multi_sizes(N, nx, nu, nc, nrhs, rhs_per_group, C.byref(used),
+                                                         C.byref(lds), C.byref(work)))
+    return dict(rhs_per_group=used.value, lds_bytes=lds.value, work_doubles_per_qp=work.value)
+
+
 class CondensedMpc:
     """``CondensedMpc(N, nx, nu, nc, max_batch)``: owns ``.dense``, a ``FBstabDenseBatch((N + 1) nu, 0, (N + 1) nc)``
     (public: ``SetFactorisation``, ``UpdateOptions`` ... apply to it), and the condensed images ``H, f, A, b`` as
@@ -191,6 +203,79 @@ class CondensedMpc:
         if host:
             res = {k: a.cpu().numpy() for k, a in res.items()}
         return res
+
+    def _multi_call(self, data, z, l, v, K, seeds, sigma, want, rhs_per_group):
+        """fbstab_hip_mpc_condensed_kkt_solve_batch (``seeds``: (gz, gl, gv)) or
+        fbstab_hip_mpc_condensed_x0_sensitivity_batch (None), on the images of the last ``Condense`` / ``Solve``."""
+        t = self._torch
+        host = not _is_torch(z)
+        d = self._data(data)
+        zd, ld, vd = (self._to_dev(a) for a in (z, l, v))
+        B = zd.shape[0]
+        assert 1 <= B <= self.max_batch, (B, self.max_batch)
+        img = self._img
+        assert all(k in img for k in ("H", "f", "A", "b")), "derivatives before anything was condensed"
+        assert img["f"].shape[0] == B and img["H"].shape[0] in (1, B), "the images are those of another batch"
+        var_lens = (self.nz, self.nl, self.nv)
+        xb = hip_api._fill_vars((zd, ld, vd), var_lens, B, [])
+        dense = _DenseBatch()
+        for k in ("H", "f", "A", "b"):
+            a, i = img[k], DENSE_ARR.index(k)
+            dense.base[i], dense.stride[i] = a.data_ptr(), (0 if (a.shape[0] == 1 and B > 1) else self._len[k])
+        sizes = condensed_multi_sizes(self.N, self.nx, self.nu, self.nc, K, rhs_per_group)
+        mk = lambda shape, dtype=t.float64: t.zeros(shape, dtype=dtype, device=self._dev)
+        res = {k: mk((B, K, n)) for k, n in zip(("dz", "dl", "dv"), var_lens) if k in want}
+        ob = hip_api._fill_multi(tuple(res.get(k) for k in ("dz", "dl", "dv")), var_lens, B, K, [], optional=True,
+                                 first_required=False) if res else None
+        work = t.empty((B, sizes["work_doubles_per_qp"]), dtype=t.float64, device=self._dev)
+        status = mk((B,), t.int32)
+        blk = self._mpc_block(d, B)
+        s = self._stream()
+        head = (self.dense._h, self.N, self.nx, self.nu, self.nc, B, C.byref(blk), C.byref(dense), C.byref(xb))
+        tail = (rhs_per_group, C.c_void_p(work.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(s) if s else None)
+        if seeds is not None:
+            sdev = tuple(None if a is None else self._to_dev(a) for a in seeds)
+            sb = hip_api._fill_multi(sdev, var_lens, B, K, [], optional=True)
+            rc = self._lib.fbstab_hip_mpc_condensed_kkt_solve_batch(*head, K, C.byref(sb), C.c_double(sigma),
+                                                                    C.byref(ob), *tail)
+        else:
+            gain = mk((B, self.nx, self.nu)) if "gain" in want else None   # (nu x nx column-major per QP)
+            rc = self._lib.fbstab_hip_mpc_condensed_x0_sensitivity_batch(
+                *head, C.c_double(sigma), C.byref(ob) if ob is not None else None,
+                C.c_void_p(gain.data_ptr()) if gain is not None else None, self.nu * self.nx, *tail)
+            if gain is not None:
+                res["gain"] = gain.transpose(1, 2)
+        _check(self._lib, rc)
+        res["status"] = status
+        if host:
+            res = {k: a.cpu().numpy() for k, a in res.items()}
+        return res
+
+    def KktSolve(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0,
+                 rhs_per_group: int = 0) -> Dict[str, object]:
+        """Several right-hand sides on ONE factorisation of the condensed K per QP
+        (fbstab_hip_mpc_condensed_kkt_solve_batch): the shapes and the returned dict of ``FBstabMpcBatch.KktSolve`` -
+        ``gz`` of shape ``(batch, K, nz)``, or ``(K, nz)`` for one block of K seeds shared by the batch, ``gl``, ``gv``
+        the same (None: zero); ``dz (batch, K, nz)``, ``dl``, ``dv`` and ``status`` - slot k what
+        ``Adjoint(..., adj=True)`` of THIS class solves for seed k (the condensed chain with its O(sigma) bias).  It
+        runs on the images of the last ``Condense`` / ``Solve``, as ``Adjoint`` does.  ``rhs_per_group``: right-hand
+        sides per workgroup of the kernels around the dense step, 0 for the library's rule; it changes speed, never
+        results.  Returns numpy arrays where ``z`` is one."""
+        assert len(gz.shape) in (2, 3), gz.shape
+        return self._multi_call(data, z, l, v, gz.shape[-2], (gz, gl, gv), sigma, ("dz", "dl", "dv"), rhs_per_group)
+
+    def X0Sensitivity(self, data: Dict[str, object], z, l, v, sigma: float = 0.0,
+                      want: Sequence[str] = ("dz", "gain"), rhs_per_group: int = 0) -> Dict[str, object]:
+        """The solutions' sensitivity to the initial state on ONE factorisation of the condensed K per QP
+        (fbstab_hip_mpc_condensed_x0_sensitivity_batch): those of ``want`` among ``dz (batch, nx, nz)``, ``dl``,
+        ``dv`` - row j the tangent for dx0 = e_j - and ``gain (batch, nu, nx)`` = du0/dx0, the local feedback law,
+        plus ``status``, as ``FBstabMpcBatch.X0Sensitivity`` returns them.  Slots not in ``want`` are neither
+        allocated nor written; with ``gain`` alone the finish kernel is not launched.  It runs on the images of the
+        last ``Condense`` / ``Solve``."""
+        unknown = set(want) - {"dz", "dl", "dv", "gain"}
+        assert not unknown, unknown
+        assert want, "nothing is wanted"
+        return self._multi_call(data, z, l, v, self.nx, None, sigma, tuple(want), rhs_per_group)
 
     def Solve(self, data: Dict[str, object], z, l, v, y, out=None, recondense="all"):
         """The signature and in-place semantics of ``FBstabMpcBatch.Solve``: the guess is read from ``(z, l, v)`` -

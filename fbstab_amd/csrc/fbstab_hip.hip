@@ -21,6 +21,7 @@
 #include "fb_dense_kkt_multi.h"  // (kDenseKktSeeded; its kernels are fb_dense_kkt_multi.hip's)
 #include "fb_condense.h"         // (CondenseLds; its kernels are fb_condense.hip's)
 #include "fb_condense_adjoint.h" // (CondenseAdjointWork; its kernels are fb_condense_adjoint.hip's)
+#include "fb_condense_multi.h"   // (CondenseMultiWork and the LDS rule; its kernels are fb_condense_multi.hip's)
 #include "fb_dense_wave.h"
 #include "fb_final_norms.h"
 #include "fb_grad_reduce.h"
@@ -570,6 +571,10 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(int whi
 // The kernels of fbstab_hip_mpc_condensed_adjoint_batch (fb_condense_adjoint.hip, a translation unit of its own):
 // which = 0 - the seeds of the dense adjoint, 1 - the finish; *threads: their workgroup size
 __attribute__((visibility("hidden"))) const void* fbstab_condense_adjoint_kernel(int which, int* threads);
+// The kernels of fbstab_hip_mpc_condensed_kkt_solve_batch / _x0_sensitivity_batch (fb_condense_multi.hip, a translation
+// unit of its own): which = 0 - the seeds, 1 - the finish, 2 - the residual, 3 - the correction; *threads: their
+// workgroup size
+__attribute__((visibility("hidden"))) const void* fbstab_condense_multi_kernel(int which, int* threads);
 #if defined(FB_SINGLE_TU)
 // (diagnostic builds with device-side counters: one translation unit, one g_stamps)
 #include "rec_12_4_20.hip"
@@ -581,6 +586,7 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_adjoint_kernel
 #include "fb_dense_kkt_multi.hip"
 #include "fb_condense.hip"
 #include "fb_condense_adjoint.hip"
+#include "fb_condense_multi.hip"
 #endif
 namespace {
 const RecordInstance* record_instances(int* count) {
@@ -1632,6 +1638,206 @@ int fbstab_hip_mpc_condensed_adjoint_batch(fbstab_dense_handle_t h, int N, int n
   const int* st = status;
   void* args[] = {&N, &nx, &nu, &nc, &o, &a, &xv, &sd, &wk, &g, &ad, &st};
   return launch(1, args, lds);
+}
+
+// ---- many right-hand sides on the condensed route (include/fbstab_hip.h; fb_condense_multi.h) -------------------
+namespace {
+struct CondenseMultiPlan {
+  fbk::CondenseLds o;
+  int R;
+  long long per, lds_bytes, work;
+};
+// What fbstab_hip_mpc_condensed_multi_sizes documents, behind its argument checks.
+int condense_multi_plan(int N, int nx, int nu, int nc, int nrhs, int rhs_per_group, CondenseMultiPlan* p) {
+  p->o.init(N, nx, nu, nc);
+  if (p->o.total == 0x3fffffff || (long long)p->o.carry * 8 > kLdsLimitBytes)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condensed multi: the stage images do not fit the 160 KiB LDS budget");
+  p->per = fbk::condense_multi_per(N, nx, nu, nc);
+  p->R = rhs_per_group > 0 ? (rhs_per_group < nrhs ? rhs_per_group : nrhs)
+                           : fbk::condense_multi_rule(nx, nrhs, p->o.carry, p->per);
+  p->lds_bytes = 8 * ((long long)p->o.carry + p->R * p->per);
+  if (p->lds_bytes > kLdsLimitBytes)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED,
+                "condensed multi: the stage images and rhs_per_group copies of a right-hand side's vectors do not fit the 160 KiB LDS budget");
+  const long long nzc = (long long)(N + 1) * nu, nv = (long long)(N + 1) * nc;
+  p->work = nzc + (long long)nrhs * (4 * nzc + 3 * nv);
+  return FBSTAB_HIP_OK;
+}
+
+// Both entry points behind their own first checks.  seed == nullptr: the x0 mode (nrhs = nx, the seeds generated in
+// the kernels); step may be null there, and gain (null, or nu x nx per QP) is served there only.
+int condensed_multi_run(fbstab_dense_handle_t h, const CondenseShape& sh, int batch, const fbstab_mpc_batch_t* data,
+                        const fbstab_dense_batch_t* dense, const fbstab_var_batch_t* x, int nrhs,
+                        const fbstab_multi_var_batch_t* seed, double sigma, const fbstab_multi_var_batch_t* step,
+                        double* gain, long long gain_stride, int rhs_per_group, double* work, int* status,
+                        void* stream) {
+  int N = sh.N, nx = sh.nx, nu = sh.nu, nc = sh.nc;
+  const bool x0_mode = seed == nullptr;
+  if (!dense || !x || !work || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: null argument");
+  const long long dlen[FBSTAB_DENSE_NARR] = {sh.nz * sh.nz, sh.nz, 0, 0, sh.nv * sh.nz, sh.nv};
+  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
+    const bool matrix = i == FBSTAB_DENSE_H || i == FBSTAB_DENSE_A;
+    if (!dense->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: null pointer in the condensed images");
+    if (batch > 1 && dense->stride[i] < dlen[i] && !(matrix && dense->stride[i] == 0))
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: stride of a condensed image smaller than the array length");
+  }
+  const long long xlen[3] = {(long long)(N + 1) * (nx + nu), (long long)(N + 1) * nx, sh.nv};
+  for (int i = 0; i < 3; i++) {
+    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: null variable pointer");
+    if (batch > 1 && x->stride[i] < xlen[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: variable stride smaller than the vector length");
+  }
+  if (seed) RC_TRY(check_multi_strides(seed, xlen, batch, nrhs, true));
+  if (step) RC_TRY(check_multi_strides(step, xlen, batch, nrhs, false));
+  const long long glen = (long long)nu * nx;
+  if (batch > 1 && gain && gain_stride < glen)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: gain stride smaller than nu x nx");
+  if (rhs_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: negative rhs_per_group");
+  // ... then the handle
+  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: null dense solver handle");
+  if (h->var_len[0] != sh.nz || h->var_len[1] != 0 || h->var_len[2] != sh.nv)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: the dense handle is not one of ((N + 1) nu, 0, (N + 1) nc)");
+  if (batch > h->max_batch)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: batch exceeds the max_batch the handle was created with");
+  if (batch == 0) return FBSTAB_HIP_OK;
+  // ... the device, then the LDS rule
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FBSTAB_HIP_ERR_DEVICE, "condensed multi: no HIP device");
+  if (h->device < 0 || h->device >= ndev) return fail(FBSTAB_HIP_ERR_DEVICE, "condensed multi: no such device");
+  CondenseMultiPlan pl;
+  RC_TRY(condense_multi_plan(N, nx, nu, nc, nrhs, rhs_per_group, &pl));
+  const long long groups = (nrhs + pl.R - 1) / pl.R;
+  if (groups * batch > 0x7fffffffLL)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: batch x groups of right-hand sides exceeds the grid limit");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  // the blocks as the kernels take them: with batch == 1 or nrhs == 1 the strides are not read by the caller's rule
+  fbstab_mpc_batch_t a = *data;
+  fbstab_var_batch_t xv = {};
+  fbstab_multi_var_batch_t sd = {}, st = {};
+  for (int i = 0; i < 3; i++) {
+    xv.base[i] = x->base[i]; xv.stride[i] = batch > 1 ? x->stride[i] : xlen[i];
+    for (int which = 0; which < 2; which++) {
+      const fbstab_multi_var_batch_t* b = which ? step : seed;
+      fbstab_multi_var_batch_t& k = which ? st : sd;
+      if (!b || !b->base[i]) continue;
+      k.base[i] = b->base[i];
+      k.rhs_stride[i] = nrhs > 1 ? b->rhs_stride[i] : xlen[i];
+      k.stride[i] = batch > 1 ? b->stride[i] : (nrhs - 1) * k.rhs_stride[i] + xlen[i];
+    }
+  }
+  const long long nb = (long long)nrhs * batch;
+  fbk::CondenseMultiWork wk;
+  wk.U = work;
+  wk.gU = wk.U + sh.nz * batch;
+  wk.dU = wk.gU + sh.nz * nb;
+  wk.rU = wk.dU + sh.nz * nb;
+  wk.eU = wk.rU + sh.nz * nb;
+  wk.gv = wk.eU + sh.nz * nb;
+  wk.dv = wk.gv + sh.nv * nb;
+  wk.ev = wk.dv + sh.nv * nb;
+  const int grid = (int)(groups * batch);
+  auto launch = [&](int which, void** args, long long bytes) -> int {
+    int threads = 0;
+    const void* kern = fbstab_condense_multi_kernel(which, &threads);
+    if (bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(threads), args, (size_t)bytes, s));
+    return FBSTAB_HIP_OK;
+  };
+  int R = pl.R, x0m = x0_mode ? 1 : 0;
+  long long per = pl.per;
+  {
+    void* args[] = {&N, &nx, &nu, &nc, &pl.o, &nrhs, &R, &per, &x0m, &a, &xv, &sd, &wk};
+    RC_TRY(launch(0, args, pl.lds_bytes));
+  }
+  {
+    // the dense multi-solve at (U, v): first the seeds (gU, gv_c), step = (dU, dv); then, behind the residual kernel,
+    // the seeds (rU, 0), step = (eU, ev), which the correction kernel adds.
+    fbstab_var_batch_t xc = {};
+    xc.base[0] = wk.U; xc.stride[0] = sh.nz;
+    xc.base[2] = xv.base[2]; xc.stride[2] = xv.stride[2];
+    fbstab_multi_var_batch_t sc = {}, ac = {};
+    sc.base[0] = wk.gU; sc.stride[0] = sh.nz * nrhs; sc.rhs_stride[0] = sh.nz;
+    sc.base[2] = wk.gv; sc.stride[2] = sh.nv * nrhs; sc.rhs_stride[2] = sh.nv;
+    ac.base[0] = wk.dU; ac.stride[0] = sh.nz * nrhs; ac.rhs_stride[0] = sh.nz;
+    ac.base[2] = wk.dv; ac.stride[2] = sh.nv * nrhs; ac.rhs_stride[2] = sh.nv;
+    fbstab_dense_batch_t dc = {};
+    for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
+      dc.base[i] = dense->base[i];
+      dc.stride[i] = batch > 1 ? dense->stride[i] : dlen[i];
+    }
+    const int flags = FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC;
+    RC_TRY(fbstab_hip_dense_kkt_solve_batch(h, batch, &dc, &xc, nrhs, &sc, sigma, &ac, status, flags, (void*)s));
+    int nzc = (int)sh.nz, nvc = (int)sh.nv;
+    const double *Hc = dc.base[FBSTAB_DENSE_H], *Ac = dc.base[FBSTAB_DENSE_A];
+    long long sH = dc.stride[FBSTAB_DENSE_H], sA = dc.stride[FBSTAB_DENSE_A];
+    double sg = sigma > 0.0 ? sigma : 1e-8;  // (the rule of fbstab_hip_dense_kkt_solve_batch)
+    void* rargs[] = {&nzc, &nvc, &nrhs, &R, &Hc, &sH, &Ac, &sA, &sg, &wk};
+    RC_TRY(launch(2, rargs, 0));
+    sc.base[0] = wk.rU;
+    sc.base[2] = nullptr;
+    ac.base[0] = wk.eU;
+    ac.base[2] = wk.ev;
+    RC_TRY(fbstab_hip_dense_kkt_solve_batch(h, batch, &dc, &xc, nrhs, &sc, sigma, &ac, status, flags, (void*)s));
+    long long gs = batch > 1 ? gain_stride : glen;
+    const int* stq = status;
+    void* cargs[] = {&nzc, &nvc, &nu, &nrhs, &R, &wk, &gain, &gs, &stq};
+    RC_TRY(launch(3, cargs, 0));
+  }
+  if (!step) return FBSTAB_HIP_OK;  // (gain alone: the finish launch is not queued)
+  const int* stq = status;
+  void* args[] = {&N, &nx, &nu, &nc, &pl.o, &nrhs, &R, &per, &x0m, &a, &sd, &wk, &st, &stq};
+  return launch(1, args, pl.lds_bytes);
+}
+}  // namespace
+
+int fbstab_hip_mpc_condensed_multi_sizes(int N, int nx, int nu, int nc, int nrhs, int rhs_per_group,
+                                         int* rhs_per_group_used, long long* lds_bytes,
+                                         long long* work_doubles_per_qp) {
+  if (rhs_per_group_used) *rhs_per_group_used = 0;
+  if (lds_bytes) *lds_bytes = 0;
+  if (work_doubles_per_qp) *work_doubles_per_qp = 0;
+  if (N < 1 || nx < 1 || nu < 1 || nc < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: problem sizes must be positive");
+  if (nrhs < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: fewer than one right-hand side");
+  if (rhs_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: negative rhs_per_group");
+  if ((long long)(N + 1) * nu > 0x7fffffff || (long long)(N + 1) * nc > 0x7fffffff)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the condensed sizes do not fit an int");
+  CondenseMultiPlan pl;
+  RC_TRY(condense_multi_plan(N, nx, nu, nc, nrhs, rhs_per_group, &pl));
+  if (rhs_per_group_used) *rhs_per_group_used = pl.R;
+  if (lds_bytes) *lds_bytes = pl.lds_bytes;
+  if (work_doubles_per_qp) *work_doubles_per_qp = pl.work;
+  return FBSTAB_HIP_OK;
+}
+
+int fbstab_hip_mpc_condensed_kkt_solve_batch(fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch,
+                                             const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                             const fbstab_var_batch_t* x, int nrhs,
+                                             const fbstab_multi_var_batch_t* seed, double sigma,
+                                             const fbstab_multi_var_batch_t* step, int rhs_per_group, double* work,
+                                             int* status, void* stream) {
+  // what needs no handle comes first, in the order of fbstab_hip_mpc_condense_batch, then that of
+  // fbstab_hip_mpc_kkt_solve_batch
+  CondenseShape sh;
+  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
+  if (nrhs < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed kkt solve: fewer than one right-hand side");
+  if (!seed || !step) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed kkt solve: null seed or step block");
+  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed kkt solve: null seed pointer (z)");
+  return condensed_multi_run(h, sh, batch, data, dense, x, nrhs, seed, sigma, step, nullptr, 0, rhs_per_group, work,
+                             status, stream);
+}
+
+int fbstab_hip_mpc_condensed_x0_sensitivity_batch(fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch,
+                                                  const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                                  const fbstab_var_batch_t* x, double sigma,
+                                                  const fbstab_multi_var_batch_t* step, double* gain,
+                                                  long long gain_stride, int rhs_per_group, double* work, int* status,
+                                                  void* stream) {
+  CondenseShape sh;
+  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
+  if (!step && !gain) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 sensitivity: both step and gain are null");
+  return condensed_multi_run(h, sh, batch, data, dense, x, nx, nullptr, sigma, step, gain, gain_stride, rhs_per_group,
+                             work, status, stream);
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;

@@ -221,6 +221,12 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "fbstab_hip_mpc_condensed_adjoint_batch"):  # (absent from an earlier build loaded for an A/B)
         lib.fbstab_hip_mpc_condensed_adjoint_batch.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [
             C.c_double] + [C.c_void_p] * 5
+    if hasattr(lib, "fbstab_hip_mpc_condensed_multi_sizes"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_condensed_multi_sizes.argtypes = [C.c_int] * 6 + [C.c_void_p] * 3
+        lib.fbstab_hip_mpc_condensed_kkt_solve_batch.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [
+            C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        lib.fbstab_hip_mpc_condensed_x0_sensitivity_batch.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [
+            C.c_double, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int] + [C.c_void_p] * 3
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -267,6 +273,8 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_kkt_solve_batch", "fbstab_hip_mpc_x0_sensitivity_batch",
     "fbstab_hip_mpc_condensed_sizes", "fbstab_hip_mpc_condense_batch", "fbstab_hip_mpc_expand_batch",
     "fbstab_hip_mpc_condensed_adjoint_batch",
+    "fbstab_hip_mpc_condensed_multi_sizes", "fbstab_hip_mpc_condensed_kkt_solve_batch",
+    "fbstab_hip_mpc_condensed_x0_sensitivity_batch",
     "fbstab_hip_dense_kkt_solve_batch", "fbstab_hip_dense_jacobian_batch",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",

@@ -585,7 +585,8 @@ int fbstab_hip_mpc_x0_sensitivity_batch(fbstab_mpc_handle_t handle, int batch, c
  * device is checked (FBSTAB_HIP_ERR_DEVICE where there is none), then the LDS rule.  batch == 0 returns OK and
  * queues nothing.  Deterministic: one thread owns each output entry and sums it in an order the shape alone
  * fixes; a QP's bits do not depend on the batch it is in.  Not here: host pointers, sharded calls, partial
- * condensing, the C++ facade. */
+ * condensing, the C++ facade.  Derivatives on this route: the two sections below (the adjoint; many right-hand
+ * sides and the x0 sensitivity). */
 enum fbstab_condense_what { FBSTAB_CONDENSE_MATRICES = 1, FBSTAB_CONDENSE_VECTORS = 2, FBSTAB_CONDENSE_ALL = 3 };
 typedef struct fbstab_dense_out_batch_t {
   double* base[FBSTAB_DENSE_NARR];
@@ -641,13 +642,84 @@ int fbstab_hip_mpc_expand_batch(int N, int nx, int nu, int nc, int batch, const 
  * the device is checked, then the LDS rule of fbstab_hip_mpc_condensed_sizes (the seed and finish kernels run in that
  * layout; the two kernels of the refinement step use no LDS).
  * batch == 0 returns OK and queues nothing.  Deterministic as the condensing kernels are.  Not here: sums over the
- * batch on the device (the _reduced form), forward mode, Jacobians and x0 sensitivities on this route, the C++
- * facade, sharded calls, and certificates of infeasibility, which this route does not translate. */
+ * batch on the device (the _reduced form), forward mode for general data directions (the x0 sensitivities and many
+ * seeds per factorisation are the section below), the C++ facade, sharded calls, and certificates of
+ * infeasibility, which this route does not translate. */
 int fbstab_hip_mpc_condensed_adjoint_batch(fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch,
                                            const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
                                            const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed,
                                            double sigma, const fbstab_mpc_grad_batch_t* grad,
                                            const fbstab_var_batch_t* adj, double* work, int* status, void* stream);
+
+/* ---- the condensed route: many right-hand sides per factorisation, and the x0 sensitivity ------------------------
+ * fbstab_hip_mpc_kkt_solve_batch and fbstab_hip_mpc_x0_sensitivity_batch for points that the condensed route
+ * returned, at the cost of that route.  The adjoint system condenses as the QP does (the section above), and
+ * fbstab_hip_dense_kkt_solve_batch factors the condensed K once for nrhs right-hand sides; these calls put the two
+ * maps around it for many right-hand sides at once (fb_condense_multi.h).  Six launches on one stream, every
+ * kernel of this section on the grid batch x ceil(nrhs / R), R right-hand sides per workgroup:
+ *   1. fbstab_mpc_condense_multi_seed_kernel: (gU, gv_c) of every right-hand side, the map of
+ *      fbstab_mpc_condense_seed_kernel.  A stage's images are staged into LDS once per workgroup and used by its R
+ *      right-hand sides; thread (row r, right-hand side k) owns entry r of right-hand side k.  The workgroup that
+ *      holds right-hand side 0 also writes U.
+ *   2. fbstab_hip_dense_kkt_solve_batch (device pointers, async, nrhs) on (gU, gv_c): (dU, dv);
+ *   3. fbstab_mpc_condense_multi_residual_kernel: rU = gU - (H_c dU + sigma dU + A_c'dv) per right-hand side;
+ *   4. the dense multi-solve again on (rU, 0): (eU, ev);
+ *   5. fbstab_mpc_condense_multi_correct_kernel: (dU, dv) += (eU, ev), and `gain` in x0 mode;
+ *   6. fbstab_mpc_condense_multi_finish_kernel: the sweeps of fbstab_mpc_condensed_adjoint_finish_kernel without
+ *      the contraction - dx_0 = -gl_0, dx_(i+1) = A_i dx_i + B_i du_i - gl_(i+1), then dl backwards - written into
+ *      the caller's step slots.  Not queued when the x0 call is asked for `gain` alone (step == NULL).
+ * The refinement step (3 - 5) is the adjoint's, for its reason: the dense multi-solve leaves eps / sigma on the z rows.
+ * fbstab_hip_mpc_condensed_kkt_solve_batch: slot k of `step` is what fbstab_hip_mpc_condensed_adjoint_batch(..., adj)
+ *   solves for seed k - the condensed chain with its O(sigma) bias, not the flat-vector system.  A right-hand side's
+ *   bits depend on its seed, the QP's data and the shape alone: not on its slot, the other seeds, nrhs, the batch or
+ *   rhs_per_group.
+ * fbstab_hip_mpc_condensed_x0_sensitivity_batch: nrhs = nx, right-hand side j the tangent's for dx0 = e_j (gz = 0,
+ *   gl = -e_j in the l_0 block, gv = 0: the signs of fbstab_hip_mpc_x0_sensitivity_batch), generated in the kernels:
+ *   bitwise what the kkt-solve entry returns for those explicit seeds.
+ *   step:  NULL, or nrhs = nx vectors per QP; NULL slots are skipped.  step and gain both NULL: ARGUMENT.
+ *   gain:  NULL, or nu x nx doubles per QP, column-major (QP q at gain + q gain_stride, gain_stride >= nu nx when
+ *          batch > 1): du0/dx0, the u_0 rows of dU, bitwise the u_0 rows of the dz columns.
+ * nrhs, seed, step, their strides (stride, rhs_stride, NULL l / v seed slots, a seed slot of stride 0 shared by the
+ * batch, the untouched doubles between vectors) and gain's layout: those of fbstab_hip_mpc_kkt_solve_batch /
+ * _x0_sensitivity_batch, word for word, with the lengths of the MPC QP ((N + 1)(nx + nu), (N + 1) nx, (N + 1) nc).
+ * handle, data, dense, x, sigma, status (1: every slot of every right-hand side of that QP is zero), DEVICE
+ * pointers only, the stream, batch == 0: those of fbstab_hip_mpc_condensed_adjoint_batch.
+ *   rhs_per_group: R.  0: the library's rule, R = clamp(256 / nx, 1, nrhs), lowered until lds_bytes <= 80 KB (two
+ *          workgroups per CU).  A value above nrhs is nrhs.  Below 0: ARGUMENT.  R changes speed, never results.
+ *   work:  caller-provided DEVICE memory, batch x work_doubles_per_qp doubles: U of (N + 1) nu doubles per QP, then
+ *          gU, dU, rU, eU of nrhs (N + 1) nu and gv_c, dv, ev of nrhs (N + 1) nc, each one packed [batch][nrhs][n]
+ *          array in this order.  Nothing is allocated by the call.
+ * fbstab_hip_mpc_condensed_multi_sizes: what the calls will use, with e(n) = n rounded up to even:
+ *   per       = max(e((N + 1) nx) + 2 e(nx),  e((N + 1)(nx + nu)) + e((N + 1) nc) + 2 e(nx))   (one right-hand side's
+ *               vectors in the seed and in the finish kernel)
+ *   window    = 2 e(ldx nx) + e(ldx nu) + e(ldc nx) + e(ldu nx) + e(ldc nu) + e(ldu nu), ldx = nx | 1, ldc = nc | 1,
+ *               ldu = nu | 1: the stage window of fbstab_hip_mpc_condensed_sizes
+ *   lds_bytes = 8 (window + rhs_per_group_used per)
+ *   work_doubles_per_qp = (N + 1) nu + nrhs (4 (N + 1) nu + 3 (N + 1) nc)
+ *   Sizes or nrhs below 1 and rhs_per_group below 0 are FBSTAB_HIP_ERR_ARGUMENT; lds_bytes above 160 KB is
+ *   FBSTAB_HIP_ERR_UNSUPPORTED (outputs 0).  Output pointers may be NULL.  Pass nrhs = nx for the x0 call.
+ * Validation of the two calls, everything before any device call: what needs no handle first - the sizes, the batch
+ * and the data block as fbstab_hip_mpc_condense_batch; nrhs, the NULL blocks and a NULL z seed (kkt solve), step and
+ * gain both NULL (x0); NULL dense, x, work, status; the condensed images; x; the seed and step strides; gain_stride;
+ * rhs_per_group < 0 - then the handle (NULL, not ((N + 1) nu, 0, (N + 1) nc), batch above max_batch), then the
+ * device, then the LDS rule (FBSTAB_HIP_ERR_UNSUPPORTED).
+ * Not here: forward mode for general data directions, the device-side reduced form, a dense factor kept between
+ * the two dense launches, the C++ facade, sharded calls, certificates of infeasibility. */
+int fbstab_hip_mpc_condensed_multi_sizes(int N, int nx, int nu, int nc, int nrhs, int rhs_per_group,
+                                         int* rhs_per_group_used, long long* lds_bytes,
+                                         long long* work_doubles_per_qp);
+int fbstab_hip_mpc_condensed_kkt_solve_batch(fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch,
+                                             const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                             const fbstab_var_batch_t* x, int nrhs,
+                                             const fbstab_multi_var_batch_t* seed, double sigma,
+                                             const fbstab_multi_var_batch_t* step, int rhs_per_group, double* work,
+                                             int* status, void* stream);
+int fbstab_hip_mpc_condensed_x0_sensitivity_batch(fbstab_dense_handle_t handle, int N, int nx, int nu, int nc,
+                                                  int batch, const fbstab_mpc_batch_t* data,
+                                                  const fbstab_dense_batch_t* dense, const fbstab_var_batch_t* x,
+                                                  double sigma, const fbstab_multi_var_batch_t* step, double* gain,
+                                                  long long gain_stride, int rhs_per_group, double* work, int* status,
+                                                  void* stream);
 
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);
