@@ -9,12 +9,15 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import hip_api
-from .hip_api import (DENSE_ARR, MPC_SEQ, FBstabDenseBatch, _DenseBatch, _DenseOutBatch, _MpcBatch, _MpcGradBatch,
-                      _VarBatch, _check, _fill_block, _is_torch)
+from .hip_api import (DENSE_ARR, MPC_SEQ, FBstabDenseBatch, _CondensedMap, _CondensedSweepLog, _DenseBatch,
+                      _DenseOutBatch, _MpcBatch, _MpcGradBatch, _Plant, _SweepScenario, _VarBatch, _check,
+                      _fill_block, _is_torch)
 
 MATRICES, VECTORS, ALL = 1, 2, 3
 _WHAT = {"matrices": MATRICES, "vectors": VECTORS, "all": ALL}
 _MATRIX_SEQ = ("Q", "R", "S", "A", "B", "E", "L")
+AFFINE, RECONDENSE = 0, 1
+_SWEEP_MODE = {"affine": AFFINE, "recondense": RECONDENSE}
 
 
 def condensed_sizes(N: int, nx: int, nu: int, nc: int) -> Dict[str, int]:
@@ -36,6 +39,19 @@ def condensed_multi_sizes(N: int, nx: int, nu: int, nc: int, nrhs: int, rhs_per_
     _check(lib, lib.fbstab_hip_mpc_condensed_multi_sizes(N, nx, nu, nc, nrhs, rhs_per_group, C.byref(used),
                                                          C.byref(lds), C.byref(work)))
     return dict(rhs_per_group=used.value, lds_bytes=lds.value, work_doubles_per_qp=work.value)
+
+
+def condensed_sweep_sizes(N: int, nx: int, nu: int, nc: int, traj_per_group: int = 0,
+                          shared_map: bool = True) -> Dict[str, int]:
+    """fbstab_hip_mpc_condensed_sweep_sizes: what the closed-loop sweep of the condensed route uses -
+    ``traj_per_group`` (0 asks for the library's rule), the ``lds_bytes`` of a workgroup of the step kernel (with
+    ``shared_map`` the one image M of a shared model is staged into LDS) and the ``work_doubles_per_traj`` of the
+    caller's work array; raises where the LDS rule refuses."""
+    lib = hip_api.load_library()
+    used, lds, work = C.c_int(), C.c_longlong(), C.c_longlong()
+    _check(lib, lib.fbstab_hip_mpc_condensed_sweep_sizes(N, nx, nu, nc, traj_per_group, 1 if shared_map else 0,
+                                                         C.byref(used), C.byref(lds), C.byref(work)))
+    return dict(traj_per_group=used.value, lds_bytes=lds.value, work_doubles_per_traj=work.value)
 
 
 class CondensedMpc:
@@ -276,6 +292,126 @@ class CondensedMpc:
         assert not unknown, unknown
         assert want, "nothing is wanted"
         return self._multi_call(data, z, l, v, self.nx, None, sigma, tuple(want), rhs_per_group)
+
+    def X0Map(self, data: Dict[str, object]) -> Dict[str, object]:
+        """The affine dependence of the condensed vectors on x0 (fbstab_hip_mpc_condensed_x0_map_batch): ``M``, the
+        images [F; G] as ``(batch, ne * nx)`` - ne = nz_c + nv rows, nx columns, column-major; ONE ``(1, ne * nx)``
+        image where every matrix sequence of ``data`` is shared - and ``f0 = f_c(0)``, ``b0 = b_c(0)``, ``(batch, n)``:
+        f_c(x) = f0 + F x, b_c(x) = b0 + G x for this ``data`` with any initial state x.  Torch tensors on the
+        device; queued on torch's current stream.  The images of the last ``Condense`` are not touched."""
+        return self._x0_map(self._data(data))
+
+    def _x0_map(self, d):
+        t = self._torch
+        B = d["x0"].shape[0]
+        assert 1 <= B <= self.max_batch, (B, self.max_batch)
+        ne = self.nzc + self.nv
+        shared = B > 1 and all(d[k].shape[0] == 1 for k in _MATRIX_SEQ)
+        M = t.empty((1 if shared else B, ne * self.nx), dtype=t.float64, device=self._dev)
+        f0 = t.empty((B, self.nzc), dtype=t.float64, device=self._dev)
+        b0 = t.empty((B, self.nv), dtype=t.float64, device=self._dev)
+        s = self._stream()
+        sp = C.c_void_p(s) if s else None
+        blk = self._mpc_block(d, B)
+        _check(self._lib, self._lib.fbstab_hip_mpc_condensed_x0_map_batch(
+            self.N, self.nx, self.nu, self.nc, B, C.byref(blk), C.c_void_p(M.data_ptr()),
+            0 if shared else ne * self.nx, self.device, sp))
+        # f_c(0), b_c(0): the vectors kernel with every QP's x0 slot on one block of zeros
+        d0 = dict(d)
+        d0["x0"] = t.zeros((1, self.nx), dtype=t.float64, device=self._dev)
+        blk0 = self._mpc_block(d0, B)
+        out = _DenseOutBatch()
+        for k, a in (("f", f0), ("b", b0)):
+            i = DENSE_ARR.index(k)
+            out.base[i], out.stride[i] = a.data_ptr(), self._len[k]
+        _check(self._lib, self._lib.fbstab_hip_mpc_condense_batch(
+            self.N, self.nx, self.nu, self.nc, B, C.byref(blk0), VECTORS, C.byref(out), self.device, sp))
+        return dict(M=M, f0=f0, b0=b0)
+
+    def RecedingSweep(self, data: Dict[str, object], z, l, v, y, A, B, steps: int, retire: bool = True, w=None,
+                      shift: bool = False, mode: str = "affine", log: Sequence[str] = (), traj_per_group: int = 0):
+        """``steps`` warm-started closed-loop steps on this route without a host round trip
+        (fbstab_hip_mpc_condensed_receding_sweep): ``data`` is condensed ("all"), in ``mode="affine"`` the map of
+        ``X0Map`` is built, and every step is the dense solve plus one small kernel that logs, advances the plant
+        x+ = A x + B u0 (+ w_k), retires and shifts as ``FBstabMpcBatch.RecedingSweep`` does, and forms the next
+        f_c = f0 + F x+, b_c = b0 + G x+ (``mode="recondense"``: the vectors kernel runs behind it instead, and the
+        sweep is bitwise a loop over ``Solve(recondense="vectors")``).  ``A``/``B``: the simulation model, row-major
+        ``(nx, nx)``/``(nx, nu)`` shared by all trajectories or ``(batch, nx, nx)``/``(batch, nx, nu)``.  ``w``:
+        ``(steps, batch, nx)`` or None.  ``data["x0"]`` ``(batch, nx)`` is advanced in place to the state behind the
+        last step, and ``(z, l, v, y)`` hold the expanded point of the LAST step.  Returns ``dict(out, u, eflag,
+        newton)`` - the dense records of the last step, ``u (steps, batch, nu)``, and the int32 ``(steps, batch)`` exit
+        flags (-1 once a trajectory is retired) and Newton counts - plus those of ``log`` among ``"x"`` (the states
+        the steps were solved for), ``"U"``, ``"v"`` (the returned condensed points).  Everything is queued on
+        torch's current stream and nothing waits for the device: torch tensors come back as they are queued; numpy
+        arguments are uploaded, and numpy arrays come back.  ``traj_per_group``: trajectories per workgroup of the
+        step kernel, 0 for the library's rule; it changes speed, never results.
+        The images of the LAST step's QP stay in this object: ``Adjoint`` / ``X0Sensitivity`` at the returned point
+        work when ``data["x0"]`` is set to the last row of the ``"x"`` log, the state that step was solved for."""
+        assert mode in _SWEEP_MODE, mode
+        unknown = set(log) - {"x", "U", "v"}
+        assert not unknown, unknown
+        t = self._torch
+        host = not _is_torch(z)
+        d = self._data(data)
+        zd, ld, vd, yd = (self._to_dev(a) for a in (z, l, v, y))
+        Bn = zd.shape[0]
+        assert d["x0"].shape == (Bn, self.nx) and d["x0"].is_contiguous(), "every trajectory has its own x0"
+        for a, n in ((zd, self.nz), (ld, self.nl), (vd, self.nv), (yd, self.nv)):
+            assert a.shape == (Bn, n) and a.stride(1) == 1, (a.shape, n)
+        self._condense(d, "all")
+        img = self._img
+        cm = None
+        if mode == "affine":
+            m = self._x0_map(d)
+            st = lambda a, n: 0 if (a.shape[0] == 1 and Bn > 1) else n
+            cm = _CondensedMap(m["M"].data_ptr(), m["f0"].data_ptr(), m["b0"].data_ptr(),
+                               st(m["M"], m["M"].shape[1]), self.nzc, self.nv)
+        dense = _DenseBatch()
+        for k in ("H", "f", "A", "b"):
+            a, i = img[k], DENSE_ARR.index(k)
+            dense.base[i], dense.stride[i] = a.data_ptr(), (0 if (a.shape[0] == 1 and Bn > 1) else self._len[k])
+        cimg = lambda a: a.detach().to(self._dev, t.float64).transpose(-1, -2).contiguous()
+        Ad, Bd = (cimg(a if _is_torch(a) else t.from_numpy(np.ascontiguousarray(a, dtype=np.float64))) for a in (A, B))
+        for a, shape in ((Ad, (self.nx, self.nx)), (Bd, (self.nu, self.nx))):
+            assert tuple(a.shape) in (shape, (Bn,) + shape), (tuple(a.shape), shape)
+        plant = _Plant(Ad.data_ptr(), Bd.data_ptr(), self.nx * self.nx if Ad.dim() == 3 else 0,
+                       self.nx * self.nu if Bd.dim() == 3 else 0)
+        wd = None
+        if w is not None:
+            wd = (w.detach() if _is_torch(w) else t.from_numpy(np.ascontiguousarray(w, dtype=np.float64))).to(
+                self._dev, t.float64).contiguous()
+            assert tuple(wd.shape) == (steps, Bn, self.nx), "w: (steps, batch, nx)"
+        sc = _SweepScenario(wd.data_ptr() if wd is not None else None, 1 if shift else 0)
+        mk = lambda shape, dtype=t.float64: t.zeros(shape, dtype=dtype, device=self._dev)
+        res = dict(u=mk((steps, Bn, self.nu)), eflag=mk((steps, Bn), t.int32), newton=mk((steps, Bn), t.int32))
+        for k, n in (("x", self.nx), ("U", self.nzc), ("v", self.nv)):
+            if k in log:
+                res[k] = mk((steps, Bn, n))
+        ptr = lambda k: res[k].data_ptr() if (k in res and steps > 0) else None
+        lg = _CondensedSweepLog(ptr("u"), ptr("x"), ptr("U"), ptr("v"), ptr("eflag"), ptr("newton"))
+        sizes = condensed_sweep_sizes(self.N, self.nx, self.nu, self.nc, traj_per_group,
+                                      cm is not None and (Bn == 1 or cm.stride_M == 0))
+        work = t.empty((Bn, sizes["work_doubles_per_traj"]), dtype=t.float64, device=self._dev)
+        out = t.zeros((Bn, 40), dtype=t.uint8, device=self._dev)
+        xb = hip_api._fill_vars((zd, ld, vd, yd), (self.nz, self.nl, self.nv, self.nv), Bn, [])
+        blk = self._mpc_block(d, Bn)
+        s = self._stream()
+        self.generation += 1
+        _check(self._lib, self._lib.fbstab_hip_mpc_condensed_receding_sweep(
+            self.dense._h, self.N, self.nx, self.nu, self.nc, Bn, C.byref(blk), C.byref(dense),
+            C.byref(cm) if cm is not None else None, C.byref(xb), C.c_void_p(out.data_ptr()), C.byref(plant), steps,
+            1 if retire else 0, C.byref(sc), _SWEEP_MODE[mode], C.byref(lg), traj_per_group,
+            C.c_void_p(work.data_ptr()), C.c_void_p(s) if s else None))
+        res["out"] = out
+        if not host:
+            return res
+        for dst, src in ((z, zd), (l, ld), (v, vd), (y, yd)):
+            dst[...] = src.cpu().numpy()
+        if not _is_torch(data["x0"]):
+            data["x0"][...] = d["x0"].cpu().numpy()
+        res = {k: a.cpu().numpy() for k, a in res.items() if k != "out"}
+        res["out"] = hip_api.out_to_numpy(out)
+        return res
 
     def Solve(self, data: Dict[str, object], z, l, v, y, out=None, recondense="all"):
         """The signature and in-place semantics of ``FBstabMpcBatch.Solve``: the guess is read from ``(z, l, v)`` -

@@ -22,6 +22,7 @@
 #include "fb_condense.h"         // (CondenseLds; its kernels are fb_condense.hip's)
 #include "fb_condense_adjoint.h" // (CondenseAdjointWork; its kernels are fb_condense_adjoint.hip's)
 #include "fb_condense_multi.h"   // (CondenseMultiWork and the LDS rule; its kernels are fb_condense_multi.hip's)
+#include "fb_condense_sweep.h"   // (CondenseSweepLds, CondenseSweepStep; its kernels are fb_condense_sweep.hip's)
 #include "fb_dense_wave.h"
 #include "fb_final_norms.h"
 #include "fb_grad_reduce.h"
@@ -575,6 +576,10 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_adjoint_kernel
 // unit of its own): which = 0 - the seeds, 1 - the finish, 2 - the residual, 3 - the correction; *threads: their
 // workgroup size
 __attribute__((visibility("hidden"))) const void* fbstab_condense_multi_kernel(int which, int* threads);
+// The kernels of fbstab_hip_mpc_condensed_x0_map_batch / fbstab_hip_mpc_condensed_receding_sweep (fb_condense_sweep.hip,
+// a translation unit of its own): which = 0 - the x0 map, 1 - the step, 2 - the begin kernel; *threads: their
+// workgroup size
+__attribute__((visibility("hidden"))) const void* fbstab_condense_sweep_kernel(int which, int* threads);
 #if defined(FB_SINGLE_TU)
 // (diagnostic builds with device-side counters: one translation unit, one g_stamps)
 #include "rec_12_4_20.hip"
@@ -587,6 +592,7 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_multi_kernel(i
 #include "fb_condense.hip"
 #include "fb_condense_adjoint.hip"
 #include "fb_condense_multi.hip"
+#include "fb_condense_sweep.hip"
 #endif
 namespace {
 const RecordInstance* record_instances(int* count) {
@@ -1838,6 +1844,207 @@ int fbstab_hip_mpc_condensed_x0_sensitivity_batch(fbstab_dense_handle_t h, int N
   if (!step && !gain) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 sensitivity: both step and gain are null");
   return condensed_multi_run(h, sh, batch, data, dense, x, nx, nullptr, sigma, step, gain, gain_stride, rhs_per_group,
                              work, status, stream);
+}
+
+// ---- the condensed route in closed loop (include/fbstab_hip.h; fb_condense_sweep.h) --------------------------------
+namespace {
+// What fbstab_hip_mpc_condensed_sweep_sizes documents, behind its argument checks.
+int condense_sweep_plan(int N, int nx, int nu, int nc, int traj_per_group, bool stage_m, fbk::CondenseSweepLds* L) {
+  L->init(N, nx, nu, nc, traj_per_group, stage_m);
+  if ((long long)L->total * 8 > kLdsLimitBytes)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED,
+                "condensed sweep: traj_per_group copies of a trajectory's vectors do not fit the 160 KiB LDS budget");
+  return FBSTAB_HIP_OK;
+}
+int condense_sweep_launch(int which, int grid, int lds, void** args, hipStream_t s) {
+  int threads = 0;
+  const void* kern = fbstab_condense_sweep_kernel(which, &threads);
+  if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
+  HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(threads), args, (size_t)lds, s));
+  return FBSTAB_HIP_OK;
+}
+}  // namespace
+
+int fbstab_hip_mpc_condensed_sweep_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
+                                         int* traj_per_group_used, long long* lds_bytes,
+                                         long long* work_doubles_per_traj) {
+  if (traj_per_group_used) *traj_per_group_used = 0;
+  if (lds_bytes) *lds_bytes = 0;
+  if (work_doubles_per_traj) *work_doubles_per_traj = 0;
+  if (N < 1 || nx < 1 || nu < 1 || nc < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: problem sizes must be positive");
+  if (traj_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: negative traj_per_group");
+  if ((long long)(N + 1) * nu > 0x7fffffff || (long long)(N + 1) * nc > 0x7fffffff)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the condensed sizes do not fit an int");
+  fbk::CondenseSweepLds L;
+  RC_TRY(condense_sweep_plan(N, nx, nu, nc, traj_per_group, shared_map != 0, &L));
+  if (traj_per_group_used) *traj_per_group_used = L.T;
+  if (lds_bytes) *lds_bytes = (long long)L.total * 8;
+  if (work_doubles_per_traj) *work_doubles_per_traj = (long long)(N + 1) * nu + 2LL * (N + 1) * nc + nx + 1;
+  return FBSTAB_HIP_OK;
+}
+
+int fbstab_hip_mpc_condensed_x0_map_batch(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+                                          double* map, long long map_stride, int device, void* stream) {
+  CondenseShape sh;
+  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
+  if (!map) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 map: null output pointer");
+  static const int kMatrixSeq[] = {FBSTAB_MPC_Q, FBSTAB_MPC_R, FBSTAB_MPC_S, FBSTAB_MPC_A,
+                                   FBSTAB_MPC_B, FBSTAB_MPC_E, FBSTAB_MPC_L};
+  bool shared_model = true;
+  for (int i : kMatrixSeq) shared_model = shared_model && data->stride[i] == 0;
+  const long long len = (sh.nz + sh.nv) * nx;
+  if (batch > 1 && map_stride < len) {
+    if (map_stride != 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 map: output stride smaller than the image");
+    if (!shared_model)
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 map: output stride 0 needs stride 0 on every one of Q, R, S, A, B, E, L");
+  }
+  if (batch == 0) return FBSTAB_HIP_OK;
+  fbk::CondenseLds o;
+  int lds = 0;
+  RC_TRY(condense_device(sh, device, &o, &lds));
+  fbstab_mpc_batch_t a = *data;
+  long long ms = batch > 1 ? map_stride : len;
+  const int blocks = (nx + nu - 1) / nu;
+  if ((long long)batch * blocks > 0x7fffffff)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 map: batch x column blocks exceeds the grid limit");
+  void* args[] = {&N, &nx, &nu, &nc, &o, &a, &map, &ms};
+  return condense_sweep_launch(0, (ms == 0 ? 1 : batch) * blocks, lds, args, (hipStream_t)stream);
+}
+
+int fbstab_hip_mpc_condensed_receding_sweep(fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch,
+                                            const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                            const fbstab_condensed_map_t* map, const fbstab_var_batch_t* x,
+                                            fbstab_solver_out_t* out, const fbstab_receding_plant_t* plant, int steps,
+                                            int retire, const fbstab_sweep_scenario_t* scenario, int mode,
+                                            const fbstab_condensed_sweep_log_t* log, int traj_per_group, double* work,
+                                            void* stream) {
+  // what needs no handle comes first, in the order of fbstab_hip_mpc_condense_batch
+  CondenseShape sh;
+  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
+  if (!dense || !x || !out || !plant || !work) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null argument");
+  if (!plant->A || !plant->B) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null plant matrix");
+  if (steps < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: negative step count");
+  if (scenario && scenario->shift != 0 && scenario->shift != 1)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: shift is 0 or 1");
+  if (mode != FBSTAB_CONDENSED_SWEEP_AFFINE && mode != FBSTAB_CONDENSED_SWEEP_RECONDENSE)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: `mode` must be AFFINE (0) or RECONDENSE (1)");
+  if (traj_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: negative traj_per_group");
+  if (batch > 1 && data->stride[FBSTAB_MPC_x0] < nx)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: every trajectory needs its own x0 (stride >= nx)");
+  const long long dlen[FBSTAB_DENSE_NARR] = {sh.nz * sh.nz, sh.nz, 0, 0, sh.nv * sh.nz, sh.nv};
+  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
+    const bool matrix = i == FBSTAB_DENSE_H || i == FBSTAB_DENSE_A;
+    if (!dense->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null pointer in the condensed images");
+    if (batch > 1 && dense->stride[i] < dlen[i] && !(matrix && dense->stride[i] == 0))
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: stride of a condensed image smaller than the array length");
+  }
+  const long long xlen[4] = {(long long)(N + 1) * (nx + nu), (long long)(N + 1) * nx, sh.nv, sh.nv};
+  for (int i = 0; i < 4; i++) {
+    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null variable pointer");
+    if (batch > 1 && x->stride[i] < xlen[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: variable stride smaller than the vector length");
+  }
+  if (batch > 1 && ((plant->stride_A != 0 && plant->stride_A < (long long)nx * nx) ||
+                    (plant->stride_B != 0 && plant->stride_B < (long long)nx * nu)))
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: plant stride smaller than the matrix");
+  const bool affine = mode == FBSTAB_CONDENSED_SWEEP_AFFINE;
+  const long long ne = sh.nz + sh.nv;
+  if (affine) {
+    if (!map) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: AFFINE mode needs the map");
+    if (!map->M || !map->f0 || !map->b0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null pointer in the map");
+    if (batch > 1 && ((map->stride_M != 0 && map->stride_M < ne * nx) || (map->stride_f0 != 0 && map->stride_f0 < sh.nz) ||
+                      (map->stride_b0 != 0 && map->stride_b0 < sh.nv)))
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: stride of the map smaller than the array length");
+  }
+  // ... then the handle
+  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null dense solver handle");
+  if (h->var_len[0] != sh.nz || h->var_len[1] != 0 || h->var_len[2] != sh.nv)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: the dense handle is not one of ((N + 1) nu, 0, (N + 1) nc)");
+  if (batch > h->max_batch)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: batch exceeds the max_batch the handle was created with");
+  if (batch == 0 || steps == 0) return FBSTAB_HIP_OK;
+  fbk::CondenseLds o;
+  int lds = 0;
+  RC_TRY(condense_device(sh, h->device, &o, &lds));
+  const bool shared_m = affine && (batch == 1 || map->stride_M == 0);
+  fbk::CondenseSweepLds L;
+  RC_TRY(condense_sweep_plan(N, nx, nu, nc, traj_per_group, shared_m, &L));
+  if (L.T > batch) L.init(N, nx, nu, nc, batch, shared_m);
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const bool one = batch == 1;
+  // the work arrays, and the blocks as the kernels take them (with batch == 1 the caller's strides are not read)
+  double* U = work;
+  double* vc = U + sh.nz * batch;
+  double* yc = vc + sh.nv * batch;
+  double* xkeep = yc + sh.nv * batch;
+  int* gone = reinterpret_cast<int*>(xkeep + (long long)nx * batch);
+  fbstab_mpc_batch_t a = *data;
+  fbstab_var_batch_t xv = {};
+  for (int i = 0; i < 4; i++) { xv.base[i] = x->base[i]; xv.stride[i] = one ? xlen[i] : x->stride[i]; }
+  fbstab_dense_batch_t dc = {};
+  fbstab_dense_out_batch_t dvec = {};  // (the VECTORS launch of RECONDENSE mode writes f and b)
+  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
+    dc.base[i] = dense->base[i];
+    dc.stride[i] = one ? dlen[i] : dense->stride[i];
+  }
+  for (int i : {FBSTAB_DENSE_f, FBSTAB_DENSE_b}) {
+    dvec.base[i] = const_cast<double*>(dc.base[i]);
+    dvec.stride[i] = dc.stride[i];
+  }
+  fbstab_var_batch_t xc = {};
+  xc.base[0] = U; xc.stride[0] = sh.nz;
+  xc.base[2] = vc; xc.stride[2] = sh.nv;
+  xc.base[3] = yc; xc.stride[3] = sh.nv;
+  {
+    void* args[] = {&N, &nx, &nu, &nc, &xv, &U, &vc, &gone};
+    RC_TRY(condense_sweep_launch(2, batch, 0, args, s));
+  }
+  fbk::CondenseSweepStep st = {};
+  st.N = N; st.nx = nx; st.nu = nu; st.nc = nc; st.batch = batch;
+  st.retire = retire != 0;
+  st.out = out; st.gone = gone; st.U = U; st.v = vc;
+  st.x0 = const_cast<double*>(data->base[FBSTAB_MPC_x0]);
+  st.sx0 = one ? nx : data->stride[FBSTAB_MPC_x0];
+  st.Ap = plant->A; st.Bp = plant->B;
+  st.sAp = one ? 0 : plant->stride_A; st.sBp = one ? 0 : plant->stride_B;
+  if (affine) {
+    st.M = map->M; st.sM = one ? 0 : map->stride_M;
+    st.f0 = map->f0; st.sf0 = one ? 0 : map->stride_f0;
+    st.b0 = map->b0; st.sb0 = one ? 0 : map->stride_b0;
+  }
+  st.f = dvec.base[FBSTAB_DENSE_f]; st.sf = dvec.stride[FBSTAB_DENSE_f];
+  st.b = dvec.base[FBSTAB_DENSE_b]; st.sb = dvec.stride[FBSTAB_DENSE_b];
+  const bool shift = scenario && scenario->shift == 1;
+  const double* w = scenario ? scenario->w : nullptr;
+  const int flags = FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC;
+  const int groups = (batch + L.T - 1) / L.T;
+  for (int k = 0; k < steps; k++) {
+    const bool last = k + 1 == steps;
+    RC_TRY(fbstab_hip_dense_solve_batch(h, batch, &dc, &xc, out, flags, (void*)s));
+    const long long kb = (long long)k * batch;
+    st.shift = shift && !last;
+    st.affine = affine && !last;
+    st.xkeep = last ? xkeep : nullptr;
+    st.w = w ? w + kb * nx : nullptr;
+    st.u_log = log && log->u ? log->u + kb * nu : nullptr;
+    st.x_log = log && log->x ? log->x + kb * nx : nullptr;
+    st.U_log = log && log->U ? log->U + kb * sh.nz : nullptr;
+    st.v_log = log && log->v ? log->v + kb * sh.nv : nullptr;
+    st.eflag_log = log && log->eflag ? log->eflag + kb : nullptr;
+    st.newton_log = log && log->newton ? log->newton + kb : nullptr;
+    void* sargs[] = {&st, &L};
+    RC_TRY(condense_sweep_launch(1, groups, L.total * 8, sargs, s));
+    if (!affine && !last) {
+      void* vargs[] = {&N, &nx, &nu, &nc, &o, &a, &dvec};
+      RC_TRY(condense_launch(1, batch, lds, vargs, s));
+    }
+  }
+  // the point of the last step, at the state it was solved for
+  fbstab_mpc_batch_t al = a;
+  al.base[FBSTAB_MPC_x0] = xkeep;
+  al.stride[FBSTAB_MPC_x0] = nx;
+  void* eargs[] = {&N, &nx, &nu, &nc, &o, &al, &xc, &xv};
+  return condense_launch(2, batch, lds, eargs, s);
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;

@@ -107,6 +107,18 @@ class _SweepLog(C.Structure):
     _fields_ = [("z", C.c_void_p), ("l", C.c_void_p), ("v", C.c_void_p), ("x0", C.c_void_p), ("eflag", C.c_void_p)]
 
 
+class _CondensedMap(C.Structure):
+    """fbstab_condensed_map_t: M = [F; G], f_c(0), b_c(0) and their strides."""
+    _fields_ = [("M", C.c_void_p), ("f0", C.c_void_p), ("b0", C.c_void_p), ("stride_M", C.c_longlong),
+                ("stride_f0", C.c_longlong), ("stride_b0", C.c_longlong)]
+
+
+class _CondensedSweepLog(C.Structure):
+    """fbstab_condensed_sweep_log_t."""
+    _fields_ = [("u", C.c_void_p), ("x", C.c_void_p), ("U", C.c_void_p), ("v", C.c_void_p), ("eflag", C.c_void_p),
+                ("newton", C.c_void_p)]
+
+
 class _SweepScenario(C.Structure):
     """fbstab_sweep_scenario_t: the disturbances (device pointer or NULL) and the shift flag."""
     _fields_ = [("w", C.c_void_p), ("shift", C.c_int)]
@@ -227,6 +239,12 @@ def load_library() -> C.CDLL:
             C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_int] + [C.c_void_p] * 3
         lib.fbstab_hip_mpc_condensed_x0_sensitivity_batch.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [
             C.c_double, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int] + [C.c_void_p] * 3
+    if hasattr(lib, "fbstab_hip_mpc_condensed_receding_sweep"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_condensed_sweep_sizes.argtypes = [C.c_int] * 6 + [C.c_void_p] * 3
+        lib.fbstab_hip_mpc_condensed_x0_map_batch.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_longlong,
+                                                              C.c_int, C.c_void_p]
+        lib.fbstab_hip_mpc_condensed_receding_sweep.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6 + [
+            C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -275,6 +293,8 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_condensed_adjoint_batch",
     "fbstab_hip_mpc_condensed_multi_sizes", "fbstab_hip_mpc_condensed_kkt_solve_batch",
     "fbstab_hip_mpc_condensed_x0_sensitivity_batch",
+    "fbstab_hip_mpc_condensed_sweep_sizes", "fbstab_hip_mpc_condensed_x0_map_batch",
+    "fbstab_hip_mpc_condensed_receding_sweep",
     "fbstab_hip_dense_kkt_solve_batch", "fbstab_hip_dense_jacobian_batch",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",

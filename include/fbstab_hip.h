@@ -721,6 +721,105 @@ int fbstab_hip_mpc_condensed_x0_sensitivity_batch(fbstab_dense_handle_t handle, 
                                                   long long gain_stride, int rhs_per_group, double* work, int* status,
                                                   void* stream);
 
+/* ---- the condensed route in closed loop: sweeps on an affine map of x0 ---------------------------------------------
+ * In a receding-horizon sweep the matrix sequences and q, r, c, d stand and only x0 moves: H_c and A_c stand, and
+ *   f_c(x) = f_c(0) + F x     b_c(x) = b_c(0) + G x      F: (N + 1) nu x nx,  G: (N + 1) nc x nx
+ * (the explicit-MPC form of the condensed QP; fb_condense_sweep.h has the derivation).  Re-condensing for a new state
+ * is then one ((N + 1)(nu + nc)) x nx matrix-vector product per trajectory, fused into the plant step.
+ *
+ * fbstab_hip_mpc_condensed_x0_map_batch: the image M = [F; G] of every QP, once per sweep, O(N nx^3) per QP.
+ *   map:   ne x nx doubles per QP, ne = (N + 1)(nu + nc), COLUMN-MAJOR with leading dimension ne: rows 0 .. (N + 1) nu
+ *          are F in the order of U, the rest G in the order of v.  QP q at map + q map_stride, map_stride >= ne nx with
+ *          batch > 1, or 0 where every one of Q, R, S, A, B, E, L has stride 0: ONE image is then computed, bitwise the
+ *          image of QP 0.  The doubles between two images are not written.
+ *   G[i] = -E_i Phi_i,  F[k] = S_k Phi_k + B_k' P_(k+1),  P_i = Q_i Phi_i + A_i' P_(i+1) (P_(N+1) = 0; no B' term at
+ *   k = N),  Phi_0 = I, Phi_(i+1) = A_i Phi_i.  One workgroup per (QP, block of at most nu columns of x0), in the LDS
+ *   layout of fbstab_hip_mpc_condensed_sizes, which stays the only shape limit.
+ *   f_c(0) and b_c(0) are fbstab_hip_mpc_condense_batch(VECTORS) with the x0 slot pointing at nx zeros, stride 0.
+ *   Validation: that of fbstab_hip_mpc_condense_batch, then a NULL map and map_stride (ARGUMENT), before any device
+ *   call; then the device, then the LDS rule.  batch == 0 returns OK and queues nothing.
+ *
+ * fbstab_hip_mpc_condensed_receding_sweep: `steps` closed-loop steps on one stream without a host round trip -
+ * per step the dense solve (device pointers, FBSTAB_HIP_ASYNC) and fbstab_mpc_condensed_sweep_step_kernel, which for
+ * the T trajectories of a workgroup
+ *   1. reads eflag and newton_iters of the dense `out` record; with retire != 0 a trajectory whose solve did not end
+ *      in SUCCESS is gone for the rest of the sweep: U = 0, v = 0, u0 = 0, x = 0, and a logged eflag of -1;
+ *   2. writes the logs that are given;
+ *   3. advances the plant, x+ = A_p x + B_p u0 (+ w_k), summed in the order of fbstab_hip_mpc_receding_sweep's plant
+ *      step, and writes it in place into data->base[FBSTAB_MPC_x0];
+ *   4. with scenario->shift == 1 moves U and v one stage towards the present (U[i] <- U[i+1], v[i] <- v[i+1], i < N;
+ *      stage N keeps its values);
+ *   5. AFFINE mode: f_c[e] = f_c(0)[e] + sum_j F[e][j] x+[j], b_c likewise, j ascending, one thread per entry.  A
+ *      shared M (stride 0) is staged into LDS once per workgroup with the leading dimension ne | 1 where it fits
+ *      beside one trajectory in 80 KB, and is read from memory otherwise, as every per-QP M is.
+ *      RECONDENSE mode: the VECTORS launch of fbstab_hip_mpc_condense_batch is queued behind the step kernel instead:
+ *      the sweep is then bitwise a loop over the public calls.
+ * 4 and 5 do not follow the last step: on return dense->f and dense->b are those of the LAST step's QP.  One
+ * fbstab_hip_mpc_expand_batch, with x0 pointing at the work copy of the state the last step was solved for, follows.
+ *   handle: the dense handle ((N + 1) nu, 0, (N + 1) nc).
+ *   data:   the MPC data; every trajectory needs its own x0 (stride >= nx with batch > 1), advanced in place to the
+ *           state behind the last step.  The other sequences are read by RECONDENSE mode and the final expand.
+ *   dense:  the images H_c, f_c, A_c, b_c as fbstab_hip_mpc_condensed_adjoint_batch takes them.  On entry they are
+ *           those of `data` (fbstab_hip_mpc_condense_batch(ALL)); f_c and b_c (stride >= length with batch > 1) are
+ *           overwritten before every step but the first.
+ *   map:    M, f0 = f_c(0), b0 = b_c(0); stride 0 shares one array among the batch, otherwise >= the length with
+ *           batch > 1.  May be NULL in RECONDENSE mode.
+ *   x:      (z, l, v, y) of the MPC QP.  The guess is read as the condensed solve reads it - U = the u blocks of z,
+ *           and v - and on return x holds the expanded point of the LAST step (zeros of U and v for a gone trajectory).
+ *   out:    DEVICE array of batch records: the dense solver's of the last step.
+ *   plant:  DEVICE matrices as for fbstab_hip_mpc_receding_sweep.
+ *   scenario: NULL, or (w, shift) as for fbstab_hip_mpc_receding_sweep_scenario.
+ *   mode:   FBSTAB_CONDENSED_SWEEP_AFFINE or FBSTAB_CONDENSED_SWEEP_RECONDENSE.
+ *   log:    NULL, or DEVICE arrays, NULL slots not logged: u [steps][batch][nu], x [steps][batch][nx] (the state the
+ *           step was solved for), U [steps][batch][(N + 1) nu] and v [steps][batch][(N + 1) nc] (the returned condensed
+ *           point, zero once gone), eflag and newton (int32 [steps][batch]; eflag -1 once gone).  There is no host
+ *           `stats` array: the logs carry what it carried.
+ *   traj_per_group: T.  0: the library's rule, ceil(1024 / ne) clamped to 1 .. 64 and lowered until the workgroup's
+ *           LDS is at most 80 KB.  T changes speed and never a bit of any result, and neither does the batch a
+ *           trajectory sits in.  Below 0: ARGUMENT.
+ *   work:   caller-provided DEVICE memory, batch x work_doubles_per_traj doubles: U, v, y of the dense solve, the
+ *           state of the last step, the gone flags - packed arrays of the batch in this order.  Nothing is allocated.
+ * EVERY pointer is a DEVICE pointer.  Asynchronous: steps x (dense solve, step kernel[, vectors launch]) and the
+ * expand are queued on `stream` (NULL: the handle's stream) and the call returns; nothing synchronises with the host.
+ * Every argument error is FBSTAB_HIP_ERR_ARGUMENT and checked before any device call, what needs no handle first:
+ * the sizes, the batch and the data block as fbstab_hip_mpc_condense_batch; NULL dense, x, out, plant, work; steps < 0;
+ * shift outside 0..1; mode outside its enum; traj_per_group < 0; the x0 stride; the condensed images; x; the plant; the
+ * map (NULL in AFFINE mode, NULL slots, strides) - then the handle (NULL, not ((N + 1) nu, 0, (N + 1) nc), batch above
+ * max_batch).  batch == 0 or steps == 0 returns OK here and queues nothing.  Then the device, then the LDS rule of
+ * fbstab_hip_mpc_condensed_sizes.
+ * fbstab_hip_mpc_condensed_sweep_sizes: what the sweep will use for traj_per_group (shared_map != 0: one M with
+ * stride 0 in AFFINE mode, which is staged into LDS; 0: per-QP images or RECONDENSE mode), with e(n) = n rounded up
+ * to even:
+ *   lds_bytes = 8 (staged M: e((ne | 1) nx)  +  T (2 e(nx) + e((N + 1) nu) + e((N + 1) nc) + 2))
+ *   work_doubles_per_traj = (N + 1) nu + 2 (N + 1) nc + nx + 1
+ *   Sizes below 1 and traj_per_group below 0 are ARGUMENT; lds_bytes above 160 KB (a traj_per_group the caller chose)
+ *   is FBSTAB_HIP_ERR_UNSUPPORTED (outputs 0).  Output pointers may be NULL.
+ * Not here: a derivative through the sweep, per-step references (q, r, c, d that move along the sweep), sharded
+ * sweeps, the C++ facade. */
+enum fbstab_condensed_sweep_mode { FBSTAB_CONDENSED_SWEEP_AFFINE = 0, FBSTAB_CONDENSED_SWEEP_RECONDENSE = 1 };
+typedef struct fbstab_condensed_map_t {
+  const double* M;      /* [F; G], ne x nx column-major */
+  const double* f0;     /* f_c(0), (N + 1) nu */
+  const double* b0;     /* b_c(0), (N + 1) nc */
+  long long stride_M, stride_f0, stride_b0;   /* doubles between trajectories; 0 = one for all */
+} fbstab_condensed_map_t;
+typedef struct fbstab_condensed_sweep_log_t {
+  double *u, *x, *U, *v;
+  int *eflag, *newton;
+} fbstab_condensed_sweep_log_t;
+int fbstab_hip_mpc_condensed_sweep_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
+                                         int* traj_per_group_used, long long* lds_bytes,
+                                         long long* work_doubles_per_traj);
+int fbstab_hip_mpc_condensed_x0_map_batch(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+                                          double* map, long long map_stride, int device, void* stream);
+int fbstab_hip_mpc_condensed_receding_sweep(fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch,
+                                            const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                            const fbstab_condensed_map_t* map, const fbstab_var_batch_t* x,
+                                            fbstab_solver_out_t* out, const fbstab_receding_plant_t* plant, int steps,
+                                            int retire, const fbstab_sweep_scenario_t* scenario, int mode,
+                                            const fbstab_condensed_sweep_log_t* log, int traj_per_group, double* work,
+                                            void* stream);
+
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);
 
