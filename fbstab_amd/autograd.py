@@ -383,3 +383,74 @@ def solve_condensed_mpc(cm, data, sigma: float = 0.0):
     batch, formed in torch).  Returns ``(z, l, v, out)`` with ``out`` the dense solver's records; see the module
     docstring."""
     return CondensedMpcSolveFunction.apply(cm, sigma, *[data[k] for k in MPC_SEQ])
+
+
+class ClosedLoopCondensedMpcFunction(torch.autograd.Function):
+    """apply(cm, steps, retire, sigma, A, B, *sequences in MPC_SEQ order, w, shift) -> (u, x, out); ``cm``: a
+    ``condense.CondensedMpc``."""
+
+    @staticmethod
+    def forward(ctx, cm, steps, retire, sigma, A, B, *rest):
+        seqs, (w, shift) = rest[:len(MPC_SEQ)], rest[len(MPC_SEQ):]
+        Bn = max(a.shape[0] if a.dim() == 2 else 1 for a in seqs)
+        ctx.shared = tuple(k for k, a in zip(MPC_SEQ, seqs) if Bn > 1 and (a.dim() == 1 or a.shape[0] == 1))
+        assert "x0" not in ctx.shared, "every trajectory has its own initial state"
+        ctx.shapes = {k: a.shape for k, a in zip(MPC_SEQ, seqs)}
+        data = {k: (a.detach().reshape(1, a.numel()) if (k in ctx.shared or a.dim() == 1) else a.detach()).contiguous()
+                for k, a in zip(MPC_SEQ, seqs)}
+        dev = data["Q"].device
+        run = dict(data)
+        run["x0"] = data["x0"].clone()  # (the sweep advances x0 in place)
+        mk = lambda n: torch.zeros((Bn, n), dtype=torch.float64, device=dev)
+        z, l, v, y = mk(cm.nz), mk(cm.nl), mk(cm.nv), mk(cm.nv)
+        r = cm.RecedingSweep(run, z, l, v, y, A.detach(), B.detach(), steps, retire=retire,
+                             w=None if w is None else w.detach(), shift=bool(shift), log=("x", "U", "v"))
+        u = r["u"]
+        x = torch.cat([r["x"][1:], run["x0"][None]], 0)
+        ctx.cm, ctx.steps, ctx.retire, ctx.sigma = cm, steps, retire, sigma
+        ctx.save_for_backward(A.detach(), B.detach(), u, r["x"], r["U"], r["v"], r["eflag"],
+                              *[data[k] for k in MPC_SEQ])
+        ctx.mark_non_differentiable(r["out"])
+        return u, x, r["out"]
+
+    @staticmethod
+    def backward(ctx, gu, gx, gout):
+        need = ctx.needs_input_grad
+        want = [k for k, n in zip(MPC_SEQ, need[6:6 + len(MPC_SEQ)]) if n]
+        plant = need[4] or need[5]
+        noise = need[6 + len(MPC_SEQ)]
+        if not want and not plant and not noise:
+            return (None,) * len(need)
+        A, B, u, xl, Ul, vl, el = ctx.saved_tensors[:7]
+        data = dict(zip(MPC_SEQ, ctx.saved_tensors[7:]))
+        log = dict(x=xl, U=Ul, v=vl, eflag=el)
+        g = ctx.cm.RecedingSweepAdjoint(data, A, B, ctx.steps, log, gu=gu.contiguous(), gx=gx.contiguous(),
+                                        retire=ctx.retire, sigma=ctx.sigma, want=[k for k in want if k != "x0"],
+                                        mu=plant or noise)
+        gA = gB = mu = None
+        if plant or noise:
+            # x_(k+1) of a retired trajectory is the constant 0: its costates reach neither the plant nor w_k
+            mu = torch.where((el == -1)[:, :, None], torch.zeros_like(g["mu"]), g["mu"])
+            gA = torch.einsum("kbi,kbj->ij", mu, xl) if need[4] else None
+            gB = torch.einsum("kbi,kbj->ij", mu, u) if need[5] else None
+        grads = []
+        for k in MPC_SEQ:
+            if k not in want:
+                grads.append(None)
+            elif k in ctx.shared:
+                grads.append(g[k].sum(0).reshape(ctx.shapes[k]))
+            else:
+                grads.append(g[k].reshape(ctx.shapes[k]))
+        return (None, None, None, None, gA, gB) + tuple(grads) + (mu if noise else None, None)
+
+
+def closed_loop_condensed_mpc(cm, data, A, B, steps: int, retire: bool = True, sigma: float = 0.0, w=None,
+                              shift: bool = False):
+    """``closed_loop_mpc`` on the condensed route: ``cm`` a ``condense.CondensedMpc``, the forward pass one
+    ``CondensedMpc.RecedingSweep`` (affine mode, logged), the backward pass ONE ``CondensedMpc.RecedingSweepAdjoint``
+    call.  ``data``, ``A``/``B``, ``w``, ``shift`` and the returned ``(u, x, out)`` as there (``out``: the dense
+    solver's records of the last step).  ``A.grad`` and ``B.grad`` are formed in torch from the costates, the state
+    log and ``u``, leaving out the costates of retired steps; ``w.grad`` is the costate of every step, zero once the
+    trajectory is retired; a shared ``(len,)`` / ``(1, len)`` sequence gets the torch sum over the batch."""
+    seqs = [data[k] for k in MPC_SEQ]
+    return ClosedLoopCondensedMpcFunction.apply(cm, steps, retire, sigma, A, B, *seqs, w, bool(shift))

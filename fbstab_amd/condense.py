@@ -54,6 +54,20 @@ def condensed_sweep_sizes(N: int, nx: int, nu: int, nc: int, traj_per_group: int
     return dict(traj_per_group=used.value, lds_bytes=lds.value, work_doubles_per_traj=work.value)
 
 
+def condensed_sweep_adjoint_sizes(N: int, nx: int, nu: int, nc: int, traj_per_group: int = 0,
+                                  shared_map: bool = True) -> Dict[str, int]:
+    """fbstab_hip_mpc_condensed_sweep_adjoint_sizes: what the adjoint through the closed-loop sweep uses -
+    ``traj_per_group`` and ``lds_bytes`` of its step kernel, and the doubles of the caller's work array per trajectory
+    without (``work_doubles_per_traj``) and with (``work_doubles_per_traj_grad``) gradients of the data."""
+    lib = hip_api.load_library()
+    used, lds, work, workg = C.c_int(), C.c_longlong(), C.c_longlong(), C.c_longlong()
+    _check(lib, lib.fbstab_hip_mpc_condensed_sweep_adjoint_sizes(N, nx, nu, nc, traj_per_group, 1 if shared_map else 0,
+                                                                 C.byref(used), C.byref(lds), C.byref(work),
+                                                                 C.byref(workg)))
+    return dict(traj_per_group=used.value, lds_bytes=lds.value, work_doubles_per_traj=work.value,
+                work_doubles_per_traj_grad=workg.value)
+
+
 class CondensedMpc:
     """``CondensedMpc(N, nx, nu, nc, max_batch)``: owns ``.dense``, a ``FBstabDenseBatch((N + 1) nu, 0, (N + 1) nc)``
     (public: ``SetFactorisation``, ``UpdateOptions`` ... apply to it), and the condensed images ``H, f, A, b`` as
@@ -411,6 +425,99 @@ class CondensedMpc:
             data["x0"][...] = d["x0"].cpu().numpy()
         res = {k: a.cpu().numpy() for k, a in res.items() if k != "out"}
         res["out"] = hip_api.out_to_numpy(out)
+        return res
+
+    def RecedingSweepAdjoint(self, data: Dict[str, object], A, B, steps: int, log: Dict[str, object], gu=None,
+                             gx=None, retire: bool = True, sigma: float = 0.0, want: Sequence[str] = (),
+                             mu: bool = False, mode: str = "affine", traj_per_group: int = 0,
+                             gf0: bool = False, gb0: bool = False) -> Dict[str, object]:
+        """Reverse mode through ``RecedingSweep`` in one call (fbstab_hip_mpc_condensed_receding_sweep_adjoint): the
+        seeds ``gu (steps, batch, nu)`` = dL/du_k and ``gx (steps, batch, nx)`` = dL/dx_(k+1) (None: zero) are taken
+        backwards along every trajectory of the sweep that ``log`` records - what ``RecedingSweep(..., log=("x", "U",
+        "v"))`` returned: its ``x``, ``U``, ``v`` and ``eflag`` are read.  ``data``: the sweep's data (its ``x0`` is
+        not read, only its batch size); ``A``/``B``: the plant as there.  This call condenses ``data`` ("all") and, in
+        ``mode="affine"``, builds the map of ``X0Map`` itself: the images this object held before are replaced, and
+        the vectors ``f``, ``b`` are scratch of the call.  Returns a dict: ``x0 (batch, nx)`` = dL/dx_0, dL/d(sequence)
+        summed over the contributing steps for every name of ``want`` (``(batch, len)``; a shared ``(1, len)`` sequence
+        gets per-trajectory gradients like every other), ``status`` (``(batch,)`` int32: the steps whose
+        factorisation failed) and, on request, ``mu (steps, batch, nx)`` (the costates: dL/dw_k where the step is not
+        retired), ``gf0 (batch, nzc)`` and ``gb0 (batch, nv)`` (the gradients of the map's f0 and b0).
+        ``mode="recondense"``: every step's f_c, b_c come from the vectors kernel, as in the forward sweep of that
+        mode.  ``retire``: the forward's.  ``traj_per_group``: as in ``RecedingSweep``; it changes speed, never
+        results.  Everything is queued on torch's current stream; numpy inputs are uploaded and numpy arrays come
+        back (decided by ``log["U"]``)."""
+        assert mode in _SWEEP_MODE, mode
+        want = tuple(want)
+        assert not set(want) - set(MPC_SEQ), set(want) - set(MPC_SEQ)
+        t = self._torch
+        host = not _is_torch(log["U"])
+        d = self._data(data)
+        Bn = d["x0"].shape[0]
+        assert 1 <= Bn <= self.max_batch, (Bn, self.max_batch)
+        f64 = lambda a: (a.detach() if _is_torch(a) else t.from_numpy(np.ascontiguousarray(a, dtype=np.float64))).to(
+            self._dev, t.float64).contiguous()
+        xl, Ul, vl = (f64(log[k]) for k in ("x", "U", "v"))
+        el = log["eflag"]
+        el = (el.detach() if _is_torch(el) else t.from_numpy(np.ascontiguousarray(el))).to(self._dev, t.int32).contiguous()
+        for a, n in ((xl, self.nx), (Ul, self.nzc), (vl, self.nv)):
+            assert tuple(a.shape) == (steps, Bn, n), (tuple(a.shape), (steps, Bn, n))
+        assert tuple(el.shape) == (steps, Bn), tuple(el.shape)
+        gud = None if gu is None else f64(gu)
+        gxd = None if gx is None else f64(gx)
+        assert gud is None or tuple(gud.shape) == (steps, Bn, self.nu), "gu: (steps, batch, nu)"
+        assert gxd is None or tuple(gxd.shape) == (steps, Bn, self.nx), "gx: (steps, batch, nx)"
+        self._condense(d, "all")
+        img = self._img
+        cm = None
+        if mode == "affine":
+            m = self._x0_map(d)
+            st = lambda a, n: 0 if (a.shape[0] == 1 and Bn > 1) else n
+            cm = _CondensedMap(m["M"].data_ptr(), m["f0"].data_ptr(), m["b0"].data_ptr(),
+                               st(m["M"], m["M"].shape[1]), self.nzc, self.nv)
+        dense = _DenseBatch()
+        for k in ("H", "f", "A", "b"):
+            a, i = img[k], DENSE_ARR.index(k)
+            dense.base[i], dense.stride[i] = a.data_ptr(), (0 if (a.shape[0] == 1 and Bn > 1) else self._len[k])
+        cimg = lambda a: f64(a).transpose(-1, -2).contiguous()
+        Ad, Bd = cimg(A), cimg(B)
+        for a, shape in ((Ad, (self.nx, self.nx)), (Bd, (self.nu, self.nx))):
+            assert tuple(a.shape) in (shape, (Bn,) + shape), (tuple(a.shape), shape)
+        plant = _Plant(Ad.data_ptr(), Bd.data_ptr(), self.nx * self.nx if Ad.dim() == 3 else 0,
+                       self.nx * self.nu if Bd.dim() == 3 else 0)
+        mk = lambda shape, dtype=t.float64: t.zeros(shape, dtype=dtype, device=self._dev)
+        names = tuple(k for k in MPC_SEQ if k in want or k == "x0")
+        res = {k: mk((Bn, n)) for k, n in zip(MPC_SEQ, self.seq_len) if k in names}
+        grad = _MpcGradBatch()
+        _fill_block(grad, MPC_SEQ, self.seq_len, res, Bn, [], optional=True, shared=False)
+        if mu:
+            res["mu"] = mk((steps, Bn, self.nx))
+        if gf0:
+            res["gf0"] = mk((Bn, self.nzc))
+        if gb0:
+            res["gb0"] = mk((Bn, self.nv))
+        status = mk((Bn,), t.int32)
+        sizes = condensed_sweep_adjoint_sizes(self.N, self.nx, self.nu, self.nc, traj_per_group,
+                                              cm is not None and (Bn == 1 or cm.stride_M == 0))
+        finish = mode != "affine" or any(k != "x0" for k in names)
+        work = t.empty((Bn, sizes["work_doubles_per_traj_grad" if finish else "work_doubles_per_traj"]),
+                       dtype=t.float64, device=self._dev)
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if (a is not None and a.numel() > 0) else None
+        lg = _CondensedSweepLog(None, xl.data_ptr() or None, Ul.data_ptr() or None, vl.data_ptr() or None,
+                                el.data_ptr() or None, None)
+        if steps == 0:  # (empty logs have no address; the call reads none of them)
+            lg = _CondensedSweepLog(None, work.data_ptr(), work.data_ptr(), work.data_ptr(), work.data_ptr(), None)
+        blk = self._mpc_block(d, Bn)
+        s = self._stream()
+        self.generation += 1
+        _check(self._lib, self._lib.fbstab_hip_mpc_condensed_receding_sweep_adjoint(
+            self.dense._h, self.N, self.nx, self.nu, self.nc, Bn, C.byref(blk), C.byref(dense),
+            C.byref(cm) if cm is not None else None, C.byref(plant), steps, 1 if retire else 0, C.byref(lg),
+            ptr(gud), ptr(gxd), C.c_double(sigma), C.byref(grad), ptr(res.get("gf0")), ptr(res.get("gb0")),
+            ptr(res.get("mu")), C.c_void_p(status.data_ptr()), _SWEEP_MODE[mode], traj_per_group,
+            C.c_void_p(work.data_ptr()), C.c_void_p(s) if s else None))
+        res["status"] = status
+        if host:
+            res = {k: a.cpu().numpy() for k, a in res.items()}
         return res
 
     def Solve(self, data: Dict[str, object], z, l, v, y, out=None, recondense="all"):

@@ -119,7 +119,16 @@ FB_DEV void condense_adjoint_seed(const C& c, int N, int nx, int nu, int nc, con
 // (dz, dl) from (dU, dv) of the dense adjoint, and the gradients of the 12 sequences: every slot of G that is not
 // null is written, and (az, al, av) where they are not null receive (dz, dl, dv); ok = false writes zeros to all of
 // them.  (z, l, v): the point.  gl: null is zero.  The caller synchronises before w is used again.
-template <class C, class P>
+// ACC (fbstab_mpc_condensed_sweep_adjoint_finish_kernel): the slots of G are ADDED to, as mpc_adjoint_contract<true>
+// adds - by the thread that wrote the entry before, so a caller that zeroes them with the same thread mapping needs
+// no synchronisation between the steps it sums over.
+#define FB_CONDENSE_ADJOINT_PUT(slot, val) \
+  do {                                     \
+    if constexpr (ACC) slot += val;        \
+    else slot = val;                       \
+  } while (0)
+
+template <bool ACC = false, class C, class P>
 FB_DEV void condense_adjoint_finish(const C& c, int N, int nx, int nu, int nc, const MpcData& D, const double* z,
                                     const double* l, const double* v, const double* gz, const double* gl,
                                     const double* dU, const double* dvc, const CondenseLds& o, P w, const MpcGrad& G,
@@ -176,25 +185,27 @@ FB_DEV void condense_adjoint_finish(const C& c, int N, int nx, int nu, int nc, c
       if (G.A)
         for (int e = c.tid; e < sq; e += C::nt) {
           const int r = e % nx, k = e / nx;
-          G.A[(long)j * sq + e] = ok ? -(lb[r] * xj[k] + lp[r] * dxj[k]) : 0.0;
+          FB_CONDENSE_ADJOINT_PUT(G.A[(long)j * sq + e], ok ? -(lb[r] * xj[k] + lp[r] * dxj[k]) : 0.0);
         }
       if (G.B)
         for (int e = c.tid; e < sb; e += C::nt) {
           const int r = e % nx, k = e / nx;
-          G.B[(long)j * sb + e] = ok ? -(lb[r] * xj[nx + k] + lp[r] * dxj[nx + k]) : 0.0;
+          FB_CONDENSE_ADJOINT_PUT(G.B[(long)j * sb + e], ok ? -(lb[r] * xj[nx + k] + lp[r] * dxj[nx + k]) : 0.0);
         }
       if (G.c)
-        for (int e = c.tid; e < nx; e += C::nt) G.c[(long)j * nx + e] = ok ? -lb[e] : 0.0;
+        for (int e = c.tid; e < nx; e += C::nt) FB_CONDENSE_ADJOINT_PUT(G.c[(long)j * nx + e], ok ? -lb[e] : 0.0);
     } else if (G.x0) {
-      for (int e = c.tid; e < nx; e += C::nt) G.x0[e] = ok ? -lb[e] : 0.0;
+      for (int e = c.tid; e < nx; e += C::nt) FB_CONDENSE_ADJOINT_PUT(G.x0[e], ok ? -lb[e] : 0.0);
     }
     const P t = la; la = lb; lb = t;
   }
   // ---- the gradients that read (dz, dv) alone --------------------------------------------------------------
   MpcGrad H = G;
   H.A = H.B = H.c = H.x0 = nullptr;
-  mpc_adjoint_contract(c, N, nx, nu, nc, z, l, v, (const double*)dz, (const double*)nullptr, dvc, H, ok, az,
-                       (double*)nullptr, av);
+  mpc_adjoint_contract<ACC>(c, N, nx, nu, nc, z, l, v, (const double*)dz, (const double*)nullptr, dvc, H, ok, az,
+                            (double*)nullptr, av);
 }
+
+#undef FB_CONDENSE_ADJOINT_PUT
 
 }  // namespace fbk

@@ -20,8 +20,8 @@
 // condense_stage in the CondenseLds layout, one thread owns each output entry and sums it in ascending index order
 // with plain FMAs.  No atomics, no sums across threads, no matrix cores.
 //
-// Not here: a derivative through the sweep, per-step references (q, r, c, d that move), sharded sweeps, the C++
-// facade.
+// Not here: per-step references (q, r, c, d that move), sharded sweeps, the C++ facade.  (The derivative through the
+// sweep: fb_condense_sweep_adjoint.h.)
 #pragma once
 
 #include "fb_condense.h"

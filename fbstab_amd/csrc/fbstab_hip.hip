@@ -23,6 +23,7 @@
 #include "fb_condense_adjoint.h" // (CondenseAdjointWork; its kernels are fb_condense_adjoint.hip's)
 #include "fb_condense_multi.h"   // (CondenseMultiWork and the LDS rule; its kernels are fb_condense_multi.hip's)
 #include "fb_condense_sweep.h"   // (CondenseSweepLds, CondenseSweepStep; its kernels are fb_condense_sweep.hip's)
+#include "fb_condense_sweep_adjoint.h"  // (CondenseSweepAdjStep; its kernels are fb_condense_sweep_adjoint.hip's)
 #include "fb_dense_wave.h"
 #include "fb_final_norms.h"
 #include "fb_grad_reduce.h"
@@ -580,6 +581,9 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_multi_kernel(i
 // a translation unit of its own): which = 0 - the x0 map, 1 - the step, 2 - the begin kernel; *threads: their
 // workgroup size
 __attribute__((visibility("hidden"))) const void* fbstab_condense_sweep_kernel(int which, int* threads);
+// The kernels of fbstab_hip_mpc_condensed_receding_sweep_adjoint (fb_condense_sweep_adjoint.hip, a translation unit of
+// its own): which = 0 - the step, 1 - the finish, 2 - the begin kernel; *threads: their workgroup size
+__attribute__((visibility("hidden"))) const void* fbstab_condense_sweep_adjoint_kernel(int which, int* threads);
 #if defined(FB_SINGLE_TU)
 // (diagnostic builds with device-side counters: one translation unit, one g_stamps)
 #include "rec_12_4_20.hip"
@@ -593,6 +597,7 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_sweep_kernel(i
 #include "fb_condense_adjoint.hip"
 #include "fb_condense_multi.hip"
 #include "fb_condense_sweep.hip"
+#include "fb_condense_sweep_adjoint.hip"
 #endif
 namespace {
 const RecordInstance* record_instances(int* count) {
@@ -2045,6 +2050,237 @@ int fbstab_hip_mpc_condensed_receding_sweep(fbstab_dense_handle_t h, int N, int 
   al.stride[FBSTAB_MPC_x0] = nx;
   void* eargs[] = {&N, &nx, &nu, &nc, &o, &al, &xc, &xv};
   return condense_launch(2, batch, lds, eargs, s);
+}
+
+// ---- reverse mode through that sweep (include/fbstab_hip.h; fb_condense_sweep_adjoint.h) ----------------------------
+namespace {
+// Doubles of work per trajectory: the seed, the dense step and its refinement, mu, -dl[0:nx], two status words; with
+// the finish kernel also the expanded point (z, l) and the zeros it reads for gz.
+long long condense_sweep_adjoint_work(int N, int nx, int nu, int nc, bool finish) {
+  const long long nzc = (long long)(N + 1) * nu, nv = (long long)(N + 1) * nc;
+  const long long base = 4 * nzc + 2 * nv + 2LL * nx + 1;
+  return finish ? base + 2LL * (N + 1) * (nx + nu) + (long long)(N + 1) * nx : base;
+}
+}  // namespace
+
+int fbstab_hip_mpc_condensed_sweep_adjoint_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
+                                                 int* traj_per_group_used, long long* lds_bytes,
+                                                 long long* work_doubles_per_traj,
+                                                 long long* work_doubles_per_traj_grad) {
+  if (traj_per_group_used) *traj_per_group_used = 0;
+  if (lds_bytes) *lds_bytes = 0;
+  if (work_doubles_per_traj) *work_doubles_per_traj = 0;
+  if (work_doubles_per_traj_grad) *work_doubles_per_traj_grad = 0;
+  if (N < 1 || nx < 1 || nu < 1 || nc < 1)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: problem sizes must be positive");
+  if (traj_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: negative traj_per_group");
+  if ((long long)(N + 1) * nu > 0x7fffffff || (long long)(N + 1) * nc > 0x7fffffff)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the condensed sizes do not fit an int");
+  fbk::CondenseSweepLds L;
+  RC_TRY(condense_sweep_plan(N, nx, nu, nc, traj_per_group, shared_map != 0, &L));
+  if (traj_per_group_used) *traj_per_group_used = L.T;
+  if (lds_bytes) *lds_bytes = (long long)L.total * 8;
+  if (work_doubles_per_traj) *work_doubles_per_traj = condense_sweep_adjoint_work(N, nx, nu, nc, false);
+  if (work_doubles_per_traj_grad) *work_doubles_per_traj_grad = condense_sweep_adjoint_work(N, nx, nu, nc, true);
+  return FBSTAB_HIP_OK;
+}
+
+int fbstab_hip_mpc_condensed_receding_sweep_adjoint(
+    fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+    const fbstab_dense_batch_t* dense, const fbstab_condensed_map_t* map, const fbstab_receding_plant_t* plant,
+    int steps, int retire, const fbstab_condensed_sweep_log_t* log, const double* gu, const double* gx, double sigma,
+    const fbstab_mpc_grad_batch_t* grad, double* gf0, double* gb0, double* mu_log, int* status, int mode,
+    int traj_per_group, double* work, void* stream) {
+  (void)retire;  // (the logged eflag of -1 carries it)
+  // what needs no handle comes first, in the order of fbstab_hip_mpc_condensed_receding_sweep
+  CondenseShape sh;
+  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
+  if (!dense || !plant || !log || !grad || !status || !work)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: null argument");
+  if (!plant->A || !plant->B) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: null plant matrix");
+  if (steps < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: negative step count");
+  if (mode != FBSTAB_CONDENSED_SWEEP_AFFINE && mode != FBSTAB_CONDENSED_SWEEP_RECONDENSE)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: `mode` must be AFFINE (0) or RECONDENSE (1)");
+  if (traj_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: negative traj_per_group");
+  const long long dlen[FBSTAB_DENSE_NARR] = {sh.nz * sh.nz, sh.nz, 0, 0, sh.nv * sh.nz, sh.nv};
+  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
+    const bool matrix = i == FBSTAB_DENSE_H || i == FBSTAB_DENSE_A;
+    if (!dense->base[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: null pointer in the condensed images");
+    if (batch > 1 && dense->stride[i] < dlen[i] && !(matrix && dense->stride[i] == 0))
+      return fail(FBSTAB_HIP_ERR_ARGUMENT,
+                  "condensed sweep adjoint: stride of a condensed image smaller than the array length");
+  }
+  if (batch > 1 && ((plant->stride_A != 0 && plant->stride_A < (long long)nx * nx) ||
+                    (plant->stride_B != 0 && plant->stride_B < (long long)nx * nu)))
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: plant stride smaller than the matrix");
+  if (!log->x || !log->U || !log->v || !log->eflag)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: the x, U, v and eflag logs are required");
+  bool data_grads = false;
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
+    if (!grad->base[i]) continue;
+    if (batch > 1 && grad->stride[i] < sh.len[i])
+      return fail(FBSTAB_HIP_ERR_ARGUMENT,
+                  "condensed sweep adjoint: gradient stride smaller than the array length (sums over the batch are the caller's)");
+    if (i != FBSTAB_MPC_x0) data_grads = true;
+  }
+  const bool affine = mode == FBSTAB_CONDENSED_SWEEP_AFFINE;
+  const long long ne = sh.nz + sh.nv;
+  if (affine) {
+    if (!map) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: AFFINE mode needs the map");
+    if (!map->M || !map->f0 || !map->b0)
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: null pointer in the map");
+    if (batch > 1 && ((map->stride_M != 0 && map->stride_M < ne * nx) || (map->stride_f0 != 0 && map->stride_f0 < sh.nz) ||
+                      (map->stride_b0 != 0 && map->stride_b0 < sh.nv)))
+      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: stride of the map smaller than the array length");
+  }
+  // ... then the handle
+  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: null dense solver handle");
+  if (h->var_len[0] != sh.nz || h->var_len[1] != 0 || h->var_len[2] != sh.nv)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT,
+                "condensed sweep adjoint: the dense handle is not one of ((N + 1) nu, 0, (N + 1) nc)");
+  if (batch > h->max_batch)
+    return fail(FBSTAB_HIP_ERR_ARGUMENT,
+                "condensed sweep adjoint: batch exceeds the max_batch the handle was created with");
+  if (batch == 0) return FBSTAB_HIP_OK;
+  fbk::CondenseLds o;
+  int lds = 0;
+  RC_TRY(condense_device(sh, h->device, &o, &lds));
+  const bool shared_m = affine && (batch == 1 || map->stride_M == 0);
+  fbk::CondenseSweepLds L;
+  RC_TRY(condense_sweep_plan(N, nx, nu, nc, traj_per_group, shared_m, &L));
+  if (L.T > batch) L.init(N, nx, nu, nc, batch, shared_m);
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const bool one = batch == 1;
+  const bool finish = data_grads || !affine;
+  const long long nzf = (long long)(N + 1) * (nx + nu);
+  // the work arrays, packed arrays of the batch in this order
+  fbk::CondenseAdjointWork wk = {};
+  wk.gU = work;
+  wk.dU = wk.gU + sh.nz * batch;
+  wk.rU = wk.dU + sh.nz * batch;
+  wk.eU = wk.rU + sh.nz * batch;
+  wk.dv = wk.eU + sh.nz * batch;
+  wk.ev = wk.dv + sh.nv * batch;
+  double* mu = wk.ev + sh.nv * batch;
+  double* dl0 = mu + (long long)nx * batch;
+  int* st1 = reinterpret_cast<int*>(dl0 + (long long)nx * batch);
+  int* st2 = st1 + batch;
+  double* zs = dl0 + (long long)nx * batch + batch;
+  double* gzs = zs + nzf * batch;
+  double* ls = gzs + nzf * batch;
+  auto launch = [&](int which, int grid, int bytes, void** args) -> int {
+    int threads = 0;
+    const void* kern = fbstab_condense_sweep_adjoint_kernel(which, &threads);
+    if (bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(threads), args, (size_t)bytes, s));
+    return FBSTAB_HIP_OK;
+  };
+  fbstab_mpc_grad_batch_t g = *grad;
+  if (one)
+    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) g.stride[i] = sh.len[i];
+  {
+    double* gz0 = finish ? gzs : nullptr;
+    void* args[] = {&N, &nx, &nu, &nc, &g, &gz0, &gf0, &gb0, &status};
+    RC_TRY(launch(2, batch, 0, args));
+  }
+  if (steps == 0) return FBSTAB_HIP_OK;
+  fbstab_mpc_batch_t a = *data;
+  a.stride[FBSTAB_MPC_x0] = nx;
+  fbstab_dense_batch_t dc = {};
+  fbstab_dense_out_batch_t dvec = {};
+  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
+    dc.base[i] = dense->base[i];
+    dc.stride[i] = one ? dlen[i] : dense->stride[i];
+  }
+  for (int i : {FBSTAB_DENSE_f, FBSTAB_DENSE_b}) {
+    dvec.base[i] = const_cast<double*>(dc.base[i]);
+    dvec.stride[i] = dc.stride[i];
+  }
+  fbk::CondenseSweepAdjStep st = {};
+  st.N = N; st.nx = nx; st.nu = nu; st.nc = nc; st.batch = batch;
+  st.affine = affine;
+  st.st1 = st1; st.st2 = st2; st.status = status;
+  st.dU = wk.dU; st.dv = wk.dv;
+  st.dl0 = affine ? nullptr : dl0;
+  st.mu = mu;
+  st.Ap = plant->A; st.Bp = plant->B;
+  st.sAp = one ? 0 : plant->stride_A; st.sBp = one ? 0 : plant->stride_B;
+  st.gU = wk.gU;
+  if (affine) {
+    st.M = map->M; st.sM = one ? 0 : map->stride_M;
+    st.f0 = map->f0; st.sf0 = one ? 0 : map->stride_f0;
+    st.b0 = map->b0; st.sb0 = one ? 0 : map->stride_b0;
+  }
+  st.f = dvec.base[FBSTAB_DENSE_f]; st.sf = dvec.stride[FBSTAB_DENSE_f];
+  st.b = dvec.base[FBSTAB_DENSE_b]; st.sb = dvec.stride[FBSTAB_DENSE_b];
+  st.gf0 = gf0; st.gb0 = gb0;
+  st.gx0 = g.base[FBSTAB_MPC_x0]; st.sgx0 = g.stride[FBSTAB_MPC_x0];
+  fbstab_mpc_grad_batch_t gfin = g;
+  gfin.base[FBSTAB_MPC_x0] = nullptr;
+  fbk::CondenseSweepAdjFinish fin = {};
+  fin.dU = wk.dU; fin.dv = wk.dv; fin.st1 = st1; fin.st2 = st2;
+  fin.z = zs; fin.l = ls; fin.gz = gzs; fin.dl0 = st.dl0;
+  const fbstab_dense_grad_batch_t none = {};
+  const int flags = FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC;
+  const int groups = (batch + L.T - 1) / L.T;
+  int nzc = (int)sh.nz, nvc = (int)sh.nv;
+  const double *Hc = dc.base[FBSTAB_DENSE_H], *Ac = dc.base[FBSTAB_DENSE_A];
+  long long sH = dc.stride[FBSTAB_DENSE_H], sA = dc.stride[FBSTAB_DENSE_A];
+  double sg = sigma > 0.0 ? sigma : 1e-8;  // (the rule of fbstab_hip_dense_adjoint_batch)
+  for (int k = steps - 1; k >= -1; k--) {
+    const long long kb = (long long)k * batch;
+    st.close = k + 1 < steps;
+    st.open = k >= 0;
+    st.eflag_close = st.close ? log->eflag + kb + batch : nullptr;
+    st.eflag_open = st.open ? log->eflag + kb : nullptr;
+    st.gu = st.open && gu ? gu + kb * nu : nullptr;
+    st.gx = st.open && gx ? gx + kb * nx : nullptr;
+    st.mu_log = st.open && mu_log ? mu_log + kb * nx : nullptr;
+    st.x_log = st.open ? log->x + kb * nx : nullptr;
+    void* sargs[] = {&st, &L};
+    RC_TRY(launch(0, groups, L.total * 8, sargs));
+    if (k < 0) break;
+    if (!affine) {
+      a.base[FBSTAB_MPC_x0] = log->x + kb * nx;
+      void* vargs[] = {&N, &nx, &nu, &nc, &o, &a, &dvec};
+      RC_TRY(condense_launch(1, batch, lds, vargs, s));
+    }
+    // the dense adjoint at the logged (U_k, v_k), read where they lie, and one step of refinement of its step
+    fbstab_var_batch_t xc = {}, sc = {}, ac = {};
+    xc.base[0] = log->U + kb * sh.nz; xc.stride[0] = sh.nz;
+    xc.base[2] = log->v + kb * sh.nv; xc.stride[2] = sh.nv;
+    sc.base[0] = wk.gU; sc.stride[0] = sh.nz;
+    sc.stride[2] = sh.nv;
+    ac.base[0] = wk.dU; ac.stride[0] = sh.nz;
+    ac.base[2] = wk.dv; ac.stride[2] = sh.nv;
+    RC_TRY(fbstab_hip_dense_adjoint_batch(h, batch, &dc, &xc, &sc, sigma, &none, &ac, st1, flags, (void*)s));
+    {
+      int threads = 0;
+      void* rargs[] = {&nzc, &nvc, &Hc, &sH, &Ac, &sA, &sg, &wk};
+      const void* kern = fbstab_condense_adjoint_kernel(2, &threads);
+      HIP_TRY(hipLaunchKernel(kern, dim3(batch), dim3(threads), rargs, 0, s));
+    }
+    sc.base[0] = wk.rU;
+    ac.base[0] = wk.eU;
+    ac.base[2] = wk.ev;
+    RC_TRY(fbstab_hip_dense_adjoint_batch(h, batch, &dc, &xc, &sc, sigma, &none, &ac, st2, flags, (void*)s));
+    {
+      int threads = 0;
+      void* cargs[] = {&nzc, &nvc, &wk};
+      const void* kern = fbstab_condense_adjoint_kernel(3, &threads);
+      HIP_TRY(hipLaunchKernel(kern, dim3(batch), dim3(threads), cargs, 0, s));
+    }
+    if (finish) {
+      fin.x = log->x + kb * nx;
+      fin.U = log->U + kb * sh.nz;
+      fin.v = log->v + kb * sh.nv;
+      fin.eflag = log->eflag + kb;
+      void* fargs[] = {&N, &nx, &nu, &nc, &o, &a, &fin, &gfin};
+      RC_TRY(launch(1, batch, lds, fargs));
+    }
+  }
+  return FBSTAB_HIP_OK;
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;

@@ -245,6 +245,11 @@ def load_library() -> C.CDLL:
                                                               C.c_int, C.c_void_p]
         lib.fbstab_hip_mpc_condensed_receding_sweep.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6 + [
             C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_condensed_receding_sweep_adjoint"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_condensed_sweep_adjoint_sizes.argtypes = [C.c_int] * 6 + [C.c_void_p] * 4
+        lib.fbstab_hip_mpc_condensed_receding_sweep_adjoint.argtypes = [C.c_void_p] + [C.c_int] * 5 + [
+            C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 5 + [
+            C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
@@ -295,6 +300,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_condensed_x0_sensitivity_batch",
     "fbstab_hip_mpc_condensed_sweep_sizes", "fbstab_hip_mpc_condensed_x0_map_batch",
     "fbstab_hip_mpc_condensed_receding_sweep",
+    "fbstab_hip_mpc_condensed_sweep_adjoint_sizes", "fbstab_hip_mpc_condensed_receding_sweep_adjoint",
     "fbstab_hip_dense_kkt_solve_batch", "fbstab_hip_dense_jacobian_batch",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",

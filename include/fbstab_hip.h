@@ -794,8 +794,8 @@ int fbstab_hip_mpc_condensed_x0_sensitivity_batch(fbstab_dense_handle_t handle, 
  *   work_doubles_per_traj = (N + 1) nu + 2 (N + 1) nc + nx + 1
  *   Sizes below 1 and traj_per_group below 0 are ARGUMENT; lds_bytes above 160 KB (a traj_per_group the caller chose)
  *   is FBSTAB_HIP_ERR_UNSUPPORTED (outputs 0).  Output pointers may be NULL.
- * Not here: a derivative through the sweep, per-step references (q, r, c, d that move along the sweep), sharded
- * sweeps, the C++ facade. */
+ * Not here: per-step references (q, r, c, d that move along the sweep), sharded sweeps, the C++ facade.  (The
+ * derivative through the sweep is the section below: this call's logs are its base.) */
 enum fbstab_condensed_sweep_mode { FBSTAB_CONDENSED_SWEEP_AFFINE = 0, FBSTAB_CONDENSED_SWEEP_RECONDENSE = 1 };
 typedef struct fbstab_condensed_map_t {
   const double* M;      /* [F; G], ne x nx column-major */
@@ -819,6 +819,78 @@ int fbstab_hip_mpc_condensed_receding_sweep(fbstab_dense_handle_t handle, int N,
                                             int retire, const fbstab_sweep_scenario_t* scenario, int mode,
                                             const fbstab_condensed_sweep_log_t* log, int traj_per_group, double* work,
                                             void* stream);
+
+/* ---- the condensed route in closed loop: reverse mode through the sweep -------------------------------------------
+ * fbstab_hip_mpc_receding_sweep_adjoint for sweeps of fbstab_hip_mpc_condensed_receding_sweep, at the cost of that
+ * route.  With u_k = U_k[0:nu] and x_(k+1) = A_p x_k + B_p u_k (+ w_k), the seeds gu[k] = dL/du_k ([steps][batch][nu])
+ * and gx[k] = dL/dx_(k+1) ([steps][batch][nx]; either may be NULL: zero) are taken backwards along every trajectory.
+ * Start with lambda = 0 and for k = steps-1 .. 0:
+ *   mu = gx[k] + lambda                             (mu_log[k] = mu where mu_log is given)
+ *   eflag_log[k] == -1 (retired):       lambda <- 0
+ *   eflag_log[k] != FBSTAB_SUCCESS:     lambda <- A_p'mu
+ *   otherwise one dense adjoint (fbstab_hip_dense_adjoint_batch's, same sigma rule) of the condensed QP at the logged
+ *   (U_k, v_k) with the seed gU = (gu[k] + B_p'mu, 0, .., 0) and gv_c = 0 - the seed map of
+ *   fbstab_hip_mpc_condensed_adjoint_batch is the identity on a seed that lives on u_0 alone, so no seed kernel runs -
+ *   refined once exactly as that call refines it (residual kernel, the dense adjoint again, correction kernel):
+ *     a factorisation failed in either launch:   status += 1, lambda <- A_p'mu
+ *     else                                       lambda <- A_p'mu + F'(-dU) + G'dv.
+ * The dense adjoint's gradients are f_bar = -dU and b_bar = dv, and f_c = f0 + F x, b_c = b0 + G x: F'(-dU) + G'dv is
+ * -dl[0:nx] of fbstab_hip_mpc_condensed_adjoint_batch's finish, without the finish.  The affine map M = [F; G] that
+ * makes the forward step one matrix-vector product makes the backward step its transpose.
+ * fbstab_mpc_condensed_sweep_adjoint_step_kernel (T trajectories per workgroup in the LDS layout of the forward step
+ * kernel) is launched steps + 1 times: one launch CLOSES step k + 1 - the case rule and
+ * lambda[j] = sum_r A_p[r][j] mu[r] + sum_e M[e][j] g[e], g = [-dU; dv], e ascending, one thread per (trajectory, j) -
+ * and OPENS step k: mu, the seed, and f_c, b_c of step k from x_log[k] with the forward kernel's loop and summation
+ * order.  Between two launches: the dense adjoint, fbstab_mpc_condensed_adjoint_residual_kernel, the dense adjoint
+ * again, fbstab_mpc_condensed_adjoint_correct_kernel, and - only where a gradient other than x0's is wanted, or in
+ * RECONDENSE mode - fbstab_mpc_condensed_sweep_adjoint_finish_kernel (one workgroup per trajectory in the LDS layout of
+ * fbstab_hip_mpc_condensed_sizes): the logged point is expanded with x0 := x_log[k] into scratch in `work`, and the
+ * finish of fbstab_hip_mpc_condensed_adjoint_batch ADDS the step's gradients to the slots, by the thread that zeroed
+ * the entry (fbstab_mpc_condensed_sweep_adjoint_begin_kernel, before the first step).
+ *   handle, data, dense, map, plant: as fbstab_hip_mpc_condensed_receding_sweep takes them.  data's x0 slot is not read.
+ *           dense's H_c and A_c are read; f_c and b_c (stride >= length with batch > 1) are per-trajectory scratch
+ *           that the call overwrites.  map may be NULL in RECONDENSE mode.
+ *   retire: the forward's (the logged eflag of -1 carries what it did).
+ *   log:    the forward's; x, U, v and eflag are required.  U and v are read where they lie, no copy is made.
+ *   grad:   one slot per sequence, NULL: not computed.  The x0 slot receives the final lambda = dL/dx_0 (not a sum
+ *           over the steps); every other slot is the sum over the contributing steps, last step first, without atomics
+ *           (the same inputs give the same bits).  Every non-NULL slot is written (zeros for a trajectory without a
+ *           contributing step) and needs stride >= length with batch > 1 (stride 0 is FBSTAB_HIP_ERR_ARGUMENT: sums over
+ *           the batch are the caller's).
+ *   gf0, gb0: NULL, or packed [batch][(N + 1) nu], [batch][(N + 1) nc]: the sums of f_bar = -dU and b_bar = dv over the
+ *           contributing steps, the gradients of the map's f0 and b0.
+ *   mu_log: NULL, or [steps][batch][nx].  dL/dw_k = mu_log[k] where eflag_log[k] != -1, zero otherwise; the plant's own
+ *           gradients are the caller's: A_bar = sum_k mu_k x_k', B_bar = sum_k mu_k u_k'.
+ *   status: [batch], the number of steps whose factorisation failed.
+ *   mode:   FBSTAB_CONDENSED_SWEEP_AFFINE: f_c, b_c of a step and lambda through the map.
+ *           FBSTAB_CONDENSED_SWEEP_RECONDENSE: the VECTORS launch of fbstab_hip_mpc_condense_batch is queued with the
+ *           x0 slot on x_log[k] - a step then sees bit for bit the images a loop over the public calls gives it - the
+ *           finish kernel runs at every step, and lambda <- A_p'mu - dl[0:nx] with its dl.
+ *   traj_per_group: T of the step kernel, as in the forward call: it changes speed, never a bit.
+ *   work:   caller-provided DEVICE memory, batch x work_doubles_per_traj doubles (the _grad figure where a gradient
+ *           other than x0's is wanted or in RECONDENSE mode), packed arrays of the batch.  Nothing is allocated.
+ * EVERY pointer is a DEVICE pointer.  Asynchronous: everything is queued on `stream` (NULL: the handle's stream) and the
+ * call returns.  Every argument error is FBSTAB_HIP_ERR_ARGUMENT and checked before any device call, what needs no
+ * handle first, in the order of fbstab_hip_mpc_condensed_receding_sweep: the sizes, the batch and the data block; NULL
+ * dense, plant, log, grad, status, work; steps < 0; mode; traj_per_group < 0; the condensed images; the plant; the
+ * required log slots; the gradient strides; the map (AFFINE mode) - then the handle.  batch == 0 returns OK and queues
+ * nothing; steps == 0 writes zeros to every non-NULL output slot and returns OK.
+ * fbstab_hip_mpc_condensed_sweep_adjoint_sizes: with e(n) = n rounded up to even, nzc = (N + 1) nu, nv = (N + 1) nc,
+ *   lds_bytes = that of fbstab_hip_mpc_condensed_sweep_sizes (the step kernel; shared_map as there)
+ *   work_doubles_per_traj      = 4 nzc + 2 nv + 2 nx + 1     (gU, dU, rU, eU; dv, ev; mu, -dl0; two status words)
+ *   work_doubles_per_traj_grad = that + 2 (N + 1)(nx + nu) + (N + 1) nx       (z and the zeros of gz; l)
+ * Not here: the device-side reduced form for shared parameters, forward mode through the sweep, seeds on the rest of
+ * U_k and v_k, reuse of the forward call's images and map, per-step references, sharded calls, the C++ facade. */
+int fbstab_hip_mpc_condensed_sweep_adjoint_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
+                                                 int* traj_per_group_used, long long* lds_bytes,
+                                                 long long* work_doubles_per_traj,
+                                                 long long* work_doubles_per_traj_grad);
+int fbstab_hip_mpc_condensed_receding_sweep_adjoint(
+    fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+    const fbstab_dense_batch_t* dense, const fbstab_condensed_map_t* map, const fbstab_receding_plant_t* plant,
+    int steps, int retire, const fbstab_condensed_sweep_log_t* log, const double* gu, const double* gx, double sigma,
+    const fbstab_mpc_grad_batch_t* grad, double* gf0, double* gb0, double* mu_log, int* status, int mode,
+    int traj_per_group, double* work, void* stream);
 
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);
