@@ -276,7 +276,10 @@ __device__ __noinline__ bool receding_plant_step(const SweepArgs* sweep, const f
   return gone;
 }
 
-template <class P, bool KEEP>
+// ORDERED (the batch solve kernels): ticket t of the queue word is QP order[t] where the launch brings an order -
+// the handle's QP indices by descending Newton count of its previous solve of this batch, longest first, so that
+// the launch drains on its shortest QPs (fb_queue_order.h; null: index order).
+template <class P, bool KEEP, bool ORDERED = false>
 struct R16Queue {
   // Only launch-uniform values live in here (SGPRs): the sweeps have no registers
   // to spare (a handful of VGPRs held across the Newton step turned 2 spilled
@@ -292,6 +295,7 @@ struct R16Queue {
   int swept = 0;
   const SweepArgs* sweep = nullptr;
   fbstab_solver_out_t* out = nullptr;
+  const int* order = nullptr;  // (ORDERED) [batch], a permutation of 0 .. batch-1, or null
 
   static __device__ __forceinline__ int tid() { return threadIdx.x & (P::LPQ - 1); }
   static __device__ __forceinline__ int row() { return threadIdx.x / P::LPQ; }  // QP slot of the wavefront
@@ -346,7 +350,12 @@ struct R16Queue {
       // a batch that does not outnumber the launch's wavefronts: one QP per wavefront (fbstab_hip.hip sizes
       // the grid to the batch then); the other rows only lend their lanes to the cooperative passes
       if (batch <= (int)gridDim.x && row() != 0) return -1;
-      if (tid() == 0) q = atomicAdd(&ctl[0], 1);
+      if (tid() == 0) {
+        q = atomicAdd(&ctl[0], 1);
+        // (the ticket is checked before it indexes: the rows that find the queue dry hold tickets past the batch)
+        if constexpr (ORDERED)
+          if (order != nullptr && q < batch) q = order[q];
+      }
       q = bcri<P::LPQ / 16, 0>(q);
     }
     if (q >= batch) return -1;
@@ -386,7 +395,10 @@ __global__ __launch_bounds__(64, 1) FB_R16_REG_ATTR void fbstab_mpc_r16_kernel(
   typename P::C ctx;
   ctx.tid = lane & (P::LPQ - 1);
   P p;
-  R16Queue<P, KEEP> qu;
+  // (the batch solve instance has no other use for `dbg`: the order of its queue, or null - fbstab_hip.hip)
+  constexpr bool kOrdered = !KEEP && !DBG;
+  R16Queue<P, KEEP, kOrdered> qu;
+  if constexpr (kOrdered) qu.order = reinterpret_cast<const int*>(dbg);
   qu.data = &data;
   qu.x = &x;
   qu.ctl = counter;

@@ -33,6 +33,7 @@
 #include "fb_mpc_r16.h"
 #include "fb_record_kernel.h"
 #include "fb_tangent.h"
+#include "fb_queue_order.h"
 
 #if defined(FB_ANY_STAMP)
 namespace fbk { __device__ unsigned long long g_stamps[32]; }
@@ -526,6 +527,13 @@ struct fbstab_mpc_solver : SolverBase {
   // one-launch kernel (nz doubles per row slot of the grid) and the per-step form's image of one step
   double* sweep_seed = nullptr;
   double* sweep_tmp = nullptr;
+  // The longest-first queue (fb_queue_order_plan.h): whether this handle keeps an order at all (record handles,
+  // FBSTAB_HIP_QUEUE_ORDER at creation), the QP indices by descending Newton count of the last packed batch solve
+  // (max_batch ints, written by fbstab_mpc_queue_order_kernel behind that solve; the kernel's counters behind them:
+  // queue_order_ints), and the batch size they are valid for, or -1
+  bool queue_order = false;
+  int* order = nullptr;
+  int order_batch = -1;
   // What this handle launches (mpc_resolve_kernels).  solve_keep: record handles only; adjoint: on the record or
   // the flat-vector kernel (`record`); sweep_adjoint: null where the sweep adjoint runs per step; kkt_multi: the
   // flat-vector kernel of fb_kkt_multi.hip on every handle.
@@ -538,6 +546,7 @@ struct fbstab_mpc_solver : SolverBase {
     if (adj_scratch) (void)hipFree(adj_scratch);
     if (sweep_seed) (void)hipFree(sweep_seed);
     if (sweep_tmp) (void)hipFree(sweep_tmp);
+    if (order) (void)hipFree(order);
   }
   // Grid of a batch launch of entry `e` (fbk::batch_grid: a record kernel's small batches are spread)
   int batch_grid(const MpcKernel& e, int batch) const {
@@ -834,6 +843,8 @@ int fbstab_hip_mpc_create_in_flight(int N, int nx, int nu, int nc, int max_batch
   s->scratch_bytes = plan.scratch_bytes;
   hipError_t e = hipMalloc(&s->scratch, (size_t)s->scratch_bytes);
   if (e != hipSuccess) return fail(FBSTAB_HIP_ERR_DEVICE, std::string("scratch allocation: ") + hipGetErrorString(e));
+  s->queue_order = s->rec != nullptr && fbk::queue_order_knob();
+  if (s->queue_order) HIP_TRY(hipMalloc(&s->order, sizeof(int) * fbk::queue_order_ints(max_batch)));
   const fbk::MpcLayout& L = s->lay;
   s->arr_len = {(long long)(N + 1) * nx * nx, (long long)(N + 1) * nu * nu,
                 (long long)(N + 1) * nu * nx, (long long)(N + 1) * nx, (long long)(N + 1) * nu,
@@ -878,8 +889,22 @@ static int mpc_solve_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_bat
     MpcKernel& e = d_trace ? h->kern.traced : keep ? h->kern.solve_keep : h->kern.solve;
     // (the traced solve: the call's one QP on one workgroup, `d_trace` in the probe's place)
     const int grid = keep ? fbk::keep_grid(batch, h->qps_per_wg) : h->batch_grid(e, batch);
-    RC_TRY(launch_mpc(h, e, grid, s, a, v, d_out, batch, d_trace, reuse));
+    // The batch solve of a record instance, packed: its tickets go out in the order the previous solve of this
+    // batch left (longest QP first; the kernel's `dbg`, which the untraced batch instance has no other use for),
+    // and its own Newton counts are sorted behind it for the next one (fb_queue_order_plan.h)
+    const bool record_batch_solve = !d_trace && !keep && e.record;
+    const bool spread = fbk::record_spreads(batch, grid);
+    const bool ordered = fbk::queue_order_applies(h->queue_order, record_batch_solve, spread, batch, h->order_batch);
+    double* const dbg = ordered ? reinterpret_cast<double*>(h->order) : d_trace;
+    RC_TRY(launch_mpc(h, e, grid, s, a, v, d_out, batch, dbg, reuse));
     if (!d_trace) h->kept_batch = keep ? batch : -1;  // (the traced solve leaves the slots alone)
+    if (fbk::queue_order_sorts(h->queue_order, record_batch_solve, spread, batch)) {
+      h->order_batch = -1;  // (until the kernel that writes the new one is queued)
+      hipLaunchKernelGGL(fbk::fbstab_mpc_queue_order_kernel, dim3(1), dim3(fbk::kQueueOrderThreads), 0, s, d_out, batch,
+                         h->order, h->order + h->max_batch);
+      HIP_TRY(hipGetLastError());
+      h->order_batch = batch;
+    }
     return FBSTAB_HIP_OK;
   };
   auto launch_norms = [=](hipStream_t s, const fbstab_mpc_batch_t& a, const fbstab_var_batch_t& v, double* dn) {
@@ -2334,6 +2359,21 @@ int fbstab_hip_mpc_refined_steps(fbstab_mpc_handle_t h, long long* steps) {
   int n = 0;  // word 1 of the queue block (zeroed before every launch): R16Queue::count_refinement, fb_mpc.h
   HIP_TRY(hipMemcpy(&n, h->counter + 1, sizeof(n), hipMemcpyDeviceToHost));
   *steps = n;
+  return FBSTAB_HIP_OK;
+}
+
+int fbstab_hip_mpc_queue_order(fbstab_mpc_handle_t h, int* order, int capacity, int* n) {
+  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null solver handle");
+  if (!n) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null output pointer");
+  *n = 0;
+  if (h->order_batch < 0) return FBSTAB_HIP_OK;
+  if (!order || capacity < h->order_batch) return fail(FBSTAB_HIP_ERR_ARGUMENT, "order array smaller than the stored order");
+  HIP_TRY(hipSetDevice(h->device));
+  // (waits for the solve whose counts the order holds and for the kernel behind it: both are inside the timed
+  // section of their call, on whatever stream it ran)
+  if (h->timed) HIP_TRY(hipEventSynchronize(h->ev1));
+  HIP_TRY(hipMemcpy(order, h->order, sizeof(int) * (size_t)h->order_batch, hipMemcpyDeviceToHost));
+  *n = h->order_batch;
   return FBSTAB_HIP_OK;
 }
 

@@ -252,6 +252,8 @@ def load_library() -> C.CDLL:
             C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_queue_order"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_queue_order.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.fbstab_hip_mpc_receding_sweep.argtypes = [
         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -288,7 +290,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_get_options", "fbstab_hip_mpc_solve_batch", "fbstab_hip_mpc_solve_batch_final",
     "fbstab_hip_mpc_solve_traced", "fbstab_hip_mpc_receding_sweep",
     "fbstab_hip_mpc_last_kernel_ms", "fbstab_hip_mpc_query", "fbstab_hip_mpc_kernel_name",
-    "fbstab_hip_mpc_refined_steps", "fbstab_hip_mpc_create_in_flight",
+    "fbstab_hip_mpc_refined_steps", "fbstab_hip_mpc_queue_order", "fbstab_hip_mpc_create_in_flight",
     "fbstab_hip_mpc_debug_newton", "fbstab_hip_mpc_adjoint_batch", "fbstab_hip_mpc_adjoint_kernel_name",
     "fbstab_hip_mpc_adjoint_batch_reduced", "fbstab_hip_mpc_tangent_batch", "fbstab_hip_debug_stamps",
     "fbstab_hip_mpc_receding_sweep_logged", "fbstab_hip_mpc_receding_sweep_adjoint",
@@ -668,6 +670,7 @@ class FBstabMpcBatch(_SolverBase):
         else:  # (a build of an earlier round, loaded for an A/B)
             _check(self._lib, self._lib.fbstab_hip_mpc_create(N, nx, nu, nc, max_batch, device, C.byref(self._h)))
         self.N, self.nx, self.nu, self.nc = N, nx, nu, nc
+        self.max_batch = max_batch
         self.nz, self.nl, self.nv = (N + 1) * (nx + nu), (N + 1) * nx, (N + 1) * nc
         self.seq_len = [(N + 1) * nx * nx, (N + 1) * nu * nu, (N + 1) * nu * nx,
                         (N + 1) * nx, (N + 1) * nu, N * nx * nx, N * nx * nu, N * nx,
@@ -691,6 +694,15 @@ class FBstabMpcBatch(_SolverBase):
         n = C.c_longlong(-1)
         _check(self._lib, self._lib.fbstab_hip_mpc_refined_steps(self._h, C.byref(n)))
         return int(n.value)
+
+    def queue_order(self) -> np.ndarray:
+        """The order in which the next batch solve of the same size hands out its queue tickets: the QP indices
+        of the last packed batch solve by descending Newton count (fbstab_hip_mpc_queue_order); empty where the
+        handle holds none."""
+        order = np.zeros(self.max_batch, dtype=np.int32)
+        n = C.c_int(0)
+        _check(self._lib, self._lib.fbstab_hip_mpc_queue_order(self._h, order.ctypes.data, order.size, C.byref(n)))
+        return order[:n.value].copy()
 
     def Solve(self, data: Dict[str, object], z, l, v, y, out=None, stream: int = 0,
               async_: bool = False, keep_matrices: bool = False):

@@ -274,6 +274,22 @@ const char* fbstab_hip_mpc_kernel_name(fbstab_mpc_handle_t handle);
  * 0 with the option off). */
 int fbstab_hip_mpc_refined_steps(fbstab_mpc_handle_t handle, long long* steps);
 
+/* The longest-first queue of a record handle.  The rows of a packed batch launch pull QP indices from a queue,
+ * and a wavefront lives until the slowest of its rows is done; with the longest QPs handed out first a launch
+ * drains on its shortest ones.  A record handle therefore remembers the Newton counts of its last packed
+ * fbstab_hip_mpc_solve_batch[_final] - one kernel of one workgroup behind the solve sorts the QP indices by them,
+ * descending, ascending index inside equal counts - and the next such solve of the SAME batch size hands its queue
+ * tickets out in that order: the case of a controller that calls the handle with the same plants one time step
+ * later, whose counts follow the previous step's (rank correlation 0.9).  The order is a hint and nothing else: a
+ * QP's results do not depend on when or where in the launch it is solved, bit for bit, so a stale order costs the
+ * gain only.  A solve of another batch size installs its own order; spread launches (batch <= the handle's
+ * workgroups), FBSTAB_HIP_KEEP_MATRICES solves, sweeps, adjoints, tangents, many-right-hand-side solves and probes
+ * neither use nor change it.  FBSTAB_HIP_QUEUE_ORDER=0 in the environment when the handle is created switches it
+ * off.  Footprint: max_batch + 1024 ints.
+ * This call copies the stored order to the host array `order` of `capacity` ints (waits for the solve that
+ * produced it): *n = its batch size, or 0 where the handle holds none (then `order` may be NULL). */
+int fbstab_hip_mpc_queue_order(fbstab_mpc_handle_t handle, int* order, int capacity, int* n);
+
 /* Diagnostics used by the parity tests: runs ONE Newton step of the device path
  * (LinearSolver::Initialize + Solve of the reference, abstract_components.h:291-338)
  * for a single QP given by host pointers.  io: [zbar, lbar, vbar] in,
