@@ -23,32 +23,9 @@
 #pragma once
 
 #include "fb_batch.h"
+#include "fb_condense_plan.h"  // (condense_ld, CondenseLds)
 
 namespace fbk {
-
-inline int condense_ld(int rows) { return rows | 1; }
-
-// Where the images of one stage and what is carried from stage to stage lie in w (offsets in doubles, all even).
-//   window: A, Q (ldx x nx each), B (ldx x nu), E (ldc x nx), S (ldu x nx), L (ldc x nu), R (ldu x nu)
-//   carry:  the larger of  (N + 2) ldx nu                       - X_k^(k+1 .. N) and two P (condense_matrices)
-//                     and  (N + 1) (nx + nu + nc) + 2 nx        - x, u, v of every stage and two p / l (the others)
-// with ldx = nx | 1, ldc = nc | 1, ldu = nu | 1 and every piece rounded up to an even number of doubles.
-struct CondenseLds {
-  int ldx, ldc, ldu;
-  int A, Q, B, E, S, L, R, carry, total;
-  void init(int N, int nx, int nu, int nc) {
-    ldx = condense_ld(nx); ldc = condense_ld(nc); ldu = condense_ld(nu);
-    long long o = 0;
-    auto take = [&o](long long n) { const long long at = o; o += n + (n & 1); return (int)at; };
-    A = take((long long)ldx * nx); Q = take((long long)ldx * nx); B = take((long long)ldx * nu);
-    E = take((long long)ldc * nx); S = take((long long)ldu * nx); L = take((long long)ldc * nu);
-    R = take((long long)ldu * nu);
-    const long long m = (long long)(N + 2) * (ldx * nu + ((ldx * nu) & 1));
-    const long long v = (long long)(N + 1) * (nx + nu + nc) + 2LL * nx + 8;  // (each of the 5 pieces even)
-    carry = take(m > v ? m : v);
-    total = o > 0x3fffffff ? 0x3fffffff : (int)o;
-  }
-};
 
 // dst (rows x cols, leading dimension ld) = the contiguous column-major image src: as tangent_stage, thread c.tid
 // takes the 16-byte pairs c.tid, c.tid + C::nt, ... counted from the first 16-byte boundary of src.  The caller

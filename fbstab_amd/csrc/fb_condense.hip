@@ -63,12 +63,12 @@ __global__ __launch_bounds__(NT) void fbstab_mpc_expand_kernel(int N, int nx, in
 
 }  // namespace fbk
 
-// which: 0 - H_c and A_c, 1 - f_c and b_c, 2 - expand.  *threads: the workgroup size of all three.
-__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(int which, int* threads) {
+// *threads: the workgroup size of all three.
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseKernel which, int* threads) {
   *threads = fbk::kCondenseThreads;
   switch (which) {
-    case 0: return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_matrices_kernel<fbk::kCondenseThreads>);
-    case 1: return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_vectors_kernel<fbk::kCondenseThreads>);
+    case fbk::kCondenseMatrices: return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_matrices_kernel<fbk::kCondenseThreads>);
+    case fbk::kCondenseVectors: return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_vectors_kernel<fbk::kCondenseThreads>);
     default: return reinterpret_cast<const void*>(fbk::fbstab_mpc_expand_kernel<fbk::kCondenseThreads>);
   }
 }

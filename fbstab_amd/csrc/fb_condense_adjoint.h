@@ -27,14 +27,9 @@
 
 #include "fb_adjoint.h"
 #include "fb_condense.h"
+#include "fb_condense_plan.h"  // (CondenseAdjointWork)
 
 namespace fbk {
-
-// The caller's work array, per QP: U, gU, dU of (N + 1) nu doubles and gv_c, dv of (N + 1) nc, then the refinement's
-// rU, eU of (N + 1) nu and ev of (N + 1) nc, each one packed array of the batch (QP q at base + q * length).
-struct CondenseAdjointWork {
-  double *U, *gU, *dU, *gv, *dv, *rU, *eU, *ev;
-};
 
 // One step of iterative refinement of the dense step, around a second launch of the dense adjoint.  The dense adjoint
 // eliminates dv: it factors K = H_c + sigma I + A_c' Gamma A_c with Gamma = C / mus up to 1 / sigma on active rows, so

@@ -75,15 +75,14 @@ __global__ __launch_bounds__(NT) void fbstab_mpc_condensed_adjoint_correct_kerne
 
 }  // namespace fbk
 
-// which: 0 - the seed kernel, 1 - the finish kernel, 2 - the residual kernel, 3 - the correction kernel.  *threads: the
-// workgroup size of all four.
-__attribute__((visibility("hidden"))) const void* fbstab_condense_adjoint_kernel(int which, int* threads) {
+// *threads: the workgroup size of all four.
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseAdjointKernel which, int* threads) {
   *threads = fbk::kCondenseAdjointThreads;
-  if (which == 0)
+  if (which == fbk::kCondenseAdjSeed)
     return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_seed_kernel<fbk::kCondenseAdjointThreads>);
-  if (which == 2)
+  if (which == fbk::kCondenseAdjResidual)
     return reinterpret_cast<const void*>(fbk::fbstab_mpc_condensed_adjoint_residual_kernel<fbk::kCondenseAdjointThreads>);
-  if (which == 3)
+  if (which == fbk::kCondenseAdjCorrect)
     return reinterpret_cast<const void*>(fbk::fbstab_mpc_condensed_adjoint_correct_kernel<fbk::kCondenseAdjointThreads>);
   return reinterpret_cast<const void*>(fbk::fbstab_mpc_condensed_adjoint_finish_kernel<fbk::kCondenseAdjointThreads>);
 }

@@ -17,27 +17,9 @@
 #pragma once
 
 #include "fb_condense_adjoint.h"
+#include "fb_condense_plan.h"  // (condense_multi_per, condense_multi_rule, CondenseMultiWork)
 
 namespace fbk {
-
-// Doubles of one right-hand side's copy of the carry region (even).
-inline long long condense_multi_per(int N, int nx, int nu, int nc) {
-  auto e = [](long long n) { return n + (n & 1); };
-  const long long n1 = N + 1;
-  const long long seed = e(n1 * nx) + 2 * e(nx);
-  const long long fin = e(n1 * (nx + nu)) + e(n1 * nc) + 2 * e(nx);
-  return seed > fin ? seed : fin;
-}
-
-// The library's rule for the right-hand sides per workgroup: clamp(256 / nx, 1, nrhs), lowered until the launch's
-// dynamic LDS - `window` doubles of stage images and R copies of `per` - lets two workgroups share a CU (80 KB).
-inline int condense_multi_rule(int nx, int nrhs, long long window, long long per) {
-  int R = 256 / nx;
-  if (R > nrhs) R = nrhs;
-  if (R < 1) R = 1;
-  while (R > 1 && (window + R * per) * 8 > 80 * 1024) R--;
-  return R;
-}
 
 // The seeds of one QP: right-hand side k of slot i at base + k * rhs_stride, a null gl or gv is zero; or, in x0 mode,
 // right-hand side k is gz = 0, gl = -e_k in the l_0 block, gv = 0 (the tangent's seeds for dx0 = e_k), generated here.
@@ -49,12 +31,6 @@ struct CondenseMultiSeeds {
   FB_DEV double z(int k, long i) const { return x0_mode ? 0.0 : gz[k * rz + i]; }
   FB_DEV double l(int k, long i) const { return x0_mode ? (i == k ? -1.0 : 0.0) : (gl ? gl[k * rl + i] : 0.0); }
   FB_DEV double v(int k, long i) const { return x0_mode ? 0.0 : (gv ? gv[k * rv + i] : 0.0); }
-};
-
-// The caller's work array: U of (N + 1) nu doubles per QP, then gU, dU, rU, eU of nrhs (N + 1) nu and gv_c, dv, ev of
-// nrhs (N + 1) nc, each one packed [batch][nrhs][n] array.
-struct CondenseMultiWork {
-  double *U, *gU, *dU, *rU, *eU, *gv, *dv, *ev;
 };
 
 // Right-hand sides k0 .. k0 + Rg - 1 of one QP: gU and gv_c (right-hand side k at gU + k nzc, gvc + k nv), and U

@@ -112,15 +112,14 @@ __global__ __launch_bounds__(NT) void fbstab_mpc_condense_multi_finish_kernel(
 
 }  // namespace fbk
 
-// which: 0 - the seed kernel, 1 - the finish kernel, 2 - the residual kernel, 3 - the correction kernel.  *threads: the
-// workgroup size of all four.
-__attribute__((visibility("hidden"))) const void* fbstab_condense_multi_kernel(int which, int* threads) {
+// *threads: the workgroup size of all four.
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseMultiKernel which, int* threads) {
   *threads = fbk::kCondenseMultiThreads;
-  if (which == 0)
+  if (which == fbk::kCondenseMultiSeed)
     return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_multi_seed_kernel<fbk::kCondenseMultiThreads>);
-  if (which == 2)
+  if (which == fbk::kCondenseMultiResidual)
     return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_multi_residual_kernel<fbk::kCondenseMultiThreads>);
-  if (which == 3)
+  if (which == fbk::kCondenseMultiCorrect)
     return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_multi_correct_kernel<fbk::kCondenseMultiThreads>);
   return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_multi_finish_kernel<fbk::kCondenseMultiThreads>);
 }

@@ -25,6 +25,7 @@
 #pragma once
 
 #include "fb_condense.h"
+#include "fb_condense_plan.h"  // (CondenseSweepLds, CondenseSweepStep)
 
 namespace fbk {
 
@@ -101,66 +102,6 @@ FB_DEV void condense_x0_map(const C& c, int N, int nx, int nu, int nc, int c0, i
 }
 
 // ---- the step between two solves -----------------------------------------------------------------------------
-// Where the pieces of a workgroup of T trajectories lie in w (offsets in doubles, all even): the shared image M with
-// leading dimension ldm = ne | 1 (m_lds: it is staged; 0: every M is read from memory), then per trajectory the state
-// the step was solved for, the next state, U, v, and a word for `gone`.
-constexpr long long condense_sweep_even(long long n) { return n + (n & 1); }
-struct CondenseSweepLds {
-  int ldm, m_lds, T;
-  int M, x, xn, U, v, gone, total;
-  long long m_doubles, per;
-  // T = 0 asks for the rule: ceil(1024 / ne) trajectories (four rounds of the 256 threads over the entries of f_c and
-  // b_c, so that staging a shared M costs a fraction of using it), at most 64, lowered until the workgroup takes no
-  // more than 80 KB (two workgroups per CU).  A shared M is staged where it leaves room for one trajectory in 80 KB.
-  void init(int N, int nx, int nu, int nc, int want_T, bool stage_m) {
-    const long long nzc = (long long)(N + 1) * nu, nv = (long long)(N + 1) * nc, ne = nzc + nv;
-    const long long budget = 80 * 1024 / 8;
-    per = 2 * condense_sweep_even(nx) + condense_sweep_even(nzc) + condense_sweep_even(nv) + 2;
-    ldm = (int)(ne | 1);
-    m_doubles = condense_sweep_even((long long)ldm * nx);
-    m_lds = (stage_m && m_doubles + per <= budget) ? 1 : 0;
-    const long long m = m_lds ? m_doubles : 0;
-    long long t = want_T;
-    if (t <= 0) {
-      t = (1024 + ne - 1) / ne;
-      if (t > 64) t = 64;
-      while (t > 1 && m + t * per > budget) t--;
-    }
-    if (t < 1) t = 1;
-    T = (int)t;
-    long long at = 0;
-    auto take = [&at](long long n) { const long long a = at; at += n; return (int)(a > 0x3fffffff ? 0x3fffffff : a); };
-    M = take(m);
-    x = take((long long)T * condense_sweep_even(nx));
-    xn = take((long long)T * condense_sweep_even(nx));
-    U = take((long long)T * condense_sweep_even(nzc));
-    v = take((long long)T * condense_sweep_even(nv));
-    gone = take(2LL * T);
-    total = at > 0x3fffffff ? 0x3fffffff : (int)at;
-  }
-};
-
-// What one launch of the step kernel works on: step k's shares of the logs (null: not logged), and the packed work
-// arrays U [batch][nzc], v [batch][nv], gone [batch] the dense solve reads its guess from and writes its point to.
-struct CondenseSweepStep {
-  int N, nx, nu, nc, batch;
-  int retire, shift, affine;     // shift, affine: 0 behind the last step
-  const fbstab_solver_out_t* out;
-  int* gone;
-  double *U, *v;
-  double* x0; long long sx0;     // the caller's x0, advanced in place
-  double* xkeep;                 // null, or [batch][nx]: receives the state the step was solved for
-  const double *Ap, *Bp; long long sAp, sBp;
-  const double* w;               // null, or this step's disturbances [batch][nx]
-  double *u_log, *x_log, *U_log, *v_log;
-  int *eflag_log, *newton_log;
-  const double* M; long long sM;
-  const double* f0; long long sf0;
-  const double* b0; long long sb0;
-  double* f; long long sf;
-  double* b; long long sb;
-};
-
 // Trajectories t0 .. t0 + Tg of the batch, Tg <= L.T.  No synchronisation is needed behind it.
 template <class C, class P>
 FB_DEV void condense_sweep_step(const C& c, const CondenseSweepStep& a, const CondenseSweepLds& L, long t0, int Tg,

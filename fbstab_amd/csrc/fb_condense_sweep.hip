@@ -56,12 +56,12 @@ __global__ __launch_bounds__(NT) void fbstab_mpc_condensed_sweep_begin_kernel(in
 
 }  // namespace fbk
 
-// which: 0 - the x0 map, 1 - the step, 2 - the begin kernel.  *threads: the workgroup size of all three.
-__attribute__((visibility("hidden"))) const void* fbstab_condense_sweep_kernel(int which, int* threads) {
+// *threads: the workgroup size of all three.
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepKernel which, int* threads) {
   *threads = fbk::kCondenseSweepThreads;
   switch (which) {
-    case 0: return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_x0_map_kernel<fbk::kCondenseSweepThreads>);
-    case 1: return reinterpret_cast<const void*>(fbk::fbstab_mpc_condensed_sweep_step_kernel<fbk::kCondenseSweepThreads>);
+    case fbk::kCondenseSweepX0Map: return reinterpret_cast<const void*>(fbk::fbstab_mpc_condense_x0_map_kernel<fbk::kCondenseSweepThreads>);
+    case fbk::kCondenseSweepStep: return reinterpret_cast<const void*>(fbk::fbstab_mpc_condensed_sweep_step_kernel<fbk::kCondenseSweepThreads>);
     default: return reinterpret_cast<const void*>(fbk::fbstab_mpc_condensed_sweep_begin_kernel<fbk::kCondenseSweepThreads>);
   }
 }

@@ -31,35 +31,10 @@
 #pragma once
 
 #include "fb_condense_adjoint.h"
+#include "fb_condense_plan.h"  // (CondenseSweepAdjStep, CondenseSweepAdjFinish)
 #include "fb_condense_sweep.h"
 
 namespace fbk {
-
-// What one launch of the step kernel works on.  close / open: which parts run (the first launch only opens, the last
-// only closes).  The arrays of the closed step k + 1 and of the opened step k are their shares of the logs.
-struct CondenseSweepAdjStep {
-  int N, nx, nu, nc, batch;
-  int close, open, affine;        // affine: lambda through M and f_c, b_c from the map; 0: dl0 and the vectors launch
-  const int* eflag_close;         // eflag_log[k + 1]
-  const int* eflag_open;          // eflag_log[k]
-  const int *st1, *st2;           // the dense adjoint's status of both launches of step k + 1
-  int* status;                    // [batch], += 1 where either is set on a step that would contribute
-  const double *dU, *dv;          // the refined dense step of step k + 1, packed [batch][nzc], [batch][nv]
-  double* dl0;                    // affine == 0: [batch][nx], -dl[0:nx] of the finish of step k + 1; zeroed by open
-  double* mu;                     // [batch][nx]: mu of the open step, read back by the close of the next launch
-  const double *Ap, *Bp; long long sAp, sBp;
-  const double *gu, *gx;          // gu[k] [batch][nu], gx[k] [batch][nx]; null: zero
-  double* mu_log;                 // null, or mu_log[k]
-  double* gU;                     // [batch][nzc]: the seed of the dense adjoint of step k
-  const double* x_log;            // x_log[k]
-  const double* M; long long sM;
-  const double* f0; long long sf0;
-  const double* b0; long long sb0;
-  double* f; long long sf;
-  double* b; long long sb;
-  double *gf0, *gb0;              // null, or packed [batch][nzc], [batch][nv]: sums of -dU and dv
-  double* gx0; long long sgx0;    // null, or the x0 slot: the final lambda (written by the launch that does not open)
-};
 
 // Trajectories t0 .. t0 + Tg of the batch, Tg <= L.T.  No synchronisation is needed behind it.
 template <class C, class P>
@@ -188,15 +163,6 @@ FB_DEV void condense_sweep_adjoint_step(const C& c, const CondenseSweepAdjStep& 
     else a.b[q * a.sb + (e - nzc)] = a.b0[q * a.sb0 + (e - nzc)] + acc;
   }
 }
-
-// What the finish kernel reads of one step: the logged point, the dense step, and who contributes.
-struct CondenseSweepAdjFinish {
-  const double *x, *U, *v;        // x_log[k], U_log[k], v_log[k], packed
-  const double *dU, *dv;          // the refined dense step, packed
-  const int *eflag, *st1, *st2;   // eflag_log[k] and the dense adjoint's status of both launches
-  double *z, *l, *gz;             // scratch [batch][nz], [batch][nl], and the zeros [batch][nz]
-  double* dl0;                    // null, or [batch][nx] (zero on entry): receives -dl[0:nx]
-};
 
 // One trajectory, one step: condense_expand of the logged point (U, v) at the state xk into (z, l), then the
 // accumulating finish with the dense step (dU, dv), gl = 0 and gz = zeros (the finish reads its x entries alone).

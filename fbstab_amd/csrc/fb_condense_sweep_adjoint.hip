@@ -61,14 +61,14 @@ __global__ __launch_bounds__(NT) void fbstab_mpc_condensed_sweep_adjoint_begin_k
 
 }  // namespace fbk
 
-// which: 0 - the step kernel, 1 - the finish kernel, 2 - the begin kernel.  *threads: the workgroup size of all three.
-__attribute__((visibility("hidden"))) const void* fbstab_condense_sweep_adjoint_kernel(int which, int* threads) {
+// *threads: the workgroup size of all three.
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepAdjKernel which, int* threads) {
   *threads = fbk::kCondenseSweepAdjointThreads;
   switch (which) {
-    case 0:
+    case fbk::kCondenseSweepAdjStep:
       return reinterpret_cast<const void*>(
           fbk::fbstab_mpc_condensed_sweep_adjoint_step_kernel<fbk::kCondenseSweepAdjointThreads>);
-    case 1:
+    case fbk::kCondenseSweepAdjFinish:
       return reinterpret_cast<const void*>(
           fbk::fbstab_mpc_condensed_sweep_adjoint_finish_kernel<fbk::kCondenseSweepAdjointThreads>);
     default:

@@ -19,11 +19,7 @@
 #include "fb_algorithm.h"
 #include "fb_dense.h"
 #include "fb_dense_kkt_multi.h"  // (kDenseKktSeeded; its kernels are fb_dense_kkt_multi.hip's)
-#include "fb_condense.h"         // (CondenseLds; its kernels are fb_condense.hip's)
-#include "fb_condense_adjoint.h" // (CondenseAdjointWork; its kernels are fb_condense_adjoint.hip's)
-#include "fb_condense_multi.h"   // (CondenseMultiWork and the LDS rule; its kernels are fb_condense_multi.hip's)
-#include "fb_condense_sweep.h"   // (CondenseSweepLds, CondenseSweepStep; its kernels are fb_condense_sweep.hip's)
-#include "fb_condense_sweep_adjoint.h"  // (CondenseSweepAdjStep; its kernels are fb_condense_sweep_adjoint.hip's)
+#include "fb_condense_plan.h"  // (the condensed route: its kernels are fb_condense*.hip's, its host side fb_condense_stage.h)
 #include "fb_dense_wave.h"
 #include "fb_final_norms.h"
 #include "fb_grad_reduce.h"
@@ -576,23 +572,14 @@ __attribute__((visibility("hidden"))) const void* fbstab_kkt_multi_kernel(int wg
 // fbstab_dense_kkt_multi_kernel / fbstab_dense_wave_kkt_multi_kernel (fb_dense_kkt_multi.hip, a translation unit of its
 // own): the kernel beside adjoint kernel `which` of dense_resolve_kernels
 __attribute__((visibility("hidden"))) const void* fbstab_dense_kkt_multi_kernel_for(int which);
-// The kernels of fbstab_hip_mpc_condense_batch / fbstab_hip_mpc_expand_batch (fb_condense.hip, a translation unit of
-// its own): which = 0 - H_c and A_c, 1 - f_c and b_c, 2 - expand; *threads: their workgroup size
-__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(int which, int* threads);
-// The kernels of fbstab_hip_mpc_condensed_adjoint_batch (fb_condense_adjoint.hip, a translation unit of its own):
-// which = 0 - the seeds of the dense adjoint, 1 - the finish; *threads: their workgroup size
-__attribute__((visibility("hidden"))) const void* fbstab_condense_adjoint_kernel(int which, int* threads);
-// The kernels of fbstab_hip_mpc_condensed_kkt_solve_batch / _x0_sensitivity_batch (fb_condense_multi.hip, a translation
-// unit of its own): which = 0 - the seeds, 1 - the finish, 2 - the residual, 3 - the correction; *threads: their
-// workgroup size
-__attribute__((visibility("hidden"))) const void* fbstab_condense_multi_kernel(int which, int* threads);
-// The kernels of fbstab_hip_mpc_condensed_x0_map_batch / fbstab_hip_mpc_condensed_receding_sweep (fb_condense_sweep.hip,
-// a translation unit of its own): which = 0 - the x0 map, 1 - the step, 2 - the begin kernel; *threads: their
-// workgroup size
-__attribute__((visibility("hidden"))) const void* fbstab_condense_sweep_kernel(int which, int* threads);
-// The kernels of fbstab_hip_mpc_condensed_receding_sweep_adjoint (fb_condense_sweep_adjoint.hip, a translation unit of
-// its own): which = 0 - the step, 1 - the finish, 2 - the begin kernel; *threads: their workgroup size
-__attribute__((visibility("hidden"))) const void* fbstab_condense_sweep_adjoint_kernel(int which, int* threads);
+// The kernels of the condensed route (fb_condense.hip, fb_condense_adjoint.hip, fb_condense_multi.hip,
+// fb_condense_sweep.hip, fb_condense_sweep_adjoint.hip, a translation unit each): the kernel that the unit's enum of
+// fb_condense_plan.h names; *threads: its workgroup size
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseKernel which, int* threads);
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseAdjointKernel which, int* threads);
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseMultiKernel which, int* threads);
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepKernel which, int* threads);
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepAdjKernel which, int* threads);
 #if defined(FB_SINGLE_TU)
 // (diagnostic builds with device-side counters: one translation unit, one g_stamps)
 #include "rec_12_4_20.hip"
@@ -608,6 +595,33 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_sweep_adjoint_
 #include "fb_condense_sweep.hip"
 #include "fb_condense_sweep_adjoint.hip"
 #endif
+
+// The condensed route (include/fbstab_hip.h): its host side is fb_condense_stage.h, tested on the CPU
+// (tests/test_condense_stage.py); here, what that header is handed: the kernels of the five units, and the dense
+// handle's own entry points on device pointers, asynchronous.
+#include "fb_condense_stage.h"
+
+namespace {
+const auto condense_gpu = [](auto id, int grid, long long lds, void** args, hipStream_t s) {
+  return condense_launch([](auto k, int* threads) { return fbstab_condense_kernel(k, threads); }, id, grid, lds, args, s);
+};
+constexpr int kCondenseDenseFlags = FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC;
+auto condense_dense_adjoint(fbstab_dense_handle_t h) {
+  return [h](int batch, const fbstab_dense_batch_t* dc, const fbstab_var_batch_t* xc, const fbstab_var_batch_t* seeds,
+             double sigma, const fbstab_var_batch_t* adj, int* status, hipStream_t s) {
+    const fbstab_dense_grad_batch_t none = {};  // (no gradients of the condensed data)
+    return fbstab_hip_dense_adjoint_batch(h, batch, dc, xc, seeds, sigma, &none, adj, status, kCondenseDenseFlags, (void*)s);
+  };
+}
+auto condense_dense_multi(fbstab_dense_handle_t h) {
+  return [h](int batch, const fbstab_dense_batch_t* dc, const fbstab_var_batch_t* xc, int nrhs,
+             const fbstab_multi_var_batch_t* seeds, double sigma, const fbstab_multi_var_batch_t* step, int* status,
+             hipStream_t s) {
+    return fbstab_hip_dense_kkt_solve_batch(h, batch, dc, xc, nrhs, seeds, sigma, step, status, kCondenseDenseFlags, (void*)s);
+  };
+}
+}  // namespace
+
 namespace {
 const RecordInstance* record_instances(int* count) {
   static const RecordInstance table[] = {
@@ -1423,427 +1437,34 @@ int fbstab_hip_mpc_x0_sensitivity_batch(fbstab_mpc_handle_t h, int batch, const 
   return kkt_multi_run(h, batch, data, x, 0, nullptr, sigma, step, gain, gain_stride, status, flags, stream);
 }
 
-// ---- condensing (include/fbstab_hip.h; fb_condense.h) -----------------------------------------------------------
-namespace {
-struct CondenseShape {
-  int N, nx, nu, nc;
-  long long len[FBSTAB_MPC_NSEQ];
-  long long nz, nv;
-};
-// What both calls check before any device call: the sizes, the batch, the data block and its strides.
-int condense_check(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data, CondenseShape* sh) {
-  if (N < 1 || nx < 1 || nu < 1 || nc < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: problem sizes must be positive");
-  if (batch < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: negative batch");
-  if (!data) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: null problem data block");
-  const long long n1 = N + 1;
-  const long long len[FBSTAB_MPC_NSEQ] = {n1 * nx * nx, n1 * nu * nu, n1 * nu * nx, n1 * nx, n1 * nu,
-                                          (long long)N * nx * nx, (long long)N * nx * nu, (long long)N * nx,
-                                          n1 * nc * nx, n1 * nc * nu, n1 * nc, nx};
-  *sh = CondenseShape{N, nx, nu, nc, {}, n1 * nu, n1 * nc};
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-    sh->len[i] = len[i];
-    if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: null problem data pointer");
-    if (batch > 1 && data->stride[i] != 0 && data->stride[i] < len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: problem data stride smaller than the array length");
-  }
-  return FBSTAB_HIP_OK;
-}
-// ... and after it: the device, then the LDS rule.  *lds: the dynamic LDS bytes of a launch.
-int condense_device(const CondenseShape& sh, int device, fbk::CondenseLds* o, int* lds) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return fail(FBSTAB_HIP_ERR_DEVICE, "condense: no HIP device");
-  if (device < 0 || device >= n) return fail(FBSTAB_HIP_ERR_DEVICE, "condense: no such device");
-  o->init(sh.N, sh.nx, sh.nu, sh.nc);
-  if ((long long)o->total * 8 > kLdsLimitBytes)
-    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the stage images and dx/du of a horizon do not fit the 160 KiB LDS budget");
-  *lds = o->total * 8;
-  HIP_TRY(hipSetDevice(device));
-  return FBSTAB_HIP_OK;
-}
-int condense_launch(int which, int grid, int lds, void** args, hipStream_t s) {
-  int threads = 0;
-  const void* kern = fbstab_condense_kernel(which, &threads);
-  if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
-  HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(threads), args, (size_t)lds, s));
-  return FBSTAB_HIP_OK;
-}
-}  // namespace
-
+// ---- the condensed route (include/fbstab_hip.h): the runs of fb_condense_stage.h on the real launches -----------
 int fbstab_hip_mpc_condensed_sizes(int N, int nx, int nu, int nc, int* nz, int* nv, long long* lds_bytes) {
-  if (nz) *nz = 0;
-  if (nv) *nv = 0;
-  if (lds_bytes) *lds_bytes = 0;
-  if (N < 1 || nx < 1 || nu < 1 || nc < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: problem sizes must be positive");
-  if ((long long)(N + 1) * nu > 0x7fffffff || (long long)(N + 1) * nc > 0x7fffffff)
-    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the condensed sizes do not fit an int");
-  if (nz) *nz = (N + 1) * nu;
-  if (nv) *nv = (N + 1) * nc;
-  fbk::CondenseLds o;
-  o.init(N, nx, nu, nc);
-  if ((long long)o.total * 8 > kLdsLimitBytes)
-    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the stage images and dx/du of a horizon do not fit the 160 KiB LDS budget");
-  if (lds_bytes) *lds_bytes = (long long)o.total * 8;
-  return FBSTAB_HIP_OK;
+  return condensed_sizes(N, nx, nu, nc, nz, nv, lds_bytes);
 }
 
 int fbstab_hip_mpc_condense_batch(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data, int what,
                                   const fbstab_dense_out_batch_t* dense, int device, void* stream) {
-  CondenseShape sh;
-  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
-  if (what < FBSTAB_CONDENSE_MATRICES || what > FBSTAB_CONDENSE_ALL)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: `what` must be MATRICES (1), VECTORS (2) or ALL (3)");
-  if (!dense) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: null output block");
-  const bool mats = (what & FBSTAB_CONDENSE_MATRICES) != 0, vecs = (what & FBSTAB_CONDENSE_VECTORS) != 0;
-  static const int kMatrixSeq[] = {FBSTAB_MPC_Q, FBSTAB_MPC_R, FBSTAB_MPC_S, FBSTAB_MPC_A,
-                                   FBSTAB_MPC_B, FBSTAB_MPC_E, FBSTAB_MPC_L};
-  bool shared_model = true;
-  for (int i : kMatrixSeq) shared_model = shared_model && data->stride[i] == 0;
-  const long long olen[FBSTAB_DENSE_NARR] = {sh.nz * sh.nz, sh.nz, 0, 0, sh.nv * sh.nz, sh.nv};
-  fbstab_dense_out_batch_t out = {};
-  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
-    const bool matrix = i == FBSTAB_DENSE_H || i == FBSTAB_DENSE_A;
-    if (matrix ? !mats : !vecs) continue;
-    if (!dense->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: null pointer in a selected output slot");
-    if (batch > 1 && dense->stride[i] < olen[i]) {
-      if (!matrix || dense->stride[i] != 0)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: output stride smaller than the array length");
-      if (!shared_model)
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "condense: output stride 0 needs stride 0 on every one of Q, R, S, A, B, E, L");
-    }
-    out.base[i] = dense->base[i];
-    out.stride[i] = batch > 1 ? dense->stride[i] : olen[i];
-  }
-  if (batch == 0) return FBSTAB_HIP_OK;
-  fbk::CondenseLds o;
-  int lds = 0;
-  RC_TRY(condense_device(sh, device, &o, &lds));
-  hipStream_t s = (hipStream_t)stream;
-  fbstab_mpc_batch_t a = *data;
-  if (mats) {
-    // (one image of each for a batch that shares its model: QP 0 alone is launched)
-    const bool one = out.stride[FBSTAB_DENSE_H] == 0 && out.stride[FBSTAB_DENSE_A] == 0;
-    void* args[] = {&N, &nx, &nu, &nc, &o, &a, &out};
-    RC_TRY(condense_launch(0, (one ? 1 : batch) * (N + 1), lds, args, s));
-  }
-  if (vecs) {
-    void* args[] = {&N, &nx, &nu, &nc, &o, &a, &out};
-    RC_TRY(condense_launch(1, batch, lds, args, s));
-  }
-  return FBSTAB_HIP_OK;
+  return condense_run(N, nx, nu, nc, batch, data, what, dense, device, stream, condense_gpu);
 }
 
 int fbstab_hip_mpc_expand_batch(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
                                 const fbstab_var_batch_t* xc, const fbstab_var_batch_t* x, int device, void* stream) {
-  CondenseShape sh;
-  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
-  if (!xc || !x) return fail(FBSTAB_HIP_ERR_ARGUMENT, "expand: null variable block");
-  if (!xc->base[0] || !xc->base[2]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "expand: null U or v pointer");
-  if (x->base[3] && !xc->base[3]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "expand: y is wanted and the condensed y is null");
-  const long long clen[4] = {sh.nz, 0, sh.nv, sh.nv};
-  const long long xlen[4] = {(long long)(N + 1) * (nx + nu), (long long)(N + 1) * nx, sh.nv, sh.nv};
-  fbstab_var_batch_t in = {}, outv = {};
-  for (int i = 0; i < 4; i++) {
-    if (i != 1 && xc->base[i]) {
-      if (batch > 1 && xc->stride[i] < clen[i])
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "expand: stride of the condensed point smaller than the vector length");
-      in.base[i] = xc->base[i];
-      in.stride[i] = batch > 1 ? xc->stride[i] : clen[i];
-    }
-    if (x->base[i]) {
-      if (batch > 1 && x->stride[i] < xlen[i])
-        return fail(FBSTAB_HIP_ERR_ARGUMENT, "expand: variable stride smaller than the vector length");
-      outv.base[i] = x->base[i];
-      outv.stride[i] = batch > 1 ? x->stride[i] : xlen[i];
-    }
-  }
-  if (batch == 0) return FBSTAB_HIP_OK;
-  fbk::CondenseLds o;
-  int lds = 0;
-  RC_TRY(condense_device(sh, device, &o, &lds));
-  fbstab_mpc_batch_t a = *data;
-  void* args[] = {&N, &nx, &nu, &nc, &o, &a, &in, &outv};
-  return condense_launch(2, batch, lds, args, (hipStream_t)stream);
+  return expand_run(N, nx, nu, nc, batch, data, xc, x, device, stream, condense_gpu);
 }
 
-// Reverse-mode derivative of the condensed route (include/fbstab_hip.h; fb_condense_adjoint.h): the seed kernel, the
-// dense handle's own adjoint launch on the condensed QP, one step of iterative refinement of that step (the residual
-// kernel, the dense adjoint again, the correction kernel), the finish kernel - six launches on one stream.
 int fbstab_hip_mpc_condensed_adjoint_batch(fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch,
                                            const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
                                            const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed, double sigma,
                                            const fbstab_mpc_grad_batch_t* grad, const fbstab_var_batch_t* adj,
                                            double* work, int* status, void* stream) {
-  // what needs no handle comes first, in the order of fbstab_hip_mpc_condense_batch
-  CondenseShape sh;
-  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
-  if (!dense || !x || !seed || !grad || !work || !status)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: null argument");
-  const long long dlen[FBSTAB_DENSE_NARR] = {sh.nz * sh.nz, sh.nz, 0, 0, sh.nv * sh.nz, sh.nv};
-  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
-    const bool matrix = i == FBSTAB_DENSE_H || i == FBSTAB_DENSE_A;
-    if (!dense->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: null pointer in the condensed images");
-    if (batch > 1 && dense->stride[i] < dlen[i] && !(matrix && dense->stride[i] == 0))
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: stride of a condensed image smaller than the array length");
-  }
-  const long long xlen[3] = {(long long)(N + 1) * (nx + nu), (long long)(N + 1) * nx, sh.nv};
-  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: null seed pointer (z)");
-  for (int i = 0; i < 3; i++) {
-    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: null variable pointer");
-    if (batch > 1 && x->stride[i] < xlen[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: variable stride smaller than the vector length");
-    if (batch > 1 && seed->base[i] && seed->stride[i] < xlen[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: seed stride smaller than the vector length");
-    if (batch > 1 && adj && adj->base[i] && adj->stride[i] < xlen[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: adjoint stride smaller than the vector length");
-  }
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
-    if (batch > 1 && grad->base[i] && grad->stride[i] < sh.len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: gradient stride smaller than the array length");
-  // ... then the handle
-  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: null dense solver handle");
-  if (h->var_len[0] != sh.nz || h->var_len[1] != 0 || h->var_len[2] != sh.nv)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: the dense handle is not one of ((N + 1) nu, 0, (N + 1) nc)");
-  if (batch > h->max_batch)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed adjoint: batch exceeds the max_batch the handle was created with");
-  if (batch == 0) return FBSTAB_HIP_OK;
-  fbk::CondenseLds o;
-  int lds = 0;
-  RC_TRY(condense_device(sh, h->device, &o, &lds));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  // the blocks as the kernels take them: with batch == 1 the strides are not read by the caller's rule
-  fbstab_mpc_batch_t a = *data;
-  fbstab_var_batch_t xv = {}, sd = {}, ad = {};
-  for (int i = 0; i < 3; i++) {
-    xv.base[i] = x->base[i]; xv.stride[i] = batch > 1 ? x->stride[i] : xlen[i];
-    sd.base[i] = seed->base[i]; sd.stride[i] = batch > 1 ? seed->stride[i] : xlen[i];
-    if (adj) { ad.base[i] = adj->base[i]; ad.stride[i] = batch > 1 ? adj->stride[i] : xlen[i]; }
-  }
-  fbstab_mpc_grad_batch_t g = *grad;
-  fbk::CondenseAdjointWork wk;
-  wk.U = work;
-  wk.gU = wk.U + sh.nz * batch;
-  wk.dU = wk.gU + sh.nz * batch;
-  wk.gv = wk.dU + sh.nz * batch;
-  wk.dv = wk.gv + sh.nv * batch;
-  wk.rU = wk.dv + sh.nv * batch;
-  wk.eU = wk.rU + sh.nz * batch;
-  wk.ev = wk.eU + sh.nz * batch;
-  auto launch = [&](int which, void** args, int bytes) -> int {
-    int threads = 0;
-    const void* kern = fbstab_condense_adjoint_kernel(which, &threads);
-    if (bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
-    HIP_TRY(hipLaunchKernel(kern, dim3(batch), dim3(threads), args, (size_t)bytes, s));
-    return FBSTAB_HIP_OK;
-  };
-  {
-    void* args[] = {&N, &nx, &nu, &nc, &o, &a, &xv, &sd, &wk};
-    RC_TRY(launch(0, args, lds));
-  }
-  {
-    // the dense adjoint at (U, v): no gradients of the condensed data.  First the seeds (gU, gv_c), adj = (dU, dv);
-    // then, behind the residual kernel, the seeds (rU, 0), adj = (eU, ev), which the correction kernel adds.
-    fbstab_var_batch_t xc = {}, sc = {}, ac = {};
-    xc.base[0] = wk.U; xc.stride[0] = sh.nz;
-    xc.base[2] = xv.base[2]; xc.stride[2] = xv.stride[2];
-    sc.base[0] = wk.gU; sc.stride[0] = sh.nz;
-    sc.base[2] = wk.gv; sc.stride[2] = sh.nv;
-    ac.base[0] = wk.dU; ac.stride[0] = sh.nz;
-    ac.base[2] = wk.dv; ac.stride[2] = sh.nv;
-    fbstab_dense_batch_t dc = {};
-    for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
-      dc.base[i] = dense->base[i];
-      dc.stride[i] = batch > 1 ? dense->stride[i] : dlen[i];
-    }
-    const fbstab_dense_grad_batch_t none = {};
-    const int flags = FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC;
-    RC_TRY(fbstab_hip_dense_adjoint_batch(h, batch, &dc, &xc, &sc, sigma, &none, &ac, status, flags, (void*)s));
-    int nzc = (int)sh.nz, nvc = (int)sh.nv;
-    const double *Hc = dc.base[FBSTAB_DENSE_H], *Ac = dc.base[FBSTAB_DENSE_A];
-    long long sH = dc.stride[FBSTAB_DENSE_H], sA = dc.stride[FBSTAB_DENSE_A];
-    double sg = sigma > 0.0 ? sigma : 1e-8;  // (the rule of fbstab_hip_dense_adjoint_batch)
-    void* rargs[] = {&nzc, &nvc, &Hc, &sH, &Ac, &sA, &sg, &wk};
-    RC_TRY(launch(2, rargs, 0));
-    sc.base[0] = wk.rU;
-    sc.base[2] = nullptr;
-    ac.base[0] = wk.eU;
-    ac.base[2] = wk.ev;
-    RC_TRY(fbstab_hip_dense_adjoint_batch(h, batch, &dc, &xc, &sc, sigma, &none, &ac, status, flags, (void*)s));
-    void* cargs[] = {&nzc, &nvc, &wk};
-    RC_TRY(launch(3, cargs, 0));
-  }
-  const int* st = status;
-  void* args[] = {&N, &nx, &nu, &nc, &o, &a, &xv, &sd, &wk, &g, &ad, &st};
-  return launch(1, args, lds);
+  return condensed_adjoint_run(h, N, nx, nu, nc, batch, data, dense, x, seed, sigma, grad, adj, work, status, stream,
+                               condense_gpu, condense_dense_adjoint(h));
 }
-
-// ---- many right-hand sides on the condensed route (include/fbstab_hip.h; fb_condense_multi.h) -------------------
-namespace {
-struct CondenseMultiPlan {
-  fbk::CondenseLds o;
-  int R;
-  long long per, lds_bytes, work;
-};
-// What fbstab_hip_mpc_condensed_multi_sizes documents, behind its argument checks.
-int condense_multi_plan(int N, int nx, int nu, int nc, int nrhs, int rhs_per_group, CondenseMultiPlan* p) {
-  p->o.init(N, nx, nu, nc);
-  if (p->o.total == 0x3fffffff || (long long)p->o.carry * 8 > kLdsLimitBytes)
-    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condensed multi: the stage images do not fit the 160 KiB LDS budget");
-  p->per = fbk::condense_multi_per(N, nx, nu, nc);
-  p->R = rhs_per_group > 0 ? (rhs_per_group < nrhs ? rhs_per_group : nrhs)
-                           : fbk::condense_multi_rule(nx, nrhs, p->o.carry, p->per);
-  p->lds_bytes = 8 * ((long long)p->o.carry + p->R * p->per);
-  if (p->lds_bytes > kLdsLimitBytes)
-    return fail(FBSTAB_HIP_ERR_UNSUPPORTED,
-                "condensed multi: the stage images and rhs_per_group copies of a right-hand side's vectors do not fit the 160 KiB LDS budget");
-  const long long nzc = (long long)(N + 1) * nu, nv = (long long)(N + 1) * nc;
-  p->work = nzc + (long long)nrhs * (4 * nzc + 3 * nv);
-  return FBSTAB_HIP_OK;
-}
-
-// Both entry points behind their own first checks.  seed == nullptr: the x0 mode (nrhs = nx, the seeds generated in
-// the kernels); step may be null there, and gain (null, or nu x nx per QP) is served there only.
-int condensed_multi_run(fbstab_dense_handle_t h, const CondenseShape& sh, int batch, const fbstab_mpc_batch_t* data,
-                        const fbstab_dense_batch_t* dense, const fbstab_var_batch_t* x, int nrhs,
-                        const fbstab_multi_var_batch_t* seed, double sigma, const fbstab_multi_var_batch_t* step,
-                        double* gain, long long gain_stride, int rhs_per_group, double* work, int* status,
-                        void* stream) {
-  int N = sh.N, nx = sh.nx, nu = sh.nu, nc = sh.nc;
-  const bool x0_mode = seed == nullptr;
-  if (!dense || !x || !work || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: null argument");
-  const long long dlen[FBSTAB_DENSE_NARR] = {sh.nz * sh.nz, sh.nz, 0, 0, sh.nv * sh.nz, sh.nv};
-  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
-    const bool matrix = i == FBSTAB_DENSE_H || i == FBSTAB_DENSE_A;
-    if (!dense->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: null pointer in the condensed images");
-    if (batch > 1 && dense->stride[i] < dlen[i] && !(matrix && dense->stride[i] == 0))
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: stride of a condensed image smaller than the array length");
-  }
-  const long long xlen[3] = {(long long)(N + 1) * (nx + nu), (long long)(N + 1) * nx, sh.nv};
-  for (int i = 0; i < 3; i++) {
-    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: null variable pointer");
-    if (batch > 1 && x->stride[i] < xlen[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: variable stride smaller than the vector length");
-  }
-  if (seed) RC_TRY(check_multi_strides(seed, xlen, batch, nrhs, true));
-  if (step) RC_TRY(check_multi_strides(step, xlen, batch, nrhs, false));
-  const long long glen = (long long)nu * nx;
-  if (batch > 1 && gain && gain_stride < glen)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: gain stride smaller than nu x nx");
-  if (rhs_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: negative rhs_per_group");
-  // ... then the handle
-  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: null dense solver handle");
-  if (h->var_len[0] != sh.nz || h->var_len[1] != 0 || h->var_len[2] != sh.nv)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: the dense handle is not one of ((N + 1) nu, 0, (N + 1) nc)");
-  if (batch > h->max_batch)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: batch exceeds the max_batch the handle was created with");
-  if (batch == 0) return FBSTAB_HIP_OK;
-  // ... the device, then the LDS rule
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FBSTAB_HIP_ERR_DEVICE, "condensed multi: no HIP device");
-  if (h->device < 0 || h->device >= ndev) return fail(FBSTAB_HIP_ERR_DEVICE, "condensed multi: no such device");
-  CondenseMultiPlan pl;
-  RC_TRY(condense_multi_plan(N, nx, nu, nc, nrhs, rhs_per_group, &pl));
-  const long long groups = (nrhs + pl.R - 1) / pl.R;
-  if (groups * batch > 0x7fffffffLL)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: batch x groups of right-hand sides exceeds the grid limit");
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  // the blocks as the kernels take them: with batch == 1 or nrhs == 1 the strides are not read by the caller's rule
-  fbstab_mpc_batch_t a = *data;
-  fbstab_var_batch_t xv = {};
-  fbstab_multi_var_batch_t sd = {}, st = {};
-  for (int i = 0; i < 3; i++) {
-    xv.base[i] = x->base[i]; xv.stride[i] = batch > 1 ? x->stride[i] : xlen[i];
-    for (int which = 0; which < 2; which++) {
-      const fbstab_multi_var_batch_t* b = which ? step : seed;
-      fbstab_multi_var_batch_t& k = which ? st : sd;
-      if (!b || !b->base[i]) continue;
-      k.base[i] = b->base[i];
-      k.rhs_stride[i] = nrhs > 1 ? b->rhs_stride[i] : xlen[i];
-      k.stride[i] = batch > 1 ? b->stride[i] : (nrhs - 1) * k.rhs_stride[i] + xlen[i];
-    }
-  }
-  const long long nb = (long long)nrhs * batch;
-  fbk::CondenseMultiWork wk;
-  wk.U = work;
-  wk.gU = wk.U + sh.nz * batch;
-  wk.dU = wk.gU + sh.nz * nb;
-  wk.rU = wk.dU + sh.nz * nb;
-  wk.eU = wk.rU + sh.nz * nb;
-  wk.gv = wk.eU + sh.nz * nb;
-  wk.dv = wk.gv + sh.nv * nb;
-  wk.ev = wk.dv + sh.nv * nb;
-  const int grid = (int)(groups * batch);
-  auto launch = [&](int which, void** args, long long bytes) -> int {
-    int threads = 0;
-    const void* kern = fbstab_condense_multi_kernel(which, &threads);
-    if (bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
-    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(threads), args, (size_t)bytes, s));
-    return FBSTAB_HIP_OK;
-  };
-  int R = pl.R, x0m = x0_mode ? 1 : 0;
-  long long per = pl.per;
-  {
-    void* args[] = {&N, &nx, &nu, &nc, &pl.o, &nrhs, &R, &per, &x0m, &a, &xv, &sd, &wk};
-    RC_TRY(launch(0, args, pl.lds_bytes));
-  }
-  {
-    // the dense multi-solve at (U, v): first the seeds (gU, gv_c), step = (dU, dv); then, behind the residual kernel,
-    // the seeds (rU, 0), step = (eU, ev), which the correction kernel adds.
-    fbstab_var_batch_t xc = {};
-    xc.base[0] = wk.U; xc.stride[0] = sh.nz;
-    xc.base[2] = xv.base[2]; xc.stride[2] = xv.stride[2];
-    fbstab_multi_var_batch_t sc = {}, ac = {};
-    sc.base[0] = wk.gU; sc.stride[0] = sh.nz * nrhs; sc.rhs_stride[0] = sh.nz;
-    sc.base[2] = wk.gv; sc.stride[2] = sh.nv * nrhs; sc.rhs_stride[2] = sh.nv;
-    ac.base[0] = wk.dU; ac.stride[0] = sh.nz * nrhs; ac.rhs_stride[0] = sh.nz;
-    ac.base[2] = wk.dv; ac.stride[2] = sh.nv * nrhs; ac.rhs_stride[2] = sh.nv;
-    fbstab_dense_batch_t dc = {};
-    for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
-      dc.base[i] = dense->base[i];
-      dc.stride[i] = batch > 1 ? dense->stride[i] : dlen[i];
-    }
-    const int flags = FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC;
-    RC_TRY(fbstab_hip_dense_kkt_solve_batch(h, batch, &dc, &xc, nrhs, &sc, sigma, &ac, status, flags, (void*)s));
-    int nzc = (int)sh.nz, nvc = (int)sh.nv;
-    const double *Hc = dc.base[FBSTAB_DENSE_H], *Ac = dc.base[FBSTAB_DENSE_A];
-    long long sH = dc.stride[FBSTAB_DENSE_H], sA = dc.stride[FBSTAB_DENSE_A];
-    double sg = sigma > 0.0 ? sigma : 1e-8;  // (the rule of fbstab_hip_dense_kkt_solve_batch)
-    void* rargs[] = {&nzc, &nvc, &nrhs, &R, &Hc, &sH, &Ac, &sA, &sg, &wk};
-    RC_TRY(launch(2, rargs, 0));
-    sc.base[0] = wk.rU;
-    sc.base[2] = nullptr;
-    ac.base[0] = wk.eU;
-    ac.base[2] = wk.ev;
-    RC_TRY(fbstab_hip_dense_kkt_solve_batch(h, batch, &dc, &xc, nrhs, &sc, sigma, &ac, status, flags, (void*)s));
-    long long gs = batch > 1 ? gain_stride : glen;
-    const int* stq = status;
-    void* cargs[] = {&nzc, &nvc, &nu, &nrhs, &R, &wk, &gain, &gs, &stq};
-    RC_TRY(launch(3, cargs, 0));
-  }
-  if (!step) return FBSTAB_HIP_OK;  // (gain alone: the finish launch is not queued)
-  const int* stq = status;
-  void* args[] = {&N, &nx, &nu, &nc, &pl.o, &nrhs, &R, &per, &x0m, &a, &sd, &wk, &st, &stq};
-  return launch(1, args, pl.lds_bytes);
-}
-}  // namespace
 
 int fbstab_hip_mpc_condensed_multi_sizes(int N, int nx, int nu, int nc, int nrhs, int rhs_per_group,
                                          int* rhs_per_group_used, long long* lds_bytes,
                                          long long* work_doubles_per_qp) {
-  if (rhs_per_group_used) *rhs_per_group_used = 0;
-  if (lds_bytes) *lds_bytes = 0;
-  if (work_doubles_per_qp) *work_doubles_per_qp = 0;
-  if (N < 1 || nx < 1 || nu < 1 || nc < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: problem sizes must be positive");
-  if (nrhs < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: fewer than one right-hand side");
-  if (rhs_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed multi: negative rhs_per_group");
-  if ((long long)(N + 1) * nu > 0x7fffffff || (long long)(N + 1) * nc > 0x7fffffff)
-    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the condensed sizes do not fit an int");
-  CondenseMultiPlan pl;
-  RC_TRY(condense_multi_plan(N, nx, nu, nc, nrhs, rhs_per_group, &pl));
-  if (rhs_per_group_used) *rhs_per_group_used = pl.R;
-  if (lds_bytes) *lds_bytes = pl.lds_bytes;
-  if (work_doubles_per_qp) *work_doubles_per_qp = pl.work;
-  return FBSTAB_HIP_OK;
+  return condensed_multi_sizes(N, nx, nu, nc, nrhs, rhs_per_group, rhs_per_group_used, lds_bytes, work_doubles_per_qp);
 }
 
 int fbstab_hip_mpc_condensed_kkt_solve_batch(fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch,
@@ -1852,15 +1473,8 @@ int fbstab_hip_mpc_condensed_kkt_solve_batch(fbstab_dense_handle_t h, int N, int
                                              const fbstab_multi_var_batch_t* seed, double sigma,
                                              const fbstab_multi_var_batch_t* step, int rhs_per_group, double* work,
                                              int* status, void* stream) {
-  // what needs no handle comes first, in the order of fbstab_hip_mpc_condense_batch, then that of
-  // fbstab_hip_mpc_kkt_solve_batch
-  CondenseShape sh;
-  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
-  if (nrhs < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed kkt solve: fewer than one right-hand side");
-  if (!seed || !step) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed kkt solve: null seed or step block");
-  if (!seed->base[0]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed kkt solve: null seed pointer (z)");
-  return condensed_multi_run(h, sh, batch, data, dense, x, nrhs, seed, sigma, step, nullptr, 0, rhs_per_group, work,
-                             status, stream);
+  return condensed_multi_run(h, N, nx, nu, nc, batch, data, dense, x, false, nrhs, seed, sigma, step, nullptr, 0,
+                             rhs_per_group, work, status, stream, condense_gpu, condense_dense_multi(h));
 }
 
 int fbstab_hip_mpc_condensed_x0_sensitivity_batch(fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch,
@@ -1869,76 +1483,20 @@ int fbstab_hip_mpc_condensed_x0_sensitivity_batch(fbstab_dense_handle_t h, int N
                                                   const fbstab_multi_var_batch_t* step, double* gain,
                                                   long long gain_stride, int rhs_per_group, double* work, int* status,
                                                   void* stream) {
-  CondenseShape sh;
-  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
-  if (!step && !gain) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 sensitivity: both step and gain are null");
-  return condensed_multi_run(h, sh, batch, data, dense, x, nx, nullptr, sigma, step, gain, gain_stride, rhs_per_group,
-                             work, status, stream);
+  return condensed_multi_run(h, N, nx, nu, nc, batch, data, dense, x, true, nx, nullptr, sigma, step, gain, gain_stride,
+                             rhs_per_group, work, status, stream, condense_gpu, condense_dense_multi(h));
 }
-
-// ---- the condensed route in closed loop (include/fbstab_hip.h; fb_condense_sweep.h) --------------------------------
-namespace {
-// What fbstab_hip_mpc_condensed_sweep_sizes documents, behind its argument checks.
-int condense_sweep_plan(int N, int nx, int nu, int nc, int traj_per_group, bool stage_m, fbk::CondenseSweepLds* L) {
-  L->init(N, nx, nu, nc, traj_per_group, stage_m);
-  if ((long long)L->total * 8 > kLdsLimitBytes)
-    return fail(FBSTAB_HIP_ERR_UNSUPPORTED,
-                "condensed sweep: traj_per_group copies of a trajectory's vectors do not fit the 160 KiB LDS budget");
-  return FBSTAB_HIP_OK;
-}
-int condense_sweep_launch(int which, int grid, int lds, void** args, hipStream_t s) {
-  int threads = 0;
-  const void* kern = fbstab_condense_sweep_kernel(which, &threads);
-  if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
-  HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(threads), args, (size_t)lds, s));
-  return FBSTAB_HIP_OK;
-}
-}  // namespace
 
 int fbstab_hip_mpc_condensed_sweep_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
                                          int* traj_per_group_used, long long* lds_bytes,
                                          long long* work_doubles_per_traj) {
-  if (traj_per_group_used) *traj_per_group_used = 0;
-  if (lds_bytes) *lds_bytes = 0;
-  if (work_doubles_per_traj) *work_doubles_per_traj = 0;
-  if (N < 1 || nx < 1 || nu < 1 || nc < 1) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: problem sizes must be positive");
-  if (traj_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: negative traj_per_group");
-  if ((long long)(N + 1) * nu > 0x7fffffff || (long long)(N + 1) * nc > 0x7fffffff)
-    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the condensed sizes do not fit an int");
-  fbk::CondenseSweepLds L;
-  RC_TRY(condense_sweep_plan(N, nx, nu, nc, traj_per_group, shared_map != 0, &L));
-  if (traj_per_group_used) *traj_per_group_used = L.T;
-  if (lds_bytes) *lds_bytes = (long long)L.total * 8;
-  if (work_doubles_per_traj) *work_doubles_per_traj = (long long)(N + 1) * nu + 2LL * (N + 1) * nc + nx + 1;
-  return FBSTAB_HIP_OK;
+  return condensed_sweep_sizes("condensed sweep", N, nx, nu, nc, traj_per_group, shared_map, traj_per_group_used,
+                               lds_bytes, work_doubles_per_traj, nullptr, false);
 }
 
 int fbstab_hip_mpc_condensed_x0_map_batch(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
                                           double* map, long long map_stride, int device, void* stream) {
-  CondenseShape sh;
-  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
-  if (!map) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 map: null output pointer");
-  static const int kMatrixSeq[] = {FBSTAB_MPC_Q, FBSTAB_MPC_R, FBSTAB_MPC_S, FBSTAB_MPC_A,
-                                   FBSTAB_MPC_B, FBSTAB_MPC_E, FBSTAB_MPC_L};
-  bool shared_model = true;
-  for (int i : kMatrixSeq) shared_model = shared_model && data->stride[i] == 0;
-  const long long len = (sh.nz + sh.nv) * nx;
-  if (batch > 1 && map_stride < len) {
-    if (map_stride != 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 map: output stride smaller than the image");
-    if (!shared_model)
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 map: output stride 0 needs stride 0 on every one of Q, R, S, A, B, E, L");
-  }
-  if (batch == 0) return FBSTAB_HIP_OK;
-  fbk::CondenseLds o;
-  int lds = 0;
-  RC_TRY(condense_device(sh, device, &o, &lds));
-  fbstab_mpc_batch_t a = *data;
-  long long ms = batch > 1 ? map_stride : len;
-  const int blocks = (nx + nu - 1) / nu;
-  if ((long long)batch * blocks > 0x7fffffff)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed x0 map: batch x column blocks exceeds the grid limit");
-  void* args[] = {&N, &nx, &nu, &nc, &o, &a, &map, &ms};
-  return condense_sweep_launch(0, (ms == 0 ? 1 : batch) * blocks, lds, args, (hipStream_t)stream);
+  return condensed_x0_map_run(N, nx, nu, nc, batch, data, map, map_stride, device, stream, condense_gpu);
 }
 
 int fbstab_hip_mpc_condensed_receding_sweep(fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch,
@@ -1948,166 +1506,20 @@ int fbstab_hip_mpc_condensed_receding_sweep(fbstab_dense_handle_t h, int N, int 
                                             int retire, const fbstab_sweep_scenario_t* scenario, int mode,
                                             const fbstab_condensed_sweep_log_t* log, int traj_per_group, double* work,
                                             void* stream) {
-  // what needs no handle comes first, in the order of fbstab_hip_mpc_condense_batch
-  CondenseShape sh;
-  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
-  if (!dense || !x || !out || !plant || !work) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null argument");
-  if (!plant->A || !plant->B) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null plant matrix");
-  if (steps < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: negative step count");
-  if (scenario && scenario->shift != 0 && scenario->shift != 1)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: shift is 0 or 1");
-  if (mode != FBSTAB_CONDENSED_SWEEP_AFFINE && mode != FBSTAB_CONDENSED_SWEEP_RECONDENSE)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: `mode` must be AFFINE (0) or RECONDENSE (1)");
-  if (traj_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: negative traj_per_group");
-  if (batch > 1 && data->stride[FBSTAB_MPC_x0] < nx)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: every trajectory needs its own x0 (stride >= nx)");
-  const long long dlen[FBSTAB_DENSE_NARR] = {sh.nz * sh.nz, sh.nz, 0, 0, sh.nv * sh.nz, sh.nv};
-  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
-    const bool matrix = i == FBSTAB_DENSE_H || i == FBSTAB_DENSE_A;
-    if (!dense->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null pointer in the condensed images");
-    if (batch > 1 && dense->stride[i] < dlen[i] && !(matrix && dense->stride[i] == 0))
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: stride of a condensed image smaller than the array length");
-  }
-  const long long xlen[4] = {(long long)(N + 1) * (nx + nu), (long long)(N + 1) * nx, sh.nv, sh.nv};
-  for (int i = 0; i < 4; i++) {
-    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null variable pointer");
-    if (batch > 1 && x->stride[i] < xlen[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: variable stride smaller than the vector length");
-  }
-  if (batch > 1 && ((plant->stride_A != 0 && plant->stride_A < (long long)nx * nx) ||
-                    (plant->stride_B != 0 && plant->stride_B < (long long)nx * nu)))
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: plant stride smaller than the matrix");
-  const bool affine = mode == FBSTAB_CONDENSED_SWEEP_AFFINE;
-  const long long ne = sh.nz + sh.nv;
-  if (affine) {
-    if (!map) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: AFFINE mode needs the map");
-    if (!map->M || !map->f0 || !map->b0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null pointer in the map");
-    if (batch > 1 && ((map->stride_M != 0 && map->stride_M < ne * nx) || (map->stride_f0 != 0 && map->stride_f0 < sh.nz) ||
-                      (map->stride_b0 != 0 && map->stride_b0 < sh.nv)))
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: stride of the map smaller than the array length");
-  }
-  // ... then the handle
-  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: null dense solver handle");
-  if (h->var_len[0] != sh.nz || h->var_len[1] != 0 || h->var_len[2] != sh.nv)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: the dense handle is not one of ((N + 1) nu, 0, (N + 1) nc)");
-  if (batch > h->max_batch)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep: batch exceeds the max_batch the handle was created with");
-  if (batch == 0 || steps == 0) return FBSTAB_HIP_OK;
-  fbk::CondenseLds o;
-  int lds = 0;
-  RC_TRY(condense_device(sh, h->device, &o, &lds));
-  const bool shared_m = affine && (batch == 1 || map->stride_M == 0);
-  fbk::CondenseSweepLds L;
-  RC_TRY(condense_sweep_plan(N, nx, nu, nc, traj_per_group, shared_m, &L));
-  if (L.T > batch) L.init(N, nx, nu, nc, batch, shared_m);
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const bool one = batch == 1;
-  // the work arrays, and the blocks as the kernels take them (with batch == 1 the caller's strides are not read)
-  double* U = work;
-  double* vc = U + sh.nz * batch;
-  double* yc = vc + sh.nv * batch;
-  double* xkeep = yc + sh.nv * batch;
-  int* gone = reinterpret_cast<int*>(xkeep + (long long)nx * batch);
-  fbstab_mpc_batch_t a = *data;
-  fbstab_var_batch_t xv = {};
-  for (int i = 0; i < 4; i++) { xv.base[i] = x->base[i]; xv.stride[i] = one ? xlen[i] : x->stride[i]; }
-  fbstab_dense_batch_t dc = {};
-  fbstab_dense_out_batch_t dvec = {};  // (the VECTORS launch of RECONDENSE mode writes f and b)
-  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
-    dc.base[i] = dense->base[i];
-    dc.stride[i] = one ? dlen[i] : dense->stride[i];
-  }
-  for (int i : {FBSTAB_DENSE_f, FBSTAB_DENSE_b}) {
-    dvec.base[i] = const_cast<double*>(dc.base[i]);
-    dvec.stride[i] = dc.stride[i];
-  }
-  fbstab_var_batch_t xc = {};
-  xc.base[0] = U; xc.stride[0] = sh.nz;
-  xc.base[2] = vc; xc.stride[2] = sh.nv;
-  xc.base[3] = yc; xc.stride[3] = sh.nv;
-  {
-    void* args[] = {&N, &nx, &nu, &nc, &xv, &U, &vc, &gone};
-    RC_TRY(condense_sweep_launch(2, batch, 0, args, s));
-  }
-  fbk::CondenseSweepStep st = {};
-  st.N = N; st.nx = nx; st.nu = nu; st.nc = nc; st.batch = batch;
-  st.retire = retire != 0;
-  st.out = out; st.gone = gone; st.U = U; st.v = vc;
-  st.x0 = const_cast<double*>(data->base[FBSTAB_MPC_x0]);
-  st.sx0 = one ? nx : data->stride[FBSTAB_MPC_x0];
-  st.Ap = plant->A; st.Bp = plant->B;
-  st.sAp = one ? 0 : plant->stride_A; st.sBp = one ? 0 : plant->stride_B;
-  if (affine) {
-    st.M = map->M; st.sM = one ? 0 : map->stride_M;
-    st.f0 = map->f0; st.sf0 = one ? 0 : map->stride_f0;
-    st.b0 = map->b0; st.sb0 = one ? 0 : map->stride_b0;
-  }
-  st.f = dvec.base[FBSTAB_DENSE_f]; st.sf = dvec.stride[FBSTAB_DENSE_f];
-  st.b = dvec.base[FBSTAB_DENSE_b]; st.sb = dvec.stride[FBSTAB_DENSE_b];
-  const bool shift = scenario && scenario->shift == 1;
-  const double* w = scenario ? scenario->w : nullptr;
-  const int flags = FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC;
-  const int groups = (batch + L.T - 1) / L.T;
-  for (int k = 0; k < steps; k++) {
-    const bool last = k + 1 == steps;
-    RC_TRY(fbstab_hip_dense_solve_batch(h, batch, &dc, &xc, out, flags, (void*)s));
-    const long long kb = (long long)k * batch;
-    st.shift = shift && !last;
-    st.affine = affine && !last;
-    st.xkeep = last ? xkeep : nullptr;
-    st.w = w ? w + kb * nx : nullptr;
-    st.u_log = log && log->u ? log->u + kb * nu : nullptr;
-    st.x_log = log && log->x ? log->x + kb * nx : nullptr;
-    st.U_log = log && log->U ? log->U + kb * sh.nz : nullptr;
-    st.v_log = log && log->v ? log->v + kb * sh.nv : nullptr;
-    st.eflag_log = log && log->eflag ? log->eflag + kb : nullptr;
-    st.newton_log = log && log->newton ? log->newton + kb : nullptr;
-    void* sargs[] = {&st, &L};
-    RC_TRY(condense_sweep_launch(1, groups, L.total * 8, sargs, s));
-    if (!affine && !last) {
-      void* vargs[] = {&N, &nx, &nu, &nc, &o, &a, &dvec};
-      RC_TRY(condense_launch(1, batch, lds, vargs, s));
-    }
-  }
-  // the point of the last step, at the state it was solved for
-  fbstab_mpc_batch_t al = a;
-  al.base[FBSTAB_MPC_x0] = xkeep;
-  al.stride[FBSTAB_MPC_x0] = nx;
-  void* eargs[] = {&N, &nx, &nu, &nc, &o, &al, &xc, &xv};
-  return condense_launch(2, batch, lds, eargs, s);
+  const auto dense_solve = [h](int b, const fbstab_dense_batch_t* dc, const fbstab_var_batch_t* xc,
+                               fbstab_solver_out_t* o, hipStream_t s) {
+    return fbstab_hip_dense_solve_batch(h, b, dc, xc, o, kCondenseDenseFlags, (void*)s);
+  };
+  return condensed_sweep_run(h, N, nx, nu, nc, batch, data, dense, map, x, out, plant, steps, retire, scenario, mode, log,
+                             traj_per_group, work, stream, condense_gpu, dense_solve);
 }
-
-// ---- reverse mode through that sweep (include/fbstab_hip.h; fb_condense_sweep_adjoint.h) ----------------------------
-namespace {
-// Doubles of work per trajectory: the seed, the dense step and its refinement, mu, -dl[0:nx], two status words; with
-// the finish kernel also the expanded point (z, l) and the zeros it reads for gz.
-long long condense_sweep_adjoint_work(int N, int nx, int nu, int nc, bool finish) {
-  const long long nzc = (long long)(N + 1) * nu, nv = (long long)(N + 1) * nc;
-  const long long base = 4 * nzc + 2 * nv + 2LL * nx + 1;
-  return finish ? base + 2LL * (N + 1) * (nx + nu) + (long long)(N + 1) * nx : base;
-}
-}  // namespace
 
 int fbstab_hip_mpc_condensed_sweep_adjoint_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
                                                  int* traj_per_group_used, long long* lds_bytes,
                                                  long long* work_doubles_per_traj,
                                                  long long* work_doubles_per_traj_grad) {
-  if (traj_per_group_used) *traj_per_group_used = 0;
-  if (lds_bytes) *lds_bytes = 0;
-  if (work_doubles_per_traj) *work_doubles_per_traj = 0;
-  if (work_doubles_per_traj_grad) *work_doubles_per_traj_grad = 0;
-  if (N < 1 || nx < 1 || nu < 1 || nc < 1)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: problem sizes must be positive");
-  if (traj_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: negative traj_per_group");
-  if ((long long)(N + 1) * nu > 0x7fffffff || (long long)(N + 1) * nc > 0x7fffffff)
-    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condense: the condensed sizes do not fit an int");
-  fbk::CondenseSweepLds L;
-  RC_TRY(condense_sweep_plan(N, nx, nu, nc, traj_per_group, shared_map != 0, &L));
-  if (traj_per_group_used) *traj_per_group_used = L.T;
-  if (lds_bytes) *lds_bytes = (long long)L.total * 8;
-  if (work_doubles_per_traj) *work_doubles_per_traj = condense_sweep_adjoint_work(N, nx, nu, nc, false);
-  if (work_doubles_per_traj_grad) *work_doubles_per_traj_grad = condense_sweep_adjoint_work(N, nx, nu, nc, true);
-  return FBSTAB_HIP_OK;
+  return condensed_sweep_sizes("condensed sweep adjoint", N, nx, nu, nc, traj_per_group, shared_map,
+                               traj_per_group_used, lds_bytes, work_doubles_per_traj, work_doubles_per_traj_grad, true);
 }
 
 int fbstab_hip_mpc_condensed_receding_sweep_adjoint(
@@ -2117,195 +1529,9 @@ int fbstab_hip_mpc_condensed_receding_sweep_adjoint(
     const fbstab_mpc_grad_batch_t* grad, double* gf0, double* gb0, double* mu_log, int* status, int mode,
     int traj_per_group, double* work, void* stream) {
   (void)retire;  // (the logged eflag of -1 carries it)
-  // what needs no handle comes first, in the order of fbstab_hip_mpc_condensed_receding_sweep
-  CondenseShape sh;
-  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
-  if (!dense || !plant || !log || !grad || !status || !work)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: null argument");
-  if (!plant->A || !plant->B) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: null plant matrix");
-  if (steps < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: negative step count");
-  if (mode != FBSTAB_CONDENSED_SWEEP_AFFINE && mode != FBSTAB_CONDENSED_SWEEP_RECONDENSE)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: `mode` must be AFFINE (0) or RECONDENSE (1)");
-  if (traj_per_group < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: negative traj_per_group");
-  const long long dlen[FBSTAB_DENSE_NARR] = {sh.nz * sh.nz, sh.nz, 0, 0, sh.nv * sh.nz, sh.nv};
-  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
-    const bool matrix = i == FBSTAB_DENSE_H || i == FBSTAB_DENSE_A;
-    if (!dense->base[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: null pointer in the condensed images");
-    if (batch > 1 && dense->stride[i] < dlen[i] && !(matrix && dense->stride[i] == 0))
-      return fail(FBSTAB_HIP_ERR_ARGUMENT,
-                  "condensed sweep adjoint: stride of a condensed image smaller than the array length");
-  }
-  if (batch > 1 && ((plant->stride_A != 0 && plant->stride_A < (long long)nx * nx) ||
-                    (plant->stride_B != 0 && plant->stride_B < (long long)nx * nu)))
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: plant stride smaller than the matrix");
-  if (!log->x || !log->U || !log->v || !log->eflag)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: the x, U, v and eflag logs are required");
-  bool data_grads = false;
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-    if (!grad->base[i]) continue;
-    if (batch > 1 && grad->stride[i] < sh.len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT,
-                  "condensed sweep adjoint: gradient stride smaller than the array length (sums over the batch are the caller's)");
-    if (i != FBSTAB_MPC_x0) data_grads = true;
-  }
-  const bool affine = mode == FBSTAB_CONDENSED_SWEEP_AFFINE;
-  const long long ne = sh.nz + sh.nv;
-  if (affine) {
-    if (!map) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: AFFINE mode needs the map");
-    if (!map->M || !map->f0 || !map->b0)
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: null pointer in the map");
-    if (batch > 1 && ((map->stride_M != 0 && map->stride_M < ne * nx) || (map->stride_f0 != 0 && map->stride_f0 < sh.nz) ||
-                      (map->stride_b0 != 0 && map->stride_b0 < sh.nv)))
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: stride of the map smaller than the array length");
-  }
-  // ... then the handle
-  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "condensed sweep adjoint: null dense solver handle");
-  if (h->var_len[0] != sh.nz || h->var_len[1] != 0 || h->var_len[2] != sh.nv)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT,
-                "condensed sweep adjoint: the dense handle is not one of ((N + 1) nu, 0, (N + 1) nc)");
-  if (batch > h->max_batch)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT,
-                "condensed sweep adjoint: batch exceeds the max_batch the handle was created with");
-  if (batch == 0) return FBSTAB_HIP_OK;
-  fbk::CondenseLds o;
-  int lds = 0;
-  RC_TRY(condense_device(sh, h->device, &o, &lds));
-  const bool shared_m = affine && (batch == 1 || map->stride_M == 0);
-  fbk::CondenseSweepLds L;
-  RC_TRY(condense_sweep_plan(N, nx, nu, nc, traj_per_group, shared_m, &L));
-  if (L.T > batch) L.init(N, nx, nu, nc, batch, shared_m);
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const bool one = batch == 1;
-  const bool finish = data_grads || !affine;
-  const long long nzf = (long long)(N + 1) * (nx + nu);
-  // the work arrays, packed arrays of the batch in this order
-  fbk::CondenseAdjointWork wk = {};
-  wk.gU = work;
-  wk.dU = wk.gU + sh.nz * batch;
-  wk.rU = wk.dU + sh.nz * batch;
-  wk.eU = wk.rU + sh.nz * batch;
-  wk.dv = wk.eU + sh.nz * batch;
-  wk.ev = wk.dv + sh.nv * batch;
-  double* mu = wk.ev + sh.nv * batch;
-  double* dl0 = mu + (long long)nx * batch;
-  int* st1 = reinterpret_cast<int*>(dl0 + (long long)nx * batch);
-  int* st2 = st1 + batch;
-  double* zs = dl0 + (long long)nx * batch + batch;
-  double* gzs = zs + nzf * batch;
-  double* ls = gzs + nzf * batch;
-  auto launch = [&](int which, int grid, int bytes, void** args) -> int {
-    int threads = 0;
-    const void* kern = fbstab_condense_sweep_adjoint_kernel(which, &threads);
-    if (bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes));
-    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(threads), args, (size_t)bytes, s));
-    return FBSTAB_HIP_OK;
-  };
-  fbstab_mpc_grad_batch_t g = *grad;
-  if (one)
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) g.stride[i] = sh.len[i];
-  {
-    double* gz0 = finish ? gzs : nullptr;
-    void* args[] = {&N, &nx, &nu, &nc, &g, &gz0, &gf0, &gb0, &status};
-    RC_TRY(launch(2, batch, 0, args));
-  }
-  if (steps == 0) return FBSTAB_HIP_OK;
-  fbstab_mpc_batch_t a = *data;
-  a.stride[FBSTAB_MPC_x0] = nx;
-  fbstab_dense_batch_t dc = {};
-  fbstab_dense_out_batch_t dvec = {};
-  for (int i : {FBSTAB_DENSE_H, FBSTAB_DENSE_f, FBSTAB_DENSE_A, FBSTAB_DENSE_b}) {
-    dc.base[i] = dense->base[i];
-    dc.stride[i] = one ? dlen[i] : dense->stride[i];
-  }
-  for (int i : {FBSTAB_DENSE_f, FBSTAB_DENSE_b}) {
-    dvec.base[i] = const_cast<double*>(dc.base[i]);
-    dvec.stride[i] = dc.stride[i];
-  }
-  fbk::CondenseSweepAdjStep st = {};
-  st.N = N; st.nx = nx; st.nu = nu; st.nc = nc; st.batch = batch;
-  st.affine = affine;
-  st.st1 = st1; st.st2 = st2; st.status = status;
-  st.dU = wk.dU; st.dv = wk.dv;
-  st.dl0 = affine ? nullptr : dl0;
-  st.mu = mu;
-  st.Ap = plant->A; st.Bp = plant->B;
-  st.sAp = one ? 0 : plant->stride_A; st.sBp = one ? 0 : plant->stride_B;
-  st.gU = wk.gU;
-  if (affine) {
-    st.M = map->M; st.sM = one ? 0 : map->stride_M;
-    st.f0 = map->f0; st.sf0 = one ? 0 : map->stride_f0;
-    st.b0 = map->b0; st.sb0 = one ? 0 : map->stride_b0;
-  }
-  st.f = dvec.base[FBSTAB_DENSE_f]; st.sf = dvec.stride[FBSTAB_DENSE_f];
-  st.b = dvec.base[FBSTAB_DENSE_b]; st.sb = dvec.stride[FBSTAB_DENSE_b];
-  st.gf0 = gf0; st.gb0 = gb0;
-  st.gx0 = g.base[FBSTAB_MPC_x0]; st.sgx0 = g.stride[FBSTAB_MPC_x0];
-  fbstab_mpc_grad_batch_t gfin = g;
-  gfin.base[FBSTAB_MPC_x0] = nullptr;
-  fbk::CondenseSweepAdjFinish fin = {};
-  fin.dU = wk.dU; fin.dv = wk.dv; fin.st1 = st1; fin.st2 = st2;
-  fin.z = zs; fin.l = ls; fin.gz = gzs; fin.dl0 = st.dl0;
-  const fbstab_dense_grad_batch_t none = {};
-  const int flags = FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC;
-  const int groups = (batch + L.T - 1) / L.T;
-  int nzc = (int)sh.nz, nvc = (int)sh.nv;
-  const double *Hc = dc.base[FBSTAB_DENSE_H], *Ac = dc.base[FBSTAB_DENSE_A];
-  long long sH = dc.stride[FBSTAB_DENSE_H], sA = dc.stride[FBSTAB_DENSE_A];
-  double sg = sigma > 0.0 ? sigma : 1e-8;  // (the rule of fbstab_hip_dense_adjoint_batch)
-  for (int k = steps - 1; k >= -1; k--) {
-    const long long kb = (long long)k * batch;
-    st.close = k + 1 < steps;
-    st.open = k >= 0;
-    st.eflag_close = st.close ? log->eflag + kb + batch : nullptr;
-    st.eflag_open = st.open ? log->eflag + kb : nullptr;
-    st.gu = st.open && gu ? gu + kb * nu : nullptr;
-    st.gx = st.open && gx ? gx + kb * nx : nullptr;
-    st.mu_log = st.open && mu_log ? mu_log + kb * nx : nullptr;
-    st.x_log = st.open ? log->x + kb * nx : nullptr;
-    void* sargs[] = {&st, &L};
-    RC_TRY(launch(0, groups, L.total * 8, sargs));
-    if (k < 0) break;
-    if (!affine) {
-      a.base[FBSTAB_MPC_x0] = log->x + kb * nx;
-      void* vargs[] = {&N, &nx, &nu, &nc, &o, &a, &dvec};
-      RC_TRY(condense_launch(1, batch, lds, vargs, s));
-    }
-    // the dense adjoint at the logged (U_k, v_k), read where they lie, and one step of refinement of its step
-    fbstab_var_batch_t xc = {}, sc = {}, ac = {};
-    xc.base[0] = log->U + kb * sh.nz; xc.stride[0] = sh.nz;
-    xc.base[2] = log->v + kb * sh.nv; xc.stride[2] = sh.nv;
-    sc.base[0] = wk.gU; sc.stride[0] = sh.nz;
-    sc.stride[2] = sh.nv;
-    ac.base[0] = wk.dU; ac.stride[0] = sh.nz;
-    ac.base[2] = wk.dv; ac.stride[2] = sh.nv;
-    RC_TRY(fbstab_hip_dense_adjoint_batch(h, batch, &dc, &xc, &sc, sigma, &none, &ac, st1, flags, (void*)s));
-    {
-      int threads = 0;
-      void* rargs[] = {&nzc, &nvc, &Hc, &sH, &Ac, &sA, &sg, &wk};
-      const void* kern = fbstab_condense_adjoint_kernel(2, &threads);
-      HIP_TRY(hipLaunchKernel(kern, dim3(batch), dim3(threads), rargs, 0, s));
-    }
-    sc.base[0] = wk.rU;
-    ac.base[0] = wk.eU;
-    ac.base[2] = wk.ev;
-    RC_TRY(fbstab_hip_dense_adjoint_batch(h, batch, &dc, &xc, &sc, sigma, &none, &ac, st2, flags, (void*)s));
-    {
-      int threads = 0;
-      void* cargs[] = {&nzc, &nvc, &wk};
-      const void* kern = fbstab_condense_adjoint_kernel(3, &threads);
-      HIP_TRY(hipLaunchKernel(kern, dim3(batch), dim3(threads), cargs, 0, s));
-    }
-    if (finish) {
-      fin.x = log->x + kb * nx;
-      fin.U = log->U + kb * sh.nz;
-      fin.v = log->v + kb * sh.nv;
-      fin.eflag = log->eflag + kb;
-      void* fargs[] = {&N, &nx, &nu, &nc, &o, &a, &fin, &gfin};
-      RC_TRY(launch(1, batch, lds, fargs));
-    }
-  }
-  return FBSTAB_HIP_OK;
+  return condensed_sweep_adjoint_run(h, N, nx, nu, nc, batch, data, dense, map, plant, steps, log, gu, gx, sigma, grad,
+                                     gf0, gb0, mu_log, status, mode, traj_per_group, work, stream, condense_gpu,
+                                     condense_dense_adjoint(h));
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;

@@ -108,7 +108,7 @@ class HostCondenseAdjoint:
 
     def __init__(self):
         self.lib = C.CDLL(hostsim.build("libhostsim_condense_adjoint.so", "condense_adjoint.cc",
-                                        ("fb_common.h", "fb_batch.h", "fb_adjoint.h", "fb_condense.h",
+                                        ("fb_common.h", "fb_batch.h", "fb_condense_plan.h", "fb_adjoint.h", "fb_condense.h",
                                          "fb_condense_adjoint.h")))
         self.lib.hostsim_condense_adjoint_seed.argtypes = [C.c_int] * 4 + [C.c_void_p] * 8
         self.lib.hostsim_condense_adjoint_finish.argtypes = [C.c_int] * 4 + [C.c_void_p] * 9 + [C.c_int] + [C.c_void_p] * 3

@@ -161,7 +161,7 @@ class HostCondense:
 
     def __init__(self):
         self.lib = C.CDLL(hostsim.build("libhostsim_condense.so", "condense.cc",
-                                        ("fb_common.h", "fb_batch.h", "fb_condense.h")))
+                                        ("fb_common.h", "fb_batch.h", "fb_condense_plan.h", "fb_condense.h")))
         self.lib.hostsim_condense.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int] + [C.c_void_p] * 4
         self.lib.hostsim_expand.argtypes = [C.c_int] * 4 + [C.c_void_p] * 8
 

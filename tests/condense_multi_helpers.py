@@ -68,7 +68,7 @@ class HostCondenseMulti:
 
     def __init__(self):
         self.lib = C.CDLL(hostsim.build("libhostsim_condense_multi.so", "condense_multi.cc",
-                                        ("fb_common.h", "fb_batch.h", "fb_adjoint.h", "fb_condense.h",
+                                        ("fb_common.h", "fb_batch.h", "fb_condense_plan.h", "fb_adjoint.h", "fb_condense.h",
                                          "fb_condense_adjoint.h", "fb_condense_multi.h")))
         L = self.lib
         L.hostsim_condense_multi_sizes.argtypes = [C.c_int] * 5 + [C.c_void_p]

@@ -33,7 +33,7 @@ class HostSweepAdjoint:
 
     def __init__(self):
         self.lib = C.CDLL(hostsim.build("libhostsim_condense_sweep_adjoint.so", "condense_sweep_adjoint.cc",
-                                        ("fb_common.h", "fb_batch.h", "fb_adjoint.h", "fb_condense.h",
+                                        ("fb_common.h", "fb_batch.h", "fb_condense_plan.h", "fb_adjoint.h", "fb_condense.h",
                                          "fb_condense_adjoint.h", "fb_condense_sweep.h", "fb_condense_sweep_adjoint.h")))
         self.lib.hostsim_sweep_adjoint_step.argtypes = [C.c_void_p] * 4
         self.lib.hostsim_sweep_adjoint_step.restype = None

@@ -234,7 +234,7 @@ class HostSweep:
 
     def __init__(self):
         self.lib = C.CDLL(hostsim.build("libhostsim_condense_sweep.so", "condense_sweep.cc",
-                                        ("fb_common.h", "fb_batch.h", "fb_condense.h", "fb_condense_sweep.h")))
+                                        ("fb_common.h", "fb_batch.h", "fb_condense_plan.h", "fb_condense.h", "fb_condense_sweep.h")))
         self.lib.hostsim_x0_map.argtypes = [C.c_int] * 4 + [C.c_void_p] * 2
         self.lib.hostsim_sweep_sizes.argtypes = [C.c_int] * 6 + [C.c_void_p]
         self.lib.hostsim_sweep_step.argtypes = [C.c_void_p] * 8
