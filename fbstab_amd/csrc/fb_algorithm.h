@@ -29,7 +29,13 @@
 
 namespace fbk {
 
-constexpr int kLineSearchTrials = 4;  // step lengths evaluated per line-search pass
+constexpr int kLineSearchTrials = 4;  // step lengths evaluated per line-search pass (flat-vector and dense kernels)
+// ... and per COOPERATIVE pass of the record kernels (P::trial_v_coop), a constant of its own.  A step that fails f
+// sufficient-decrease tests pays ceil(f / K) passes, and on the benchmark's QPs f = 5 ... 8 is the most common failing
+// count (tools/line_search_lengths.py): K = 8 runs 38 % fewer passes than K = 4.  It was measured and is SLOWER - the
+// headline loses 0.6 % at K = 6, 1.2 % at K = 8 and 3.9 % at K = 12, a pass costing about 0.25 + 0.19 K of what it
+// costs at K = 4: three quarters of a pass is the arithmetic of its step lengths (LABNOTES R7.2).
+constexpr int kCoopLineSearchTrials = 4;
 
 // TRACE: the kernel instance behind fbstab_hip_*_solve_traced.  It records the
 // numbers of every display line of the reference (PrintIterLine,
@@ -399,7 +405,8 @@ struct Solver : TraceState<TRACE> {
         for (int k = 1; k < 5; k++) m0 = merit[k] > m0 ? merit[k] : m0;
       }
       // impl:283-297: trial j = 0 at t = 1 came with the Newton step; later
-      // trials are evaluated four step lengths per pass.
+      // trials are evaluated kLineSearchTrials step lengths per pass (the record kernels' loop below has its
+      // own constant, kCoopLineSearchTrials).
       double t = 1.0;
       double Et = sqrt(ti2), Eot = sqrt(to2);
       bool known = true;  // (Et, Eot) belong to the current t
@@ -721,7 +728,8 @@ struct Solver : TraceState<TRACE> {
       if constexpr (kCoop) {
         // ---- one Newton step, then the line search with COOPERATIVE trial passes: the
         // rows stay in the loop until the last one of the wavefront is done, and every
-        // trial pass of a row is run by all rows (P::norms_at_multi_coop).  Same
+        // trial pass of a row is run by all rows (P::trial_v_coop: the passes of the rows
+        // that search after the same step share one call).  Same
         // statements per QP as below; a row's scalars wait in its save area while the
         // sweeps run, the rows without a step included (nothing of theirs may stay in
         // registers across a Newton step: the sweeps have none to spare).
@@ -778,24 +786,31 @@ struct Solver : TraceState<TRACE> {
             }
           }
         }
-        constexpr int KT = kLineSearchTrials;
+        constexpr int KT = kCoopLineSearchTrials;
         for (;;) {
           unsigned long long need = __ballot(searching);
           if (need == 0ull) break;
+          // the constraint blocks' share, squared (the pass reads nothing else): one call serves the searching rows
+          // one after the other, each row gets its own QP's sums (zeros where the row is not searching)
+          // (P::kChainTrialPasses; otherwise a call per owner, selected into the owner's row here)
           double Em[KT], Eom[KT];
+          if constexpr (P::kChainTrialPasses) {
+            p.template trial_v_coop<KT>(need, t, o.beta, sigma, o.alpha, Em, Eom);
+          } else {
 #pragma unroll
-          for (int m = 0; m < KT; m++) Em[m] = Eom[m] = 0.0;
-          while (need != 0ull) {
-            const int owner = __builtin_ctzll(need);
-            double Ec[KT], Eoc[KT];  // the constraint blocks' share, squared (the pass reads nothing else)
-            p.template trial_v_coop<KT>(owner, t, o.beta, sigma, o.alpha, Ec, Eoc);
-            const bool mine = ((threadIdx.x ^ owner) & 63 & ~(C::nt - 1)) == 0;
+            for (int m = 0; m < KT; m++) Em[m] = Eom[m] = 0.0;
+            while (need != 0ull) {
+              const int owner = __builtin_ctzll(need);
+              double Ec[KT], Eoc[KT];
+              p.template trial_v_coop_one<KT>(owner, t, o.beta, sigma, o.alpha, Ec, Eoc);
+              const bool mine = ((threadIdx.x ^ owner) & 63 & ~(C::nt - 1)) == 0;
 #pragma unroll
-            for (int m = 0; m < KT; m++) {
-              Em[m] = mine ? Ec[m] : Em[m];
-              Eom[m] = mine ? Eoc[m] : Eom[m];
+              for (int m = 0; m < KT; m++) {
+                Em[m] = mine ? Ec[m] : Em[m];
+                Eom[m] = mine ? Eoc[m] : Eom[m];
+              }
+              need &= ~(((C::nt == 64) ? ~0ull : ((1ull << C::nt) - 1ull)) << (owner & ~(C::nt - 1)));
             }
-            need &= ~(((C::nt == 64) ? ~0ull : ((1ull << C::nt) - 1ull)) << (owner & ~(C::nt - 1)));
           }
           {  // ... plus the z and l blocks' share at t beta^m (P::trial_zl), and the root
             auto sv = qu.save_area();

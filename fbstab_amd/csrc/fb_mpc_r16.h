@@ -952,13 +952,14 @@ struct MpcR16 {
     });
   }
 
-  // The same pass for ONE QP of the wavefront (the one whose lane `owner` is), run by ALL
-  // its rows: row q takes the stages q, q + QW, q + 2 QW, ... - the rows that need a
-  // line-search pass at a given moment are usually one or two of the four, and the
-  // others' lanes would only wait.  Every lane calls this (wave-uniform control flow);
-  // every lane gets the owner's norms.  The sums over the stages are formed per row and
-  // then over the rows: same terms as norms_at_multi(), different order of summation.
-  // No step is pending here (the Newton step's forward sweep applied it).
+  // The same pass for ONE QP of the wavefront at a time (the owner), run by ALL its rows:
+  // row q takes the stages q, q + QW, q + 2 QW, ... - the rows that need a line-search
+  // pass at a given moment are usually two or three of the four, and the others' lanes
+  // would only wait.  Every lane calls this (wave-uniform control flow) with the ballot
+  // of the searching rows; the owners are served one after the other in ONE call, and a
+  // row's lanes get the norms of the row's own QP.  The sums over the stages are formed
+  // per row and then over the rows: same terms as norms_at_multi(), different order of
+  // summation.  No step is pending here (the Newton step's forward sweep applied it).
   // The pass proper is a real call (trial_pass_coop, not inlined): it takes nothing but
   // scalars, so the policy object stays in registers; inlined into the solver loop the
   // exact <12,4,32> instance came out finishing every QP at its first convergence test
@@ -989,9 +990,15 @@ struct MpcR16 {
     });
     ldv<sVB, KS>(R, in.vb);
   }
+  // Two forms.  One call per owner (trial_v_coop_one / trial_pass_coop_one) is what the row-pair instances run: two
+  // rows, long horizons - `<18,5,10>` at N = 80 loses 2-3 % with the other form (41 trips per pass: a first trip with
+  // nothing requested ahead is 1 in 41, and every trip pays the selects of the hand-over).  One call for all searching
+  // rows (trial_v_coop / trial_pass_coop, below) is what the one-row instances run: +1.0 % on the headline
+  // (LABNOTES R7.2).
+  static constexpr bool kChainTrialPasses = RQ == 1;
   // R0: the owner's record base with this lane's offset within ITS row (2 * r)
   template <int K>
-  static __device__ __attribute__((noinline)) TrialNorms<K> trial_pass_coop(const double* R0, int N_, double t0,
+  static __device__ __attribute__((noinline)) TrialNorms<K> trial_pass_coop_one(const double* R0, int N_, double t0,
                                                                             double beta, double sigma, double alpha) {
     constexpr int QW = kQpPerWave;
     const int lane = threadIdx.x & 63;
@@ -1054,6 +1061,138 @@ struct MpcR16 {
     });
     return out;
   }
+  // Vi, Vo: the squared norms' constraint-block shares for t0 beta^k, k < K, of the owner's QP
+  template <int K>
+  FB_DEV void trial_v_coop_one(int owner, double t0, double beta, double sigma, double alpha, double (&Vi)[K],
+                           double (&Vo)[K]) const {
+    FB_WAVE_COUNT(24);
+    FB_WAVE_TIMER(23);
+    // (the owner's records were written by the owner's lanes: their stores are complete
+    // before another row's lanes read them)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    // the owner's record base (lane 0 of its row: rec carries 2 * tid) and horizon
+    const int own0 = owner & ~(LPQ - 1);
+    const unsigned long long rb = (unsigned long long)rec;
+    const unsigned long long rbo = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(rb >> 32), own0) << 32) |
+                                   (unsigned)__builtin_amdgcn_readlane((int)rb, own0);
+    const double* const R0 = reinterpret_cast<const double*>(rbo) + 2 * (threadIdx.x & (LPQ - 1));
+    const TrialNorms<K> n = trial_pass_coop_one<K>(R0, __builtin_amdgcn_readlane(N, own0), lane_value(t0, own0), beta, sigma, alpha);
+    sfor<0, K>([&](auto Kk) {
+      Vi[decltype(Kk)::value] = n.vi[decltype(Kk)::value];
+      Vo[decltype(Kk)::value] = n.vo[decltype(Kk)::value];
+    });
+  }
+
+  // The passes of ALL searching rows (`need_`: their lanes' ballot), owner after owner in row order.  Rl, Nl, tl:
+  // every lane's own record base (rec carries 2 * tid), horizon and step length - plain values, see above; only the
+  // owners' are read (lane 0 of a row speaks for it).  An owner's sums are formed by themselves, in the order a call
+  // per owner formed them (LABNOTES R7.2: bitwise the same), and go to the lanes of the owner's row; the other rows'
+  // stay zero.
+  // One stage per trip and row: the slots of a trip are requested a trip ahead - this pass stores nothing; at the
+  // top of their own trip, two trips ahead and two or four stages per trip all lost (LABNOTES, retired switches; in
+  // the passes that also STORE records - open, close, the packing pass - every form of requesting ahead has lost,
+  // see open_pass_coop).  With the z and l slots gone a trip moves five slot pairs.  The look-ahead of an owner's LAST
+  // trip requests the NEXT owner's first stage, so that only the first owner of a call starts on a trip with nothing
+  // requested ahead; the last owner's re-reads a clamped stage, as every owner's did when each had a call of its own.
+  template <int K>
+  static __device__ __attribute__((noinline)) TrialNorms<K> trial_pass_coop(unsigned long long need_, const double* Rl, int Nl,
+                                                                            double tl, double beta, double sigma, double alpha) {
+    constexpr int QW = kQpPerWave;
+    constexpr unsigned long long kRow = LPQ == 64 ? ~0ull : ((1ull << (LPQ & 63)) - 1ull);
+    const int lane = threadIdx.x & 63;
+    const int q = lane / LPQ;
+    unsigned long long need = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(need_ >> 32)) << 32) |
+                              (unsigned)__builtin_amdgcn_readfirstlane((int)need_);
+    auto base_of = [&](int own0) {  // the owner's record base (lane 0 of its row) with this lane's offset within ITS row
+      const unsigned long long rb = (unsigned long long)Rl;
+      const unsigned long long rbo = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(rb >> 32), own0) << 32) |
+                                     (unsigned)__builtin_amdgcn_readlane((int)rb, own0);
+      return reinterpret_cast<const double*>(rbo) + 2 * (lane & (LPQ - 1));
+    };
+    TrialNorms<K> out;
+    sfor<0, K>([&](auto Kk) { out.vi[decltype(Kk)::value] = out.vo[decltype(Kk)::value] = 0.0; });
+    int own0 = __builtin_ctzll(need) & ~(LPQ - 1);
+    const double* R0 = base_of(own0);
+    int N_ = __builtin_amdgcn_readlane(Nl, own0);
+    TrialInV in;
+    load_trial_v(R0 + (long)(q < N_ ? q : N_) * kRec, spare_of(R0, N_), in);
+    for (;;) {
+      need &= ~(kRow << own0);
+      const bool more = need != 0ull;
+      const int own1 = more ? (__builtin_ctzll(need) & ~(LPQ - 1)) : own0;
+      const double* const R1 = base_of(own1);
+      const int N1 = __builtin_amdgcn_readlane(Nl, own1);
+      double tt[K], s[2 * K];
+      tt[0] = lane_value(tl, own0);
+      sfor<1, K>([&](auto Kk) { tt[decltype(Kk)::value] = tt[decltype(Kk)::value - 1] * beta; });
+      sfor<0, 2 * K>([&](auto Kk) { s[decltype(Kk)::value] = 0.0; });
+      for (int j = 0; j <= N_; j += QW) {  // (trip j serves stage q + j in row q: the same trip count in every row)
+        FB_PHASE(trip_top);
+        const int i = q + j;
+        const TrialInV cu = in;
+        const bool hand_over = more && j + QW > N_;  // the owner's last trip, and another owner follows
+        const int ia = hand_over ? q : i + QW;
+        const int Na = hand_over ? N1 : N_;
+        const double* const Ra = hand_over ? R1 : R0;
+        load_trial_v(Ra + (long)(ia < Na ? ia : Na) * kRec, spare_of(Ra, Na), in);
+        // A row that has run out of stages (the last trip) re-reads the last stage - lines the row that owns
+        // that stage has just pulled into the cache - and its terms are selected away.  (Round 6 measured two
+        // ways of saving the four selects per step length and slot, both SLOWER although shorter: such rows
+        // pointed at an all-zero spare record, no select at all - 25 instructions fewer per trip, 595 k against
+        // 627 k QP/s: the spare's lines are cold and every pass ended on a trip to HBM for data nobody uses;
+        // and the trip's arithmetic behind a branch on `live` - 46 instructions fewer, 624 k against 637 k.)
+        const bool live = i <= N_;
+        sfor<0, KS>([&](auto S_) {
+          constexpr int sl = decltype(S_)::value;
+          sfor<0, K>([&](auto Kk) {
+            constexpr int k = decltype(Kk)::value;
+            const double vi = fma(tt[k], cu.da[sl][0], cu.vy[sl][0]);
+            const double yi = fma(-tt[k], cu.da[sl][1], cu.vy[sl][1]);
+            const double ys = yi + sigma * (vi - cu.vb[sl]);
+            const double ph = pfb(ys, vi, alpha);
+            const double pn = pnr(yi, vi, alpha);
+            s[k] = live ? fma(ph, ph, s[k]) : s[k];
+            s[K + k] = live ? fma(pn, pn, s[K + k]) : s[K + k];
+          });
+        });
+        FB_PHASE(trip_end);
+      }
+      const bool mine = (lane & ~(LPQ - 1)) == own0;
+      sfor<0, 2 * K>([&](auto Kk) {
+        constexpr int k = decltype(Kk)::value;
+        const double rs = qp_reduce<RQ, OpSum16>(s[k]);  // the row's (row pair's) stages
+        double tot = lane_value(rs, 0);
+        sfor<1, QW>([&](auto Q_) { tot += lane_value(rs, LPQ * decltype(Q_)::value); });
+        if constexpr (k < K) out.vi[k] = mine ? tot : out.vi[k];
+        else out.vo[k - K] = mine ? tot : out.vo[k - K];
+      });
+      if (!more) break;
+      own0 = own1;
+      R0 = R1;
+      N_ = N1;
+    }
+    return out;
+  }
+  // Vi, Vo: the squared norms' constraint-block shares for t0 beta^k, k < K, of this row's QP, where the row is one
+  // of `need` (the ballot of the searching rows; not empty)
+  template <int K>
+  FB_DEV void trial_v_coop(unsigned long long need, double t0, double beta, double sigma, double alpha, double (&Vi)[K],
+                           double (&Vo)[K]) const {
+    constexpr unsigned long long kRow = LPQ == 64 ? ~0ull : ((1ull << (LPQ & 63)) - 1ull);
+    // (the diagnostic builds count a pass per owner, as when each was a call)
+    for (unsigned long long m = need; m != 0ull; m &= ~(kRow << (__builtin_ctzll(m) & ~(LPQ - 1)))) FB_WAVE_COUNT(24);
+    FB_WAVE_TIMER(23);
+    // (the owners' records were written by the owners' lanes: their stores are complete before another row's
+    // lanes read them - once for the call: nothing is stored between its passes)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const TrialNorms<K> n = trial_pass_coop<K>(need, rec, N, t0, beta, sigma, alpha);
+    sfor<0, K>([&](auto Kk) {
+      Vi[decltype(Kk)::value] = n.vi[decltype(Kk)::value];
+      Vo[decltype(Kk)::value] = n.vo[decltype(Kk)::value];
+    });
+  }
   // (Round 6 also evaluated the LAST constraint slot of four stages as one slot: 4.4 % fewer vector instructions and
   // 0.9 % slower, the third shorter trial pass that was not a faster one - LABNOTES, retired switches.)
   // The z and l blocks' share of the squared trial norms at x + t dx, from four sums of the Newton step.
@@ -1068,29 +1207,6 @@ struct MpcR16 {
   static FB_DEV double trial_zl(double A, double S, double B, double t) {
     return fmax(0.0, fma(B, t * t - t, fma(A, 1.0 - t, t * S)));
   }
-  // Vi, Vo: the squared norms' constraint-block shares for t0 beta^k, k < K, of the owner's QP
-  template <int K>
-  FB_DEV void trial_v_coop(int owner, double t0, double beta, double sigma, double alpha, double (&Vi)[K],
-                           double (&Vo)[K]) const {
-    FB_WAVE_COUNT(24);
-    FB_WAVE_TIMER(23);
-    // (the owner's records were written by the owner's lanes: their stores are complete
-    // before another row's lanes read them)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    // the owner's record base (lane 0 of its row: rec carries 2 * tid) and horizon
-    const int own0 = owner & ~(LPQ - 1);
-    const unsigned long long rb = (unsigned long long)rec;
-    const unsigned long long rbo = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(rb >> 32), own0) << 32) |
-                                   (unsigned)__builtin_amdgcn_readlane((int)rb, own0);
-    const double* const R0 = reinterpret_cast<const double*>(rbo) + 2 * (threadIdx.x & (LPQ - 1));
-    const TrialNorms<K> n = trial_pass_coop<K>(R0, __builtin_amdgcn_readlane(N, own0), lane_value(t0, own0), beta, sigma, alpha);
-    sfor<0, K>([&](auto Kk) {
-      Vi[decltype(Kk)::value] = n.vi[decltype(Kk)::value];
-      Vo[decltype(Kk)::value] = n.vo[decltype(Kk)::value];
-    });
-  }
-
   // x <- x + t dx, (rz, rl) <- (rz, rl) + t W for the pending step (impl:298,
   // full_variable.cc:55-65).
   FB_DEV void flush(const C& c) {
