@@ -77,8 +77,10 @@ Forward: ``cm.Solve`` from a zero guess, condensing ``data`` first.  Backward: O
 (fbstab_hip_mpc_condensed_adjoint_batch: the seeds condensed, the dense adjoint, the step expanded and contracted)
 with the gradients torch asks for; QPs whose condensed solve did not end in SUCCESS, or whose factorisation failed,
 get zero gradients.  A shared ``(len,)`` or ``(1, len)`` input gets the torch sum over the batch of the per-QP
-gradients: the device-side reduced form is not served on this route, and neither are forward mode, Jacobians and
-x0 sensitivities.
+gradients: the device-side reduced form is not served on this route.  Forward mode (``torch.autograd.forward_ad``):
+ONE call of ``cm.Tangent`` (fbstab_hip_mpc_condensed_tangent_batch) with the tangents that are present, zero
+tangents for the same QPs.  Either pass re-condenses first where another ``Condense`` or ``Solve`` of ``cm`` has
+replaced the forward's images since.
 """
 import torch
 
@@ -348,9 +350,28 @@ class CondensedMpcSolveFunction(torch.autograd.Function):
         out = cm.Solve(data, z, l, v, y, recondense="all")
         ctx.cm, ctx.sigma, ctx.generation = cm, sigma, cm.generation
         ctx.save_for_backward(*[data[k] for k in MPC_SEQ], z, l, v, out)
+        ctx.save_for_forward(*[data[k] for k in MPC_SEQ], z, l, v, out)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(out)
         return z, l, v, out
+
+    @staticmethod
+    def jvp(ctx, cm_t, sigma_t, *tangents):
+        saved = ctx.saved_tensors
+        data = dict(zip(MPC_SEQ, saved[:len(MPC_SEQ)]))
+        z, l, v, out = saved[len(MPC_SEQ):]
+        ddata = {}
+        for k, t in zip(MPC_SEQ, tangents):
+            if t is None or t.numel() == 0:
+                continue
+            t = t.detach()
+            ddata[k] = (t.reshape(1, t.numel()) if (k in ctx.shared or t.dim() == 1) else t).contiguous()
+        if ctx.cm.generation != ctx.generation:  # another Condense or Solve has replaced the forward's images
+            ctx.cm.Condense(data)
+        res = ctx.cm.Tangent(data, z, l, v, ddata, sigma=ctx.sigma)
+        eflag = out[:, 0:4].contiguous().view(torch.int32)[:, 0]  # SolverOut::eflag, on the device
+        keep = ((eflag == 0) & (res["status"] == 0))[:, None]
+        return tuple(torch.where(keep, res[k], torch.zeros_like(res[k])) for k in ("dz", "dl", "dv")) + (None,)
 
     @staticmethod
     def backward(ctx, gz, gl, gv, gout):

@@ -234,6 +234,59 @@ class CondensedMpc:
             res = {k: a.cpu().numpy() for k, a in res.items()}
         return res
 
+    def Tangent(self, data: Dict[str, object], z, l, v, ddata: Dict[str, object], sigma: float = 0.0,
+                rhs: bool = False) -> Dict[str, object]:
+        """Forward-mode derivative of the solution map on this route (fbstab_hip_mpc_condensed_tangent_batch): what
+        ``FBstabMpcBatch.Tangent`` returns - the first-order change ``dz, dl, dv`` (``(batch, n)``) of the solutions
+        at the point ``(z, l, v)`` for the perturbation ``ddata`` of the problem data (name -> ``(batch, len)``
+        direction, or ``(1, len)`` for one direction shared by the batch; absent names and None are zero
+        perturbations; dQ and dR enter through their symmetric part), ``"status"`` (``(batch,)`` int32: 1 where the
+        dense factorisation failed and the tangent is zero) and, with ``rhs=True``, the seeds ``"gz", "gl", "gv"`` of
+        the tangent system.  It runs on the condensed images of the last ``Condense`` or ``Solve``, which must be
+        those of ``data``: the direction kernel forms the seeds, then the six launches of ``Adjoint`` solve for them
+        - seven launches on torch's current stream, and the step is ``Adjoint(..., adj=True)``'s for those seeds,
+        bit for bit.  ``sigma <= 0``: 1e-8.  Returns numpy arrays where ``z`` is one."""
+        t = self._torch
+        host = not _is_torch(z)
+        unknown = set(ddata) - set(MPC_SEQ)
+        assert not unknown, unknown
+        d = self._data(data)
+        dd = {k: self._to_dev(a) for k, a in ddata.items() if a is not None}
+        zd, ld, vd = (self._to_dev(a) for a in (z, l, v))
+        B = zd.shape[0]
+        assert 1 <= B <= self.max_batch, (B, self.max_batch)
+        img = self._img
+        assert all(k in img for k in ("H", "f", "A", "b")), "Tangent before anything was condensed"
+        assert img["f"].shape[0] == B and img["H"].shape[0] in (1, B), "the images are those of another batch"
+        var_lens = (self.nz, self.nl, self.nv)
+        xb = hip_api._fill_vars((zd, ld, vd), var_lens, B, [])
+        dense = _DenseBatch()
+        for k in ("H", "f", "A", "b"):
+            a, i = img[k], DENSE_ARR.index(k)
+            dense.base[i], dense.stride[i] = a.data_ptr(), (0 if (a.shape[0] == 1 and B > 1) else self._len[k])
+        dirb = _MpcBatch()
+        _fill_block(dirb, MPC_SEQ, self.seq_len, dd, B, [], optional=True)
+        mk = lambda shape, dtype=t.float64: t.zeros(shape, dtype=dtype, device=self._dev)
+        res = {k: mk((B, n)) for k, n in zip(("dz", "dl", "dv"), var_lens)}
+        ob = hip_api._fill_vars((res["dz"], res["dl"], res["dv"]), var_lens, B, [])
+        rb = None
+        if rhs:
+            for k, n in zip(("gz", "gl", "gv"), var_lens):
+                res[k] = mk((B, n))
+            rb = hip_api._fill_vars((res["gz"], res["gl"], res["gv"]), var_lens, B, [])
+        work = t.empty((B, 5 * self.nzc + 3 * self.nv + sum(var_lens)), dtype=t.float64, device=self._dev)
+        status = mk((B,), t.int32)
+        blk = self._mpc_block(d, B)
+        s = self._stream()
+        _check(self._lib, self._lib.fbstab_hip_mpc_condensed_tangent_batch(
+            self.dense._h, self.N, self.nx, self.nu, self.nc, B, C.byref(blk), C.byref(dense), C.byref(xb),
+            C.byref(dirb), C.c_double(sigma), C.byref(ob), C.byref(rb) if rb is not None else None,
+            C.c_void_p(work.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(s) if s else None))
+        res["status"] = status
+        if host:
+            res = {k: a.cpu().numpy() for k, a in res.items()}
+        return res
+
     def _multi_call(self, data, z, l, v, K, seeds, sigma, want, rhs_per_group):
         """fbstab_hip_mpc_condensed_kkt_solve_batch (``seeds``: (gz, gl, gv)) or
         fbstab_hip_mpc_condensed_x0_sensitivity_batch (None), on the images of the last ``Condense`` / ``Solve``."""

@@ -17,6 +17,7 @@ enum CondenseMultiKernel { kCondenseMultiSeed = 0, kCondenseMultiFinish = 1, kCo
 enum CondenseSweepKernel { kCondenseSweepX0Map = 0, kCondenseSweepStep = 1, kCondenseSweepBegin = 2 };  // fb_condense_sweep.hip
 enum CondenseSweepAdjKernel { kCondenseSweepAdjStep = 0, kCondenseSweepAdjFinish = 1,
                               kCondenseSweepAdjBegin = 2 };                           // fb_condense_sweep_adjoint.hip
+enum CondenseTangentKernel { kCondenseTangentRhs = 0 };                                    // fb_condense_tangent.hip
 
 // ---- fb_condense.h ----------------------------------------------------------------------------------------------
 inline int condense_ld(int rows) { return rows | 1; }
@@ -200,6 +201,22 @@ struct CondenseAdjointCarve {
     wk.U = c.take(nz); wk.gU = c.take(nz); wk.dU = c.take(nz);
     wk.gv = c.take(nv); wk.dv = c.take(nv);
     wk.rU = c.take(nz); wk.eU = c.take(nz); wk.ev = c.take(nv);
+    per = c.per;
+  }
+};
+
+// fbstab_hip_mpc_condensed_tangent_batch: the adjoint's work (`adjoint`, carved as above), then the seeds gz, gl, gv of
+// the MPC QP's lengths nzf = (N + 1)(nx + nu), nlf = (N + 1) nx and nv - the tail the call uses where the caller gives
+// no rhs block.
+struct CondenseTangentCarve {
+  CondenseAdjointWork wk;
+  double *gz, *gl, *gv;
+  long long per;
+  CondenseTangentCarve(long long nz, long long nv, long long nzf, long long nlf, double* work, int batch) {
+    const CondenseAdjointCarve adjoint(nz, nv, work, batch);
+    wk = adjoint.wk;
+    CondenseCarve c = {work ? work + adjoint.per * batch : nullptr, batch, adjoint.per};
+    gz = c.take(nzf); gl = c.take(nlf); gv = c.take(nv);
     per = c.per;
   }
 };

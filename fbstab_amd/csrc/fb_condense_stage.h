@@ -6,6 +6,7 @@
 //   dense_solve(batch, dc, xc, out, stream)                                      fbstab_hip_dense_solve_batch
 //   dense_adjoint(batch, dc, xc, seeds, sigma, adj, status, stream)              fbstab_hip_dense_adjoint_batch
 //   dense_multi(batch, dc, xc, nrhs, seeds, sigma, step, status, stream)         fbstab_hip_dense_kkt_solve_batch
+//   direction(N, nx, nu, nc, batch, dir, x, seeds, stream)                       the direction kernel of the forward mode
 // (on the handle, device pointers, asynchronous) - so tests/test_condense_stage.py compiles this header with the host
 // compiler over tests/hostsim/runtime_shim and runs it, host lambdas in their place, under the address sanitizer.
 #pragma once
@@ -260,6 +261,28 @@ int expand_run(int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_
 
 // ---- reverse mode (fb_condense_adjoint.h) ---------------------------------------------------------------------------
 // The seed kernel, the refined dense adjoint step on the condensed QP, the finish kernel - six launches on one stream.
+// condensed_adjoint_queue is those six behind every check, on the blocks as the kernels take them (xv, sd, ad: the
+// point, the seeds, and where the step goes - null slots skipped); the forward mode below queues them as well.
+template <class Launch, class DenseAdjoint>
+int condensed_adjoint_queue(const CondenseShape& sh, int batch, CondenseLds o, int lds, fbstab_mpc_batch_t a,
+                            const fbstab_dense_batch_t& dc, fbstab_var_batch_t xv, fbstab_var_batch_t sd, double sigma,
+                            fbstab_mpc_grad_batch_t g, fbstab_var_batch_t ad, CondenseAdjointWork wk, int* status,
+                            hipStream_t s, Launch launch, DenseAdjoint dense_adjoint) {
+  int N = sh.N, nx = sh.nx, nu = sh.nu, nc = sh.nc;
+  {
+    void* args[] = {&N, &nx, &nu, &nc, &o, &a, &xv, &sd, &wk};
+    RC_TRY(launch(kCondenseAdjSeed, batch, lds, args, s));
+  }
+  // the dense adjoint at (U, v): no gradients of the condensed data
+  fbstab_var_batch_t xc = {};
+  xc.base[0] = wk.U; xc.stride[0] = sh.nz;
+  xc.base[2] = xv.base[2]; xc.stride[2] = xv.stride[2];
+  RC_TRY(condense_refined_step(launch, dense_adjoint, sh, batch, dc, xc, wk.gv, sigma, wk, status, status, s));
+  const int* st = status;
+  void* args[] = {&N, &nx, &nu, &nc, &o, &a, &xv, &sd, &wk, &g, &ad, &st};
+  return launch(kCondenseAdjFinish, batch, lds, args, s);
+}
+
 template <class Launch, class DenseAdjoint>
 int condensed_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
                           const fbstab_dense_batch_t* dense, const fbstab_var_batch_t* x,
@@ -294,27 +317,76 @@ int condensed_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, int batc
   RC_TRY(condense_device(sh, h->device, &o, &lds));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   // the blocks as the kernels take them: with batch == 1 the strides are not read by the caller's rule
-  fbstab_mpc_batch_t a = *data;
   fbstab_var_batch_t xv = {}, sd = {}, ad = {};
   for (int i = 0; i < 3; i++) {
     xv.base[i] = x->base[i]; xv.stride[i] = batch > 1 ? x->stride[i] : xlen[i];
     sd.base[i] = seed->base[i]; sd.stride[i] = batch > 1 ? seed->stride[i] : xlen[i];
     if (adj) { ad.base[i] = adj->base[i]; ad.stride[i] = batch > 1 ? adj->stride[i] : xlen[i]; }
   }
-  fbstab_mpc_grad_batch_t g = *grad;
   CondenseAdjointWork wk = CondenseAdjointCarve(sh.nz, sh.nv, work, batch).wk;
-  {
-    void* args[] = {&N, &nx, &nu, &nc, &o, &a, &xv, &sd, &wk};
-    RC_TRY(launch(kCondenseAdjSeed, batch, lds, args, s));
+  return condensed_adjoint_queue(sh, batch, o, lds, *data, dc, xv, sd, sigma, *grad, ad, wk, status, s, launch,
+                                 dense_adjoint);
+}
+
+// ---- forward mode (fb_tangent.h's direction on this route's blocks, then the adjoint's launches) ----------------------
+// `direction(N, nx, nu, nc, batch, dir, x, seeds, stream)`: the direction kernel of fb_condense_tangent.hip on the grid
+// batch x (N + 1), behind its own two refusals (its LDS layout is a kernel header's: this header does not see it).
+// Seven launches on one stream: the direction, then condensed_adjoint_queue on the seeds it wrote, no gradient slot,
+// adj = dx.
+template <class Launch, class DenseAdjoint, class Direction>
+int condensed_tangent_run(SolverBase* h, int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+                          const fbstab_dense_batch_t* dense, const fbstab_var_batch_t* x,
+                          const fbstab_mpc_batch_t* ddata, double sigma, const fbstab_var_batch_t* dx,
+                          const fbstab_var_batch_t* rhs, double* work, int* status, void* stream, Launch launch,
+                          DenseAdjoint dense_adjoint, Direction direction) {
+  // what needs no handle comes first, in the order of fbstab_hip_mpc_condense_batch
+  CondenseShape sh = {};
+  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
+  if (!dense || !x || !ddata || !dx || !work || !status) return condense_bad("condensed tangent", "null argument");
+  fbstab_dense_batch_t dc;
+  RC_TRY(condense_check_images("condensed tangent", sh, batch, dense, &dc));
+  const long long xlen[3] = {(long long)(N + 1) * (nx + nu), (long long)(N + 1) * nx, sh.nv};
+  for (int i = 0; i < 3; i++) {
+    if (!x->base[i]) return condense_bad("condensed tangent", "null variable pointer");
+    if (batch > 1 && x->stride[i] < xlen[i])
+      return condense_bad("condensed tangent", "variable stride smaller than the vector length");
+    if (!dx->base[i]) return condense_bad("condensed tangent", "null tangent pointer (dx)");
+    if (batch > 1 && dx->stride[i] < xlen[i])
+      return condense_bad("condensed tangent", "tangent stride smaller than the vector length");
+    if (rhs && !rhs->base[i]) return condense_bad("condensed tangent", "null right-hand side pointer (rhs)");
+    if (batch > 1 && rhs && rhs->stride[i] < xlen[i])
+      return condense_bad("condensed tangent", "right-hand side stride smaller than the vector length");
   }
-  // the dense adjoint at (U, v): no gradients of the condensed data
-  fbstab_var_batch_t xc = {};
-  xc.base[0] = wk.U; xc.stride[0] = sh.nz;
-  xc.base[2] = xv.base[2]; xc.stride[2] = xv.stride[2];
-  RC_TRY(condense_refined_step(launch, dense_adjoint, sh, batch, dc, xc, wk.gv, sigma, wk, status, status, s));
-  const int* st = status;
-  void* args[] = {&N, &nx, &nu, &nc, &o, &a, &xv, &sd, &wk, &g, &ad, &st};
-  return launch(kCondenseAdjFinish, batch, lds, args, s);
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
+    if (batch > 1 && ddata->base[i] && ddata->stride[i] != 0 && ddata->stride[i] < sh.len[i])
+      return condense_bad("condensed tangent", "perturbation stride is neither 0 nor at least the array length");
+  // ... then the handle
+  RC_TRY(condense_check_handle("condensed tangent", h, sh, batch));
+  if (batch == 0) return FBSTAB_HIP_OK;
+  CondenseLds o;
+  int lds = 0;
+  RC_TRY(condense_device(sh, h->device, &o, &lds));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  // the blocks as the kernels take them: with batch == 1 the strides are not read by the caller's rule; the seeds in
+  // the caller's rhs, or in the tail of the work array (which is not addressed where rhs is given)
+  const CondenseTangentCarve wk(sh.nz, sh.nv, xlen[0], xlen[1], work, batch);
+  double* const tail[3] = {wk.gz, wk.gl, wk.gv};
+  fbstab_mpc_batch_t dir = {};
+  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
+    if (!ddata->base[i]) continue;
+    dir.base[i] = ddata->base[i];
+    dir.stride[i] = batch > 1 ? ddata->stride[i] : sh.len[i];
+  }
+  fbstab_var_batch_t xv = {}, sd = {}, ad = {};
+  for (int i = 0; i < 3; i++) {
+    xv.base[i] = x->base[i]; xv.stride[i] = batch > 1 ? x->stride[i] : xlen[i];
+    ad.base[i] = dx->base[i]; ad.stride[i] = batch > 1 ? dx->stride[i] : xlen[i];
+    sd.base[i] = rhs ? rhs->base[i] : tail[i];
+    sd.stride[i] = rhs && batch > 1 ? rhs->stride[i] : xlen[i];
+  }
+  RC_TRY(direction(N, nx, nu, nc, batch, dir, xv, sd, s));
+  return condensed_adjoint_queue(sh, batch, o, lds, *data, dc, xv, sd, sigma, fbstab_mpc_grad_batch_t{}, ad, wk.wk,
+                                 status, s, launch, dense_adjoint);
 }
 
 // ---- many right-hand sides (fb_condense_multi.h) ----------------------------------------------------------------------

@@ -573,13 +573,14 @@ __attribute__((visibility("hidden"))) const void* fbstab_kkt_multi_kernel(int wg
 // own): the kernel beside adjoint kernel `which` of dense_resolve_kernels
 __attribute__((visibility("hidden"))) const void* fbstab_dense_kkt_multi_kernel_for(int which);
 // The kernels of the condensed route (fb_condense.hip, fb_condense_adjoint.hip, fb_condense_multi.hip,
-// fb_condense_sweep.hip, fb_condense_sweep_adjoint.hip, a translation unit each): the kernel that the unit's enum of
-// fb_condense_plan.h names; *threads: its workgroup size
+// fb_condense_sweep.hip, fb_condense_sweep_adjoint.hip, fb_condense_tangent.hip, a translation unit each): the kernel
+// that the unit's enum of fb_condense_plan.h names; *threads: its workgroup size
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseAdjointKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseMultiKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepAdjKernel which, int* threads);
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseTangentKernel which, int* threads);
 #if defined(FB_SINGLE_TU)
 // (diagnostic builds with device-side counters: one translation unit, one g_stamps)
 #include "rec_12_4_20.hip"
@@ -594,6 +595,7 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::Co
 #include "fb_condense_multi.hip"
 #include "fb_condense_sweep.hip"
 #include "fb_condense_sweep_adjoint.hip"
+#include "fb_condense_tangent.hip"
 #endif
 
 // The condensed route (include/fbstab_hip.h): its host side is fb_condense_stage.h, tested on the CPU
@@ -613,6 +615,20 @@ auto condense_dense_adjoint(fbstab_dense_handle_t h) {
     return fbstab_hip_dense_adjoint_batch(h, batch, dc, xc, seeds, sigma, &none, adj, status, kCondenseDenseFlags, (void*)s);
   };
 }
+// The direction kernel of the forward mode on the grid batch x (N + 1), behind the limits of its own LDS layout
+// (fb_tangent.h: MpcTangentLds) and of the grid.
+const auto condense_tangent_direction = [](int N, int nx, int nu, int nc, int batch, fbstab_mpc_batch_t dir,
+                                           fbstab_var_batch_t x, fbstab_var_batch_t seed, hipStream_t s) {
+  MpcTangentLds o;
+  o.init(nx, nu, nc);
+  if ((long long)o.total * 8 > kLdsLimitBytes)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED,
+                "condensed tangent: the perturbation images of one stage do not fit the 160 KiB LDS budget");
+  if ((long long)batch * (N + 1) > 0x7fffffffLL)
+    return condense_bad("condensed tangent", "batch x stages exceeds the grid limit");
+  void* args[] = {&N, &nx, &nu, &nc, &o, &dir, &x, &seed};
+  return condense_gpu(kCondenseTangentRhs, batch * (N + 1), (long long)o.total * 8, args, s);
+};
 auto condense_dense_multi(fbstab_dense_handle_t h) {
   return [h](int batch, const fbstab_dense_batch_t* dc, const fbstab_var_batch_t* xc, int nrhs,
              const fbstab_multi_var_batch_t* seeds, double sigma, const fbstab_multi_var_batch_t* step, int* status,
@@ -1459,6 +1475,15 @@ int fbstab_hip_mpc_condensed_adjoint_batch(fbstab_dense_handle_t h, int N, int n
                                            double* work, int* status, void* stream) {
   return condensed_adjoint_run(h, N, nx, nu, nc, batch, data, dense, x, seed, sigma, grad, adj, work, status, stream,
                                condense_gpu, condense_dense_adjoint(h));
+}
+
+int fbstab_hip_mpc_condensed_tangent_batch(fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch,
+                                           const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                           const fbstab_var_batch_t* x, const fbstab_mpc_batch_t* ddata, double sigma,
+                                           const fbstab_var_batch_t* dx, const fbstab_var_batch_t* rhs, double* work,
+                                           int* status, void* stream) {
+  return condensed_tangent_run(h, N, nx, nu, nc, batch, data, dense, x, ddata, sigma, dx, rhs, work, status, stream,
+                               condense_gpu, condense_dense_adjoint(h), condense_tangent_direction);
 }
 
 int fbstab_hip_mpc_condensed_multi_sizes(int N, int nx, int nu, int nc, int nrhs, int rhs_per_group,

@@ -233,6 +233,9 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "fbstab_hip_mpc_condensed_adjoint_batch"):  # (absent from an earlier build loaded for an A/B)
         lib.fbstab_hip_mpc_condensed_adjoint_batch.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [
             C.c_double] + [C.c_void_p] * 5
+    if hasattr(lib, "fbstab_hip_mpc_condensed_tangent_batch"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_condensed_tangent_batch.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [
+            C.c_double] + [C.c_void_p] * 5
     if hasattr(lib, "fbstab_hip_mpc_condensed_multi_sizes"):  # (absent from an earlier build loaded for an A/B)
         lib.fbstab_hip_mpc_condensed_multi_sizes.argtypes = [C.c_int] * 6 + [C.c_void_p] * 3
         lib.fbstab_hip_mpc_condensed_kkt_solve_batch.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [
@@ -297,7 +300,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_sweep_adjoint_kernel_name", "fbstab_hip_mpc_receding_sweep_scenario",
     "fbstab_hip_mpc_kkt_solve_batch", "fbstab_hip_mpc_x0_sensitivity_batch",
     "fbstab_hip_mpc_condensed_sizes", "fbstab_hip_mpc_condense_batch", "fbstab_hip_mpc_expand_batch",
-    "fbstab_hip_mpc_condensed_adjoint_batch",
+    "fbstab_hip_mpc_condensed_adjoint_batch", "fbstab_hip_mpc_condensed_tangent_batch",
     "fbstab_hip_mpc_condensed_multi_sizes", "fbstab_hip_mpc_condensed_kkt_solve_batch",
     "fbstab_hip_mpc_condensed_x0_sensitivity_batch",
     "fbstab_hip_mpc_condensed_sweep_sizes", "fbstab_hip_mpc_condensed_x0_map_batch",

@@ -658,14 +658,53 @@ int fbstab_hip_mpc_expand_batch(int N, int nx, int nu, int nc, int batch, const 
  * the device is checked, then the LDS rule of fbstab_hip_mpc_condensed_sizes (the seed and finish kernels run in that
  * layout; the two kernels of the refinement step use no LDS).
  * batch == 0 returns OK and queues nothing.  Deterministic as the condensing kernels are.  Not here: sums over the
- * batch on the device (the _reduced form), forward mode for general data directions (the x0 sensitivities and many
- * seeds per factorisation are the section below), the C++ facade, sharded calls, and certificates of
+ * batch on the device (the _reduced form; forward mode, the x0 sensitivities and many seeds per factorisation are the
+ * sections below), the C++ facade, sharded calls, and certificates of
  * infeasibility, which this route does not translate. */
 int fbstab_hip_mpc_condensed_adjoint_batch(fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch,
                                            const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
                                            const fbstab_var_batch_t* x, const fbstab_var_batch_t* seed,
                                            double sigma, const fbstab_mpc_grad_batch_t* grad,
                                            const fbstab_var_batch_t* adj, double* work, int* status, void* stream);
+
+/* ---- the condensed route: forward mode ------------------------------------------------------------------------------
+ * fbstab_hip_mpc_tangent_batch for points that the condensed route returned, at the cost of that route: the tangent
+ * (dz, dl, dv) = J dtheta of the solution map along a perturbation `ddata` of the 12 sequences.  Seven launches on
+ * one stream:
+ *   1. fbstab_mpc_condensed_tangent_rhs_kernel, grid batch x (N + 1), one workgroup per (QP, stage): the seeds
+ *      (gz, gl, gv) of the tangent system V dx = (gz, -gl, -C gv) from the perturbation and the point - the device
+ *      function of fbstab_hip_mpc_tangent_batch's direction kernel (fb_tangent.h), and its bits;
+ *   2. - 7. the six launches of fbstab_hip_mpc_condensed_adjoint_batch, unchanged, on those seeds, with every gradient
+ *      slot NULL and adj = dx.
+ * The step is the adjoint's: V regularised in the condensed variables alone, a bias of O(sigma), and dual to the
+ * adjoint's gradient table, <g, J dtheta> = sum_k <grad_k(g), dtheta_k>, up to rounding.
+ *   handle, data, dense, x, sigma, status, stream: exactly as for fbstab_hip_mpc_condensed_adjoint_batch.
+ *   ddata: as for fbstab_hip_mpc_tangent_batch - one slot per sequence; a NULL slot is a zero perturbation, neither
+ *          read nor multiplied; stride 0 is one direction shared by the batch, any other stride below the length with
+ *          batch > 1 is FBSTAB_HIP_ERR_ARGUMENT.  dQ and dR enter through their symmetric part.
+ *   dx:    receives (dz, dl, dv); all three slots are needed (the y slot is unused).
+ *   rhs:   NULL, or it receives the seeds (gz, gl, gv) (all three slots): the direction kernel writes them into the
+ *          caller's arrays and the chain reads them there.  With rhs NULL they live in the tail of `work`.
+ *   work:  caller-provided DEVICE memory, batch x (5 (N + 1) nu + 3 (N + 1) nc + nz + nl + nv) doubles with nz =
+ *          (N + 1)(nx + nu), nl = (N + 1) nx, nv = (N + 1) nc: the adjoint's work array, then gz, gl, gv, each one
+ *          packed array of the batch in this order.  Nothing is allocated by the call.
+ *   status: per QP, 0, or 1 where the dense factorisation failed (dx of that QP is zero), as in the adjoint.
+ * EVERY pointer is a DEVICE pointer; the work is queued on `stream` and the call returns.  Deterministic: a QP's bits
+ * depend on its own inputs and the shape alone, not on the batch, its place in it, or the grid.
+ * Checked in this order, everything before any device call: what needs no handle, in the order of
+ * fbstab_hip_mpc_condense_batch - the sizes, the batch and the data block; a NULL dense, x, ddata, dx, work or status;
+ * the condensed images; per vector the point's, dx's and rhs's pointer and stride; the strides of ddata - then the
+ * handle (NULL, not ((N + 1) nu, 0, (N + 1) nc), batch above max_batch).  batch == 0 returns OK and queues nothing.
+ * Then the device, then the LDS rule of fbstab_hip_mpc_condensed_sizes, then the direction kernel's own limits: its
+ * stage layout (fb_tangent.h: MpcTangentLds) above 160 KB is FBSTAB_HIP_ERR_UNSUPPORTED, batch x (N + 1) above
+ * INT_MAX is FBSTAB_HIP_ERR_ARGUMENT.
+ * Not here: several directions per factorisation, forward mode through the closed-loop sweep, the device-side
+ * reduced form, the C++ facade, sharded calls, certificates of infeasibility. */
+int fbstab_hip_mpc_condensed_tangent_batch(fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch,
+                                           const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                           const fbstab_var_batch_t* x, const fbstab_mpc_batch_t* ddata, double sigma,
+                                           const fbstab_var_batch_t* dx, const fbstab_var_batch_t* rhs, double* work,
+                                           int* status, void* stream);
 
 /* ---- the condensed route: many right-hand sides per factorisation, and the x0 sensitivity ------------------------
  * fbstab_hip_mpc_kkt_solve_batch and fbstab_hip_mpc_x0_sensitivity_batch for points that the condensed route
@@ -719,7 +758,7 @@ int fbstab_hip_mpc_condensed_adjoint_batch(fbstab_dense_handle_t handle, int N, 
  * gain both NULL (x0); NULL dense, x, work, status; the condensed images; x; the seed and step strides; gain_stride;
  * rhs_per_group < 0 - then the handle (NULL, not ((N + 1) nu, 0, (N + 1) nc), batch above max_batch), then the
  * device, then the LDS rule (FBSTAB_HIP_ERR_UNSUPPORTED).
- * Not here: forward mode for general data directions, the device-side reduced form, a dense factor kept between
+ * Not here: the device-side reduced form, a dense factor kept between
  * the two dense launches, the C++ facade, sharded calls, certificates of infeasibility. */
 int fbstab_hip_mpc_condensed_multi_sizes(int N, int nx, int nu, int nc, int nrhs, int rhs_per_group,
                                          int* rhs_per_group_used, long long* lds_bytes,
