@@ -373,6 +373,13 @@ struct SolverBase {
   }
 };
 
+// A handle's timed launch of an entry: the bracket of last_kernel_ms around launch_entry.
+inline int launch_timed(SolverBase* h, KernelEntry& e, int grid, void** args, hipStream_t s) {
+  RC_TRY(h->begin_timed(s));
+  RC_TRY(launch_entry(e, grid, args, s));
+  return h->end_timed(s);
+}
+
 // Device allocation released at scope exit.
 struct DevBuf {
   void* p = nullptr;
@@ -892,5 +899,85 @@ struct MultiStage {
     return FBSTAB_HIP_OK;
   }
 };
+
+// What a many-right-hand-side launch reads: the kernel-side arguments as multi_run staged them.
+template <class Data>
+struct MultiLaunchArgs {
+  Data a;                          // problem arrays
+  fbstab_var_batch_t v;            // point
+  fbstab_multi_var_batch_t sd, st; // seeds (all null in the generated-seed modes), steps
+  double* gain = nullptr;          // the extra per-QP output block (null: not asked for, or a kind without one)
+  long long gain_stride = 0;
+  int* d_st = nullptr;             // status
+  int nrhs = 0;
+  hipStream_t s = nullptr;
+};
+
+// ... and fbstab_hip_mpc_kkt_solve_batch / _x0_sensitivity_batch and fbstab_hip_dense_kkt_solve_batch /
+// _jacobian_batch behind the checks that need no handle: the argument checks in the order all four have always made
+// them, the staging of the arrays, the point, the seed and step blocks, `gain` (MPC's nu x nx per QP; null for
+// dense) and the status, `launch(k)` - the counter block zeroed, the argument list, the timed launch - and the results
+// back.  `sizes(&nrhs, &gain_len)` runs behind check_common and in front of every other check: the generated-seed
+// modes (seed == nullptr) take nrhs from the handle there (and dense refuses wrt = h without equality constraints),
+// MPC says how long a gain is.  A seed or step slot of a vector of length 0 is dropped, whatever it holds (dense
+// handles with nl == 0; every length of an MPC handle is positive).  step == nullptr: no step is asked for (x0 mode).
+template <class Handle, class Data, class Sizes, class Launch>
+int multi_run(Handle h, int batch, const Data* data, const fbstab_var_batch_t* x, int nrhs,
+              const fbstab_multi_var_batch_t* seed, const fbstab_multi_var_batch_t* step, double* gain,
+              long long gain_stride, int* status, int flags, void* stream, Sizes sizes, Launch launch) {
+  RC_TRY(check_common(h, batch, data, x, status, h ? h->max_batch : 0));
+  long long glen = 0;
+  RC_TRY(sizes(&nrhs, &glen));
+  const long long* vlen = h->var_len;
+  for (size_t i = 0; i < h->arr_len.size(); i++)  // (nl == 0: the G and h slots are empty)
+    if (!data->base[i] && h->arr_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
+  for (int i = 0; i < 3; i++)
+    if (!x->base[i] && vlen[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
+  for (int i = 0; i < 3; i++) RC_TRY(h->check_var_stride(x->stride, i, batch));
+  fbstab_multi_var_batch_t sd_in{}, st_in{};
+  if (seed) sd_in = *seed;
+  if (step) st_in = *step;
+  for (int i = 0; i < 3; i++)
+    if (vlen[i] == 0) sd_in.base[i] = st_in.base[i] = nullptr;
+  RC_TRY(check_multi_strides(&sd_in, vlen, batch, nrhs, true));
+  RC_TRY(check_multi_strides(&st_in, vlen, batch, nrhs, false));
+  if (batch > 1 && gain && gain_stride < glen) return fail(FBSTAB_HIP_ERR_ARGUMENT, "gain stride smaller than nu x nx");
+  RC_TRY(h->check_data_strides(data->stride, batch));
+  if (batch == 0) return FBSTAB_HIP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  MultiLaunchArgs<Data> k;
+  hipStream_t s = k.s = stream ? (hipStream_t)stream : h->stream;
+  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
+  RC_TRY(h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, k.a.base, k.a.stride));
+  RC_TRY(h->stage_vars(x->base, x->stride, 3, batch, dev_ptrs, s, &k.v));
+  MultiStage sd, st;
+  RC_TRY(sd.open(&sd_in, vlen, batch, nrhs, dev_ptrs, true, s));
+  RC_TRY(st.open(&st_in, vlen, batch, nrhs, dev_ptrs, false, s));
+  k.sd = sd.k;
+  k.st = st.k;
+  DevBuf d_gain, d_status;
+  k.gain = gain;
+  k.gain_stride = batch > 1 ? gain_stride : 0;
+  if (gain && !dev_ptrs) {
+    HIP_TRY(hipMalloc(&d_gain.p, sizeof(double) * (size_t)glen * batch));
+    k.gain = static_cast<double*>(d_gain.p);
+    k.gain_stride = glen;
+  }
+  k.d_st = status;
+  const bool status_host = SolverBase::out_on_host(flags);
+  if (status_host) {
+    HIP_TRY(hipMalloc(&d_status.p, sizeof(int) * (size_t)batch));
+    k.d_st = static_cast<int*>(d_status.p);
+  }
+  k.nrhs = nrhs;
+  RC_TRY(launch(k));
+  if (!dev_ptrs) {
+    RC_TRY(st.download(&st_in, vlen, batch, nrhs, s));
+    if (gain) RC_TRY(h->download(gain, gain_stride, glen, batch, k.gain, s));
+  }
+  if (status_host) HIP_TRY(hipMemcpyAsync(status, k.d_st, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
+  if (status_host || !(flags & FBSTAB_HIP_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
+  return FBSTAB_HIP_OK;
+}
 
 }  // namespace

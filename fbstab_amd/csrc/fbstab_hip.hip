@@ -498,8 +498,9 @@ __global__ __launch_bounds__(kDenseTangentThreads) void fbstab_dense_tangent_rhs
 
 }  // namespace
 
-// The host staging of every entry point below: no device code, and tested on the CPU (tests/test_host_stage.py).
-#include "fb_host_stage.h"
+// The host staging of every entry point below (fb_host_stage.h, and the sweeps' beside it): no device code, and tested
+// on the CPU (tests/test_host_stage.py).
+#include "fb_sweep_stage.h"
 
 // An entry of an MPC handle's table.  The kernels of a record instance share one argument list and run in the
 // handle's scratch; the flat-vector kernels share another (the adjoint a third) and run in `ws`.
@@ -519,10 +520,9 @@ struct fbstab_mpc_solver : SolverBase {
   // the record kernel), allocated by the first call
   bool flat_adjoint = false;
   double* adj_scratch = nullptr;
-  // fbstab_hip_mpc_receding_sweep_adjoint, allocated by the first call that needs them: the seed vectors of the
-  // one-launch kernel (nz doubles per row slot of the grid) and the per-step form's image of one step
-  double* sweep_seed = nullptr;
-  double* sweep_tmp = nullptr;
+  // fbstab_hip_mpc_receding_sweep_adjoint, allocated by the first call that needs them (sweep_adjoint_run): the seed
+  // vectors of the one-launch kernel (nz doubles per row slot of the grid) and the per-step form's image of one step
+  SweepScratch sweep;
   // The longest-first queue (fb_queue_order_plan.h): whether this handle keeps an order at all (record handles,
   // FBSTAB_HIP_QUEUE_ORDER at creation), the QP indices by descending Newton count of the last packed batch solve
   // (max_batch ints, written by fbstab_mpc_queue_order_kernel behind that solve; the kernel's counters behind them:
@@ -540,8 +540,8 @@ struct fbstab_mpc_solver : SolverBase {
   ~fbstab_mpc_solver() {
     (void)hipSetDevice(device);
     if (adj_scratch) (void)hipFree(adj_scratch);
-    if (sweep_seed) (void)hipFree(sweep_seed);
-    if (sweep_tmp) (void)hipFree(sweep_tmp);
+    if (sweep.seed) (void)hipFree(sweep.seed);
+    if (sweep.tmp) (void)hipFree(sweep.tmp);
     if (order) (void)hipFree(order);
   }
   // Grid of a batch launch of entry `e` (fbk::batch_grid: a record kernel's small batches are spread)
@@ -969,8 +969,15 @@ int fbstab_hip_mpc_solve_traced(fbstab_mpc_handle_t h, const fbstab_mpc_batch_t*
   return tb.close(trace, capacity, count);
 }
 
+// What the sweeps' host stages (fb_sweep_stage.h) read of a handle.
+static SweepShape sweep_shape(const fbstab_mpc_solver* h) {
+  if (!h) return SweepShape{};
+  return SweepShape{h->lay.N, h->lay.nx, h->lay.nu, h->lay.nc, h->rec != nullptr, h->qps_per_wg,
+                    h->kern.sweep_adjoint.kern != nullptr};
+}
+
 // BASELINE configs[4]: `steps` closed-loop steps without a host round trip in
-// between - solve, plant step, solve, ... queued on one stream.
+// between - solve, plant step, solve, ... queued on one stream: sweep_run on the real launches.
 // (`log`: fbstab_hip_mpc_receding_sweep_logged; null: nothing is logged.  `sc`:
 // fbstab_hip_mpc_receding_sweep_scenario; null: no disturbance, no shift)
 static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
@@ -978,108 +985,44 @@ static int mpc_receding_sweep_impl(fbstab_mpc_handle_t h, int batch, const fbsta
                                    const fbstab_receding_plant_t* plant, int steps, int retire, double* u_log,
                                    unsigned long long* stats, float* kernel_ms, void* stream,
                                    const fbstab_sweep_log_t* log, const fbstab_sweep_scenario_t* sc = nullptr) {
-  int rc = check_common(h, batch, data, x, out, h ? h->max_batch : 0);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  if (!plant || !plant->A || !plant->B || steps < 0)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "plant matrices and a non-negative step count are required");
-  if (sc && sc->shift != 0 && sc->shift != 1)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "receding sweep scenario: shift is 0 or 1");
-  const double* w = sc ? sc->w : nullptr;
-  const bool shift = sc && sc->shift == 1;
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
-    if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
-  for (int i = 0; i < 4; i++)
-    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
-  // x0 is advanced in place, one state per trajectory: a shared x0 would be written by all of them
-  if (batch > 1 && data->stride[FBSTAB_MPC_x0] < h->lay.nx)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "receding sweep: every trajectory needs its own x0 (stride >= nx)");
-  rc = h->check_solve_strides(data->stride, x->stride, batch, FBSTAB_MPC_x0);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  if (batch == 0 || steps == 0) return FBSTAB_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  DevBuf d_ret, d_stats;
-  HIP_TRY(hipMalloc(&d_ret.p, sizeof(int) * (size_t)batch));
-  HIP_TRY(hipMalloc(&d_stats.p, sizeof(unsigned long long) * 4 * (size_t)steps));
-  HIP_TRY(hipMemsetAsync(d_ret.p, 0, sizeof(int) * (size_t)batch, s));
-  HIP_TRY(hipMemsetAsync(d_stats.p, 0, sizeof(unsigned long long) * 4 * (size_t)steps, s));
-  std::vector<hipEvent_t> ev;
-  struct EvGuard {
-    std::vector<hipEvent_t>& e;
-    ~EvGuard() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
-  } guard{ev};
-  if (kernel_ms) {
-    ev.resize(2 * (size_t)steps, nullptr);
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-  }
-  const fbk::MpcLayout& L = h->lay;
-  double* x0 = const_cast<double*>(data->base[FBSTAB_MPC_x0]);
-  // Record kernels: the whole sweep is ONE launch of the KEEP instance, every row
-  // looping over its own trajectory (SweepArgs; FBSTAB_HIP_SWEEP_PER_STEP=1 keeps the
-  // launch per step below, which the flat-vector kernel always uses).
-  if (fbk::sweep_in_one_launch(h->rec != nullptr, batch, h->workgroups, h->qps_per_wg, steps, fbk::sweep_per_step())) {
-    SweepArgs sa;
-    sa.A = plant->A; sa.B = plant->B; sa.sA = plant->stride_A; sa.sB = plant->stride_B;
-    sa.x0 = x0; sa.sx0 = data->stride[FBSTAB_MPC_x0];
-    sa.u_log = u_log; sa.stats = static_cast<unsigned long long*>(d_stats.p);
-    sa.steps = steps; sa.retire = retire;
-    sa.nx = L.nx; sa.nu = L.nu; sa.nz = L.nz; sa.nl = L.nl; sa.nv = L.nv;
-    sa.log_z = log ? log->z : nullptr; sa.log_l = log ? log->l : nullptr; sa.log_v = log ? log->v : nullptr;
-    sa.log_x0 = log ? log->x0 : nullptr; sa.log_eflag = log ? log->eflag : nullptr;
-    sa.w = w; sa.shift = shift ? 1 : 0; sa.N = L.N; sa.nc = L.nc;
-    sa.lpq = 64 / h->qps_per_wg; sa.cnt = static_cast<int*>(d_ret.p);
-    for (int i = 0; i < 3; i++) { sa.xb[i] = x->base[i]; sa.sxb[i] = x->stride[i]; }
-    DevBuf d_sa;
-    HIP_TRY(hipMalloc(&d_sa.p, sizeof(SweepArgs)));
-    HIP_TRY(hipMemcpyAsync(d_sa.p, &sa, sizeof(SweepArgs), hipMemcpyHostToDevice, s));
+  // (the callables run behind sweep_run's checks: h, data, x and plant are there)
+  auto x0 = [=] { return const_cast<double*>(data->base[FBSTAB_MPC_x0]); };
+  auto fill_args = [=](SweepArgs* sa, unsigned long long* d_stats, int* d_ret) {
+    const fbk::MpcLayout& L = h->lay;
+    sa->A = plant->A; sa->B = plant->B; sa->sA = plant->stride_A; sa->sB = plant->stride_B;
+    sa->x0 = x0(); sa->sx0 = data->stride[FBSTAB_MPC_x0];
+    sa->u_log = u_log; sa->stats = d_stats;
+    sa->steps = steps; sa->retire = retire;
+    sa->nx = L.nx; sa->nu = L.nu; sa->nz = L.nz; sa->nl = L.nl; sa->nv = L.nv;
+    sa->log_z = log ? log->z : nullptr; sa->log_l = log ? log->l : nullptr; sa->log_v = log ? log->v : nullptr;
+    sa->log_x0 = log ? log->x0 : nullptr; sa->log_eflag = log ? log->eflag : nullptr;
+    sa->w = sc ? sc->w : nullptr; sa->shift = sc && sc->shift == 1 ? 1 : 0; sa->N = L.N; sa->nc = L.nc;
+    sa->lpq = 64 / h->qps_per_wg; sa->cnt = d_ret;
+    for (int i = 0; i < 3; i++) { sa->xb[i] = x->base[i]; sa->sxb[i] = x->stride[i]; }
+  };
+  auto one_launch = [=](hipStream_t s, double* d_sa) -> int {
     HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
     RC_TRY(h->begin_timed(s));
-    RC_TRY(launch_mpc(h, h->kern.solve_keep, fbk::keep_grid(batch, h->qps_per_wg), s, *data, *x, out, batch,
-                      static_cast<double*>(d_sa.p), false));
+    RC_TRY(launch_mpc(h, h->kern.solve_keep, fbk::keep_grid(batch, h->qps_per_wg), s, *data, *x, out, batch, d_sa, false));
     RC_TRY(h->end_timed(s));
     h->kept_batch = batch;
-    if (stats)
-      HIP_TRY(hipMemcpyAsync(stats, d_stats.p, sizeof(unsigned long long) * 4 * (size_t)steps, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (kernel_ms) {  // one launch: every step is charged its share
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-      for (int k = 0; k < steps; k++) kernel_ms[k] = ms / (float)steps;
-    }
     return FBSTAB_HIP_OK;
-  }
-  const int flags = FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC | FBSTAB_HIP_KEEP_MATRICES;
-  h->kept_batch = -1;  // the first step builds the matrix copies
-  DevBuf d_xtmp;  // the plant step's new states, for more than 64 of them per trajectory
-  if (L.nx > 64) HIP_TRY(hipMalloc(&d_xtmp.p, sizeof(double) * (size_t)batch * L.nx));
-  for (int k = 0; k < steps; k++) {
-    if (kernel_ms) HIP_TRY(hipEventRecord(ev[2 * k], s));
-    rc = mpc_solve_impl(h, batch, data, x, out, flags, s, nullptr);
-    if (rc != FBSTAB_HIP_OK) return rc;
-    if (kernel_ms) HIP_TRY(hipEventRecord(ev[2 * k + 1], s));
-    SweepLogStep lg = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (log) {
-      const long long kb = (long long)k * batch;
-      lg.z = log->z ? log->z + kb * L.nz : nullptr;
-      lg.l = log->l ? log->l + kb * L.nl : nullptr;
-      lg.v = log->v ? log->v + kb * L.nv : nullptr;
-      lg.x0 = log->x0 ? log->x0 + kb * L.nx : nullptr;
-      lg.eflag = log->eflag ? log->eflag + kb : nullptr;
-    }
+  };
+  auto solve = [=](hipStream_t s, int k) {
+    if (k == 0) h->kept_batch = -1;  // the first step builds the matrix copies
+    return mpc_solve_impl(h, batch, data, x, out, FBSTAB_HIP_DEVICE_POINTERS | FBSTAB_HIP_ASYNC | FBSTAB_HIP_KEEP_MATRICES,
+                          s, nullptr);
+  };
+  auto plant_step = [=](hipStream_t s, const SweepStep& st, int* d_ret, double* d_xtmp) {
+    const fbk::MpcLayout& L = h->lay;
+    const SweepLogStep lg = {st.z, st.l, st.v, st.x0, st.eflag};
     hipLaunchKernelGGL(fbstab_receding_plant_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, batch, L.nx, L.nu,
-                       L.nz, L.nl, L.nv, plant->A, plant->stride_A, plant->B, plant->stride_B, x0,
-                       data->stride[FBSTAB_MPC_x0], *x, out, static_cast<int*>(d_ret.p), retire,
-                       u_log ? u_log + (long long)k * batch * L.nu : nullptr,
-                       static_cast<unsigned long long*>(d_stats.p) + 4 * k, static_cast<double*>(d_xtmp.p), lg,
-                       w ? w + (long long)k * batch * L.nx : nullptr, shift && k + 1 < steps ? L.N : 0, L.nc);
-  }
-  HIP_TRY(hipGetLastError());
-  if (stats)
-    HIP_TRY(hipMemcpyAsync(stats, d_stats.p, sizeof(unsigned long long) * 4 * (size_t)steps, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (kernel_ms)
-    for (int k = 0; k < steps; k++) HIP_TRY(hipEventElapsedTime(&kernel_ms[k], ev[2 * k], ev[2 * k + 1]));
-  return FBSTAB_HIP_OK;
+                       L.nz, L.nl, L.nv, plant->A, plant->stride_A, plant->B, plant->stride_B, x0(),
+                       data->stride[FBSTAB_MPC_x0], *x, out, d_ret, retire, st.u_log, st.stats, d_xtmp, lg, st.w,
+                       st.shift_stages, L.nc);
+  };
+  return sweep_run<SweepArgs>(h, sweep_shape(h), batch, data, x, out, plant, steps, u_log, stats, kernel_ms, stream,
+                              log, sc, fill_args, one_launch, solve, plant_step);
 }
 
 int fbstab_hip_mpc_receding_sweep(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
@@ -1203,56 +1146,16 @@ int fbstab_hip_mpc_adjoint_batch_reduced(fbstab_mpc_handle_t h, int batch, const
 // Reverse mode through a logged receding-horizon sweep (include/fbstab_hip.h has the recursion).  Handles on a
 // record adjoint: one launch of fbstab_mpc_r16_sweep_adjoint_kernel; every other handle, and
 // FBSTAB_HIP_SWEEP_ADJOINT_PER_STEP=1: per step the costate kernel, the handle's adjoint launch, the costate kernel.
-static bool sweep_adjoint_in_one_launch(const fbstab_mpc_solver* h) {
-  return h->kern.sweep_adjoint.kern && !fbk::sweep_adjoint_per_step();
-}
-
 int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data,
                                           const fbstab_receding_plant_t* plant, int steps, int retire,
                                           const fbstab_sweep_log_t* log, const double* gu, const double* gx,
                                           double sigma, const fbstab_mpc_grad_batch_t* grad, double* mu_log,
                                           int* status, void* stream) {
   (void)retire;  // (what it did to the sweep is in the log: eflag -1)
-  // what needs no handle comes first
-  if (!log) return fail(FBSTAB_HIP_ERR_ARGUMENT, "sweep adjoint: null log");
-  if (!log->z || !log->l || !log->v || !log->eflag)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "sweep adjoint: the log's z, l, v and eflag are required");
-  if (steps < 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "sweep adjoint: negative step count");
-  if (!data || !grad || !status) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null argument");
-  if (!plant || !plant->A || !plant->B) return fail(FBSTAB_HIP_ERR_ARGUMENT, "sweep adjoint: plant matrices are required");
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++)
-    if (batch > 1 && grad->base[i] && grad->stride[i] == 0)
-      return fail(FBSTAB_HIP_ERR_ARGUMENT,
-                  "sweep adjoint: a gradient slot of stride 0 (summed over the batch) is not served");
-  if (!h) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null solver handle");
-  if (batch < 0 || batch > h->max_batch)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "batch exceeds the max_batch the handle was created with");
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-    if (i != FBSTAB_MPC_x0 && !data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
-    if (batch > 1 && i != FBSTAB_MPC_x0 && data->stride[i] != 0 && data->stride[i] < h->arr_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "problem data stride smaller than the array length");
-    if (batch > 1 && grad->base[i] && grad->stride[i] < h->arr_len[i])
-      return fail(FBSTAB_HIP_ERR_ARGUMENT, "gradient stride smaller than the array length");
-  }
-  if (batch == 0) return FBSTAB_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const fbk::MpcLayout& L = h->lay;
-  const double sig = sigma_or_default(sigma);
-  const long long nz = L.nz, nl = L.nl, nv = L.nv;
-  // the kernels' problem data: the x0 slot, which the Newton matrix at x = xbar does not depend on, points at the
-  // states of the logged z (the record packs read SOMETHING there)
-  fbstab_mpc_batch_t a = *data;
-  if (batch == 1)
-    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) a.stride[i] = 0;
-  a.base[FBSTAB_MPC_x0] = log->z;
-  a.stride[FBSTAB_MPC_x0] = nz;
-  h->kept_batch = -1;  // the slots' matrix copies are overwritten
-  if (sweep_adjoint_in_one_launch(h)) {
+  // (the callables run behind sweep_adjoint_run's checks: h, plant, log and grad are there)
+  auto one_launch = [=](hipStream_t s, const fbstab_mpc_batch_t& a, double* seed) -> int {
+    h->kept_batch = -1;  // the slots' matrix copies are overwritten
     MpcKernel& e = h->kern.sweep_adjoint;
-    const size_t seed_bytes = fbk::sweep_seed_bytes(nz, h->workgroups, h->qps_per_wg);
-    if (!h->sweep_seed) HIP_TRY(hipMalloc(&h->sweep_seed, seed_bytes));
-    HIP_TRY(hipMemsetAsync(h->sweep_seed, 0, seed_bytes, s));
     HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
     MpcBatchPtrs d = record_data(h, a);
     SweepAdjointArgs aa;
@@ -1260,73 +1163,36 @@ int fbstab_hip_mpc_receding_sweep_adjoint(fbstab_mpc_handle_t h, int batch, cons
     aa.A = plant->A; aa.B = plant->B; aa.sA = plant->stride_A; aa.sB = plant->stride_B;
     aa.lz = log->z; aa.ll = log->l; aa.lv = log->v; aa.le = log->eflag;
     aa.gu = gu; aa.gx = gx;
-    aa.mu_log = mu_log; aa.status = status; aa.seed = h->sweep_seed;
-    aa.steps = steps; aa.sigma = sig; aa.alpha = h->opts.alpha;
+    aa.mu_log = mu_log; aa.status = status; aa.seed = seed;
+    aa.steps = steps; aa.sigma = sigma_or_default(sigma); aa.alpha = h->opts.alpha;
     // (as the adjoint: a batch that does not outnumber the workgroups runs one trajectory per wavefront)
-    int N = L.N;
-    void* args[] = {&d, &aa, &h->scratch, &h->counter, &batch, &N};
-    RC_TRY(h->begin_timed(s));
-    RC_TRY(launch_entry(e, h->batch_grid(e, batch), args, s));
-    RC_TRY(h->end_timed(s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return FBSTAB_HIP_OK;
-  }
-  // per step: the image of one step (every sequence), the seed vectors, lambda / mu, A'mu, the step's status
-  long long img = 0;
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) img += h->arr_len[i];
-  const long long per_qp = img + nz + 2 * L.nx + 1;  // (+ the status word, in a double's place)
-  if (!h->sweep_tmp) HIP_TRY(hipMalloc(&h->sweep_tmp, sizeof(double) * (size_t)per_qp * (size_t)h->max_batch));
-  SweepCostateArgs ca;
-  AdjointLaunchArgs st;
-  double* w = h->sweep_tmp;
-  ca.grad = *grad;
-  st.a = a;
-  for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) {
-    const bool wanted = grad->base[i] != nullptr || i == FBSTAB_MPC_x0;
-    ca.len[i] = h->arr_len[i];
-    ca.tmp[i] = wanted ? w : nullptr;
-    st.g.base[i] = wanted ? w : nullptr; st.g.stride[i] = h->arr_len[i];
-    w += h->arr_len[i] * h->max_batch;
-  }
-  ca.seed = w; w += nz * h->max_batch;
-  ca.lam = w; w += (long long)L.nx * h->max_batch;
-  ca.atm = w; w += (long long)L.nx * h->max_batch;
-  int* tmp_status = reinterpret_cast<int*>(w);
-  ca.tmp_status = tmp_status;
-  ca.status = status;
-  ca.A = plant->A; ca.B = plant->B; ca.sA = plant->stride_A; ca.sB = plant->stride_B;
-  ca.nx = L.nx; ca.nu = L.nu; ca.nz = L.nz;
-  ca.eflag = nullptr; ca.gu = ca.gx = nullptr; ca.mu_log = nullptr;
-  st.v = st.sd = st.ad = fbstab_var_batch_t{};
-  st.sd.base[0] = ca.seed; st.sd.stride[0] = nz;
-  st.d_st = tmp_status;
-  st.s = s;
-  hipLaunchKernelGGL(fbstab_sweep_costate_kernel, dim3(batch), dim3(64), 0, s, ca, 0, 0);
-  HIP_TRY(hipGetLastError());
-  for (int k = steps - 1; k >= 0; k--) {
-    const long long kb = (long long)k * batch;
-    ca.eflag = log->eflag + kb;
-    ca.gu = gu ? gu + kb * L.nu : nullptr;
-    ca.gx = gx ? gx + kb * L.nx : nullptr;
-    ca.mu_log = mu_log ? mu_log + kb * L.nx : nullptr;
-    hipLaunchKernelGGL(fbstab_sweep_costate_kernel, dim3(batch), dim3(64), 0, s, ca, 1, 0);
-    HIP_TRY(hipGetLastError());
-    st.v.base[0] = log->z + kb * nz; st.v.stride[0] = nz;
-    st.v.base[1] = log->l + kb * nl; st.v.stride[1] = nl;
-    st.v.base[2] = log->v + kb * nv; st.v.stride[2] = nv;
-    int rc = mpc_adjoint_launch(h, batch, st, sig);
-    if (rc != FBSTAB_HIP_OK) return rc;
-    hipLaunchKernelGGL(fbstab_sweep_costate_kernel, dim3(batch), dim3(64), 0, s, ca, 2, k == 0 ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  return FBSTAB_HIP_OK;
+    int N = h->lay.N, b = batch;
+    void* args[] = {&d, &aa, &h->scratch, &h->counter, &b, &N};
+    return launch_timed(h, e, h->batch_grid(e, batch), args, s);
+  };
+  auto costate = [=](hipStream_t s, const SweepCostateStep& c, int phase, int last) {
+    if (phase == 0) h->kept_batch = -1;  // (as above, whichever kernel the adjoint launches run on)
+    SweepCostateArgs ca;
+    ca.A = plant->A; ca.B = plant->B; ca.sA = plant->stride_A; ca.sB = plant->stride_B;
+    ca.eflag = c.eflag; ca.gu = c.gu; ca.gx = c.gx; ca.mu_log = c.mu_log;
+    ca.grad = *grad;
+    for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) { ca.tmp[i] = c.tmp[i]; ca.len[i] = c.len[i]; }
+    ca.seed = c.seed; ca.lam = c.lam; ca.atm = c.atm;
+    ca.tmp_status = c.tmp_status;
+    ca.status = status;
+    ca.nx = h->lay.nx; ca.nu = h->lay.nu; ca.nz = h->lay.nz;
+    hipLaunchKernelGGL(fbstab_sweep_costate_kernel, dim3(batch), dim3(64), 0, s, ca, phase, last);
+  };
+  auto adjoint = [=](AdjointLaunchArgs& st, double sig) { return mpc_adjoint_launch(h, batch, st, sig); };
+  SweepScratch none;
+  return sweep_adjoint_run(h, sweep_shape(h), h ? h->sweep : none, batch, data, plant, steps, log, gu, gx, sigma, grad,
+                           mu_log, status, stream, one_launch, costate, adjoint);
 }
 
 // Name of what the next fbstab_hip_mpc_receding_sweep_adjoint of this handle launches (diagnostics, tests, tools).
 const char* fbstab_hip_mpc_sweep_adjoint_kernel_name(fbstab_mpc_handle_t h) {
   if (!h) return "";
-  return sweep_adjoint_in_one_launch(h) ? h->kern.sweep_adjoint.name : "fbstab_sweep_costate_kernel";
+  return sweep_adjoint_in_one_launch(sweep_shape(h)) ? h->kern.sweep_adjoint.name : "fbstab_sweep_costate_kernel";
 }
 
 // Forward-mode derivative of the solution map (include/fbstab_hip.h): fbstab_tangent_rhs_kernel forms the seeds
@@ -1359,74 +1225,32 @@ int fbstab_hip_mpc_tangent_batch(fbstab_mpc_handle_t h, int batch, const fbstab_
 
 // ---- many right-hand sides on one factorisation (include/fbstab_hip.h; fb_kkt_multi.h) --------------------------
 namespace {
-// Both entry points behind what needs no handle.  seed == nullptr: the x0 mode (nrhs = nx, the seeds generated in the
-// kernel); step may be null there, and gain (null, or nu x nx per QP) is served there only.
+// Both entry points behind what needs no handle, on multi_run (fb_host_stage.h).  seed == nullptr: the x0 mode (nrhs =
+// nx, the seeds generated in the kernel); step may be null there, and gain (null, or nu x nx per QP) is served there
+// only.
 int kkt_multi_run(fbstab_mpc_handle_t h, int batch, const fbstab_mpc_batch_t* data, const fbstab_var_batch_t* x,
                   int nrhs, const fbstab_multi_var_batch_t* seed, double sigma, const fbstab_multi_var_batch_t* step,
                   double* gain, long long gain_stride, int* status, int flags, void* stream) {
-  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  const fbk::MpcLayout& L = h->lay;
-  const bool x0_mode = seed == nullptr;
-  if (x0_mode) nrhs = L.nx;
-  const long long* vlen = h->var_len;
-  const long long glen = (long long)L.nu * L.nx;
-  for (size_t i = 0; i < h->arr_len.size(); i++)
-    if (!data->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
-  for (int i = 0; i < 3; i++)
-    if (!x->base[i]) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
-  for (int i = 0; i < 3; i++) RC_TRY(h->check_var_stride(x->stride, i, batch));
-  if (seed) RC_TRY(check_multi_strides(seed, vlen, batch, nrhs, true));
-  if (step) RC_TRY(check_multi_strides(step, vlen, batch, nrhs, false));
-  if (batch > 1 && gain && gain_stride < glen)
-    return fail(FBSTAB_HIP_ERR_ARGUMENT, "gain stride smaller than nu x nx");
-  RC_TRY(h->check_data_strides(data->stride, batch));
-  if (batch == 0) return FBSTAB_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
-  fbstab_mpc_batch_t a;
-  fbstab_var_batch_t v;
-  RC_TRY(h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride));
-  RC_TRY(h->stage_vars(x->base, x->stride, 3, batch, dev_ptrs, s, &v));
-  MultiStage sd, st;
-  RC_TRY(sd.open(seed, vlen, batch, nrhs, dev_ptrs, true, s));
-  RC_TRY(st.open(step, vlen, batch, nrhs, dev_ptrs, false, s));
-  DevBuf d_gain, d_status;
-  double* k_gain = gain;
-  long long k_gain_stride = batch > 1 ? gain_stride : 0;
-  if (gain && !dev_ptrs) {
-    HIP_TRY(hipMalloc(&d_gain.p, sizeof(double) * (size_t)glen * batch));
-    k_gain = static_cast<double*>(d_gain.p);
-    k_gain_stride = glen;
-  }
-  int* d_st = status;
-  const bool status_host = SolverBase::out_on_host(flags);
-  if (status_host) {
-    HIP_TRY(hipMalloc(&d_status.p, sizeof(int) * (size_t)batch));
-    d_st = static_cast<int*>(d_status.p);
-  }
-  double sig = sigma_or_default(sigma);
-  double alpha = h->opts.alpha;
-  int x0m = x0_mode ? 1 : 0;
-  HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, s));
-  MpcKernel& e = h->kern.kkt_multi;
-  // (the flat adjoint's scratch on a record handle, allocated here by the first call that needs it; the handle's
-  // own scratch and kept_batch stay as they are)
-  double* scratch;
-  RC_TRY(flat_workspace(h, e, &scratch));
-  void* args[] = {const_cast<fbk::MpcLayout*>(&L), &a, &v, &sd.k, &st.k, &k_gain, &k_gain_stride, &d_st, &nrhs, &x0m,
-                  &sig, &alpha, &scratch, &h->counter, &batch};
-  RC_TRY(h->begin_timed(s));
-  RC_TRY(launch_entry(e, h->batch_grid(e, batch), args, s));
-  RC_TRY(h->end_timed(s));
-  if (!dev_ptrs) {
-    RC_TRY(st.download(step, vlen, batch, nrhs, s));
-    if (gain) RC_TRY(h->download(gain, gain_stride, glen, batch, k_gain, s));
-  }
-  if (status_host) HIP_TRY(hipMemcpyAsync(status, d_st, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
-  if (status_host || !(flags & FBSTAB_HIP_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
-  return FBSTAB_HIP_OK;
+  int x0m = seed ? 0 : 1;
+  auto sizes = [&](int* n, long long* gain_len) {
+    if (x0m) *n = h->lay.nx;
+    *gain_len = (long long)h->lay.nu * h->lay.nx;
+    return (int)FBSTAB_HIP_OK;
+  };
+  auto launch = [&](MultiLaunchArgs<fbstab_mpc_batch_t>& k) -> int {
+    double sig = sigma_or_default(sigma);
+    double alpha = h->opts.alpha;
+    HIP_TRY(hipMemsetAsync(h->counter, 0, kQueueBytes, k.s));
+    MpcKernel& e = h->kern.kkt_multi;
+    // (the flat adjoint's scratch on a record handle, allocated here by the first call that needs it; the handle's
+    // own scratch and kept_batch stay as they are)
+    double* scratch;
+    RC_TRY(flat_workspace(h, e, &scratch));
+    void* args[] = {&h->lay, &k.a, &k.v, &k.sd, &k.st, &k.gain, &k.gain_stride, &k.d_st, &k.nrhs, &x0m, &sig, &alpha,
+                    &scratch, &h->counter, &batch};
+    return launch_timed(h, e, h->batch_grid(e, batch), args, k.s);
+  };
+  return multi_run(h, batch, data, x, nrhs, seed, step, gain, gain_stride, status, flags, stream, sizes, launch);
 }
 }  // namespace
 
@@ -1878,66 +1702,32 @@ int fbstab_hip_dense_tangent_batch(fbstab_dense_handle_t h, int batch, const fbs
 // ---- many right-hand sides on one factorisation of the dense Newton matrix (include/fbstab_hip.h;
 // fb_dense_kkt_multi.h) ----------------------------------------------------------------------------------------
 namespace {
-// Both entry points behind what needs no handle.  seed == nullptr: the Jacobian mode (nrhs = the length of f, h or
-// b, the seeds generated in the kernel).  One launch of the kernel beside the handle's adjoint kernel, in the
-// handle's own scratch, around the staging the MPC calls use (MultiStage).
+// Both entry points behind what needs no handle, on multi_run (fb_host_stage.h).  seed == nullptr: the Jacobian mode
+// (nrhs = the length of f, h or b, the seeds generated in the kernel).  One launch of the kernel beside the handle's
+// adjoint kernel, in the handle's own scratch.
 int dense_kkt_multi_run(fbstab_dense_handle_t h, int batch, const fbstab_dense_batch_t* data,
                         const fbstab_var_batch_t* x, int nrhs, const fbstab_multi_var_batch_t* seed, int wrt,
                         double sigma, const fbstab_multi_var_batch_t* step, int* status, int flags, void* stream) {
-  int rc = check_common(h, batch, data, x, status, h ? h->max_batch : 0);
-  if (rc != FBSTAB_HIP_OK) return rc;
-  const long long* vlen = h->var_len;
-  if (!seed) {
+  if (seed) wrt = fbk::kDenseKktSeeded;
+  auto sizes = [&](int* n, long long*) {
+    if (seed) return (int)FBSTAB_HIP_OK;
+    const long long* vlen = h->var_len;
     if (wrt == FBSTAB_DENSE_h && vlen[1] == 0)
       return fail(FBSTAB_HIP_ERR_ARGUMENT, "dense jacobian: wrt = h on a handle without equality constraints");
-    nrhs = (int)(wrt == FBSTAB_DENSE_f ? vlen[0] : wrt == FBSTAB_DENSE_h ? vlen[1] : vlen[2]);
-  } else {
-    wrt = fbk::kDenseKktSeeded;
-  }
-  for (size_t i = 0; i < h->arr_len.size(); i++)  // (nl == 0: the G and h slots are empty)
-    if (!data->base[i] && h->arr_len[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null problem data pointer");
-  for (int i = 0; i < 3; i++)
-    if (!x->base[i] && vlen[i] > 0) return fail(FBSTAB_HIP_ERR_ARGUMENT, "null variable pointer");
-  for (int i = 0; i < 3; i++) RC_TRY(h->check_var_stride(x->stride, i, batch));
-  // (nl == 0: the l slots are ignored, whatever they hold)
-  fbstab_multi_var_batch_t sd_in{}, st_in = *step;
-  if (seed) sd_in = *seed;
-  if (vlen[1] == 0) sd_in.base[1] = st_in.base[1] = nullptr;
-  if (seed) RC_TRY(check_multi_strides(&sd_in, vlen, batch, nrhs, true));
-  RC_TRY(check_multi_strides(&st_in, vlen, batch, nrhs, false));
-  RC_TRY(h->check_data_strides(data->stride, batch));
-  if (batch == 0) return FBSTAB_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  const bool dev_ptrs = (flags & FBSTAB_HIP_DEVICE_POINTERS) != 0;
-  fbstab_dense_batch_t a;
-  fbstab_var_batch_t v;
-  RC_TRY(h->stage_arrays(data->base, data->stride, batch, dev_ptrs, s, a.base, a.stride));
-  RC_TRY(h->stage_vars(x->base, x->stride, 3, batch, dev_ptrs, s, &v));
-  MultiStage sd, st;
-  RC_TRY(sd.open(seed ? &sd_in : nullptr, vlen, batch, nrhs, dev_ptrs, true, s));
-  RC_TRY(st.open(&st_in, vlen, batch, nrhs, dev_ptrs, false, s));
-  DevBuf d_status;
-  int* d_st = status;
-  const bool status_host = SolverBase::out_on_host(flags);
-  if (status_host) {
-    HIP_TRY(hipMalloc(&d_status.p, sizeof(int) * (size_t)batch));
-    d_st = static_cast<int*>(d_status.p);
-  }
-  double sig = sigma_or_default(sigma);
-  double alpha = h->opts.alpha;
-  // the queue word alone, as the dense adjoint: the words from kDenseFallbackSlot on still describe the last solve
-  HIP_TRY(hipMemsetAsync(h->counter, 0, sizeof(int) * kDenseFallbackSlot, s));
-  DenseKernel& e = h->kern.kkt_multi;
-  void* wave_args[] = {&h->wlay, &a, &v, &sd.k, &st.k, &d_st, &nrhs, &wrt, &sig, &alpha, &h->counter, &batch, &h->scratch};
-  void* args[] = {&h->lay, &a, &v, &sd.k, &st.k, &d_st, &nrhs, &wrt, &sig, &alpha, &h->counter, &batch, &h->scratch};
-  RC_TRY(h->begin_timed(s));
-  RC_TRY(launch_entry(e, fbk::dense_grid(batch, h->workgroups), e.wave ? wave_args : args, s));
-  RC_TRY(h->end_timed(s));
-  if (!dev_ptrs) RC_TRY(st.download(&st_in, vlen, batch, nrhs, s));
-  if (status_host) HIP_TRY(hipMemcpyAsync(status, d_st, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
-  if (status_host || !(flags & FBSTAB_HIP_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
-  return FBSTAB_HIP_OK;
+    *n = (int)(wrt == FBSTAB_DENSE_f ? vlen[0] : wrt == FBSTAB_DENSE_h ? vlen[1] : vlen[2]);
+    return (int)FBSTAB_HIP_OK;
+  };
+  auto launch = [&](MultiLaunchArgs<fbstab_dense_batch_t>& k) -> int {
+    double sig = sigma_or_default(sigma);
+    double alpha = h->opts.alpha;
+    // the queue word alone, as the dense adjoint: the words from kDenseFallbackSlot on still describe the last solve
+    HIP_TRY(hipMemsetAsync(h->counter, 0, sizeof(int) * kDenseFallbackSlot, k.s));
+    DenseKernel& e = h->kern.kkt_multi;
+    void* args[] = {e.wave ? (void*)&h->wlay : (void*)&h->lay, &k.a, &k.v, &k.sd, &k.st, &k.d_st, &k.nrhs, &wrt, &sig,
+                    &alpha, &h->counter, &batch, &h->scratch};
+    return launch_timed(h, e, fbk::dense_grid(batch, h->workgroups), args, k.s);
+  };
+  return multi_run(h, batch, data, x, nrhs, seed, step, nullptr, 0, status, flags, stream, sizes, launch);
 }
 }  // namespace
 

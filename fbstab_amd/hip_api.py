@@ -602,6 +602,45 @@ def _tangent(self, batch_struct, dir_struct, names, lens, data, z, l, v, ddata, 
     return res
 
 
+def _multi_call(self, batch_struct, names, lens, fn, data, z, l, v, K, seeds, head, sigma, want, gain_shape, stream,
+                async_):
+    """The many-right-hand-side calls behind ``KktSolve``, ``X0Sensitivity`` and ``Jacobian``: ``fn(handle, B, data, x,
+    *head, sigma, step, [gain, gain_stride,] status, flags, stream)``.  ``seeds``: (gz, gl, gv), which travel with K at
+    the head (fbstab_hip_*_kkt_solve_batch), or None (the seeds are generated in the kernel).  ``gain_shape``: None,
+    or the ``(cols, rows)`` of the column-major per-QP block the call takes behind ``step`` - allocated where ``want``
+    names ``"gain"``, NULL otherwise.  A vector of length 0 - the l slots with nl == 0 - travels as a NULL slot."""
+    dev_flags = []
+    B = z.shape[0]
+    _fill_block(batch_struct, names, lens, data, B, dev_flags)
+    var_lens = (self.nz, self.nl, self.nv)
+    xb = _fill_vars((z, l, v), var_lens, B, dev_flags)
+    live = lambda arrs: tuple(None if n == 0 else a for a, n in zip(arrs, var_lens))
+    if seeds is not None:
+        head = (K, C.byref(_fill_multi(live(seeds), var_lens, B, K, dev_flags, optional=True))) + tuple(head)
+    where, flags, stream = _placement(dev_flags, z, stream, async_)
+    status = where.zeros(z, B, "i4")
+    if where.on_dev:
+        zeros = lambda *shape: where.zeros(z, (B,) + shape)
+    else:
+        zeros = lambda *shape: np.zeros((max(B, 1),) + shape)[:B]   # (an empty batch keeps the strides of a row)
+    res = {k: zeros(K, n) for k, n in zip(("dz", "dl", "dv"), var_lens) if k in want}
+    ob = _fill_multi(live(tuple(res.get(k) for k in ("dz", "dl", "dv"))), var_lens, B, K, [], optional=True,
+                     first_required=False) if res else None
+    gain = gain_shape is not None and "gain" in want
+    extra = ()
+    if gain_shape is not None:
+        if gain:
+            res["gain"] = zeros(*gain_shape)
+        extra = (C.c_void_p(where.ptr(res["gain"])) if gain else None, gain_shape[0] * gain_shape[1])
+    _check(self._lib, fn(self._h, B, C.byref(batch_struct), C.byref(xb), *head, C.c_double(sigma),
+                         C.byref(ob) if ob is not None else None, *extra, C.c_void_p(where.ptr(status)), flags,
+                         C.c_void_p(stream) if stream else None))
+    if gain:
+        res["gain"] = res["gain"].transpose(1, 2) if where.on_dev else res["gain"].transpose(0, 2, 1)
+    res["status"] = status
+    return res
+
+
 def _solve_traced(self, batch_struct, names, lens, arrays, var_lens, z, l, v, y, capacity):
     """fbstab_hip_*_solve_traced for ONE QP in (1, n) numpy arrays.  Returns
     ``(out, records)``; records is ``(n, 8)``: kind, i0, i1, v0..v4
@@ -895,42 +934,6 @@ class FBstabMpcBatch(_SolverBase):
         return _tangent(self, _MpcBatch(), _MpcBatch(), MPC_SEQ, self.seq_len, data, z, l, v, ddata, sigma, rhs,
                         stream, async_)
 
-
-    def _multi_call(self, data, z, l, v, K, seeds, sigma, want, gain, stream, async_):
-        """fbstab_hip_mpc_kkt_solve_batch (``seeds``: (gz, gl, gv)) or fbstab_hip_mpc_x0_sensitivity_batch (None)."""
-        dev_flags = []
-        B = z.shape[0]
-        batch_struct = _MpcBatch()
-        _fill_block(batch_struct, MPC_SEQ, self.seq_len, data, B, dev_flags)
-        var_lens = (self.nz, self.nl, self.nv)
-        xb = _fill_vars((z, l, v), var_lens, B, dev_flags)
-        sb = _fill_multi(seeds, var_lens, B, K, dev_flags, optional=True) if seeds is not None else None
-        where, flags, stream = _placement(dev_flags, z, stream, async_)
-        status = where.zeros(z, B, "i4")
-        if where.on_dev:
-            zeros = lambda *shape: where.zeros(z, (B,) + shape)
-        else:
-            zeros = lambda *shape: np.zeros((max(B, 1),) + shape)[:B]   # (an empty batch keeps the strides of a row)
-        res = {k: zeros(K, n) for k, n in zip(("dz", "dl", "dv"), var_lens) if k in want}
-        ob = _fill_multi(tuple(res.get(k) for k in ("dz", "dl", "dv")), var_lens, B, K, [], optional=True,
-                         first_required=False) if res else None
-        tail = (C.c_void_p(where.ptr(status)), flags, C.c_void_p(stream) if stream else None)
-        if seeds is not None:
-            rc = self._lib.fbstab_hip_mpc_kkt_solve_batch(self._h, B, C.byref(batch_struct), C.byref(xb), K,
-                                                          C.byref(sb), C.c_double(sigma), C.byref(ob), *tail)
-        else:
-            if gain:
-                res["gain"] = zeros(self.nx, self.nu)   # (nu x nx column-major per QP)
-            rc = self._lib.fbstab_hip_mpc_x0_sensitivity_batch(
-                self._h, B, C.byref(batch_struct), C.byref(xb), C.c_double(sigma),
-                C.byref(ob) if ob is not None else None,
-                C.c_void_p(where.ptr(res["gain"])) if gain else None, self.nu * self.nx, *tail)
-        _check(self._lib, rc)
-        if gain:
-            res["gain"] = res["gain"].transpose(1, 2) if where.on_dev else res["gain"].transpose(0, 2, 1)
-        res["status"] = status
-        return res
-
     def KktSolve(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0, stream: int = 0,
                  async_: bool = False) -> Dict[str, object]:
         """Several right-hand sides on ONE factorisation per QP (fbstab_hip_mpc_kkt_solve_batch): ``gz`` of shape
@@ -940,8 +943,8 @@ class FBstabMpcBatch(_SolverBase):
         every right-hand side's step is zero).  All numpy or all torch CUDA tensors, like ``Adjoint``.
         ``sigma <= 0``: 1e-8."""
         assert len(gz.shape) in (2, 3), gz.shape
-        return self._multi_call(data, z, l, v, gz.shape[-2], (gz, gl, gv), sigma, ("dz", "dl", "dv"), False, stream,
-                                async_)
+        return _multi_call(self, _MpcBatch(), MPC_SEQ, self.seq_len, self._lib.fbstab_hip_mpc_kkt_solve_batch, data,
+                           z, l, v, gz.shape[-2], (gz, gl, gv), (), sigma, ("dz", "dl", "dv"), None, stream, async_)
 
     def X0Sensitivity(self, data: Dict[str, object], z, l, v, sigma: float = 0.0,
                       want: Sequence[str] = ("dz", "gain"), stream: int = 0, async_: bool = False) -> Dict[str, object]:
@@ -951,7 +954,8 @@ class FBstabMpcBatch(_SolverBase):
         feedback law, plus ``status``.  All numpy or all torch CUDA tensors, like ``Adjoint``."""
         unknown = set(want) - {"dz", "dl", "dv", "gain"}
         assert not unknown, unknown
-        return self._multi_call(data, z, l, v, self.nx, None, sigma, want, "gain" in want, stream, async_)
+        return _multi_call(self, _MpcBatch(), MPC_SEQ, self.seq_len, self._lib.fbstab_hip_mpc_x0_sensitivity_batch,
+                           data, z, l, v, self.nx, None, (), sigma, want, (self.nx, self.nu), stream, async_)
 
 
 class FBstabDenseBatch(_SolverBase):
@@ -1027,38 +1031,6 @@ class FBstabDenseBatch(_SolverBase):
 
     WRT = {"f": DENSE_ARR.index("f"), "h": DENSE_ARR.index("h"), "b": DENSE_ARR.index("b")}   # FBSTAB_DENSE_f, _h, _b
 
-    def _multi_call(self, data, z, l, v, K, seeds, wrt, sigma, want, stream, async_):
-        """fbstab_hip_dense_kkt_solve_batch (``seeds``: (gz, gl, gv)) or fbstab_hip_dense_jacobian_batch (None, with
-        ``wrt`` the array's index)."""
-        dev_flags = []
-        B = z.shape[0]
-        batch_struct = _DenseBatch()
-        _fill_block(batch_struct, DENSE_ARR, self.arr_len, data, B, dev_flags)
-        var_lens = (self.nz, self.nl, self.nv)
-        xb = _fill_vars((z, l, v), var_lens, B, dev_flags)
-        # (a vector of length 0 - the l slots with nl == 0 - travels as a NULL slot)
-        live = lambda arrs: tuple(None if n == 0 else a for a, n in zip(arrs, var_lens))
-        sb = _fill_multi(live(seeds), var_lens, B, K, dev_flags, optional=True) if seeds is not None else None
-        where, flags, stream = _placement(dev_flags, z, stream, async_)
-        status = where.zeros(z, B, "i4")
-        if where.on_dev:
-            zeros = lambda *shape: where.zeros(z, (B,) + shape)
-        else:
-            zeros = lambda *shape: np.zeros((max(B, 1),) + shape)[:B]   # (an empty batch keeps the strides of a row)
-        res = {k: zeros(K, n) for k, n in zip(("dz", "dl", "dv"), var_lens) if k in want}
-        ob = _fill_multi(live(tuple(res.get(k) for k in ("dz", "dl", "dv"))), var_lens, B, K, [], optional=True,
-                         first_required=False)
-        tail = (C.byref(ob), C.c_void_p(where.ptr(status)), flags, C.c_void_p(stream) if stream else None)
-        if seeds is not None:
-            rc = self._lib.fbstab_hip_dense_kkt_solve_batch(self._h, B, C.byref(batch_struct), C.byref(xb), K,
-                                                            C.byref(sb), C.c_double(sigma), *tail)
-        else:
-            rc = self._lib.fbstab_hip_dense_jacobian_batch(self._h, B, C.byref(batch_struct), C.byref(xb), wrt,
-                                                           C.c_double(sigma), *tail)
-        _check(self._lib, rc)
-        res["status"] = status
-        return res
-
     def KktSolve(self, data: Dict[str, object], z, l, v, gz, gl=None, gv=None, sigma: float = 0.0, stream: int = 0,
                  async_: bool = False) -> Dict[str, object]:
         """Several right-hand sides on ONE factorisation per QP (fbstab_hip_dense_kkt_solve_batch): ``gz`` of shape
@@ -1068,8 +1040,9 @@ class FBstabDenseBatch(_SolverBase):
         every right-hand side's step is zero).  All numpy or all torch CUDA tensors, like ``Adjoint``.
         ``sigma <= 0``: 1e-8.  With ``nl == 0`` ``gl`` is None or ``(batch, K, 0)``."""
         assert len(gz.shape) in (2, 3), gz.shape
-        return self._multi_call(data, z, l, v, gz.shape[-2], (gz, gl, gv), 0, sigma, ("dz", "dl", "dv"), stream,
-                                async_)
+        return _multi_call(self, _DenseBatch(), DENSE_ARR, self.arr_len, self._lib.fbstab_hip_dense_kkt_solve_batch,
+                           data, z, l, v, gz.shape[-2], (gz, gl, gv), (), sigma, ("dz", "dl", "dv"), None, stream,
+                           async_)
 
     def Jacobian(self, data: Dict[str, object], z, l, v, wrt: str = "b", want: Sequence[str] = ("dz",),
                  sigma: float = 0.0, stream: int = 0, async_: bool = False) -> Dict[str, object]:
@@ -1082,7 +1055,8 @@ class FBstabDenseBatch(_SolverBase):
         assert not unknown and len(want) > 0, want
         assert wrt in self.WRT, wrt
         K = {"f": self.nz, "h": self.nl, "b": self.nv}[wrt]
-        return self._multi_call(data, z, l, v, K, None, self.WRT[wrt], sigma, want, stream, async_)
+        return _multi_call(self, _DenseBatch(), DENSE_ARR, self.arr_len, self._lib.fbstab_hip_dense_jacobian_batch,
+                           data, z, l, v, K, None, (self.WRT[wrt],), sigma, want, None, stream, async_)
 
 
 class ShardGroup:

@@ -1,5 +1,5 @@
 """The host staging of the C-ABI (fbstab_amd/csrc/fb_host_stage.h: SolverBase, the stages, the *_run templates, the
-stride rules that take a handle's lengths) on the CPU: the header compiles with the host compiler over a heap-backed
+stride rules that take a handle's lengths; fb_sweep_stage.h: the closed-loop sweeps and their adjoint) on the CPU: the header compiles with the host compiler over a heap-backed
 <hip/hip_runtime.h> (tests/hostsim/runtime_shim), and tests/hostsim/stage_driver.cc runs it with host lambdas in the
 kernels' place - plain, and once more under the address and undefined-behaviour sanitizers, where device memory is
 the heap and a copy that overruns a staging buffer by one double ends the driver.  The driver holds the expected
@@ -15,7 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fbstab_amd", "csrc")
 HOSTSIM = os.path.join(ROOT, "tests", "hostsim")
 
-GROUPS = ("solve", "solve_device_pointers", "adjoint", "tangent", "multi", "probe", "refusals", "leaks")
+GROUPS = ("solve", "solve_device_pointers", "adjoint", "tangent", "multi", "multi_run", "sweep", "sweep_adjoint", "probe",
+          "refusals", "leaks")
 
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
@@ -59,4 +60,9 @@ def test_no_kernel_header_is_in_the_closure_of_the_staging_header():
     assert closure == {"include/fbstab_hip.h", "include/fbstab_types.h", "fbstab_amd/csrc/fb_grad_reduce_plan.h",
                        "fbstab_amd/csrc/fb_launch_plan.h", "fbstab_amd/csrc/fb_in_flight.h"}, closure
     text = open(os.path.join(CSRC, "fb_host_stage.h")).read()
+    assert "__global__" not in text and "hipLaunchKernelGGL" not in text
+    # ... and the sweeps' staging header adds fb_host_stage.h to that closure, and nothing else
+    sweep = {os.path.relpath(p, ROOT) for p in _include_closure(os.path.join(CSRC, "fb_sweep_stage.h"), set())}
+    assert sweep == closure | {"fbstab_amd/csrc/fb_host_stage.h"}, sweep
+    text = open(os.path.join(CSRC, "fb_sweep_stage.h")).read()
     assert "__global__" not in text and "hipLaunchKernelGGL" not in text
