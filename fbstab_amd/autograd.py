@@ -86,6 +86,8 @@ import torch
 
 from .hip_api import DENSE_ARR, MPC_SEQ
 
+_REF_SEQ = ("q", "r", "c", "d")   # (condense.py: the sequences a closed loop may track step by step)
+
 __all__ = ["MpcSolveFunction", "solve_mpc", "DenseSolveFunction", "solve_dense", "ClosedLoopMpcFunction",
            "closed_loop_mpc", "mpc_x0_sensitivity", "dense_jacobian", "CondensedMpcSolveFunction",
            "solve_condensed_mpc"]
@@ -407,12 +409,15 @@ def solve_condensed_mpc(cm, data, sigma: float = 0.0):
 
 
 class ClosedLoopCondensedMpcFunction(torch.autograd.Function):
-    """apply(cm, steps, retire, sigma, A, B, *sequences in MPC_SEQ order, w, shift) -> (u, x, out); ``cm``: a
-    ``condense.CondensedMpc``."""
+    """apply(cm, steps, retire, sigma, A, B, *sequences in MPC_SEQ order, w, shift[, q, r, c, d references]) ->
+    (u, x, out); ``cm``: a ``condense.CondensedMpc``.  A reference is None or ``(steps, batch, len)`` /
+    ``(steps, 1, len)``."""
 
     @staticmethod
     def forward(ctx, cm, steps, retire, sigma, A, B, *rest):
-        seqs, (w, shift) = rest[:len(MPC_SEQ)], rest[len(MPC_SEQ):]
+        seqs, (w, shift), refs = rest[:len(MPC_SEQ)], rest[len(MPC_SEQ):len(MPC_SEQ) + 2], rest[len(MPC_SEQ) + 2:]
+        ctx.nrefs = len(refs)
+        ref = {k: a.detach() for k, a in zip(_REF_SEQ, refs) if a is not None}
         Bn = max(a.shape[0] if a.dim() == 2 else 1 for a in seqs)
         ctx.shared = tuple(k for k, a in zip(MPC_SEQ, seqs) if Bn > 1 and (a.dim() == 1 or a.shape[0] == 1))
         assert "x0" not in ctx.shared, "every trajectory has its own initial state"
@@ -425,29 +430,37 @@ class ClosedLoopCondensedMpcFunction(torch.autograd.Function):
         mk = lambda n: torch.zeros((Bn, n), dtype=torch.float64, device=dev)
         z, l, v, y = mk(cm.nz), mk(cm.nl), mk(cm.nv), mk(cm.nv)
         r = cm.RecedingSweep(run, z, l, v, y, A.detach(), B.detach(), steps, retire=retire,
-                             w=None if w is None else w.detach(), shift=bool(shift), log=("x", "U", "v"))
+                             w=None if w is None else w.detach(), shift=bool(shift), log=("x", "U", "v"),
+                             ref=ref or None)
         u = r["u"]
         x = torch.cat([r["x"][1:], run["x0"][None]], 0)
         ctx.cm, ctx.steps, ctx.retire, ctx.sigma = cm, steps, retire, sigma
+        ctx.ref_names = tuple(ref)
         ctx.save_for_backward(A.detach(), B.detach(), u, r["x"], r["U"], r["v"], r["eflag"],
-                              *[data[k] for k in MPC_SEQ])
+                              *[data[k] for k in MPC_SEQ], *ref.values())
         ctx.mark_non_differentiable(r["out"])
         return u, x, r["out"]
 
     @staticmethod
     def backward(ctx, gu, gx, gout):
         need = ctx.needs_input_grad
-        want = [k for k, n in zip(MPC_SEQ, need[6:6 + len(MPC_SEQ)]) if n]
+        nseq = len(MPC_SEQ)
+        ref_need = dict(zip(_REF_SEQ, need[8 + nseq:]))
+        ref_want = [k for k in ctx.ref_names if ref_need.get(k)]
+        # (the data's own q, r, c, d do not enter where a reference stands in their place: their gradient is None)
+        want = [k for k, n in zip(MPC_SEQ, need[6:6 + nseq]) if n and k not in ctx.ref_names]
         plant = need[4] or need[5]
-        noise = need[6 + len(MPC_SEQ)]
-        if not want and not plant and not noise:
+        noise = need[6 + nseq]
+        if not want and not ref_want and not plant and not noise:
             return (None,) * len(need)
         A, B, u, xl, Ul, vl, el = ctx.saved_tensors[:7]
-        data = dict(zip(MPC_SEQ, ctx.saved_tensors[7:]))
+        data = dict(zip(MPC_SEQ, ctx.saved_tensors[7:7 + nseq]))
+        ref = dict(zip(ctx.ref_names, ctx.saved_tensors[7 + nseq:]))
         log = dict(x=xl, U=Ul, v=vl, eflag=el)
         g = ctx.cm.RecedingSweepAdjoint(data, A, B, ctx.steps, log, gu=gu.contiguous(), gx=gx.contiguous(),
-                                        retire=ctx.retire, sigma=ctx.sigma, want=[k for k in want if k != "x0"],
-                                        mu=plant or noise)
+                                        retire=ctx.retire, sigma=ctx.sigma,
+                                        want=[k for k in want if k != "x0"] + ref_want, mu=plant or noise,
+                                        ref=ref or None)
         gA = gB = mu = None
         if plant or noise:
             # x_(k+1) of a retired trajectory is the constant 0: its costates reach neither the plant nor w_k
@@ -462,16 +475,32 @@ class ClosedLoopCondensedMpcFunction(torch.autograd.Function):
                 grads.append(g[k].sum(0).reshape(ctx.shapes[k]))
             else:
                 grads.append(g[k].reshape(ctx.shapes[k]))
-        return (None, None, None, None, gA, gB) + tuple(grads) + (mu if noise else None, None)
+        rgrads = []
+        for k in _REF_SEQ[:ctx.nrefs]:   # a (steps, 1, len) reference: the torch sum over the batch
+            if k not in ref_want:
+                rgrads.append(None)
+            else:
+                rgrads.append(g[k].sum(1, keepdim=True) if ref[k].shape[1] == 1 and g[k].shape[1] > 1 else g[k])
+        return (None, None, None, None, gA, gB) + tuple(grads) + (mu if noise else None, None) + tuple(rgrads)
 
 
 def closed_loop_condensed_mpc(cm, data, A, B, steps: int, retire: bool = True, sigma: float = 0.0, w=None,
-                              shift: bool = False):
+                              shift: bool = False, ref=None):
     """``closed_loop_mpc`` on the condensed route: ``cm`` a ``condense.CondensedMpc``, the forward pass one
     ``CondensedMpc.RecedingSweep`` (affine mode, logged), the backward pass ONE ``CondensedMpc.RecedingSweepAdjoint``
     call.  ``data``, ``A``/``B``, ``w``, ``shift`` and the returned ``(u, x, out)`` as there (``out``: the dense
     solver's records of the last step).  ``A.grad`` and ``B.grad`` are formed in torch from the costates, the state
     log and ``u``, leaving out the costates of retired steps; ``w.grad`` is the costate of every step, zero once the
-    trajectory is retired; a shared ``(len,)`` / ``(1, len)`` sequence gets the torch sum over the batch."""
+    trajectory is retired; a shared ``(len,)`` / ``(1, len)`` sequence gets the torch sum over the batch.
+    ``ref``: per-step references as ``CondensedMpc.RecedingSweep`` takes them - a dict with any of ``q, r, c, d``,
+    ``(steps, batch, len)`` or ``(steps, 1, len)``.  They are inputs of the function: a reference's ``.grad`` is the
+    per-step array (the torch sum over the batch for a ``(steps, 1, len)`` one, folded back by torch where the
+    reference is an ``as_strided`` sliding window over a longer tensor), and ``data``'s sequence of that name does
+    not enter the loop."""
     seqs = [data[k] for k in MPC_SEQ]
-    return ClosedLoopCondensedMpcFunction.apply(cm, steps, retire, sigma, A, B, *seqs, w, bool(shift))
+    if ref is None:
+        return ClosedLoopCondensedMpcFunction.apply(cm, steps, retire, sigma, A, B, *seqs, w, bool(shift))
+    unknown = set(ref) - set(_REF_SEQ)
+    assert not unknown, unknown
+    return ClosedLoopCondensedMpcFunction.apply(cm, steps, retire, sigma, A, B, *seqs, w, bool(shift),
+                                                *[ref.get(k) for k in _REF_SEQ])

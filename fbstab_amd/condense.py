@@ -9,15 +9,17 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import hip_api
-from .hip_api import (DENSE_ARR, MPC_SEQ, FBstabDenseBatch, _CondensedMap, _CondensedSweepLog, _DenseBatch,
-                      _DenseOutBatch, _MpcBatch, _MpcGradBatch, _Plant, _SweepScenario, _VarBatch, _check,
-                      _fill_block, _is_torch)
+from .hip_api import (DENSE_ARR, MPC_SEQ, FBstabDenseBatch, _CondensedMap, _CondensedRefGrad, _CondensedRefImages,
+                      _CondensedRefs,
+                      _CondensedSweepLog, _DenseBatch, _DenseOutBatch, _MpcBatch, _MpcGradBatch, _Plant,
+                      _SweepScenario, _VarBatch, _check, _fill_block, _is_torch)
 
 MATRICES, VECTORS, ALL = 1, 2, 3
 _WHAT = {"matrices": MATRICES, "vectors": VECTORS, "all": ALL}
 _MATRIX_SEQ = ("Q", "R", "S", "A", "B", "E", "L")
 AFFINE, RECONDENSE = 0, 1
 _SWEEP_MODE = {"affine": AFFINE, "recondense": RECONDENSE}
+_REF_SEQ = ("q", "r", "c", "d")   # the sequences that may move along a sweep, in the order of fbstab_condensed_refs_t
 
 
 def condensed_sizes(N: int, nx: int, nu: int, nc: int) -> Dict[str, int]:
@@ -52,6 +54,17 @@ def condensed_sweep_sizes(N: int, nx: int, nu: int, nc: int, traj_per_group: int
     _check(lib, lib.fbstab_hip_mpc_condensed_sweep_sizes(N, nx, nu, nc, traj_per_group, 1 if shared_map else 0,
                                                          C.byref(used), C.byref(lds), C.byref(work)))
     return dict(traj_per_group=used.value, lds_bytes=lds.value, work_doubles_per_traj=work.value)
+
+
+def condensed_reference_sizes(N: int, nx: int, nu: int, nc: int, steps: int, refs_per_group: int = 0) -> Dict[str, int]:
+    """fbstab_hip_mpc_condensed_reference_sizes: what the images of per-step references use for ``steps`` steps -
+    ``refs_per_group`` (0 asks for the library's rule) and the ``lds_bytes`` of a workgroup; raises where the LDS
+    rule refuses."""
+    lib = hip_api.load_library()
+    used, lds = C.c_int(), C.c_longlong()
+    _check(lib, lib.fbstab_hip_mpc_condensed_reference_sizes(N, nx, nu, nc, steps, refs_per_group, C.byref(used),
+                                                             C.byref(lds)))
+    return dict(refs_per_group=used.value, lds_bytes=lds.value)
 
 
 def condensed_sweep_adjoint_sizes(N: int, nx: int, nu: int, nc: int, traj_per_group: int = 0,
@@ -395,8 +408,70 @@ class CondensedMpc:
             self.N, self.nx, self.nu, self.nc, B, C.byref(blk0), VECTORS, C.byref(out), self.device, sp))
         return dict(M=M, f0=f0, b0=b0)
 
+    # ---- per-step references ---------------------------------------------------------------------------------
+    def _refs(self, ref, steps, B):
+        """``ref``: name -> ``(steps, batch, len)`` or ``(steps, 1, len)`` (one row for the batch) for any of q, r, c,
+        d; any view whose last dimension is contiguous is passed on by its own strides (a sliding window made by
+        ``torch.as_strided`` costs no copy).  -> (the block, the device tensors by name)."""
+        unknown = set(ref) - set(_REF_SEQ)
+        assert not unknown, unknown
+        blk, dev = _CondensedRefs(), {}
+        for i, k in enumerate(_REF_SEQ):
+            if ref.get(k) is None:
+                continue
+            a = self._to_dev(ref[k])
+            n = self.seq_len[MPC_SEQ.index(k)]
+            assert a.dtype == self._torch.float64, a.dtype
+            assert a.dim() == 3 and a.shape[0] == steps and a.shape[1] in (1, B) and a.shape[2] == n, (
+                k, tuple(a.shape), (steps, B, n))
+            assert a.stride(2) == 1 or n <= 1, "the last dimension of a reference is contiguous"
+            blk.base[i], blk.step[i] = a.data_ptr(), a.stride(0)
+            blk.stride[i] = 0 if (a.shape[1] == 1 and B > 1) else a.stride(1)
+            dev[k] = a
+        return blk, dev
+
+    @staticmethod
+    def _data_at_step(d, rdev, k):
+        """``d`` with step ``k`` of the references in the place of q, r, c, d (views: nothing is copied)."""
+        dk = dict(d)
+        for name, a in rdev.items():
+            dk[name] = a[k]
+        return dk
+
+    def _reference_images(self, d, refs_blk, steps, B, refs_per_group=0):
+        t = self._torch
+        f0 = t.empty((steps, B, self.nzc), dtype=t.float64, device=self._dev)
+        b0 = t.empty((steps, B, self.nv), dtype=t.float64, device=self._dev)
+        im = _CondensedRefImages(f0.data_ptr(), b0.data_ptr(), B * self.nzc, B * self.nv, self.nzc, self.nv)
+        blk = self._mpc_block(d, B)
+        s = self._stream()
+        _check(self._lib, self._lib.fbstab_hip_mpc_condensed_reference_images_batch(
+            self.N, self.nx, self.nu, self.nc, B, steps, C.byref(blk), C.byref(refs_blk), C.byref(im), refs_per_group,
+            self.device, C.c_void_p(s) if s else None))
+        return f0, b0, im
+
+    def ReferenceImages(self, data: Dict[str, object], ref: Dict[str, object], refs_per_group: int = 0):
+        """The images of per-step references (fbstab_hip_mpc_condensed_reference_images_batch): with the matrix
+        sequences of ``data`` and, at step k, the q, r, c, d of ``ref`` (name -> ``(steps, batch, len)`` or
+        ``(steps, 1, len)``; names that are absent take ``data``'s sequence at every step), ``f0 (steps, batch, nzc)``
+        and ``b0 (steps, batch, nv)`` such that step k's condensed vectors are f_c = f0[k] + F x, b_c = b0[k] + G x
+        with the [F; G] of ``X0Map`` - bit for bit what ``Condense(data_k with x0 = 0, "vectors")`` gives, in ONE
+        launch for all steps.  ``data["x0"]`` gives the batch size and is not read.  ``refs_per_group``: steps per
+        workgroup, 0 for the library's rule; it changes speed, never results.  Torch tensors on the device, queued on
+        torch's current stream; numpy arrays where every array of ``ref`` is one."""
+        assert ref, "no reference"
+        host = not any(_is_torch(a) for a in ref.values())
+        d = self._data(data)
+        B = d["x0"].shape[0]
+        assert 1 <= B <= self.max_batch, (B, self.max_batch)
+        steps = next(a for a in ref.values() if a is not None).shape[0]
+        blk, _ = self._refs(ref, steps, B)
+        f0, b0, _ = self._reference_images(d, blk, steps, B, refs_per_group)
+        return dict(f0=f0.cpu().numpy(), b0=b0.cpu().numpy()) if host else dict(f0=f0, b0=b0)
+
     def RecedingSweep(self, data: Dict[str, object], z, l, v, y, A, B, steps: int, retire: bool = True, w=None,
-                      shift: bool = False, mode: str = "affine", log: Sequence[str] = (), traj_per_group: int = 0):
+                      shift: bool = False, mode: str = "affine", log: Sequence[str] = (), traj_per_group: int = 0,
+                      ref: Optional[Dict[str, object]] = None):
         """``steps`` warm-started closed-loop steps on this route without a host round trip
         (fbstab_hip_mpc_condensed_receding_sweep): ``data`` is condensed ("all"), in ``mode="affine"`` the map of
         ``X0Map`` is built, and every step is the dense solve plus one small kernel that logs, advances the plant
@@ -413,7 +488,12 @@ class CondensedMpc:
         arguments are uploaded, and numpy arrays come back.  ``traj_per_group``: trajectories per workgroup of the
         step kernel, 0 for the library's rule; it changes speed, never results.
         The images of the LAST step's QP stay in this object: ``Adjoint`` / ``X0Sensitivity`` at the returned point
-        work when ``data["x0"]`` is set to the last row of the ``"x"`` log, the state that step was solved for."""
+        work when ``data["x0"]`` is set to the last row of the ``"x"`` log, the state that step was solved for.
+        ``ref``: per-step references (fbstab_hip_mpc_condensed_tracking_sweep) - a dict with any of ``q, r, c, d``,
+        each ``(steps, batch, len)`` or ``(steps, 1, len)``, passed on by its own strides where the last dimension is
+        contiguous: step k solves the QP with those sequences, ``data`` is condensed with step 0's in place, in
+        ``mode="affine"`` the images of ``ReferenceImages`` are built, and the returned point is expanded with the
+        LAST step's sequences (with ``ref`` and that ``data["x0"]``, use those for ``Adjoint``)."""
         assert mode in _SWEEP_MODE, mode
         unknown = set(log) - {"x", "U", "v"}
         assert not unknown, unknown
@@ -425,7 +505,12 @@ class CondensedMpc:
         assert d["x0"].shape == (Bn, self.nx) and d["x0"].is_contiguous(), "every trajectory has its own x0"
         for a, n in ((zd, self.nz), (ld, self.nl), (vd, self.nv), (yd, self.nv)):
             assert a.shape == (Bn, n) and a.stride(1) == 1, (a.shape, n)
-        self._condense(d, "all")
+        rblk, rimg = None, None
+        if ref is not None and steps > 0:
+            rblk, rdev = self._refs(ref, steps, Bn)
+            self._condense(self._data_at_step(d, rdev, 0), "all")
+        else:
+            self._condense(d, "all")
         img = self._img
         cm = None
         if mode == "affine":
@@ -433,6 +518,8 @@ class CondensedMpc:
             st = lambda a, n: 0 if (a.shape[0] == 1 and Bn > 1) else n
             cm = _CondensedMap(m["M"].data_ptr(), m["f0"].data_ptr(), m["b0"].data_ptr(),
                                st(m["M"], m["M"].shape[1]), self.nzc, self.nv)
+            if rblk is not None:
+                keep_f0, keep_b0, rimg = self._reference_images(d, rblk, steps, Bn)
         dense = _DenseBatch()
         for k in ("H", "f", "A", "b"):
             a, i = img[k], DENSE_ARR.index(k)
@@ -464,11 +551,16 @@ class CondensedMpc:
         blk = self._mpc_block(d, Bn)
         s = self._stream()
         self.generation += 1
-        _check(self._lib, self._lib.fbstab_hip_mpc_condensed_receding_sweep(
-            self.dense._h, self.N, self.nx, self.nu, self.nc, Bn, C.byref(blk), C.byref(dense),
-            C.byref(cm) if cm is not None else None, C.byref(xb), C.c_void_p(out.data_ptr()), C.byref(plant), steps,
-            1 if retire else 0, C.byref(sc), _SWEEP_MODE[mode], C.byref(lg), traj_per_group,
-            C.c_void_p(work.data_ptr()), C.c_void_p(s) if s else None))
+        head = (self.dense._h, self.N, self.nx, self.nu, self.nc, Bn, C.byref(blk), C.byref(dense),
+                C.byref(cm) if cm is not None else None, C.byref(xb), C.c_void_p(out.data_ptr()), C.byref(plant), steps,
+                1 if retire else 0, C.byref(sc), _SWEEP_MODE[mode], C.byref(lg))
+        tail = (traj_per_group, C.c_void_p(work.data_ptr()), C.c_void_p(s) if s else None)
+        if rblk is None:
+            rc = self._lib.fbstab_hip_mpc_condensed_receding_sweep(*head, *tail)
+        else:
+            rc = self._lib.fbstab_hip_mpc_condensed_tracking_sweep(
+                *head, C.byref(rblk), C.byref(rimg) if rimg is not None else None, *tail)
+        _check(self._lib, rc)
         res["out"] = out
         if not host:
             return res
@@ -483,7 +575,8 @@ class CondensedMpc:
     def RecedingSweepAdjoint(self, data: Dict[str, object], A, B, steps: int, log: Dict[str, object], gu=None,
                              gx=None, retire: bool = True, sigma: float = 0.0, want: Sequence[str] = (),
                              mu: bool = False, mode: str = "affine", traj_per_group: int = 0,
-                             gf0: bool = False, gb0: bool = False) -> Dict[str, object]:
+                             gf0: bool = False, gb0: bool = False,
+                             ref: Optional[Dict[str, object]] = None) -> Dict[str, object]:
         """Reverse mode through ``RecedingSweep`` in one call (fbstab_hip_mpc_condensed_receding_sweep_adjoint): the
         seeds ``gu (steps, batch, nu)`` = dL/du_k and ``gx (steps, batch, nx)`` = dL/dx_(k+1) (None: zero) are taken
         backwards along every trajectory of the sweep that ``log`` records - what ``RecedingSweep(..., log=("x", "U",
@@ -498,7 +591,11 @@ class CondensedMpc:
         ``mode="recondense"``: every step's f_c, b_c come from the vectors kernel, as in the forward sweep of that
         mode.  ``retire``: the forward's.  ``traj_per_group``: as in ``RecedingSweep``; it changes speed, never
         results.  Everything is queued on torch's current stream; numpy inputs are uploaded and numpy arrays come
-        back (decided by ``log["U"]``)."""
+        back (decided by ``log["U"]``).
+        ``ref``: the forward's per-step references (fbstab_hip_mpc_condensed_tracking_sweep_adjoint).  A name of
+        ``want`` that is in ``ref`` comes back as the per-step array ``(steps, batch, len)`` - dL/d(sequence of step
+        k), zeros for a step that does not contribute; a ``(steps, 1, len)`` reference gets per-trajectory rows like
+        every shared sequence - and ``gf0`` / ``gb0`` are not available."""
         assert mode in _SWEEP_MODE, mode
         want = tuple(want)
         assert not set(want) - set(MPC_SEQ), set(want) - set(MPC_SEQ)
@@ -519,7 +616,11 @@ class CondensedMpc:
         gxd = None if gx is None else f64(gx)
         assert gud is None or tuple(gud.shape) == (steps, Bn, self.nu), "gu: (steps, batch, nu)"
         assert gxd is None or tuple(gxd.shape) == (steps, Bn, self.nx), "gx: (steps, batch, nx)"
-        self._condense(d, "all")
+        rblk, rimg, rdev = None, None, {}
+        if ref is not None and steps > 0:
+            assert not gf0 and not gb0, "gf0 / gb0 are not available with per-step references"
+            rblk, rdev = self._refs(ref, steps, Bn)
+        self._condense(d, "all")   # (H_c and A_c do not depend on q, r, c, d; f and b are scratch of the call)
         img = self._img
         cm = None
         if mode == "affine":
@@ -527,6 +628,8 @@ class CondensedMpc:
             st = lambda a, n: 0 if (a.shape[0] == 1 and Bn > 1) else n
             cm = _CondensedMap(m["M"].data_ptr(), m["f0"].data_ptr(), m["b0"].data_ptr(),
                                st(m["M"], m["M"].shape[1]), self.nzc, self.nv)
+            if rblk is not None:
+                keep_f0, keep_b0, rimg = self._reference_images(d, rblk, steps, Bn)
         dense = _DenseBatch()
         for k in ("H", "f", "A", "b"):
             a, i = img[k], DENSE_ARR.index(k)
@@ -539,9 +642,15 @@ class CondensedMpc:
                        self.nx * self.nu if Bd.dim() == 3 else 0)
         mk = lambda shape, dtype=t.float64: t.zeros(shape, dtype=dtype, device=self._dev)
         names = tuple(k for k in MPC_SEQ if k in want or k == "x0")
-        res = {k: mk((Bn, n)) for k, n in zip(MPC_SEQ, self.seq_len) if k in names}
+        res = {k: mk((Bn, n)) for k, n in zip(MPC_SEQ, self.seq_len) if k in names and k not in rdev}
         grad = _MpcGradBatch()
         _fill_block(grad, MPC_SEQ, self.seq_len, res, Bn, [], optional=True, shared=False)
+        rgrad = _CondensedRefGrad()
+        for i, k in enumerate(_REF_SEQ):   # (the call writes every entry of a per-step gradient)
+            if k in names and k in rdev:
+                n = self.seq_len[MPC_SEQ.index(k)]
+                res[k] = t.empty((steps, Bn, n), dtype=t.float64, device=self._dev)
+                rgrad.base[i], rgrad.step[i], rgrad.stride[i] = res[k].data_ptr(), Bn * n, n
         if mu:
             res["mu"] = mk((steps, Bn, self.nx))
         if gf0:
@@ -562,12 +671,19 @@ class CondensedMpc:
         blk = self._mpc_block(d, Bn)
         s = self._stream()
         self.generation += 1
-        _check(self._lib, self._lib.fbstab_hip_mpc_condensed_receding_sweep_adjoint(
-            self.dense._h, self.N, self.nx, self.nu, self.nc, Bn, C.byref(blk), C.byref(dense),
-            C.byref(cm) if cm is not None else None, C.byref(plant), steps, 1 if retire else 0, C.byref(lg),
-            ptr(gud), ptr(gxd), C.c_double(sigma), C.byref(grad), ptr(res.get("gf0")), ptr(res.get("gb0")),
-            ptr(res.get("mu")), C.c_void_p(status.data_ptr()), _SWEEP_MODE[mode], traj_per_group,
-            C.c_void_p(work.data_ptr()), C.c_void_p(s) if s else None))
+        head = (self.dense._h, self.N, self.nx, self.nu, self.nc, Bn, C.byref(blk), C.byref(dense),
+                C.byref(cm) if cm is not None else None, C.byref(plant), steps, 1 if retire else 0, C.byref(lg),
+                ptr(gud), ptr(gxd), C.c_double(sigma), C.byref(grad))
+        tail = (traj_per_group, C.c_void_p(work.data_ptr()), C.c_void_p(s) if s else None)
+        if rblk is None:
+            rc = self._lib.fbstab_hip_mpc_condensed_receding_sweep_adjoint(
+                *head, ptr(res.get("gf0")), ptr(res.get("gb0")), ptr(res.get("mu")), C.c_void_p(status.data_ptr()),
+                _SWEEP_MODE[mode], *tail)
+        else:
+            rc = self._lib.fbstab_hip_mpc_condensed_tracking_sweep_adjoint(
+                *head, ptr(res.get("mu")), C.c_void_p(status.data_ptr()), _SWEEP_MODE[mode], C.byref(rblk),
+                C.byref(rimg) if rimg is not None else None, C.byref(rgrad), *tail)
+        _check(self._lib, rc)
         res["status"] = status
         if host:
             res = {k: a.cpu().numpy() for k, a in res.items()}

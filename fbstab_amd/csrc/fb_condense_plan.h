@@ -18,6 +18,7 @@ enum CondenseSweepKernel { kCondenseSweepX0Map = 0, kCondenseSweepStep = 1, kCon
 enum CondenseSweepAdjKernel { kCondenseSweepAdjStep = 0, kCondenseSweepAdjFinish = 1,
                               kCondenseSweepAdjBegin = 2 };                           // fb_condense_sweep_adjoint.hip
 enum CondenseTangentKernel { kCondenseTangentRhs = 0 };                                    // fb_condense_tangent.hip
+enum CondenseRefsKernel { kCondenseRefsImages = 0 };                                          // fb_condense_refs.hip
 
 // ---- fb_condense.h ----------------------------------------------------------------------------------------------
 inline int condense_ld(int rows) { return rows | 1; }
@@ -75,6 +76,21 @@ inline int condense_multi_rule(int nx, int nrhs, long long window, long long per
 // nrhs (N + 1) nc, each one packed [batch][nrhs][n] array.
 struct CondenseMultiWork {
   double *U, *gU, *dU, *rU, *eU, *gv, *dv, *ev;
+};
+
+// ---- fb_condense_refs.h -----------------------------------------------------------------------------------------
+// Doubles of one reference's copy of the carry region (even): what condense_vectors carries - xbar_i of every stage
+// and two p.
+inline long long condense_refs_per(int N, int nx) {
+  auto e = [](long long n) { return n + (n & 1); };
+  return e((long long)(N + 1) * nx) + 2 * e(nx);
+}
+
+// The q, r, c, d of one trajectory at the first reference of a workgroup: reference kk at + kk * step (0: one sequence
+// for every step).
+struct CondenseRefSeqs {
+  const double *q, *r, *c, *d;
+  long long sq, sr, sc, sd;
 };
 
 // ---- fb_condense_sweep.h ----------------------------------------------------------------------------------------

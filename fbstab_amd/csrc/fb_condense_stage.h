@@ -529,6 +529,145 @@ int condensed_multi_run(SolverBase* h, int N, int nx, int nu, int nc, int batch,
   return launch(kCondenseMultiFinish, grid, pl.lds_bytes, args, s);
 }
 
+// ---- per-step references (fb_condense_refs.h) -------------------------------------------------------------------------
+struct CondenseRefsPlan {
+  CondenseLds o;
+  int R;
+  long long per, lds_bytes;
+};
+// What fbstab_hip_mpc_condensed_reference_sizes documents, behind its argument checks: the rule for R is
+// condense_multi_rule's on the references of one trajectory.
+inline int condense_refs_plan(int N, int nx, int nu, int nc, int steps, int refs_per_group, CondenseRefsPlan* p) {
+  p->o.init(N, nx, nu, nc);
+  if (p->o.total == 0x3fffffff || (long long)p->o.carry * 8 > kLdsLimitBytes)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED, "condensed references: the stage images do not fit the 160 KiB LDS budget");
+  p->per = condense_refs_per(N, nx);
+  p->R = refs_per_group > 0 ? (refs_per_group < steps ? refs_per_group : steps)
+                            : condense_multi_rule(nx, steps, p->o.carry, p->per);
+  p->lds_bytes = 8 * ((long long)p->o.carry + p->R * p->per);
+  if (p->lds_bytes > kLdsLimitBytes)
+    return fail(FBSTAB_HIP_ERR_UNSUPPORTED,
+                "condensed references: the stage images and refs_per_group copies of a reference's vectors do not fit the 160 KiB LDS budget");
+  return FBSTAB_HIP_OK;
+}
+
+inline int condensed_reference_sizes(int N, int nx, int nu, int nc, int steps, int refs_per_group,
+                                     int* refs_per_group_used, long long* lds_bytes) {
+  const char* bad = steps < 1 ? "fewer than one step" : refs_per_group < 0 ? "negative refs_per_group" : nullptr;
+  RC_TRY(condense_sizes_prologue("condensed references", N, nx, nu, nc, bad, {refs_per_group_used}, {lds_bytes}));
+  CondenseRefsPlan pl;
+  RC_TRY(condense_refs_plan(N, nx, nu, nc, steps, refs_per_group, &pl));
+  if (refs_per_group_used) *refs_per_group_used = pl.R;
+  if (lds_bytes) *lds_bytes = pl.lds_bytes;
+  return FBSTAB_HIP_OK;
+}
+
+// The slots of fbstab_condensed_refs_t in fbstab_mpc_batch_t.
+constexpr int kCondenseRefSeq[4] = {FBSTAB_MPC_q, FBSTAB_MPC_r, FBSTAB_MPC_c, FBSTAB_MPC_d};
+
+// The references of a caller (null: every sequence is `data`'s at every step): no negative step or stride, with
+// batch > 1 every trajectory its own rows (stride >= length) or one for all (0).  *rr: the block without a null slot -
+// where the caller gave no sequence, `data`'s with step 0 - and, with batch == 1, without the caller's strides.
+inline int condense_check_refs(const char* who, const CondenseShape& sh, int batch, const fbstab_mpc_batch_t* data,
+                               const fbstab_condensed_refs_t* refs, fbstab_condensed_refs_t* rr) {
+  *rr = fbstab_condensed_refs_t{};
+  for (int i = 0; i < 4; i++) {
+    const int seq = kCondenseRefSeq[i];
+    if (!refs || !refs->base[i]) {
+      rr->base[i] = data->base[seq];
+      rr->stride[i] = batch > 1 ? data->stride[seq] : 0;
+      continue;
+    }
+    if (refs->step[i] < 0) return condense_bad(who, "negative step in the references");
+    if (refs->stride[i] < 0) return condense_bad(who, "negative stride in the references");
+    if (batch > 1 && refs->stride[i] != 0 && refs->stride[i] < sh.len[seq])
+      return condense_bad(who, "trajectory stride of a reference is neither 0 nor at least the sequence length");
+    rr->base[i] = refs->base[i];
+    rr->step[i] = refs->step[i];
+    rr->stride[i] = batch > 1 ? refs->stride[i] : 0;
+  }
+  return FBSTAB_HIP_OK;
+}
+
+// `data` with the sequences of step k of the (checked) references in the place of q, r, c, d.
+inline fbstab_mpc_batch_t condense_data_at_step(fbstab_mpc_batch_t a, const fbstab_condensed_refs_t& rr, long long k) {
+  for (int i = 0; i < 4; i++) {
+    a.base[kCondenseRefSeq[i]] = rr.base[i] + k * rr.step[i];
+    a.stride[kCondenseRefSeq[i]] = rr.stride[i];
+  }
+  return a;
+}
+
+// The images f0_k, b0_k of a caller that a sweep READS (writing: condensed_reference_images_run's own check).
+inline int condense_check_ref_images(const char* who, const CondenseShape& sh, int batch,
+                                     const fbstab_condensed_ref_images_t* images) {
+  if (!images) return condense_bad(who, "AFFINE mode with references needs their images");
+  if (!images->f0 || !images->b0) return condense_bad(who, "null pointer in the reference images");
+  if (images->step_f0 < 0 || images->step_b0 < 0) return condense_bad(who, "negative step in the reference images");
+  if (batch > 1 && ((images->stride_f0 != 0 && images->stride_f0 < sh.nz) ||
+                    (images->stride_b0 != 0 && images->stride_b0 < sh.nv)))
+    return condense_bad(who, "trajectory stride of the reference images is neither 0 nor at least the length");
+  return FBSTAB_HIP_OK;
+}
+
+// What both tracking calls check behind the map, in front of the handle: the map (with references in AFFINE mode M
+// alone is looked at: f0 and b0 are the references' images), the references, their images.
+inline int condense_check_tracking(const char* who, bool affine, const fbstab_condensed_map_t* map,
+                                   const CondenseShape& sh, int batch, const fbstab_mpc_batch_t* data,
+                                   const fbstab_condensed_refs_t* refs, const fbstab_condensed_ref_images_t* images,
+                                   fbstab_condensed_refs_t* rr) {
+  *rr = fbstab_condensed_refs_t{};
+  if (!refs) return condense_check_map(who, affine, map, sh, batch);
+  if (affine) {
+    if (!map || !map->M) return condense_bad(who, "AFFINE mode needs the map");
+    if (batch > 1 && map->stride_M != 0 && map->stride_M < (sh.nz + sh.nv) * sh.nx)
+      return condense_bad(who, "stride of the map smaller than the array length");
+  }
+  RC_TRY(condense_check_refs(who, sh, batch, data, refs, rr));
+  if (affine) RC_TRY(condense_check_ref_images(who, sh, batch, images));
+  return FBSTAB_HIP_OK;
+}
+
+// fbstab_hip_mpc_condensed_reference_images_batch: one launch on the grid batch x ceil(steps / R).
+template <class Launch>
+int condensed_reference_images_run(int N, int nx, int nu, int nc, int batch, int steps, const fbstab_mpc_batch_t* data,
+                                   const fbstab_condensed_refs_t* refs, const fbstab_condensed_ref_images_t* images,
+                                   int refs_per_group, int device, void* stream, Launch launch) {
+  CondenseShape sh;
+  RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
+  if (steps < 0) return condense_bad("condensed references", "negative step count");
+  if (refs_per_group < 0) return condense_bad("condensed references", "negative refs_per_group");
+  fbstab_condensed_refs_t rr;
+  RC_TRY(condense_check_refs("condensed references", sh, batch, data, refs, &rr));
+  if (!images || !images->f0 || !images->b0) return condense_bad("condensed references", "null output pointer");
+  // every (step, trajectory) writes rows of its own
+  if (steps > 1 && (images->step_f0 < sh.nz || images->step_b0 < sh.nv))
+    return condense_bad("condensed references", "output step smaller than the image");
+  if (batch > 1 && (images->stride_f0 < sh.nz || images->stride_b0 < sh.nv))
+    return condense_bad("condensed references", "output stride smaller than the image");
+  if (batch == 0 || steps == 0) return FBSTAB_HIP_OK;
+  // ... the device, then the LDS rule
+  RC_TRY(condense_device_exists("condensed references", device));
+  CondenseRefsPlan pl;
+  RC_TRY(condense_refs_plan(N, nx, nu, nc, steps, refs_per_group, &pl));
+  const long long groups = (steps + pl.R - 1) / pl.R;
+  if (groups * batch > 0x7fffffffLL)
+    return condense_bad("condensed references", "batch x groups of steps exceeds the grid limit");
+  HIP_TRY(hipSetDevice(device));
+  // the blocks as the kernel takes them: with batch == 1 or steps == 1 the caller's strides and steps are not read
+  fbstab_mpc_batch_t a = *data;
+  fbstab_condensed_ref_images_t im = *images;
+  if (batch == 1) im.stride_f0 = im.stride_b0 = 0;
+  if (steps == 1) {
+    im.step_f0 = im.step_b0 = 0;
+    for (int i = 0; i < 4; i++) rr.step[i] = 0;
+  }
+  int R = pl.R;
+  long long per = pl.per;
+  void* args[] = {&N, &nx, &nu, &nc, &pl.o, &steps, &R, &per, &a, &rr, &im};
+  return launch(kCondenseRefsImages, (int)(groups * batch), pl.lds_bytes, args, (hipStream_t)stream);
+}
+
 // ---- the condensed route in closed loop (fb_condense_sweep.h) ---------------------------------------------------------
 // What fbstab_hip_mpc_condensed_sweep_sizes documents, behind its argument checks.
 inline int condense_sweep_plan(int N, int nx, int nu, int nc, int traj_per_group, bool stage_m, CondenseSweepLds* L) {
@@ -582,13 +721,18 @@ int condensed_x0_map_run(int N, int nx, int nu, int nc, int batch, const fbstab_
   return launch(kCondenseSweepX0Map, (ms == 0 ? 1 : batch) * blocks, lds, args, (hipStream_t)stream);
 }
 
+// Both sweeps: fbstab_hip_mpc_condensed_receding_sweep (refs == nullptr: `images` is not looked at) and
+// fbstab_hip_mpc_condensed_tracking_sweep, where step k is the QP of the references' step k - per-step pointers into
+// the references and their images, the launches and their order are the same.
 template <class Launch, class DenseSolve>
-int condensed_sweep_run(SolverBase* h, int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
-                        const fbstab_dense_batch_t* dense, const fbstab_condensed_map_t* map,
-                        const fbstab_var_batch_t* x, fbstab_solver_out_t* out, const fbstab_receding_plant_t* plant,
-                        int steps, int retire, const fbstab_sweep_scenario_t* scenario, int mode,
-                        const fbstab_condensed_sweep_log_t* log, int traj_per_group, double* work, void* stream,
-                        Launch launch, DenseSolve dense_solve) {
+int condensed_tracking_sweep_run(SolverBase* h, int N, int nx, int nu, int nc, int batch,
+                                 const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                 const fbstab_condensed_map_t* map, const fbstab_var_batch_t* x,
+                                 fbstab_solver_out_t* out, const fbstab_receding_plant_t* plant, int steps, int retire,
+                                 const fbstab_sweep_scenario_t* scenario, int mode,
+                                 const fbstab_condensed_sweep_log_t* log, const fbstab_condensed_refs_t* refs,
+                                 const fbstab_condensed_ref_images_t* images, int traj_per_group, double* work,
+                                 void* stream, Launch launch, DenseSolve dense_solve) {
   // what needs no handle comes first, in the order of fbstab_hip_mpc_condense_batch
   CondenseShape sh;
   RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
@@ -612,7 +756,9 @@ int condensed_sweep_run(SolverBase* h, int N, int nx, int nu, int nc, int batch,
   }
   RC_TRY(condense_check_plant("condensed sweep", plant, nx, nu, batch));
   const bool affine = mode == FBSTAB_CONDENSED_SWEEP_AFFINE;
-  RC_TRY(condense_check_map("condensed sweep", affine, map, sh, batch));
+  // ... the map and the references, in front of the handle
+  fbstab_condensed_refs_t rr;
+  RC_TRY(condense_check_tracking("condensed sweep", affine, map, sh, batch, data, refs, images, &rr));
   // ... then the handle
   RC_TRY(condense_check_handle("condensed sweep", h, sh, batch));
   if (batch == 0 || steps == 0) return FBSTAB_HIP_OK;
@@ -653,8 +799,13 @@ int condensed_sweep_run(SolverBase* h, int N, int nx, int nu, int nc, int batch,
   st.sAp = one ? 0 : plant->stride_A; st.sBp = one ? 0 : plant->stride_B;
   if (affine) {
     st.M = map->M; st.sM = one ? 0 : map->stride_M;
-    st.f0 = map->f0; st.sf0 = one ? 0 : map->stride_f0;
-    st.b0 = map->b0; st.sb0 = one ? 0 : map->stride_b0;
+    if (refs) {
+      st.sf0 = one ? 0 : images->stride_f0;
+      st.sb0 = one ? 0 : images->stride_b0;
+    } else {
+      st.f0 = map->f0; st.sf0 = one ? 0 : map->stride_f0;
+      st.b0 = map->b0; st.sb0 = one ? 0 : map->stride_b0;
+    }
   }
   st.f = dvec.base[FBSTAB_DENSE_f]; st.sf = dvec.stride[FBSTAB_DENSE_f];
   st.b = dvec.base[FBSTAB_DENSE_b]; st.sb = dvec.stride[FBSTAB_DENSE_b];
@@ -675,30 +826,54 @@ int condensed_sweep_run(SolverBase* h, int N, int nx, int nu, int nc, int batch,
     st.v_log = log && log->v ? log->v + kb * sh.nv : nullptr;
     st.eflag_log = log && log->eflag ? log->eflag + kb : nullptr;
     st.newton_log = log && log->newton ? log->newton + kb : nullptr;
+    if (refs && affine && !last) {  // the vectors of step k + 1 from the images of step k + 1
+      st.f0 = images->f0 + (k + 1) * images->step_f0;
+      st.b0 = images->b0 + (k + 1) * images->step_b0;
+    }
     void* sargs[] = {&st, &L};
     RC_TRY(launch(kCondenseSweepStep, groups, L.total * 8, sargs, s));
     if (!affine && !last) {
-      void* vargs[] = {&N, &nx, &nu, &nc, &o, &a, &dvec};
+      fbstab_mpc_batch_t an = refs ? condense_data_at_step(a, rr, k + 1) : a;
+      void* vargs[] = {&N, &nx, &nu, &nc, &o, &an, &dvec};
       RC_TRY(launch(kCondenseVectors, batch, lds, vargs, s));
     }
   }
   // the point of the last step, at the state it was solved for
-  fbstab_mpc_batch_t al = a;
+  fbstab_mpc_batch_t al = refs ? condense_data_at_step(a, rr, steps - 1) : a;
   al.base[FBSTAB_MPC_x0] = wk.xkeep;
   al.stride[FBSTAB_MPC_x0] = nx;
   void* eargs[] = {&N, &nx, &nu, &nc, &o, &al, &xc, &xv};
   return launch(kCondenseExpand, batch, lds, eargs, s);
 }
 
+template <class Launch, class DenseSolve>
+int condensed_sweep_run(SolverBase* h, int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+                        const fbstab_dense_batch_t* dense, const fbstab_condensed_map_t* map,
+                        const fbstab_var_batch_t* x, fbstab_solver_out_t* out, const fbstab_receding_plant_t* plant,
+                        int steps, int retire, const fbstab_sweep_scenario_t* scenario, int mode,
+                        const fbstab_condensed_sweep_log_t* log, int traj_per_group, double* work, void* stream,
+                        Launch launch, DenseSolve dense_solve) {
+  return condensed_tracking_sweep_run(h, N, nx, nu, nc, batch, data, dense, map, x, out, plant, steps, retire, scenario,
+                                      mode, log, nullptr, nullptr, traj_per_group, work, stream, launch, dense_solve);
+}
+
 // ---- reverse mode through that sweep (fb_condense_sweep_adjoint.h) --------------------------------------------------
+// Both adjoints: fbstab_hip_mpc_condensed_receding_sweep_adjoint (refs == nullptr: `images` and `ref_grad` are not
+// looked at) and fbstab_hip_mpc_condensed_tracking_sweep_adjoint (gf0 == gb0 == nullptr), where every launch of step k
+// is handed the pointers of step k: the images f0[k], b0[k] or the VECTORS launch's q, r, c, d, the finish kernel's data
+// block, and for a sequence that moves its gradient's rows of step k (zeroed by one begin launch per step in front of
+// the recursion, so that a step the finish kernel leaves alone holds zeros).
 template <class Launch, class DenseAdjoint>
-int condensed_sweep_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
-                                const fbstab_dense_batch_t* dense, const fbstab_condensed_map_t* map,
-                                const fbstab_receding_plant_t* plant, int steps,
-                                const fbstab_condensed_sweep_log_t* log, const double* gu, const double* gx,
-                                double sigma, const fbstab_mpc_grad_batch_t* grad, double* gf0, double* gb0,
-                                double* mu_log, int* status, int mode, int traj_per_group, double* work, void* stream,
-                                Launch launch, DenseAdjoint dense_adjoint) {
+int condensed_tracking_sweep_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, int batch,
+                                         const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                         const fbstab_condensed_map_t* map, const fbstab_receding_plant_t* plant,
+                                         int steps, const fbstab_condensed_sweep_log_t* log, const double* gu,
+                                         const double* gx, double sigma, const fbstab_mpc_grad_batch_t* grad,
+                                         double* gf0, double* gb0, double* mu_log, int* status, int mode,
+                                         const fbstab_condensed_refs_t* refs,
+                                         const fbstab_condensed_ref_images_t* images,
+                                         const fbstab_condensed_ref_grad_t* ref_grad, int traj_per_group, double* work,
+                                         void* stream, Launch launch, DenseAdjoint dense_adjoint) {
   // what needs no handle comes first, in the order of fbstab_hip_mpc_condensed_receding_sweep
   CondenseShape sh;
   RC_TRY(condense_check(N, nx, nu, nc, batch, data, &sh));
@@ -722,7 +897,26 @@ int condensed_sweep_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, in
     if (i != FBSTAB_MPC_x0) data_grads = true;
   }
   const bool affine = mode == FBSTAB_CONDENSED_SWEEP_AFFINE;
-  RC_TRY(condense_check_map("condensed sweep adjoint", affine, map, sh, batch));
+  // ... the map and the references, in front of the handle
+  fbstab_condensed_refs_t rr;
+  RC_TRY(condense_check_tracking("condensed sweep adjoint", affine, map, sh, batch, data, refs, images, &rr));
+  fbstab_condensed_ref_grad_t rg = {};
+  if (refs)
+    for (int i = 0; i < 4; i++) {
+      const int seq = kCondenseRefSeq[i];
+      const bool moves = refs->base[i] != nullptr;
+      if (moves && grad->base[seq])
+        return condense_bad("condensed sweep adjoint", "the summed gradient slot of a sequence that moves (its gradient is per step: ref_grad)");
+      if (!ref_grad || !ref_grad->base[i]) continue;
+      if (!moves)
+        return condense_bad("condensed sweep adjoint", "per-step gradient of a sequence that does not move (its gradient is the summed slot of grad)");
+      if ((steps > 1 && ref_grad->step[i] < sh.len[seq]) || (batch > 1 && ref_grad->stride[i] < sh.len[seq]))
+        return condense_bad("condensed sweep adjoint", "every step and trajectory needs its own rows of a per-step gradient (step, stride >= length)");
+      rg.base[i] = ref_grad->base[i];
+      rg.step[i] = steps > 1 ? ref_grad->step[i] : 0;
+      rg.stride[i] = batch > 1 ? ref_grad->stride[i] : sh.len[seq];
+      data_grads = true;
+    }
   // ... then the handle
   RC_TRY(condense_check_handle("condensed sweep adjoint", h, sh, batch));
   if (batch == 0) return FBSTAB_HIP_OK;
@@ -742,6 +936,24 @@ int condensed_sweep_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, in
     for (int i = 0; i < FBSTAB_MPC_NSEQ; i++) g.stride[i] = sh.len[i];
   {
     void* args[] = {&N, &nx, &nu, &nc, &g, &wk.gz, &gf0, &gb0, &status};
+    RC_TRY(launch(kCondenseSweepAdjBegin, batch, 0, args, s));
+  }
+  // the rows of step k of the per-step gradients, as a gradient block (null where none is wanted)
+  const auto ref_rows = [&rg](fbstab_mpc_grad_batch_t* to, long long k) {
+    bool any = false;
+    for (int i = 0; i < 4; i++) {
+      if (!rg.base[i]) continue;
+      to->base[kCondenseRefSeq[i]] = rg.base[i] + k * rg.step[i];
+      to->stride[kCondenseRefSeq[i]] = rg.stride[i];
+      any = true;
+    }
+    return any;
+  };
+  for (int k = 0; k < steps; k++) {  // (status is zeroed once more: nothing has counted yet)
+    fbstab_mpc_grad_batch_t gk = {};
+    if (!ref_rows(&gk, k)) break;
+    double* none = nullptr;
+    void* args[] = {&N, &nx, &nu, &nc, &gk, &none, &none, &none, &status};
     RC_TRY(launch(kCondenseSweepAdjBegin, batch, 0, args, s));
   }
   if (steps == 0) return FBSTAB_HIP_OK;
@@ -764,8 +976,13 @@ int condensed_sweep_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, in
   st.gU = wk.wk.gU;
   if (affine) {
     st.M = map->M; st.sM = one ? 0 : map->stride_M;
-    st.f0 = map->f0; st.sf0 = one ? 0 : map->stride_f0;
-    st.b0 = map->b0; st.sb0 = one ? 0 : map->stride_b0;
+    if (refs) {
+      st.sf0 = one ? 0 : images->stride_f0;
+      st.sb0 = one ? 0 : images->stride_b0;
+    } else {
+      st.f0 = map->f0; st.sf0 = one ? 0 : map->stride_f0;
+      st.b0 = map->b0; st.sb0 = one ? 0 : map->stride_b0;
+    }
   }
   st.f = dvec.base[FBSTAB_DENSE_f]; st.sf = dvec.stride[FBSTAB_DENSE_f];
   st.b = dvec.base[FBSTAB_DENSE_b]; st.sb = dvec.stride[FBSTAB_DENSE_b];
@@ -787,9 +1004,21 @@ int condensed_sweep_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, in
     st.gx = st.open && gx ? gx + kb * nx : nullptr;
     st.mu_log = st.open && mu_log ? mu_log + kb * nx : nullptr;
     st.x_log = st.open ? log->x + kb * nx : nullptr;
+    if (refs && affine && st.open) {  // opening step k: the images of step k
+      st.f0 = images->f0 + k * images->step_f0;
+      st.b0 = images->b0 + k * images->step_b0;
+    }
     void* sargs[] = {&st, &L};
     RC_TRY(launch(kCondenseSweepAdjStep, groups, L.total * 8, sargs, s));
     if (k < 0) break;
+    if (refs) {  // step k's sequences, for the VECTORS launch and the finish kernel
+      const fbstab_mpc_batch_t ak = condense_data_at_step(a, rr, k);
+      for (int i = 0; i < 4; i++) {
+        a.base[kCondenseRefSeq[i]] = ak.base[kCondenseRefSeq[i]];
+        a.stride[kCondenseRefSeq[i]] = ak.stride[kCondenseRefSeq[i]];
+      }
+      ref_rows(&gfin, k);
+    }
     if (!affine) {
       a.base[FBSTAB_MPC_x0] = log->x + kb * nx;
       void* vargs[] = {&N, &nx, &nu, &nc, &o, &a, &dvec};
@@ -810,6 +1039,19 @@ int condensed_sweep_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, in
     }
   }
   return FBSTAB_HIP_OK;
+}
+
+template <class Launch, class DenseAdjoint>
+int condensed_sweep_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+                                const fbstab_dense_batch_t* dense, const fbstab_condensed_map_t* map,
+                                const fbstab_receding_plant_t* plant, int steps,
+                                const fbstab_condensed_sweep_log_t* log, const double* gu, const double* gx,
+                                double sigma, const fbstab_mpc_grad_batch_t* grad, double* gf0, double* gb0,
+                                double* mu_log, int* status, int mode, int traj_per_group, double* work, void* stream,
+                                Launch launch, DenseAdjoint dense_adjoint) {
+  return condensed_tracking_sweep_adjoint_run(h, N, nx, nu, nc, batch, data, dense, map, plant, steps, log, gu, gx,
+                                              sigma, grad, gf0, gb0, mu_log, status, mode, nullptr, nullptr, nullptr,
+                                              traj_per_group, work, stream, launch, dense_adjoint);
 }
 
 }  // namespace

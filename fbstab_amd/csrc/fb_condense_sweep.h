@@ -20,7 +20,8 @@
 // condense_stage in the CondenseLds layout, one thread owns each output entry and sums it in ascending index order
 // with plain FMAs.  No atomics, no sums across threads, no matrix cores.
 //
-// Not here: per-step references (q, r, c, d that move), sharded sweeps, the C++ facade.  (The derivative through the
+// Not here: sharded sweeps, the C++ facade.  (Per-step references - q, r, c, d that move - need no code here: the
+// host stage hands each launch of condense_sweep_step the f0, b0 of its step, fb_condense_refs.h.  The derivative through the
 // sweep: fb_condense_sweep_adjoint.h.)
 #pragma once
 

@@ -573,7 +573,8 @@ __attribute__((visibility("hidden"))) const void* fbstab_kkt_multi_kernel(int wg
 // own): the kernel beside adjoint kernel `which` of dense_resolve_kernels
 __attribute__((visibility("hidden"))) const void* fbstab_dense_kkt_multi_kernel_for(int which);
 // The kernels of the condensed route (fb_condense.hip, fb_condense_adjoint.hip, fb_condense_multi.hip,
-// fb_condense_sweep.hip, fb_condense_sweep_adjoint.hip, fb_condense_tangent.hip, a translation unit each): the kernel
+// fb_condense_sweep.hip, fb_condense_sweep_adjoint.hip, fb_condense_tangent.hip, fb_condense_refs.hip, a translation
+// unit each): the kernel
 // that the unit's enum of fb_condense_plan.h names; *threads: its workgroup size
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseAdjointKernel which, int* threads);
@@ -581,6 +582,7 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::Co
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepAdjKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseTangentKernel which, int* threads);
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseRefsKernel which, int* threads);
 #if defined(FB_SINGLE_TU)
 // (diagnostic builds with device-side counters: one translation unit, one g_stamps)
 #include "rec_12_4_20.hip"
@@ -596,10 +598,11 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::Co
 #include "fb_condense_sweep.hip"
 #include "fb_condense_sweep_adjoint.hip"
 #include "fb_condense_tangent.hip"
+#include "fb_condense_refs.hip"
 #endif
 
 // The condensed route (include/fbstab_hip.h): its host side is fb_condense_stage.h, tested on the CPU
-// (tests/test_condense_stage.py); here, what that header is handed: the kernels of the five units, and the dense
+// (tests/test_condense_stage.py); here, what that header is handed: the kernels of the route's units, and the dense
 // handle's own entry points on device pointers, asynchronous.
 #include "fb_condense_stage.h"
 
@@ -1363,6 +1366,37 @@ int fbstab_hip_mpc_condensed_receding_sweep(fbstab_dense_handle_t h, int N, int 
                              traj_per_group, work, stream, condense_gpu, dense_solve);
 }
 
+int fbstab_hip_mpc_condensed_reference_sizes(int N, int nx, int nu, int nc, int steps, int refs_per_group,
+                                             int* refs_per_group_used, long long* lds_bytes) {
+  return condensed_reference_sizes(N, nx, nu, nc, steps, refs_per_group, refs_per_group_used, lds_bytes);
+}
+
+int fbstab_hip_mpc_condensed_reference_images_batch(int N, int nx, int nu, int nc, int batch, int steps,
+                                                    const fbstab_mpc_batch_t* data,
+                                                    const fbstab_condensed_refs_t* refs,
+                                                    const fbstab_condensed_ref_images_t* images, int refs_per_group,
+                                                    int device, void* stream) {
+  return condensed_reference_images_run(N, nx, nu, nc, batch, steps, data, refs, images, refs_per_group, device, stream,
+                                        condense_gpu);
+}
+
+int fbstab_hip_mpc_condensed_tracking_sweep(fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch,
+                                            const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                            const fbstab_condensed_map_t* map, const fbstab_var_batch_t* x,
+                                            fbstab_solver_out_t* out, const fbstab_receding_plant_t* plant, int steps,
+                                            int retire, const fbstab_sweep_scenario_t* scenario, int mode,
+                                            const fbstab_condensed_sweep_log_t* log,
+                                            const fbstab_condensed_refs_t* refs,
+                                            const fbstab_condensed_ref_images_t* images, int traj_per_group,
+                                            double* work, void* stream) {
+  const auto dense_solve = [h](int b, const fbstab_dense_batch_t* dc, const fbstab_var_batch_t* xc,
+                               fbstab_solver_out_t* o, hipStream_t s) {
+    return fbstab_hip_dense_solve_batch(h, b, dc, xc, o, kCondenseDenseFlags, (void*)s);
+  };
+  return condensed_tracking_sweep_run(h, N, nx, nu, nc, batch, data, dense, map, x, out, plant, steps, retire, scenario,
+                                      mode, log, refs, images, traj_per_group, work, stream, condense_gpu, dense_solve);
+}
+
 int fbstab_hip_mpc_condensed_sweep_adjoint_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
                                                  int* traj_per_group_used, long long* lds_bytes,
                                                  long long* work_doubles_per_traj,
@@ -1381,6 +1415,20 @@ int fbstab_hip_mpc_condensed_receding_sweep_adjoint(
   return condensed_sweep_adjoint_run(h, N, nx, nu, nc, batch, data, dense, map, plant, steps, log, gu, gx, sigma, grad,
                                      gf0, gb0, mu_log, status, mode, traj_per_group, work, stream, condense_gpu,
                                      condense_dense_adjoint(h));
+}
+
+int fbstab_hip_mpc_condensed_tracking_sweep_adjoint(
+    fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+    const fbstab_dense_batch_t* dense, const fbstab_condensed_map_t* map, const fbstab_receding_plant_t* plant,
+    int steps, int retire, const fbstab_condensed_sweep_log_t* log, const double* gu, const double* gx, double sigma,
+    const fbstab_mpc_grad_batch_t* grad, double* mu_log, int* status, int mode, const fbstab_condensed_refs_t* refs,
+    const fbstab_condensed_ref_images_t* images, const fbstab_condensed_ref_grad_t* ref_grad, int traj_per_group,
+    double* work, void* stream) {
+  (void)retire;  // (the logged eflag of -1 carries it)
+  return condensed_tracking_sweep_adjoint_run(h, N, nx, nu, nc, batch, data, dense, map, plant, steps, log, gu, gx,
+                                              sigma, grad, nullptr, nullptr, mu_log, status, mode, refs, images,
+                                              ref_grad, traj_per_group, work, stream, condense_gpu,
+                                              condense_dense_adjoint(h));
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;

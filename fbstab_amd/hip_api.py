@@ -119,6 +119,22 @@ class _CondensedSweepLog(C.Structure):
                 ("newton", C.c_void_p)]
 
 
+class _CondensedRefs(C.Structure):
+    """fbstab_condensed_refs_t: per-step q, r, c, d - base, doubles between steps, doubles between trajectories."""
+    _fields_ = [("base", C.c_void_p * 4), ("step", C.c_longlong * 4), ("stride", C.c_longlong * 4)]
+
+
+class _CondensedRefGrad(C.Structure):
+    """fbstab_condensed_ref_grad_t: where the per-step gradients of q, r, c, d go."""
+    _fields_ = [("base", C.c_void_p * 4), ("step", C.c_longlong * 4), ("stride", C.c_longlong * 4)]
+
+
+class _CondensedRefImages(C.Structure):
+    """fbstab_condensed_ref_images_t: f0_k, b0_k and their steps and strides."""
+    _fields_ = [("f0", C.c_void_p), ("b0", C.c_void_p), ("step_f0", C.c_longlong), ("step_b0", C.c_longlong),
+                ("stride_f0", C.c_longlong), ("stride_b0", C.c_longlong)]
+
+
 class _SweepScenario(C.Structure):
     """fbstab_sweep_scenario_t: the disturbances (device pointer or NULL) and the shift flag."""
     _fields_ = [("w", C.c_void_p), ("shift", C.c_int)]
@@ -253,6 +269,15 @@ def load_library() -> C.CDLL:
         lib.fbstab_hip_mpc_condensed_receding_sweep_adjoint.argtypes = [C.c_void_p] + [C.c_int] * 5 + [
             C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 5 + [
             C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_condensed_tracking_sweep"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_condensed_reference_sizes.argtypes = [C.c_int] * 6 + [C.c_void_p] * 2
+        lib.fbstab_hip_mpc_condensed_reference_images_batch.argtypes = [C.c_int] * 6 + [C.c_void_p] * 3 + [
+            C.c_int, C.c_int, C.c_void_p]
+        lib.fbstab_hip_mpc_condensed_tracking_sweep.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6 + [
+            C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.fbstab_hip_mpc_condensed_tracking_sweep_adjoint.argtypes = [C.c_void_p] + [C.c_int] * 5 + [
+            C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 3 + [
+            C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_queue_order"):  # (absent from an earlier build loaded for an A/B)
@@ -306,6 +331,8 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_condensed_sweep_sizes", "fbstab_hip_mpc_condensed_x0_map_batch",
     "fbstab_hip_mpc_condensed_receding_sweep",
     "fbstab_hip_mpc_condensed_sweep_adjoint_sizes", "fbstab_hip_mpc_condensed_receding_sweep_adjoint",
+    "fbstab_hip_mpc_condensed_reference_sizes", "fbstab_hip_mpc_condensed_reference_images_batch",
+    "fbstab_hip_mpc_condensed_tracking_sweep", "fbstab_hip_mpc_condensed_tracking_sweep_adjoint",
     "fbstab_hip_dense_kkt_solve_batch", "fbstab_hip_dense_jacobian_batch",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",

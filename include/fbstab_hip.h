@@ -849,8 +849,9 @@ int fbstab_hip_mpc_condensed_x0_sensitivity_batch(fbstab_dense_handle_t handle, 
  *   work_doubles_per_traj = (N + 1) nu + 2 (N + 1) nc + nx + 1
  *   Sizes below 1 and traj_per_group below 0 are ARGUMENT; lds_bytes above 160 KB (a traj_per_group the caller chose)
  *   is FBSTAB_HIP_ERR_UNSUPPORTED (outputs 0).  Output pointers may be NULL.
- * Not here: per-step references (q, r, c, d that move along the sweep), sharded sweeps, the C++ facade.  (The
- * derivative through the sweep is the section below: this call's logs are its base.) */
+ * Not here: sharded sweeps, the C++ facade.  (Per-step references - q, r, c, d that move along the sweep - are
+ * fbstab_hip_mpc_condensed_tracking_sweep, and the derivative through the sweep is the section below: this call's logs
+ * are its base.) */
 enum fbstab_condensed_sweep_mode { FBSTAB_CONDENSED_SWEEP_AFFINE = 0, FBSTAB_CONDENSED_SWEEP_RECONDENSE = 1 };
 typedef struct fbstab_condensed_map_t {
   const double* M;      /* [F; G], ne x nx column-major */
@@ -935,7 +936,8 @@ int fbstab_hip_mpc_condensed_receding_sweep(fbstab_dense_handle_t handle, int N,
  *   work_doubles_per_traj      = 4 nzc + 2 nv + 2 nx + 1     (gU, dU, rU, eU; dv, ev; mu, -dl0; two status words)
  *   work_doubles_per_traj_grad = that + 2 (N + 1)(nx + nu) + (N + 1) nx       (z and the zeros of gz; l)
  * Not here: the device-side reduced form for shared parameters, forward mode through the sweep, seeds on the rest of
- * U_k and v_k, reuse of the forward call's images and map, per-step references, sharded calls, the C++ facade. */
+ * U_k and v_k, reuse of the forward call's images and map, sharded calls, the C++ facade.  (Per-step references:
+ * fbstab_hip_mpc_condensed_tracking_sweep_adjoint.) */
 int fbstab_hip_mpc_condensed_sweep_adjoint_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
                                                  int* traj_per_group_used, long long* lds_bytes,
                                                  long long* work_doubles_per_traj,
@@ -946,6 +948,111 @@ int fbstab_hip_mpc_condensed_receding_sweep_adjoint(
     int steps, int retire, const fbstab_condensed_sweep_log_t* log, const double* gu, const double* gx, double sigma,
     const fbstab_mpc_grad_batch_t* grad, double* gf0, double* gb0, double* mu_log, int* status, int mode,
     int traj_per_group, double* work, void* stream);
+
+/* ---- the condensed route in closed loop: sweeps that track per-step references -------------------------------------
+ * A controller that follows a moving set-point, a previewed trajectory or time-of-day bounds has q_k, r_k, d_k (and
+ * sometimes c_k) that change at every closed-loop step.  H_c, A_c and the map M = [F; G] do not depend on q, r, c, d,
+ * so step k solves
+ *   f_c,k(x) = f0_k + F x        b_c,k(x) = b0_k + G x
+ * with (f0_k, b0_k) what fbstab_hip_mpc_condense_batch(VECTORS) gives for x0 = 0 and the step's q_k, r_k, c_k, d_k.
+ *
+ * fbstab_condensed_refs_t: the sequences of every step.  Slot i (0 .. 3: q, r, c, d) of step k and trajectory b is at
+ * base[i] + k step[i] + b stride[i]; a NULL base is the sequence of `data` at every step.  step >= 0, and windows may
+ * overlap (the references are only read): step nx over one array of (steps + N) nx doubles is a sliding window over a
+ * longer reference.  stride: 0 shares the rows among the batch, otherwise >= the sequence length with batch > 1.
+ * fbstab_condensed_ref_images_t: f0_k at f0 + k step_f0 + b stride_f0, b0_k likewise.
+ *
+ * fbstab_hip_mpc_condensed_reference_images_batch: the images of all steps in ONE launch of
+ * fbstab_mpc_condense_reference_kernel on the grid batch x ceil(steps / R): a workgroup serves R steps of one
+ * trajectory, stages each stage's A, Q, S, B, E once for all of them and runs thread (row, reference).  Per reference
+ * the operations and their order are those of the VECTORS kernel: the images are bit for bit those of
+ * fbstab_hip_mpc_condense_batch(VECTORS) on the step's data with the x0 slot on a block of zeros, and neither R, the
+ * batch nor the neighbouring steps change a bit.  Handle-free, DEVICE pointers only, asynchronous on `stream`.
+ *   data:   the MPC data; its matrix sequences are read, q, r, c, d where refs has no slot, and x0 (checked like every
+ *           slot) is not read.
+ *   refs:   as above; NULL: every step is `data`'s.
+ *   images: the outputs; every (step, trajectory) needs rows of its own: step >= the length with steps > 1 and stride
+ *           >= the length with batch > 1.  The doubles between two images are not written.
+ *   refs_per_group: R.  0: the library's rule, clamp(256 / nx, 1, steps), lowered until the LDS is at most 80 KB.
+ * Validation (FBSTAB_HIP_ERR_ARGUMENT, before any device call): that of fbstab_hip_mpc_condense_batch; steps < 0;
+ * refs_per_group < 0; the references (negative step or stride, a stride below the length that is not 0); the outputs.
+ * batch == 0 or steps == 0 returns OK and queues nothing.  Then the device, then the LDS rule.
+ * fbstab_hip_mpc_condensed_reference_sizes: what that call will use, with e(n) = n rounded up to even, ldx = nx | 1,
+ * ldc = nc | 1, ldu = nu | 1:
+ *   lds_bytes = 8 (2 e(ldx nx) + e(ldx nu) + e(ldc nx) + e(ldu nx) + e(ldc nu) + e(ldu nu)      the stage images
+ *                  + R (e((N + 1) nx) + 2 e(nx)))                                    per reference: xbar and two p
+ *   Sizes or steps below 1 and refs_per_group below 0 are ARGUMENT; lds_bytes above 160 KB is
+ *   FBSTAB_HIP_ERR_UNSUPPORTED (outputs 0).  Output pointers may be NULL.
+ *
+ * fbstab_hip_mpc_condensed_tracking_sweep: fbstab_hip_mpc_condensed_receding_sweep where step k solves the QP of the
+ * references' step k.  The arguments are that call's, plus
+ *   refs:   the references of `steps` steps.  NULL: the call IS fbstab_hip_mpc_condensed_receding_sweep, bit for bit
+ *           (`images` is not looked at).
+ *   images: AFFINE mode with refs: f0_k, b0_k of every step as the call above writes them; they are READ (a stride of
+ *           0 shares them among the batch).  map->f0 and map->b0 are then not looked at; map->M is.
+ * On entry dense->f, dense->b are those of step 0's QP.  AFFINE mode: the step kernel of step k forms the vectors of
+ * step k + 1 from f0[k + 1], b0[k + 1].  RECONDENSE mode: the VECTORS launch behind step k reads step k + 1's
+ * sequences - the sweep is bitwise a loop over the public calls with the step's sequences.  The final expand uses the
+ * LAST step's sequences.  The kernels are those of fbstab_hip_mpc_condensed_receding_sweep: only the pointers a launch
+ * is handed differ.  Validation: that call's, in its order; in front of the handle checks the references as above, and
+ * in AFFINE mode NULL images, NULL f0 or b0, negative steps, and strides below the length that are not 0.
+ *
+ * fbstab_hip_mpc_condensed_tracking_sweep_adjoint: fbstab_hip_mpc_condensed_receding_sweep_adjoint through a sweep of
+ * the call above.  The lambda recursion does not change (M is the same at every step); the arguments are that call's
+ * without gf0 and gb0, plus
+ *   refs, images: the forward's.  NULL refs: the call IS the existing adjoint with gf0 = gb0 = NULL, bit for bit.
+ *   ref_grad: NULL, or one slot per q, r, c, d, NULL where not wanted: dL/d(sequence of step k, trajectory b) at
+ *           base[i] + k step[i] + b stride[i].  Every (step, trajectory) needs rows of its own: step >= the length with
+ *           steps > 1, stride >= the length with batch > 1.  EVERY entry is written: a retired step, a step that did
+ *           not end in SUCCESS and a step with a failed factorisation get zeros (one launch of the begin kernel per
+ *           step zeroes the rows in front of the recursion).  A slot of a sequence that does not move (refs->base[i]
+ *           NULL) is ARGUMENT: its gradient is grad's summed slot.
+ *   grad:   as there for x0, the seven matrix sequences and those of q, r, c, d that do not move - summed over the
+ *           contributing steps.  The slot of a sequence that moves is ARGUMENT.
+ * Opening step k uses f0[k], b0[k]; in RECONDENSE mode the VECTORS launch uses step k's sequences.  The finish kernel at
+ * step k sees step k's sequences (the expansion of the logged point needs q_k and c_k) and, for a sequence that
+ * moves, step k's rows of ref_grad.  x0, mu_log, status and the case rule are unchanged, and so is the device code:
+ * only the pointers a launch is handed differ.  Validation: the existing adjoint's, in its order; the references, their
+ * images and ref_grad in front of the handle checks.
+ * Not here: references on the record-kernel sweep, per-step gf0 / gb0, the device-side reduced form, forward mode
+ * through the sweep, sharded sweeps, the C++ facade. */
+typedef struct fbstab_condensed_refs_t {       /* per-step q, r, c, d */
+  const double* base[4];      /* q, r, c, d; NULL: the sequence of `data` at every step */
+  long long step[4];          /* doubles between steps (>= 0; overlapping windows are allowed: read-only) */
+  long long stride[4];        /* doubles between trajectories; 0 = one for all */
+} fbstab_condensed_refs_t;
+typedef struct fbstab_condensed_ref_images_t { /* f0_k, b0_k */
+  double *f0, *b0;
+  long long step_f0, step_b0, stride_f0, stride_b0;
+} fbstab_condensed_ref_images_t;
+typedef struct fbstab_condensed_ref_grad_t {   /* dL/d(q_k, r_k, c_k, d_k) */
+  double* base[4];            /* NULL: not wanted */
+  long long step[4];          /* doubles between steps (>= the length) */
+  long long stride[4];        /* doubles between trajectories (>= the length) */
+} fbstab_condensed_ref_grad_t;
+int fbstab_hip_mpc_condensed_reference_sizes(int N, int nx, int nu, int nc, int steps, int refs_per_group,
+                                             int* refs_per_group_used, long long* lds_bytes);
+int fbstab_hip_mpc_condensed_reference_images_batch(int N, int nx, int nu, int nc, int batch, int steps,
+                                                    const fbstab_mpc_batch_t* data,
+                                                    const fbstab_condensed_refs_t* refs,
+                                                    const fbstab_condensed_ref_images_t* images, int refs_per_group,
+                                                    int device, void* stream);
+int fbstab_hip_mpc_condensed_tracking_sweep(fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch,
+                                            const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
+                                            const fbstab_condensed_map_t* map, const fbstab_var_batch_t* x,
+                                            fbstab_solver_out_t* out, const fbstab_receding_plant_t* plant, int steps,
+                                            int retire, const fbstab_sweep_scenario_t* scenario, int mode,
+                                            const fbstab_condensed_sweep_log_t* log,
+                                            const fbstab_condensed_refs_t* refs,
+                                            const fbstab_condensed_ref_images_t* images, int traj_per_group,
+                                            double* work, void* stream);
+int fbstab_hip_mpc_condensed_tracking_sweep_adjoint(
+    fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch, const fbstab_mpc_batch_t* data,
+    const fbstab_dense_batch_t* dense, const fbstab_condensed_map_t* map, const fbstab_receding_plant_t* plant,
+    int steps, int retire, const fbstab_condensed_sweep_log_t* log, const double* gu, const double* gx, double sigma,
+    const fbstab_mpc_grad_batch_t* grad, double* mu_log, int* status, int mode, const fbstab_condensed_refs_t* refs,
+    const fbstab_condensed_ref_images_t* images, const fbstab_condensed_ref_grad_t* ref_grad, int traj_per_group,
+    double* work, void* stream);
 
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
 int fbstab_hip_debug_stamps(unsigned long long* out32, int reset);
