@@ -18,11 +18,15 @@
 //     copy of A exists (40 KB per QP at 50/10/100: a third of the scratch a resident
 //     QP used to hold); the tiles reach the row layout through a 64 x 16 staging
 //     panel in LDS, one column block at a time;
-//   * LDL' by Eigen::LDLT's pivoting rule (largest |diagonal| of what is left, the first
+//   * LDL' by diagonal pivoting after Eigen::LDLT (largest |diagonal| of what is left, the first
 //     maximum wins; dense_cholesky_solver.cc:70-79), the DEFAULT since round 4: it
 //     eliminates in place without swapping anything and keeps its multipliers in a 64 x 64
-//     global scratch.  Same elimination order as the reference, same iteration counts on
-//     every QP tried ("which order is the default");
+//     global scratch.  Same iteration counts as the reference on every QP tried (DESIGN.md 4.2,
+//     "which order is the default").  NOT the same elimination order in general
+//     (tests/dense_wave_rules.py: eigen_ldlt, DEVICE_AS_DOCUMENTED; LABNOTES): Eigen's
+//     left-looking storage still holds the diagonal AS ASSEMBLED when it searches, this
+//     right-looking loop searches the UPDATED diagonal; and Eigen's first maximum is first by
+//     position after its swaps, the one here has the lowest row index;
 //   * LDL' in the NATURAL order, unrolled over its steps and fused with both
 //     substitutions (factor_solve_static, round 3), a per-handle option
 //     (fbstab_hip_dense_set_factorisation: NATURAL, or AUTO = natural until a QP shows
@@ -39,7 +43,7 @@
 // DenseCholeskySolver::Initialize / Solve (dense_cholesky_solver.cc:32-127),
 // FullFeasibility::CheckFeasibility (full_feasibility.cc:25-88).  The pivoted
 // path is the same factorisation as Eigen's up to rounding (right-looking here,
-// left-looking there; the pivot order is the same rule); the natural-order path
+// left-looking there; the pivot rule differs as said above); the natural-order path
 // solves the same systems with a different rounding, which shows where the
 // answer is not unique - the multipliers of dual-degenerate QPs (tests/
 // test_gpu_parity.py, _unique_duals) - and where a convergence test is decided by the
@@ -556,7 +560,9 @@ struct DenseWave {
   // LDS busy for 32 instructions that seven other wavefronts wait behind; the column
   // goes to LDS with ONE store and comes back as the pivot row, kLdsCols columns as
   // 16-byte broadcasts and the rest through v_readlane (the LDS and the vector pipe
-  // share the work).  Returns false where Eigen reports failure.
+  // share the work).  Returns false on a NaN diagonal and on a valid pivot behind an invalid one, as Eigen
+  // does; the column under an invalid (zero) pivot is NOT examined, where Eigen fails if it is not zero
+  // ([[0, 1], [1, 0]]: true here, false there) - sigma > 0 keeps every caller away from such a matrix.
   // out = a[p], p wavefront-uniform.  Real branches: the empty asm keeps the
   // optimiser from turning the tree into selects of loads, i.e. into a copy of the
   // array in scratch memory that every update then has to write through.

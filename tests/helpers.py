@@ -154,13 +154,14 @@ def mpc_explicit(p, b=0):
     return H, f, G, h, A, bb
 
 
-def newton_system_residual(p, q, step, x=None, xbar=None, sigma=1e-8, alpha=0.95):
+def newton_system_residual(p, q, step, x=None, xbar=None, sigma=1e-8, alpha=0.95, explicit=None):
     """|V dx - r| of the Newton system V(x, xbar, sigma) dx = -R(x, xbar, sigma) (abstract_components.h:276-288,
     full_residual.cc:49-74) for QP ``q`` of the MpcProblem ``p`` at x = (z, l, v) (default: zeros), evaluated in
     numpy longdouble (64-bit mantissa).  step: dict with dz, dl, dv.  Returns ([max |.| of the z, l, v block
-    rows], 2-norm over all rows)."""
+    rows], 2-norm over all rows).  ``explicit``: the QP's (H, f, G, h, A, b) where ``p`` is not an MpcProblem
+    (``dense_explicit(p, q)`` for a dense one)."""
     LD = np.longdouble
-    Hm, f, G, hh, A, b = (m.astype(LD) for m in mpc_explicit(p, q))
+    Hm, f, G, hh, A, b = (m.astype(LD) for m in (explicit if explicit is not None else mpc_explicit(p, q)))
     zero = lambda n: np.zeros(n, LD)
     z, l, v = (t.astype(LD) for t in x) if x is not None else (zero(p.nz), zero(p.nl), zero(p.nv))
     zb, lb, vb = (t.astype(LD) for t in xbar) if xbar is not None else (z, l, v)
@@ -182,7 +183,7 @@ def newton_system_residual(p, q, step, x=None, xbar=None, sigma=1e-8, alpha=0.95
     e1 = Hm @ dz + sig * dz + G.T @ dl + A.T @ dv - rz
     e2 = -G @ dz + sig * dl - rl
     e3 = -gam * (A @ dz) + mus * dv + phi
-    blocks = [float(np.abs(e).max()) for e in (e1, e2, e3)]
+    blocks = [float(np.abs(e).max()) if e.size else 0.0 for e in (e1, e2, e3)]  # (a dense QP may have no l rows)
     return blocks, float(np.sqrt((e1 * e1).sum() + (e2 * e2).sum() + (e3 * e3).sum()))
 
 

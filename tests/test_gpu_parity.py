@@ -328,7 +328,7 @@ def test_dense_synthetic_batch_parity(hip, oracle):
 @pytest.mark.parametrize("shape", [(7, 0, 9), (16, 3, 20), (33, 5, 61), (30, 20, 64), (64, 0, 128), (48, 16, 131)])
 def test_dense_odd_shapes(hip, oracle, monkeypatch, shape, order):
     """Dense kernel paths by shape: no equalities, nz not a multiple of 16, nv not
-    a multiple of 4 (scalar K assembly instead of MFMA), A too large for LDS,
+    a multiple of 16 (the last matrix-core trip re-reads the last rows with weight zero), A too large for LDS,
     nz + nl == 64 (largest register-resident solve).  The default elimination order of the
     one-wavefront kernel is Eigen's (dense_cholesky_solver.cc:70-79): iteration counts equal
     the oracle's on every QP and every multiplier is compared entry by entry.  The opt-in
