@@ -54,8 +54,8 @@ returned point one stage towards the present before it is the next guess (fbstab
 fewer Newton steps on time-invariant horizons, more on random time-varying ones).  The backward is the same call:
 the recursion does not change, and ``w.grad`` is the logged costate, dL/dw_k = mu_k, zero at and after a
 trajectory's retirement step.  Not served: the batch-summed
-(reduced) path inside the library, forward mode through the sweep, and losses of anything but ``u`` and ``x`` (the
-rest of z_k, l_k, v_k).
+(reduced) path inside the library, forward mode through the sweep (the condensed route below serves it), and losses
+of anything but ``u`` and ``x`` (the rest of z_k, l_k, v_k).
 
 Jacobians of the solution map with respect to the initial state, as matrices:
 
@@ -436,10 +436,54 @@ class ClosedLoopCondensedMpcFunction(torch.autograd.Function):
         x = torch.cat([r["x"][1:], run["x0"][None]], 0)
         ctx.cm, ctx.steps, ctx.retire, ctx.sigma = cm, steps, retire, sigma
         ctx.ref_names = tuple(ref)
-        ctx.save_for_backward(A.detach(), B.detach(), u, r["x"], r["U"], r["v"], r["eflag"],
-                              *[data[k] for k in MPC_SEQ], *ref.values())
+        saved = (A.detach(), B.detach(), u, r["x"], r["U"], r["v"], r["eflag"], *[data[k] for k in MPC_SEQ],
+                 *ref.values())
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        # absent tangents reach `jvp` as None instead of zeros (a tangent on a matrix sequence must be told from none);
+        # `backward` hands an absent seed on as None, which the adjoint call reads as zeros
+        ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(r["out"])
         return u, x, r["out"]
+
+    @staticmethod
+    def jvp(ctx, cm_t, steps_t, retire_t, sigma_t, A_t, B_t, *rest):
+        nseq = len(MPC_SEQ)
+        seq_t, w_t, ref_t = rest[:nseq], rest[nseq], rest[nseq + 2:]
+        A, B, u, xl, Ul, vl, el = ctx.saved_tensors[:7]
+        data = dict(zip(MPC_SEQ, ctx.saved_tensors[7:7 + nseq]))
+        ref = dict(zip(ctx.ref_names, ctx.saved_tensors[7 + nseq:]))
+        dx0, ddata, dref = None, {}, {}
+        for k, t in zip(MPC_SEQ, seq_t):
+            if t is None or t.numel() == 0:
+                continue
+            if k not in _REF_SEQ and k != "x0":
+                raise NotImplementedError(
+                    "forward mode through closed_loop_condensed_mpc: a tangent on the matrix sequence %r - x0, q, r, c, "
+                    "d, the per-step references, w, A and B are served" % k)
+            t = t.detach()
+            if k == "x0":
+                dx0 = t.reshape(data["x0"].shape).contiguous()
+            elif k not in ctx.ref_names:   # (data's sequence does not enter where a reference stands in its place)
+                ddata[k] = (t.reshape(1, t.numel()) if (k in ctx.shared or t.dim() == 1) else t).contiguous()
+        for k, t in zip(_REF_SEQ, ref_t):
+            if t is not None and k in ctx.ref_names:
+                dref[k] = t.detach().contiguous()
+        dw = None if w_t is None else w_t.detach().contiguous()
+        if A_t is not None or B_t is not None:
+            # directions of the plant enter as dw_k += dA x_k + dB u_k; x_(k+1) of a retired step is the constant 0
+            # (a plant of every trajectory's own, (batch, nx, nx) / (batch, nx, nu), has a tangent of that shape)
+            fold = lambda t, v: torch.einsum("bij,kbj->kbi" if t.dim() == 3 else "ij,kbj->kbi", t.detach(), v)
+            extra = torch.zeros_like(xl)
+            if A_t is not None:
+                extra = extra + fold(A_t, xl)
+            if B_t is not None:
+                extra = extra + fold(B_t, u)
+            extra = torch.where((el == -1)[:, :, None], torch.zeros_like(extra), extra)
+            dw = extra if dw is None else dw + extra
+        res = ctx.cm.RecedingSweepTangent(data, A, B, ctx.steps, dict(x=xl, U=Ul, v=vl, eflag=el), dx0=dx0, dw=dw,
+                                          ddata=ddata or None, dref=dref or None, ref=ref or None, sigma=ctx.sigma)
+        return res["du"], res["dx"], None
 
     @staticmethod
     def backward(ctx, gu, gx, gout):
@@ -457,8 +501,8 @@ class ClosedLoopCondensedMpcFunction(torch.autograd.Function):
         data = dict(zip(MPC_SEQ, ctx.saved_tensors[7:7 + nseq]))
         ref = dict(zip(ctx.ref_names, ctx.saved_tensors[7 + nseq:]))
         log = dict(x=xl, U=Ul, v=vl, eflag=el)
-        g = ctx.cm.RecedingSweepAdjoint(data, A, B, ctx.steps, log, gu=gu.contiguous(), gx=gx.contiguous(),
-                                        retire=ctx.retire, sigma=ctx.sigma,
+        g = ctx.cm.RecedingSweepAdjoint(data, A, B, ctx.steps, log, gu=None if gu is None else gu.contiguous(),
+                                        gx=None if gx is None else gx.contiguous(), retire=ctx.retire, sigma=ctx.sigma,
                                         want=[k for k in want if k != "x0"] + ref_want, mu=plant or noise,
                                         ref=ref or None)
         gA = gB = mu = None
@@ -496,7 +540,13 @@ def closed_loop_condensed_mpc(cm, data, A, B, steps: int, retire: bool = True, s
     ``(steps, batch, len)`` or ``(steps, 1, len)``.  They are inputs of the function: a reference's ``.grad`` is the
     per-step array (the torch sum over the batch for a ``(steps, 1, len)`` one, folded back by torch where the
     reference is an ``as_strided`` sliding window over a longer tensor), and ``data``'s sequence of that name does
-    not enter the loop."""
+    not enter the loop.
+    Forward mode (``torch.autograd.forward_ad``): ONE ``CondensedMpc.RecedingSweepTangent`` call gives ``u`` and ``x``
+    their tangents along the tangents of ``x0, q, r, c, d``, the references, ``w`` and the plant (``A``, ``B`` are
+    folded into the disturbance direction in torch, dw_k += dA x_k + dB u_k, left out at retired steps; a shared
+    ``(nx, nx)`` / ``(nx, nu)`` plant or a per-trajectory ``(batch, nx, nx)`` / ``(batch, nx, nu)`` one - the backward's
+    ``A.grad``, ``B.grad`` serve the shared form alone).  A tangent on a matrix sequence raises
+    ``NotImplementedError``."""
     seqs = [data[k] for k in MPC_SEQ]
     if ref is None:
         return ClosedLoopCondensedMpcFunction.apply(cm, steps, retire, sigma, A, B, *seqs, w, bool(shift))

@@ -81,6 +81,18 @@ def condensed_sweep_adjoint_sizes(N: int, nx: int, nu: int, nc: int, traj_per_gr
                 work_doubles_per_traj_grad=workg.value)
 
 
+def condensed_sweep_tangent_sizes(N: int, nx: int, nu: int, nc: int, traj_per_group: int = 0,
+                                  shared_map: bool = True) -> Dict[str, int]:
+    """fbstab_hip_mpc_condensed_sweep_tangent_sizes: what forward mode through the closed-loop sweep uses -
+    ``traj_per_group`` and ``lds_bytes`` of its step kernel (those of the forward sweep's), and the
+    ``work_doubles_per_traj`` of the caller's work array."""
+    lib = hip_api.load_library()
+    used, lds, work = C.c_int(), C.c_longlong(), C.c_longlong()
+    _check(lib, lib.fbstab_hip_mpc_condensed_sweep_tangent_sizes(N, nx, nu, nc, traj_per_group, 1 if shared_map else 0,
+                                                                 C.byref(used), C.byref(lds), C.byref(work)))
+    return dict(traj_per_group=used.value, lds_bytes=lds.value, work_doubles_per_traj=work.value)
+
+
 class CondensedMpc:
     """``CondensedMpc(N, nx, nu, nc, max_batch)``: owns ``.dense``, a ``FBstabDenseBatch((N + 1) nu, 0, (N + 1) nc)``
     (public: ``SetFactorisation``, ``UpdateOptions`` ... apply to it), and the condensed images ``H, f, A, b`` as
@@ -684,6 +696,146 @@ class CondensedMpc:
                 *head, ptr(res.get("mu")), C.c_void_p(status.data_ptr()), _SWEEP_MODE[mode], C.byref(rblk),
                 C.byref(rimg) if rimg is not None else None, C.byref(rgrad), *tail)
         _check(self._lib, rc)
+        res["status"] = status
+        if host:
+            res = {k: a.cpu().numpy() for k, a in res.items()}
+        return res
+
+    def _direction_images(self, d, ddata, dref, rdev, steps, Bn):
+        """The directions of f0_k, b0_k from those of q, r, c, d: the images are linear in the four sequences, so
+        ``ReferenceImages``' kernel on the direction sequences gives them - every slot given, zeros where nothing
+        moves.  -> (df0, db0, step count of the images: 1 where no per-step reference moves), or None."""
+        t = self._torch
+        ddata, dref = dict(ddata or {}), dict(dref or {})
+        for name, src in (("ddata", ddata), ("dref", dref)):
+            for k in src:
+                if k in _MATRIX_SEQ:
+                    raise NotImplementedError(
+                        "RecedingSweepTangent: a direction on the matrix sequence %r (%s) - forward mode through the "
+                        "sweep serves x0, w, q, r, c, d and the per-step references; H_c, A_c and the map M are held "
+                        "fixed" % (k, name))
+            unknown = set(src) - set(_REF_SEQ)
+            assert not unknown, (name, unknown, "the direction of x0 is dx0")
+        ddata = {k: a for k, a in ddata.items() if a is not None}
+        dref = {k: a for k, a in dref.items() if a is not None}
+        if not ddata and not dref:
+            return None
+        nsteps = steps if dref else 1
+        blk, keep = _CondensedRefs(), []
+        for i, k in enumerate(_REF_SEQ):
+            n = self.seq_len[MPC_SEQ.index(k)]
+            if k in dref:
+                assert k in rdev, "dref[%r]: %r is not a per-step reference of this sweep (ref)" % (k, k)
+                assert k not in ddata, "ddata[%r]: the sweep reads ref[%r], not data's sequence" % (k, k)
+                a = self._to_dev(dref[k].detach() if _is_torch(dref[k]) else dref[k]).to(t.float64).contiguous()
+                assert a.dim() == 3 and a.shape[0] == steps and a.shape[1] in (1, Bn) and a.shape[2] == n, (
+                    k, tuple(a.shape), (steps, Bn, n))
+                blk.base[i], blk.step[i] = a.data_ptr(), a.stride(0)
+                blk.stride[i] = 0 if (a.shape[1] == 1 and Bn > 1) else n
+            elif k in ddata:
+                assert k not in rdev, "ddata[%r]: the sweep reads ref[%r], not data's sequence" % (k, k)
+                a = self._to_dev(ddata[k].detach() if _is_torch(ddata[k]) else ddata[k]).to(t.float64).contiguous()
+                a = a.reshape(1, n) if a.dim() == 1 else a
+                assert a.dim() == 2 and a.shape[0] in (1, Bn) and a.shape[1] == n, (k, tuple(a.shape), (Bn, n))
+                blk.base[i], blk.step[i] = a.data_ptr(), 0
+                blk.stride[i] = 0 if (a.shape[0] == 1 and Bn > 1) else n
+            else:
+                a = t.zeros((1, n), dtype=t.float64, device=self._dev)
+                blk.base[i], blk.step[i], blk.stride[i] = a.data_ptr(), 0, 0
+            keep.append(a)
+        df0, db0, _ = self._reference_images(d, blk, nsteps, Bn)
+        return df0, db0, nsteps
+
+    def RecedingSweepTangent(self, data: Dict[str, object], A, B, steps: int, log: Dict[str, object], dx0=None,
+                             dw=None, ddata: Optional[Dict[str, object]] = None,
+                             dref: Optional[Dict[str, object]] = None, ref: Optional[Dict[str, object]] = None,
+                             sigma: float = 0.0, traj_per_group: int = 0) -> Dict[str, object]:
+        """Forward mode through ``RecedingSweep`` in one call (fbstab_hip_mpc_condensed_receding_sweep_tangent): how
+        the closed-loop u_k and x_(k+1) of the sweep that ``log`` records - what ``RecedingSweep(..., log=("x", "U",
+        "v"))`` returned: its ``x``, ``U``, ``v`` and ``eflag`` are read - move along ONE direction:
+        ``dx0`` ``(batch, nx)`` (``(nx,)`` or ``(1, nx)``: shared), ``dw`` ``(steps, batch, nx)``, ``ddata`` - directions
+        of ``data``'s ``q, r, c, d``, ``(batch, len)``, or ``(len,)`` / ``(1, len)`` for one shared by the batch - and
+        ``dref`` - directions of the per-step references ``ref`` (the forward's), ``(steps, batch, len)`` or
+        ``(steps, 1, len)``.  None is zero everywhere.  ``ddata`` and ``dref`` are mapped to the directions of the
+        images f0_k, b0_k by ``ReferenceImages``' kernel on the direction sequences.  A direction on a matrix sequence
+        raises ``NotImplementedError``.  Directions of the plant are the caller's: add dA x_k + dB u_k to ``dw[k]``
+        where step k is not retired.  ``data``: the sweep's data (its ``x0`` is not read, only its batch size);
+        ``A``/``B``: the plant as there.  This call condenses ``data`` ("all") and builds the map of ``X0Map`` itself
+        (a sweep that ran in ``mode="recondense"`` is differentiated through it): the images this object held before
+        are replaced, and the vectors ``f``, ``b`` are scratch of the call.  Returns ``dict(du (steps, batch, nu),
+        dx (steps, batch, nx), status)`` - du_k, dx_(k+1), and per trajectory the steps whose factorisation failed;
+        du and dx are zero at and behind a retirement, and du is zero at a step that did not end in SUCCESS.
+        ``traj_per_group``: as in ``RecedingSweep``; it changes speed, never results.  Everything is queued on torch's
+        current stream; numpy inputs are uploaded and numpy arrays come back (decided by ``log["U"]``)."""
+        t = self._torch
+        host = not _is_torch(log["U"])
+        d = self._data(data)
+        Bn = d["x0"].shape[0]
+        assert 1 <= Bn <= self.max_batch, (Bn, self.max_batch)
+        f64 = lambda a: (a.detach() if _is_torch(a) else t.from_numpy(np.ascontiguousarray(a, dtype=np.float64))).to(
+            self._dev, t.float64).contiguous()
+        xl, Ul, vl = (f64(log[k]) for k in ("x", "U", "v"))
+        el = log["eflag"]
+        el = (el.detach() if _is_torch(el) else t.from_numpy(np.ascontiguousarray(el))).to(self._dev, t.int32).contiguous()
+        for a, n in ((xl, self.nx), (Ul, self.nzc), (vl, self.nv)):
+            assert tuple(a.shape) == (steps, Bn, n), (tuple(a.shape), (steps, Bn, n))
+        assert tuple(el.shape) == (steps, Bn), tuple(el.shape)
+        rblk, rimg, rdev = None, None, {}
+        if ref is not None and steps > 0:
+            rblk, rdev = self._refs(ref, steps, Bn)
+        dimg = self._direction_images(d, ddata, dref, rdev, steps, Bn) if steps > 0 else None
+        self._condense(d, "all")   # (H_c and A_c do not depend on q, r, c, d; f and b are scratch of the call)
+        img = self._img
+        m = self._x0_map(d)
+        st = lambda a, n: 0 if (a.shape[0] == 1 and Bn > 1) else n
+        cm = _CondensedMap(m["M"].data_ptr(), m["f0"].data_ptr(), m["b0"].data_ptr(), st(m["M"], m["M"].shape[1]),
+                           self.nzc, self.nv)
+        if rblk is not None:
+            keep_f0, keep_b0, rimg = self._reference_images(d, rblk, steps, Bn)
+        dense = _DenseBatch()
+        for k in ("H", "f", "A", "b"):
+            a, i = img[k], DENSE_ARR.index(k)
+            dense.base[i], dense.stride[i] = a.data_ptr(), (0 if (a.shape[0] == 1 and Bn > 1) else self._len[k])
+        cimg = lambda a: f64(a).transpose(-1, -2).contiguous()
+        Ad, Bd = cimg(A), cimg(B)
+        for a, shape in ((Ad, (self.nx, self.nx)), (Bd, (self.nu, self.nx))):
+            assert tuple(a.shape) in (shape, (Bn,) + shape), (tuple(a.shape), shape)
+        plant = _Plant(Ad.data_ptr(), Bd.data_ptr(), self.nx * self.nx if Ad.dim() == 3 else 0,
+                       self.nx * self.nu if Bd.dim() == 3 else 0)
+        dr = hip_api._CondensedSweepDir()
+        if dx0 is not None:
+            x0d = f64(dx0)
+            x0d = x0d.reshape(1, self.nx) if x0d.dim() == 1 else x0d
+            assert tuple(x0d.shape) in ((1, self.nx), (Bn, self.nx)), "dx0: (batch, nx), (1, nx) or (nx,)"
+            dr.dx0, dr.stride_dx0 = x0d.data_ptr(), (0 if (x0d.shape[0] == 1 and Bn > 1) else self.nx)
+        if dw is not None and steps > 0:
+            dwd = f64(dw)
+            assert tuple(dwd.shape) == (steps, Bn, self.nx), "dw: (steps, batch, nx)"
+            dr.dw = dwd.data_ptr()
+        if dimg is not None:
+            df0, db0, nsteps = dimg
+            dr.df0, dr.db0 = df0.data_ptr(), db0.data_ptr()
+            dr.step_df0, dr.step_db0 = (Bn * self.nzc, Bn * self.nv) if nsteps > 1 else (0, 0)
+            dr.stride_df0, dr.stride_db0 = self.nzc, self.nv
+        mk = lambda shape, dtype=t.float64: t.zeros(shape, dtype=dtype, device=self._dev)
+        res = dict(du=mk((steps, Bn, self.nu)), dx=mk((steps, Bn, self.nx)))
+        status = mk((Bn,), t.int32)
+        sizes = condensed_sweep_tangent_sizes(self.N, self.nx, self.nu, self.nc, traj_per_group,
+                                              Bn == 1 or cm.stride_M == 0)
+        work = t.empty((Bn, sizes["work_doubles_per_traj"]), dtype=t.float64, device=self._dev)
+        lg = _CondensedSweepLog(None, xl.data_ptr() or None, Ul.data_ptr() or None, vl.data_ptr() or None,
+                                el.data_ptr() or None, None)
+        outs = (C.c_void_p(res["du"].data_ptr()), C.c_void_p(res["dx"].data_ptr()))
+        if steps == 0:  # (empty arrays have no address; the call reads and writes none of them)
+            lg = _CondensedSweepLog(None, work.data_ptr(), work.data_ptr(), work.data_ptr(), work.data_ptr(), None)
+            outs = (C.c_void_p(work.data_ptr()), C.c_void_p(work.data_ptr()))
+        s = self._stream()
+        self.generation += 1
+        _check(self._lib, self._lib.fbstab_hip_mpc_condensed_receding_sweep_tangent(
+            self.dense._h, self.N, self.nx, self.nu, self.nc, Bn, C.byref(dense), C.byref(cm),
+            C.byref(rimg) if rimg is not None else None, C.byref(plant), steps, C.byref(lg), C.byref(dr),
+            C.c_double(sigma), outs[0], outs[1], C.c_void_p(status.data_ptr()), traj_per_group,
+            C.c_void_p(work.data_ptr()), C.c_void_p(s) if s else None))
         res["status"] = status
         if host:
             res = {k: a.cpu().numpy() for k, a in res.items()}

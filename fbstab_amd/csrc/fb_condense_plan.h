@@ -19,6 +19,7 @@ enum CondenseSweepAdjKernel { kCondenseSweepAdjStep = 0, kCondenseSweepAdjFinish
                               kCondenseSweepAdjBegin = 2 };                           // fb_condense_sweep_adjoint.hip
 enum CondenseTangentKernel { kCondenseTangentRhs = 0 };                                    // fb_condense_tangent.hip
 enum CondenseRefsKernel { kCondenseRefsImages = 0 };                                          // fb_condense_refs.hip
+enum CondenseSweepTanKernel { kCondenseSweepTanStep = 0 };                            // fb_condense_sweep_tangent.hip
 
 // ---- fb_condense.h ----------------------------------------------------------------------------------------------
 inline int condense_ld(int rows) { return rows | 1; }
@@ -190,6 +191,34 @@ struct CondenseSweepAdjFinish {
   double* dl0;                    // null, or [batch][nx] (zero on entry): receives -dl[0:nx]
 };
 
+// ---- fb_condense_sweep_tangent.h --------------------------------------------------------------------------------
+// What one launch of the step kernel works on.  close / open: which parts run (the first launch only opens, the last
+// only closes).  The arrays of the closed step k and of the opened step k + 1 are their shares of the logs, of the
+// directions and of the outputs.
+struct CondenseSweepTanStep {
+  int N, nx, nu, nc, batch;
+  int close, open;
+  const int* eflag_close;         // eflag_log[k]
+  const int* eflag_open;          // eflag_log[k + 1]
+  const int *st1, *st2;           // the dense adjoint's status of both launches of step k
+  int* status;                    // [batch]: zeroed by the launch that does not close, += 1 as in the adjoint
+  const double* dU;               // the refined dense step of step k, packed [batch][nzc]
+  double* dx;                     // [batch][nx]: the direction of the state, carried from launch to launch
+  const double* dx0; long long sdx0;  // read by the launch that does not close (null: zero)
+  const double *Ap, *Bp; long long sAp, sBp;
+  const double* dw;               // null (zero), or dw[k] [batch][nx]
+  double *du_out, *dx_out;        // null, or du_out[k] [batch][nu], dx_out[k] [batch][nx]
+  const double* x_log;            // x_log[k + 1]
+  const double* M; long long sM;
+  const double* f0; long long sf0;
+  const double* b0; long long sb0;
+  double* f; long long sf;
+  double* b; long long sb;
+  const double* df0; long long sdf0;  // null (zero), or the directions of f0, b0 of step k + 1
+  const double* db0; long long sdb0;
+  double *gU, *gv;                // [batch][nzc], [batch][nv]: the seeds of the dense adjoint of step k + 1
+};
+
 // ---- the callers' work arrays -------------------------------------------------------------------------------------
 // A work array is packed pieces, [batch][n] each, one behind the other.  Each struct below is the ONE description of
 // an array: constructed on (work, batch) it holds the pieces and `per`, the doubles of one QP or trajectory that the
@@ -286,6 +315,27 @@ struct CondenseSweepAdjCarve {
       z = c.take((long long)(N + 1) * (nx + nu)); gz = c.take((long long)(N + 1) * (nx + nu));
       l = c.take((long long)(N + 1) * nx);
     }
+    per = c.per;
+  }
+};
+
+// fbstab_hip_mpc_condensed_sweep_tangent_sizes: the seeds, the dense step and its refinement (wk; its U is not
+// used), the carried direction of the state, the two status words st1 and st2 ([batch] ints each, in ONE double per
+// trajectory).
+struct CondenseSweepTanCarve {
+  CondenseAdjointWork wk;
+  double* dx;
+  int *st1, *st2;
+  long long per;
+  CondenseSweepTanCarve(int N, int nx, int nu, int nc, double* work, int batch) {
+    const long long nz = (long long)(N + 1) * nu, nv = (long long)(N + 1) * nc;
+    CondenseCarve c = {work, batch, 0};
+    wk = CondenseAdjointWork{};
+    wk.gU = c.take(nz); wk.dU = c.take(nz); wk.rU = c.take(nz); wk.eU = c.take(nz);
+    wk.gv = c.take(nv); wk.dv = c.take(nv); wk.ev = c.take(nv);
+    dx = c.take(nx);
+    st1 = c.take_ints();
+    st2 = st1 ? st1 + batch : nullptr;
     per = c.per;
   }
 };

@@ -1,5 +1,5 @@
 // Host side of the condensed MPC route (include/fbstab_hip.h: fbstab_hip_mpc_condense_batch to
-// fbstab_hip_mpc_condensed_receding_sweep_adjoint): the argument checks, the blocks as the kernels take them, the
+// fbstab_hip_mpc_condensed_receding_sweep_tangent): the argument checks, the blocks as the kernels take them, the
 // callers' work arrays (fb_condense_plan.h) and the order of the launches.  As fb_host_stage.h: no device code and no
 // kernel header.  What reaches a kernel or the dense handle is passed in by fbstab_hip.hip as a callable -
 //   launch(id, grid, lds_bytes, args, stream)                                    kernel `id` of fb_condense_plan.h's enums
@@ -1052,6 +1052,125 @@ int condensed_sweep_adjoint_run(SolverBase* h, int N, int nx, int nu, int nc, in
   return condensed_tracking_sweep_adjoint_run(h, N, nx, nu, nc, batch, data, dense, map, plant, steps, log, gu, gx,
                                               sigma, grad, gf0, gb0, mu_log, status, mode, nullptr, nullptr, nullptr,
                                               traj_per_group, work, stream, launch, dense_adjoint);
+}
+
+// ---- forward mode through that sweep (fb_condense_sweep_tangent.h) ---------------------------------------------------
+// What fbstab_hip_mpc_condensed_sweep_tangent_sizes documents.
+inline int condensed_sweep_tangent_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
+                                         int* traj_per_group_used, long long* lds_bytes, long long* work) {
+  RC_TRY(condense_sizes_prologue("condensed sweep tangent", N, nx, nu, nc,
+                                 traj_per_group < 0 ? "negative traj_per_group" : nullptr, {traj_per_group_used},
+                                 {lds_bytes, work}));
+  CondenseSweepLds L;
+  RC_TRY(condense_sweep_plan(N, nx, nu, nc, traj_per_group, shared_map != 0, &L));
+  if (traj_per_group_used) *traj_per_group_used = L.T;
+  if (lds_bytes) *lds_bytes = (long long)L.total * 8;
+  if (work) *work = CondenseSweepTanCarve(N, nx, nu, nc, nullptr, 0).per;
+  return FBSTAB_HIP_OK;
+}
+
+// fbstab_hip_mpc_condensed_receding_sweep_tangent: steps + 1 launches of the step kernel - the first only opens step
+// 0, the last only closes step steps - 1 - and between two of them condense_refined_step at the logged (U_k, v_k) on
+// the seeds the launch in front wrote.  Every launch is handed the pointers of the step it closes (dw[k], du[k], dx[k])
+// and of the step it opens (x_log, the images f0, b0 and their directions).  AFFINE mode always: there is no `data`.
+template <class Launch, class DenseAdjoint>
+int condensed_sweep_tangent_run(SolverBase* h, int N, int nx, int nu, int nc, int batch,
+                                const fbstab_dense_batch_t* dense, const fbstab_condensed_map_t* map,
+                                const fbstab_condensed_ref_images_t* images, const fbstab_receding_plant_t* plant,
+                                int steps, const fbstab_condensed_sweep_log_t* log,
+                                const fbstab_condensed_sweep_dir_t* dir, double sigma, double* du, double* dx,
+                                int* status, int traj_per_group, double* work, void* stream, Launch launch,
+                                DenseAdjoint dense_adjoint) {
+  const char* who = "condensed sweep tangent";
+  // what needs no handle comes first, in the order of fbstab_hip_mpc_condensed_receding_sweep_adjoint
+  if (N < 1 || nx < 1 || nu < 1 || nc < 1) return condense_bad(who, "problem sizes must be positive");
+  if (batch < 0) return condense_bad(who, "negative batch");
+  if (!dense || !plant || !log || !dir || !status || !work) return condense_bad(who, "null argument");
+  if (!du && !dx) return condense_bad(who, "both du and dx are null");
+  if (!plant->A || !plant->B) return condense_bad(who, "null plant matrix");
+  if (steps < 0) return condense_bad(who, "negative step count");
+  if (traj_per_group < 0) return condense_bad(who, "negative traj_per_group");
+  CondenseShape sh = {};
+  sh.N = N; sh.nx = nx; sh.nu = nu; sh.nc = nc;
+  sh.nz = (long long)(N + 1) * nu; sh.nv = (long long)(N + 1) * nc;
+  fbstab_dense_batch_t dc;
+  RC_TRY(condense_check_images(who, sh, batch, dense, &dc));
+  RC_TRY(condense_check_plant(who, plant, nx, nu, batch));
+  if (!log->x || !log->U || !log->v || !log->eflag) return condense_bad(who, "the x, U, v and eflag logs are required");
+  // the directions: a step below 0, or with batch > 1 a stride below the length that is not 0
+  if (dir->step_df0 < 0 || dir->step_db0 < 0) return condense_bad(who, "negative step in the directions");
+  if (batch > 1 && ((dir->dx0 && dir->stride_dx0 != 0 && dir->stride_dx0 < nx) ||
+                    (dir->df0 && dir->stride_df0 != 0 && dir->stride_df0 < sh.nz) ||
+                    (dir->db0 && dir->stride_db0 != 0 && dir->stride_db0 < sh.nv)))
+    return condense_bad(who, "trajectory stride of a direction is neither 0 nor at least the length");
+  // ... the map and the images, in front of the handle (with images M alone is looked at)
+  if (images) {
+    if (!map || !map->M) return condense_bad(who, "AFFINE mode needs the map");
+    if (batch > 1 && map->stride_M != 0 && map->stride_M < (sh.nz + sh.nv) * sh.nx)
+      return condense_bad(who, "stride of the map smaller than the array length");
+    RC_TRY(condense_check_ref_images(who, sh, batch, images));
+  } else {
+    RC_TRY(condense_check_map(who, true, map, sh, batch));
+  }
+  // ... then the handle
+  RC_TRY(condense_check_handle(who, h, sh, batch));
+  if (batch == 0) return FBSTAB_HIP_OK;
+  RC_TRY(condense_device_exists(who, h->device));
+  const bool shared_m = batch == 1 || map->stride_M == 0;
+  CondenseSweepLds L;
+  RC_TRY(condense_sweep_plan(N, nx, nu, nc, traj_per_group, shared_m, &L));
+  if (L.T > batch) L.init(N, nx, nu, nc, batch, shared_m);
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  const bool one = batch == 1;
+  CondenseSweepTanCarve wk(N, nx, nu, nc, work, batch);
+  CondenseSweepTanStep st = {};
+  st.N = N; st.nx = nx; st.nu = nu; st.nc = nc; st.batch = batch;
+  st.st1 = wk.st1; st.st2 = wk.st2; st.status = status;
+  st.dU = wk.wk.dU; st.dx = wk.dx;
+  st.dx0 = dir->dx0; st.sdx0 = one ? 0 : dir->stride_dx0;
+  st.Ap = plant->A; st.Bp = plant->B;
+  st.sAp = one ? 0 : plant->stride_A; st.sBp = one ? 0 : plant->stride_B;
+  st.M = map->M; st.sM = one ? 0 : map->stride_M;
+  if (images) {
+    st.sf0 = one ? 0 : images->stride_f0;
+    st.sb0 = one ? 0 : images->stride_b0;
+  } else {
+    st.f0 = map->f0; st.sf0 = one ? 0 : map->stride_f0;
+    st.b0 = map->b0; st.sb0 = one ? 0 : map->stride_b0;
+  }
+  st.f = const_cast<double*>(dc.base[FBSTAB_DENSE_f]); st.sf = dc.stride[FBSTAB_DENSE_f];
+  st.b = const_cast<double*>(dc.base[FBSTAB_DENSE_b]); st.sb = dc.stride[FBSTAB_DENSE_b];
+  st.sdf0 = one ? 0 : dir->stride_df0;
+  st.sdb0 = one ? 0 : dir->stride_db0;
+  st.gU = wk.wk.gU; st.gv = wk.wk.gv;
+  const int groups = (batch + L.T - 1) / L.T;
+  for (int k = -1; k < steps; k++) {  // the launch that closes step k and opens step k + 1
+    const long long kb = (long long)k * batch, kn = (long long)(k + 1) * batch;
+    st.close = k >= 0;
+    st.open = k + 1 < steps;
+    st.eflag_close = st.close ? log->eflag + kb : nullptr;
+    st.dw = st.close && dir->dw ? dir->dw + kb * nx : nullptr;
+    st.du_out = st.close && du ? du + kb * nu : nullptr;
+    st.dx_out = st.close && dx ? dx + kb * nx : nullptr;
+    st.eflag_open = st.open ? log->eflag + kn : nullptr;
+    st.x_log = st.open ? log->x + kn * nx : nullptr;
+    if (images && st.open) {
+      st.f0 = images->f0 + (k + 1) * images->step_f0;
+      st.b0 = images->b0 + (k + 1) * images->step_b0;
+    }
+    st.df0 = st.open && dir->df0 ? dir->df0 + (k + 1) * dir->step_df0 : nullptr;
+    st.db0 = st.open && dir->db0 ? dir->db0 + (k + 1) * dir->step_db0 : nullptr;
+    void* sargs[] = {&st, &L};
+    RC_TRY(launch(kCondenseSweepTanStep, groups, L.total * 8, sargs, s));
+    if (!st.open) break;
+    // the dense adjoint at the logged (U, v) of the opened step, read where they lie, refined once
+    fbstab_var_batch_t xc = {};
+    xc.base[0] = log->U + kn * sh.nz; xc.stride[0] = sh.nz;
+    xc.base[2] = log->v + kn * sh.nv; xc.stride[2] = sh.nv;
+    RC_TRY(condense_refined_step(launch, dense_adjoint, sh, batch, dc, xc, wk.wk.gv, sigma, wk.wk, wk.st1, wk.st2, s));
+  }
+  return FBSTAB_HIP_OK;
 }
 
 }  // namespace

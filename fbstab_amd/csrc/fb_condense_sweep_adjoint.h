@@ -26,10 +26,10 @@
 // As fb_condense.h: written against Ctx, one thread owns each output entry and sums it in ascending index order with
 // plain FMAs.  No atomics, no sums across threads, no matrix cores.
 //
-// Not here: the device-side reduced form for shared parameters, forward mode through the sweep, seeds on the rest of
-// U_k and v_k, reuse of the forward call's images and map, sharded sweeps, the C++ facade.  (Per-step references need
-// no code here: the host stage hands the step kernel the f0, b0 of the step it opens and the finish kernel the step's
-// sequences and, for a sequence that moves, the step's rows of its gradient - fb_condense_stage.h.)
+// Not here: the device-side reduced form for shared parameters, seeds on the rest of U_k and v_k, reuse of the forward
+// call's images and map, sharded sweeps, the C++ facade.  (Forward mode: fb_condense_sweep_tangent.h.  Per-step
+// references need no code here: the host stage hands the step kernel the f0, b0 of the step it opens and the finish
+// kernel the step's sequences and, for a sequence that moves, the step's rows of its gradient - fb_condense_stage.h.)
 #pragma once
 
 #include "fb_condense_adjoint.h"

@@ -573,14 +573,15 @@ __attribute__((visibility("hidden"))) const void* fbstab_kkt_multi_kernel(int wg
 // own): the kernel beside adjoint kernel `which` of dense_resolve_kernels
 __attribute__((visibility("hidden"))) const void* fbstab_dense_kkt_multi_kernel_for(int which);
 // The kernels of the condensed route (fb_condense.hip, fb_condense_adjoint.hip, fb_condense_multi.hip,
-// fb_condense_sweep.hip, fb_condense_sweep_adjoint.hip, fb_condense_tangent.hip, fb_condense_refs.hip, a translation
-// unit each): the kernel
+// fb_condense_sweep.hip, fb_condense_sweep_adjoint.hip, fb_condense_sweep_tangent.hip, fb_condense_tangent.hip,
+// fb_condense_refs.hip, a translation unit each): the kernel
 // that the unit's enum of fb_condense_plan.h names; *threads: its workgroup size
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseAdjointKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseMultiKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepAdjKernel which, int* threads);
+__attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseSweepTanKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseTangentKernel which, int* threads);
 __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::CondenseRefsKernel which, int* threads);
 #if defined(FB_SINGLE_TU)
@@ -597,6 +598,7 @@ __attribute__((visibility("hidden"))) const void* fbstab_condense_kernel(fbk::Co
 #include "fb_condense_multi.hip"
 #include "fb_condense_sweep.hip"
 #include "fb_condense_sweep_adjoint.hip"
+#include "fb_condense_sweep_tangent.hip"
 #include "fb_condense_tangent.hip"
 #include "fb_condense_refs.hip"
 #endif
@@ -1429,6 +1431,23 @@ int fbstab_hip_mpc_condensed_tracking_sweep_adjoint(
                                               sigma, grad, nullptr, nullptr, mu_log, status, mode, refs, images,
                                               ref_grad, traj_per_group, work, stream, condense_gpu,
                                               condense_dense_adjoint(h));
+}
+
+int fbstab_hip_mpc_condensed_sweep_tangent_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
+                                                 int* traj_per_group_used, long long* lds_bytes,
+                                                 long long* work_doubles_per_traj) {
+  return condensed_sweep_tangent_sizes(N, nx, nu, nc, traj_per_group, shared_map, traj_per_group_used, lds_bytes,
+                                       work_doubles_per_traj);
+}
+
+int fbstab_hip_mpc_condensed_receding_sweep_tangent(
+    fbstab_dense_handle_t h, int N, int nx, int nu, int nc, int batch, const fbstab_dense_batch_t* dense,
+    const fbstab_condensed_map_t* map, const fbstab_condensed_ref_images_t* images,
+    const fbstab_receding_plant_t* plant, int steps, const fbstab_condensed_sweep_log_t* log,
+    const fbstab_condensed_sweep_dir_t* dir, double sigma, double* du, double* dx, int* status, int traj_per_group,
+    double* work, void* stream) {
+  return condensed_sweep_tangent_run(h, N, nx, nu, nc, batch, dense, map, images, plant, steps, log, dir, sigma, du, dx,
+                                     status, traj_per_group, work, stream, condense_gpu, condense_dense_adjoint(h));
 }
 
 // Diagnostic builds (-DFB_STAMP): per-phase shader cycles summed over waves;

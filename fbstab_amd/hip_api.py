@@ -135,6 +135,13 @@ class _CondensedRefImages(C.Structure):
                 ("stride_f0", C.c_longlong), ("stride_b0", C.c_longlong)]
 
 
+class _CondensedSweepDir(C.Structure):
+    """fbstab_condensed_sweep_dir_t: the directions of x0, of the disturbances and of the images f0_k, b0_k."""
+    _fields_ = [("dx0", C.c_void_p), ("stride_dx0", C.c_longlong), ("dw", C.c_void_p), ("df0", C.c_void_p),
+                ("db0", C.c_void_p), ("step_df0", C.c_longlong), ("step_db0", C.c_longlong),
+                ("stride_df0", C.c_longlong), ("stride_db0", C.c_longlong)]
+
+
 class _SweepScenario(C.Structure):
     """fbstab_sweep_scenario_t: the disturbances (device pointer or NULL) and the shift flag."""
     _fields_ = [("w", C.c_void_p), ("shift", C.c_int)]
@@ -278,6 +285,11 @@ def load_library() -> C.CDLL:
         lib.fbstab_hip_mpc_condensed_tracking_sweep_adjoint.argtypes = [C.c_void_p] + [C.c_int] * 5 + [
             C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 3 + [
             C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "fbstab_hip_mpc_condensed_receding_sweep_tangent"):  # (absent from an earlier build loaded for an A/B)
+        lib.fbstab_hip_mpc_condensed_sweep_tangent_sizes.argtypes = [C.c_int] * 6 + [C.c_void_p] * 3
+        lib.fbstab_hip_mpc_condensed_receding_sweep_tangent.argtypes = [C.c_void_p] + [C.c_int] * 5 + [
+            C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 2 + [C.c_double] + [C.c_void_p] * 3 + [
+            C.c_int, C.c_void_p, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_refined_steps"):  # (absent from a round-4 build loaded for an A/B: FBSTAB_HIP_LIB)
         lib.fbstab_hip_mpc_refined_steps.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(lib, "fbstab_hip_mpc_queue_order"):  # (absent from an earlier build loaded for an A/B)
@@ -333,6 +345,7 @@ EXPORTED_SYMBOLS = (
     "fbstab_hip_mpc_condensed_sweep_adjoint_sizes", "fbstab_hip_mpc_condensed_receding_sweep_adjoint",
     "fbstab_hip_mpc_condensed_reference_sizes", "fbstab_hip_mpc_condensed_reference_images_batch",
     "fbstab_hip_mpc_condensed_tracking_sweep", "fbstab_hip_mpc_condensed_tracking_sweep_adjoint",
+    "fbstab_hip_mpc_condensed_sweep_tangent_sizes", "fbstab_hip_mpc_condensed_receding_sweep_tangent",
     "fbstab_hip_dense_kkt_solve_batch", "fbstab_hip_dense_jacobian_batch",
     "fbstab_hip_dense_create", "fbstab_hip_dense_destroy", "fbstab_hip_dense_set_options",
     "fbstab_hip_dense_get_options", "fbstab_hip_dense_solve_batch", "fbstab_hip_dense_solve_batch_final",

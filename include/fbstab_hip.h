@@ -698,8 +698,9 @@ int fbstab_hip_mpc_condensed_adjoint_batch(fbstab_dense_handle_t handle, int N, 
  * Then the device, then the LDS rule of fbstab_hip_mpc_condensed_sizes, then the direction kernel's own limits: its
  * stage layout (fb_tangent.h: MpcTangentLds) above 160 KB is FBSTAB_HIP_ERR_UNSUPPORTED, batch x (N + 1) above
  * INT_MAX is FBSTAB_HIP_ERR_ARGUMENT.
- * Not here: several directions per factorisation, forward mode through the closed-loop sweep, the device-side
- * reduced form, the C++ facade, sharded calls, certificates of infeasibility. */
+ * Not here: several directions per factorisation, the device-side reduced form, the C++ facade, sharded calls,
+ * certificates of infeasibility.  (Forward mode through the closed-loop sweep:
+ * fbstab_hip_mpc_condensed_receding_sweep_tangent.) */
 int fbstab_hip_mpc_condensed_tangent_batch(fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch,
                                            const fbstab_mpc_batch_t* data, const fbstab_dense_batch_t* dense,
                                            const fbstab_var_batch_t* x, const fbstab_mpc_batch_t* ddata, double sigma,
@@ -935,9 +936,10 @@ int fbstab_hip_mpc_condensed_receding_sweep(fbstab_dense_handle_t handle, int N,
  *   lds_bytes = that of fbstab_hip_mpc_condensed_sweep_sizes (the step kernel; shared_map as there)
  *   work_doubles_per_traj      = 4 nzc + 2 nv + 2 nx + 1     (gU, dU, rU, eU; dv, ev; mu, -dl0; two status words)
  *   work_doubles_per_traj_grad = that + 2 (N + 1)(nx + nu) + (N + 1) nx       (z and the zeros of gz; l)
- * Not here: the device-side reduced form for shared parameters, forward mode through the sweep, seeds on the rest of
- * U_k and v_k, reuse of the forward call's images and map, sharded calls, the C++ facade.  (Per-step references:
- * fbstab_hip_mpc_condensed_tracking_sweep_adjoint.) */
+ * Not here: the device-side reduced form for shared parameters, seeds on the rest of U_k and v_k, reuse of the forward
+ * call's images and map, sharded calls, the C++ facade.  (Per-step references:
+ * fbstab_hip_mpc_condensed_tracking_sweep_adjoint; forward mode through the sweep:
+ * fbstab_hip_mpc_condensed_receding_sweep_tangent.) */
 int fbstab_hip_mpc_condensed_sweep_adjoint_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
                                                  int* traj_per_group_used, long long* lds_bytes,
                                                  long long* work_doubles_per_traj,
@@ -1014,8 +1016,9 @@ int fbstab_hip_mpc_condensed_receding_sweep_adjoint(
  * moves, step k's rows of ref_grad.  x0, mu_log, status and the case rule are unchanged, and so is the device code:
  * only the pointers a launch is handed differ.  Validation: the existing adjoint's, in its order; the references, their
  * images and ref_grad in front of the handle checks.
- * Not here: references on the record-kernel sweep, per-step gf0 / gb0, the device-side reduced form, forward mode
- * through the sweep, sharded sweeps, the C++ facade. */
+ * Not here: references on the record-kernel sweep, per-step gf0 / gb0, the device-side reduced form, sharded sweeps,
+ * the C++ facade.  (Forward mode through a tracking sweep: fbstab_hip_mpc_condensed_receding_sweep_tangent with
+ * `images`.) */
 typedef struct fbstab_condensed_refs_t {       /* per-step q, r, c, d */
   const double* base[4];      /* q, r, c, d; NULL: the sequence of `data` at every step */
   long long step[4];          /* doubles between steps (>= 0; overlapping windows are allowed: read-only) */
@@ -1052,6 +1055,84 @@ int fbstab_hip_mpc_condensed_tracking_sweep_adjoint(
     int steps, int retire, const fbstab_condensed_sweep_log_t* log, const double* gu, const double* gx, double sigma,
     const fbstab_mpc_grad_batch_t* grad, double* mu_log, int* status, int mode, const fbstab_condensed_refs_t* refs,
     const fbstab_condensed_ref_images_t* images, const fbstab_condensed_ref_grad_t* ref_grad, int traj_per_group,
+    double* work, void* stream);
+
+/* ---- the condensed route in closed loop: forward mode through the sweep -------------------------------------------
+ * How does the whole closed-loop trajectory move along ONE direction of x0, the disturbances and the vectors of the
+ * condensed QP?  The forward-mode counterpart of fbstab_hip_mpc_condensed_receding_sweep_adjoint (and, with `images`,
+ * of fbstab_hip_mpc_condensed_tracking_sweep_adjoint), on the same logs.  AFFINE mode is the contract: step k solved
+ * (H_c, f_c = f0_k + F x_k, A_c, b_c = b0_k + G x_k), u_k = U_k[0:nu], x_(k+1) = A_p x_k + B_p u_k (+ w_k).
+ * fbstab_condensed_sweep_dir_t, the directions:
+ *   dx0:    [batch][nx] at dx0 + b stride_dx0 (stride 0: one for the batch); NULL: zero.
+ *   dw:     [steps][batch][nx], packed; NULL: zero.
+ *   df0, db0: the directions of f0_k, b0_k in the layout of fbstab_condensed_ref_images_t: step k, trajectory b at
+ *           df0 + k step_df0 + b stride_df0.  A step of 0: one direction for all steps; a stride of 0: shared by the
+ *           batch; NULL: zero.
+ * Start with dx = dx0 and for k = 0 .. steps-1:
+ *   eflag_log[k] == -1 (retired):       du_k = 0, dx <- 0             (the parked state is the constant 0; dw_k is not
+ *                                                                      added)
+ *   eflag_log[k] != FBSTAB_SUCCESS:     du_k = 0, dx <- A_p dx + dw_k (u_k is a constant, as in the adjoint's case rule)
+ *   otherwise df_c = df0_k + F dx, db_c = db0_k + G dx and one dense adjoint (fbstab_hip_dense_adjoint_batch's, same
+ *   sigma rule) of the condensed QP at the logged (U_k, v_k) with the seeds gU = -df_c, gv_c = db_c - the seeds
+ *   fbstab_hip_dense_tangent_batch forms for (df, db) - refined once exactly as fbstab_hip_mpc_condensed_adjoint_batch
+ *   refines it (residual kernel, the dense adjoint again, correction kernel):
+ *     a factorisation failed in either launch:   status += 1, du_k = 0, dx <- A_p dx + dw_k
+ *     else                                       du_k = dU[0:nu], dx <- A_p dx + B_p du_k + dw_k
+ *   du[k] = du_k, dx[k] = dx (= dx_(k+1)).
+ * This is the transpose of the adjoint's recursion, case for case: with that call's seeds and results on the same log
+ *   sum_k <gu_k, du_k> + <gx_k, dx_(k+1)> = <lambda_0, dx0> + sum_k <mu_k, dw_k> [k not retired] + <gf0, df0> + <gb0, db0>
+ * (df0, db0 one direction for all steps; with per-step directions the last two terms are sums over the steps of the
+ * per-step gradients).  Directions of the plant are the caller's: they enter as dw_k += dA_p x_k + dB_p u_k.  Directions
+ * of q, r, c, d - of `data` or of per-step references - reach df0_k, db0_k through
+ * fbstab_hip_mpc_condensed_reference_images_batch on the direction sequences (the images are linear in those four
+ * sequences; every slot must be given there, zeros where nothing moves: a NULL slot means `data`'s sequence).
+ * fbstab_mpc_condensed_sweep_tangent_step_kernel (T trajectories per workgroup in the LDS layout of the forward step
+ * kernel; a shared M is staged once per workgroup) is launched steps + 1 times: one launch CLOSES step k - the case
+ * rule, du_k, and dx+ in the summation order of the forward kernel's plant step - and OPENS step k + 1: f_c, b_c of that
+ * step from x_log[k + 1] with the forward kernel's loop and summation order (the dense handle needs b_c at the point),
+ * and the seeds from dx+; both products with M are formed in one pass over a row of M, one thread per (row,
+ * trajectory), j ascending.  Between two launches: the dense adjoint, fbstab_mpc_condensed_adjoint_residual_kernel,
+ * the dense adjoint again, fbstab_mpc_condensed_adjoint_correct_kernel.  No atomics: the same inputs give the same
+ * bits, and a trajectory's bits depend on its own inputs and the shape alone.
+ *   handle, dense, map, plant: as fbstab_hip_mpc_condensed_receding_sweep_adjoint takes them.  dense's H_c and A_c are
+ *           read; f_c and b_c (stride >= length with batch > 1) are per-trajectory scratch that the call overwrites.
+ *           The map is always needed: a sweep that ran in RECONDENSE mode is differentiated through the map of
+ *           fbstab_hip_mpc_condensed_x0_map_batch.
+ *   images: NULL: map->f0, map->b0 at every step.  Otherwise the forward's f0_k, b0_k (they are READ; map->f0 and
+ *           map->b0 are then not looked at).
+ *   log:    the forward's; x, U, v and eflag are required.  U and v are read where they lie, no copy is made.
+ *   du, dx: [steps][batch][nu], [steps][batch][nx], packed; one of them may be NULL.  Every entry is written.
+ *   status: [batch], the number of steps whose factorisation failed.
+ *   traj_per_group: T of the step kernel, as in the forward call: it changes speed, never a bit.
+ *   work:   caller-provided DEVICE memory, batch x work_doubles_per_traj doubles, packed arrays of the batch.  Nothing
+ *           is allocated.
+ * EVERY pointer is a DEVICE pointer.  Asynchronous: everything is queued on `stream` (NULL: the handle's stream) and the
+ * call returns.  Every argument error is FBSTAB_HIP_ERR_ARGUMENT and checked before any device call, what needs no
+ * handle first, in the order of fbstab_hip_mpc_condensed_receding_sweep_adjoint: the sizes, the batch; NULL dense,
+ * plant, log, dir, status, work; du and dx both NULL; a NULL plant matrix; steps < 0; traj_per_group < 0; the condensed
+ * images; the plant; the required log slots; the directions (a negative step; with batch > 1 a stride below the length
+ * that is not 0); the map; the images - then the handle.  batch == 0 returns OK and queues nothing; steps == 0 writes
+ * status = 0 and nothing else.
+ * fbstab_hip_mpc_condensed_sweep_tangent_sizes: with nzc = (N + 1) nu, nv = (N + 1) nc,
+ *   lds_bytes = that of fbstab_hip_mpc_condensed_sweep_sizes (the step kernel; shared_map as there)
+ *   work_doubles_per_traj = 4 nzc + 3 nv + nx + 1      (gU, dU, rU, eU; gv_c, dv, ev; dx; two status words)
+ * Not here: directions on the matrix sequences, several directions per factorisation, RECONDENSE mode, the reduced
+ * form, sharded sweeps, the C++ facade, the record-kernel sweep. */
+typedef struct fbstab_condensed_sweep_dir_t {
+  const double* dx0;
+  long long stride_dx0;
+  const double* dw;
+  const double *df0, *db0;
+  long long step_df0, step_db0, stride_df0, stride_db0;
+} fbstab_condensed_sweep_dir_t;
+int fbstab_hip_mpc_condensed_sweep_tangent_sizes(int N, int nx, int nu, int nc, int traj_per_group, int shared_map,
+                                                 int* traj_per_group_used, long long* lds_bytes,
+                                                 long long* work_doubles_per_traj);
+int fbstab_hip_mpc_condensed_receding_sweep_tangent(
+    fbstab_dense_handle_t handle, int N, int nx, int nu, int nc, int batch, const fbstab_dense_batch_t* dense,
+    const fbstab_condensed_map_t* map, const fbstab_condensed_ref_images_t* images,
+    const fbstab_receding_plant_t* plant, int steps, const fbstab_condensed_sweep_log_t* log,
+    const fbstab_condensed_sweep_dir_t* dir, double sigma, double* du, double* dx, int* status, int traj_per_group,
     double* work, void* stream);
 
 /* Diagnostic builds only (-DFB_STAMP): in-kernel per-phase cycle counters. */
