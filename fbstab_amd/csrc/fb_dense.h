@@ -6,8 +6,9 @@
 //   * DenseData products and axpys            dense_data.cc:12-41
 //   * DenseCholeskySolver::Initialize/Solve   dense_cholesky_solver.cc:32-127
 //     (E = H + sigma I + A'Gamma A, K = [E .; G -sigma I], pivoted LDL' with
-//     symmetric pivoting on the largest |diagonal| as Eigen::LDLT does,
-//     pseudo-inverse of D in the solve)
+//     symmetric pivoting on the largest |diagonal| - of the UPDATED trailing matrix,
+//     where Eigen::LDLT searches the diagonal as assembled: see ldlt_rows and
+//     ldlt_impl -, pseudo-inverse of D in the solve)
 //   * FullFeasibility::CheckFeasibility       full_feasibility.cc:25-88
 //
 // K and every iterate vector live in LDS for the whole solve; H, G, A are read
@@ -15,8 +16,11 @@
 // beside the vectors (nz + nl > ~140) the KGLOBAL instance keeps K in a
 // per-workgroup global scratch instead (L2-resident at these sizes), the vectors
 // stay in LDS, and the generic multi-wavefront factorisation runs unchanged.  The LDL' here is right-looking (rank-1
-// trailing updates spread over the workgroup) where Eigen's is left-looking;
-// pivot order is the same rule, summation order differs (rounding only).
+// trailing updates spread over the workgroup) where Eigen's is left-looking: summation order differs
+// (rounding), and so does the pivot order, because a right-looking search sees the updated diagonal
+// (ldlt_rows, ldlt_impl).  Which assembly, factorisation, substitution and placement a shape takes:
+// DESIGN 4.2 (tests/test_dense_rules_cpu.py derives that table from DenseLayout::init as compiled, and
+// tests/test_gpu_dense_stages.py runs every stage on every path of it).
 #pragma once
 
 #include <float.h>
@@ -306,11 +310,18 @@ struct DenseProblem {
   }
 
   // Pivoted LDL' for n <= 64 on ONE wavefront with the matrix in registers: lane t
-  // holds row t of the (full, symmetric) trailing matrix, Kr[j] = K[t][j].  Same
-  // pivot rule as Eigen::LDLT (largest |diagonal| of what is left, the first maximum
-  // wins), but nothing is swapped: eliminated rows and columns simply drop out of
-  // the pivot search, and the elimination order is kept as a list (perm[k] = row
-  // eliminated at step k).  A step is: the pivot row goes to LDS once (so that every
+  // holds row t of the (full, symmetric) trailing matrix, Kr[j] = K[t][j].  The
+  // pivot is the largest |diagonal| of what is left, and nothing is swapped:
+  // eliminated rows and columns simply drop out of the pivot search, and the
+  // elimination order is kept as a list (perm[k] = row eliminated at step k).
+  // NOT Eigen::LDLT's rule, in the three ways DenseWave::factor (fb_dense_wave.h) is
+  // not - this is the same code shape: the search runs on the UPDATED diagonal (Eigen,
+  // left-looking, searches the diagonal as assembled and only takes the updated
+  // entry as the pivot); a tie goes to the lowest ROW INDEX (Eigen: the first position
+  // after its swaps); and the column under an invalid (zero) pivot is not examined
+  // (Eigen fails if it is not zero) - a zero pivot only fails the factorisation when a
+  // valid one follows it.  tests/test_gpu_dense_stages.py asserts exactly this order and
+  // these verdicts (tests/dense_wave_rules.DEVICE_AS_DOCUMENTED).  A step is: the pivot row goes to LDS once (so that every
   // lane can fetch "its" entry of it, the multiplier column), then every lane updates
   // its whole row with the pivot row broadcast through v_readlane into scalar
   // registers - no barrier, no LDS round trip per column.  The multipliers of step k
@@ -453,6 +464,10 @@ struct DenseProblem {
   // touch different entries), the search itself is DPP + v_readlane in the first
   // wavefront, and barriers that only separated reads are gone: two per pivot
   // (three with a swap) instead of five.
+  // NOT REACHED by any shape today: `ldlt` comes here only with K in LDS, lay.wave == 0 and
+  // nk <= 64, and DenseLayout::init clears `wave` for nk <= 64 only on its way to k_global
+  // (tests/test_dense_rules_cpu.py asserts both over a grid of shapes).  It was the n <= 64
+  // path before ldlt_rows; no test runs it.  Pivot rule as ldlt_impl.
   FB_DEV bool ldlt_fused(const C& c) const {
     const int n = lay.nk;
     bool found_zero_pivot = false;
@@ -582,7 +597,13 @@ struct DenseProblem {
     c.sync();
   }
 
-  // Pivoted LDL' of the lower triangle of K in place (Eigen::LDLT semantics).
+  // Pivoted LDL' of the lower triangle of K in place, with Eigen::LDLT's storage (L below the diagonal in its
+  // swapped position, D on it, perm[k] = the position swapped with k: a sequence of transpositions; nothing above
+  // the diagonal is read or written) and verdict on a valid pivot behind an invalid one.  The pivot RULE is not
+  // Eigen's: the update is in place, so the search sees the UPDATED diagonal (Eigen's left-looking search sees the
+  // diagonal as assembled); a tie goes to the first CURRENT position, as in Eigen; and the column under an invalid
+  // pivot is not examined.  On a tied diagonal the order is Eigen's for some matrices and not for others
+  // (tests/test_gpu_dense_stages.py prints which).
   template <class W>
   FB_DEV bool ldlt_impl(const W& c) const {
     const int n = lay.nk;

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY: the single-threaded host compilations of the device logic (hostsim.cc, adjoint.cc,
-dense_adjoint.cc, tangent.cc, against the <hip/hip_runtime.h> of shim/) and their ctypes wrappers.  Beside them,
+dense_adjoint.cc, tangent.cc, dense_stage.cc, against the <hip/hip_runtime.h> of shim/) and their ctypes wrappers.  Beside them,
 with no wrapper here: runtime_shim/ (a heap-backed <hip/hip_runtime.h>: the runtime calls, not the device environment)
 and stage_driver.cc, the stand-alone program over fbstab_amd/csrc/fb_host_stage.h that tests/test_host_stage.py
 builds and runs."""
@@ -169,3 +169,64 @@ class HostTangent:
                                                          gl.ctypes.data, gv.ctypes.data)
             assert self.cb >= 1, "not one column fits the budget"
         return gz[:p.nz], gl[:p.nl], gv[:p.nv]
+
+
+class HostDenseStage:
+    """The stages of fb_dense.h on one host thread (dense_stage.cc): DenseLayout::init as compiled, and ldlt with
+    ldlt_solve, newton_step and dense_adjoint of DenseProblem<Ctx<1>>, with the outputs of tests/dense_probe.py."""
+    STEP_OUT = (("y", "nv"), ("rz", "nz"), ("rl", "nl"), ("dz", "nz"), ("dl", "nl"), ("dv", "nv"), ("adz", "nv"),
+                ("wz", "nz"), ("wl", "nl"), ("gam", "nv"), ("rvm", "nv"), ("yb", "nv"))
+
+    def __init__(self):
+        self.lib = C.CDLL(build("libhostsim_dense_stage.so", "dense_stage.cc",
+                                ("fb_common.h", "fb_adjoint.h", "fb_mpc.h", "fb_dense.h")))
+        self.lib.hostsim_dense_path.restype = C.c_long
+        self.lib.hostsim_dense_path.argtypes = [C.c_int] * 4 + [C.c_void_p]
+        self.lib.hostsim_dense_stage_factor.argtypes = [C.c_int] * 2 + [C.c_void_p] * 5
+        self.lib.hostsim_dense_stage_step.argtypes = ([C.c_int] * 3 + [C.c_void_p] * 8 + [C.c_double] * 2 + [C.c_int]
+                                                      + [C.c_void_p] * 3)
+
+    def layout(self, nz, nl, nv, nthreads):
+        out = (C.c_int * 7)()
+        scratch = self.lib.hostsim_dense_path(nz, nl, nv, nthreads, out)
+        names = ("wave", "k_global", "v_global", "a_lds", "lds_doubles", "lda", "nk")
+        return dict(zip(names, list(out)), scratch=scratch)
+
+    def factor(self, img, rhs, nv=4):
+        """As DenseProbe.factor (the K region, perm, x; no dpiv / ord: one thread takes ldlt_impl)."""
+        count, n = img.shape[0], img.shape[1]
+        out = dict(verdict=np.zeros(count, dtype=np.int32), perm=np.full((count, n), -1, dtype=np.int32),
+                   flat=np.full((count, n * n), np.nan), x=np.full((count, n), np.nan))
+        for q in range(count):
+            cols = np.ascontiguousarray(np.asarray(img[q], dtype=np.float64).T)
+            b = np.ascontiguousarray(rhs[q], dtype=np.float64)
+            out["verdict"][q] = self.lib.hostsim_dense_stage_factor(n, nv, cols.ctypes.data, b.ctypes.data,
+                                                                    out["perm"][q].ctypes.data,
+                                                                    out["flat"][q].ctypes.data, out["x"][q].ctypes.data)
+        out["K"] = out["flat"].reshape(count, n, n).transpose(0, 2, 1)
+        return out
+
+    def step(self, d, xb, sigma, alpha=0.95, adjoint=False, h_step=None):
+        """As DenseProbe.step, for a batch of tests/dense_wave_rules.problem's kind."""
+        count, nz, nl, nv = d["H"].shape[0], d["H"].shape[1], d["G"].shape[1], d["A"].shape[1]
+        n = nz + nl
+        size = dict(nz=nz, nl=nl, nv=nv)
+        out = dict(verdict=np.zeros(count, dtype=np.int32), perm=np.full((count, n), -1, dtype=np.int32),
+                   flat=np.full((count, n * n), np.nan))
+        for name, m in self.STEP_OUT:
+            out[name] = np.full((count, max(1, size[m])), np.nan)
+        cm = lambda M: _pad(np.ascontiguousarray(np.asarray(M, dtype=np.float64).T))
+        vec = lambda a: _pad(np.ascontiguousarray(a, dtype=np.float64))
+        for q in range(count):
+            keep = [cm(d["H"][q]), vec(d["f"][q]), cm(d["G"][q]), vec(d["h"][q]), cm(d["A"][q]), vec(d["b"][q])]
+            data = (C.c_void_p * 6)(*[a.ctypes.data for a in keep])
+            pt = [vec(d[k][q]) for k in ("z", "l", "v")] + [cm((d["H"] if h_step is None else h_step)[q])]
+            pt += [vec(t[q]) for t in xb]
+            outs = (C.c_void_p * 12)(*[out[name][q].ctypes.data for name, _ in self.STEP_OUT])
+            out["verdict"][q] = self.lib.hostsim_dense_stage_step(
+                nz, nl, nv, data, *[a.ctypes.data for a in pt], sigma, alpha, int(adjoint),
+                out["perm"][q].ctypes.data, out["flat"][q].ctypes.data, outs)
+        for name, m in self.STEP_OUT:
+            out[name] = out[name][:, :size[m]]
+        out["K"] = out["flat"].reshape(count, n, n).transpose(0, 2, 1)
+        return out

@@ -547,6 +547,8 @@ _DENSE_SHAPES = [
     ((1, 0, 1), 64), ((7, 3, 40), 64), ((50, 10, 100), 64), ((33, 0, 9), 64), ((60, 4, 131), 64), ((20, 5, 40), 64),
     ((64, 1, 30), 256), ((90, 12, 77), 256), ((120, 20, 60), 256), ((70, 0, 200), 256),
     ((150, 10, 90), 256), ((159, 24, 239), 256),
+    # nz <= 64 < nz + nl with nv a multiple of 4: the MFMA assembly of fb_dense.h by default dispatch
+    ((40, 30, 8), 256), ((33, 32, 64), 256),
 ]
 
 
